@@ -835,6 +835,21 @@ def headline_record(rec: dict) -> dict:
     return out
 
 
+TALLY_WIDE = ("power", "quorum")                                         # 128-bit: four 32-bit limbs each, low limb first
+TALLY_COUNTS = ("valid_rows", "distinct_senders", "has_quorum", "proposer_rows")
+
+
+def dump_outputs(out_dir: str, verdict, tally) -> None:
+    """--dump-outputs: what a caller of the timed path received from its last step, as float arrays that two builds can be
+    compared on — verdict.npy (float32, 1.0 = valid seal, one per row; the merged mask at N > 1) and tally.npy (float64:
+    TALLY_WIDE as 32-bit limbs, which float64 holds exactly, then TALLY_COUNTS)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "verdict.npy"), np.asarray(verdict, dtype=bool).astype(np.float32))
+    words = [(int(getattr(tally, f)) >> (32 * k)) & 0xFFFFFFFF for f in TALLY_WIDE for k in range(4)]
+    words += [int(getattr(tally, f)) for f in TALLY_COUNTS]
+    np.save(os.path.join(out_dir, "tally.npy"), np.asarray(words, dtype=np.float64))
+
+
 def emit(rec: dict) -> str:
     """detail record → gpurun_out/bench_detail.json + one stdout line; then the headline line, LAST on stdout"""
     try:
@@ -882,6 +897,8 @@ def main():
     ap.add_argument("--no-host-mirror", action="store_true", help="skip the end-to-end legs through include/ibft_host.h")
     ap.add_argument("--extended-steps", type=int, default=400,
                     help="a second, longer sample of the headline leg (reported next to the K-step one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (verdict mask, tally) as DIR/<name>.npy")
     ap.add_argument("--path", choices=["cold", "warm"], default="cold",
                     help="cold = ECDSA recover+compare for every row (headline); warm = keys already learned, "
                          "rows verified against per-validator tables (IBFT_FLAG_PUBKEY_CACHE)")
@@ -1111,7 +1128,7 @@ def main():
                "kernel_ms": kernel_ms, "kernel_launches": kernel_launches,
                "kname": kernel_name(path, cold_lanes, warm_lanes, bv.last_cold_table()),
                "src": rd["src"], "rd": rd, "tables": bv.cache_stats()[0] if path == "warm" else 0, "input_generation_s": t_gen,
-               "valid_fraction": float(verdict.mean())}
+               "valid_fraction": float(verdict.mean()), "out": (verdict, tally)}
         if dist:
             bv.comm_destroy()
         if keep is not None and "bv" not in keep:
@@ -1127,6 +1144,8 @@ def main():
     carry = {} if (world == 1 and args.extended_steps > 0) else None
     long_leg = run_config(args.rows, False, args.extended_steps, 10, args.path, keep=carry) if carry is not None else None
     main_leg = run_config(args.rows, False, args.steps, args.warmup, args.path, keep=carry)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *main_leg["out"])
 
     rec = None
     if rank == 0:

@@ -85,6 +85,25 @@ def test_dry_run_one_rank_prints_detail_then_headline():
     assert os.path.exists(os.path.join(ROOT, "gpurun_out", "bench_detail.json"))
 
 
+def test_dry_run_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
+    """--dump-outputs DIR: the last timed step's verdict mask and tally as float .npy files; the same arguments give the same
+    files, and --steps is the number of timed steps the line reports"""
+    import numpy as np
+    got = []
+    for k, steps in enumerate((3, 7)):
+        d = tmp_path / f"run{k}"
+        lines = _run_bench(["--steps", str(steps), "--warmup", "1", "--extended-steps", "0", "--dump-outputs", str(d)], {})
+        rec = _check_headline(lines[-1], 1)
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["tally.npy", "verdict.npy"]
+        v, t = np.load(d / "verdict.npy"), np.load(d / "tally.npy")
+        assert v.dtype == np.float32 and v.shape == (4096,) and set(np.unique(v)) <= {0.0, 1.0}
+        assert t.dtype == np.float64 and t.shape == (12,)
+        assert t[8] == v.sum() and t[10] == 1.0                                  # valid_rows, has_quorum
+        got.append((v, t))
+    assert (got[0][0] == got[1][0]).all() and (got[0][1] == got[1][1]).all()
+
+
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_dry_run_gpus_n_relaunches_shards_exchanges_and_merges(world):
     """`python bench.py --gpus N` from a bare shell → N ranks under torch.distributed.run; every rank verifies its 64-aligned

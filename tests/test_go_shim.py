@@ -8,6 +8,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "tools", "check_go_shim.py")
+# the checks against go-ibft's own packages run when GO_IBFT_SRC names a checkout of it (the tools read the same variable)
+HAVE_REF = bool(os.environ.get("GO_IBFT_SRC")) and os.path.isdir(os.environ["GO_IBFT_SRC"])
 
 
 def test_shim_is_self_consistent():
@@ -28,7 +30,7 @@ def test_checker_catches_the_round1_defects(tmp_path):
     out = subprocess.run([sys.executable, TOOL, str(dst)], capture_output=True, text=True)
     assert out.returncode == 1
     assert "import path" in out.stdout and "ibft_seals_runn" in out.stdout
-    if os.path.isdir("/root/reference"):          # methods of core.IBFT are looked up in the reference too
+    if HAVE_REF:          # methods of core.IBFT are looked up in the reference too
         assert "addVerifiedMessage" in out.stdout
 
 
@@ -129,7 +131,7 @@ def test_go_calls_fit_their_definitions():
     out = subprocess.run([sys.executable, ARITY_TOOL], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     judged = int(__import__("re").search(r"(\d+) calls judged", out.stdout).group(1))
-    assert judged >= (200 if os.path.isdir("/root/reference") else 60), out.stdout
+    assert judged >= (200 if HAVE_REF else 60), out.stdout
 
 
 def test_go_arity_check_catches_seeded_defects(tmp_path):
@@ -157,11 +159,11 @@ def test_go_arity_check_catches_seeded_defects(tmp_path):
     out = subprocess.run([sys.executable, ARITY_TOOL, str(dst)], capture_output=True, text=True)
     assert out.returncode == 1, out.stdout
     assert "*hoststore.Store.HandleCommit has the signature" in out.stdout and "core.hostStore wants" in out.stdout
-    if os.path.isdir("/root/reference"):
+    if HAVE_REF:
         assert "*hoststore.Store.PruneByHeight has the signature (uint32) ()" in out.stdout       # core.Messages is the reference's
     assert "hs.AddWireMessages argument 1: raw is []byte, the parameter is [][]byte" in out.stdout
     assert "1 names receive the 2 results of hs.HandlePrepare" in out.stdout
     assert "wv.VerifySendersWire called with 1 arguments, the definition takes 2" in out.stdout
     assert "ibftgpu.Bit called with 1 arguments, the definition takes 2" in out.stdout
-    if os.path.isdir("/root/reference"):
+    if HAVE_REF:
         assert "i.addWireStockRenamed is not defined on core.IBFT" in out.stdout

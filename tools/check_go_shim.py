@@ -2,7 +2,7 @@
 """CI-less sanity check of shim/go (no Go toolchain in this image): every identifier the shim uses must be
 DEFINED somewhere a Go compiler would find it —
 
-  i.<method>(            method or field of core.IBFT: shim/go/core or /root/reference/core
+  i.<method>(            method or field of core.IBFT: shim/go/core or $GO_IBFT_SRC/core
   i.state.<m>( / i.messages.<m>( / i.backend.<m>(   the reference's state / Messages interface / Backend
   ibftgpu.<Symbol>       exported by shim/go/ibftgpu
   messages.<Func>, proto.<Type>                     shim/go/messages or the reference packages
@@ -13,14 +13,15 @@ DEFINED somewhere a Go compiler would find it —
   import paths           the overlay layout documented in shim/go/ibftgpu/ibftgpu.go
   compile errors         an import nothing uses, a local variable declared and never read
 
-Exit code 0 = consistent.  The reference checks are skipped (with a note) when /root/reference is absent."""
+Exit code 0 = consistent.  The reference checks need a go-ibft checkout named by $GO_IBFT_SRC; without
+one they are skipped (with a note)."""
 import glob
 import os
 import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+REF = os.environ.get("GO_IBFT_SRC", "")   # a checkout of github.com/0xPolygon/go-ibft (optional): the reference checks
 
 
 def read(paths):
@@ -119,7 +120,7 @@ def main(shim_root: str | None = None) -> int:
         return "\n".join(l.split("//")[0] for l in text.splitlines())
     shim = {p: code(open(p).read()) for p in glob.glob(os.path.join(shim_root, "**", "*.go"), recursive=True)}
     all_shim = "\n".join(shim.values())
-    have_ref = os.path.isdir(REF)
+    have_ref = bool(REF) and os.path.isdir(REF)
     ref_core = read(glob.glob(os.path.join(REF, "core", "*.go"))) if have_ref else ""
     ref_msgs = read(glob.glob(os.path.join(REF, "messages", "*.go"))) if have_ref else ""
     ref_proto = read(glob.glob(os.path.join(REF, "messages", "proto", "*.go"))) if have_ref else ""
@@ -252,7 +253,7 @@ def main(shim_root: str | None = None) -> int:
                 if len(re.findall(r"(?<![\w\.])%s\b" % re.escape(n), b)) < 2:
                     errors.append(f"{rel}: {fname}: {n} declared and not used")
     if not have_ref:
-        print("note: /root/reference absent — only the intra-repo checks ran")
+        print("note: no go-ibft checkout (GO_IBFT_SRC) — only the intra-repo checks ran")
     for e in errors:
         print("ERROR:", e)
     print(f"shim/go: {len(shim)} files, {len(errors)} problems")

@@ -5,7 +5,7 @@ tools/check_go_shim.py proves that every identifier exists and tools/cgo_typeche
 left for "the Go side has never met a compiler" is the typing between the Go packages of the overlay and the reference.  This
 tool resolves what it can without implementing Go's type system:
 
-  packages     shim/go/<pkg>/*.go overlaid on /root/reference/<pkg>/*.go (core, messages, messages/proto → proto), plus
+  packages     shim/go/<pkg>/*.go overlaid on $GO_IBFT_SRC/<pkg>/*.go (core, messages, messages/proto → proto), plus
                shim/go/ibftgpu and shim/go/hoststore
   definitions  every func, every method by receiver type, every interface's methods (embedded interfaces followed), every
                struct's fields with their types
@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cgo_typecheck as T  # noqa: E402  (lexical helpers: matching, split_top, strip_go_comments, go_functions, parse_go_params)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+REF = os.environ.get("GO_IBFT_SRC", "")   # a checkout of github.com/0xPolygon/go-ibft (optional): the reference checks
 IMPORT_TO_PKG = {"github.com/0xPolygon/go-ibft/messages/proto": "proto", "github.com/0xPolygon/go-ibft/messages": "messages",
                  "github.com/0xPolygon/go-ibft/ibftgpu": "ibftgpu", "github.com/0xPolygon/go-ibft/core": "core",
                  "github.com/0xPolygon/go-ibft/hoststore": "hoststore"}
@@ -176,7 +176,7 @@ class World:
                 code = T.strip_go_comments(open(p).read())
                 self.pkg(pkg).add_source(code)
                 self.files.append((p, pkg, code))
-        self.have_ref = os.path.isdir(REF)
+        self.have_ref = bool(REF) and os.path.isdir(REF)
         if self.have_ref:
             for d, pkg in (("core", "core"), ("messages", "messages"), ("messages/proto", "proto")):
                 for p in sorted(glob.glob(os.path.join(REF, d, "*.go"))):
@@ -456,8 +456,8 @@ def main(argv: list[str]) -> int:
     errors, judged, unresolved = check(shim_root, verbose)
     ierrors, compared = check_implements(shim_root)
     errors += ierrors
-    if not os.path.isdir(REF):
-        print("note: /root/reference absent — calls into the reference's own types are not judged")
+    if not (REF and os.path.isdir(REF)):
+        print("note: no go-ibft checkout (GO_IBFT_SRC) — calls into the reference's own types are not judged")
     for e in errors:
         print("ERROR:", e)
     print("go arity: %d calls judged against their definitions (%d arguments of builtin-shaped types compared with their parameters), "
