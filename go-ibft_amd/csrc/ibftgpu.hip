@@ -147,6 +147,11 @@ struct ibft_ctx {
   uint32_t power_words = 1;                          // 64-bit words per voting power: 1 (u64) or 4 (256-bit)
   uint64_t quorum_w[ibftk::TALLY_SUM_WORDS] = {0};   // ⌊2·total/3⌋+1, little-endian words
   DevBuf d_seen, d_acc, d_quorum;                    // tally: distinct-sender bitmap, launch-wide sums + ticket, quorum words
+  // chain sync (ibft_verify_block_seals): the blocks' hashes and row offsets, and one 4-word record per block, delivered into
+  // mapped pinned host memory when the device can write it (h_btally / dh_btally, grown on demand) or through d_btally
+  DevBuf d_bhash, d_boff, d_btally;
+  uint64_t *h_btally = nullptr, *dh_btally = nullptr;
+  size_t h_btally_blocks = 0;
   uint64_t last_wide[ibftk::TALLY_SUM_WORDS] = {0};  // full-width power of the last fetched tally
   uint64_t height = 0;
   // the seal-digest convention of the embedding Backend (ibft_set_seal_digest): 0 = the proposalHash itself
@@ -770,6 +775,19 @@ int apply_seal_digest(ibft_ctx *c, uint32_t row0, uint32_t n, bool keep_copy) {
     if (rc) return rc;
     a.copy32 = (uint8_t *)c->d_hash_copy.p;
   }
+  a.n = n;
+  memcpy(a.suffix_words, c->seal_suffix_words, sizeof a.suffix_words);
+  hipLaunchKernelGGL(ibftk::seal_digest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return IBFT_OK;
+}
+
+// the same convention over the n hashes of another column: ibft_verify_block_seals converts the blocks' hashes before they are
+// spread over their rows — one Keccak per block instead of one per row
+int seal_digest_column(ibft_ctx *c, uint8_t *col, uint32_t n) {
+  if (c->seal_digest_mode == 0 || n == 0) return IBFT_OK;
+  ibftk::seal_digest_args a{};
+  a.hash32 = col;
   a.n = n;
   memcpy(a.suffix_words, c->seal_suffix_words, sizeof a.suffix_words);
   hipLaunchKernelGGL(ibftk::seal_digest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
@@ -1484,7 +1502,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_xbuf[0], &c->d_xbuf[1], &c->d_xres[0], &c->d_xres[1], &c->d_set, &c->d_noseal, &c->d_class,
                     &c->d_cert_nodes, &c->d_cert_span, &c->d_cert_count, &c->d_cert_prop, &c->d_cert_masks, &c->d_cert_total,
                     &c->d_cert_slot, &c->d_cert_tiles, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
-                    &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b})
+                    &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally})
     release(*b);
   if (c->tstream) {
     (void)hipStreamSynchronize(c->tstream);
@@ -1522,6 +1540,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
     if (c->ev_pass[i]) (void)hipEventDestroy(c->ev_pass[i]);
   }
   if (c->h_mask) (void)hipHostFree(c->h_mask);
+  if (c->h_btally) (void)hipHostFree(c->h_btally);
   if (c->h_tally) (void)hipHostFree(c->h_tally);
   if (c->h_digest) (void)hipHostFree(c->h_digest);
   if (c->h_set) (void)hipHostFree(c->h_set);
@@ -2507,6 +2526,130 @@ int ibft_verify_seals(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65, 
   if ((rc = seals_stage_locked(c, hash32, sig65, signer20, pre_flags, n, false))) return rc;
   if ((rc = seals_launch_locked(c, 1))) return rc;
   return fetch_results(c, c->staged_n, out_mask, tally, true);
+}
+
+// Chain sync: the committed seals of n_blocks finalized blocks — one upload, one verdict launch over every row (the AUTO rule
+// sees the TOTAL row count), one segmented tally (block_tally_kernel), one synchronisation.
+int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, uint64_t *out_mask,
+                            ibft_tally_t *out_tally) {
+  if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
+  if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;  // (max_rows never changes after ibft_ctx_create)
+  uint32_t widest = 0;  // rows of the largest block: picks the tally's workgroup size
+  for (size_t b = 0; b < n_blocks; b++) {
+    if (seal_off[b + 1] < seal_off[b]) return IBFT_E_INVAL;
+    widest = std::max(widest, seal_off[b + 1] - seal_off[b]);
+  }
+  const size_t n = seal_off[n_blocks];
+  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  if (n && (!block_hash32 || !sig65 || !signer20 || !out_mask)) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  if (!c->have_valset) return IBFT_E_NOVALSET;
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint32_t nb = (uint32_t)n_blocks, nr = (uint32_t)n;
+  int rc;
+  c->wire_valid = false;
+  if (nr) {
+    if ((rc = ensure(c, c->d_boff, ((size_t)nb + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->d_bhash, (size_t)nb * 32))) return rc;
+    if ((rc = ensure(c, c->d_btally, (size_t)nb * 32))) return rc;
+    if (nb > c->h_btally_blocks) {  // (every call that delivers into it has synchronised before it returned: nothing writes it now)
+      if (c->h_btally) (void)hipHostFree(c->h_btally);
+      c->h_btally = c->dh_btally = nullptr;
+      c->h_btally_blocks = 0;
+      const size_t want = std::max<size_t>(nb, 256);
+      if (hipHostMalloc((void **)&c->h_btally, want * 32) != hipSuccess) {
+        c->h_btally = nullptr;
+        return IBFT_E_NOMEM;
+      }
+      c->h_btally_blocks = want;
+      void *d = nullptr;  // the tally writes the records itself where the verdict words go there too (not under IBFT_NO_HOST_DIRECT)
+      if (c->dh_mask && hipHostGetDevicePointer(&d, c->h_btally, 0) == hipSuccess) c->dh_btally = (uint64_t *)d;
+    }
+    ColumnCopies cc;
+    cc.add(c->d_boff.p, seal_off, ((size_t)nb + 1) * 4);
+    cc.add(c->d_bhash.p, block_hash32, (size_t)nb * 32);
+    cc.add(c->d_sig.p, sig65, n * 65);
+    cc.add(c->d_signer.p, signer20, n * 20);
+    if (pre_flags) cc.add(c->d_pre.p, pre_flags, n);
+    if ((rc = cc.flush(c))) return rc;
+    if ((rc = seal_digest_column(c, (uint8_t *)c->d_bhash.p, nb))) return rc;
+    hipLaunchKernelGGL(ibftk::block_rows_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)c->d_bhash.p,
+                       (const uint32_t *)c->d_boff.p, nb, nr, (uint8_t *)c->d_hash.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  // the rows are the resident batch from here on, exactly as ibft_seals_stage would have left them
+  c->staged_n = nr;
+  c->staged_pre = pre_flags != nullptr;
+  if (nr) {
+    if (c->ev_used >= 4096) c->ev_used = 0;
+    const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
+    if ((rc = enqueue_recover(c, nr, c->staged_pre, 0, time_it))) return rc;
+    if (c->read_pending) {  // a consumer stream is still copying the previous results (ibft_seals_export_on / exchange)
+      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
+      c->read_pending = false;
+    }
+    ibftk::block_tally_args t{};
+    t.work_mask = (uint64_t *)c->d_mask.p;
+    t.mask = (uint64_t *)c->d_mask_out.p;
+    t.host_mask = c->dh_mask;
+    t.vidx = (const int32_t *)c->d_vidx.p;
+    t.vpower32 = (const uint32_t *)c->d_vpower.p;
+    t.off = (const uint32_t *)c->d_boff.p;
+    t.n = nr;
+    t.n_blocks = nb;
+    t.n_validators = c->n_validators;
+    const size_t lds = (size_t)((c->n_validators + 31) / 32) * 4;
+    t.lds_bitmap = lds <= 49152 ? 1u : 0u;  // beyond: one workgroup walks every block over the HBM bitmap (tally_kernel's bound)
+    t.seen = (uint32_t *)c->d_seen.p;
+    t.acc = (uint64_t *)c->d_acc.p;
+    t.quorum = (const uint64_t *)c->d_quorum.p;
+    t.out = c->dh_btally ? c->dh_btally : (uint64_t *)c->d_btally.p;
+    const dim3 grid(t.lds_bitmap ? std::min(nb, ibftk::BTALLY_MAX_GRID) : 1u);
+    const size_t dyn = t.lds_bitmap ? lds : 0;
+    const bool wide = widest > 256u * ibftk::BTALLY_RPT;  // a block that one step of 256 threads does not cover
+    if (c->power_words == 1) {
+      if (wide)
+        hipLaunchKernelGGL((ibftk::block_tally_kernel<1, 1024>), grid, dim3(1024), dyn, c->stream, t);
+      else
+        hipLaunchKernelGGL((ibftk::block_tally_kernel<1, 256>), grid, dim3(256), dyn, c->stream, t);
+    } else {
+      if (wide)
+        hipLaunchKernelGGL((ibftk::block_tally_kernel<4, 1024>), grid, dim3(1024), dyn, c->stream, t);
+      else
+        hipLaunchKernelGGL((ibftk::block_tally_kernel<4, 256>), grid, dim3(256), dyn, c->stream, t);
+    }
+    HIPCHK(c, hipGetLastError());
+    if ((uint32_t)mask_words(nr) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed every word that held bits
+    c->host_direct = false;
+    const size_t mw = (size_t)mask_words(nr);
+    if (!c->dh_mask) HIPCHK(c, hipMemcpyAsync(c->h_mask, c->d_mask_out.p, mw * 8, hipMemcpyDeviceToHost, c->stream));
+    if (!c->dh_btally)
+      HIPCHK(c, hipMemcpyAsync(c->h_btally, c->d_btally.p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->stream));
+    if (c->cache_on) HIPCHK(c, hipMemcpyAsync(c->h_tally + 4, c->dev->d_learned.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->cache_on) {  // keys these rows taught the device → tables (the next call is warm)
+      const uint32_t *lw = reinterpret_cast<const uint32_t *>(c->h_tally + 4);
+      if ((rc = build_new_tables(c, lw[0], lw[1]))) return rc;
+    }
+    memcpy(out_mask, c->h_mask, mw * 8);
+    if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
+  }
+  if (out_tally)
+    for (uint32_t b = 0; b < nb; b++) {  // (no rows at all: every block is empty, power 0 < quorum)
+      ibft_tally_t &t = out_tally[b];
+      memset(&t, 0, sizeof t);
+      t.quorum_lo = c->quorum_w[0];
+      t.quorum_hi = c->quorum_w[1];
+      if (!nr) continue;
+      const uint64_t *r = c->h_btally + 4ull * b;
+      t.power_lo = r[0];
+      t.power_hi = r[1];
+      t.valid_rows = (uint32_t)(r[2] & 0xFFFFFFFFull);
+      t.distinct_senders = (uint32_t)(r[2] >> 32);
+      t.has_quorum = (uint32_t)r[3];
+    }
+  return IBFT_OK;
 }
 
 // a3 up to and including the tally (c->mu held)

@@ -14,6 +14,7 @@
 //   verify_known_group_kernel<G>    same, G = 2..32 lanes per signature
 //   verify_known_wave_kernel        same, one wavefront per signature in the row layout of wave_fe_dev.h
 //   tally_kernel                a8  HasQuorum             (core/validator_manager.go:77-96)
+//   block_rows_kernel, block_tally_kernel   chain sync: each block's hash → its rows, one HasQuorum per block
 //   gtab_build_kernel, qtab_build_kernel, qtab_commit_kernel   one-time fixed-base tables
 //   lookup_kernel                   sender → validator index for ibft_tally()
 //   wire_parse_kernel, wire_stage_seals_kernel   §8f rank 3: wire bytes → columns on the device (wire_dev.h)
@@ -1807,6 +1808,150 @@ __global__ void __launch_bounds__(TALLY_THREADS) tally_kernel(tally_args a) {
 #pragma unroll
     for (int i = 0; i < TALLY_SUM_WORDS; i++) a.host_tally[TALLY_OUT_WIDE + i] = w[i];
   }
+}
+
+// ---- chain sync: the committed seals of many finalized blocks in one call (ibft_verify_block_seals) ----------------
+// Only the blocks' hashes (n_blocks × 32 B) and their row offsets cross PCIe; one thread per row finds its block by binary
+// search over the offsets and writes the block's hash into the row's slot of the hash column the verdict kernels read.
+// (Empty blocks repeat an offset: the LAST b with off[b] ≤ row is the one whose range [off[b], off[b+1]) holds the row.)
+__global__ void block_rows_kernel(const uint8_t *__restrict__ block_hash32, const uint32_t *__restrict__ off, uint32_t n_blocks,
+                                  uint32_t n, uint8_t *__restrict__ hash32) {
+  const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  uint32_t lo = 0, hi = n_blocks - 1;  // off[0] = 0 ≤ row < off[n_blocks] = n: the answer lies in [lo, hi]
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= row) lo = mid;
+    else hi = mid - 1;
+  }
+  const uint4 *s = reinterpret_cast<const uint4 *>(block_hash32 + 32ull * lo);
+  uint4 *d = reinterpret_cast<uint4 *>(hash32 + 32ull * row);
+  d[0] = s[0];
+  d[1] = s[1];
+}
+
+// Segmented HasQuorum: one verdict launch judged the rows of every block, this kernel answers HasQuorum per block against
+// the one quorum of the context's validator set (core/validator_manager.go:77-96, 128-136, 147-155) — bit for bit what
+// tally_kernel computes for the same rows passed as a batch of their own.  A workgroup takes one block at a time (grid-stride:
+// the HBM-bitmap form runs ONE workgroup over all blocks, the bitmap being the context's single zeroed `seen`): distinct-
+// sender bitmap cleared, the block's rows walked, 2·PW 32-bit power pieces reduced through wave_sum_u64 and LDS, thread 0
+// recombines them and writes the block's record {power_lo, power_hi, valid | distinct << 32, has_quorum}.
+// The work mask is read by several workgroups (block boundaries do not fall on verdict words), so it is moved and zeroed by
+// the LAST workgroup to finish (a ticket in acc[TALLY_MAX_PIECES + 2], left zero again): no word is cleared under a reader.
+// THREADS: 256 for blocks of chain-sized seal sets, 1024 when a block has more rows than that (the host picks); a thread
+// takes BTALLY_RPT rows per step and issues their loads together (verdict word, validator index, then the powers of the rows
+// whose bit is set) — one dependent round trip per step instead of one per row.
+constexpr int BTALLY_RPT = 4;
+constexpr uint32_t BTALLY_MAX_GRID = 2048;  // workgroups of one launch (each takes blocks b, b + grid, …): few ticket arrivals
+struct block_tally_args {
+  uint64_t *work_mask;        // verdict words of the launch; consumed (moved to mask / host_mask, zeroed) here
+  uint64_t *mask, *host_mask; // host_mask: mapped pinned host memory or null
+  const int32_t *vidx;        // n: validator index of the row's signer (meaningful where the verdict bit is set)
+  const uint32_t *vpower32;   // n_validators × 2·PW pieces
+  const uint32_t *off;        // n_blocks + 1 row offsets
+  uint32_t n, n_blocks, n_validators;
+  uint32_t lds_bitmap;        // ⌈n_validators/32⌉ words of dynamic LDS; 0: `seen` in HBM, and the grid is one workgroup
+  uint32_t *seen;             // ⌈n_validators/32⌉ words, zero between launches (HBM form only)
+  uint64_t *acc;              // TALLY_ACC_WORDS, zero between launches (the ticket)
+  const uint64_t *quorum;     // TALLY_SUM_WORDS
+  uint64_t *out;              // n_blocks × 4 u64 (device memory or mapped pinned host memory)
+};
+template <int PW, int THREADS>
+__global__ void __launch_bounds__(THREADS) block_tally_kernel(block_tally_args a) {
+  constexpr int NP = 2 * PW;
+  constexpr int WAVES = THREADS / 64;
+  constexpr uint32_t STEP = (uint32_t)THREADS * BTALLY_RPT;
+  extern __shared__ uint32_t lseen[];
+  __shared__ uint64_t part[NP + 1][WAVES];
+  __shared__ uint32_t last_flag;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t seen_words = (a.n_validators + 31) / 32;
+  uint32_t *bm = a.lds_bitmap ? lseen : a.seen;
+  for (uint32_t b = blockIdx.x; b < a.n_blocks; b += gridDim.x) {
+    const uint32_t r0 = a.off[b], r1 = a.off[b + 1];
+    if (a.lds_bitmap)
+      for (uint32_t i = tid; i < seen_words; i += THREADS) lseen[i] = 0;
+    __syncthreads();
+    uint64_t p[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) p[k] = 0;
+    uint64_t valid = 0, distinct = 0;
+    for (uint32_t base = r0; base < r1; base += STEP) {
+      bool bit[BTALLY_RPT];
+      int vi[BTALLY_RPT];
+      uint32_t pw[BTALLY_RPT][NP];
+#pragma unroll
+      for (int j = 0; j < BTALLY_RPT; j++) {
+        const uint32_t r = base + (uint32_t)j * THREADS + tid;
+        bit[j] = r < r1 && ((a.work_mask[r >> 6] >> (r & 63)) & 1ull);
+        vi[j] = r < r1 ? a.vidx[r] : -1;
+      }
+#pragma unroll
+      for (int j = 0; j < BTALLY_RPT; j++) {
+        const bool use = bit[j] && vi[j] >= 0;  // (vidx is only meaningful where the verdict bit is set)
+#pragma unroll
+        for (int k = 0; k < NP; k++) pw[j][k] = use ? a.vpower32[(size_t)vi[j] * NP + k] : 0u;
+      }
+#pragma unroll
+      for (int j = 0; j < BTALLY_RPT; j++) {
+        valid += bit[j];
+        if (!bit[j] || vi[j] < 0) continue;  // unknown signers contribute 0 (validator_manager.go:88-92)
+        const uint32_t m = 1u << (vi[j] & 31);
+        if (atomicOr(&bm[vi[j] >> 5], m) & m) continue;  // a signer's power counts once per block (:147-155)
+        distinct++;
+#pragma unroll
+        for (int k = 0; k < NP; k++) p[k] += pw[j][k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+      const uint64_t s = wave_sum_u64(p[k]);
+      if (lane == 0) part[k][wave] = s;
+    }
+    const uint64_t cnt = wave_sum_u64(valid | (distinct << 32));
+    if (lane == 0) part[NP][wave] = cnt;
+    __syncthreads();
+    if (!a.lds_bitmap)  // the HBM bitmap is left zero for the next block: clear exactly the words this block set
+      for (uint32_t r = r0 + tid; r < r1; r += THREADS)
+        if ((a.work_mask[r >> 6] >> (r & 63)) & 1ull) {
+          const int v = a.vidx[r];
+          if (v >= 0) bm[v >> 5] = 0u;
+        }
+    if (tid == 0) {
+      uint64_t piece[TALLY_MAX_PIECES], c = 0;
+#pragma unroll
+      for (int k = 0; k < TALLY_MAX_PIECES; k++) {
+        piece[k] = 0;
+        if (k < NP)
+          for (int w = 0; w < WAVES; w++) piece[k] += part[k][w];
+      }
+      for (int w = 0; w < WAVES; w++) c += part[NP][w];
+      uint64_t wd[TALLY_SUM_WORDS];
+      pieces_to_words(piece, NP, wd);
+      uint64_t *o = a.out + 4ull * b;
+      o[0] = wd[0];
+      o[1] = wd[1];
+      o[2] = c;
+      o[3] = words_ge(wd, a.quorum) ? 1ull : 0ull;
+    }
+    __syncthreads();  // part[] and the bitmap are reused by the next block
+  }
+  // ---- every workgroup has read its rows' verdict words: the last one to get here moves and zeroes them ----
+  if (tid == 0) {
+    __threadfence();
+    const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES + 2), 1ull);
+    last_flag = (t == (unsigned long long)gridDim.x - 1ull) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!last_flag) return;
+  const uint32_t words = (a.n + 63) / 64;
+  for (uint32_t i = tid; i < words; i += THREADS) {
+    const uint64_t w = a.work_mask[i];
+    a.work_mask[i] = 0;
+    a.mask[i] = w;
+    if (a.host_mask) a.host_mask[i] = w;
+  }
+  if (tid == 0) __hip_atomic_store(a.acc + TALLY_MAX_PIECES + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- multi-GPU: the one exchange step -------------------------------------------------

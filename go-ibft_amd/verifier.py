@@ -41,9 +41,12 @@ EXPORTS = [
     "ibft_verify_messages_wire", "ibft_forget_proposal", "ibft_verify_certificates_wire", "ibft_keccak256",
     "ibft_cache_memory", "ibft_tally_prepare", "ibft_comm_info", "ibft_set_seal_digest", "ibft_group_set_seal_digest",
     "ibft_seals_stage_next", "ibft_seals_swap", "ibft_last_cold_table", "ibft_seals_submit", "ibft_seals_collect",
-    "ibft_comm_preload", "ibft_issue_probe", "ibft_seals_rows", "ibft_pipeline_stats",
+    "ibft_comm_preload", "ibft_issue_probe", "ibft_seals_rows", "ibft_pipeline_stats", "ibft_verify_block_seals",
 ]
-EXPORTS_SINCE = {"ibft_pipeline_stats": 4}   # exports younger than version 3: the version that brought them
+# exports younger than version 3: the version that brought them (ibft_verify_block_seals came without a version step: an older
+# build simply lacks it, and BatchVerifier.verify_block_seals raises GpuUnavailable there)
+EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
+OPTIONAL_EXPORTS = {"ibft_verify_block_seals"}
 COMM_ID_BYTES = 128
 E_RCCL = -8
 
@@ -128,6 +131,7 @@ def load_library() -> C.CDLL:
     if L.ibft_version() < need:   # a stale .so writes past the caller's ibft_tally_t (48 → 56 bytes at version 2)
         raise GpuUnavailable(f"{lib_path}: ibft_version() = {L.ibft_version()}, this binding needs >= {need} — rebuild")
     later = {name for name, since in EXPORTS_SINCE.items() if since > need}
+    later |= {name for name in OPTIONAL_EXPORTS if not hasattr(L, name)}
     missing = [name for name in EXPORTS if name not in later and not hasattr(L, name)]   # BEFORE the prototypes below touch any of them
     if missing:
         raise GpuUnavailable(f"{lib_path} lacks {', '.join(missing)} — a stale build: rebuild")
@@ -176,6 +180,8 @@ def load_library() -> C.CDLL:
     L.ibft_seals_rows.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if hasattr(L, "ibft_pipeline_stats"):
         L.ibft_pipeline_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "ibft_verify_block_seals"):
+        L.ibft_verify_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.ibft_verify_senders_wire.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.POINTER(Tally)]
     L.ibft_wire_stage_seals.argtypes = [vp]
     L.ibft_verify_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, vp, vp]
@@ -403,6 +409,28 @@ class BatchVerifier:
         self._chk(self._L.ibft_verify_seals(self._h, _p(h), _p(s), _p(f), _p(pre), n, _p(mask), C.byref(t)),
                   "ibft_verify_seals")
         return mask_to_bool(mask, n), t
+
+    # chain sync: IsValidCommittedSeal + HasQuorum for many finalized blocks in one call
+    def verify_block_seals(self, block_hash32, seal_off, sig65, signer20, pre_flags=None):
+        """ibft_verify_block_seals: block b's seals are rows [seal_off[b], seal_off[b+1]) and sign block_hash32[b] →
+        (verdict bool[n], Tally array[n_blocks]) — what one is_valid_committed_seal call per block returns"""
+        if not hasattr(self._L, "ibft_verify_block_seals"):
+            raise GpuUnavailable("this build of the library has no ibft_verify_block_seals — rebuild")
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
+        n = len(s)
+        if len(bh) != nb or len(f) != n or int(off[-1]) != n:
+            raise ValueError("block_hash32 needs one row per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        tallies = (Tally * max(nb, 1))()
+        self._chk(self._L.ibft_verify_block_seals(self._h, _p(bh), _p(off), nb, _p(s), _p(f), _p(pre), _p(mask), tallies),
+                  "ibft_verify_block_seals")
+        self._staged = n
+        return mask_to_bool(mask, n), list(tallies)[:nb]
 
     # Verifier.IsValidValidator, batched
     def is_valid_validator(self, payload: bytes, off, sig65, from20, pre_flags=None):

@@ -221,6 +221,26 @@ int ibft_verify_seals(ibft_ctx *ctx, const uint8_t *hash32, const uint8_t *sig65
                       const uint8_t *signer20, const uint8_t *pre_flags, size_t n,
                       uint64_t *out_mask, ibft_tally_t *tally);
 
+/* Chain sync: the committed seals of n_blocks finalized blocks, one validator set (the context's), one launch — what a
+ * syncing node checks before InsertProposal for every (Proposal, []CommittedSeal) pair it receives
+ * (/root/reference/core/backend.go:53-55, 80-82; core/validator_manager.go:77-96).
+ *   block_hash32  n_blocks × 32: each block's proposal hash, i.e. what its seals sign (the seal-digest convention of
+ *                 ibft_set_seal_digest applies as for ibft_verify_seals)
+ *   seal_off      n_blocks + 1, seal_off[0] = 0, non-decreasing: the seals of block b are rows [seal_off[b], seal_off[b+1])
+ *   sig65, signer20, pre_flags   one row per seal, as for ibft_verify_seals (pre_flags may be NULL)
+ *   out_mask      ⌈n/64⌉ words, n = seal_off[n_blocks]: bit i = IsValidCommittedSeal(block_hash(i), {signer20[i], sig65[i]})
+ *   out_tally     n_blocks entries (may be NULL): HasQuorum over the distinct member signers of block b's valid rows
+ * Bit for bit what n_blocks separate ibft_verify_seals calls return (each block's hash repeated over its rows): duplicate
+ * signers of a block count once, non-members 0, a seal placed in another block than its own is invalid; a block with no
+ * rows has has_quorum = 0.  shard_overlap = proposer_rows = 0.  With u256 powers each entry carries the low 128 bits and
+ * the exact has_quorum; ibft_last_tally_wide is NOT updated by this call.  IBFT_E_INVAL: NULL ctx or seal_off, seal_off[0]
+ * ≠ 0 or decreasing, a NULL column with n > 0; IBFT_E_TOOBIG: n or n_blocks > cfg.max_rows; IBFT_E_NOVALSET.  On return
+ * the rows are the resident staged batch, as after ibft_verify_seals; a pipelined pass in flight (ibft_seals_submit) is
+ * left to its ibft_seals_collect, as ibft_verify_seals leaves it.                                                      */
+int ibft_verify_block_seals(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags,
+                            uint64_t *out_mask, ibft_tally_t *out_tally);
+
 /* a3.  payload = concatenated PayloadNoSig bytes; row i is payload[off[i]..off[i+1]);
  * off has n+1 entries.                                                             */
 int ibft_verify_senders(ibft_ctx *ctx, const uint8_t *payload, const uint32_t *off,

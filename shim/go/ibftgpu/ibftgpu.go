@@ -220,6 +220,33 @@ func (c *Ctx) VerifySeals(hash32, sig65, signer20, preFlags []byte) ([]uint64, T
 	return mask, tally(t), c.check(rc)
 }
 
+// VerifyBlockSeals = IsValidCommittedSeal + HasQuorum for the committed seals of many finalized blocks in one call
+// (ibft_verify_block_seals): the seals of block b are rows [sealOff[b], sealOff[b+1]) and sign
+// blockHash32[32b:32b+32].  mask bit i is row i's verdict, tallies[b] block b's HasQuorum — what one VerifySeals
+// per block returns.  One validator set per call: a syncer splits its batch where the set changes.
+func (c *Ctx) VerifyBlockSeals(blockHash32 []byte, sealOff []uint32, sig65, signer20, preFlags []byte) ([]uint64, []Tally, error) {
+	if len(sealOff) == 0 {
+		return nil, nil, fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(blockHash32) < 32*nb || len(sig65) < 65*n || len(signer20) < 20*n || (preFlags != nil && len(preFlags) < n) {
+		return nil, nil, fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	mask := make([]uint64, (n+63)/64+1)
+	ct := make([]C.ibft_tally_t, nb+1)
+	rc := C.ibft_verify_block_seals(c.h, ptr8(blockHash32), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), C.size_t(nb),
+		ptr8(sig65), ptr8(signer20), ptr8(preFlags), (*C.uint64_t)(unsafe.Pointer(&mask[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err := c.check(rc); err != nil {
+		return nil, nil, err
+	}
+	tallies := make([]Tally, nb)
+	for b := range tallies {
+		tallies[b] = tally(ct[b])
+	}
+	return mask, tallies, nil
+}
+
 // VerifySenders = IsValidValidator over a batch (core/ibft.go:1128); payload is the
 // concatenation of msg.PayloadNoSig(), off its n+1 offsets.
 func (c *Ctx) VerifySenders(payload []byte, off []uint32, sig65, from20, preFlags []byte) ([]uint64, Tally, error) {
