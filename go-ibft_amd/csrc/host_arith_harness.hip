@@ -165,6 +165,8 @@ int dev_verify_known(const uint8_t *digest32, const uint8_t *sig65, const uint8_
   return ibftk::verify_known(g_gtab.data(), g_qtab.data(), secp::from_be32(digest32), secp::from_be32(sig65),
                              secp::from_be32(sig65 + 32), sig65[64], flags) ? 1 : 0;
 }
+// the fixed-base window width this harness was built with (the warm-path case builder splits u1 by it)
+int dev_gtab_bits(void) { return ibftk::GTAB_BITS; }
 // table entry (w, e) of the last key: x ‖ y big-endian
 void dev_qtab_entry(int w, int e, uint8_t *out64) {
   const uint32_t *p = g_qtab.data() + (size_t)ibftk::GTAB_ENTRY_DWORDS * (w * ibftk::QTAB_ENTRIES + e);

@@ -278,5 +278,6 @@ void wvh_recover2(const uint8_t *hash32, const uint8_t *sig65, uint32_t flags, u
   wave_emul::run(lane_rec2_main, &j);
 }
 uint32_t wvh_neg_limb(int which, int i) { return wv::wneg_limb(which, i); }
+int wvh_gtab_bits(void) { return ibftk::GTAB_BITS; }  // the fixed-base window width of this harness's table
 
 }  // extern "C"
