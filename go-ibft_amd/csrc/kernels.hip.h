@@ -959,11 +959,8 @@ __global__ void __launch_bounds__(128 * PAIRS_PER_BLOCK) ecrecover_wave2_kernel(
 // waves_per_eu(1, 2): the scheduler may spend registers (up to 256) on interleaving the independent
 // multiplications of a doubling — 42 → 9 s_nop per doubling in the main loop, 0.474 → 0.470 ms at 4 096 rows
 // (profiles/r02c_sweeps.txt) — while two wavefronts per SIMD (8 192 rows) still fit.
-#ifndef IBFT_ROWS_WAVES_PER_EU_ATTR
-#define IBFT_ROWS_WAVES_PER_EU_ATTR __attribute__((amdgpu_waves_per_eu(1, 2)))
-#endif
 template <int MODE>
-__global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) IBFT_ROWS_WAVES_PER_EU_ATTR ecrecover_rows_kernel(recover_args a) {
+__global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) __attribute__((amdgpu_waves_per_eu(1, 2))) ecrecover_rows_kernel(recover_args a) {
   const uint32_t wave = blockIdx.x * WAVE_KERNEL_WAVES + (threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63u;
   if (wave * 4u >= a.n) return;  // whole wavefront

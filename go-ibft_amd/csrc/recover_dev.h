@@ -169,9 +169,6 @@ constexpr int WINDOW_DIGITS = 33;
 // it in front of the four doublings of the window, whose ≈520 instructions then cover the latency of the scratch loads (a
 // lone wavefront per SIMD otherwise waits it out, 66 times per signature; hosts differ in how fast scratch is served:
 // DESIGN.md §5.1) — and window_add_q adds it.
-#ifndef IBFT_WINDOW_PREFETCH
-#define IBFT_WINDOW_PREFETCH 1  // 0: the entry is read where it is used, behind the doublings (A/B)
-#endif
 __host__ __device__ __forceinline__ aff window_operand(const wtab &t, int e, bool lambda, bool flip) {
   const uint32_t mag = (uint32_t)(e < 0 ? -e : e);
   const uint32_t idx = mag ? mag : 1u;  // (a dummy operand for e = 0: the sum is computed and dropped)
@@ -185,11 +182,7 @@ __host__ __device__ __forceinline__ jac window_add_q(const jac &acc, const aff &
   const jac sum = secp::jac_add_aff_t<true>(acc, q);
   return secp::jac_select(e != 0, sum, acc);
 }
-__host__ __device__ __forceinline__ jac window_add(const jac &acc, const wtab &t, int e, bool lambda, bool flip) {
-  return window_add_q(acc, window_operand(t, e, lambda, flip), e);
-}
-template <bool PREFETCH>
-__host__ __device__ __forceinline__ jac ecmult_var_t(const aff &R, const u256 &k) {
+__host__ __device__ __forceinline__ jac ecmult_var(const aff &R, const u256 &k) {
   secp::glv_split sp = secp::sc_split_lambda(k);
   aff R1 = R;
   R1.y = secp::l26_select(sp.neg1, secp::fe_normalize_weak(secp::fe_neg(R.y, 1)), R.y);
@@ -201,31 +194,22 @@ __host__ __device__ __forceinline__ jac ecmult_var_t(const aff &R, const u256 &k
 #pragma unroll 1
   for (int i = WINDOW_DIGITS - 1; i >= 0; i--) {
     const int e1 = (int)secp::nibble(k1, i) - 8, e2 = (int)secp::nibble(k2, i) - 8;
-    aff q1, q2;
-    if (PREFETCH) {
-      q1 = window_operand(t, e1, false, false);
-      q2 = window_operand(t, e2, true, flip2);
-    }
+    const aff q1 = window_operand(t, e1, false, false), q2 = window_operand(t, e2, true, flip2);
     if (i != WINDOW_DIGITS - 1) {
 #pragma unroll 1
       for (int d = 0; d < 4; d++) acc = secp::jac_dbl_t<true>(acc);
     }
 #pragma unroll 1
     for (int h = 0; h < 2; h++) {
-      if (PREFETCH) {
-        aff q;  // (one inlined copy of the mixed addition: the operand is chosen, not the code)
-        q.x = secp::l26_select(h != 0, q2.x, q1.x);
-        q.y = secp::l26_select(h != 0, q2.y, q1.y);
-        acc = window_add_q(acc, q, h ? e2 : e1);
-      } else {
-        acc = window_add(acc, t, h ? e2 : e1, h != 0, h != 0 && flip2);
-      }
+      aff q;  // (one inlined copy of the mixed addition: the operand is chosen, not the code)
+      q.x = secp::l26_select(h != 0, q2.x, q1.x);
+      q.y = secp::l26_select(h != 0, q2.y, q1.y);
+      acc = window_add_q(acc, q, h ? e2 : e1);
     }
   }
   acc.z = secp::fe_mul(acc.z, t.zc);  // back from the isomorphic curve
   return acc;
 }
-__host__ __device__ __forceinline__ jac ecmult_var(const aff &R, const u256 &k) { return ecmult_var_t<IBFT_WINDOW_PREFETCH != 0>(R, k); }
 
 // ---- the same multiplication with the window table in LDS (round 5) -------------------------------------------------
 // The private-segment table above costs 3 056 B of scratch per lane — 1.3 GB of HBM traffic per N = 65 536 launch, 172 × the
@@ -388,9 +372,6 @@ __host__ __device__ __forceinline__ jac ecmult_var_lds(const aff &R, const u256 
 // where the operand comes from (an LDS table entry, with β·X on the odd steps — or the G-table entry asked for one step
 // earlier) and whether four doublings run first; all of that hangs on the step number, which is wave-uniform.  The first
 // G-table entry is asked for before the window table is even built.
-#ifndef IBFT_LANE_MERGED
-#define IBFT_LANE_MERGED 1  // 0: ecmult_gen(ecmult_var_lds(…)) — two copies of the mixed addition (round 5; A/B)
-#endif
 template <int TPB>
 __host__ __device__ __forceinline__ jac ecmult_var_gen_lds(const aff &R, const u256 &k, const uint32_t *__restrict__ gtab,
                                                            const u256 &u1, uint32_t *col) {
@@ -559,10 +540,8 @@ template <bool PREFETCH>
 struct var_mult_private {
   __host__ __device__ __forceinline__ jac operator()(const aff &R, const u256 &k, const uint32_t *__restrict__ gtab,
                                                      const u256 &u1) const {
-#if IBFT_LANE_MERGED
     if constexpr (!PREFETCH) return ecmult_var_gen_private(R, k, gtab, u1);  // (the form the AUTO rule dispatches beyond 65 536 rows)
-#endif
-    return ecmult_gen(gtab, u1, ecmult_var_t<PREFETCH>(R, k));  // (round 4's form with the entries read in front of the doublings: A/B)
+    return ecmult_gen(gtab, u1, ecmult_var(R, k));  // (round 4's form with the entries read in front of the doublings: A/B)
   }
 };
 template <int TPB>
@@ -570,13 +549,7 @@ struct var_mult_lds {
   uint32_t *col;
   __host__ __device__ __forceinline__ jac operator()(const aff &R, const u256 &k, const uint32_t *__restrict__ gtab,
                                                      const u256 &u1) const {
-#if IBFT_LANE_MERGED
     return ecmult_var_gen_lds<TPB>(R, k, gtab, u1, col);
-#else
-    // (round 5 measured a first form of the merged loop at −2.6 % on a lease of the slow kind, +1.5 % on the fast kind and kept
-    // the two copies: profiles/r05la_lane_merge_ab.txt)
-    return ecmult_gen(gtab, u1, ecmult_var_lds<TPB>(R, k, col));
-#endif
   }
 };
 template <class VARMULT>
@@ -617,7 +590,7 @@ __host__ __device__ __forceinline__ bool recover_pubkey_with(const uint32_t *__r
 __host__ __device__ __forceinline__ bool recover_pubkey(const uint32_t *__restrict__ gtab, const u256 &z_raw,
                                                         const u256 &r, const u256 &s, uint32_t v,
                                                         uint32_t flags, uint32_t addr[5], aff &Qa) {
-  return recover_pubkey_with(gtab, z_raw, r, s, v, flags, addr, Qa, var_mult_private<IBFT_WINDOW_PREFETCH != 0>{});
+  return recover_pubkey_with(gtab, z_raw, r, s, v, flags, addr, Qa, var_mult_private<true>{});
 }
 __host__ __device__ __forceinline__ bool recover_address(const uint32_t *__restrict__ gtab, const u256 &z_raw,
                                                          const u256 &r, const u256 &s, uint32_t v,

@@ -123,20 +123,10 @@ HD uint32_t lane_perm(uint32_t v, uint32_t src) {
 struct u32x2 {
   uint32_t a, b;
 };
-#ifndef IBFT_ROW_SWAPS
-#define IBFT_ROW_SWAPS 1  // 0: the same exchanges through ds_bpermute (A/B timing)
-#endif
 HD u32x2 rows_swap16(uint32_t d, uint32_t s) {
 #if defined(__HIP_DEVICE_COMPILE__)
-#if IBFT_ROW_SWAPS
   const auto r = __builtin_amdgcn_permlane16_swap(d, s, false, false);
   return u32x2{r[0], r[1]};
-#else
-  const uint32_t l = __lane_id();
-  const uint32_t sd = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l - 16u) << 2), (int)s);
-  const uint32_t du = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l + 16u) << 2), (int)d);
-  return u32x2{(l & 16u) ? sd : d, (l & 16u) ? s : du};
-#endif
 #elif defined(IBFT_WAVE_EMUL)
   const int l = wave_emul::lane();
   const bool odd = (l & 16) != 0;
@@ -149,15 +139,8 @@ HD u32x2 rows_swap16(uint32_t d, uint32_t s) {
 }
 HD u32x2 rows_swap32(uint32_t d, uint32_t s) {
 #if defined(__HIP_DEVICE_COMPILE__)
-#if IBFT_ROW_SWAPS
   const auto r = __builtin_amdgcn_permlane32_swap(d, s, false, false);
   return u32x2{r[0], r[1]};
-#else
-  const uint32_t l = __lane_id();
-  const uint32_t sd = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l - 32u) << 2), (int)s);
-  const uint32_t du = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((l + 32u) << 2), (int)d);
-  return u32x2{(l & 32u) ? sd : d, (l & 32u) ? s : du};
-#endif
 #elif defined(IBFT_WAVE_EMUL)
   const int l = wave_emul::lane();
   const bool up = (l & 32) != 0;
@@ -485,9 +468,7 @@ WVF wjac wjac_add(const wjac &p, const wjac &q, const wk &k) {
 }
 // madd-2007-bl (q affine, never infinity) with Z3 = (Z1 + H)² − Z1Z1 − HH written as 2·Z1·H (S = M here) and
 // Y3 = r·(V − X3) − 2·Y1·J as ONE fused multiply-add: nine multiplications and a fused pair instead of eleven.
-// RARE_INL: the doubling of the exceptional case P = Q with its multiplications pasted in too — for a caller that must stay a
-// LEAF function (rows_two_adds_fn: a nested call makes the compiler save a register to the stack on every entry)
-template <bool INL = false, bool RARE_INL = false>
+template <bool INL = false>
 WVF wjac wjac_add_aff(const wjac &p, const waff &q, const wk &k) {
   const uint32_t z1z1 = wfe_sqr<INL>(p.z, k);
   const uint32_t u2 = wfe_mul<INL>(q.x, z1z1, k);
@@ -513,46 +494,11 @@ WVF wjac wjac_add_aff(const wjac &p, const waff &q, const wk &k) {
     bool rz = false;
     if (any(hz)) rz = wfe_is_zero(rr);
     const bool same = hz && rz, opposite = hz && !rz;
-    if (any(same)) r = wjac_select(same, wjac_dbl<RARE_INL>(qj, k), r);
+    if (any(same)) r = wjac_select(same, wjac_dbl<false>(qj, k), r);
     r = wjac_select(opposite, wjac_inf(), r);
   }
   r = wjac_select(p.inf, qj, r);
   return r;
-}
-// Two mixed additions in a row — acc ← acc + q1 (if t1), then + q2 (if t2) — as ONE outlined leaf function with the
-// multiplications pasted in (round 6, the A/B form IBFT_ROWS_SHARED_ADDS: see the macro for what it measured).  The idea: the
-// row-per-signature recover runs this pair 32 times in its main loop and 8 times for the fixed-base windows, whose own pasted copy
-// issues at 3.5 ns per instruction where the main loop's identical additions take 2.0 (profiles/r06e_rows_stage_issue.txt).
-#if defined(__HIP_DEVICE_COMPILE__)
-struct wjac4 {
-  uint32_t x, y, z, inf;
-};
-static __device__ __attribute__((noinline)) wjac4 rows_two_adds_fn(uint32_t x, uint32_t y, uint32_t z, uint32_t inf, uint32_t q1x,
-                                                                  uint32_t q1y, uint32_t q2x, uint32_t q2y, uint32_t t1, uint32_t t2,
-                                                                  uint32_t li, uint32_t row, uint32_t act, uint32_t m3, uint32_t lt3,
-                                                                  uint32_t lt9, uint32_t kr, uint32_t k1, uint32_t k2, uint32_t k8) {
-  wk k;
-  k.li = li; k.row = row; k.act = act; k.m3 = m3; k.lt3 = lt3; k.lt9 = lt9; k.kr = kr; k.k1 = k1; k.k2 = k2; k.k8 = k8;
-  wjac acc = wjac{x, y, z, inf != 0};
-  const wjac s1 = wjac_add_aff<true, true>(acc, waff{q1x, q1y}, k);
-  acc = wjac_select(t1 != 0, s1, acc);
-  const wjac s2 = wjac_add_aff<true, true>(acc, waff{q2x, q2y}, k);
-  acc = wjac_select(t2 != 0, s2, acc);
-  return wjac4{acc.x, acc.y, acc.z, acc.inf ? 1u : 0u};
-}
-#endif
-WVF wjac rows_two_adds(const wjac &acc, const waff &q1, const waff &q2, bool t1, bool t2, const wk &k) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const wjac4 r = rows_two_adds_fn(acc.x, acc.y, acc.z, acc.inf ? 1u : 0u, q1.x, q1.y, q2.x, q2.y, t1 ? 1u : 0u, t2 ? 1u : 0u, k.li,
-                                   k.row, k.act, k.m3, k.lt3, k.lt9, k.kr, k.k1, k.k2, k.k8);
-  return wjac{r.x, r.y, r.z, r.inf != 0};
-#else
-  wjac a = acc;
-  const wjac s1 = wjac_add_aff<true>(a, q1, k);
-  a = wjac_select(t1, s1, a);
-  const wjac s2 = wjac_add_aff<true>(a, q2, k);
-  return wjac_select(t2, s2, a);
-#endif
 }
 HD wjac wjac_lane_xor(const wjac &p, int off) {
   wjac r;
@@ -639,7 +585,6 @@ WVF uint32_t wfe_pow_chain_rolled(uint32_t a, const wk &k) {
   }
   return cur;
 }
-WVF uint32_t wfe_sqrt_candidate_rolled(uint32_t a, const wk &k) { return wfe_pow_chain_rolled<false>(a, k); }
 
 // ---- √ on a spare row ------------------------------------------------------------------------------
 // The a^((p+1)/4) chain (secp::fe_sqrt_candidate) is 266 dependent multiplications — but it needs
@@ -899,18 +844,6 @@ WVF bool jac_to_aff_wave(aff &r, const jac &p, const wk &k) {
   return !(p.inf || secp::fe_is_zero(p.z));
 }
 
-// The same from the row layout, multiplications included: Z⁻¹ goes back into the row and X·Z⁻², Y·Z⁻³ are four
-// wfe_mul (≈90 instructions each, and code that is hot anyway) instead of four lane-layout multiplications
-// (≈224 each, fetched for this one use).
-WVF bool wjac_to_aff(aff &r, const wjac &p, const wk &k) {
-  const fe zf = gather(p.z);
-  const uint32_t zi = scatter(secp::fe_from_u256(modinv_wave<secp::ModP>(secp::fe_to_u256(zf), k)), k);
-  const uint32_t zi2 = wfe_sqr(zi, k);
-  r.x = secp::fe_normalize(gather(wfe_mul(p.x, zi2, k)));
-  r.y = secp::fe_normalize(gather(wfe_mul(p.y, wfe_mul(zi2, zi, k), k)));
-  return !(p.inf || secp::fe_is_zero(zf));
-}
-
 // u1·G summed into acc: the GTAB_WINDOWS fixed-base windows dealt to the four rows (rows hold partial sums: the caller joins)
 // Table point t of this row's share (window row·WPR + t) — the load only; gen_windows_wave consumes it.
 WVF waff gen_window_point(const uint32_t *__restrict__ gtab, const u256 &u1, int t, const wk &k) {
@@ -946,9 +879,6 @@ WVF wjac gen_windows_wave(const uint32_t *__restrict__ gtab, const u256 &u1, wja
 WVF wjac gen_windows_wave(const uint32_t *__restrict__ gtab, const u256 &u1, wjac acc, const wk &k) {
   return gen_windows_wave(gtab, u1, acc, gen_window_point(gtab, u1, 0, k), k);
 }
-#ifndef IBFT_WAVE_COMMON_Z
-#define IBFT_WAVE_COMMON_Z 1  // 1: the one-wavefront recover brings each row's table to one common Z (mixed additions); 0: A/B
-#endif
 // ---- the recover, one signature per wavefront -------------------------------------------------------
 // Same contract and rejection list as ibftk::recover_pubkey (recover_dev.h); every lane of the
 // wavefront passes the same (z, r, s, v) and gets the same answer.
@@ -1054,7 +984,6 @@ WVF bool recover_pubkey_wave(const uint32_t *__restrict__ gtab, const u256 &z_ra
   T[6] = wjac_dbl(T[3], k);
   T[7] = wjac_add(T[6], T[1], k);
   T[8] = wjac_dbl(T[4], k);
-#if IBFT_WAVE_COMMON_Z
   // ONE common Z for the row's table, as in the row-per-signature recover: with Zc = z1·…·z8 and s_i = Zc / z_i entry i
   // is the affine point (x_i·s_i², y_i·s_i³) of an isomorphic curve, the sixteen additions of the main loop are MIXED
   // (10.5 multiplications instead of 16) and Zc goes into the accumulator's Z once behind the loop: 51 multiplications
@@ -1096,24 +1025,6 @@ WVF bool recover_pubkey_wave(const uint32_t *__restrict__ gtab, const u256 &z_ra
     acc = wjac_select(mag != 0, sum, acc);
   }
   acc.z = wfe_mul(acc.z, Zc, k);  // back from the table's curve (an accumulator at infinity keeps its flag)
-#else
-  WV_STAGE(3, T[3].x ^ T[5].y ^ T[6].z ^ T[7].x ^ T[8].y ^ yc ^ u1.v[0])
-  wjac acc = wjac_select(top, T[1], wjac_inf());
-#pragma unroll 1
-  for (int jd = 15; jd >= 0; jd--) {
-#pragma unroll 1
-    for (int d = 0; d < 4; d++) acc = wjac_dbl<true>(acc, k);
-    const uint32_t word = jd >= 8 ? d_hi : d_lo;
-    const int dg = (int)((word >> (4 * (jd & 7))) & 15u) - 8;
-    const uint32_t mag = (uint32_t)(dg < 0 ? -dg : dg);
-    wjac q = T[1];
-#pragma unroll
-    for (int e = 2; e <= 8; e++) q = wjac_select(mag == (uint32_t)e, T[e], q);
-    q.y = dg < 0 ? wfe_neg1(q.y, k) : q.y;  // magnitude ≤ 2
-    const wjac sum = wjac_add<true>(acc, q, k);
-    acc = wjac_select(mag != 0, sum, acc);
-  }
-#endif
   WV_STAGE(4, acc.x ^ acc.y ^ acc.z ^ yc ^ u1.v[0])
   // back to the real curve: y² = w ?  parity(y) = v; Z ← Z·y
   ok = ok && wfe_is_zero(wfe_sqr(yc, k) + wfe_neg1(w, k));
@@ -1172,30 +1083,6 @@ WVF void recover_helper_wave(const uint32_t *__restrict__ gtab, const u256 &z_ra
   }
   if (lane_id() == 0) sh->ginf = acc.inf ? 1u : 0u;
   sync();  // barrier 2
-}
-
-// One dword per lane from global memory straight into LDS — no VGPR in between, nothing for the wavefront to wait for until it
-// says so: on gfx950 `global_load_lds_dword` (LDS address = M0 + 4·lane, the global address is per lane); the load is asynchronous
-// and counted by vmcnt.  Written as an asm statement on purpose: hipcc does not count it, so it puts NO wait in front of later
-// LDS reads (it would wait vmcnt(0) at the very next one if it knew) — the reader says lds_prefetch_wait() before it reads
-// what was prefetched.  dst64: a wave-uniform pointer to 64 dwords of LDS (one per lane).  The emulator copies.
-WVF void lds_prefetch_dword(uint32_t *dst64, const uint32_t *src) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  typedef __attribute__((address_space(3))) uint32_t lds_u32;
-  const uint32_t m0v = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_u32 *)dst64);
-  uint32_t keep;  // (M0 is the compiler's: saved and restored inside the statement that borrows it)
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(m0v)
-               : "memory");
-#else
-  dst64[lane_id()] = *src;
-#endif
-}
-WVF void lds_prefetch_wait() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 }
 
 WVF waff load_waff(const uint32_t *__restrict__ e20, const wk &k) {
@@ -1294,87 +1181,27 @@ WVF bool rows_finish_deferred(aff &Qa, const wjac &p1, const wjac &p2, uint32_t 
 // STOP < 99 cuts the function short after a stage (devtest timing breakdown only; addr then holds junk).
 // wtab: ROW_TAB_SLOTS × 64 dwords of wave-private scratch (LDS in the kernels): element (slot, lane) at
 // wtab[slot·64 + lane]; a lane only ever touches its own column, so no barrier is involved.
-#ifndef IBFT_ROWS_VARIANT
-#define IBFT_ROWS_VARIANT 2  // 1: table in registers, straight-line build (kept for A/B timing); 2: table in LDS, rolled loops
-#endif
-#ifndef IBFT_ROWS_PEEL
-#define IBFT_ROWS_PEEL 1  // 1: the first digit of the main loop and the first G window are choices, not additions (A/B: 0)
-#endif
-#ifndef IBFT_ROWS_DEFER_SQRT
-#define IBFT_ROWS_DEFER_SQRT 1  // 1: √ and the final inversion from one exponentiation at the end (rows_finish_deferred); 0: √ first, safegcd last (A/B)
-#endif
-// IBFT_ROWS_G_PREFETCH = 1: the sixteen table points of u1·G go into wave-private LDS as soon as u1 is known (global → LDS
-// directly, no register, no wait: lds_prefetch_dword) and are long there when the G additions come.  BUILT AND MEASURED in round
-// 6, NOT ADOPTED: the dependent table reads in front of the fifteen additions are not what those additions wait for — with the
-// prefetch the kernel is 0.9 % SLOWER on a resident batch (0.3329 → 0.3360 ms: 32 DMA instructions, 32 KB more LDS per
-// workgroup) and 0.4 % slower on fresh batches whose entries come from beyond the L2 (0.3349 → 0.3362 ms), and the stage
-// between the main loop and the closing exponentiation takes 0.038 ms as before (profiles/r06b_kernel_ab.txt,
-// r06b_fresh_batch_ab.txt, r06b_rows_stage_ms.txt).  Kept behind the macro for the A/B.
-#ifndef IBFT_ROWS_G_PREFETCH
-#define IBFT_ROWS_G_PREFETCH 0
-#endif
-// IBFT_ROWS_G_MERGED = 1 (round 6): the fixed-base additions run as further iterations of the MAIN LOOP — two table points per
-// iteration through the main loop's own two pasted mixed additions, no doublings — instead of a loop of their own around a third
-// pasted copy.  What the per-stage counters showed (profiles/r06e_rows_stage_issue.txt): the G stage issues 10.2 k instructions in
-// 36 µs, 3.5 ns each where the main loop's identical additions take 2.0 — and the excess does not move when the table points are
-// prefetched (profiles/r06f_gpre_stage_ab.txt): it is the first walk through 5.5 KB of code the instruction cache has never
-// seen, by every wavefront of the chip at once (so the reading went).
-// — BUILT AND MEASURED, NOT ADOPTED: the fixed-base stage fell from 0.035 to 0.023 ms, the main loop rose from 0.205 to 0.216 ms
-// (≈ 110 more instructions per iteration for the phase logic, and a worse schedule): N = 4 096 0.3338 → 0.3402 ms
-// (profiles/r06g_kernel_ab.txt, r06g_rows_stage_ms.txt).  What replaced it: IBFT_ROWS_SHARED_ADDS.
-// IBFT_ROWS_G_MERGED = 2 (with IBFT_ROWS_G_PREFETCH = 1): the uniform form — both phases read their operands from LDS by slot
-// number; 0.3336 → 0.3415 ms (profiles/r06p_kernel_ab.txt), not adopted either.
-#ifndef IBFT_ROWS_G_MERGED
-#define IBFT_ROWS_G_MERGED 0
-#endif
-// IBFT_ROWS_SHARED_ADDS = 1: both loops keep their shape and CALL one outlined pair of pasted mixed additions (rows_two_adds,
-// a leaf function: no stack).  BUILT AND MEASURED, NOT ADOPTED either: the main loop loses the same 0.010 ms (its two additions
-// no longer share a scheduling region with the doublings and the table reads around them) and the fixed-base stage gains
-// nothing: N = 4 096 0.3337 → 0.3406 ms (profiles/r06h_kernel_ab.txt, r06h_rows_stage_ms.txt).  The three pasted copies of the
-// mixed addition are a local optimum of THIS compiler's schedule; DESIGN.md §9 has the table.
-#ifndef IBFT_ROWS_SHARED_ADDS
-#define IBFT_ROWS_SHARED_ADDS 0
-#endif
-constexpr int ROW_TAB_G0 = 32;  // 8 entries × (x, y, z → X·β) + 8 prefix products, then (x, y) of the GTAB_WINDOWS points of u1·G
-#ifndef IBFT_ROWS_TAB_PAD_SLOTS
-#define IBFT_ROWS_TAB_PAD_SLOTS 0  // experiment: unused slots (what does a workgroup's LDS SIZE alone cost?)
-#endif
-constexpr int ROW_TAB_SLOTS = ROW_TAB_G0 + (IBFT_ROWS_G_PREFETCH ? 2 * ibftk::GTAB_WINDOWS : 0) + IBFT_ROWS_TAB_PAD_SLOTS;
+// Built, measured and removed: the table in registers, built straight-line; √t first, safegcd last; no peeled
+// first digit; the G-table points prefetched into LDS; the G additions merged into the main loop, or sharing its additions.
+constexpr int ROW_TAB_SLOTS = 32;  // 8 entries × (x, y, z → X·β) + 8 prefix products
 template <int STOP = 99>
 WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw, const u256 &r, const u256 &s,
                            uint32_t v, uint32_t flags, uint32_t addr[5], aff &Qa, uint32_t *wtab) {
 #define WV_STAGE(n, keep)     \
   if (STOP == (n)) {          \
-    lds_prefetch_wait();      \
     addr[0] = (keep);         \
     return ok;                \
   }
-  // (the wait: a wavefront must not end with a prefetch into its LDS still on its way)
   const wk k = wk_init();
-#if defined(__HIP_DEVICE_COMPILE__) && defined(IBFT_ROWS_PAD_DWORDS)
-  // code-placement experiment (profiles/r04n_*): every instruction behind this point moves by 4·IBFT_ROWS_PAD_DWORDS bytes
-#pragma unroll
-  for (int pad_ = 0; pad_ < IBFT_ROWS_PAD_DWORDS; pad_++) asm volatile("s_nop 0");
-#endif
   bool ok = ibftk::sig_in_range(r, s, v, flags);
   const fe rx = secp::fe_from_u256(r);
   const uint32_t x = scatter(rx, k);
   const uint32_t one = k.li == 0 ? 1u : 0u;
   const uint32_t rhs = wfe_mul(wfe_sqr(x, k), x, k) + (k.li == 0 ? 7u : 0u);  // t = x³ + 7, magnitude 2
-#if IBFT_ROWS_DEFER_SQRT
   // y = √t is not computed here: R′ = (x·t, t²) on the isomorphic curve stands in for R until the very end, where ONE
   // exponentiation yields both √t and the inverse of the final Z (rows_finish_deferred)
   const waff R1 = waff{wfe_mul(x, rhs, k), wfe_sqr(rhs, k)};
   const uint32_t skeep = R1.x ^ R1.y;
-#else
-  const uint32_t yc = wfe_sqrt_candidate_rolled(rhs, k);
-  const bool on_curve = wfe_is_zero(wfe_sqr(yc, k) + wfe_neg2(rhs, k));  // cross-lane: every row evaluates it
-  ok = ok && on_curve;
-  fe y = secp::fe_normalize(gather(yc));
-  y = secp::l26_select((y.n[0] & 1u) != v, secp::fe_normalize_weak(secp::fe_neg(y, 1)), y);
-  const waff R1 = waff{x, scatter(y, k)};
-  const uint32_t skeep = y.n[0] ^ y.n[3];
-#endif
   WV_STAGE(1, skeep)
   // u1 = −z/r, u2 = s/r (mod n); u2 = k1 + k2·λ
   const secp::sc rinv = secp::sc_from_u256(modinv_wave<secp::ModN>(r, k));
@@ -1382,21 +1209,6 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
   const u256 u1 = secp::sc_neg_canon(secp::sc_canon(secp::sc_mul(secp::sc_from_u256(z_raw), rinv)));
   const u256 u2 = secp::sc_canon(secp::sc_mul(secp::sc_from_u256(s), rinv));
   WV_STAGE(22, skeep ^ u1.v[0] ^ u2.v[3])
-#if IBFT_ROWS_G_PREFETCH
-  // (A/B form, see the macro: the sixteen table points of u1·G are asked for NOW — global memory → wave-private LDS — and are
-  // long there when the G additions come, ≈ 0.25 ms later)
-  {
-    const uint32_t ld = k.li < 10 ? k.li : 0u;  // (idle lanes fetch limb 0 and are masked at use)
-#pragma unroll
-    for (int win = 0; win < ibftk::GTAB_WINDOWS; win++) {
-      const int bit = win * ibftk::GTAB_BITS;
-      const uint32_t dgt = (u1.v[bit >> 5] >> (bit & 31)) & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
-      const uint32_t *e = gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * ((size_t)win * ibftk::GTAB_ENTRIES + dgt) + ld;
-      lds_prefetch_dword(wtab + (ROW_TAB_G0 + 2 * win) * 64, e);
-      lds_prefetch_dword(wtab + (ROW_TAB_G0 + 2 * win + 1) * 64, e + 10);
-    }
-  }
-#endif
   const secp::glv_split sp = secp::sc_split_lambda(u2);
   WV_STAGE(2, skeep ^ u1.v[0] ^ sp.k1.v[0] ^ sp.k2.v[1])
   // signed radix-16 digits of |k1|, |k2|: k + 0x88…8 has nibbles d_j + 8, bit 128 is digit 32
@@ -1411,75 +1223,6 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
     w1[4] = c1;
     w2[4] = c2;
   }
-#if IBFT_ROWS_VARIANT == 1
-  // tables 1..8 of R (affine start: mixed additions) and, through X·β, of λR
-  wjac T[9];
-  T[1] = wjac_from_aff(R1, k);
-  T[2] = wjac_dbl(T[1], k);
-  T[3] = wjac_add_aff(T[2], R1, k);
-  T[4] = wjac_dbl(T[2], k);
-  T[5] = wjac_add_aff(T[4], R1, k);
-  T[6] = wjac_dbl(T[3], k);
-  T[7] = wjac_add_aff(T[6], R1, k);
-  T[8] = wjac_dbl(T[4], k);
-  // One common Z for the whole table ("effective affine"): with Zc = z2·z3·…·z8 and s_i = Zc / z_i, entry i is
-  // (x_i·s_i², y_i·s_i³, Zc) — the SAME Z everywhere, i.e. the affine point (x_i·s_i², y_i·s_i³) of the isomorphic
-  // curve y² = x³ + 7·Zc⁶.  The a = 0 formulas never look at the curve constant, so the main loop adds table
-  // entries with MIXED additions (11 multiplications instead of 16, 66 times) and Zc is multiplied into the
-  // accumulator's Z once, before the G additions bring it back among points of the real curve.  Prefix products
-  // forward, suffix products backward: 6 + 12 multiplications, then 4 per entry.
-  uint32_t AX[9], AY[9];
-  uint32_t Zc;
-  {
-    uint32_t pre[9];
-    pre[2] = T[2].z;
-#pragma unroll
-    for (int i = 3; i <= 7; i++) pre[i] = wfe_mul(pre[i - 1], T[i].z, k);
-    uint32_t suf = T[8].z;  // z_{i+1}·…·z8 while walking down
-#pragma unroll
-    for (int i = 8; i >= 1; i--) {
-      // s_i = (z2…z_{i-1})·(z_{i+1}…z8)
-      const uint32_t sc = i == 8 ? pre[7] : (i <= 2 ? suf : wfe_mul(pre[i - 1], suf, k));
-      const uint32_t s2 = wfe_sqr(sc, k);
-      AX[i] = wfe_mul(T[i].x, s2, k);
-      AY[i] = wfe_mul(T[i].y, wfe_mul(s2, sc, k), k);
-      if (i <= 7 && i >= 3) suf = wfe_mul(suf, T[i].z, k);  // after the step for i: suf = z_i·…·z8 (needed by i − 1)
-      if (i == 2) Zc = wfe_mul(suf, T[2].z, k);              // s_1 = z2·…·z8 = Zc: computed before the step for i = 1
-      if (i == 2) suf = Zc;
-    }
-  }
-  const uint32_t beta = scatter(secp::GLV_CONST(1), k);
-  uint32_t TX[9];
-#pragma unroll
-  for (int e = 1; e <= 8; e++) TX[e] = wfe_mul(AX[e], beta, k);
-  WV_STAGE(3, AX[3] ^ AY[5] ^ AX[6] ^ AX[7] ^ AY[8] ^ TX[2] ^ TX[8] ^ u1.v[0] ^ w1[0] ^ w2[1] ^ Zc)
-  wjac acc = wjac_inf();
-#pragma unroll 1
-  for (int jd = 32; jd >= 0; jd--) {
-    if (jd < 32) {
-#pragma unroll 1
-      for (int d = 0; d < 4; d++) acc = wjac_dbl<true>(acc, k);
-    }
-    // digit jd of both scalars (digit 32 is the carry bit, never negative)
-    const int n1 = (int)((w1[jd >> 3] >> (4 * (jd & 7))) & 15u), n2 = (int)((w2[jd >> 3] >> (4 * (jd & 7))) & 15u);
-    const int d1 = jd == 32 ? (int)(w1[4] & 1u) : n1 - 8, d2 = jd == 32 ? (int)(w2[4] & 1u) : n2 - 8;
-    const uint32_t m1 = (uint32_t)(d1 < 0 ? -d1 : d1), m2 = (uint32_t)(d2 < 0 ? -d2 : d2);
-    waff q1 = waff{AX[1], AY[1]}, q2 = waff{TX[1], AY[1]};
-#pragma unroll
-    for (int e = 2; e <= 8; e++) {
-      q1.x = m1 == (uint32_t)e ? AX[e] : q1.x;
-      q1.y = m1 == (uint32_t)e ? AY[e] : q1.y;
-      q2.x = m2 == (uint32_t)e ? TX[e] : q2.x;
-      q2.y = m2 == (uint32_t)e ? AY[e] : q2.y;
-    }
-    q1.y = ((d1 < 0) != sp.neg1) ? wfe_neg1(q1.y, k) : q1.y;  // magnitude ≤ 2
-    q2.y = ((d2 < 0) != sp.neg2) ? wfe_neg1(q2.y, k) : q2.y;
-    const wjac s1 = wjac_add_aff<true>(acc, q1, k);
-    acc = wjac_select(m1 != 0, s1, acc);
-    const wjac s2 = wjac_add_aff<true>(acc, q2, k);
-    acc = wjac_select(m2 != 0, s2, acc);
-  }
-#else
   // Tables 1..8 of R (affine start: mixed additions) and, through X·β, of λR — in wave-private LDS, built and
   // brought to ONE common Z by rolled loops: code that runs once per signature is fetched, not executed
   // (profiles/r02c_rows_stage_ms.txt: the same arithmetic written straight-line cost 0.05 ms of instruction-cache
@@ -1539,7 +1282,6 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
   }
   WV_STAGE(3, WT(0) ^ WT(7) ^ WT(23) ^ u1.v[0] ^ w1[0] ^ w2[1] ^ Zc)
   wjac acc = wjac_inf();
-#if IBFT_ROWS_PEEL
   // Digit 32 (the carry bit of the recoding, 0 or 1, never negative) outside the loop: the accumulator is still at
   // infinity, so k1's digit is a choice between T[1] and infinity, not an addition, and k2's is ONE addition that runs
   // once per signature (outlined multiply: its code is fetched, not executed).
@@ -1551,109 +1293,10 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
     const wjac s2 = wjac_add_aff(acc, waff{WT(2), sp.neg2 ? yn : y1}, k);
     acc = wjac_select((w2[4] & 1u) != 0, s2, acc);
   }
-#endif
-#if IBFT_ROWS_G_MERGED == 2
-  // The UNIFORM form (needs IBFT_ROWS_G_PREFETCH): both phases read their two operands from wave-private LDS by slot number —
-  // table entries in the window iterations, the prefetched G-table points in the fixed-base ones — so an iteration is the same
-  // instruction stream in both phases: a slot computation, 4 or 0 doublings, two additions.  No operand path of its own for the
-  // fixed-base phase, no preload logic: what the first merged form (IBFT_ROWS_G_MERGED = 1) paid the main loop.
-  static_assert(ibftk::GTAB_WINDOWS % 2 == 0 && IBFT_ROWS_G_PREFETCH, "two prefetched fixed-base windows per iteration");
-  constexpr int GIT = ibftk::GTAB_WINDOWS / 2;
-  wjac hold = wjac_inf();
 #pragma unroll 1
-  for (int it = 0; it < 32 + GIT; it++) {
-    const bool is_g = it >= 32;  // (wave-uniform)
-    const int jd = is_g ? 0 : 31 - it, g = is_g ? it - 32 : 0;
-    const int n1 = (int)((w1[jd >> 3] >> (4 * (jd & 7))) & 15u), n2 = (int)((w2[jd >> 3] >> (4 * (jd & 7))) & 15u);
-    const int d1 = n1 - 8, d2 = n2 - 8;
-    const uint32_t m1 = (uint32_t)(d1 < 0 ? -d1 : d1), m2 = (uint32_t)(d2 < 0 ? -d2 : d2);
-    const int b1 = 3 * (int)((m1 ? m1 : 1u) - 1u), b2 = 3 * (int)((m2 ? m2 : 1u) - 1u);
-    const int gs = ROW_TAB_G0 + 4 * g;
-    const int s1x = is_g ? gs : b1, s1y = is_g ? gs + 1 : b1 + 1, s2x = is_g ? gs + 2 : b2 + 2, s2y = is_g ? gs + 3 : b2 + 1;
-    if (it == 32) {
-      acc.z = wfe_mul(acc.z, Zc, k);  // back from the isomorphic curve (an accumulator at infinity keeps its flag)
-      WV_STAGE(4, acc.x ^ acc.y ^ acc.z ^ u1.v[0])
-      hold = acc;
-      acc = wjac_inf();
-      lds_prefetch_wait();  // (asked for a quarter of a millisecond ago)
-    }
-    waff q1 = waff{WT(s1x) & k.act, WT(s1y) & k.act}, q2 = waff{WT(s2x) & k.act, WT(s2y) & k.act};
-    const int ndbl = is_g ? 0 : 4;
-#pragma unroll 1
-    for (int d = 0; d < ndbl; d++) acc = wjac_dbl<true>(acc, k);
-    const bool f1 = !is_g && ((d1 < 0) != sp.neg1), f2 = !is_g && ((d2 < 0) != sp.neg2);
-    q1.y = f1 ? wfe_neg1(q1.y, k) : q1.y;  // magnitude ≤ 2
-    q2.y = f2 ? wfe_neg1(q2.y, k) : q2.y;
-    const int bit1 = (2 * g) * ibftk::GTAB_BITS, bit2 = (2 * g + 1) * ibftk::GTAB_BITS;
-    const uint32_t gd1 = (u1.v[bit1 >> 5] >> (bit1 & 31)) & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
-    const uint32_t gd2 = (u1.v[bit2 >> 5] >> (bit2 & 31)) & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
-    const bool t1 = is_g ? gd1 != 0 : m1 != 0, t2 = is_g ? gd2 != 0 : m2 != 0;
-    const wjac s1 = wjac_add_aff<true>(acc, q1, k);
-    acc = wjac_select(t1, s1, acc);
-    const wjac s2 = wjac_add_aff<true>(acc, q2, k);
-    acc = wjac_select(t2, s2, acc);
-  }
-  const wjac accg_merged = acc;
-  acc = hold;
-#elif IBFT_ROWS_G_MERGED
-  // iterations jd = 31 … 0: digit jd of both scalars (four doublings, two table additions); iterations jd = −1 … −GIT: the
-  // fixed-base windows 2g, 2g + 1 (g = −1 − jd) of u1 into an accumulator of their own — the u2·R′ sum steps aside at jd = −1.
-  // The two table points of an iteration are asked for one iteration earlier.
-  static_assert(ibftk::GTAB_WINDOWS % 2 == 0, "two fixed-base windows per iteration");
-  constexpr int GIT = ibftk::GTAB_WINDOWS / 2;
-  wjac hold = wjac_inf();
-  waff pre1 = waff{0u, 0u}, pre2 = waff{0u, 0u};
-  auto g_digit = [&](int win) -> uint32_t {
-    const int bit = win * ibftk::GTAB_BITS;
-    return (u1.v[bit >> 5] >> (bit & 31)) & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
-  };
-#pragma unroll 1
-  for (int jd = 31; jd >= -GIT; jd--) {
-    waff q1, q2;
-    bool t1, t2;
-    if (jd >= 0) {  // (wave-uniform)
-      const int n1 = (int)((w1[jd >> 3] >> (4 * (jd & 7))) & 15u), n2 = (int)((w2[jd >> 3] >> (4 * (jd & 7))) & 15u);
-      const int d1 = n1 - 8, d2 = n2 - 8;
-      const uint32_t m1 = (uint32_t)(d1 < 0 ? -d1 : d1), m2 = (uint32_t)(d2 < 0 ? -d2 : d2);
-      const int e1 = 3 * (int)((m1 ? m1 : 1u) - 1u), e2 = 3 * (int)((m2 ? m2 : 1u) - 1u);
-      q1 = waff{WT(e1), WT(e1 + 1)};  // (read before the doublings that hide the latency)
-      q2 = waff{WT(e2 + 2), WT(e2 + 1)};
-#pragma unroll 1
-      for (int d = 0; d < 4; d++) acc = wjac_dbl<true>(acc, k);
-      q1.y = ((d1 < 0) != sp.neg1) ? wfe_neg1(q1.y, k) : q1.y;  // magnitude ≤ 2
-      q2.y = ((d2 < 0) != sp.neg2) ? wfe_neg1(q2.y, k) : q2.y;
-      t1 = m1 != 0;
-      t2 = m2 != 0;
-    } else {
-      if (jd == -1) {
-        acc.z = wfe_mul(acc.z, Zc, k);  // back from the isomorphic curve (an accumulator at infinity keeps its flag)
-        WV_STAGE(4, acc.x ^ acc.y ^ acc.z ^ u1.v[0])
-        hold = acc;
-        acc = wjac_inf();
-      }
-      const int g = -1 - jd;
-      q1 = pre1;
-      q2 = pre2;
-      t1 = g_digit(2 * g) != 0;
-      t2 = g_digit(2 * g + 1) != 0;
-    }
-    if (jd <= 0 && jd > -GIT) {  // the two points of the NEXT iteration: on their way while this one's additions run
-      const int g = -jd;
-      pre1 = load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * ((size_t)(2 * g) * ibftk::GTAB_ENTRIES + g_digit(2 * g)), k);
-      pre2 = load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * ((size_t)(2 * g + 1) * ibftk::GTAB_ENTRIES + g_digit(2 * g + 1)), k);
-    }
-    const wjac s1 = wjac_add_aff<true>(acc, q1, k);
-    acc = wjac_select(t1, s1, acc);
-    const wjac s2 = wjac_add_aff<true>(acc, q2, k);
-    acc = wjac_select(t2, s2, acc);
-  }
-  const wjac accg_merged = acc;
-  acc = hold;
-#else
-#pragma unroll 1
-  for (int jd = IBFT_ROWS_PEEL ? 31 : 32; jd >= 0; jd--) {
-    // digit jd of both scalars (digit 32 is the carry bit, never negative); the table reads are issued before the
-    // doublings that hide their latency
+  for (int jd = 31; jd >= 0; jd--) {
+    // digit jd of both scalars; the table reads are issued before the doublings that hide their latency.  The jd == 32 and
+    // jd < 32 tests are constant (digit 32 is peeled above) but stay: without them this compiler schedules the loop differently.
     const int n1 = (int)((w1[jd >> 3] >> (4 * (jd & 7))) & 15u), n2 = (int)((w2[jd >> 3] >> (4 * (jd & 7))) & 15u);
     const int d1 = jd == 32 ? (int)(w1[4] & 1u) : n1 - 8, d2 = jd == 32 ? (int)(w2[4] & 1u) : n2 - 8;
     const uint32_t m1 = (uint32_t)(d1 < 0 ? -d1 : d1), m2 = (uint32_t)(d2 < 0 ? -d2 : d2);
@@ -1665,85 +1308,33 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
     }
     q1.y = ((d1 < 0) != sp.neg1) ? wfe_neg1(q1.y, k) : q1.y;  // magnitude ≤ 2
     q2.y = ((d2 < 0) != sp.neg2) ? wfe_neg1(q2.y, k) : q2.y;
-#if IBFT_ROWS_SHARED_ADDS
-    acc = rows_two_adds(acc, q1, q2, m1 != 0, m2 != 0, k);
-#else
     const wjac s1 = wjac_add_aff<true>(acc, q1, k);
     acc = wjac_select(m1 != 0, s1, acc);
     const wjac s2 = wjac_add_aff<true>(acc, q2, k);
     acc = wjac_select(m2 != 0, s2, acc);
-#endif
   }
-#endif  // IBFT_ROWS_G_MERGED
 #undef WT
-#endif
-#if IBFT_ROWS_G_MERGED
-  const wjac accg = accg_merged;
-#else
   acc.z = wfe_mul(acc.z, Zc, k);  // back from the isomorphic curve (an accumulator at infinity keeps its flag)
   WV_STAGE(4, acc.x ^ acc.y ^ acc.z ^ u1.v[0])
-  // u1·G: all the fixed-base windows in this row — into the accumulator itself, or (deferred √) into one of its own: the
-  // table points are points of the curve, the accumulator still lives on the isomorphic one
-#if IBFT_ROWS_DEFER_SQRT
+  // u1·G: all the fixed-base windows in this row, into an accumulator of its own: the table points are points of the curve,
+  // the accumulator still lives on the isomorphic one
   wjac accg = wjac_inf();
-#else
-  wjac &accg = acc;
-#endif
-#if IBFT_ROWS_G_PREFETCH
-  lds_prefetch_wait();  // (issued a quarter of a millisecond ago)
-  const uint32_t gl_ = lane_id();
-#define WV_GPOINT(win) waff{wtab[(ROW_TAB_G0 + 2 * (win)) * 64 + gl_] & k.act, wtab[(ROW_TAB_G0 + 2 * (win) + 1) * 64 + gl_] & k.act}
-#else
-#define WV_GPOINT(win) load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * ((size_t)(win) * ibftk::GTAB_ENTRIES + dgt), k)
-#endif
-#if IBFT_ROWS_SHARED_ADDS
-  // two windows per step through the main loop's own pair of additions (rows_two_adds); the two table points of the next
-  // step are asked for before this step's additions run
-  {
-    static_assert(ibftk::GTAB_WINDOWS % 2 == 0, "two fixed-base windows per step");
-    auto g_digit = [&](int win) -> uint32_t {
-      const int bit = win * ibftk::GTAB_BITS;
-      return (u1.v[bit >> 5] >> (bit & 31)) & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
-    };
-    auto g_point = [&](int win) -> waff {
-      return load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * ((size_t)win * ibftk::GTAB_ENTRIES + g_digit(win)), k);
-    };
-    waff c1 = g_point(0), c2 = g_point(1);
-#pragma unroll 1
-    for (int g = 0; g < ibftk::GTAB_WINDOWS / 2; g++) {
-      const int gn = g + 1 < ibftk::GTAB_WINDOWS / 2 ? g + 1 : g;  // (the last step re-reads its own points)
-      const waff n1 = g_point(2 * gn), n2 = g_point(2 * gn + 1);
-      accg = rows_two_adds(accg, c1, c2, g_digit(2 * g) != 0, g_digit(2 * g + 1) != 0, k);
-      c1 = n1;
-      c2 = n2;
-    }
-  }
-#else
-#if IBFT_ROWS_PEEL && IBFT_ROWS_DEFER_SQRT
   // window 0 into an accumulator at infinity is the table point itself (or still infinity for a zero digit)
   {
     const uint32_t dgt = u1.v[0] & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
-    const waff pt = WV_GPOINT(0);
+    const waff pt = load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * dgt, k);
     accg = wjac_select(dgt != 0, wjac_from_aff(pt, k), accg);
   }
-#endif
 #pragma unroll 1
-  for (int win = (IBFT_ROWS_PEEL && IBFT_ROWS_DEFER_SQRT) ? 1 : 0; win < ibftk::GTAB_WINDOWS; win++) {
+  for (int win = 1; win < ibftk::GTAB_WINDOWS; win++) {
     const int bit = win * ibftk::GTAB_BITS;
     const uint32_t dgt = (u1.v[bit >> 5] >> (bit & 31)) & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
-    const waff pt = WV_GPOINT(win);
+    const waff pt = load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * ((size_t)win * ibftk::GTAB_ENTRIES + dgt), k);
     const wjac sum = wjac_add_aff<true>(accg, pt, k);
     accg = wjac_select(dgt != 0, sum, accg);
   }
-#endif  // IBFT_ROWS_SHARED_ADDS
-#undef WV_GPOINT
-#endif  // IBFT_ROWS_G_MERGED
   WV_STAGE(5, acc.x ^ acc.y ^ acc.z ^ accg.x ^ accg.z)
-#if IBFT_ROWS_DEFER_SQRT
   ok = rows_finish_deferred(Qa, accg, acc, rhs, v, k) && ok;
-#else
-  ok = wjac_to_aff(Qa, acc, k) && ok;
-#endif
   WV_STAGE(6, Qa.x.n[0] ^ Qa.y.n[1])
   u256 qx = secp::l26_to_u256(Qa.x), qy = secp::l26_to_u256(Qa.y);
   keccak::address_from_xy(qx.v, qy.v, addr);
