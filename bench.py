@@ -28,8 +28,12 @@ Inputs are resident in HBM when the timed region starts.
   region are the library's own stream syncs (ibft_sync: verdict, exchange and copy streams) — torch's streams never carried
   any of this work.  Every rank pins itself to its GPU's NUMA node first (go_ibft_amd/numa.py: 0.333 vs 0.345 ms per kernel).
 
-Rank 0 prints TWO JSON lines: first the detail record ({"bench_detail": …}: sweep with counters, sequence forms, host-mirror
-legs, certificates — also written to gpurun_out/bench_detail.json), then, LAST on stdout and under 6 KB, the headline line the
+A plain run (`--gpus N --steps K --warmup W`) does what the headline needs and nothing else: set up, warm up, time the K steps,
+write --dump-outputs, print ONE JSON line (metric, value, ms_per_step, config, the roofline of the timed steps' own HIP-event
+kernel samples with the committed counter files attached).  Everything else the benchmark measures runs with --full.
+
+With --full, rank 0 prints TWO JSON lines: first the detail record ({"bench_detail": …}: sweep with counters, sequence forms,
+host-mirror legs, certificates — also written to DETAIL_PATH), then, LAST on stdout and under 6 KB, the headline line the
 driver parses (metric, value, config, quorum latency, roofline with the VALU-issue bound, cpu_baseline).
 """
 from __future__ import annotations
@@ -269,14 +273,14 @@ def _attachment_files(suffix: str):
     return live + sorted(glob.glob(os.path.join(ROOT, "profiles", f"r*_{suffix}")), reverse=True)
 
 
-LIVE_BUDGET_S = 200   # the default run's counter sub-steps are abandoned after this long (the line then attaches the committed files)
+LIVE_BUDGET_S = 200   # a --full run's counter sub-steps are abandoned after this long (the line then attaches the committed files)
 
 
 def collect_live_counters(rows: int, lean: bool) -> tuple[str | None, dict]:
     """The rocprofv3 passes of tools/profile.sh (kernel stats, FETCH_SIZE, WRITE_SIZE: separate runs) and tools/pmc_wave.sh
     (instruction counters, one counter set per run) as sub-steps of THIS run, over the same command line they always use; their
-    summaries land in gpurun_out/profiles/live_n<rows>_* and are what this line then attaches.  lean (the default run, round 6:
-    the driver's own line must carry counters from the driver's own box): the headline stats pass, the two traffic passes and
+    summaries land in the output directory's profiles/live_n<rows>_* and are what this line then attaches.  lean (a --full run:
+    its line carries counters from its own box): the headline stats pass, the two traffic passes and
     two counter sets — five short processes, ≈ 40 s; --profile: the full series (≈ 2 minutes).  Returns (tag or None, what happened)."""
     import shutil
     info = {"mode": "lean" if lean else "full"}
@@ -764,11 +768,11 @@ def _r(x, nd=6):
     return x
 
 
-def headline_record(rec: dict) -> dict:
+def headline_record(rec: dict, detail: bool = True) -> dict:
     """The driver's line: SURVEY §8d's quantities and nothing else — metric / value / config, quorum latency, the roofline of the
     dominant kernel with the VALU-issue bound that applies, the CPU baseline; one number per sweep size.  Everything else
     (sweep with counters, extended sample, sequence forms, set change, certificates, host-mirror legs, prose) is the DETAIL
-    record: gpurun_out/bench_detail.json and an EARLIER stdout line."""
+    record: DETAIL_PATH and an EARLIER stdout line (detail = False: a plain run, which writes neither)."""
     out = {k: rec[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                "scaling", "vs_baseline", "dtype", "data") if k in rec}
     cfg = rec.get("config", {})
@@ -824,7 +828,8 @@ def headline_record(rec: dict) -> dict:
     if rec.get("dry_run"):
         out["dry_run"] = True
     out["parity"] = "numerics unpinned by the reference (DESIGN.md §3): verdicts checked against the CPU oracle"
-    out["detail"] = "gpurun_out/bench_detail.json (also the previous stdout line)"
+    if detail:
+        out["detail"] = os.path.relpath(DETAIL_PATH, ROOT) + " (also the previous stdout line)"
     out = _r(out)
     # never let an extra take the line over the limit: drop optional objects, widest first
     for k in ("sweep", "sweep_columns", "small_n", "warm_path", "config5", "sustained_incl_h2d", "build", "parity", "sharded_sweep_columns",
@@ -850,17 +855,19 @@ def dump_outputs(out_dir: str, verdict, tally) -> None:
     np.save(os.path.join(out_dir, "tally.npy"), np.asarray(words, dtype=np.float64))
 
 
-def emit(rec: dict) -> str:
-    """detail record → gpurun_out/bench_detail.json + one stdout line; then the headline line, LAST on stdout"""
-    try:
-        os.makedirs(os.path.dirname(DETAIL_PATH), exist_ok=True)
-        with open(DETAIL_PATH, "w") as f:
-            json.dump(rec, f)
-    except OSError:
-        pass
-    line = json.dumps(headline_record(rec))
+def emit(rec: dict, detail: bool = True) -> str:
+    """detail (--full): the detail record → DETAIL_PATH + one stdout line; then the headline line, LAST on stdout"""
+    if detail:
+        try:
+            os.makedirs(os.path.dirname(DETAIL_PATH), exist_ok=True)
+            with open(DETAIL_PATH, "w") as f:
+                json.dump(rec, f)
+        except OSError:
+            pass
+    line = json.dumps(headline_record(rec, detail))
     assert len(line) < LINE_LIMIT, len(line)
-    print(json.dumps({"bench_detail": rec}), flush=True)
+    if detail:
+        print(json.dumps({"bench_detail": rec}), flush=True)
     print(line, flush=True)
     return line
 
@@ -882,10 +889,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rows", type=int, default=ROWS_PER_GPU, help="rows (validators) per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: the extended sample, step latencies, the device canary, "
+                         "rocprofv3 counters of this run, the warm path, the config-#3 sequence, the sweep, the sustained, "
+                         "small-N, set-change, certificate and host-mirror legs, the CPU baseline, at N > 1 the sharded sweep, "
+                         "and the detail record.  The --no-* options below leave legs of a --full run out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile", action="store_true",
-                    help="N = 1: the FULL series of rocprofv3 sub-steps (tools/profile.sh, tools/pmc_wave.sh; ≈2 minutes).  Without "
-                         "it the run still collects roofline.traffic / valu_issue itself with a lean series (≈40 s)")
+                    help="N = 1: the FULL series of rocprofv3 sub-steps (tools/profile.sh, tools/pmc_wave.sh; ≈2 minutes); implies "
+                         "--full.  Without it a --full run still collects roofline.traffic / valu_issue itself with a lean series (≈40 s)")
     ap.add_argument("--no-live-counters", action="store_true",
                     help="no rocprofv3 sub-steps at all: attach the committed profiles/ files (what the sub-steps themselves run with)")
     ap.add_argument("--no-sequence", action="store_true", help="skip the config-#3 sequence latency legs")
@@ -903,6 +915,10 @@ def main():
                     help="cold = ECDSA recover+compare for every row (headline); warm = keys already learned, "
                          "rows verified against per-validator tables (IBFT_FLAG_PUBKEY_CACHE)")
     args = ap.parse_args()
+    args.full = args.full or args.profile
+    if not args.full:   # a plain run: the headline's own steps and nothing else
+        args.no_live_counters = args.no_warm = args.no_sequence = args.no_sweep = args.no_sustained = True
+        args.no_certificates = args.no_host_mirror = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch(args))
@@ -961,10 +977,11 @@ def main():
 
     import go_ibft_amd.shard as S
 
-    def run_config(rows: int, byzantine: bool, steps: int, warmup: int, path: str, keep=None):
+    def run_config(rows: int, byzantine: bool, steps: int, warmup: int, path: str, keep=None, extras: bool = True):
         """one timed leg: `steps` passes over this rank's resident shard (+ the exchange when sharded).
         keep: a dict that carries the context and the resident batch from one leg to the next (a node keeps its context for
-        its lifetime: the K-step leg runs on the context the extended leg has been using, not on a minute-old one)"""
+        its lifetime: the K-step leg runs on the context the extended leg has been using, not on a minute-old one).
+        extras: the step latencies and the device canary behind the timed passes (none of them feeds value or ms_per_step)"""
         n_total = rows * world
         lo, hi = rank * rows, (rank + 1) * rows
         if keep is not None and "bv" in keep:
@@ -1071,6 +1088,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
             kernel_ms, kernel_launches = bv.last_kernel_ms()  # the last pass's kernels (events are per launch)
+        if dist is not None and extras:
             for k in range(min(steps, 20)):                   # latency of one synchronous pass incl. the exchange
                 s0 = time.perf_counter()
                 bv.seals_launch(1)
@@ -1078,14 +1096,14 @@ def main():
                 bv.seals_fetch_merged()
                 lat.append(time.perf_counter() - s0)
         # the synchronous round trip of ONE pass (launch → verdict kernel → tally → results on the host), outside the timed region
-        if dist is None:
+        if dist is None and extras:
             for _ in range(min(max(steps, 20), 100)):
                 s0 = time.perf_counter()
                 step()
                 lat.append(time.perf_counter() - s0)
         # quorum latency of this one call including the host→device copies
         lat_h2d = []
-        if dist is None:
+        if dist is None and extras:
             for _ in range(min(steps, 200)):
                 s0 = time.perf_counter()
                 bv.is_valid_committed_seal(rd["hash32"], rd["seal65"], rd["signer20"], rd["pre"])
@@ -1117,7 +1135,7 @@ def main():
             bv.cache_stats()
             warm_lanes = bv.lanes_per_signature
         canary = None
-        if not DRY_RUN and hasattr(bv, "issue_probe"):
+        if extras and not DRY_RUN and hasattr(bv, "issue_probe"):
             try:      # the device canary right behind the timed passes (clocks up): ns per aligned VALU instruction per SIMD
                 canary = bv.issue_probe()
             except Exception as e:  # noqa: BLE001 — a diagnostic: its failure is recorded, nothing else
@@ -1140,10 +1158,14 @@ def main():
     # the driver's K may be small (20 steps = 5 kernel-time samples): a second, longer sample of the same leg, reported
     # NEXT TO the K-step one (value / ms_per_step stay the K-step numbers the contract asks for).  It runs FIRST: the first
     # launches after a process start run ≈4 % slower (the r03a line: kernel 0.459 ms in a 20-step leg right after start-up,
-    # 0.440 ms over the following 400 steps), and a steady-state throughput is what the metric means.
+    # 0.440 ms over the following 400 steps), and a steady-state throughput is what the metric means.  So a plain run keeps
+    # this leg, with what runs behind its timed passes, in front of the headline leg as its settle phase and leaves its numbers
+    # out (--full reports them as `extended`): the headline is measured behind the same work as before.  Without that work the
+    # headline step came out 0.7 % shorter at the same kernel time (0.3400 against 0.3425 ms, three runs each, alternating with
+    # the bench.py before --full); with it 0.3407 against 0.3422, inside that bench.py's own spread (0.3411 … 0.3442 ms).
     carry = {} if (world == 1 and args.extended_steps > 0) else None
     long_leg = run_config(args.rows, False, args.extended_steps, 10, args.path, keep=carry) if carry is not None else None
-    main_leg = run_config(args.rows, False, args.steps, args.warmup, args.path, keep=carry)
+    main_leg = run_config(args.rows, False, args.steps, args.warmup, args.path, keep=carry, extras=args.full)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, *main_leg["out"])
 
@@ -1157,8 +1179,8 @@ def main():
         live_info = None
         if world == 1 and dist is None and not DRY_RUN and not args.no_live_counters and args.path == "cold" and \
                 os.environ.get("IBFT_BENCH_NO_LIVE") != "1":
-            # (behind the timed legs: the sub-steps are processes of their own.  Round 6: the DEFAULT, so that the line the
-            # driver parses carries counters collected on the driver's own box in the driver's own run)
+            # (behind the timed legs: the sub-steps are processes of their own.  --full only: a plain run attaches the
+            # committed profiles/ files and starts no process of its own)
             LIVE_TAG, live_info = collect_live_counters(rows, lean=not args.profile)
         traffic, valu = profile_attachments(m["kname"], rows, avg_kernel_s)
         live_traffic = live_valu = False
@@ -1187,8 +1209,8 @@ def main():
                                    "IBFT_SIDE_TALLY=0 turns that off); N > 1: exchange k overlaps the kernels of pass k+1); "
                                    "step_latency_ms_p50 = one synchronous pass",
                        "numa_pin": numa_pin},
-            "step_latency_ms_p50": float(np.median(m["lat"]) * 1e3),
-            "step_latency_ms_p50_incl_h2d": float(np.median(m["lat_h2d"]) * 1e3) if m["lat_h2d"] else None,
+            **({"step_latency_ms_p50": float(np.median(m["lat"]) * 1e3),
+                "step_latency_ms_p50_incl_h2d": float(np.median(m["lat_h2d"]) * 1e3) if m["lat_h2d"] else None} if m["lat"] else {}),
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "kernel": m["kname"], "avg_kernel_ms": avg_kernel_s * 1e3, "kernel_samples": m["kernel_launches"],
@@ -1211,7 +1233,8 @@ def main():
         rp = rocprof_avg_kernel_ms(m["kname"])
         if rp:   # the rocprofv3 --kernel-trace --stats average of the same kernel in this run's own sub-step
             rec["roofline"]["rocprof_avg_kernel_ms"], rec["roofline"]["rocprof_calls"] = rp
-        rec["quorum_latency_ms_p50"] = rec["step_latency_ms_p50"]   # replaced by the sequence below at N=1
+        if m["lat"]:
+            rec["quorum_latency_ms_p50"] = rec["step_latency_ms_p50"]   # replaced by the sequence below at N=1
         if DRY_RUN:
             rec["dry_run"] = True
             rec["data"] = "DRY RUN (IBFT_BENCH_DRYRUN=1): CPU ranks, stub verifier — plumbing only, NOT a measurement"
@@ -1232,7 +1255,7 @@ def main():
                                             "throughput figure of this line is then off by about as much (DESIGN.md §5.8)"}
         elif m.get("canary") is not None:
             rec["device_canary"] = {"error": m["canary"]}
-        if long_leg is not None:
+        if long_leg is not None and args.full:
             L = long_leg
             lk = (L["kernel_ms"] / 1e3) / max(L["kernel_launches"], 1)
             rec["extended"] = {"steps": L["steps"], "value": L["n_total"] * L["steps"] / L["elapsed"],
@@ -1323,14 +1346,15 @@ def main():
             rec.setdefault("quorum_latency", {})["host_mirror_from_wire"] = hm
         except Exception as e:  # noqa: BLE001
             rec.setdefault("quorum_latency", {})["host_mirror_from_wire"] = {"error": repr(e)}
-    if dist is not None and (world > 1 or os.environ.get("IBFT_BENCH_CONFIG5") == "1" or os.environ.get("IBFT_BENCH_SHARDED_SWEEP") == "1") \
+    if dist is not None and ((world > 1 and args.full) or os.environ.get("IBFT_BENCH_CONFIG5") == "1" or os.environ.get("IBFT_BENCH_SHARDED_SWEEP") == "1") \
             and os.environ.get("IBFT_BENCH_SKIP_SHARDED_SWEEP") != "1" and os.environ.get("IBFT_BENCH_SKIP_CONFIG5") != "1":
         # north star: "sig-verifies/sec on synthetic rounds of N ∈ {64 … 65 536} validators reported at 1/2/4/8 GPUs".  Beyond
         # one GPU's share of the headline (4 096 rows per rank) the line carries a SHARDED SWEEP: N_total ∈ {16 384, 65 536}
         # split over the ranks in 64-aligned shards — BASELINE config #4 falls out of it at G = 4 (16 384 validators, all
         # valid) and config #5 at G = 8 (65 536 validators, 20 % Byzantine seals, every rank's shard of the merged mask held
         # against the CPU oracle outside the timed region).  With IBFT_BENCH_FORCE_DIST=1 on one GPU the same legs run as ONE
-        # shard through the sharded code path and a real one-rank RCCL communicator.
+        # shard through the sharded code path and a real one-rank RCCL communicator.  At world > 1 the sweep is part of
+        # --full; IBFT_BENCH_SHARDED_SWEEP=1 / IBFT_BENCH_CONFIG5=1 ask for it by name in any run.
         # These legs meet a multi-GPU node for the first time in the driver's run: should a rank stall (a collective one rank
         # never reaches), the headline line — complete by now — must still go out.  A timer on every rank ends the process;
         # rank 0 prints the line first, with the stall recorded.
@@ -1347,7 +1371,7 @@ def main():
             if rank == 0:
                 sweep_out.append({"error": f"no result within {CONFIG5_TIMEOUT_S} s (leg abandoned, headline unaffected)"})
                 sys.stdout.flush()
-                emit(rec)
+                emit(rec, args.full)
             os._exit(0)
         watchdog = threading.Timer(CONFIG5_TIMEOUT_S, give_up)
         watchdog.daemon = True
@@ -1393,7 +1417,7 @@ def main():
         import ctypes
         sys.stdout.flush()
         ctypes.CDLL(None).fflush(None)
-        emit(rec)
+        emit(rec, args.full)
 
 
 if __name__ == "__main__":

@@ -77,7 +77,7 @@ def _run_bench(args, env_extra, timeout=600):
 
 
 def test_dry_run_one_rank_prints_detail_then_headline():
-    lines = _run_bench(["--steps", "6", "--warmup", "2", "--extended-steps", "8"], {})
+    lines = _run_bench(["--full", "--steps", "6", "--warmup", "2", "--extended-steps", "8"], {})
     rec = _check_headline(lines[-1], 1)
     assert rec["dry_run"] is True and "DRY RUN" in rec["data"] and rec["steps"] == 6 and rec["warmup"] == 2
     detail = _strict(lines[-2])["bench_detail"]
@@ -92,7 +92,7 @@ def test_dry_run_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
     got = []
     for k, steps in enumerate((3, 7)):
         d = tmp_path / f"run{k}"
-        lines = _run_bench(["--steps", str(steps), "--warmup", "1", "--extended-steps", "0", "--dump-outputs", str(d)], {})
+        lines = _run_bench(["--full", "--steps", str(steps), "--warmup", "1", "--extended-steps", "0", "--dump-outputs", str(d)], {})
         rec = _check_headline(lines[-1], 1)
         assert rec["steps"] == steps and rec["ms_per_step"] > 0
         assert sorted(os.listdir(d)) == ["tally.npy", "verdict.npy"]
@@ -104,6 +104,35 @@ def test_dry_run_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
     assert (got[0][0] == got[1][0]).all() and (got[0][1] == got[1][1]).all()
 
 
+PLAIN = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline")
+FULL_ONLY = ("extended", "device_canary", "step_latency_ms_p50", "quorum_latency_ms_p50", "warm_path", "sweep", "small_n",
+             "sustained_incl_h2d", "cpu_baseline", "sharded_sweep", "config5", "detail")
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_dry_run_plain_run_prints_the_headline_and_nothing_else(world, tmp_path):
+    """without --full a run sets up, warms up, times the steps, dumps and prints ONE line: the headline quantities, none of the
+    legs --full adds, no detail record; its dumped outputs are those of a --full run with the same arguments"""
+    import numpy as np
+    import bench
+    detail_path = bench.DETAIL_PATH
+    before = os.stat(detail_path).st_mtime_ns if os.path.exists(detail_path) else None
+    args = ["--gpus", str(world), "--steps", "5", "--warmup", "1"]
+    lines = [l for l in _run_bench(args + ["--dump-outputs", str(tmp_path / "plain")], {}) if l.startswith("{")]
+    assert len(lines) == 1                                     # (gloo's own chatter at world > 1 aside)
+    rec = _strict(lines[0])
+    assert len(lines[0]) < 6144 and all(k in rec for k in PLAIN) and not any(k in rec for k in FULL_ONLY)
+    assert rec["metric"] == "committed_seal_verifies_per_sec" and rec["unit"] == "verifies/s" and rec["dtype"] == "u32"
+    assert rec["higher_is_better"] is True and rec["n_gpus"] == world and rec["steps"] == 5 and rec["warmup"] == 1
+    assert rec["value"] == pytest.approx(4096 * world * 5 / (rec["ms_per_step"] * 5e-3), rel=1e-3)
+    assert rec["config"]["validators"] == 4096 * world and rec["roofline"]["kernel"] == rec["config"]["kernel"]
+    assert (os.stat(detail_path).st_mtime_ns if os.path.exists(detail_path) else None) == before
+    full = _run_bench(args + ["--full", "--dump-outputs", str(tmp_path / "full")], {})
+    assert "sharded_sweep" in _strict(full[-1]) if world > 1 else "extended" in _strict(full[-2])["bench_detail"]
+    for name in ("verdict.npy", "tally.npy"):
+        assert (np.load(tmp_path / "plain" / name) == np.load(tmp_path / "full" / name)).all()
+
+
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_dry_run_gpus_n_relaunches_shards_exchanges_and_merges(world):
     """`python bench.py --gpus N` from a bare shell → N ranks under torch.distributed.run; every rank verifies its 64-aligned
@@ -111,7 +140,7 @@ def test_dry_run_gpus_n_relaunches_shards_exchanges_and_merges(world):
     env = {k: "" for k in ()}
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         assert k not in os.environ
-    lines = _run_bench(["--gpus", str(world), "--steps", "5", "--warmup", "1"], env)
+    lines = _run_bench(["--full", "--gpus", str(world), "--steps", "5", "--warmup", "1"], env)
     rec = _check_headline(lines[-1], world)
     assert rec["dry_run"] is True and rec["rccl_nranks"] == world
     assert rec["config"]["validators"] == 4096 * world and rec["config"]["rows_per_gpu"] == 4096

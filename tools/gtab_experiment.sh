@@ -12,10 +12,10 @@ P='import sys,json; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); w=r
 for lib in "" go-ibft_amd/csrc/libibftgpu_g8.so; do
   echo "== G table: ${lib:-16-bit windows, 84 MB (product)}"
   for n in 1024 4096; do
-    IBFT_GPU_LIB=$lib python $ROOT/bench.py --rows $n --steps 100 --warmup 10 --no-cpu-baseline --no-sequence | python -c "$P"
+    IBFT_GPU_LIB=$lib python $ROOT/bench.py --full --rows $n --steps 100 --warmup 10 --no-cpu-baseline --no-sequence | python -c "$P"
   done
   cd /tmp
-  timeout 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/f${lib:+8}" -o f --output-format csv -- env IBFT_GPU_LIB=$lib python $ROOT/bench.py --rows 4096 --steps 20 --warmup 3 --no-cpu-baseline --no-sequence > "$OUT/f.log" 2>&1
+  timeout 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/f${lib:+8}" -o f --output-format csv -- env IBFT_GPU_LIB=$lib python $ROOT/bench.py --full --rows 4096 --steps 20 --warmup 3 --no-cpu-baseline --no-sequence > "$OUT/f.log" 2>&1
   cd "$ROOT"
   python - "$OUT/f${lib:+8}" <<'PY'
 import csv, glob, os, sys

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/lease_pmc_$TAG
 mkdir -p "$OUT"
 { timeout 60 tools/scatter_probe | grep -E "loop body +(16|48|64|96) KB +wavefronts +1024"; timeout 120 python tools/table_ab.py 16384 65536 2>/dev/null | grep -E "lds"; } > gpurun_out/profiles/${TAG}_lease_pmc.txt 2>&1
 export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --rows 65536 --steps 12 --warmup 2 --no-cpu-baseline --no-sequence --no-sweep --no-sustained --no-certificates --no-host-mirror --no-warm --extended-steps 0"
+CMD="python $ROOT/bench.py --full --rows 65536 --steps 12 --warmup 2 --no-cpu-baseline --no-sequence --no-sweep --no-sustained --no-certificates --no-host-mirror --no-warm --extended-steps 0"
 cd /tmp
 rocprofv3 -L > "$OUT/list.txt" 2>&1
 for set in "SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES" "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES" "SQC_DCACHE_REQ SQC_DCACHE_HITS SQC_DCACHE_MISSES" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM" "SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES" "SQC_TC_INST_REQ SQC_TC_DATA_READ_REQ" "SQ_IFETCH_LEVEL" "SQC_ICACHE_MISSES_DUPLICATE" "SQ_INST_LEVEL_VMEM SQ_INSTS_VMEM_RD SQ_INSTS_LDS"; do

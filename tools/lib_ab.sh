@@ -5,7 +5,7 @@ OLD=$1; NEW=$2; R=${3:-3}
 for i in $(seq 1 $R); do
   for which in old new; do
     lib=$OLD; [ $which = new ] && lib=$NEW
-    IBFT_GPU_LIB=$lib timeout 300 python bench.py --no-cpu-baseline --no-host-mirror --no-certificates --no-sequence --extended-steps 200 2>/dev/null | python -c "
+    IBFT_GPU_LIB=$lib timeout 300 python bench.py --full --no-cpu-baseline --no-host-mirror --no-certificates --no-sequence --extended-steps 200 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().split('\n')[-1])
 sw=' '.join('%d:%.4f/%.4f'%(e['validators'],e['cold']['kernel_ms'],e['warm']['kernel_ms']) for e in r['sweep']['sizes'])

@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY -d "$OUT/dev" -o p --output-format csv -- python $ROOT/tools/rows_stages.py 4096 > "$OUT/dev.log" 2>&1
-timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY -d "$OUT/prod" -o p --output-format csv -- python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-sequence --no-warm > "$OUT/prod.log" 2>&1
+timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY -d "$OUT/prod" -o p --output-format csv -- python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-sequence --no-warm > "$OUT/prod.log" 2>&1
 cd "$ROOT"
 python - <<'PY'
 import csv, glob, os

@@ -5,7 +5,7 @@
 #   pass 1: --kernel-trace --stats           (per-kernel average duration; includes the config-#3 sequence kernels)
 #   pass 2: --pmc FETCH_SIZE                 (own run: counters never share a run with traces)
 #   pass 3: --pmc WRITE_SIZE
-# LEAN=1 (bench.py's default run, round 6: the counters of the driver's own line come from the driver's own box): the
+# LEAN=1 (bench.py --full, round 6: the counters of that run's line come from its own box): the
 # headline stats pass and the two traffic passes only, shorter legs, 90 s per pass at most.
 set -u
 TAG=${1:-r03}
@@ -18,7 +18,7 @@ export TMPDIR=/tmp
 # the headline leg only: the sequence legs launch the same kernel over 8 192 rows (a COMMIT set), which would mix two
 # launch shapes into one per-kernel average; their kernels are summarised by a second stats pass (…_seq_kernel_stats.csv)
 LEAN=${LEAN:-0}
-COMMON="--no-live-counters --no-cpu-baseline --no-sweep --no-sustained --no-certificates --no-host-mirror --extended-steps 0"
+COMMON="--full --no-live-counters --no-cpu-baseline --no-sweep --no-sustained --no-certificates --no-host-mirror --extended-steps 0"
 CMD="python $ROOT/bench.py --rows $ROWS --steps 50 --warmup 5 --no-sequence $COMMON"
 SEQ="python $ROOT/bench.py --rows $ROWS --steps 10 --warmup 2 --no-warm --seq-rounds 30 $COMMON"
 PMC="python $ROOT/bench.py --rows $ROWS --steps 30 --warmup 3 --no-sequence $COMMON"
