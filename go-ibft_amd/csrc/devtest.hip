@@ -361,3 +361,84 @@ extern "C" int devtest_rows_repeat_ms(int n, const uint8_t *dig, const uint8_t *
   (void)hipFree(dd); (void)hipFree(ds); (void)hipFree(dout); (void)hipFree(dg);
   return rc;
 }
+
+// ---- the rows pair (recover_pubkey_row<…, PAIR> + recover_helper_row): where each wavefront's time goes ----
+// The product kernel's shape (four main wavefronts, their helpers w + 4, one workgroup per compute unit); the pair's barriers
+// go through a SYNC that stamps s_memrealtime (100 MHz) on each side.  Per wavefront, 8 u64 in `stamps`: [0] start,
+// [1] [2] barrier 1 reached / left, [3] [4] barrier 2 reached / left, [5] end.  Stamps go to this buffer only.
+struct stamp_sync {
+  uint64_t *st;
+  uint32_t *cnt;  // (LDS, this wavefront's: how many barriers it has passed)
+  __device__ void operator()() const {
+    const uint64_t a = __builtin_amdgcn_s_memrealtime();
+    __syncthreads();
+    const uint64_t b = __builtin_amdgcn_s_memrealtime();
+    if (__lane_id() == 0) {
+      const uint32_t i = *cnt;
+      st[1 + 2 * i] = a;
+      st[2 + 2 * i] = b;
+      *cnt = i + 1;
+    }
+  }
+};
+__global__ void __launch_bounds__(512) devtest_rows_pair_kernel(const uint32_t *gtab, const uint8_t *dig, const uint8_t *sig65,
+                                                              uint32_t n, uint8_t *out, uint64_t *stamps) {
+  __shared__ uint32_t row_tab[4][wv::ROW_TAB_SLOTS * 64];
+  __shared__ wv::rows_pair_shared sh[4];
+  __shared__ uint32_t cnt[8];
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u, slot = w & 3u;
+  uint64_t *st = stamps + (size_t)(blockIdx.x * 8 + w) * 8;
+  if (lane == 0) {
+    cnt[w] = 0;
+    st[0] = __builtin_amdgcn_s_memrealtime();
+  }
+  const stamp_sync sync{st, &cnt[w]};
+  const uint32_t row_raw = (blockIdx.x * 4 + slot) * 4u + (lane >> 4);
+  const uint32_t i = row_raw < n ? row_raw : n - 1;
+  const u256 r = from_be32(sig65 + 65 * i), s = from_be32(sig65 + 65 * i + 32);
+  if (w >= 4) {
+    wv::recover_helper_row(gtab, from_be32(dig + 32 * i), r, s, &sh[slot], sync);
+    if (lane == 0) st[5] = __builtin_amdgcn_s_memrealtime();
+    return;
+  }
+  uint32_t addr[5] = {0, 0, 0, 0, 0};
+  aff Q;
+  const bool ok = wv::recover_pubkey_row<99, true>(gtab, zero256(), r, s, sig65[65 * i + 64], 0, addr, Q, row_tab[slot], &sh[slot], sync);
+  if (lane == 0) st[5] = __builtin_amdgcn_s_memrealtime();
+  if ((lane & 15u) == 0 && row_raw < n) {
+    uint8_t *o = out + (size_t)24 * i;
+    for (int k = 0; k < 5; k++) reinterpret_cast<uint32_t *>(o)[k] = addr[k];
+    o[20] = ok ? 1 : 0;
+  }
+}
+// n rows (a multiple of 16: whole workgroups), three launches; out24 = addresses + ok, stamps8 = (n / 4) · 2 wavefronts × 8
+// u64 of the last launch (main wavefronts of workgroup b at 8b … 8b + 3, helpers at 8b + 4 … 8b + 7); ms = its kernel time
+extern "C" int devtest_rows_pair_stamps(int n, const uint8_t *dig, const uint8_t *sig65, uint8_t *out24, uint64_t *stamps8,
+                                        float *ms) {
+  if (n <= 0 || n % 16 != 0) return -3;
+  uint32_t *dg;
+  size_t gbytes = (size_t)ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES * ibftk::GTAB_ENTRY_DWORDS * 4;
+  if (hipMalloc(&dg, gbytes) != hipSuccess) return -1;
+  const int blocks = n / 16;
+  const size_t st_words = (size_t)blocks * 8 * 8;
+  uint8_t *dd = dev_copy(dig, (size_t)32 * n), *ds = dev_copy(sig65, (size_t)65 * n), *dout;
+  uint64_t *dst;
+  if (!dd || !ds || hipMalloc(&dout, (size_t)24 * n) != hipSuccess || hipMalloc(&dst, st_words * 8) != hipSuccess) return -1;
+  devtest_gtab_kernel<<<(ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES + 63) / 64, 64>>>(dg);
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+  for (int rep = 0; rep < 3; rep++) {
+    (void)hipEventRecord(e0, 0);
+    devtest_rows_pair_kernel<<<blocks, 512>>>(dg, dd, ds, (uint32_t)n, dout, dst);
+    (void)hipEventRecord(e1, 0);
+    (void)hipEventSynchronize(e1);
+    (void)hipEventElapsedTime(ms, e0, e1);
+  }
+  int rc = hipDeviceSynchronize() == hipSuccess ? 0 : -2;
+  if (rc == 0) {
+    (void)hipMemcpy(out24, dout, (size_t)24 * n, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(stamps8, dst, st_words * 8, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dd); (void)hipFree(ds); (void)hipFree(dout); (void)hipFree(dst); (void)hipFree(dg);
+  return rc;
+}

@@ -155,6 +155,36 @@ void lane_rec4(void *vp) {
   j->ok[l] = ok ? 1 : 0;
 }
 
+// the rows pair: the helper's half (scalars, u1·G), then the main half, for the same four rows, `sh` in plain memory
+struct rec4p_job {
+  const uint8_t *hash32x4, *sig65x4;
+  uint8_t *addr20;  // [64][20]
+  int *ok;          // [64]
+  wv::rows_pair_shared *sh;
+};
+void lane_rec4p_helper(void *vp) {
+  rec4p_job *j = (rec4p_job *)vp;
+  const int row = wave_emul::lane() >> 4;
+  const uint8_t *h = j->hash32x4 + 32 * row, *sg = j->sig65x4 + 65 * row;
+  u256 z = secp::from_be32(h), r = secp::from_be32(sg), s = secp::from_be32(sg + 32);
+  wv::recover_helper_row(g_gtab.data(), z, r, s, j->sh, wv::no_sync());
+}
+void lane_rec4p_main(void *vp) {
+  rec4p_job *j = (rec4p_job *)vp;
+  const int l = wave_emul::lane(), row = l >> 4;
+  const uint8_t *sg = j->sig65x4 + 65 * row;
+  u256 r = secp::from_be32(sg), s = secp::from_be32(sg + 32);
+  uint32_t a[5];
+  secp::aff Q;
+  static uint32_t wtab[wv::ROW_TAB_SLOTS * 64];
+  // the main wavefront never sees the digest: a poisoned one here proves it
+  u256 z;
+  memset(&z, 0x5A, sizeof z);
+  bool ok = wv::recover_pubkey_row<99, true>(g_gtab.data(), z, r, s, sg[64], 0, a, Q, wtab, j->sh, wv::no_sync());
+  memcpy(j->addr20 + 20 * l, a, 20);
+  j->ok[l] = ok ? 1 : 0;
+}
+
 // rows_finish_deferred on its own: per row P1 (on the curve), P2′ (on y² = x³ + 7t³), t and the recovery id
 struct fin_job {
   const uint32_t *p1, *p2;  // [4][31] each
@@ -276,6 +306,14 @@ void wvh_recover2(const uint8_t *hash32, const uint8_t *sig65, uint32_t flags, u
   rec2_job j{hash32, sig65, flags, addr64x20, ok64, &sh};
   wave_emul::run(lane_rec2_helper, &j);
   wave_emul::run(lane_rec2_main, &j);
+}
+// the rows pair: helper then main over one `sh` — sequential here, concurrent on the device
+void wvh_recover4_pair(const uint8_t *hash32x4, const uint8_t *sig65x4, uint8_t *addr64x20, int *ok64) {
+  wv::rows_pair_shared sh;
+  memset(&sh, 0xA5, sizeof sh);  // (nothing may be read before the helper wrote it)
+  rec4p_job j{hash32x4, sig65x4, addr64x20, ok64, &sh};
+  wave_emul::run(lane_rec4p_helper, &j);
+  wave_emul::run(lane_rec4p_main, &j);
 }
 uint32_t wvh_neg_limb(int which, int i) { return wv::wneg_limb(which, i); }
 int wvh_gtab_bits(void) { return ibftk::GTAB_BITS; }  // the fixed-base window width of this harness's table

@@ -202,6 +202,10 @@ struct ibft_ctx {
                                   // IBFT_PAIR_ROWS_MAX=0 turns the form off)
   uint32_t wave_rows_max = 2048;  // AUTO: one wavefront per signature up to this many rows (two per SIMD: 0.45 ms); the
                                   // row-per-signature kernel (0.55 ms up to 4 096 rows) wins from there
+  // AUTO: the row-per-signature kernel with a helper wavefront per four signatures (scalars, u1·G on the same SIMD) up to
+  // this many rows — where the plain form runs at most one wavefront per SIMD; IBFT_ROWS_PAIR=0|1 pins either form
+  uint32_t rows_pair_max = 4096;
+  int rows_pair_force = -1;
 
   // a1: the proposal whose Keccak the device holds in d_H (raw ‖ BE64(round)); the same proposal is checked
   // against every PREPARE and COMMIT set of a round and on every wake-up, so it is hashed once
@@ -531,11 +535,20 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
   if (CG == 16) {
     if (!warm && (rc_clean = clean_mask(c))) return rc_clean;
     const uint32_t waves = (n + 3) / 4;
-    const dim3 rgrid((waves + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES), rblock(64 * ibftk::WAVE_KERNEL_WAVES);
-    if (mode == 0)
-      hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<0>, rgrid, rblock, 0, c->stream, a);
-    else
-      hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<1>, rgrid, rblock, 0, c->stream, a);
+    const bool pair = c->rows_pair_force >= 0 ? c->rows_pair_force != 0 : (uint64_t)n <= c->rows_pair_max;
+    if (pair) {
+      const dim3 pgrid((waves + ibftk::ROWS_PAIRS_PER_BLOCK - 1) / ibftk::ROWS_PAIRS_PER_BLOCK), pblock(128 * ibftk::ROWS_PAIRS_PER_BLOCK);
+      if (mode == 0)
+        hipLaunchKernelGGL(ibftk::ecrecover_rows_pair_kernel<0>, pgrid, pblock, 0, c->stream, a);
+      else
+        hipLaunchKernelGGL(ibftk::ecrecover_rows_pair_kernel<1>, pgrid, pblock, 0, c->stream, a);
+    } else {
+      const dim3 rgrid((waves + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES), rblock(64 * ibftk::WAVE_KERNEL_WAVES);
+      if (mode == 0)
+        hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<0>, rgrid, rblock, 0, c->stream, a);
+      else
+        hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<1>, rgrid, rblock, 0, c->stream, a);
+    }
   } else if (CG == 128) {
     if (!warm && (rc_clean = clean_mask(c))) return rc_clean;
     const dim3 pgrid((n + ibftk::PAIRS_PER_BLOCK - 1) / ibftk::PAIRS_PER_BLOCK), pblock(128 * ibftk::PAIRS_PER_BLOCK);
@@ -1429,6 +1442,10 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   if (const char *e = getenv("IBFT_WAVE_ROWS_MAX")) c->wave_rows_max = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_PAIR_ROWS_MAX")) c->pair_rows_max = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_ROWS_KERNEL_MAX")) c->rows_kernel_max = (uint32_t)strtoul(e, nullptr, 10);
+  if (const char *e = getenv("IBFT_ROWS_PAIR")) {
+    if (!strcmp(e, "0")) c->rows_pair_force = 0;
+    else if (!strcmp(e, "1")) c->rows_pair_force = 1;
+  }
   int rc = IBFT_OK;
   do {
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { rc = IBFT_E_HIP; break; }

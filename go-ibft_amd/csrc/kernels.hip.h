@@ -10,6 +10,7 @@
 //   ecrecover_group_kernel<G>   a3  IsValidValidator      (core/ibft.go:1128)     1 / 2,4,8 lanes per signature
 //   ecrecover_wave_kernel           same, one wavefront per signature (limbs spread over lanes, wave_fe_dev.h)
 //   ecrecover_rows_kernel           same, sixteen lanes (one DPP row) per signature, four signatures per wavefront
+//   ecrecover_rows_pair_kernel      same, plus a helper wavefront per four signatures (scalars, u1·G) on the same SIMD
 //   verify_known_lane_kernel    a2/a3 against the validator's known key (warm path), 1 lane per signature
 //   verify_known_group_kernel<G>    same, G = 2..32 lanes per signature
 //   verify_known_wave_kernel        same, one wavefront per signature in the row layout of wave_fe_dev.h
@@ -955,7 +956,7 @@ __global__ void __launch_bounds__(128 * PAIRS_PER_BLOCK) ecrecover_wave2_kernel(
 
 // ---- cold path, SIXTEEN LANES PER SIGNATURE: every row of a wavefront recovers its own signature ------
 // (wave_fe_dev.h:recover_pubkey_row).  n = 4 096 is one wavefront per SIMD again; used for
-// 2 048 < n ≤ 8 192.  Rows beyond n recompute the last row and store nothing.
+// 4 096 < n ≤ 8 192 (up to 4 096: the pair form below).  Rows beyond n recompute the last row and store nothing.
 // waves_per_eu(1, 2): the scheduler may spend registers (up to 256) on interleaving the independent
 // multiplications of a doubling — 42 → 9 s_nop per doubling in the main loop, 0.474 → 0.470 ms at 4 096 rows
 // (profiles/r02c_sweeps.txt) — while two wavefronts per SIMD (8 192 rows) still fit.
@@ -991,6 +992,66 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) __attribute__((amdgpu_
   aff Qa;
   __shared__ uint32_t row_tab[WAVE_KERNEL_WAVES][wv::ROW_TAB_SLOTS * 64];  // the window tables: wave-private LDS
   bool ok = wv::recover_pubkey_row(a.gtab, z, r, s, v, a.flags, got, Qa, row_tab[threadIdx.x >> 6]);
+  ok = ok && need && !pre && vi >= 0;
+#pragma unroll
+  for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+  if ((lane & 15u) == 0 && ok) {
+    learn_key(a, vi, Qa);
+    atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
+  }
+}
+
+// ---- the same, TWO WAVEFRONTS PER FOUR SIGNATURES (2 048 < n ≤ 4 096, where the kernel above runs one wavefront per SIMD) --
+// A workgroup is four MAIN wavefronts (0…3: R′, tables, main loop, closing chain, Keccak) and their HELPERS (4…7, helper of
+// main w is w + 4: r⁻¹ mod n, u1, u2, the GLV split, then u1·G) for the same four rows each (wave_fe_dev.h: rows_pair_shared,
+// recover_pubkey_row<…, PAIR>, recover_helper_row).  Wavefronts w and w + 4 of a workgroup share a SIMD
+// (tools/simd_placement_probe.hip), so a helper issues in its main wavefront's stalls.  The two meet in LDS at two workgroup
+// barriers: every wavefront passes both, whatever its rows turn out to be — a pair with nothing to do only synchronises, and
+// main and helper decide that on the same rows.  More than 128 registers: a second workgroup never shares the compute unit.
+constexpr int ROWS_PAIRS_PER_BLOCK = 4;
+template <int MODE>
+__global__ void __launch_bounds__(128 * ROWS_PAIRS_PER_BLOCK) ecrecover_rows_pair_kernel(recover_args a) {
+  __shared__ uint32_t row_tab[ROWS_PAIRS_PER_BLOCK][wv::ROW_TAB_SLOTS * 64];  // the main wavefronts' window tables
+  __shared__ wv::rows_pair_shared sh[ROWS_PAIRS_PER_BLOCK];
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t slot = w % ROWS_PAIRS_PER_BLOCK;
+  const bool helper = w >= ROWS_PAIRS_PER_BLOCK;
+  const uint32_t wave = blockIdx.x * ROWS_PAIRS_PER_BLOCK + slot;
+  const uint32_t row_raw = wave * 4u + (lane >> 4);
+  const bool live = row_raw < a.n;
+  const uint32_t row = live ? row_raw : a.n - 1;
+  uint32_t want[5];
+#pragma unroll
+  for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
+  const int vi = valset_lookup(a.vtab, a.vslot_mask, want);
+  const bool pre = a.pre_flags && a.pre_flags[row] != 0;
+  const bool done = a.warm_done && a.warm_done[row] != 0;
+  const bool need = live && !done;
+  if (!helper && need && (lane & 15u) == 0) a.vidx[row] = vi;
+  auto sync = [] { __syncthreads(); };
+  if (!__any((need && !pre && vi >= 0) ? 1 : 0)) {  // (wave-uniform, the same for both wavefronts of the pair)
+    sync();
+    sync();
+    return;
+  }
+  const u256 r = secp::from_be32(a.sig65 + 65ull * row);
+  const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
+  if (helper) {
+    u256 z;
+    if (MODE == 0) {
+      z = secp::from_be32(a.hash32 + 32ull * row);
+    } else {
+      uint64_t d[4];
+      hash_range_dwords(a.payload + a.off[row], a.off[row + 1] - a.off[row], d);
+      keccak::digest_to_limbs(d, z.v);
+    }
+    wv::recover_helper_row(a.gtab, z, r, s, &sh[slot], sync);
+    return;
+  }
+  const uint32_t v = a.sig65[65ull * row + 64];
+  uint32_t got[5];
+  aff Qa;
+  bool ok = wv::recover_pubkey_row<99, true>(a.gtab, secp::zero256(), r, s, v, a.flags, got, Qa, row_tab[slot], &sh[slot], sync);
   ok = ok && need && !pre && vi >= 0;
 #pragma unroll
   for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);

@@ -1184,9 +1184,55 @@ WVF bool rows_finish_deferred(aff &Qa, const wjac &p1, const wjac &p2, uint32_t 
 // Built, measured and removed: the table in registers, built straight-line; √t first, safegcd last; no peeled
 // first digit; the G-table points prefetched into LDS; the G additions merged into the main loop, or sharing its additions.
 constexpr int ROW_TAB_SLOTS = 32;  // 8 entries × (x, y, z → X·β) + 8 prefix products
-template <int STOP = 99>
+
+// u1·G of the row-per-signature recover: all the fixed-base windows of each row's u1, into an accumulator of its own (the
+// table points are points of the curve itself).  Window 0 into an accumulator at infinity is the table point itself (or
+// still infinity for a zero digit).  SHIFT: u1 is read as a shift register (the window at a fixed place, eight funnel
+// shifts per window) instead of by a word index — in the rows pair kernel, whose two halves together exceed the compiler's
+// budget for keeping indexed arrays in registers, the indexed form puts u1 in the private segment.
+template <bool SHIFT = false>
+WVF wjac rows_fixed_base(const uint32_t *__restrict__ gtab, const u256 &u1, const wk &k) {
+  static_assert(ibftk::GTAB_BITS < 32, "a window lies within two words");
+  wjac accg = wjac_inf();
+  {
+    const uint32_t dgt = u1.v[0] & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
+    const waff pt = load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * dgt, k);
+    accg = wjac_select(dgt != 0, wjac_from_aff(pt, k), accg);
+  }
+  u256 sr = u1;  // (SHIFT)
+#pragma unroll 1
+  for (int win = 1; win < ibftk::GTAB_WINDOWS; win++) {
+    uint32_t dgt;
+    if constexpr (SHIFT) {
+#pragma unroll
+      for (int i = 0; i < 7; i++) sr.v[i] = (sr.v[i] >> ibftk::GTAB_BITS) | (sr.v[i + 1] << (32 - ibftk::GTAB_BITS));
+      sr.v[7] >>= ibftk::GTAB_BITS;
+      dgt = sr.v[0] & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
+    } else {
+      const int bit = win * ibftk::GTAB_BITS;
+      dgt = (u1.v[bit >> 5] >> (bit & 31)) & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
+    }
+    const waff pt = load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * ((size_t)win * ibftk::GTAB_ENTRIES + dgt), k);
+    const wjac sum = wjac_add_aff<true>(accg, pt, k);
+    accg = wjac_select(dgt != 0, sum, accg);
+  }
+  return accg;
+}
+
+// TWO WAVEFRONTS PER FOUR SIGNATURES (2 048 < n ≤ 4 096, where the single form runs one wavefront per SIMD).  PAIR = true
+// is the MAIN wavefront: R′, the window tables (they need only R′), barrier 1, the digits of the split scalars from `sh`,
+// the main loop, barrier 2, u1·G from `sh`, the closing chain, Keccak.  The HELPER wavefront (recover_helper_row) computes
+// what the u2·R chain does not wait for — r⁻¹ mod n, u1, u2, the GLV split, then the sixteen fixed-base additions — for
+// the same four rows, on the same SIMD, meanwhile.  The hand-over holds exactly the values the single form computes
+// itself, by the same code, so the verdicts are the same, rare rows included.
+struct rows_pair_shared {
+  uint32_t sc[4][9];                          // per row: |k1| (4 words), |k2| (4 words), signs (bit 0: k1 < 0, bit 1: k2 < 0)
+  uint32_t gx[64], gy[64], gz[64], ginf[64];  // u1·G in the row layout, per lane
+};
+template <int STOP = 99, bool PAIR = false, class SYNC = no_sync>
 WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw, const u256 &r, const u256 &s,
-                           uint32_t v, uint32_t flags, uint32_t addr[5], aff &Qa, uint32_t *wtab) {
+                           uint32_t v, uint32_t flags, uint32_t addr[5], aff &Qa, uint32_t *wtab,
+                           const rows_pair_shared *sh = nullptr, SYNC sync = SYNC()) {
 #define WV_STAGE(n, keep)     \
   if (STOP == (n)) {          \
     addr[0] = (keep);         \
@@ -1203,17 +1249,12 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
   const waff R1 = waff{wfe_mul(x, rhs, k), wfe_sqr(rhs, k)};
   const uint32_t skeep = R1.x ^ R1.y;
   WV_STAGE(1, skeep)
-  // u1 = −z/r, u2 = s/r (mod n); u2 = k1 + k2·λ
-  const secp::sc rinv = secp::sc_from_u256(modinv_wave<secp::ModN>(r, k));
-  WV_STAGE(21, skeep ^ rinv.n[0] ^ rinv.n[9])
-  const u256 u1 = secp::sc_neg_canon(secp::sc_canon(secp::sc_mul(secp::sc_from_u256(z_raw), rinv)));
-  const u256 u2 = secp::sc_canon(secp::sc_mul(secp::sc_from_u256(s), rinv));
-  WV_STAGE(22, skeep ^ u1.v[0] ^ u2.v[3])
-  const secp::glv_split sp = secp::sc_split_lambda(u2);
-  WV_STAGE(2, skeep ^ u1.v[0] ^ sp.k1.v[0] ^ sp.k2.v[1])
+  // u1 = −z/r, u2 = s/r (mod n); u2 = k1 + k2·λ — here, or (PAIR) by the helper wavefront while the tables are built
+  u256 u1;
+  secp::glv_split sp;
   // signed radix-16 digits of |k1|, |k2|: k + 0x88…8 has nibbles d_j + 8, bit 128 is digit 32
   uint32_t w1[5], w2[5];
-  {
+  auto digits = [&] {
     uint32_t c1 = 0, c2 = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -1222,6 +1263,18 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
     }
     w1[4] = c1;
     w2[4] = c2;
+  };
+  if constexpr (PAIR) {
+    u1 = secp::zero256();  // (the helper's; named here by the STOP variants only)
+  } else {
+    const secp::sc rinv = secp::sc_from_u256(modinv_wave<secp::ModN>(r, k));
+    WV_STAGE(21, skeep ^ rinv.n[0] ^ rinv.n[9])
+    u1 = secp::sc_neg_canon(secp::sc_canon(secp::sc_mul(secp::sc_from_u256(z_raw), rinv)));
+    const u256 u2 = secp::sc_canon(secp::sc_mul(secp::sc_from_u256(s), rinv));
+    WV_STAGE(22, skeep ^ u1.v[0] ^ u2.v[3])
+    sp = secp::sc_split_lambda(u2);
+    WV_STAGE(2, skeep ^ u1.v[0] ^ sp.k1.v[0] ^ sp.k2.v[1])
+    digits();
   }
   // Tables 1..8 of R (affine start: mixed additions) and, through X·β, of λR — in wave-private LDS, built and
   // brought to ONE common Z by rolled loops: code that runs once per signature is fetched, not executed
@@ -1280,6 +1333,19 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
     }
     Zc = suf;
   }
+  if constexpr (PAIR) {
+    sync();  // barrier 1: the helper has written the split scalars
+    const uint32_t *sr = sh->sc[k.row];
+    sp.k1 = sp.k2 = secp::zero256();
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      sp.k1.v[i] = sr[i];
+      sp.k2.v[i] = sr[4 + i];
+    }
+    sp.neg1 = (sr[8] & 1u) != 0;
+    sp.neg2 = (sr[8] & 2u) != 0;
+    digits();
+  }
   WV_STAGE(3, WT(0) ^ WT(7) ^ WT(23) ^ u1.v[0] ^ w1[0] ^ w2[1] ^ Zc)
   wjac acc = wjac_inf();
   // Digit 32 (the carry bit of the recoding, 0 or 1, never negative) outside the loop: the accumulator is still at
@@ -1317,21 +1383,16 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
   acc.z = wfe_mul(acc.z, Zc, k);  // back from the isomorphic curve (an accumulator at infinity keeps its flag)
   WV_STAGE(4, acc.x ^ acc.y ^ acc.z ^ u1.v[0])
   // u1·G: all the fixed-base windows in this row, into an accumulator of its own: the table points are points of the curve,
-  // the accumulator still lives on the isomorphic one
-  wjac accg = wjac_inf();
-  // window 0 into an accumulator at infinity is the table point itself (or still infinity for a zero digit)
-  {
-    const uint32_t dgt = u1.v[0] & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
-    const waff pt = load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * dgt, k);
-    accg = wjac_select(dgt != 0, wjac_from_aff(pt, k), accg);
-  }
-#pragma unroll 1
-  for (int win = 1; win < ibftk::GTAB_WINDOWS; win++) {
-    const int bit = win * ibftk::GTAB_BITS;
-    const uint32_t dgt = (u1.v[bit >> 5] >> (bit & 31)) & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
-    const waff pt = load_waff(gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * ((size_t)win * ibftk::GTAB_ENTRIES + dgt), k);
-    const wjac sum = wjac_add_aff<true>(accg, pt, k);
-    accg = wjac_select(dgt != 0, sum, accg);
+  // the accumulator still lives on the isomorphic one (PAIR: the helper wavefront has summed them meanwhile)
+  wjac accg;
+  if constexpr (PAIR) {
+    sync();  // barrier 2: u1·G is in `sh`
+    accg.x = sh->gx[lane_];
+    accg.y = sh->gy[lane_];
+    accg.z = sh->gz[lane_];
+    accg.inf = sh->ginf[lane_] != 0;
+  } else {
+    accg = rows_fixed_base(gtab, u1, k);
   }
   WV_STAGE(5, acc.x ^ acc.y ^ acc.z ^ accg.x ^ accg.z)
   ok = rows_finish_deferred(Qa, accg, acc, rhs, v, k) && ok;
@@ -1340,6 +1401,35 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
   keccak::address_from_xy(qx.v, qy.v, addr);
   return ok;
 #undef WV_STAGE
+}
+
+// The HELPER wavefront of a rows pair (see rows_pair_shared): for the same four rows as its main wavefront, r⁻¹ mod n, u1,
+// u2 and the GLV split of u2 → `sh`, barrier 1; then u1·G (rows_fixed_base) → `sh`, barrier 2.
+template <class SYNC>
+WVF void recover_helper_row(const uint32_t *__restrict__ gtab, const u256 &z_raw, const u256 &r, const u256 &s,
+                            rows_pair_shared *sh, SYNC sync) {
+  const wk k = wk_init();
+  const secp::sc rinv = secp::sc_from_u256(modinv_wave<secp::ModN>(r, k));
+  const u256 u1 = secp::sc_neg_canon(secp::sc_canon(secp::sc_mul(secp::sc_from_u256(z_raw), rinv)));
+  const u256 u2 = secp::sc_canon(secp::sc_mul(secp::sc_from_u256(s), rinv));
+  const secp::glv_split sp = secp::sc_split_lambda(u2);
+  if (k.li == 0) {
+    uint32_t *sr = sh->sc[k.row];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      sr[i] = sp.k1.v[i];
+      sr[4 + i] = sp.k2.v[i];
+    }
+    sr[8] = (sp.neg1 ? 1u : 0u) | (sp.neg2 ? 2u : 0u);
+  }
+  sync();  // barrier 1
+  const wjac accg = rows_fixed_base<true>(gtab, u1, k);
+  const uint32_t l = lane_id();
+  sh->gx[l] = accg.x;
+  sh->gy[l] = accg.y;
+  sh->gz[l] = accg.z;
+  sh->ginf[l] = accg.inf ? 1u : 0u;
+  sync();  // barrier 2
 }
 
 // ---- the warm path, one signature per wavefront --------------------------------------------------------
