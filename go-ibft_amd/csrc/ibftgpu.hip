@@ -152,6 +152,21 @@ struct ibft_ctx {
   DevBuf d_bhash, d_boff, d_btally;
   uint64_t *h_btally = nullptr, *dh_btally = nullptr;
   size_t h_btally_blocks = 0;
+  // Streamed chain sync (ibft_block_seals_submit / _collect): at most two batches in flight.  Batch k is copied on the copy
+  // stream into the SPARE column set — d_sig_nx / d_signer_nx / d_pre_nx of the seal pipeline plus a second pair of offset and
+  // block-hash buffers — while the kernels of batch k − 1 read the resident set; the submit then swaps the two sets, exactly
+  // as ibft_seals_stage_next + ibft_seals_swap would (ev_cols_read: the spare set's last reader, ev_staged: the copy landed).
+  // Every kernel of a batch runs on the MAIN stream: the per-row hash column block_rows_kernel fills, the work mask, the
+  // validator indices, d_seen and the ticket word in d_acc exist once and rely on that order — and any other entry point that
+  // enqueues on the main stream is behind the batches in flight by the same order, their results already on the way to
+  // their slots.  Results: verdict words in the seal pipeline's mapped slots (p_mask; the two pipelines are never mixed),
+  // {keys learned, a learned slot} in p_tally[s][4], the per-block records in bs_tally[s] (mapped) or through bs_dtally[s].
+  DevBuf d_bhash_nx, d_boff_nx, bs_dtally[2];
+  uint64_t *bs_tally[2] = {nullptr, nullptr}, *bs_dtally_map[2] = {nullptr, nullptr};
+  size_t bs_tally_blocks[2] = {0, 0};
+  hipEvent_t ev_bs[2] = {nullptr, nullptr};
+  uint32_t bs_issued = 0, bs_collected = 0, bs_rows[2] = {0, 0}, bs_blocks[2] = {0, 0};
+  uint64_t bs_quorum[2][2] = {{0, 0}, {0, 0}};  // the quorum a batch was judged under (the set current at its submit)
   uint64_t last_wide[ibftk::TALLY_SUM_WORDS] = {0};  // full-width power of the last fetched tally
   uint64_t height = 0;
   // the seal-digest convention of the embedding Backend (ibft_set_seal_digest): 0 = the proposalHash itself
@@ -1512,6 +1527,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->hstream) (void)hipStreamSynchronize(c->hstream);
   if (c->tstream) (void)hipStreamSynchronize(c->tstream);
+  if (c->cstream) (void)hipStreamSynchronize(c->cstream);  // block batches in flight are drained, never delivered
   for (DevBuf *b : {&c->d_hash, &c->d_sig, &c->d_signer, &c->d_pre, &c->d_hash_len, &c->d_payload,
                     &c->d_off, &c->d_raw, &c->d_mask, &c->d_mask_out, &c->d_vidx, &c->d_tally, &c->d_H,
                     &c->d_vtab, &c->d_vpower, &c->d_vslot,
@@ -1519,7 +1535,8 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_xbuf[0], &c->d_xbuf[1], &c->d_xres[0], &c->d_xres[1], &c->d_set, &c->d_noseal, &c->d_class,
                     &c->d_cert_nodes, &c->d_cert_span, &c->d_cert_count, &c->d_cert_prop, &c->d_cert_masks, &c->d_cert_total,
                     &c->d_cert_slot, &c->d_cert_tiles, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
-                    &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally})
+                    &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally,
+                    &c->d_bhash_nx, &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1]})
     release(*b);
   if (c->tstream) {
     (void)hipStreamSynchronize(c->tstream);
@@ -1558,6 +1575,10 @@ void ibft_ctx_destroy(ibft_ctx *c) {
   }
   if (c->h_mask) (void)hipHostFree(c->h_mask);
   if (c->h_btally) (void)hipHostFree(c->h_btally);
+  for (int i = 0; i < 2; i++) {
+    if (c->bs_tally[i]) (void)hipHostFree(c->bs_tally[i]);
+    if (c->ev_bs[i]) (void)hipEventDestroy(c->ev_bs[i]);
+  }
   if (c->h_tally) (void)hipHostFree(c->h_tally);
   if (c->h_digest) (void)hipHostFree(c->h_digest);
   if (c->h_set) (void)hipHostFree(c->h_set);
@@ -1950,13 +1971,9 @@ int ibft_seals_stage(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65, c
   return seals_stage_locked(c, hash32, sig65, signer20, pre_flags, n, true);
 }
 
-// Double-buffered staging: the copy of batch k+1 overlaps the verdict kernels of batch k.
-int ibft_seals_stage_next(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65, const uint8_t *signer20,
-                          const uint8_t *pre_flags, size_t n) {
-  if (!c || (n && (!hash32 || !sig65 || !signer20))) return IBFT_E_INVAL;
-  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself: no join_side)
-  if (n > c->max_rows) return IBFT_E_TOOBIG;
-  HIPCHK(c, hipSetDevice(c->device));
+// The copy stream with its two events and the spare set of seal columns, on first use (ibft_seals_stage_next,
+// ibft_block_seals_submit)
+static int ensure_spare_columns(ibft_ctx *c) {
   if (!c->cstream) {
     HIPCHK(c, hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming));
@@ -1969,6 +1986,18 @@ int ibft_seals_stage_next(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig
   if ((rc = ensure(c, c->d_sig_nx, m * 65 + 64))) return rc;
   if ((rc = ensure(c, c->d_signer_nx, m * 20))) return rc;
   if ((rc = ensure(c, c->d_pre_nx, m))) return rc;
+  return IBFT_OK;
+}
+
+// Double-buffered staging: the copy of batch k+1 overlaps the verdict kernels of batch k.
+int ibft_seals_stage_next(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65, const uint8_t *signer20,
+                          const uint8_t *pre_flags, size_t n) {
+  if (!c || (n && (!hash32 || !sig65 || !signer20))) return IBFT_E_INVAL;
+  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself: no join_side)
+  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_spare_columns(c))) return rc;
   // the spare slot was the resident one until the last swap: kernels enqueued before that swap may still read it
   HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_cols_read, 0));
   if (n) {
@@ -2025,25 +2054,9 @@ static int seals_launch_locked(ibft_ctx *c, uint32_t repeat) {
   return IBFT_OK;
 }
 
-// Pipelined passes over the resident batch: submit enqueues one pass whose results go to one of two host-visible slots,
-// collect waits for the OLDEST submitted pass only (the event behind its tally, not the stream).
-int ibft_seals_submit(ibft_ctx *c) {
-  if (!c) return IBFT_E_INVAL;
-  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself: no join_side)
-  if (!c->have_valset) return IBFT_E_NOVALSET;
-  if (c->pass_issued - c->pass_collected >= 2) {
-    c->last_error = "two passes already in flight: call ibft_seals_collect first";
-    return IBFT_E_INVAL;
-  }
-  if (c->learn_rc != IBFT_OK) {  // the table build behind an already delivered pass failed (ibft_seals_collect): say so once
-    const int rc = c->learn_rc;
-    c->learn_rc = IBFT_OK;
-    return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t s = c->pass_issued & 1u;
-  // mapped result slots (the tally kernel writes them itself) and the pass events, on first use — piece by piece, so that a
-  // failure half way leaves nothing to leak and nothing half set up for the next call
+// mapped result slots (the tally kernel writes them itself) and the pass events, on first use — piece by piece, so that a
+// failure half way leaves nothing to leak and nothing half set up for the next call (ibft_seals_submit, ibft_block_seals_submit)
+static int ensure_result_slots(ibft_ctx *c) {
   for (int i = 0; i < 2; i++) {
     if (!c->p_mask[i] &&
         hipHostMalloc((void **)&c->p_mask[i], (size_t)mask_words(std::max<size_t>(c->max_rows, c->row_cap)) * 8 + 64) != hipSuccess)
@@ -2057,6 +2070,34 @@ int ibft_seals_submit(ibft_ctx *c) {
       c->dp_tally[i] = (uint64_t *)dt;
     }
     if (!c->ev_pass[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_pass[i], hipEventDisableTiming));
+  }
+  return IBFT_OK;
+}
+
+// Pipelined passes over the resident batch: submit enqueues one pass whose results go to one of two host-visible slots,
+// collect waits for the OLDEST submitted pass only (the event behind its tally, not the stream).
+int ibft_seals_submit(ibft_ctx *c) {
+  if (!c) return IBFT_E_INVAL;
+  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself: no join_side)
+  if (!c->have_valset) return IBFT_E_NOVALSET;
+  if (c->pass_issued - c->pass_collected >= 2) {
+    c->last_error = "two passes already in flight: call ibft_seals_collect first";
+    return IBFT_E_INVAL;
+  }
+  if (c->bs_issued != c->bs_collected) {  // the two pipelines share the result slots and the spare columns
+    c->last_error = "block batches in flight: call ibft_block_seals_collect first";
+    return IBFT_E_INVAL;
+  }
+  if (c->learn_rc != IBFT_OK) {  // the table build behind an already delivered pass failed (ibft_seals_collect): say so once
+    const int rc = c->learn_rc;
+    c->learn_rc = IBFT_OK;
+    return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint32_t s = c->pass_issued & 1u;
+  {
+    const int rcs = ensure_result_slots(c);
+    if (rcs) return rcs;
   }
   if (c->ev_used >= 4096) c->ev_used = 0;
   const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
@@ -2545,6 +2586,49 @@ int ibft_verify_seals(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65, 
   return fetch_results(c, c->staged_n, out_mask, tally, true);
 }
 
+// The segmented tally of a block batch over the resident work mask / validator indices and the offsets in d_boff, on the main
+// stream.  Work mask, d_seen and the ticket word in d_acc exist once per context: two batches in flight (ibft_block_seals_submit)
+// take turns at them in main-stream order.
+static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t widest, uint64_t *host_mask, uint64_t *out) {
+  if (c->read_pending) {  // a consumer stream is still copying the previous results (ibft_seals_export_on / exchange)
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
+    c->read_pending = false;
+  }
+  ibftk::block_tally_args t{};
+  t.work_mask = (uint64_t *)c->d_mask.p;
+  t.mask = (uint64_t *)c->d_mask_out.p;
+  t.host_mask = host_mask;
+  t.vidx = (const int32_t *)c->d_vidx.p;
+  t.vpower32 = (const uint32_t *)c->d_vpower.p;
+  t.off = (const uint32_t *)c->d_boff.p;
+  t.n = nr;
+  t.n_blocks = nb;
+  t.n_validators = c->n_validators;
+  const size_t lds = (size_t)((c->n_validators + 31) / 32) * 4;
+  t.lds_bitmap = lds <= 49152 ? 1u : 0u;  // beyond: one workgroup walks every block over the HBM bitmap (tally_kernel's bound)
+  t.seen = (uint32_t *)c->d_seen.p;
+  t.acc = (uint64_t *)c->d_acc.p;
+  t.quorum = (const uint64_t *)c->d_quorum.p;
+  t.out = out;
+  const dim3 grid(t.lds_bitmap ? std::min(nb, ibftk::BTALLY_MAX_GRID) : 1u);
+  const size_t dyn = t.lds_bitmap ? lds : 0;
+  const bool wide = widest > 256u * ibftk::BTALLY_RPT;  // a block that one step of 256 threads does not cover
+  if (c->power_words == 1) {
+    if (wide)
+      hipLaunchKernelGGL((ibftk::block_tally_kernel<1, 1024>), grid, dim3(1024), dyn, c->stream, t);
+    else
+      hipLaunchKernelGGL((ibftk::block_tally_kernel<1, 256>), grid, dim3(256), dyn, c->stream, t);
+  } else {
+    if (wide)
+      hipLaunchKernelGGL((ibftk::block_tally_kernel<4, 1024>), grid, dim3(1024), dyn, c->stream, t);
+    else
+      hipLaunchKernelGGL((ibftk::block_tally_kernel<4, 256>), grid, dim3(256), dyn, c->stream, t);
+  }
+  HIPCHK(c, hipGetLastError());
+  if ((uint32_t)mask_words(nr) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed every word that held bits
+  return IBFT_OK;
+}
+
 // Chain sync: the committed seals of n_blocks finalized blocks — one upload, one verdict launch over every row (the AUTO rule
 // sees the TOTAL row count), one segmented tally (block_tally_kernel), one synchronisation.
 int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
@@ -2602,42 +2686,7 @@ int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint
     if (c->ev_used >= 4096) c->ev_used = 0;
     const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
     if ((rc = enqueue_recover(c, nr, c->staged_pre, 0, time_it))) return rc;
-    if (c->read_pending) {  // a consumer stream is still copying the previous results (ibft_seals_export_on / exchange)
-      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
-      c->read_pending = false;
-    }
-    ibftk::block_tally_args t{};
-    t.work_mask = (uint64_t *)c->d_mask.p;
-    t.mask = (uint64_t *)c->d_mask_out.p;
-    t.host_mask = c->dh_mask;
-    t.vidx = (const int32_t *)c->d_vidx.p;
-    t.vpower32 = (const uint32_t *)c->d_vpower.p;
-    t.off = (const uint32_t *)c->d_boff.p;
-    t.n = nr;
-    t.n_blocks = nb;
-    t.n_validators = c->n_validators;
-    const size_t lds = (size_t)((c->n_validators + 31) / 32) * 4;
-    t.lds_bitmap = lds <= 49152 ? 1u : 0u;  // beyond: one workgroup walks every block over the HBM bitmap (tally_kernel's bound)
-    t.seen = (uint32_t *)c->d_seen.p;
-    t.acc = (uint64_t *)c->d_acc.p;
-    t.quorum = (const uint64_t *)c->d_quorum.p;
-    t.out = c->dh_btally ? c->dh_btally : (uint64_t *)c->d_btally.p;
-    const dim3 grid(t.lds_bitmap ? std::min(nb, ibftk::BTALLY_MAX_GRID) : 1u);
-    const size_t dyn = t.lds_bitmap ? lds : 0;
-    const bool wide = widest > 256u * ibftk::BTALLY_RPT;  // a block that one step of 256 threads does not cover
-    if (c->power_words == 1) {
-      if (wide)
-        hipLaunchKernelGGL((ibftk::block_tally_kernel<1, 1024>), grid, dim3(1024), dyn, c->stream, t);
-      else
-        hipLaunchKernelGGL((ibftk::block_tally_kernel<1, 256>), grid, dim3(256), dyn, c->stream, t);
-    } else {
-      if (wide)
-        hipLaunchKernelGGL((ibftk::block_tally_kernel<4, 1024>), grid, dim3(1024), dyn, c->stream, t);
-      else
-        hipLaunchKernelGGL((ibftk::block_tally_kernel<4, 256>), grid, dim3(256), dyn, c->stream, t);
-    }
-    HIPCHK(c, hipGetLastError());
-    if ((uint32_t)mask_words(nr) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed every word that held bits
+    if ((rc = enqueue_block_tally(c, nb, nr, widest, c->dh_mask, c->dh_btally ? c->dh_btally : (uint64_t *)c->d_btally.p))) return rc;
     c->host_direct = false;
     const size_t mw = (size_t)mask_words(nr);
     if (!c->dh_mask) HIPCHK(c, hipMemcpyAsync(c->h_mask, c->d_mask_out.p, mw * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2666,6 +2715,166 @@ int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint
       t.distinct_senders = (uint32_t)(r[2] >> 32);
       t.has_quorum = (uint32_t)r[3];
     }
+  return IBFT_OK;
+}
+
+// Streamed chain sync: the same batch as ibft_verify_block_seals, enqueued and not waited for.  Up to two batches in flight;
+// the copy of batch k + 1 (copy stream, into the spare column set) runs under the kernels of batch k (main stream).
+int ibft_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags) {
+  if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
+  if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;
+  uint32_t widest = 0;
+  for (size_t b = 0; b < n_blocks; b++) {
+    if (seal_off[b + 1] < seal_off[b]) return IBFT_E_INVAL;
+    widest = std::max(widest, seal_off[b + 1] - seal_off[b]);
+  }
+  const size_t n = seal_off[n_blocks];
+  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  if (n && (!block_hash32 || !sig65 || !signer20)) return IBFT_E_INVAL;
+  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself; side-stream tallies are joined below)
+  if (!c->have_valset) return IBFT_E_NOVALSET;
+  if (c->pass_issued != c->pass_collected || c->next_valid) {  // the two pipelines share the result slots and the spare columns
+    c->last_error = c->next_valid ? "a batch staged by ibft_seals_stage_next awaits its ibft_seals_swap"
+                                  : "seal passes in flight: call ibft_seals_collect first";
+    return IBFT_E_INVAL;
+  }
+  if (c->bs_issued - c->bs_collected >= 2) {
+    c->last_error = "two block batches already in flight: call ibft_block_seals_collect first";
+    return IBFT_E_INVAL;
+  }
+  if (c->learn_rc != IBFT_OK) {  // the table build behind an already delivered batch failed (ibft_block_seals_collect): say so once
+    const int rc = c->learn_rc;
+    c->learn_rc = IBFT_OK;
+    return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = join_side(c))) return rc;  // tallies of collected seal passes may still be on the side stream
+  const uint32_t s = c->bs_issued & 1u, nb = (uint32_t)n_blocks, nr = (uint32_t)n;
+  if (!c->ev_bs[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bs[s], hipEventDisableTiming));
+  if (nr) {
+    if ((rc = ensure_result_slots(c))) return rc;
+    if ((rc = ensure_spare_columns(c))) return rc;
+    // (hipFree waits for the device: a buffer that grows here is read by nothing any more)
+    if ((rc = ensure(c, c->d_boff_nx, ((size_t)nb + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->d_bhash_nx, (size_t)nb * 32))) return rc;
+    // the records of slot s: the batch that used them last (k − 2) has been collected, nothing writes them now
+    if (nb > c->bs_tally_blocks[s]) {
+      if (c->bs_tally[s]) (void)hipHostFree(c->bs_tally[s]);
+      c->bs_tally[s] = c->bs_dtally_map[s] = nullptr;
+      c->bs_tally_blocks[s] = 0;
+      const size_t want = std::max<size_t>(nb, 256);
+      if (hipHostMalloc((void **)&c->bs_tally[s], want * 32) != hipSuccess) {
+        c->bs_tally[s] = nullptr;
+        return IBFT_E_NOMEM;
+      }
+      c->bs_tally_blocks[s] = want;
+      void *d = nullptr;  // (IBFT_NO_HOST_DIRECT: records and verdict words through device buffers and copies behind the tally)
+      if (c->dh_mask && hipHostGetDevicePointer(&d, c->bs_tally[s], 0) == hipSuccess) c->bs_dtally_map[s] = (uint64_t *)d;
+    }
+    if (!c->bs_dtally_map[s] && (rc = ensure(c, c->bs_dtally[s], (size_t)nb * 32))) return rc;
+    // The spare set was the resident one until the previous swap: batch k − 2's kernels — its tally reads the offsets — may
+    // still be at it.  ev_cols_read was recorded behind them.
+    HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_cols_read, 0));
+    HIPCHK(c, hipMemcpyAsync(c->d_boff_nx.p, seal_off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, c->cstream));
+    HIPCHK(c, hipMemcpyAsync(c->d_bhash_nx.p, block_hash32, (size_t)nb * 32, hipMemcpyHostToDevice, c->cstream));
+    HIPCHK(c, hipMemcpyAsync(c->d_sig_nx.p, sig65, n * 65, hipMemcpyHostToDevice, c->cstream));
+    HIPCHK(c, hipMemcpyAsync(c->d_signer_nx.p, signer20, n * 20, hipMemcpyHostToDevice, c->cstream));
+    if (pre_flags) HIPCHK(c, hipMemcpyAsync(c->d_pre_nx.p, pre_flags, n, hipMemcpyHostToDevice, c->cstream));
+    HIPCHK(c, hipEventRecord(c->ev_staged, c->cstream));
+    // everything on the main stream so far (batch k − 1 included) read the set that becomes the spare one now; what follows
+    // reads the other set once its copy has landed
+    HIPCHK(c, hipEventRecord(c->ev_cols_read, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_staged, 0));
+    std::swap(c->d_sig, c->d_sig_nx);
+    std::swap(c->d_signer, c->d_signer_nx);
+    std::swap(c->d_pre, c->d_pre_nx);
+    std::swap(c->d_boff, c->d_boff_nx);
+    std::swap(c->d_bhash, c->d_bhash_nx);
+    c->wire_valid = false;
+    c->staged_n = nr;  // the rows are the resident batch from here on, as after ibft_verify_block_seals
+    c->staged_pre = pre_flags != nullptr;
+    // from here on a failure leaves commands of this batch on the streams: nothing of it is delivered, the slot stays free,
+    // and whatever the main stream gets next is behind them
+    if ((rc = seal_digest_column(c, (uint8_t *)c->d_bhash.p, nb))) return rc;
+    // (the per-row hash column exists once: block_rows_kernel of this batch is behind the verdict kernels of the last one)
+    hipLaunchKernelGGL(ibftk::block_rows_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)c->d_bhash.p,
+                       (const uint32_t *)c->d_boff.p, nb, nr, (uint8_t *)c->d_hash.p);
+    HIPCHK(c, hipGetLastError());
+    if (c->ev_used >= 4096) c->ev_used = 0;
+    const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
+    if ((rc = enqueue_recover(c, nr, c->staged_pre, 0, time_it))) return rc;
+    const bool direct = c->bs_dtally_map[s] != nullptr;
+    if ((rc = enqueue_block_tally(c, nb, nr, widest, direct ? c->dp_mask[s] : nullptr,
+                                  direct ? c->bs_dtally_map[s] : (uint64_t *)c->bs_dtally[s].p)))
+      return rc;
+    c->host_direct = false;
+    if (!direct) {
+      HIPCHK(c, hipMemcpyAsync(c->p_mask[s], c->d_mask_out.p, (size_t)mask_words(nr) * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->bs_tally[s], c->bs_dtally[s].p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->stream));
+    }
+    // {keys learned, a learned slot} as of this batch: what its collect builds tables from
+    if (c->cache_on) HIPCHK(c, hipMemcpyAsync(c->p_tally[s] + 4, c->dev->d_learned.p, 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipEventRecord(c->ev_bs[s], c->stream));
+  c->bs_rows[s] = nr;
+  c->bs_blocks[s] = nb;
+  c->bs_quorum[s][0] = c->quorum_w[0];
+  c->bs_quorum[s][1] = c->quorum_w[1];
+  c->bs_issued++;
+  return IBFT_OK;
+}
+
+int ibft_block_seals_collect(ibft_ctx *c, uint64_t *out_mask, ibft_tally_t *out_tally) {
+  if (!c) return IBFT_E_INVAL;
+  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself)
+  if (c->bs_collected == c->bs_issued) {
+    c->last_error = "ibft_block_seals_collect without a submitted batch";
+    return IBFT_E_INVAL;
+  }
+  const uint32_t s = c->bs_collected & 1u, nr = c->bs_rows[s], nb = c->bs_blocks[s];
+  if (nr && !out_mask) return IBFT_E_INVAL;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->ev_bs[s]));
+  if (nr) {
+    const size_t mw = (size_t)mask_words(nr);
+    memcpy(out_mask, c->p_mask[s], mw * 8);
+    if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
+  }
+  if (out_tally)
+    for (uint32_t b = 0; b < nb; b++) {  // (no rows at all: every block is empty, power 0 < quorum)
+      ibft_tally_t &t = out_tally[b];
+      memset(&t, 0, sizeof t);
+      t.quorum_lo = c->bs_quorum[s][0];
+      t.quorum_hi = c->bs_quorum[s][1];
+      if (!nr) continue;
+      const uint64_t *r = c->bs_tally[s] + 4ull * b;
+      t.power_lo = r[0];
+      t.power_hi = r[1];
+      t.valid_rows = (uint32_t)(r[2] & 0xFFFFFFFFull);
+      t.distinct_senders = (uint32_t)(r[2] >> 32);
+      t.has_quorum = (uint32_t)r[3];
+    }
+  // The batch is DELIVERED before anything else can fail (the rule of ibft_seals_collect).
+  c->bs_collected++;
+  if (c->cache_on && nr) {  // keys this batch taught the device → tables (build_new_tables drains the main stream when there
+                            // are any — a newer batch in flight included; its results wait in their slot)
+    const uint32_t *lw = reinterpret_cast<const uint32_t *>(c->p_tally[s] + 4);
+    const int rcb = build_new_tables(c, lw[0], lw[1]);
+    if (rcb) c->learn_rc = rcb;
+  }
+  return IBFT_OK;
+}
+
+// Batches in flight, rows and blocks of the oldest (0 when none): a binding sizes its verdict and tally buffers from these.
+int ibft_block_seals_pending(ibft_ctx *c, uint32_t *batches_in_flight, uint32_t *oldest_rows, uint32_t *oldest_blocks) {
+  if (!c) return IBFT_E_INVAL;
+  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself)
+  const bool any = c->bs_collected != c->bs_issued;
+  if (batches_in_flight) *batches_in_flight = c->bs_issued - c->bs_collected;
+  if (oldest_rows) *oldest_rows = any ? c->bs_rows[c->bs_collected & 1u] : 0u;
+  if (oldest_blocks) *oldest_blocks = any ? c->bs_blocks[c->bs_collected & 1u] : 0u;
   return IBFT_OK;
 }
 

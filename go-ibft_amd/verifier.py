@@ -42,11 +42,12 @@ EXPORTS = [
     "ibft_cache_memory", "ibft_tally_prepare", "ibft_comm_info", "ibft_set_seal_digest", "ibft_group_set_seal_digest",
     "ibft_seals_stage_next", "ibft_seals_swap", "ibft_last_cold_table", "ibft_seals_submit", "ibft_seals_collect",
     "ibft_comm_preload", "ibft_issue_probe", "ibft_seals_rows", "ibft_pipeline_stats", "ibft_verify_block_seals",
+    "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
 ]
-# exports younger than version 3: the version that brought them (ibft_verify_block_seals came without a version step: an older
-# build simply lacks it, and BatchVerifier.verify_block_seals raises GpuUnavailable there)
+# exports younger than version 3: the version that brought them (ibft_verify_block_seals and the streamed ibft_block_seals_*
+# came without a version step: an older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
 EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
-OPTIONAL_EXPORTS = {"ibft_verify_block_seals"}
+OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending"}
 COMM_ID_BYTES = 128
 E_RCCL = -8
 
@@ -182,6 +183,12 @@ def load_library() -> C.CDLL:
         L.ibft_pipeline_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if hasattr(L, "ibft_verify_block_seals"):
         L.ibft_verify_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_block_seals_submit"):
+        L.ibft_block_seals_submit.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
+    if hasattr(L, "ibft_block_seals_collect"):
+        L.ibft_block_seals_collect.argtypes = [vp, vp, vp]
+    if hasattr(L, "ibft_block_seals_pending"):
+        L.ibft_block_seals_pending.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.ibft_verify_senders_wire.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.POINTER(Tally)]
     L.ibft_wire_stage_seals.argtypes = [vp]
     L.ibft_verify_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, vp, vp]
@@ -431,6 +438,50 @@ class BatchVerifier:
                   "ibft_verify_block_seals")
         self._staged = n
         return mask_to_bool(mask, n), list(tallies)[:nb]
+
+    # chain sync as a stream: submit(k + 1), collect(k) — at most two batches in flight
+    def _need_block_stream(self):
+        for name in ("ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending"):
+            if not hasattr(self._L, name):
+                raise GpuUnavailable(f"this build of the library has no {name} — rebuild")
+
+    def block_seals_submit(self, block_hash32, seal_off, sig65, signer20, pre_flags=None) -> int:
+        """ibft_block_seals_submit: the batch of verify_block_seals, enqueued and not waited for → its row count.  The arrays
+        are kept alive here until the batch is collected; pass ibft_pinned_alloc memory — pinned_copy() — for the copy to
+        run under the kernels of the batch before."""
+        self._need_block_stream()
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
+        n = len(s)
+        if len(bh) != nb or len(f) != n or int(off[-1]) != n:
+            raise ValueError("block_hash32 needs one row per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        self._chk(self._L.ibft_block_seals_submit(self._h, _p(bh), _p(off), nb, _p(s), _p(f), _p(pre)), "ibft_block_seals_submit")
+        self._block_cols = getattr(self, "_block_cols", []) + [(bh, off, s, f, pre)]
+        self._staged = n
+        return n
+
+    def block_seals_collect(self):
+        """ibft_block_seals_collect: the OLDEST submitted batch → (verdict bool[n], Tally list[n_blocks]), what
+        verify_block_seals returns for it; waits for that batch only"""
+        self._need_block_stream()
+        _, n, nb = self.block_seals_pending()     # the library's own counts size the buffers
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        tallies = (Tally * max(nb, 1))()
+        self._chk(self._L.ibft_block_seals_collect(self._h, _p(mask), tallies), "ibft_block_seals_collect")
+        if getattr(self, "_block_cols", None):
+            self._block_cols.pop(0)
+        return mask_to_bool(mask, n), list(tallies)[:nb]
+
+    def block_seals_pending(self):
+        """ibft_block_seals_pending: (batches in flight, rows of the oldest, blocks of the oldest)"""
+        self._need_block_stream()
+        a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.ibft_block_seals_pending(self._h, C.byref(a), C.byref(b), C.byref(c)), "ibft_block_seals_pending")
+        return int(a.value), int(b.value), int(c.value)
 
     # Verifier.IsValidValidator, batched
     def is_valid_validator(self, payload: bytes, off, sig65, from20, pre_flags=None):

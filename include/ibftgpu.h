@@ -241,7 +241,36 @@ int ibft_verify_block_seals(ibft_ctx *ctx, const uint8_t *block_hash32, const ui
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags,
                             uint64_t *out_mask, ibft_tally_t *out_tally);
 
-/* a3.  payload = concatenated PayloadNoSig bytes; row i is payload[off[i]..off[i+1]);
+/* Streamed chain sync: the batch of ibft_verify_block_seals, submitted and collected in two calls, up to TWO batches in
+ * flight — for a node that checks thousands of batches in a row and should not leave the device idle while the host copies
+ * verdicts out and pushes the next seals across PCIe.  Per step: submit(k + 1), collect(k).
+ *   ibft_block_seals_submit   the arguments and the checks of ibft_verify_block_seals (same codes, same order; a refused call
+ *       takes no slot).  Copies the batch into one of two column sets on the context's copy stream, enqueues the kernels
+ *       behind that copy and returns WITHOUT waiting for the device.  The caller's buffers must stay untouched until the
+ *       collect of this batch has returned.  The copy runs under the kernels of the batch before only from page-locked
+ *       sources (ibft_pinned_alloc); pageable sources give the same results, and the submit then lasts as long as the copy.
+ *       A batch without rows is a legal batch and takes a slot.  IBFT_E_INVAL (ibft_last_error says which): two batches
+ *       already in flight; seal passes of ibft_seals_submit in flight or a batch of ibft_seals_stage_next awaiting its swap —
+ *       the two pipelines share their slots and are not mixed (ibft_seals_submit likewise refuses while block batches are in
+ *       flight).  A batch is judged under the validator set and the seal-digest convention current at ITS submit.
+ *   ibft_block_seals_collect  waits for the OLDEST batch only and delivers what ibft_verify_block_seals would have returned
+ *       for it, bit for bit: out_mask ⌈n/64⌉ words (may be NULL only for a batch without rows), out_tally n_blocks entries
+ *       (may be NULL).  IBFT_E_INVAL with nothing in flight.  With IBFT_FLAG_PUBKEY_CACHE the tables of the keys the batch
+ *       taught the device are built here, after the batch is delivered: that build waits for a newer batch in flight too
+ *       (once per cold-to-warm transition), and if it fails the NEXT submit reports it.
+ *   ibft_block_seals_pending  batches in flight, rows and blocks of the oldest (0, 0 when none): size out_mask / out_tally
+ *       from these.  Any pointer may be NULL.
+ * Every other entry point may be called between a submit and its collect: what it enqueues runs behind the batches in
+ * flight, which stay collectable (their results wait in their slots); ibft_sync waits for them, ibft_ctx_destroy drops
+ * them.  Which form to use (both from pinned sources): from about 16 000 rows per batch on the streamed
+ * one (0.96 / 0.88 × the synchronous call's time per batch cold / warm there, 0.87 / 0.72 × at 65 536 rows); up to a few
+ * thousand rows a batch is a chain of launch latencies with nothing to hide a copy under, and the synchronous call is as fast. */
+int ibft_block_seals_submit(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags);
+int ibft_block_seals_collect(ibft_ctx *ctx, uint64_t *out_mask, ibft_tally_t *out_tally);
+int ibft_block_seals_pending(ibft_ctx *ctx, uint32_t *batches_in_flight, uint32_t *oldest_rows, uint32_t *oldest_blocks);
+
+/* a3. payload = concatenated PayloadNoSig bytes; row i is payload[off[i]..off[i+1]);
  * off has n+1 entries.                                                             */
 int ibft_verify_senders(ibft_ctx *ctx, const uint8_t *payload, const uint32_t *off,
                         const uint8_t *sig65, const uint8_t *from20, const uint8_t *pre_flags,

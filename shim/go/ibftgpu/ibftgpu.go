@@ -29,6 +29,7 @@ import (
 	"fmt"
 	"math/big"
 	"runtime"
+	"sync"
 	"unsafe"
 )
 
@@ -68,6 +69,8 @@ type Ctx struct {
 	// returned, so they are pinned (runtime.Pinner: the collector neither moves nor frees them) until SealsSwap has waited
 	// for that copy
 	next runtime.Pinner
+	// the batches of BlockSealsSubmit not yet collected, oldest first (their columns stay reachable until then)
+	blocks []*blockBatch
 }
 
 // Options mirrors ibft_cfg.  KeyCache turns on the warm path (IBFT_FLAG_PUBKEY_CACHE): the
@@ -111,6 +114,10 @@ func (c *Ctx) Close() {
 		c.h = nil
 	}
 	c.next.Unpin()
+	for _, b := range c.blocks {
+		b.pin.Unpin()
+	}
+	c.blocks = nil
 }
 
 // SetSealDigest tells the context WHAT a committed seal signs in this Backend (core/backend.go:53-55 leaves it open):
@@ -247,6 +254,88 @@ func (c *Ctx) VerifyBlockSeals(blockHash32 []byte, sealOff []uint32, sig65, sign
 	return mask, tallies, nil
 }
 
+// blockBatch keeps the columns of one BlockSealsSubmit reachable — and, where they are Go memory, pinned — until its
+// BlockSealsCollect: the library's copy stream reads them after the cgo call has returned.
+type blockBatch struct {
+	blockHash32, sig65, signer20, preFlags []byte
+	sealOff                                []uint32
+	pin                                    runtime.Pinner
+}
+
+func (b *blockBatch) hold(p unsafe.Pointer) {
+	if p != nil && !inPinnedBytes(p) { // (PinnedBytes memory is C memory: nothing to pin, and Pinner must not see it)
+		b.pin.Pin(p)
+	}
+}
+
+// BlockSealsSubmit enqueues the batch of VerifyBlockSeals and returns without waiting for the device
+// (ibft_block_seals_submit); BlockSealsCollect delivers the OLDEST batch in flight.  At most two batches in flight; per
+// step of a chain sync: BlockSealsSubmit(k+1), BlockSealsCollect(k).  The slices must not be written to before the collect
+// of their batch; carve them from PinnedBytes for the copy to run under the kernels of the batch before.  Not to be mixed
+// with SealsSubmit passes in flight (the library refuses).
+func (c *Ctx) BlockSealsSubmit(blockHash32 []byte, sealOff []uint32, sig65, signer20, preFlags []byte) error {
+	if len(sealOff) == 0 {
+		return fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(blockHash32) < 32*nb || len(sig65) < 65*n || len(signer20) < 20*n || (preFlags != nil && len(preFlags) < n) {
+		return fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	b := &blockBatch{blockHash32: blockHash32, sealOff: sealOff, sig65: sig65, signer20: signer20, preFlags: preFlags}
+	b.hold(unsafe.Pointer(&sealOff[0]))
+	b.hold(unsafe.Pointer(ptr8(blockHash32)))
+	b.hold(unsafe.Pointer(ptr8(sig65)))
+	b.hold(unsafe.Pointer(ptr8(signer20)))
+	b.hold(unsafe.Pointer(ptr8(preFlags)))
+	rc := C.ibft_block_seals_submit(c.h, ptr8(blockHash32), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), C.size_t(nb),
+		ptr8(sig65), ptr8(signer20), ptr8(preFlags))
+	if err := c.check(rc); err != nil {
+		b.pin.Unpin() // a refused submit took no slot and reads nothing
+		return err
+	}
+	c.blocks = append(c.blocks, b)
+	return nil
+}
+
+// BlockSealsPending = batches in flight, rows and blocks of the oldest, as the LIBRARY counts them
+// (ibft_block_seals_pending): what BlockSealsCollect sizes its buffers from.
+func (c *Ctx) BlockSealsPending() (inFlight, oldestRows, oldestBlocks int, err error) {
+	var a, r, b C.uint32_t
+	if err = c.check(C.ibft_block_seals_pending(c.h, &a, &r, &b)); err != nil {
+		return 0, 0, 0, err
+	}
+	return int(a), int(r), int(b), nil
+}
+
+// BlockSealsCollect waits for the oldest submitted batch only and returns what VerifyBlockSeals returns for it
+// (ibft_block_seals_collect); ErrFallback with nothing in flight.
+func (c *Ctx) BlockSealsCollect() ([]uint64, []Tally, error) {
+	inFlight, n, nb, err := c.BlockSealsPending()
+	if err != nil {
+		return nil, nil, err
+	}
+	if inFlight == 0 {
+		return nil, nil, ErrFallback // nothing submitted
+	}
+	mask := make([]uint64, (n+63)/64+1)
+	ct := make([]C.ibft_tally_t, nb+1)
+	rc := C.ibft_block_seals_collect(c.h, (*C.uint64_t)(unsafe.Pointer(&mask[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err := c.check(rc); err != nil {
+		return nil, nil, err
+	}
+	if len(c.blocks) > 0 { // the batch is delivered: the device has read its columns
+		c.blocks[0].pin.Unpin()
+		c.blocks[0] = nil
+		c.blocks = c.blocks[1:]
+	}
+	tallies := make([]Tally, nb)
+	for b := range tallies {
+		tallies[b] = tally(ct[b])
+	}
+	return mask, tallies, nil
+}
+
 // VerifySenders = IsValidValidator over a batch (core/ibft.go:1128); payload is the
 // concatenation of msg.PayloadNoSig(), off its n+1 offsets.
 func (c *Ctx) VerifySenders(payload []byte, off []uint32, sig65, from20, preFlags []byte) ([]uint64, Tally, error) {
@@ -345,14 +434,39 @@ func PinnedBytes(n int) []byte {
 	if p == nil {
 		return make([]byte, n) // ordinary memory works everywhere, only slower
 	}
+	pinnedMu.Lock()
+	pinnedBlocks[uintptr(p)] = uintptr(n)
+	pinnedMu.Unlock()
 	return unsafe.Slice((*byte)(p), n)
 }
 
 // FreePinned releases a slice obtained from PinnedBytes (and only such a slice).
 func FreePinned(b []byte) {
 	if len(b) > 0 {
+		pinnedMu.Lock()
+		delete(pinnedBlocks, uintptr(unsafe.Pointer(&b[0])))
+		pinnedMu.Unlock()
 		C.ibft_pinned_free(unsafe.Pointer(&b[0]))
 	}
+}
+
+// The blocks PinnedBytes handed out: C memory, which runtime.Pinner must never be given (it panics on a pointer that is
+// not a Go pointer before Go 1.22).  inPinnedBytes tells whether an address lies in one of them.
+var (
+	pinnedMu     sync.Mutex
+	pinnedBlocks = map[uintptr]uintptr{}
+)
+
+func inPinnedBytes(p unsafe.Pointer) bool {
+	a := uintptr(p)
+	pinnedMu.Lock()
+	defer pinnedMu.Unlock()
+	for base, n := range pinnedBlocks {
+		if a >= base && a < base+n {
+			return true
+		}
+	}
+	return false
 }
 
 // WireRow is what the device found in one IbftMessage (ibft_wire_row_t).
