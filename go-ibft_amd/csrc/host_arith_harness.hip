@@ -249,6 +249,41 @@ uint32_t dev_addr_hash(const uint8_t *addr20) {
   return ibftk::addr_hash(a);
 }
 
+// The emitting cold kernels' epilogue (recover_dev.h: emit_row) behind the lane kernel's recovery, over a validator table built
+// as ibft_set_validators builds it (open addressing, 6 dwords per slot, a repeated address keeps its first index).
+// out_addr20: what the row stores; *out_vidx: its validator index; returns the verdict bit.
+int dev_emit_row(const uint8_t *digest32, const uint8_t *sig65, uint32_t flags, int pre, const uint8_t *addrs20, uint32_t n_validators,
+                 uint8_t *out_addr20, int32_t *out_vidx) {
+  dev_gtab_init();
+  uint32_t slots = 64;
+  while (slots < 2 * n_validators + 2) slots <<= 1;
+  std::vector<uint32_t> tab((size_t)slots * 6, 0u);
+  uint32_t next = 0;
+  for (uint32_t i = 0; i < n_validators; i++) {
+    uint32_t a[5];
+    memcpy(a, addrs20 + 20 * (size_t)i, 20);
+    uint32_t s = ibftk::addr_hash(a) & (slots - 1);
+    for (;;) {
+      uint32_t *e = &tab[(size_t)s * 6];
+      if (e[5] == 0) {
+        memcpy(e, a, 20);
+        e[5] = ++next;
+        break;
+      }
+      if (memcmp(e, a, 20) == 0) break;
+      s = (s + 1) & (slots - 1);
+    }
+  }
+  uint32_t got[5];
+  ibftk::aff Qa;
+  const bool rec = ibftk::recover_pubkey_with(g_gtab.data(), secp::from_be32(digest32), secp::from_be32(sig65), secp::from_be32(sig65 + 32),
+                                              sig65[64], flags, got, Qa, ibftk::var_mult_private<false>{});
+  const ibftk::emitted e = ibftk::emit_row(rec, pre != 0, got, tab.data(), slots - 1);
+  memcpy(out_addr20, e.addr, 20);
+  *out_vidx = e.vi;
+  return e.bit ? 1 : 0;
+}
+
 // §8f rank 3: the device wire walker on the CPU.  out: row_info (80 B) ‖ digest (32) ‖ sig (65) ‖ from (20)
 // ‖ seal (65) ‖ pre_flag (1) = 263 bytes
 void dev_wire_row(const uint8_t *m, uint32_t n, uint8_t *out263) {

@@ -92,6 +92,7 @@ struct ibft_ctx {
 
   // columns in HBM
   DevBuf d_hash, d_sig, d_signer, d_pre, d_hash_len, d_payload, d_off, d_raw;
+  DevBuf d_signer_out;  // the address column the emitting cold kernels write (ibft_recover_seals / ibft_recover_block_seals)
   // the SECOND staging slot of the seal columns (ibft_seals_stage_next / ibft_seals_swap): batch k+1 is copied here on a
   // copy stream of its own while the verdict kernels read batch k from the columns above; a swap exchanges the two sets
   DevBuf d_hash_nx, d_sig_nx, d_signer_nx, d_pre_nx;
@@ -318,6 +319,7 @@ int alloc_rows(ibft_ctx *c, uint32_t rows) {
   if ((rc = ensure(c, c->d_hash, m * 32))) return rc;
   if ((rc = ensure(c, c->d_sig, m * 65 + 64))) return rc;
   if ((rc = ensure(c, c->d_signer, m * 20))) return rc;
+  if ((rc = ensure(c, c->d_signer_out, m * 20))) return rc;
   if ((rc = ensure(c, c->d_pre, m))) return rc;
   if ((rc = ensure(c, c->d_hash_len, m))) return rc;
   if ((rc = ensure(c, c->d_off, (m + 1) * 4))) return rc;
@@ -358,6 +360,7 @@ ibftk::recover_args make_args(ibft_ctx *c, uint32_t n, bool with_pre, uint32_t r
   a.flags = c->flags;
   a.mask = (uint64_t *)c->d_mask.p + row_base / 64;
   a.vidx = (int32_t *)c->d_vidx.p + row_base;
+  a.signer_out = (uint8_t *)c->d_signer_out.p + 20ull * row_base;
   if (c->cache_on) {  // (the caller holds c->dev->mu: the pointers cannot move before the launch is enqueued)
     a.pub = (uint32_t *)c->dev->d_pub.p;
     a.pub_state = (uint32_t *)c->dev->d_state.p;
@@ -415,6 +418,9 @@ struct ctx_lock {
 
 // enqueue the verdict kernels over the resident columns: warm kernel first when tables exist
 // (its rows are then skipped by the recover kernel), recover kernel for everything else
+// mode: ibftk::MODE_SEALS / MODE_SENDERS, or MODE_EMIT (ibft_recover_seals: bare seals, the recovered address goes to
+// d_signer_out) — always the cold branch, no warm stage in front even when tables are built: a warm kernel needs a claimed key to
+// pick a table.  Thresholds, pins and the split are those of the other modes.
 // keep_mask: a second batch of the same call (rows [row_base, row_base + n)): the work mask already holds the first batch's
 // bits and must not be zeroed again (the caller saw to it that this batch's words are clean)
 // validators of this context's set whose table is built, recounted when a build pass has run since the last count
@@ -478,7 +484,7 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(e0, c->stream));
   }
-  const bool warm = c->cache_on && c->my_built > 0;
+  const bool warm = c->cache_on && c->my_built > 0 && mode != ibftk::MODE_EMIT;
   if (warm) {
     a.warm_done = (uint8_t *)c->d_warm_done.p + row_base;
     // lanes per signature: ≈ one wavefront per SIMD (1024 SIMDs × 64 lanes / n rows), a power of two
@@ -555,12 +561,16 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
       const dim3 pgrid((waves + ibftk::ROWS_PAIRS_PER_BLOCK - 1) / ibftk::ROWS_PAIRS_PER_BLOCK), pblock(128 * ibftk::ROWS_PAIRS_PER_BLOCK);
       if (mode == 0)
         hipLaunchKernelGGL(ibftk::ecrecover_rows_pair_kernel<0>, pgrid, pblock, 0, c->stream, a);
+      else if (mode == ibftk::MODE_EMIT)
+        hipLaunchKernelGGL(ibftk::ecrecover_rows_pair_kernel<ibftk::MODE_EMIT>, pgrid, pblock, 0, c->stream, a);
       else
         hipLaunchKernelGGL(ibftk::ecrecover_rows_pair_kernel<1>, pgrid, pblock, 0, c->stream, a);
     } else {
       const dim3 rgrid((waves + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES), rblock(64 * ibftk::WAVE_KERNEL_WAVES);
       if (mode == 0)
         hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<0>, rgrid, rblock, 0, c->stream, a);
+      else if (mode == ibftk::MODE_EMIT)
+        hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<ibftk::MODE_EMIT>, rgrid, rblock, 0, c->stream, a);
       else
         hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<1>, rgrid, rblock, 0, c->stream, a);
     }
@@ -569,12 +579,17 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
     const dim3 pgrid((n + ibftk::PAIRS_PER_BLOCK - 1) / ibftk::PAIRS_PER_BLOCK), pblock(128 * ibftk::PAIRS_PER_BLOCK);
     if (mode == 0)
       hipLaunchKernelGGL(ibftk::ecrecover_wave2_kernel<0>, pgrid, pblock, 0, c->stream, a);
+    else if (mode == ibftk::MODE_EMIT)
+      hipLaunchKernelGGL(ibftk::ecrecover_wave2_kernel<ibftk::MODE_EMIT>, pgrid, pblock, 0, c->stream, a);
     else
       hipLaunchKernelGGL(ibftk::ecrecover_wave2_kernel<1>, pgrid, pblock, 0, c->stream, a);
   } else if (CG == 64) {
     if (!warm && (rc_clean = clean_mask(c))) return rc_clean;
     if (mode == 0)
       hipLaunchKernelGGL(ibftk::ecrecover_wave_kernel<0>, dim3((n + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES),
+                         dim3(64 * ibftk::WAVE_KERNEL_WAVES), 0, c->stream, a);
+    else if (mode == ibftk::MODE_EMIT)
+      hipLaunchKernelGGL(ibftk::ecrecover_wave_kernel<ibftk::MODE_EMIT>, dim3((n + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES),
                          dim3(64 * ibftk::WAVE_KERNEL_WAVES), 0, c->stream, a);
     else
       hipLaunchKernelGGL(ibftk::ecrecover_wave_kernel<1>, dim3((n + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES),
@@ -590,6 +605,10 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
     hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<0, GG, ibftk::TAB_LDS>), cgrid, cblock, 0, c->stream, a);       \
   else if (mode == 0)                                                                                                 \
     hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<0, GG, ibftk::TAB_PRIVATE_PREFETCH>), cgrid, cblock, 0, c->stream, a); \
+  else if (mode == ibftk::MODE_EMIT && lds_tab)                                                                       \
+    hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<ibftk::MODE_EMIT, GG, ibftk::TAB_LDS>), cgrid, cblock, 0, c->stream, a); \
+  else if (mode == ibftk::MODE_EMIT)                                                                                  \
+    hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<ibftk::MODE_EMIT, GG, ibftk::TAB_PRIVATE_PREFETCH>), cgrid, cblock, 0, c->stream, a); \
   else if (lds_tab)                                                                                                   \
     hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<1, GG, ibftk::TAB_LDS>), cgrid, cblock, 0, c->stream, a);       \
   else                                                                                                                \
@@ -609,6 +628,8 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
 #define IBFT_LAUNCH_LANE(TT)                                                                       \
   if (mode == 0)                                                                                   \
     hipLaunchKernelGGL((ibftk::ecrecover_lane_kernel<0, TT>), grid, block, 0, c->stream, a);       \
+  else if (mode == ibftk::MODE_EMIT)                                                               \
+    hipLaunchKernelGGL((ibftk::ecrecover_lane_kernel<ibftk::MODE_EMIT, TT>), grid, block, 0, c->stream, a); \
   else                                                                                             \
     hipLaunchKernelGGL((ibftk::ecrecover_lane_kernel<1, TT>), grid, block, 0, c->stream, a);
     switch (tab) {
@@ -1528,7 +1549,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
   if (c->hstream) (void)hipStreamSynchronize(c->hstream);
   if (c->tstream) (void)hipStreamSynchronize(c->tstream);
   if (c->cstream) (void)hipStreamSynchronize(c->cstream);  // block batches in flight are drained, never delivered
-  for (DevBuf *b : {&c->d_hash, &c->d_sig, &c->d_signer, &c->d_pre, &c->d_hash_len, &c->d_payload,
+  for (DevBuf *b : {&c->d_hash, &c->d_sig, &c->d_signer, &c->d_signer_out, &c->d_pre, &c->d_hash_len, &c->d_payload,
                     &c->d_off, &c->d_raw, &c->d_mask, &c->d_mask_out, &c->d_vidx, &c->d_tally, &c->d_H,
                     &c->d_vtab, &c->d_vpower, &c->d_vslot,
                     &c->d_warm_done, &c->d_seen, &c->d_acc, &c->d_quorum, &c->d_wire_rows, &c->d_seal,
@@ -1943,9 +1964,10 @@ int ibft_verify_hashes_digest(ibft_ctx *c, const uint8_t digest32[32], const uin
   return hash_eq_locked(c, hash32, hash_len, n, out_mask);
 }
 
+// bare: the rows are bare seals (ibft_recover_seals) — there is no signer column to stage
 static int seals_stage_locked(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65, const uint8_t *signer20,
-                              const uint8_t *pre_flags, size_t n, bool wait) {
-  if (n && (!hash32 || !sig65 || !signer20)) return IBFT_E_INVAL;
+                              const uint8_t *pre_flags, size_t n, bool wait, bool bare = false) {
+  if (n && (!hash32 || !sig65 || (!bare && !signer20))) return IBFT_E_INVAL;
   if (n > c->max_rows) return IBFT_E_TOOBIG;
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
@@ -1953,7 +1975,7 @@ static int seals_stage_locked(ibft_ctx *c, const uint8_t *hash32, const uint8_t 
   ColumnCopies cc;
   cc.add(c->d_hash.p, hash32, n * 32);
   cc.add(c->d_sig.p, sig65, n * 65);
-  cc.add(c->d_signer.p, signer20, n * 20);
+  if (!bare) cc.add(c->d_signer.p, signer20, n * 20);
   if (pre_flags) cc.add(c->d_pre.p, pre_flags, n);
   if ((rc = cc.flush(c))) return rc;
   if ((rc = apply_seal_digest(c, 0, (uint32_t)n, false))) return rc;
@@ -2039,7 +2061,7 @@ int ibft_seals_swap(ibft_ctx *c, int wait_for_copy) {
   return IBFT_OK;
 }
 
-static int seals_launch_locked(ibft_ctx *c, uint32_t repeat) {
+static int seals_launch_locked(ibft_ctx *c, uint32_t repeat, int mode = ibftk::MODE_SEALS) {
   if (!c->have_valset) return IBFT_E_NOVALSET;
   HIPCHK(c, hipSetDevice(c->device));
   if (c->ev_used >= 4096) c->ev_used = 0;  // event pairs accumulate until ibft_last_kernel_ms reads (and resets) them
@@ -2048,7 +2070,7 @@ static int seals_launch_locked(ibft_ctx *c, uint32_t repeat) {
   for (uint32_t k = 0; k < repeat; k++) {
     int rc;
     const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
-    if ((rc = enqueue_recover(c, c->staged_n, c->staged_pre, 0, time_it))) return rc;
+    if ((rc = enqueue_recover(c, c->staged_n, c->staged_pre, mode, time_it))) return rc;
     if ((rc = enqueue_tally(c, c->staged_n))) return rc;
   }
   return IBFT_OK;
@@ -2586,6 +2608,30 @@ int ibft_verify_seals(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65, 
   return fetch_results(c, c->staged_n, out_mask, tally, true);
 }
 
+// The emitted columns of the last MODE_EMIT launch → the caller's buffers, on the main stream (behind the tally, which only
+// reads the validator indices).  The caller synchronises.
+static int copy_emitted(ibft_ctx *c, size_t n, uint8_t *out_signer20, int32_t *out_vidx) {
+  if (!n) return IBFT_OK;
+  HIPCHK(c, hipMemcpyAsync(out_signer20, c->d_signer_out.p, n * 20, hipMemcpyDeviceToHost, c->stream));
+  if (out_vidx) HIPCHK(c, hipMemcpyAsync(out_vidx, c->d_vidx.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+  return IBFT_OK;
+}
+
+// Bare seals: who signed?  The cold kernels in their emitting form, then the tally over the validator indices they found.
+int ibft_recover_seals(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65, const uint8_t *pre_flags, size_t n,
+                       uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *tally) {
+  if (!c || (n && (!out_signer20 || !out_mask))) return IBFT_E_INVAL;
+  ctx_lock lk(c);  // one critical section: stage + launch + fetch
+  if (!c->have_valset) return IBFT_E_NOVALSET;
+  int rc;
+  if ((rc = seals_stage_locked(c, hash32, sig65, nullptr, pre_flags, n, false, true))) return rc;
+  if ((rc = seals_launch_locked(c, 1, ibftk::MODE_EMIT))) return rc;
+  if ((rc = copy_emitted(c, n, out_signer20, out_vidx))) return rc;
+  rc = fetch_results(c, (uint32_t)n, out_mask, tally, true);
+  c->staged_n = 0;  // bare rows are no resident batch: there is no signer column ibft_seals_launch could judge them against
+  return rc;
+}
+
 // The segmented tally of a block batch over the resident work mask / validator indices and the offsets in d_boff, on the main
 // stream.  Work mask, d_seen and the ticket word in d_acc exist once per context: two batches in flight (ibft_block_seals_submit)
 // take turns at them in main-stream order.
@@ -2631,9 +2677,24 @@ static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t w
 
 // Chain sync: the committed seals of n_blocks finalized blocks — one upload, one verdict launch over every row (the AUTO rule
 // sees the TOTAL row count), one segmented tally (block_tally_kernel), one synchronisation.
+// bare: ibft_recover_block_seals — no signer20 column; the emitting kernels fill out_signer20 / out_vidx and the validator
+// indices the tally reads.
+static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
+                            uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally);
 int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, uint64_t *out_mask,
                             ibft_tally_t *out_tally) {
+  return block_seals_impl(c, block_hash32, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally);
+}
+int ibft_recover_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                             const uint8_t *sig65, const uint8_t *pre_flags, uint8_t *out_signer20, int32_t *out_vidx,
+                             uint64_t *out_mask, ibft_tally_t *out_tally) {
+  return block_seals_impl(c, block_hash32, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally);
+}
+static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
+                            uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally) {
   if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
   if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;  // (max_rows never changes after ibft_ctx_create)
   uint32_t widest = 0;  // rows of the largest block: picks the tally's workgroup size
@@ -2643,7 +2704,7 @@ int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint
   }
   const size_t n = seal_off[n_blocks];
   if (n > c->max_rows) return IBFT_E_TOOBIG;
-  if (n && (!block_hash32 || !sig65 || !signer20 || !out_mask)) return IBFT_E_INVAL;
+  if (n && (!block_hash32 || !sig65 || (bare ? !out_signer20 : !signer20) || !out_mask)) return IBFT_E_INVAL;
   ctx_lock lk(c);
   if (!c->have_valset) return IBFT_E_NOVALSET;
   HIPCHK(c, hipSetDevice(c->device));
@@ -2671,7 +2732,7 @@ int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint
     cc.add(c->d_boff.p, seal_off, ((size_t)nb + 1) * 4);
     cc.add(c->d_bhash.p, block_hash32, (size_t)nb * 32);
     cc.add(c->d_sig.p, sig65, n * 65);
-    cc.add(c->d_signer.p, signer20, n * 20);
+    if (!bare) cc.add(c->d_signer.p, signer20, n * 20);
     if (pre_flags) cc.add(c->d_pre.p, pre_flags, n);
     if ((rc = cc.flush(c))) return rc;
     if ((rc = seal_digest_column(c, (uint8_t *)c->d_bhash.p, nb))) return rc;
@@ -2685,8 +2746,9 @@ int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint
   if (nr) {
     if (c->ev_used >= 4096) c->ev_used = 0;
     const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
-    if ((rc = enqueue_recover(c, nr, c->staged_pre, 0, time_it))) return rc;
+    if ((rc = enqueue_recover(c, nr, c->staged_pre, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
     if ((rc = enqueue_block_tally(c, nb, nr, widest, c->dh_mask, c->dh_btally ? c->dh_btally : (uint64_t *)c->d_btally.p))) return rc;
+    if (bare && (rc = copy_emitted(c, nr, out_signer20, out_vidx))) return rc;
     c->host_direct = false;
     const size_t mw = (size_t)mask_words(nr);
     if (!c->dh_mask) HIPCHK(c, hipMemcpyAsync(c->h_mask, c->d_mask_out.p, mw * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2701,6 +2763,7 @@ int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint
     memcpy(out_mask, c->h_mask, mw * 8);
     if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
   }
+  if (bare) c->staged_n = 0;  // (as after ibft_recover_seals: bare rows are no resident batch)
   if (out_tally)
     for (uint32_t b = 0; b < nb; b++) {  // (no rows at all: every block is empty, power 0 < quorum)
       ibft_tally_t &t = out_tally[b];

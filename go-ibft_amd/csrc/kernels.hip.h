@@ -45,20 +45,8 @@ using secp::u256;
 
 constexpr int ROWS_PER_BLOCK = 64; // one wavefront per block in the lane kernel
 
-// ---- validator table lookup (open addressing, linear probing) ----------------------
-__device__ __forceinline__ int valset_lookup(const uint32_t *__restrict__ vtab, uint32_t slot_mask,
-                                             const uint32_t a[5]) {
-  uint32_t s = addr_hash(a) & slot_mask;
-  for (uint32_t probe = 0; probe <= slot_mask; probe++) {
-    const uint32_t *e = vtab + 6u * s;
-    uint32_t tag = e[5];
-    if (tag == 0) return -1;
-    if (e[0] == a[0] && e[1] == a[1] && e[2] == a[2] && e[3] == a[3] && e[4] == a[4])
-      return (int)tag - 1;
-    s = (s + 1) & slot_mask;
-  }
-  return -1;
-}
+// (validator table lookup — valset_lookup — and the emitting form's decision — emit_row — live in recover_dev.h: the CPU harness
+// compiles them too)
 
 // ---- warm path: remember a recovered key, exactly once per validator ---------------------------
 // Several valid rows of the SAME validator in one cold batch are normal (PREPARE + COMMIT of one
@@ -303,7 +291,13 @@ struct recover_args {
   // slot — and its table — across validator-set changes): vslot[validator index] = the slot of that validator's
   // address in pub / pub_state / qtab, 0xFFFFFFFF = none (the pool is full: the validator stays on the recover path).
   const uint32_t *vslot;
+  uint8_t *signer_out;      // MODE_EMIT: n×20, the address recovered from each row (zeros where there is none)
 };
+// MODE of the cold kernels.  MODE_SEALS / MODE_SENDERS answer "did signer20[row] sign": digest = the hash32 row / keccak256 of
+// the payload row.  MODE_EMIT answers "who signed" for bare seals (digest as MODE_SEALS): no signer20 column is read, the
+// recovered address is stored, and membership is that of the RECOVERED address — so only pre_flags and `live` decide whether a
+// row needs the curve.  The verify kernels of the warm path know MODE_SEALS and MODE_SENDERS only.
+constexpr int MODE_SEALS = 0, MODE_SENDERS = 1, MODE_EMIT = 2;
 __device__ __forceinline__ int key_slot(const recover_args &a, int vi) { return (int)a.vslot[vi]; }
 // states of a key-cache slot.  0 → WRITING (claimed by one row's compare-and-swap) → KNOWN (the key is in `pub`) → BUILDING
 // (claimed by one build pass: keys that become KNOWN while the pass runs wait for the next one) → BUILT (the table is complete)
@@ -320,6 +314,20 @@ __device__ __forceinline__ void learn_key(const recover_args &a, int vi, const a
   __hip_atomic_store(a.pub_state + sl, KEY_KNOWN, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   atomicAdd(a.learned, 1u);
   a.learned[1] = (uint32_t)sl;  // any learned slot: operand for idle lanes of the warm kernel
+}
+
+// MODE_EMIT: one lane of a row stores what emit_row decided — the address column and the validator index; the verdict bit goes
+// the way the kernel stores its bits.  Rows past n never come here.
+__device__ __forceinline__ void emit_store(const recover_args &a, uint32_t row, const emitted &e) {
+  uint32_t *o = reinterpret_cast<uint32_t *>(a.signer_out + 20ull * row);
+#pragma unroll
+  for (int i = 0; i < 5; i++) o[i] = e.addr[i];
+  a.vidx[row] = e.vi;
+}
+// ... and what a row that never reaches the curve (pre_flags) stores
+__device__ __forceinline__ void emit_store_none(const recover_args &a, uint32_t row) {
+  const uint32_t none[5] = {0u, 0u, 0u, 0u, 0u};
+  emit_store(a, row, emit_row(false, true, none, a.vtab, a.vslot_mask));
 }
 
 // Stage the block's rows through LDS (coalesced dword loads) and unpack this lane's row.
@@ -344,9 +352,11 @@ __device__ __forceinline__ row_regs stage_rows(const recover_args &a, uint8_t *l
     const uint32_t *g = reinterpret_cast<const uint32_t *>(a.sig65 + 65ull * row0);
     for (uint32_t i = lane; i < nb / 4; i += ROWS_PER_BLOCK) reinterpret_cast<uint32_t *>(l_sig)[i] = g[i];
     for (uint32_t i = (nb & ~3u) + lane; i < nb; i += ROWS_PER_BLOCK) l_sig[i] = a.sig65[65ull * row0 + i];
-    const uint32_t *gf = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row0);
-    for (uint32_t i = lane; i < rows * 5; i += ROWS_PER_BLOCK) reinterpret_cast<uint32_t *>(l_from)[i] = gf[i];
-    if (MODE == 0) {
+    if (MODE != MODE_EMIT) {
+      const uint32_t *gf = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row0);
+      for (uint32_t i = lane; i < rows * 5; i += ROWS_PER_BLOCK) reinterpret_cast<uint32_t *>(l_from)[i] = gf[i];
+    }
+    if (MODE != MODE_SENDERS) {
       const uint4 *gh = reinterpret_cast<const uint4 *>(a.hash32 + 32ull * row0);
       for (uint32_t i = lane; i < rows * 2; i += ROWS_PER_BLOCK) reinterpret_cast<uint4 *>(l_hash)[i] = gh[i];
     }
@@ -360,7 +370,7 @@ __device__ __forceinline__ row_regs stage_rows(const recover_args &a, uint8_t *l
   q.r = secp::from_be32(l_sig + 65 * lrow);
   q.s = secp::from_be32(l_sig + 65 * lrow + 32);
   q.v = l_sig[65 * lrow + 64];
-  if (MODE == 0) {
+  if (MODE != MODE_SENDERS) {
     q.z = secp::from_be32(l_hash + 32 * lrow);
   } else {
     uint64_t d[4];
@@ -369,11 +379,11 @@ __device__ __forceinline__ row_regs stage_rows(const recover_args &a, uint8_t *l
     keccak::digest_to_limbs(d, q.z.v);
   }
 #pragma unroll
-  for (int i = 0; i < 5; i++) q.want[i] = reinterpret_cast<const uint32_t *>(l_from)[5 * lrow + i];
+  for (int i = 0; i < 5; i++) q.want[i] = MODE != MODE_EMIT ? reinterpret_cast<const uint32_t *>(l_from)[5 * lrow + i] : 0u;
   return q;
 }
 
-// MODE 0: seals (digest = hash32 row).  MODE 1: senders (digest = keccak256(payload row)).
+// MODE: MODE_SEALS / MODE_SENDERS / MODE_EMIT (above recover_args).
 // TAB: where the per-lane window table of u2·R lives (recover_dev.h) —
 //   TAB_LDS      in the workgroup's LDS (640 B per lane: one wavefront per SIMD, what a batch of ≤ 65 536 rows offers anyway);
 //                no private segment at all: the launch moves the rows, the G-table lines and nothing else through HBM;
@@ -404,13 +414,22 @@ __global__ void __launch_bounds__(ROWS_PER_BLOCK) ecrecover_lane_kernel(recover_
     rec = recover_pubkey_with(a.gtab, q.z, q.r, q.s, q.v, a.flags, got, Qa, var_mult_lds<ROWS_PER_BLOCK>{ldsw + lane});
   else
     rec = recover_pubkey_with(a.gtab, q.z, q.r, q.s, q.v, a.flags, got, Qa, var_mult_private<TAB == TAB_PRIVATE_PREFETCH>{});
-  bool ok = need && !q.pre && rec;
+  bool ok;
+  int vi;
+  if (MODE == MODE_EMIT) {
+    const emitted e = emit_row(rec, q.pre, got, a.vtab, a.vslot_mask);
+    if (need) emit_store(a, q.row, e);
+    ok = need && e.bit;
+    vi = e.vi;
+  } else {
+    ok = need && !q.pre && rec;
 #pragma unroll
-  for (int i = 0; i < 5; i++) ok = ok && (got[i] == q.want[i]);
-  // membership: "the signer address is one of the validators" (backend.go:44, 53-54)
-  int vi = valset_lookup(a.vtab, a.vslot_mask, q.want);
-  ok = ok && vi >= 0;
-  if (need) a.vidx[q.row] = vi;
+    for (int i = 0; i < 5; i++) ok = ok && (got[i] == q.want[i]);
+    // membership: "the signer address is one of the validators" (backend.go:44, 53-54)
+    vi = valset_lookup(a.vtab, a.vslot_mask, q.want);
+    ok = ok && vi >= 0;
+    if (need) a.vidx[q.row] = vi;
+  }
   // a key that hashes to a member's address is remembered for the warm path
   if (ok) learn_key(a, vi, Qa);
   uint64_t bal = __ballot(ok);
@@ -650,7 +669,7 @@ __global__ void __launch_bounds__(64) ecrecover_group_kernel(recover_args a) {
   u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
   const uint32_t v = a.sig65[65ull * row + 64];
   u256 z;
-  if (MODE == 0) {
+  if (MODE != MODE_SENDERS) {
     z = secp::from_be32(a.hash32 + 32ull * row);
   } else {
     uint64_t d[4];
@@ -659,7 +678,7 @@ __global__ void __launch_bounds__(64) ecrecover_group_kernel(recover_args a) {
   }
   uint32_t want[5];
 #pragma unroll
-  for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
+  for (int i = 0; i < 5; i++) want[i] = MODE != MODE_EMIT ? reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i] : 0u;
 
   bool ok = sig_in_range(r, s, v, a.flags);
   // R = (r, y), y² = r³ + 7, parity(y) = v
@@ -845,13 +864,21 @@ __global__ void __launch_bounds__(64) ecrecover_group_kernel(recover_args a) {
   u256 qx = secp::l26_to_u256(Qa.x), qy = secp::l26_to_u256(Qa.y);
   uint32_t got[5];
   keccak::address_from_xy(qx.v, qy.v, got);
-  ok = ok && need && !pre;
+  int vi;
+  if (MODE == MODE_EMIT) {
+    const emitted e = emit_row(ok, pre, got, a.vtab, a.vslot_mask);
+    if (sub == 0 && need) emit_store(a, row, e);
+    ok = e.bit;
+    vi = e.vi;
+  } else {
+    ok = ok && need && !pre;
 #pragma unroll
-  for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
-  int vi = valset_lookup(a.vtab, a.vslot_mask, want);
-  ok = ok && vi >= 0;
+    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+    vi = valset_lookup(a.vtab, a.vslot_mask, want);
+    ok = ok && vi >= 0;
+    if (sub == 0 && need) a.vidx[row] = vi;
+  }
   if (sub == 0 && need) {
-    a.vidx[row] = vi;
     if (ok) learn_key(a, vi, Qa);
     if (ok) atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
   }
@@ -869,17 +896,27 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) ecrecover_wave_kernel(
   if (row >= a.n) return;                            // whole wavefront
   if (a.warm_done && a.warm_done[row] != 0) return;  // decided by the warm kernel
   uint32_t want[5];
+  int vi = -1;
+  if (MODE != MODE_EMIT) {
 #pragma unroll
-  for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
-  const int vi = valset_lookup(a.vtab, a.vslot_mask, want);
+    for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
+    vi = valset_lookup(a.vtab, a.vslot_mask, want);
+  }
   const bool pre = a.pre_flags && a.pre_flags[row] != 0;
-  if (lane == 0) a.vidx[row] = vi;
-  if (pre || vi < 0) return;  // verdict stays 0 (mask was cleared by the host before the launch)
+  if (MODE == MODE_EMIT) {
+    if (pre) {  // nothing to recover: zeros, -1, verdict 0
+      if (lane == 0) emit_store_none(a, row);
+      return;
+    }
+  } else {
+    if (lane == 0) a.vidx[row] = vi;
+    if (pre || vi < 0) return;  // verdict stays 0 (mask was cleared by the host before the launch)
+  }
   const u256 r = secp::from_be32(a.sig65 + 65ull * row);
   const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
   const uint32_t v = a.sig65[65ull * row + 64];
   u256 z;
-  if (MODE == 0) {
+  if (MODE != MODE_SENDERS) {
     z = secp::from_be32(a.hash32 + 32ull * row);
   } else {
     uint64_t d[4];
@@ -889,8 +926,15 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) ecrecover_wave_kernel(
   uint32_t got[5];
   aff Qa;
   bool ok = wv::recover_pubkey_wave(a.gtab, z, r, s, v, a.flags, got, Qa);
+  if (MODE == MODE_EMIT) {
+    const emitted e = emit_row(ok, false, got, a.vtab, a.vslot_mask);
+    if (lane == 0) emit_store(a, row, e);
+    ok = e.bit;
+    vi = e.vi;
+  } else {
 #pragma unroll
-  for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+  }
   if (lane == 0 && ok) {
     learn_key(a, vi, Qa);
     atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
@@ -916,14 +960,19 @@ __global__ void __launch_bounds__(128 * PAIRS_PER_BLOCK) ecrecover_wave2_kernel(
   const uint32_t row = live ? row_raw : a.n - 1;
   const bool done = a.warm_done && a.warm_done[row] != 0;
   uint32_t want[5];
+  int vi = -1;
+  if (MODE != MODE_EMIT) {
 #pragma unroll
-  for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
-  const int vi = valset_lookup(a.vtab, a.vslot_mask, want);
+    for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
+    vi = valset_lookup(a.vtab, a.vslot_mask, want);
+  }
   const bool pre = a.pre_flags && a.pre_flags[row] != 0;
-  if (!helper && lane == 0 && live && !done) a.vidx[row] = vi;
-  const bool active = live && !done && !pre && vi >= 0;  // the same for both wavefronts of the pair
+  if (MODE != MODE_EMIT && !helper && lane == 0 && live && !done) a.vidx[row] = vi;
+  // the same for both wavefronts of the pair (MODE_EMIT: membership is not known before the recovery)
+  const bool active = live && !done && !pre && (MODE == MODE_EMIT || vi >= 0);
   auto sync = [] { __syncthreads(); };
   if (!active) {  // (wave-uniform) nothing to recover: keep the workgroup's barrier count
+    if (MODE == MODE_EMIT && !helper && lane == 0 && live && !done) emit_store_none(a, row);  // (a pre_flags row)
     sync();
     sync();
     return;
@@ -932,7 +981,7 @@ __global__ void __launch_bounds__(128 * PAIRS_PER_BLOCK) ecrecover_wave2_kernel(
   const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
   const uint32_t v = a.sig65[65ull * row + 64];
   u256 z;
-  if (MODE == 0) {
+  if (MODE != MODE_SENDERS) {
     z = secp::from_be32(a.hash32 + 32ull * row);
   } else {
     uint64_t d[4];
@@ -946,8 +995,15 @@ __global__ void __launch_bounds__(128 * PAIRS_PER_BLOCK) ecrecover_wave2_kernel(
   uint32_t got[5];
   aff Qa;
   bool ok = wv::recover_pubkey_wave<99, true>(a.gtab, z, r, s, v, a.flags, got, Qa, &sh[slot], sync);
+  if (MODE == MODE_EMIT) {
+    const emitted e = emit_row(ok, false, got, a.vtab, a.vslot_mask);
+    if (lane == 0) emit_store(a, row, e);
+    ok = e.bit;
+    vi = e.vi;
+  } else {
 #pragma unroll
-  for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+  }
   if (lane == 0 && ok) {
     learn_key(a, vi, Qa);
     atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
@@ -969,19 +1025,25 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) __attribute__((amdgpu_
   const bool live = row_raw < a.n;
   const uint32_t row = live ? row_raw : a.n - 1;
   uint32_t want[5];
+  int vi = -1;
+  if (MODE != MODE_EMIT) {
 #pragma unroll
-  for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
-  const int vi = valset_lookup(a.vtab, a.vslot_mask, want);
+    for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
+    vi = valset_lookup(a.vtab, a.vslot_mask, want);
+  }
   const bool pre = a.pre_flags && a.pre_flags[row] != 0;
   const bool done = a.warm_done && a.warm_done[row] != 0;
   const bool need = live && !done;
-  if (need && (lane & 15u) == 0) a.vidx[row] = vi;
-  if (!__any((need && !pre && vi >= 0) ? 1 : 0)) return;  // nothing in this wavefront needs the curve
+  if (MODE != MODE_EMIT && need && (lane & 15u) == 0) a.vidx[row] = vi;
+  if (!__any((need && !pre && (MODE == MODE_EMIT || vi >= 0)) ? 1 : 0)) {  // nothing in this wavefront needs the curve
+    if (MODE == MODE_EMIT && need && (lane & 15u) == 0) emit_store_none(a, row);  // (every row left is a pre_flags row)
+    return;
+  }
   const u256 r = secp::from_be32(a.sig65 + 65ull * row);
   const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
   const uint32_t v = a.sig65[65ull * row + 64];
   u256 z;
-  if (MODE == 0) {
+  if (MODE != MODE_SENDERS) {
     z = secp::from_be32(a.hash32 + 32ull * row);
   } else {
     uint64_t d[4];
@@ -992,9 +1054,16 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) __attribute__((amdgpu_
   aff Qa;
   __shared__ uint32_t row_tab[WAVE_KERNEL_WAVES][wv::ROW_TAB_SLOTS * 64];  // the window tables: wave-private LDS
   bool ok = wv::recover_pubkey_row(a.gtab, z, r, s, v, a.flags, got, Qa, row_tab[threadIdx.x >> 6]);
-  ok = ok && need && !pre && vi >= 0;
+  if (MODE == MODE_EMIT) {  // (rows past n recomputed the last row: `need` keeps them from storing it again)
+    const emitted e = emit_row(ok, pre, got, a.vtab, a.vslot_mask);
+    if (need && (lane & 15u) == 0) emit_store(a, row, e);
+    ok = need && e.bit;
+    vi = e.vi;
+  } else {
+    ok = ok && need && !pre && vi >= 0;
 #pragma unroll
-  for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+  }
   if ((lane & 15u) == 0 && ok) {
     learn_key(a, vi, Qa);
     atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
@@ -1021,15 +1090,20 @@ __global__ void __launch_bounds__(128 * ROWS_PAIRS_PER_BLOCK) ecrecover_rows_pai
   const bool live = row_raw < a.n;
   const uint32_t row = live ? row_raw : a.n - 1;
   uint32_t want[5];
+  int vi = -1;
+  if (MODE != MODE_EMIT) {
 #pragma unroll
-  for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
-  const int vi = valset_lookup(a.vtab, a.vslot_mask, want);
+    for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
+    vi = valset_lookup(a.vtab, a.vslot_mask, want);
+  }
   const bool pre = a.pre_flags && a.pre_flags[row] != 0;
   const bool done = a.warm_done && a.warm_done[row] != 0;
   const bool need = live && !done;
-  if (!helper && need && (lane & 15u) == 0) a.vidx[row] = vi;
+  if (MODE != MODE_EMIT && !helper && need && (lane & 15u) == 0) a.vidx[row] = vi;
   auto sync = [] { __syncthreads(); };
-  if (!__any((need && !pre && vi >= 0) ? 1 : 0)) {  // (wave-uniform, the same for both wavefronts of the pair)
+  // (wave-uniform, the same for both wavefronts of the pair: in MODE_EMIT from pre_flags and `live` alone)
+  if (!__any((need && !pre && (MODE == MODE_EMIT || vi >= 0)) ? 1 : 0)) {
+    if (MODE == MODE_EMIT && !helper && need && (lane & 15u) == 0) emit_store_none(a, row);  // (every row left is a pre_flags row)
     sync();
     sync();
     return;
@@ -1038,7 +1112,7 @@ __global__ void __launch_bounds__(128 * ROWS_PAIRS_PER_BLOCK) ecrecover_rows_pai
   const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
   if (helper) {
     u256 z;
-    if (MODE == 0) {
+    if (MODE != MODE_SENDERS) {
       z = secp::from_be32(a.hash32 + 32ull * row);
     } else {
       uint64_t d[4];
@@ -1052,9 +1126,16 @@ __global__ void __launch_bounds__(128 * ROWS_PAIRS_PER_BLOCK) ecrecover_rows_pai
   uint32_t got[5];
   aff Qa;
   bool ok = wv::recover_pubkey_row<99, true>(a.gtab, secp::zero256(), r, s, v, a.flags, got, Qa, row_tab[slot], &sh[slot], sync);
-  ok = ok && need && !pre && vi >= 0;
+  if (MODE == MODE_EMIT) {  // (rows past n recomputed the last row: `need` keeps them from storing it again)
+    const emitted e = emit_row(ok, pre, got, a.vtab, a.vslot_mask);
+    if (need && (lane & 15u) == 0) emit_store(a, row, e);
+    ok = need && e.bit;
+    vi = e.vi;
+  } else {
+    ok = ok && need && !pre && vi >= 0;
 #pragma unroll
-  for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+  }
   if ((lane & 15u) == 0 && ok) {
     learn_key(a, vi, Qa);
     atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));

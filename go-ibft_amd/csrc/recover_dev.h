@@ -41,6 +41,40 @@ __host__ __device__ __forceinline__ uint32_t addr_hash(const uint32_t a[5]) {
   h = (h ^ (h >> 15)) + a[4] * 0x165667B1u;
   return h ^ (h >> 16);
 }
+__host__ __device__ __forceinline__ int valset_lookup(const uint32_t *__restrict__ vtab, uint32_t slot_mask,
+                                                      const uint32_t a[5]) {
+  uint32_t s = addr_hash(a) & slot_mask;
+  for (uint32_t probe = 0; probe <= slot_mask; probe++) {
+    const uint32_t *e = vtab + 6u * s;
+    uint32_t tag = e[5];
+    if (tag == 0) return -1;
+    if (e[0] == a[0] && e[1] == a[1] && e[2] == a[2] && e[3] == a[3] && e[4] == a[4])
+      return (int)tag - 1;
+    s = (s + 1) & slot_mask;
+  }
+  return -1;
+}
+
+// ---- emitting form of the cold kernels (ibft_recover_seals): what a row stores once the curve is done ----------------
+// rec: a key was recovered (r, s, v in range, a curve point, not the point at infinity) and `got` is its address; pre: the
+// caller's pre_flags ruled the row out.  The address goes out as recovered — a non-member's too —, twenty zero bytes where there
+// is none; membership is looked up for the RECOVERED address (IsValidCommittedSeal with the signer ecrecover names), and only a
+// recovered address is looked up: a validator whose address is twenty zero bytes is not found by a row that recovered nothing.
+struct emitted {
+  uint32_t addr[5];
+  int vi;    // index in the validator set, -1: no member / nothing recovered
+  bool bit;  // the row's verdict: a key was recovered AND its address is a member
+};
+__host__ __device__ __forceinline__ emitted emit_row(bool rec, bool pre, const uint32_t got[5], const uint32_t *__restrict__ vtab,
+                                                     uint32_t slot_mask) {
+  emitted e;
+  const bool have = rec && !pre;
+#pragma unroll
+  for (int i = 0; i < 5; i++) e.addr[i] = have ? got[i] : 0u;
+  e.vi = have ? valset_lookup(vtab, slot_mask, e.addr) : -1;
+  e.bit = e.vi >= 0;
+  return e;
+}
 
 // ---- fixed-base table: gtab[w][e] = e * 2^(B·w) * G, affine ------------------------------
 // Each entry is 20 dwords: x then y, ten 26-bit limbs each (the kernels' native form, so a

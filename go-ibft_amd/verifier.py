@@ -43,11 +43,13 @@ EXPORTS = [
     "ibft_seals_stage_next", "ibft_seals_swap", "ibft_last_cold_table", "ibft_seals_submit", "ibft_seals_collect",
     "ibft_comm_preload", "ibft_issue_probe", "ibft_seals_rows", "ibft_pipeline_stats", "ibft_verify_block_seals",
     "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
+    "ibft_recover_seals", "ibft_recover_block_seals",
 ]
-# exports younger than version 3: the version that brought them (ibft_verify_block_seals and the streamed ibft_block_seals_*
-# came without a version step: an older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
+# exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
+# ibft_recover_seals / ibft_recover_block_seals came without a version step: an older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
 EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
-OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending"}
+OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
+                    "ibft_recover_seals", "ibft_recover_block_seals"}
 COMM_ID_BYTES = 128
 E_RCCL = -8
 
@@ -183,6 +185,10 @@ def load_library() -> C.CDLL:
         L.ibft_pipeline_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if hasattr(L, "ibft_verify_block_seals"):
         L.ibft_verify_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_recover_seals"):
+        L.ibft_recover_seals.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Tally)]
+    if hasattr(L, "ibft_recover_block_seals"):
+        L.ibft_recover_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "ibft_block_seals_submit"):
         L.ibft_block_seals_submit.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
     if hasattr(L, "ibft_block_seals_collect"):
@@ -438,6 +444,49 @@ class BatchVerifier:
                   "ibft_verify_block_seals")
         self._staged = n
         return mask_to_bool(mask, n), list(tallies)[:nb]
+
+    # bare seals (headers that carry only signatures): who signed?
+    def recover_seals(self, hash32, sig65, pre_flags=None):
+        """ibft_recover_seals: ecrecover in batch → (signer20 (n, 20) uint8 — zeros where nothing is recovered —, vidx int32[n]
+        — index in the validator set or -1 —, verdict bool[n] — recovered and a member —, Tally over the distinct members)"""
+        if not hasattr(self._L, "ibft_recover_seals"):
+            raise GpuUnavailable("this build of the library has no ibft_recover_seals — rebuild")
+        h = _u8(hash32, (-1, 32)); s = _u8(sig65, (-1, 65))
+        n = len(s)
+        if len(h) != n:
+            raise ValueError("hash32 needs one row per seal")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        signer = np.zeros((max(n, 1), 20), dtype=np.uint8)
+        vidx = np.full(max(n, 1), -1, dtype=np.int32)
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        t = Tally()
+        self._chk(self._L.ibft_recover_seals(self._h, _p(h), _p(s), _p(pre), n, _p(signer), _p(vidx), _p(mask), C.byref(t)),
+                  "ibft_recover_seals")
+        self._staged = 0
+        return signer[:n], vidx[:n], mask_to_bool(mask, n), t
+
+    def recover_block_seals(self, block_hash32, seal_off, sig65, pre_flags=None):
+        """ibft_recover_block_seals: recover_seals for many finalized blocks in one call (rows and offsets as
+        verify_block_seals, no signer column) → (signer20 (n, 20), vidx int32[n], verdict bool[n], Tally list[n_blocks])"""
+        if not hasattr(self._L, "ibft_recover_block_seals"):
+            raise GpuUnavailable("this build of the library has no ibft_recover_block_seals — rebuild")
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65))
+        n = len(s)
+        if len(bh) != nb or int(off[-1]) != n:
+            raise ValueError("block_hash32 needs one row per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        signer = np.zeros((max(n, 1), 20), dtype=np.uint8)
+        vidx = np.full(max(n, 1), -1, dtype=np.int32)
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        tallies = (Tally * max(nb, 1))()
+        self._chk(self._L.ibft_recover_block_seals(self._h, _p(bh), _p(off), nb, _p(s), _p(pre), _p(signer), _p(vidx), _p(mask),
+                                                   tallies), "ibft_recover_block_seals")
+        self._staged = 0
+        return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb]
 
     # chain sync as a stream: submit(k + 1), collect(k) — at most two batches in flight
     def _need_block_stream(self):

@@ -15,6 +15,9 @@
  *   ibft_verify_seals    <- Verifier.IsValidCommittedSeal(proposalHash, seal)
  *                           /root/reference/core/backend.go:53-55; call site
  *                           /root/reference/core/ibft.go:943
+ *   ibft_recover_seals, ibft_recover_block_seals
+ *                        <- the same for BARE committed seals (finalized headers that carry only signatures): the signer
+ *                           is what ecrecover returns — address out, membership of the recovered address, HasQuorum
  *   ibft_verify_senders  <- Verifier.IsValidValidator(msg)
  *                           /root/reference/core/backend.go:41-45; call sites
  *                           /root/reference/core/ibft.go:735, 1128, 1213, 1220
@@ -269,6 +272,41 @@ int ibft_block_seals_submit(ibft_ctx *ctx, const uint8_t *block_hash32, const ui
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags);
 int ibft_block_seals_collect(ibft_ctx *ctx, uint64_t *out_mask, ibft_tally_t *out_tally);
 int ibft_block_seals_pending(ibft_ctx *ctx, uint32_t *batches_in_flight, uint32_t *oldest_rows, uint32_t *oldest_blocks);
+
+/* Bare seals: who signed?  The batch form of ecrecover for committed seals whose signer is not on the wire — finalized headers
+ * that store only the 65-byte signatures; an embedder's header check recovers the address, looks it up in the validator
+ * set, drops duplicates and asks HasQuorum (/root/reference/core/backend.go:53-55, core/validator_manager.go:77-96).
+ *   hash32 n×32 (per-row proposal hash; the ibft_set_seal_digest convention applies as for ibft_verify_seals), sig65 n×65,
+ *   pre_flags n or NULL.
+ *   out_signer20  n×20: keccak256(X‖Y)[12:32] of the key recovered from row i; TWENTY ZERO BYTES where nothing is
+ *                 recovered (r or s out of range, v > 1, no curve point, point at infinity, high s under
+ *                 IBFT_FLAG_STRICT_LOW_S) or pre_flags[i] != 0.  A non-member's address is delivered like a member's.
+ *   out_vidx      n × int32, may be NULL: index of out_signer20[i] in the context's validator set (the index of its first
+ *                 occurrence in the ibft_set_validators list without repeated addresses), -1 when it is no member or nothing
+ *                 was recovered
+ *   out_mask      ⌈n/64⌉ words: bit i = a key was recovered AND its address is a member
+ *                 (= IsValidCommittedSeal(hash_i, {out_signer20[i], sig_i}))
+ *   tally         may be NULL: HasQuorum over the distinct member signers of the rows whose bit is set
+ * Defining property: out_signer20 fed back as signer20 into ibft_verify_seals with the same other columns returns the same
+ * mask words and the same tally, bit for bit, on a cold context and on a warm one.  Always the cold (recovering) kernels,
+ * chosen by batch size as for a cold ibft_verify_seals — a warm kernel needs a claimed key to pick its table; with
+ * IBFT_FLAG_PUBKEY_CACHE the call teaches the device its validators' keys, so that later VERIFY calls are warm.
+ * Errors as ibft_verify_seals (IBFT_E_INVAL: NULL ctx, NULL out_signer20 / out_mask / column with n > 0; IBFT_E_NOVALSET;
+ * IBFT_E_TOOBIG); nothing is written to the out buffers of a refused call; n = 0 is legal.  Towards the two pipelines as
+ * ibft_verify_seals: what it enqueues runs behind batches in flight, a pass in flight is left to its collect.  Bare rows are
+ * NOT a resident staged batch afterwards (ibft_seals_launch finds no rows).  ibft_last_dispatch, ibft_last_kernel_ms and
+ * ibft_set_kernel_timing see the call as a cold verify pass.                                                          */
+int ibft_recover_seals(ibft_ctx *ctx, const uint8_t *hash32, const uint8_t *sig65, const uint8_t *pre_flags, size_t n,
+                       uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *tally);
+
+/* The same for n_blocks finalized blocks in one launch: arguments, checks and error codes of ibft_verify_block_seals minus
+ * the signer20 column, plus out_signer20 (n×20, NULL with n > 0: IBFT_E_INVAL) and out_vidx (n, may be NULL); out_tally
+ * n_blocks entries, may be NULL.  Equal to one ibft_recover_seals per block: a signer counts once per block, in every block
+ * it signed; a seal placed in another block recovers some other address and counts only if that address is a member.
+ * There is no streamed (submit / collect) form of this call.                                                         */
+int ibft_recover_block_seals(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                             const uint8_t *sig65, const uint8_t *pre_flags,
+                             uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally);
 
 /* a3. payload = concatenated PayloadNoSig bytes; row i is payload[off[i]..off[i+1]);
  * off has n+1 entries.                                                             */

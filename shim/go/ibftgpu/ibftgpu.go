@@ -254,6 +254,56 @@ func (c *Ctx) VerifyBlockSeals(blockHash32 []byte, sealOff []uint32, sig65, sign
 	return mask, tallies, nil
 }
 
+// RecoverSeals = ecrecover over a batch of BARE committed seals (ibft_recover_seals): headers that carry only
+// []Signature.  signer20[20i:20i+20] is the address recovered from row i (twenty zero bytes where there is none or
+// preFlags[i] != 0), vidx[i] its index in the validator set (-1: no member), mask bit i = recovered AND a member, and the
+// tally HasQuorum over the distinct member signers.  Always at the cold rate: when the signers are known use VerifySeals.
+func (c *Ctx) RecoverSeals(hash32, sig65, preFlags []byte) (signer20 []byte, vidx []int32, mask []uint64, t Tally, err error) {
+	n := len(sig65) / 65
+	if len(hash32) < 32*n || (preFlags != nil && len(preFlags) < n) {
+		return nil, nil, nil, Tally{}, fmt.Errorf("%w: columns shorter than sig65 says", ErrFallback)
+	}
+	signer20 = make([]byte, 20*n+20)
+	vidx = make([]int32, n+1)
+	mask = make([]uint64, (n+63)/64+1)
+	var ct C.ibft_tally_t
+	rc := C.ibft_recover_seals(c.h, ptr8(hash32), ptr8(sig65), ptr8(preFlags), C.size_t(n), ptr8(signer20),
+		(*C.int32_t)(unsafe.Pointer(&vidx[0])), (*C.uint64_t)(unsafe.Pointer(&mask[0])), &ct)
+	if err := c.check(rc); err != nil {
+		return nil, nil, nil, Tally{}, err
+	}
+	return signer20[:20*n], vidx[:n], mask, tally(ct), nil
+}
+
+// RecoverBlockSeals = RecoverSeals for the committed seals of many finalized blocks in one call
+// (ibft_recover_block_seals): rows and offsets as VerifyBlockSeals, no signer column; tallies[b] is block b's HasQuorum
+// over the signers recovered from its rows.
+func (c *Ctx) RecoverBlockSeals(blockHash32 []byte, sealOff []uint32, sig65, preFlags []byte) (signer20 []byte, vidx []int32, mask []uint64, tallies []Tally, err error) {
+	if len(sealOff) == 0 {
+		return nil, nil, nil, nil, fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(blockHash32) < 32*nb || len(sig65) < 65*n || (preFlags != nil && len(preFlags) < n) {
+		return nil, nil, nil, nil, fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	signer20 = make([]byte, 20*n+20)
+	vidx = make([]int32, n+1)
+	mask = make([]uint64, (n+63)/64+1)
+	ct := make([]C.ibft_tally_t, nb+1)
+	rc := C.ibft_recover_block_seals(c.h, ptr8(blockHash32), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), C.size_t(nb),
+		ptr8(sig65), ptr8(preFlags), ptr8(signer20), (*C.int32_t)(unsafe.Pointer(&vidx[0])),
+		(*C.uint64_t)(unsafe.Pointer(&mask[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err := c.check(rc); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	tallies = make([]Tally, nb)
+	for b := range tallies {
+		tallies[b] = tally(ct[b])
+	}
+	return signer20[:20*n], vidx[:n], mask, tallies, nil
+}
+
 // blockBatch keeps the columns of one BlockSealsSubmit reachable — and, where they are Go memory, pinned — until its
 // BlockSealsCollect: the library's copy stream reads them after the cgo call has returned.
 type blockBatch struct {

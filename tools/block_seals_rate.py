@@ -6,6 +6,7 @@ ibft_verify_seals (one call per block) over the same rows on the same context.
     python tools/block_seals_rate.py --v 100 --blocks 655  # one configuration (e.g. under rocprofv3 --kernel-trace --stats)
     python tools/block_seals_rate.py --v 1024 --blocks 1 --repeat 64   # one block of 65 536 rows
     python tools/block_seals_rate.py --stream              # the streamed form (ibft_block_seals_submit / _collect) against the call
+    python tools/block_seals_rate.py --recover             # bare seals: ibft_recover_block_seals against the verify call and the host route
 
 Every block carries one seal of every validator (V rows), signed on the device (ibft_sign_seals).  "max" = as many blocks as
 fit 65 536 rows.  cold: a context without the key cache (every call recovers); warm: IBFT_FLAG_PUBKEY_CACHE after the
@@ -16,6 +17,14 @@ function directly through ctypes with pointers computed in advance (no numpy sli
 the rounds are reported): the synchronous call from pageable sources, the synchronous call from ibft_pinned_alloc sources
 (pinning alone), and the streamed form from the pinned sources with one batch kept in flight — submit(k + 1), collect(k) —
 (pinning + pipelining).  Every leg rotates three distinct pre-signed batches, so no leg re-reads rows a cache still holds.
+--recover: headers that carry only signatures.  Three legs over the same batch on one lease, alternated --alternations times
+on contexts WITHOUT the key cache: ibft_recover_block_seals (the emitting cold kernels), ibft_verify_block_seals with the
+signers given (the same cold kernels comparing), and the host route an embedder has without the recover call — the oracle's
+tuned recovery of every row on --threads cores (orc_verify_seals_tuned_mt: it recovers each row's key and address natively on a
+thread pool of its own and compares the address, which is the cost of recovering it), then ibft_verify_block_seals.  Kernel times are ibft_last_kernel_ms of the
+verdict launch alone.  --parent-lib OLD.so adds a fourth figure: the cold verify launch of ANOTHER build of the library (the
+parent commit's) over the same rows, in child processes that alternate with child processes of this build (IBFT_GPU_LIB).
+The lease's ibft_issue_probe value is printed beside every configuration.
 One JSON line per configuration, then a table."""
 import argparse
 import ctypes as C
@@ -170,6 +179,166 @@ def measure_stream(V_, nb, warm, repeat=1, alternations=5, budget_s=0.15):
         bv.close()
 
 
+def _recover_batch(bv, V_, rows):
+    """rows seals, every validator signing every block (blocks of V_ rows), signed on the device"""
+    import go_ibft_amd.verifier as V  # noqa: F401
+    from oracle import binding as B, workload as W
+    r = W.make_round(V_, 7, raw_len=64)
+    nb = max(1, rows // V_)
+    n = nb * V_
+    bv.set_validators(r.height, r.addrs, r.power)
+    bh = np.frombuffer(b"".join(B.keccak256(b"rec" + b.to_bytes(4, "little")) for b in range(nb)), np.uint8).reshape(nb, 32).copy()
+    off = (np.arange(nb + 1) * V_).astype(np.uint32)
+    sk = np.tile(np.frombuffer(b"".join(r.sks), np.uint8).reshape(V_, 32), (nb, 1))
+    sig, signer, ok = bv.sign_seals(sk, np.repeat(bh, V_, axis=0))
+    assert ok.all()
+    return r, nb, n, bh, off, sig, signer
+
+
+def kernel_leg(V_, rows, leg, reps=30):
+    """child process of --recover --parent-lib: kernel ms (median of reps) of ONE leg's verdict launch under the library
+    IBFT_GPU_LIB names → one JSON line"""
+    import go_ibft_amd.verifier as V
+    bv = V.BatchVerifier(max_rows=65536)
+    try:
+        r, nb, n, bh, off, sig, signer = _recover_batch(bv, V_, rows)
+        fn = (lambda: bv.recover_block_seals(bh, off, sig)) if leg == "recover" else (lambda: bv.verify_block_seals(bh, off, sig, signer))
+        for _ in range(3):
+            fn()
+        bv.set_kernel_timing(1)
+        bv.last_kernel_ms()
+        ms = []
+        for _ in range(reps):
+            fn()
+            ms.append(bv.last_kernel_ms()[0])
+        print(json.dumps({"leg": leg, "v": V_, "rows": n, "kernel_ms": float(np.median(ms)), "kernel_min_ms": min(ms),
+                          "cold_lanes": bv.last_dispatch()[0], "lib": os.environ.get("IBFT_GPU_LIB", "")}), flush=True)
+    finally:
+        bv.close()
+
+
+def measure_recover(V_, rows, alternations=5, threads=16, budget_s=0.15, parent_lib=None):
+    import subprocess
+    import go_ibft_amd.verifier as V
+    from oracle import binding as B
+    bv = V.BatchVerifier(max_rows=65536)
+    try:
+        probe_ns = bv.issue_probe()[0]
+        r, nb, n, bh, off, sig, signer = _recover_batch(bv, V_, rows)
+        rh = np.repeat(bh, V_, axis=0)
+        L = bv._L
+        mask = np.zeros((n + 63) // 64, np.uint64)
+        tal = (V.Tally * nb)()
+        out_signer = np.zeros((n, 20), np.uint8)
+        out_vidx = np.zeros(n, np.int32)
+        host_signer = np.zeros((n, 20), np.uint8)
+        a_rec = (bv._h, V._p(bh), V._p(off), nb, V._p(sig), None, V._p(out_signer), V._p(out_vidx), V._p(mask), tal)
+        a_ver = (bv._h, V._p(bh), V._p(off), nb, V._p(sig), V._p(signer), None, V._p(mask), tal)
+        a_host = (bv._h, V._p(bh), V._p(off), nb, V._p(sig), V._p(host_signer), None, V._p(mask), tal)
+        vs = B.ValSet(r.addrs, r.power)
+        host_signer[:] = signer
+
+        def host_recover_only():
+            ok = B.verify_seals_tuned(vs, rh, sig, signer, None, 0, nthreads=threads)
+            assert ok.all()
+
+        def recover():
+            rc = L.ibft_recover_block_seals(*a_rec)
+            assert rc == 0, rc
+
+        def verify():
+            rc = L.ibft_verify_block_seals(*a_ver)
+            assert rc == 0, rc
+
+        def host_route():
+            host_recover_only()
+            rc = L.ibft_verify_block_seals(*a_host)
+            assert rc == 0, rc
+
+        legs = {"recover": recover, "verify": verify, "host_route": host_route}
+        times = {k: [] for k in legs}
+        kms = {"recover": [], "verify": []}
+        host_only = []
+        for _ in range(alternations):
+            for name, fn in legs.items():
+                if name == "host_route":       # seconds per call at size: a few calls, not a budget of them
+                    fn()
+                    t0 = time.perf_counter()
+                    fn()
+                    times[name].append((time.perf_counter() - t0) * 1e3)
+                    t0 = time.perf_counter()
+                    host_recover_only()
+                    host_only.append((time.perf_counter() - t0) * 1e3)
+                else:
+                    bv.set_kernel_timing(0)
+                    times[name].append(timed(fn, budget_s) * 1e3)
+                    bv.set_kernel_timing(1)
+                    bv.last_kernel_ms()
+                    k = []
+                    for _ in range(10):
+                        fn()
+                        k.append(bv.last_kernel_ms()[0])
+                    kms[name].append(float(np.median(k)))
+                assert V.mask_to_bool(mask, n).all() and all(t.has_quorum == 1 for t in tal)
+            assert (out_signer == signer).all() and (out_vidx == np.tile(np.arange(V_, dtype=np.int32), nb)).all()
+        res = {"v": V_, "blocks": nb, "rows": n, "cold_lanes": bv.last_dispatch()[0], "alternations": alternations, "threads": threads,
+               "issue_probe_ns": probe_ns}
+        for name, ts in times.items():
+            res[name + "_ms"] = float(np.median(ts))
+            res[name + "_min_ms"] = min(ts)
+            res[name + "_max_ms"] = max(ts)
+        res["host_recover_only_ms"] = float(np.median(host_only))
+        res["host_recover_M_per_s"] = n / res["host_recover_only_ms"] / 1e3
+        for name, ks in kms.items():
+            res[name + "_kernel_ms"] = float(np.median(ks))
+            res[name + "_kernel_all_ms"] = [round(x, 4) for x in ks]
+        res["kernel_recover_over_verify"] = res["recover_kernel_ms"] / res["verify_kernel_ms"]
+        res["recover_over_host_route"] = res["recover_ms"] / res["host_route_ms"]
+    finally:
+        bv.close()
+    if parent_lib:     # the parent build's cold verify launch against this build's emitting launch: fresh processes, alternating
+        got = {"parent_verify": [], "recover": []}
+        for _ in range(alternations):
+            for key, lib, leg in (("parent_verify", parent_lib, "verify"), ("recover", None, "recover")):
+                env = {k: v for k, v in os.environ.items() if k != "IBFT_GPU_LIB"}
+                if lib:
+                    env.update(IBFT_GPU_LIB=lib, IBFT_MIN_ABI="3")
+                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--kernel-leg", leg, "--v", str(V_), "--rows", str(rows)],
+                                   capture_output=True, text=True, timeout=300, env=env)
+                if p.returncode != 0:   # (nothing more is started on the device after a child that failed)
+                    raise RuntimeError(f"kernel leg {key} failed ({p.returncode}): {p.stdout[-500:]}{p.stderr[-1500:]}")
+                got[key].append(json.loads(p.stdout.strip().split("\n")[-1])["kernel_ms"])
+        res["parent_verify_kernel_ms"] = float(np.median(got["parent_verify"]))
+        res["child_recover_kernel_ms"] = float(np.median(got["recover"]))
+        res["parent_verify_kernel_all_ms"] = [round(x, 4) for x in got["parent_verify"]]
+        res["child_recover_kernel_all_ms"] = [round(x, 4) for x in got["recover"]]
+        res["kernel_recover_over_parent_verify"] = res["child_recover_kernel_ms"] / res["parent_verify_kernel_ms"]
+    return res
+
+
+def main_recover(a):
+    vs = a.v if a.v != [4, 100, 1024] else [100, 1024]
+    rows = []
+    for V_ in vs:
+        for n in a.rows:
+            res = measure_recover(V_, n, a.alternations, a.threads, parent_lib=a.parent_lib)
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            for res in rows:
+                f.write(json.dumps(res) + "\n")
+    print(f"{'V':>5} {'rows':>6} {'lanes':>5} {'probe ns':>8} {'recover ms':>22} {'verify ms':>22} {'host route ms':>24} {'rec/host':>8} "
+          f"{'k rec ms':>9} {'k ver ms':>9} {'k rec/ver':>9} {'k parent ver':>12} {'k rec/parent':>12} {'host rec M/s':>12}")
+    cell = lambda r, k: f"{r[k + '_ms']:.3f} ({r[k + '_min_ms']:.3f}…{r[k + '_max_ms']:.3f})"
+    for r in rows:
+        pv = f"{r['parent_verify_kernel_ms']:.4f}" if "parent_verify_kernel_ms" in r else "-"
+        pr = f"{r['kernel_recover_over_parent_verify']:.3f}" if "parent_verify_kernel_ms" in r else "-"
+        print(f"{r['v']:>5} {r['rows']:>6} {r['cold_lanes']:>5} {r['issue_probe_ns']:>8.3f} {cell(r, 'recover'):>22} {cell(r, 'verify'):>22} "
+              f"{cell(r, 'host_route'):>24} {r['recover_over_host_route']:>8.4f} {r['recover_kernel_ms']:>9.4f} {r['verify_kernel_ms']:>9.4f} "
+              f"{r['kernel_recover_over_verify']:>9.3f} {pv:>12} {pr:>12} {r['host_recover_M_per_s']:>12.3f}")
+
+
 def main_stream(a):
     shapes = [(4, 16), (4, 16384), (100, 1), (100, 16), (100, 256), (100, 655), (1024, 16), (1024, 64)]
     if a.v != [4, 100, 1024] or a.blocks != ["1", "16", "256", "max"]:
@@ -202,8 +371,19 @@ def main():
                     "V·repeat rows: --v 1024 --blocks 1 --repeat 64 is one block of 65 536 rows)")
     ap.add_argument("--out", type=str, default=None, help="also write the JSON lines here")
     ap.add_argument("--stream", action="store_true", help="the streamed form against the synchronous call (pageable and pinned)")
-    ap.add_argument("--alternations", type=int, default=5, help="--stream: rounds of the three legs")
+    ap.add_argument("--alternations", type=int, default=5, help="--stream / --recover: rounds of the legs")
+    ap.add_argument("--recover", action="store_true", help="bare seals: ibft_recover_block_seals against ibft_verify_block_seals "
+                    "and the host route (CPU recovery, then the verify call)")
+    ap.add_argument("--rows", type=int, nargs="*", default=[4096, 16384, 65500], help="--recover: rows per call (rounded down to whole blocks)")
+    ap.add_argument("--threads", type=int, default=16, help="--recover: cores of the host route's recovery")
+    ap.add_argument("--parent-lib", type=str, default=None, help="--recover: another build of libibftgpu.so whose cold verify "
+                    "launch is timed over the same rows in alternating child processes")
+    ap.add_argument("--kernel-leg", type=str, default=None, choices=["recover", "verify"], help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.kernel_leg:
+        return kernel_leg(a.v[0], a.rows[0], a.kernel_leg)
+    if a.recover:
+        return main_recover(a)
     if a.stream:
         return main_stream(a)
     rows = []
