@@ -183,5 +183,18 @@ def build_cert_wave_harness(force: bool = False) -> str:
     return CERT_WAVE_HARNESS
 
 
+PROPOSAL_DIGEST_HARNESS = os.path.join(CSRC, "libdev_proposal_digest_host.so")
+
+
+def build_proposal_digest_harness(force: bool = False) -> str:
+    """TEST-ONLY: the lane and the wavefront form of proposal_digest_kernel's absorb routine on the CPU."""
+    deps = ["host_proposal_digest_harness.hip", "cert_wave_dev.h", "wave_emul.h", "wire_dev.h", "keccak_dev.h"]
+    if force or _stale(PROPOSAL_DIGEST_HARNESS, deps):
+        subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
+                               "-o", PROPOSAL_DIGEST_HARNESS, os.path.join(CSRC, "host_proposal_digest_harness.hip")], cwd=CSRC)
+        _mark(PROPOSAL_DIGEST_HARNESS, deps)
+    return PROPOSAL_DIGEST_HARNESS
+
+
 if __name__ == "__main__":
     print(build_lib(verbose=True))

@@ -168,6 +168,16 @@ struct ibft_ctx {
   hipEvent_t ev_bs[2] = {nullptr, nullptr};
   uint32_t bs_issued = 0, bs_collected = 0, bs_rows[2] = {0, 0}, bs_blocks[2] = {0, 0};
   uint64_t bs_quorum[2][2] = {{0, 0}, {0, 0}};  // the quorum a batch was judged under (the set current at its submit)
+  // Chain sync from the proposals (ibft_proposal_hashes, the _raw block calls): the caller's proposals as they are — bytes,
+  // offsets, rounds — in buffers of their own (grown on demand and kept, like d_payload; the bytes carry 256 of slack), the n
+  // digests proposal_digest_kernel writes (what block_rows_kernel then reads in place of an uploaded d_bhash), and the pinned
+  // mirror the digests come back through.  None of it is the remembered proposal of ibft_proposal_hash (d_H, hashed_proposal).
+  DevBuf d_praw, d_proff, d_pround, d_phash;
+  uint8_t *h_phash = nullptr;
+  size_t h_phash_rows = 0;
+  uint64_t proposal_bytes_max = 256ull << 20;  // IBFT_PROPOSAL_BYTES_MAX: the most raw_off[n] may be (IBFT_E_TOOBIG beyond)
+  uint32_t proposal_lanes_force = 0;           // IBFT_PROPOSAL_LANES=1|64 pins the form of proposal_digest_kernel (tests, A/B)
+  uint32_t proposal_lane_rows = 8192;          // AUTO: the lane form from this many proposals of the longest one's length on
   uint64_t last_wide[ibftk::TALLY_SUM_WORDS] = {0};  // full-width power of the last fetched tally
   uint64_t height = 0;
   // the seal-digest convention of the embedding Backend (ibft_set_seal_digest): 0 = the proposalHash itself
@@ -1478,6 +1488,13 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   if (const char *e = getenv("IBFT_WAVE_ROWS_MAX")) c->wave_rows_max = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_PAIR_ROWS_MAX")) c->pair_rows_max = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_ROWS_KERNEL_MAX")) c->rows_kernel_max = (uint32_t)strtoul(e, nullptr, 10);
+  if (const char *e = getenv("IBFT_PROPOSAL_LANES")) {
+    const int g = atoi(e);
+    if (g == 1 || g == 64) c->proposal_lanes_force = (uint32_t)g;
+  }
+  if (const char *e = getenv("IBFT_PROPOSAL_LANE_ROWS")) c->proposal_lane_rows = (uint32_t)strtoul(e, nullptr, 10);
+  if (const char *e = getenv("IBFT_PROPOSAL_BYTES_MAX"))  // (offsets are 32-bit; room is kept for the round and the slack)
+    c->proposal_bytes_max = std::min<uint64_t>(strtoull(e, nullptr, 10), 0xFFFFFE00ull);
   if (const char *e = getenv("IBFT_ROWS_PAIR")) {
     if (!strcmp(e, "0")) c->rows_pair_force = 0;
     else if (!strcmp(e, "1")) c->rows_pair_force = 1;
@@ -1557,8 +1574,10 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_cert_nodes, &c->d_cert_span, &c->d_cert_count, &c->d_cert_prop, &c->d_cert_masks, &c->d_cert_total,
                     &c->d_cert_slot, &c->d_cert_tiles, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
                     &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally,
-                    &c->d_bhash_nx, &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1]})
+                    &c->d_bhash_nx, &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
+                    &c->d_phash})
     release(*b);
+  if (c->h_phash) (void)hipHostFree(c->h_phash);
   if (c->tstream) {
     (void)hipStreamSynchronize(c->tstream);
     (void)hipStreamDestroy(c->tstream);
@@ -2675,24 +2694,132 @@ static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t w
   return IBFT_OK;
 }
 
+// ---- chain sync from the proposals: keccak256(RawProposal ‖ BE64(Round)) of n proposals on the device ------------------------
+// A batch of proposals as the caller holds it.  check_proposals is everything that needs no device (and writes nothing);
+// stage_proposals adds the three columns to the call's ColumnCopies — the route of every neighbouring call: ONE gather launch
+// when all columns of the call lie in ibft_pinned_alloc memory, a copy command per column otherwise —;
+// enqueue_proposal_digests launches proposal_digest_kernel behind them on the main stream and, if the caller wants the
+// digests, their copy into the pinned mirror.  The digests stay in d_phash for whoever reads them next (block_seals_impl).
+struct proposal_batch {
+  const uint8_t *raw;
+  const uint32_t *raw_off;
+  const uint64_t *round;
+  uint8_t *out_hash32;  // may be null (the _raw block calls)
+  uint64_t total_blocks = 0, max_blocks = 0;  // rate blocks of all proposals / of the longest (filled by check_proposals)
+};
+static int check_proposals(const ibft_ctx *c, proposal_batch &p, size_t n) {
+  if (n == 0) return IBFT_OK;
+  if (!p.raw_off || !p.round || p.raw_off[0] != 0) return IBFT_E_INVAL;
+  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  for (size_t i = 0; i < n; i++) {
+    if (p.raw_off[i + 1] < p.raw_off[i]) return IBFT_E_INVAL;
+    const uint64_t blocks = ((uint64_t)(p.raw_off[i + 1] - p.raw_off[i]) + 8u) / 136u + 1u;
+    p.total_blocks += blocks;
+    p.max_blocks = std::max(p.max_blocks, blocks);
+  }
+  if (p.raw_off[n] > c->proposal_bytes_max) return IBFT_E_TOOBIG;
+  if (p.raw_off[n] && !p.raw) return IBFT_E_INVAL;
+  return IBFT_OK;
+}
+// Which form of proposal_digest_kernel: 1 = a lane per proposal, 64 = a wavefront per proposal.  The lane form ends with its
+// longest proposal (max_blocks × ≈9.4 µs) however many there are, up to a wavefront on every SIMD; the wavefront form walks a
+// proposal in ≈5.3 µs per block but the chip holds only so many of them at once, so its time grows with the TOTAL number of
+// blocks.  total_blocks / max_blocks is the batch's size in proposals of the longest one's length: the lane form from
+// proposal_lane_rows of them on (IBFT_PROPOSAL_LANE_ROWS), and never for fewer than 64 proposals.  IBFT_PROPOSAL_LANES pins.
+static uint32_t proposal_form(const ibft_ctx *c, const proposal_batch &p, size_t n) {
+  if (c->proposal_lanes_force) return c->proposal_lanes_force;
+  return n >= 64 && p.total_blocks >= (uint64_t)c->proposal_lane_rows * p.max_blocks ? 1u : 64u;
+}
+static int stage_proposals(ibft_ctx *c, ColumnCopies &cc, const proposal_batch &p, size_t n) {
+  int rc;
+  const size_t bytes = p.raw_off[n];
+  if ((rc = ensure(c, c->d_praw, bytes + 256))) return rc;
+  if ((rc = ensure(c, c->d_proff, (n + 1) * 4))) return rc;
+  if ((rc = ensure(c, c->d_pround, n * 8))) return rc;
+  if ((rc = ensure(c, c->d_phash, n * 32))) return rc;
+  if (p.out_hash32 && n > c->h_phash_rows) {  // (every call that delivers into it has synchronised before it returned)
+    if (c->h_phash) (void)hipHostFree(c->h_phash);
+    c->h_phash = nullptr;
+    c->h_phash_rows = 0;
+    const size_t want = std::max<size_t>(n, 256);
+    if (hipHostMalloc((void **)&c->h_phash, want * 32) != hipSuccess) {
+      c->h_phash = nullptr;
+      return IBFT_E_NOMEM;
+    }
+    c->h_phash_rows = want;
+  }
+  cc.add(c->d_praw.p, p.raw, bytes);
+  cc.add(c->d_proff.p, p.raw_off, (n + 1) * 4);
+  cc.add(c->d_pround.p, p.round, n * 8);
+  return IBFT_OK;
+}
+static int enqueue_proposal_digests(ibft_ctx *c, const proposal_batch &p, size_t n) {
+  ibftk::proposal_digest_args a{};
+  a.raw = (const uint8_t *)c->d_praw.p;
+  a.raw_off = (const uint32_t *)c->d_proff.p;
+  a.round = (const uint64_t *)c->d_pround.p;
+  a.out32 = (uint8_t *)c->d_phash.p;
+  a.n = (uint32_t)n;
+  if (proposal_form(c, p, n) == 1)
+    hipLaunchKernelGGL(ibftk::proposal_digest_kernel<1>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(ibftk::proposal_digest_kernel<64>, dim3((unsigned)n), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  if (p.out_hash32) HIPCHK(c, hipMemcpyAsync(c->h_phash, c->d_phash.p, n * 32, hipMemcpyDeviceToHost, c->stream));
+  return IBFT_OK;
+}
+
+int ibft_proposal_hashes(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round, size_t n,
+                         uint8_t *out_hash32) {
+  if (!c || (n && !out_hash32)) return IBFT_E_INVAL;
+  proposal_batch p{raw, raw_off, round, out_hash32};
+  int rc;
+  if ((rc = check_proposals(c, p, n))) return rc;
+  if (n == 0) return IBFT_OK;
+  ctx_lock lk(c);
+  HIPCHK(c, hipSetDevice(c->device));
+  ColumnCopies cc;
+  if ((rc = stage_proposals(c, cc, p, n))) return rc;
+  if ((rc = cc.flush(c))) return rc;
+  if ((rc = enqueue_proposal_digests(c, p, n))) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(out_hash32, c->h_phash, n * 32);
+  return IBFT_OK;
+}
+
 // Chain sync: the committed seals of n_blocks finalized blocks — one upload, one verdict launch over every row (the AUTO rule
 // sees the TOTAL row count), one segmented tally (block_tally_kernel), one synchronisation.
+// props: the _raw calls — the blocks' proposals in place of block_hash32; their hashes are computed on the device
+// (proposal_digest_kernel) into d_phash, which then plays d_bhash's part: one code path from there on.
 // bare: ibft_recover_block_seals — no signer20 column; the emitting kernels fill out_signer20 / out_vidx and the validator
 // indices the tally reads.
-static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off, size_t n_blocks,
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
                             uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally);
 int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, uint64_t *out_mask,
                             ibft_tally_t *out_tally) {
-  return block_seals_impl(c, block_hash32, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally);
+  return block_seals_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally);
 }
 int ibft_recover_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
                              const uint8_t *sig65, const uint8_t *pre_flags, uint8_t *out_signer20, int32_t *out_vidx,
                              uint64_t *out_mask, ibft_tally_t *out_tally) {
-  return block_seals_impl(c, block_hash32, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally);
+  return block_seals_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally);
 }
-static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+int ibft_verify_block_seals_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20,
+                                const uint8_t *pre_flags, uint8_t *out_block_hash32, uint64_t *out_mask, ibft_tally_t *out_tally) {
+  proposal_batch p{raw, raw_off, round, out_block_hash32};
+  return block_seals_impl(c, nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally);
+}
+int ibft_recover_block_seals_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                 const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags,
+                                 uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask,
+                                 ibft_tally_t *out_tally) {
+  proposal_batch p{raw, raw_off, round, out_block_hash32};
+  return block_seals_impl(c, nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally);
+}
+static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off, size_t n_blocks,
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
                             uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally) {
   if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
@@ -2704,13 +2831,18 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, const uint
   }
   const size_t n = seal_off[n_blocks];
   if (n > c->max_rows) return IBFT_E_TOOBIG;
-  if (n && (!block_hash32 || !sig65 || (bare ? !out_signer20 : !signer20) || !out_mask)) return IBFT_E_INVAL;
+  if (n && ((!props && !block_hash32) || !sig65 || (bare ? !out_signer20 : !signer20) || !out_mask)) return IBFT_E_INVAL;
   ctx_lock lk(c);
   if (!c->have_valset) return IBFT_E_NOVALSET;
+  int rc;
+  if (props && (rc = check_proposals(c, *props, n_blocks))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const uint32_t nb = (uint32_t)n_blocks, nr = (uint32_t)n;
-  int rc;
   c->wire_valid = false;
+  // the proposals are hashed when rows wait for the hashes or the caller wants them
+  const bool hash_here = props && nb && (nr || props->out_hash32);
+  ColumnCopies cc;
+  if (hash_here && (rc = stage_proposals(c, cc, *props, nb))) return rc;
   if (nr) {
     if ((rc = ensure(c, c->d_boff, ((size_t)nb + 1) * 4))) return rc;
     if ((rc = ensure(c, c->d_bhash, (size_t)nb * 32))) return rc;
@@ -2728,15 +2860,19 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, const uint
       void *d = nullptr;  // the tally writes the records itself where the verdict words go there too (not under IBFT_NO_HOST_DIRECT)
       if (c->dh_mask && hipHostGetDevicePointer(&d, c->h_btally, 0) == hipSuccess) c->dh_btally = (uint64_t *)d;
     }
-    ColumnCopies cc;
     cc.add(c->d_boff.p, seal_off, ((size_t)nb + 1) * 4);
-    cc.add(c->d_bhash.p, block_hash32, (size_t)nb * 32);
+    if (!props) cc.add(c->d_bhash.p, block_hash32, (size_t)nb * 32);
     cc.add(c->d_sig.p, sig65, n * 65);
     if (!bare) cc.add(c->d_signer.p, signer20, n * 20);
     if (pre_flags) cc.add(c->d_pre.p, pre_flags, n);
-    if ((rc = cc.flush(c))) return rc;
-    if ((rc = seal_digest_column(c, (uint8_t *)c->d_bhash.p, nb))) return rc;
-    hipLaunchKernelGGL(ibftk::block_rows_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)c->d_bhash.p,
+  }
+  if ((rc = cc.flush(c))) return rc;
+  // (the digests' copy out is enqueued here, in front of the seal-digest convention that converts them in place)
+  if (hash_here && (rc = enqueue_proposal_digests(c, *props, nb))) return rc;
+  if (nr) {
+    uint8_t *d_block_hash = (uint8_t *)(props ? c->d_phash.p : c->d_bhash.p);
+    if ((rc = seal_digest_column(c, d_block_hash, nb))) return rc;
+    hipLaunchKernelGGL(ibftk::block_rows_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)d_block_hash,
                        (const uint32_t *)c->d_boff.p, nb, nr, (uint8_t *)c->d_hash.p);
     HIPCHK(c, hipGetLastError());
   }
@@ -2762,7 +2898,10 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, const uint
     }
     memcpy(out_mask, c->h_mask, mw * 8);
     if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
+  } else if (hash_here) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  if (hash_here && props->out_hash32) memcpy(props->out_hash32, c->h_phash, (size_t)nb * 32);
   if (bare) c->staged_n = 0;  // (as after ibft_recover_seals: bare rows are no resident batch)
   if (out_tally)
     for (uint32_t b = 0; b < nb; b++) {  // (no rows at all: every block is empty, power 0 < quorum)

@@ -158,6 +158,61 @@ HD void hash_bytes(const uint8_t *in, uint32_t len, uint64_t out4[4]) {
   for (int i = 0; i < 4; i++) out4[i] = s[i];
 }
 
+// Keccak-256 of in[0, len) ‖ tail by one lane — a proposal and the eight bytes of its round, which are NOT in memory behind
+// the proposal: `tail` holds them as they would lie there (byte k of the message tail = bits 8k … 8k+7) and the absorb step
+// splices them in, wherever they fall: inside a rate block, across two, or in front of a block that holds only the padding
+// (len + 8 ≡ 0 mod 136).  The proposal is read as kernels.hip.h:hash_range_dwords reads a payload — a block is 35 aligned
+// dword loads issued together and realigned with funnel shifts, a start at any offset mod 4 — and only where a block holds
+// proposal bytes.  Reads up to 7 bytes past in + len: the staged buffer carries 256 bytes of slack.  len ≤ 2^32 − 9.
+// (HD: tests/test_dev_proposal_digest_host.py runs this very source on the CPU.)
+HD void hash_range_tail_dwords(const uint8_t *__restrict__ in, uint32_t len, uint64_t tail, uint64_t out4[4]) {
+  uint64_t s[25];
+#pragma unroll
+  for (int i = 0; i < 25; i++) s[i] = 0;
+  const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in) & 3u), sh = 8u * mis;
+  const uint32_t *p = reinterpret_cast<const uint32_t *>(in - mis);
+  const uint32_t total = len + 8u;
+  for (uint32_t done = 0;; done += 136u, p += 34) {
+    const uint32_t left = total - done;
+    const uint32_t take = left < 136u ? left : 136u;                  // message bytes in this block, the round's included
+    const uint32_t ahead = done < len ? len - done : 0u;              // proposal bytes still to come (this block and later)
+    const uint32_t back = done < len ? 0u : done - len;               // bytes of the round already absorbed (0 … 7)
+    const uint32_t rawb = ahead < 136u ? ahead : 136u;                // proposal bytes in this block
+    const uint32_t nd = (rawb + 3u) >> 2;                             // dwords that hold them
+    uint32_t raw[35];
+#pragma unroll
+    for (int j = 0; j < 35; j++) raw[j] = (rawb && (uint32_t)j <= nd) ? p[j] : 0u;
+    uint32_t w[34];
+#pragma unroll
+    for (int j = 0; j < 34; j++) {
+      const uint32_t at = 4u * (uint32_t)j;                           // bytes at … at+3 of the block
+      const uint32_t v = (uint32_t)(((uint64_t)raw[j + 1] << 32 | raw[j]) >> sh);
+      const uint32_t have = rawb > at ? rawb - at : 0u;               // how many of them are proposal bytes
+      w[j] = have >= 4u ? v : (have ? (v & ((1u << (8u * have)) - 1u)) : 0u);
+      // the round: from byte (at − ahead + back) of the tail on, or — where the proposal ends inside this word — shifted up
+      // behind its last 1 … 3 bytes.  (ahead ≥ 136: neither branch is taken, the round lies in a later block.)
+      if (at >= ahead) {
+        const uint32_t d = at - ahead + back;
+        w[j] |= d < 8u ? (uint32_t)(tail >> (8u * d)) : 0u;
+      } else if (at + 4u > ahead) {
+        w[j] |= (uint32_t)tail << (8u * (ahead - at));
+      }
+      // pad10*1: first bit right after the message … (static register index: no scratch)
+      w[j] |= (take < 136u && (take >> 2) == (uint32_t)j) ? 0x01u << (8u * (take & 3u)) : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < 17; i++) s[i] ^= (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+    if (take < 136u) s[16] ^= 0x8000000000000000ULL;                  // … last bit at byte 135
+    f1600(s);
+    if (take < 136u) break;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) out4[i] = s[i];
+}
+
+// BE64(round) as the eight bytes lie in memory behind a proposal (the `tail` of hash_range_tail_dwords / cw::sponge_message)
+HD uint64_t round_tail(uint64_t round) { return bswap64(round); }
+
 // digest lanes (little-endian bytes) -> 256-bit big-endian integer in 8 LE limbs
 HD void digest_to_limbs(const uint64_t d[4], uint32_t limbs[8]) {
 #pragma unroll

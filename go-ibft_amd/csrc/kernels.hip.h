@@ -6,6 +6,7 @@
 //
 //   hash_eq_kernel              a1  IsValidProposalHash   (core/ibft.go:858-861, 938)
 //   proposal_hash_kernel            keccak256(raw ‖ BE64(round)), once per batch
+//   proposal_digest_kernel<1|64>    n of them in one launch, the round spliced in on the device (chain sync from proposals)
 //   ecrecover_lane_kernel       a2  IsValidCommittedSeal  (core/ibft.go:943)      cold path,
 //   ecrecover_group_kernel<G>   a3  IsValidValidator      (core/ibft.go:1128)     1 / 2,4,8 lanes per signature
 //   ecrecover_wave_kernel           same, one wavefront per signature (limbs spread over lanes, wave_fe_dev.h)
@@ -244,6 +245,47 @@ __global__ void __launch_bounds__(64) proposal_hash_kernel(const uint64_t *__res
     sp.permute(A, B);
   }
   if (lane < 4u) out4[lane] = sp.s;
+}
+
+// ---- chain sync from the proposals: n proposal hashes in one launch (ibft_proposal_hashes, the _raw block calls) ----------
+// out32[i] = keccak256(raw[raw_off[i], raw_off[i+1]) ‖ BE64(round[i])), straight from the caller's bytes as they were staged:
+// nothing is padded or re-packed on the host, the eight bytes of the round are spliced in by the absorb step.  One sponge is
+// sequential, n sponges are not — two forms, the same digests:
+//   LANES = 1   a lane per proposal (keccak::hash_range_tail_dwords): 64 proposals per wavefront in the time of the longest
+//               one, ≈9.4 µs per 136-byte block — the throughput form;
+//   LANES = 64  a wavefront per proposal (cw::sponge_message, the state over 25 lanes, ≈5.3 µs per block) — the latency form:
+//               one sponge per wavefront, one wavefront per workgroup (the sponge's barrier orders ONE wavefront's LDS accesses).
+// The host picks by batch shape (ibftgpu.hip:proposal_form).  Proposals start at any offset mod 4; reads stay inside the staged
+// buffer (≤ 7 bytes past a proposal's end, the buffer carries 256 bytes of slack).
+struct proposal_digest_args {
+  const uint8_t *raw;       // the proposals, concatenated
+  const uint32_t *raw_off;  // n + 1 offsets, raw_off[0] = 0, non-decreasing (checked by the host)
+  const uint64_t *round;    // n
+  uint8_t *out32;           // n × 32
+  uint32_t n;
+};
+template <int LANES>
+__global__ void __launch_bounds__(64) proposal_digest_kernel(proposal_digest_args a) {
+  if constexpr (LANES == 1) {
+    const uint32_t row = blockIdx.x * 64u + threadIdx.x;
+    const bool live = row < a.n;
+    // idle lanes hash an empty proposal (one block) and store nothing
+    const uint32_t o0 = live ? a.raw_off[row] : 0u, o1 = live ? a.raw_off[row + 1] : 0u;
+    const uint64_t tail = keccak::round_tail(live ? a.round[row] : 0ull);
+    uint64_t d[4];
+    keccak::hash_range_tail_dwords(a.raw + o0, o1 - o0, tail, d);
+    if (live) {
+      uint4 *o = reinterpret_cast<uint4 *>(a.out32 + 32ull * row);
+      o[0] = make_uint4((uint32_t)d[0], (uint32_t)(d[0] >> 32), (uint32_t)d[1], (uint32_t)(d[1] >> 32));
+      o[1] = make_uint4((uint32_t)d[2], (uint32_t)(d[2] >> 32), (uint32_t)d[3], (uint32_t)(d[3] >> 32));
+    }
+  } else {
+    __shared__ uint64_t A[32], B[32];
+    const uint32_t row = blockIdx.x, lane = threadIdx.x;  // (grid = n: block-uniform, always a live row)
+    const uint32_t o0 = a.raw_off[row], len = a.raw_off[row + 1] - o0;
+    const uint64_t word = cw::sponge_message(a.raw + o0, len, 0u, len + 8u, keccak::round_tail(a.round[row]), true, lane, A, B);
+    if (lane < 4u) *reinterpret_cast<uint64_t *>(a.out32 + 32ull * row + 8u * lane) = word;
+  }
 }
 
 // bit i of mask = (hash_len[i] == 32 && hash32[i] == H); rows are 32 B so each lane

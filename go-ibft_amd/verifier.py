@@ -44,12 +44,15 @@ EXPORTS = [
     "ibft_comm_preload", "ibft_issue_probe", "ibft_seals_rows", "ibft_pipeline_stats", "ibft_verify_block_seals",
     "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
     "ibft_recover_seals", "ibft_recover_block_seals",
+    "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
-# ibft_recover_seals / ibft_recover_block_seals came without a version step: an older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
+# ibft_recover_seals / ibft_recover_block_seals and ibft_proposal_hashes / the two _raw block calls came without a version step: an
+# older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
 EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
 OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
-                    "ibft_recover_seals", "ibft_recover_block_seals"}
+                    "ibft_recover_seals", "ibft_recover_block_seals",
+                    "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw"}
 COMM_ID_BYTES = 128
 E_RCCL = -8
 
@@ -189,6 +192,12 @@ def load_library() -> C.CDLL:
         L.ibft_recover_seals.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Tally)]
     if hasattr(L, "ibft_recover_block_seals"):
         L.ibft_recover_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_proposal_hashes"):
+        L.ibft_proposal_hashes.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+    if hasattr(L, "ibft_verify_block_seals_raw"):
+        L.ibft_verify_block_seals_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_recover_block_seals_raw"):
+        L.ibft_recover_block_seals_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "ibft_block_seals_submit"):
         L.ibft_block_seals_submit.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
     if hasattr(L, "ibft_block_seals_collect"):
@@ -267,6 +276,25 @@ def _bytes_col(x) -> np.ndarray:
     if isinstance(x, np.ndarray) and x.dtype == np.uint8 and x.flags["C_CONTIGUOUS"] and x.size:
         return x.reshape(-1)
     return np.frombuffer(bytes(x) or b"\0", dtype=np.uint8)
+
+
+def proposal_columns(raws, rounds):
+    """the proposals of a batch as the C ABI wants them: `raws` is a list of bytes-likes or a pair (raw, raw_off) — the concatenated
+    bytes (bytes or a uint8 array; a pinned one stays pinned) and n + 1 offsets — → (raw uint8[], raw_off uint32[n + 1], round uint64[n])"""
+    if isinstance(raws, tuple) and len(raws) == 2 and not isinstance(raws[1], (bytes, bytearray, memoryview)):
+        raw, off = _bytes_col(raws[0]), np.ascontiguousarray(raws[1], dtype=np.uint32)
+    else:
+        raws = [bytes(r) for r in raws]
+        raw = _bytes_col(b"".join(raws))
+        off = np.zeros(len(raws) + 1, dtype=np.uint32)
+        total = np.cumsum([len(r) for r in raws], dtype=np.uint64)
+        if len(total) and int(total[-1]) > 0xFFFFFFFF:
+            raise ValueError("proposals of one call must stay below 4 GiB (32-bit offsets)")
+        off[1:] = total
+    rnd = np.ascontiguousarray(rounds, dtype=np.uint64).reshape(-1)
+    if len(off) != len(rnd) + 1:
+        raise ValueError("raw_off needs one entry more than there are rounds")
+    return raw, off, rnd
 
 
 def shard_range(n_total: int, rank: int, world: int) -> tuple[int, int]:
@@ -487,6 +515,66 @@ class BatchVerifier:
                                                    tallies), "ibft_recover_block_seals")
         self._staged = 0
         return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb]
+
+    # chain sync from the proposals: the blocks' hashes are computed on the device
+    def proposal_hashes(self, raws, rounds) -> np.ndarray:
+        """ibft_proposal_hashes: keccak256(raw_i ‖ BE64(round_i)) of n proposals in one call → uint8 (n, 32).  raws: a list of
+        bytes, or (raw, raw_off) — see proposal_columns"""
+        if not hasattr(self._L, "ibft_proposal_hashes"):
+            raise GpuUnavailable("this build of the library has no ibft_proposal_hashes — rebuild")
+        raw, off, rnd = proposal_columns(raws, rounds)
+        n = len(rnd)
+        out = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        self._chk(self._L.ibft_proposal_hashes(self._h, _p(raw), _p(off), _p(rnd), n, _p(out)), "ibft_proposal_hashes")
+        return out[:n]
+
+    def verify_block_seals_raw(self, raws, rounds, seal_off, sig65, signer20, pre_flags=None, want_hashes: bool = True):
+        """ibft_verify_block_seals_raw: verify_block_seals with the blocks' PROPOSALS (raws, rounds as for proposal_hashes) in
+        place of their hashes → (verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
+        if not hasattr(self._L, "ibft_verify_block_seals_raw"):
+            raise GpuUnavailable("this build of the library has no ibft_verify_block_seals_raw — rebuild")
+        raw, roff, rnd = proposal_columns(raws, rounds)
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
+        n = len(s)
+        if len(rnd) != nb or len(f) != n or int(off[-1]) != n:
+            raise ValueError("one proposal per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        tallies = (Tally * max(nb, 1))()
+        bh = np.zeros((max(nb, 1), 32), dtype=np.uint8) if want_hashes else None
+        self._chk(self._L.ibft_verify_block_seals_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(f), _p(pre),
+                                                      _p(bh), _p(mask), tallies), "ibft_verify_block_seals_raw")
+        self._staged = n
+        return mask_to_bool(mask, n), list(tallies)[:nb], (bh[:nb] if want_hashes else None)
+
+    def recover_block_seals_raw(self, raws, rounds, seal_off, sig65, pre_flags=None, want_hashes: bool = True):
+        """ibft_recover_block_seals_raw: recover_block_seals with the blocks' PROPOSALS in place of their hashes →
+        (signer20 (n, 20), vidx int32[n], verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
+        if not hasattr(self._L, "ibft_recover_block_seals_raw"):
+            raise GpuUnavailable("this build of the library has no ibft_recover_block_seals_raw — rebuild")
+        raw, roff, rnd = proposal_columns(raws, rounds)
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        s = _u8(sig65, (-1, 65))
+        n = len(s)
+        if len(rnd) != nb or int(off[-1]) != n:
+            raise ValueError("one proposal per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        signer = np.zeros((max(n, 1), 20), dtype=np.uint8)
+        vidx = np.full(max(n, 1), -1, dtype=np.int32)
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        tallies = (Tally * max(nb, 1))()
+        bh = np.zeros((max(nb, 1), 32), dtype=np.uint8) if want_hashes else None
+        self._chk(self._L.ibft_recover_block_seals_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(pre), _p(bh),
+                                                       _p(signer), _p(vidx), _p(mask), tallies), "ibft_recover_block_seals_raw")
+        self._staged = 0
+        return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb], (bh[:nb] if want_hashes else None)
 
     # chain sync as a stream: submit(k + 1), collect(k) — at most two batches in flight
     def _need_block_stream(self):

@@ -18,6 +18,10 @@
  *   ibft_recover_seals, ibft_recover_block_seals
  *                        <- the same for BARE committed seals (finalized headers that carry only signatures): the signer
  *                           is what ecrecover returns — address out, membership of the recovered address, HasQuorum
+ *   ibft_proposal_hashes, ibft_verify_block_seals_raw, ibft_recover_block_seals_raw
+ *                        <- chain sync from (Proposal, []CommittedSeal) pairs (core/backend.go:80-82): the proposal hash of
+ *                           every block — keccak256(RawProposal ‖ BE64(Round)), what IsValidProposalHash recomputes
+ *                           (core/backend.go:50-51) — on the device, alone or in front of the two block calls above
  *   ibft_verify_senders  <- Verifier.IsValidValidator(msg)
  *                           /root/reference/core/backend.go:41-45; call sites
  *                           /root/reference/core/ibft.go:735, 1128, 1213, 1220
@@ -210,7 +214,8 @@ int ibft_verify_hashes_digest(ibft_ctx *ctx, const uint8_t digest32[32], const u
  * can work on it absorbs 25 MB/s (41 ms for 1 MiB, round 2); the 32-byte digest then reaches the device on the side
  * stream, behind the verdict launch it overlaps with.  IBFT_PROPOSAL_HASH=device selects the wavefront kernel (A/B,
  * tests).  The device keeps every hash of which there are MANY to do in parallel: PayloadNoSig of every message, the
- * address of every recovered key, the digests of a certificate tree.                                               */
+ * address of every recovered key, the digests of a certificate tree, the proposals of a batch of blocks
+ * (ibft_proposal_hashes below).                                                                                     */
 int ibft_proposal_hash(ibft_ctx *ctx, const uint8_t *raw, size_t raw_len, uint64_t round,
                        uint8_t out32[32]);
 
@@ -307,6 +312,50 @@ int ibft_recover_seals(ibft_ctx *ctx, const uint8_t *hash32, const uint8_t *sig6
 int ibft_recover_block_seals(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
                              const uint8_t *sig65, const uint8_t *pre_flags,
                              uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally);
+
+/* Chain sync from the PROPOSALS.  A node that is catching up holds (Proposal, []CommittedSeal) pairs
+ * (/root/reference/core/backend.go:80-82, messages/helpers.go:16-35), not proposal hashes: what the seals of a block sign is
+ * keccak256(RawProposal ‖ BE64(Round)) and the node has to COMPUTE it — a hash a peer sends along is evidence of nothing.
+ * One sponge is sequential (ibft_proposal_hash: on the host); the hashes of a batch of blocks are MANY, so they are the device's.
+ *   raw       the proposals' RawProposal bytes, concatenated — as they are: nothing is padded, aligned or re-packed
+ *   raw_off   n + 1 offsets, raw_off[0] = 0, non-decreasing: proposal i is raw[raw_off[i], raw_off[i+1]) (any length, 0 included)
+ *   round     n: Proposal.Round of each
+ *   out_hash32[32·i …] = keccak256(raw_i ‖ BE64(round[i]))
+ * Defining property: row i equals ibft_proposal_hash(ctx, raw_i, len_i, round[i]) byte for byte, for every length, in both forms
+ * of the kernel — one lane per proposal (throughput) or one wavefront per proposal (latency), chosen by batch shape: the lane
+ * form from 8 192 proposals of the longest one's length on (total rate blocks ≥ 8 192 × the longest proposal's; environment
+ * IBFT_PROPOSAL_LANE_ROWS moves that, IBFT_PROPOSAL_LANES = 1|64 pins a form; both read at ibft_ctx_create).
+ * The call neither reads nor changes the proposal the context remembers (ibft_proposal_hash / ibft_verify_hashes /
+ * ibft_forget_proposal work as before), needs no validator set and leaves a resident staged batch alone; n = 0 is legal (no
+ * pointer is looked at).  Sources in ibft_pinned_alloc memory are read by one gather launch, pageable ones by a copy command
+ * per column; the results are the same.  Checked in this order: IBFT_E_INVAL NULL ctx, NULL out_hash32 / raw_off / round with
+ * n > 0, raw_off[0] ≠ 0; IBFT_E_TOOBIG n > cfg.max_rows; IBFT_E_INVAL decreasing offsets; IBFT_E_TOOBIG raw_off[n] above the
+ * byte budget (environment IBFT_PROPOSAL_BYTES_MAX, default 256 MiB = 268435456; the device buffer grows on demand up to it and
+ * is kept); IBFT_E_INVAL NULL raw with raw_off[n] > 0.  Nothing is written to out_hash32 by a refused call.  From which proposal
+ * size on a caller with idle cores should hash on the host instead: INTEGRATION.md §11.                                   */
+int ibft_proposal_hashes(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round, size_t n,
+                         uint8_t *out_hash32);
+
+/* ibft_verify_block_seals / ibft_recover_block_seals with the PROPOSALS of the n_blocks blocks (raw, raw_off, round as for
+ * ibft_proposal_hashes with n = n_blocks) in place of block_hash32: the hashes are computed on the device and never cross
+ * PCIe on the way in.  out_block_hash32: n_blocks × 32, may be NULL — the computed proposal hashes (BEFORE the seal-digest
+ * convention is applied), for the caller's own IsValidProposalHash compare of 32 bytes.
+ * Defining property: the call equals ibft_proposal_hashes followed by the hashes-given call with those hashes — same mask
+ * words, tallies, signer / index columns, bit for bit, cold and warm, under every convention of ibft_set_seal_digest (applied
+ * to the computed hash exactly as to a given one).  Everything the hashes-given calls document holds unchanged: the rows are
+ * the resident staged batch after the verify form and not after the recover form, behaviour towards the two pipelines, key
+ * learning.  Errors: those of the hashes-given call in its order (minus the NULL block_hash32), then those of
+ * ibft_proposal_hashes' arguments in its order; nothing is written to any out buffer of a refused call.  With no seal rows at
+ * all the proposals are hashed only if out_block_hash32 is given.  There is no streamed (submit / collect) form of these calls:
+ * a node that streams hashes the next batch with ibft_proposal_hashes and submits the hashes.                              */
+int ibft_verify_block_seals_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20,
+                                const uint8_t *pre_flags, uint8_t *out_block_hash32, uint64_t *out_mask,
+                                ibft_tally_t *out_tally);
+int ibft_recover_block_seals_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                 const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags,
+                                 uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask,
+                                 ibft_tally_t *out_tally);
 
 /* a3. payload = concatenated PayloadNoSig bytes; row i is payload[off[i]..off[i+1]);
  * off has n+1 entries.                                                             */

@@ -304,6 +304,112 @@ func (c *Ctx) RecoverBlockSeals(blockHash32 []byte, sealOff []uint32, sig65, pre
 	return signer20[:20*n], vidx[:n], mask, tallies, nil
 }
 
+// checkProposals makes the length checks of the three calls that take a batch of proposals: rawOff has one entry more
+// than round, raw holds rawOff's last offset.  (Order and start of the offsets are the library's to check.)
+func checkProposals(raw []byte, rawOff []uint32, round []uint64) error {
+	if len(rawOff) != len(round)+1 {
+		return fmt.Errorf("%w: rawOff needs one entry more than round", ErrFallback)
+	}
+	if len(raw) < int(rawOff[len(round)]) {
+		return fmt.Errorf("%w: raw shorter than rawOff says", ErrFallback)
+	}
+	return nil
+}
+
+// ProposalHashes = keccak256(RawProposal ‖ BE64(Round)) of n proposals in one call (ibft_proposal_hashes): proposal i is
+// raw[rawOff[i]:rawOff[i+1]] with round[i]; hash32[32i:32i+32] is its proposal hash — what ProposalHash returns for it,
+// computed on the device.  For a syncing node that holds (Proposal, []CommittedSeal) pairs and no hashes.
+func (c *Ctx) ProposalHashes(raw []byte, rawOff []uint32, round []uint64) (hash32 []byte, err error) {
+	if err = checkProposals(raw, rawOff, round); err != nil {
+		return nil, err
+	}
+	n := len(round)
+	hash32 = make([]byte, 32*n+32)
+	roundCol := make([]uint64, n+1) // (never empty: a pointer to its first entry exists)
+	copy(roundCol, round)
+	rc := C.ibft_proposal_hashes(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
+		(*C.uint64_t)(unsafe.Pointer(&roundCol[0])), C.size_t(n), ptr8(hash32))
+	if err = c.check(rc); err != nil {
+		return nil, err
+	}
+	return hash32[:32*n], nil
+}
+
+// VerifyBlockSealsRaw = VerifyBlockSeals with the blocks' PROPOSALS (raw, rawOff, round as for ProposalHashes, one per
+// block) in place of their hashes (ibft_verify_block_seals_raw): the hashes are computed on the device and returned in
+// blockHash32 for the caller's own 32-byte compare.
+func (c *Ctx) VerifyBlockSealsRaw(raw []byte, rawOff []uint32, round []uint64, sealOff []uint32, sig65, signer20, preFlags []byte) (blockHash32 []byte, mask []uint64, tallies []Tally, err error) {
+	if len(sealOff) == 0 {
+		return nil, nil, nil, fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(round) != nb {
+		return nil, nil, nil, fmt.Errorf("%w: one proposal per block", ErrFallback)
+	}
+	if err = checkProposals(raw, rawOff, round); err != nil {
+		return nil, nil, nil, err
+	}
+	if len(sig65) < 65*n || len(signer20) < 20*n || (preFlags != nil && len(preFlags) < n) {
+		return nil, nil, nil, fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	blockHash32 = make([]byte, 32*nb+32)
+	mask = make([]uint64, (n+63)/64+1)
+	ct := make([]C.ibft_tally_t, nb+1)
+	roundCol := make([]uint64, nb+1)
+	copy(roundCol, round)
+	rc := C.ibft_verify_block_seals_raw(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
+		(*C.uint64_t)(unsafe.Pointer(&roundCol[0])), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), C.size_t(nb),
+		ptr8(sig65), ptr8(signer20), ptr8(preFlags), ptr8(blockHash32), (*C.uint64_t)(unsafe.Pointer(&mask[0])),
+		(*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err = c.check(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	tallies = make([]Tally, nb)
+	for b := range tallies {
+		tallies[b] = tally(ct[b])
+	}
+	return blockHash32[:32*nb], mask, tallies, nil
+}
+
+// RecoverBlockSealsRaw = RecoverBlockSeals with the blocks' PROPOSALS in place of their hashes
+// (ibft_recover_block_seals_raw); blockHash32 as from VerifyBlockSealsRaw.
+func (c *Ctx) RecoverBlockSealsRaw(raw []byte, rawOff []uint32, round []uint64, sealOff []uint32, sig65, preFlags []byte) (blockHash32, signer20 []byte, vidx []int32, mask []uint64, tallies []Tally, err error) {
+	if len(sealOff) == 0 {
+		return nil, nil, nil, nil, nil, fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(round) != nb {
+		return nil, nil, nil, nil, nil, fmt.Errorf("%w: one proposal per block", ErrFallback)
+	}
+	if err = checkProposals(raw, rawOff, round); err != nil {
+		return nil, nil, nil, nil, nil, err
+	}
+	if len(sig65) < 65*n || (preFlags != nil && len(preFlags) < n) {
+		return nil, nil, nil, nil, nil, fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	blockHash32 = make([]byte, 32*nb+32)
+	signer20 = make([]byte, 20*n+20)
+	vidx = make([]int32, n+1)
+	mask = make([]uint64, (n+63)/64+1)
+	ct := make([]C.ibft_tally_t, nb+1)
+	roundCol := make([]uint64, nb+1)
+	copy(roundCol, round)
+	rc := C.ibft_recover_block_seals_raw(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
+		(*C.uint64_t)(unsafe.Pointer(&roundCol[0])), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), C.size_t(nb),
+		ptr8(sig65), ptr8(preFlags), ptr8(blockHash32), ptr8(signer20), (*C.int32_t)(unsafe.Pointer(&vidx[0])),
+		(*C.uint64_t)(unsafe.Pointer(&mask[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err = c.check(rc); err != nil {
+		return nil, nil, nil, nil, nil, err
+	}
+	tallies = make([]Tally, nb)
+	for b := range tallies {
+		tallies[b] = tally(ct[b])
+	}
+	return blockHash32[:32*nb], signer20[:20*n], vidx[:n], mask, tallies, nil
+}
+
 // blockBatch keeps the columns of one BlockSealsSubmit reachable — and, where they are Go memory, pinned — until its
 // BlockSealsCollect: the library's copy stream reads them after the cgo call has returned.
 type blockBatch struct {
