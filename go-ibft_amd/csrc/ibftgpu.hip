@@ -75,6 +75,25 @@ struct DeviceShared {
 std::mutex g_devices_mu;
 std::map<int, std::weak_ptr<DeviceShared>> g_devices;
 
+// A FAMILY of validator sets (ibft_set_validator_sets): state of its own next to the context's single set.  The first block
+// of members is what the verdict kernels and the key cache know as "the validator set" — one table over the UNION of the
+// family's addresses, the union's key-cache slots; while a _sets call runs these are exchanged with the context's own
+// (family_view), so enqueue_recover, build_new_tables and the key cache serve both without knowing which they serve.  The
+// rest is what only block_tally_sets_kernel reads.
+struct ValFamily {
+  DevBuf d_vtab, d_vslot;
+  std::vector<uint32_t> vslot;
+  uint32_t vslot_mask = 0, n_union = 0, my_built = 0;
+  uint64_t seen_build_epoch = 0;
+  bool cache_on = false;
+
+  bool have = false;
+  uint32_t n_sets = 0, power_words = 1, largest_set = 0;
+  DevBuf d_setidx, d_meta, d_power, d_quorum, d_seen, d_bset;
+  std::vector<uint64_t> quorum;  // n_sets × TALLY_SUM_WORDS
+  uint64_t device_bytes = 0;
+};
+
 struct ibft_ctx {
   std::mutex mu;
   std::shared_ptr<DeviceShared> dev;   // the G table and the key cache of this context's device
@@ -178,6 +197,8 @@ struct ibft_ctx {
   uint64_t proposal_bytes_max = 256ull << 20;  // IBFT_PROPOSAL_BYTES_MAX: the most raw_off[n] may be (IBFT_E_TOOBIG beyond)
   uint32_t proposal_lanes_force = 0;           // IBFT_PROPOSAL_LANES=1|64 pins the form of proposal_digest_kernel (tests, A/B)
   uint32_t proposal_lane_rows = 8192;          // AUTO: the lane form from this many proposals of the longest one's length on
+  ValFamily fam;                                     // ibft_set_validator_sets / the _sets block calls
+  uint64_t valsets_bytes_max = 512ull << 20;         // IBFT_VALSETS_BYTES_MAX: the most a family's device tables may take
   uint64_t last_wide[ibftk::TALLY_SUM_WORDS] = {0};  // full-width power of the last fetched tally
   uint64_t height = 0;
   // the seal-digest convention of the embedding Backend (ibft_set_seal_digest): 0 = the proposalHash itself
@@ -424,6 +445,39 @@ struct ctx_lock {
       c->side_pending = false;
     }
   }
+};
+
+// While one lives (c->mu held), "the validator set" of the context — table, slot mask, size, key-cache slots and their
+// counters — is the family's union, and the context's own set waits in the family's fields; the destructor puts both back.
+// EXCHANGED (what make_args, enqueue_recover, recount_built, build_new_tables and key_cache_map / _unmap read): d_vtab, d_vslot,
+// vslot, vslot_mask, n_validators, my_built, seen_build_epoch, cache_on.  A field added to the context that these helpers read
+// as part of "the validator set" belongs in exchange().
+// NOT exchanged — they stay the SINGLE set's while a view lives, and nothing on the _sets path may read them: have_valset,
+// d_vpower, d_quorum, quorum_w, power_words, d_seen, h_vtab, valset_addrs, height, last_wide.  Their family counterparts are
+// read from c->fam directly (enqueue_block_tally_sets: fam.d_power, d_quorum, power_words, d_seen, largest_set; block_seals_impl:
+// fam.have, fam.quorum, fam.n_sets).
+struct family_view {
+  ibft_ctx *c;
+  static void exchange(ibft_ctx *c) {
+    ValFamily &f = c->fam;
+    std::swap(c->d_vtab, f.d_vtab);
+    std::swap(c->d_vslot, f.d_vslot);
+    c->vslot.swap(f.vslot);
+    std::swap(c->vslot_mask, f.vslot_mask);
+    std::swap(c->n_validators, f.n_union);
+    std::swap(c->my_built, f.my_built);
+    std::swap(c->seen_build_epoch, f.seen_build_epoch);
+    std::swap(c->cache_on, f.cache_on);
+  }
+  bool on;
+  explicit family_view(ibft_ctx *cc, bool on_ = true) : c(cc), on(on_) {
+    if (on) exchange(c);
+  }
+  ~family_view() {
+    if (on) exchange(c);
+  }
+  family_view(const family_view &) = delete;
+  family_view &operator=(const family_view &) = delete;
 };
 
 // enqueue the verdict kernels over the resident columns: warm kernel first when tables exist
@@ -1495,6 +1549,7 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   if (const char *e = getenv("IBFT_PROPOSAL_LANE_ROWS")) c->proposal_lane_rows = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_PROPOSAL_BYTES_MAX"))  // (offsets are 32-bit; room is kept for the round and the slack)
     c->proposal_bytes_max = std::min<uint64_t>(strtoull(e, nullptr, 10), 0xFFFFFE00ull);
+  if (const char *e = getenv("IBFT_VALSETS_BYTES_MAX")) c->valsets_bytes_max = strtoull(e, nullptr, 10);
   if (const char *e = getenv("IBFT_ROWS_PAIR")) {
     if (!strcmp(e, "0")) c->rows_pair_force = 0;
     else if (!strcmp(e, "1")) c->rows_pair_force = 1;
@@ -1575,7 +1630,8 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_cert_slot, &c->d_cert_tiles, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
                     &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally,
                     &c->d_bhash_nx, &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
-                    &c->d_phash})
+                    &c->d_phash, &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
+                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset})
     release(*b);
   if (c->h_phash) (void)hipHostFree(c->h_phash);
   if (c->tstream) {
@@ -1593,6 +1649,8 @@ void ibft_ctx_destroy(ibft_ctx *c) {
   if (c->dev) {
     {
       std::lock_guard<std::mutex> dlk(c->dev->mu);
+      key_cache_unmap(c);
+      family_view fv(c);  // … and the slots the family's union holds
       key_cache_unmap(c);
     }
     std::lock_guard<std::mutex> glk(g_devices_mu);
@@ -1766,6 +1824,46 @@ static int key_cache_map(ibft_ctx *c, const std::vector<KeyAddr> &vaddr) {
   return IBFT_OK;
 }
 
+// total voting power of nv validators (pw little-endian 64-bit words each) and quorum = ⌊2·total/3⌋ + 1 (calculateQuorum,
+// validator_manager.go:130-135) in TALLY_SUM_WORDS × 64 bits, as 32-bit halves: total → ×2 → long division by 3 → +1.
+// false: the total is zero (no quorum exists).
+static bool quorum_words(const uint64_t *pwv, size_t nv, uint32_t pw, uint64_t quorum_w[ibftk::TALLY_SUM_WORDS]) {
+  constexpr int H = 2 * ibftk::TALLY_SUM_WORDS;
+  uint64_t piece[H] = {0};
+  for (size_t v = 0; v < nv; v++)
+    for (uint32_t k = 0; k < 2 * pw; k++) piece[k] += (pwv[v * pw + k / 2] >> (32 * (k & 1))) & 0xFFFFFFFFull;
+  uint32_t half[H];
+  {
+    uint64_t carry = 0;
+    for (int k = 0; k < H; k++) {
+      const uint64_t t = carry + piece[k];
+      half[k] = (uint32_t)t;
+      carry = t >> 32;
+    }
+  }
+  bool zero = true;
+  for (int k = 0; k < H; k++) zero = zero && half[k] == 0;
+  if (zero) return false;
+  {
+    uint32_t carry = 0;  // × 2
+    for (int k = 0; k < H; k++) {
+      const uint32_t top = half[k] >> 31;
+      half[k] = (half[k] << 1) | carry;
+      carry = top;
+    }
+    uint64_t rem = 0;    // ÷ 3
+    for (int k = H - 1; k >= 0; k--) {
+      const uint64_t cur = (rem << 32) | half[k];
+      half[k] = (uint32_t)(cur / 3);
+      rem = cur % 3;
+    }
+    for (int k = 0; k < H; k++)  // + 1
+      if (++half[k] != 0) break;
+  }
+  for (int i = 0; i < ibftk::TALLY_SUM_WORDS; i++) quorum_w[i] = (uint64_t)half[2 * i] | ((uint64_t)half[2 * i + 1] << 32);
+  return true;
+}
+
 static int set_validators_impl(ibft_ctx *c, uint64_t height, const uint8_t *addrs20, const uint64_t *power, uint32_t pw,
                                size_t n) {
   ctx_lock lk(c);
@@ -1802,42 +1900,8 @@ static int set_validators_impl(ibft_ctx *c, uint64_t height, const uint8_t *addr
     }
   }
   const size_t nv = pwv.size() / pw;
-  // total voting power and quorum = ⌊2·total/3⌋ + 1 (calculateQuorum, validator_manager.go:130-135) in
-  // TALLY_SUM_WORDS × 64 bits, as 32-bit halves: total → ×2 → long division by 3 → +1
-  constexpr int H = 2 * ibftk::TALLY_SUM_WORDS;
-  uint64_t piece[H] = {0};
-  for (size_t v = 0; v < nv; v++)
-    for (uint32_t k = 0; k < 2 * pw; k++) piece[k] += (pwv[v * pw + k / 2] >> (32 * (k & 1))) & 0xFFFFFFFFull;
-  uint32_t half[H];
-  {
-    uint64_t carry = 0;
-    for (int k = 0; k < H; k++) {
-      const uint64_t t = carry + piece[k];
-      half[k] = (uint32_t)t;
-      carry = t >> 32;
-    }
-  }
-  bool zero = true;
-  for (int k = 0; k < H; k++) zero = zero && half[k] == 0;
-  if (zero) return IBFT_E_POWER;  // validator_manager.go:68-70
-  {
-    uint32_t carry = 0;  // × 2
-    for (int k = 0; k < H; k++) {
-      const uint32_t top = half[k] >> 31;
-      half[k] = (half[k] << 1) | carry;
-      carry = top;
-    }
-    uint64_t rem = 0;    // ÷ 3
-    for (int k = H - 1; k >= 0; k--) {
-      const uint64_t cur = (rem << 32) | half[k];
-      half[k] = (uint32_t)(cur / 3);
-      rem = cur % 3;
-    }
-    for (int k = 0; k < H; k++)  // + 1
-      if (++half[k] != 0) break;
-  }
   uint64_t quorum_w[ibftk::TALLY_SUM_WORDS];
-  for (int i = 0; i < ibftk::TALLY_SUM_WORDS; i++) quorum_w[i] = (uint64_t)half[2 * i] | ((uint64_t)half[2 * i + 1] << 32);
+  if (!quorum_words(pwv.data(), nv, pw, quorum_w)) return IBFT_E_POWER;  // validator_manager.go:68-70
   int rc;
   if ((rc = upload(c, c->d_vtab, tab.data(), tab.size() * 4))) return rc;
   if ((rc = upload(c, c->d_vpower, pwv.data(), pwv.size() * 8))) return rc;
@@ -1880,6 +1944,169 @@ int ibft_set_validators_u256(ibft_ctx *c, uint64_t height, const uint8_t *addrs2
       words[4 * i + w] = v;
     }
   return set_validators_impl(c, height, addrs20, words.data(), 4, n);
+}
+
+// ---- a family of validator sets: the union's table, setidx[s][u], per-set powers / quorum / size ---------------------------
+// Everything that can refuse is decided on the host before the device is touched, and the new tables are complete in buffers
+// of their own before the old family is let go: a refused install leaves the previous family as it was.
+static int check_validator_sets_args(const ibft_ctx *c, size_t n_sets, const uint32_t *set_off, const void *addrs20, const void *power) {
+  if (!c || n_sets == 0 || !set_off || set_off[0] != 0) return IBFT_E_INVAL;
+  for (size_t s = 0; s < n_sets; s++)
+    if (set_off[s + 1] < set_off[s]) return IBFT_E_INVAL;
+  if (set_off[n_sets] && (!addrs20 || !power)) return IBFT_E_INVAL;
+  return IBFT_OK;
+}
+
+static int set_validator_sets_impl(ibft_ctx *c, size_t n_sets, const uint32_t *set_off, const uint8_t *addrs20, const uint64_t *power,
+                                   uint32_t pw) {
+  for (size_t s = 0; s < n_sets; s++)
+    if (set_off[s + 1] - set_off[s] > c->max_rows) return IBFT_E_TOOBIG;
+  // union index of an address: the order of first appearance over the whole family.  Within a set a repeated address keeps
+  // its FIRST position and its LAST power, as in set_validators_impl.
+  std::unordered_map<KeyAddr, uint32_t, KeyAddrHash> union_of;
+  std::vector<KeyAddr> uaddr;
+  std::vector<uint32_t> stamp, pos;     // by union index: the last set that listed it (+1), its index in that set
+  std::vector<uint32_t> member_u;       // the sets' distinct members, set after set, as union indices
+  std::vector<uint64_t> pwv;            // … and their powers, pw words each
+  std::vector<uint32_t> pbase(n_sets + 1, 0);
+  member_u.reserve(set_off[n_sets]);
+  pwv.reserve((size_t)set_off[n_sets] * pw);
+  for (size_t s = 0; s < n_sets; s++) {
+    pbase[s] = (uint32_t)member_u.size();
+    for (uint32_t i = set_off[s]; i < set_off[s + 1]; i++) {
+      KeyAddr ka;
+      memcpy(ka.b, addrs20 + 20ull * i, 20);
+      auto it = union_of.find(ka);
+      uint32_t u;
+      if (it == union_of.end()) {
+        u = (uint32_t)uaddr.size();
+        if (u >= c->max_rows) return IBFT_E_TOOBIG;
+        union_of.emplace(ka, u);
+        uaddr.push_back(ka);
+        stamp.push_back(0);
+        pos.push_back(0);
+      } else {
+        u = it->second;
+      }
+      if (stamp[u] == (uint32_t)s + 1) {
+        memcpy(&pwv[((size_t)pbase[s] + pos[u]) * pw], power + (size_t)i * pw, (size_t)pw * 8);
+        continue;
+      }
+      stamp[u] = (uint32_t)s + 1;
+      pos[u] = (uint32_t)member_u.size() - pbase[s];
+      member_u.push_back(u);
+      pwv.insert(pwv.end(), power + (size_t)i * pw, power + (size_t)(i + 1) * pw);
+    }
+  }
+  pbase[n_sets] = (uint32_t)member_u.size();
+  const size_t nu = uaddr.size();
+  uint32_t slots = 64, largest = 0;
+  while (slots < 2 * nu + 2) slots <<= 1;
+  for (size_t s = 0; s < n_sets; s++) largest = std::max(largest, pbase[s + 1] - pbase[s]);
+  const size_t seen_bytes = std::max<size_t>(((size_t)(largest + 31) / 32) * 4, 4);
+  const uint64_t setidx_bytes = (uint64_t)n_sets * nu * 4;
+  const uint64_t bytes = (uint64_t)slots * 24 + setidx_bytes + (uint64_t)n_sets * 8 + (uint64_t)pwv.size() * 8 +
+                         (uint64_t)n_sets * ibftk::TALLY_SUM_WORDS * 8 + seen_bytes;
+  if (bytes > c->valsets_bytes_max) return IBFT_E_TOOBIG;
+  std::vector<uint64_t> quorum(n_sets * ibftk::TALLY_SUM_WORDS);
+  for (size_t s = 0; s < n_sets; s++)  // an empty set included: its total is zero
+    if (!quorum_words(pwv.data() + (size_t)pbase[s] * pw, pbase[s + 1] - pbase[s], pw, &quorum[s * ibftk::TALLY_SUM_WORDS]))
+      return IBFT_E_POWER;
+  std::vector<uint32_t> tab((size_t)slots * 6, 0);
+  for (size_t u = 0; u < nu; u++) {
+    uint32_t a[5];
+    memcpy(a, uaddr[u].b, 20);
+    uint32_t sl = ibftk::addr_hash(a) & (slots - 1);
+    while (tab[(size_t)sl * 6 + 5] != 0) sl = (sl + 1) & (slots - 1);
+    memcpy(&tab[(size_t)sl * 6], a, 20);
+    tab[(size_t)sl * 6 + 5] = (uint32_t)u + 1;
+  }
+  std::vector<int32_t> setidx((size_t)n_sets * nu, -1);
+  std::vector<uint32_t> meta(n_sets * 2);
+  for (size_t s = 0; s < n_sets; s++) {
+    meta[2 * s] = pbase[s];
+    meta[2 * s + 1] = pbase[s + 1] - pbase[s];
+    for (uint32_t k = pbase[s]; k < pbase[s + 1]; k++) setidx[s * nu + member_u[k]] = (int32_t)(k - pbase[s]);
+  }
+
+  ctx_lock lk(c);
+  HIPCHK(c, hipSetDevice(c->device));
+  ValFamily nf;
+  DevBuf *fresh[] = {&nf.d_vtab, &nf.d_setidx, &nf.d_meta, &nf.d_power, &nf.d_quorum, &nf.d_seen};
+  int rc = IBFT_OK;
+  if (!(rc = upload(c, nf.d_vtab, tab.data(), tab.size() * 4)) && !(rc = upload(c, nf.d_setidx, setidx.data(), setidx.size() * 4)) &&
+      !(rc = upload(c, nf.d_meta, meta.data(), meta.size() * 4)) && !(rc = upload(c, nf.d_power, pwv.data(), pwv.size() * 8)) &&
+      !(rc = upload(c, nf.d_quorum, quorum.data(), quorum.size() * 8)) && !(rc = ensure(c, nf.d_seen, seen_bytes))) {
+    if (hipMemsetAsync(nf.d_seen.p, 0, nf.d_seen.cap, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+      c->last_error = "ibft_set_validator_sets: upload failed";
+      rc = IBFT_E_HIP;
+    }
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);
+    for (DevBuf *b : fresh) release(*b);
+    return rc;
+  }
+  // the new family is whole: the old one goes (no kernel reads it — every _sets call has synchronised before it returned)
+  ValFamily &f = c->fam;
+  std::swap(f.d_vtab, nf.d_vtab);
+  std::swap(f.d_setidx, nf.d_setidx);
+  std::swap(f.d_meta, nf.d_meta);
+  std::swap(f.d_power, nf.d_power);
+  std::swap(f.d_quorum, nf.d_quorum);
+  std::swap(f.d_seen, nf.d_seen);
+  for (DevBuf *b : fresh) release(*b);
+  f.vslot_mask = slots - 1;
+  f.n_union = (uint32_t)nu;
+  f.n_sets = (uint32_t)n_sets;
+  f.power_words = pw;
+  f.largest_set = largest;
+  f.quorum.swap(quorum);
+  f.have = true;
+  // warm path: the union's addresses hold key-cache slots while the family is installed — references of their own, next to
+  // those of the context's single set; an address the previous family held keeps its slot and its table
+  if (c->flags & IBFT_FLAG_PUBKEY_CACHE) {
+    family_view fv(c);
+    std::lock_guard<std::mutex> dlk(c->dev->mu);
+    c->cache_on = key_cache_map(c, uaddr) == IBFT_OK;
+  }
+  f.device_bytes = f.d_vtab.cap + f.d_setidx.cap + f.d_meta.cap + f.d_power.cap + f.d_quorum.cap + f.d_seen.cap + f.d_vslot.cap;
+  return IBFT_OK;
+}
+
+int ibft_set_validator_sets(ibft_ctx *c, size_t n_sets, const uint64_t *height, const uint32_t *set_off, const uint8_t *addrs20,
+                            const uint64_t *power) {
+  (void)height;  // informational
+  int rc = check_validator_sets_args(c, n_sets, set_off, addrs20, power);
+  if (rc) return rc;
+  return set_validator_sets_impl(c, n_sets, set_off, addrs20, power, 1);
+}
+
+int ibft_set_validator_sets_u256(ibft_ctx *c, size_t n_sets, const uint64_t *height, const uint32_t *set_off, const uint8_t *addrs20,
+                                 const uint8_t *power_be32) {
+  (void)height;
+  int rc = check_validator_sets_args(c, n_sets, set_off, addrs20, power_be32);
+  if (rc) return rc;
+  for (size_t s = 0; s < n_sets; s++)  // (before the powers are converted: a list beyond max_rows is not walked)
+    if (set_off[s + 1] - set_off[s] > c->max_rows) return IBFT_E_TOOBIG;
+  const size_t n = set_off[n_sets];
+  std::vector<uint64_t> words(n * 4);  // big.Int.FillBytes(32) → four little-endian words
+  for (size_t i = 0; i < n; i++)
+    for (int w = 0; w < 4; w++) {
+      uint64_t v = 0;
+      for (int b = 0; b < 8; b++) v = (v << 8) | power_be32[32 * i + 8 * (3 - w) + b];
+      words[4 * i + w] = v;
+    }
+  return set_validator_sets_impl(c, n_sets, set_off, addrs20, words.data(), 4);
+}
+
+int ibft_validator_sets_info(ibft_ctx *c, uint32_t *n_sets, uint32_t *union_size, uint64_t *device_bytes) {
+  if (!c) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  if (n_sets) *n_sets = c->fam.have ? c->fam.n_sets : 0;
+  if (union_size) *union_size = c->fam.have ? c->fam.n_union : 0;
+  if (device_bytes) *device_bytes = c->fam.have ? c->fam.device_bytes + c->fam.d_bset.cap : 0;  // + the calls' block_set column
+  return IBFT_OK;
 }
 
 int ibft_last_tally_wide(ibft_ctx *c, ibft_tally_wide_t *out) {
@@ -2694,6 +2921,52 @@ static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t w
   return IBFT_OK;
 }
 
+// The same under a family of validator sets (the block's set in fam.d_bset): block_tally_sets_kernel, the launch shapes of the
+// tally above with the LARGEST set in the place of the one set's size.
+static int enqueue_block_tally_sets(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t widest, uint64_t *host_mask, uint64_t *out) {
+  if (c->read_pending) {
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
+    c->read_pending = false;
+  }
+  const ValFamily &f = c->fam;
+  ibftk::block_tally_sets_args t{};
+  t.work_mask = (uint64_t *)c->d_mask.p;
+  t.mask = (uint64_t *)c->d_mask_out.p;
+  t.host_mask = host_mask;
+  t.vidx = (int32_t *)c->d_vidx.p;
+  t.vpower32 = (const uint32_t *)f.d_power.p;
+  t.off = (const uint32_t *)c->d_boff.p;
+  t.block_set = (const uint32_t *)f.d_bset.p;
+  t.setidx = (const int32_t *)f.d_setidx.p;
+  t.set_meta = (const uint2 *)f.d_meta.p;
+  t.quorum = (const uint64_t *)f.d_quorum.p;
+  t.n = nr;
+  t.n_blocks = nb;
+  t.n_union = c->n_validators;  // (under family_view: the union's size)
+  const size_t lds = (size_t)((f.largest_set + 31) / 32) * 4;
+  t.lds_bitmap = lds <= 49152 ? 1u : 0u;
+  t.seen = (uint32_t *)f.d_seen.p;
+  t.acc = (uint64_t *)c->d_acc.p;
+  t.out = out;
+  const dim3 grid(t.lds_bitmap ? std::min(nb, ibftk::BTALLY_MAX_GRID) : 1u);
+  const size_t dyn = t.lds_bitmap ? lds : 0;
+  const bool wide = widest > 256u * ibftk::BTALLY_RPT;
+  if (f.power_words == 1) {
+    if (wide)
+      hipLaunchKernelGGL((ibftk::block_tally_sets_kernel<1, 1024>), grid, dim3(1024), dyn, c->stream, t);
+    else
+      hipLaunchKernelGGL((ibftk::block_tally_sets_kernel<1, 256>), grid, dim3(256), dyn, c->stream, t);
+  } else {
+    if (wide)
+      hipLaunchKernelGGL((ibftk::block_tally_sets_kernel<4, 1024>), grid, dim3(1024), dyn, c->stream, t);
+    else
+      hipLaunchKernelGGL((ibftk::block_tally_sets_kernel<4, 256>), grid, dim3(256), dyn, c->stream, t);
+  }
+  HIPCHK(c, hipGetLastError());
+  if ((uint32_t)mask_words(nr) >= c->mask_dirty_words) c->mask_dirty_words = 0;
+  return IBFT_OK;
+}
+
 // ---- chain sync from the proposals: keccak256(RawProposal ‖ BE64(Round)) of n proposals on the device ------------------------
 // A batch of proposals as the caller holds it.  check_proposals is everything that needs no device (and writes nothing);
 // stage_proposals adds the three columns to the call's ColumnCopies — the route of every neighbouring call: ONE gather launch
@@ -2795,7 +3068,8 @@ int ibft_proposal_hashes(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_of
 // indices the tally reads.
 static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off, size_t n_blocks,
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
-                            uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally);
+                            uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally,
+                            bool sets = false, const uint32_t *block_set = nullptr);
 int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, uint64_t *out_mask,
                             ibft_tally_t *out_tally) {
@@ -2821,7 +3095,8 @@ int ibft_recover_block_seals_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t
 }
 static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off, size_t n_blocks,
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
-                            uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally) {
+                            uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally,
+                            bool sets, const uint32_t *block_set) {
   if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
   if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;  // (max_rows never changes after ibft_ctx_create)
   uint32_t widest = 0;  // rows of the largest block: picks the tally's workgroup size
@@ -2832,8 +3107,14 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
   const size_t n = seal_off[n_blocks];
   if (n > c->max_rows) return IBFT_E_TOOBIG;
   if (n && ((!props && !block_hash32) || !sig65 || (bare ? !out_signer20 : !signer20) || !out_mask)) return IBFT_E_INVAL;
+  if (sets && n_blocks && !block_set) return IBFT_E_INVAL;
   ctx_lock lk(c);
-  if (!c->have_valset) return IBFT_E_NOVALSET;
+  if (sets ? !c->fam.have : !c->have_valset) return IBFT_E_NOVALSET;
+  if (sets)  // refused on the host: no launch ever sees a set the family does not have
+    for (size_t b = 0; b < n_blocks; b++)
+      if (block_set[b] >= c->fam.n_sets) return IBFT_E_INVAL;
+  // sets: from here to the return "the validator set" of the context is the family's union (table, size, key-cache slots)
+  family_view fv(c, sets);
   int rc;
   if (props && (rc = check_proposals(c, *props, n_blocks))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -2861,6 +3142,10 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
       if (c->dh_mask && hipHostGetDevicePointer(&d, c->h_btally, 0) == hipSuccess) c->dh_btally = (uint64_t *)d;
     }
     cc.add(c->d_boff.p, seal_off, ((size_t)nb + 1) * 4);
+    if (sets) {
+      if ((rc = ensure(c, c->fam.d_bset, (size_t)nb * 4))) return rc;
+      cc.add(c->fam.d_bset.p, block_set, (size_t)nb * 4);
+    }
     if (!props) cc.add(c->d_bhash.p, block_hash32, (size_t)nb * 32);
     cc.add(c->d_sig.p, sig65, n * 65);
     if (!bare) cc.add(c->d_signer.p, signer20, n * 20);
@@ -2876,14 +3161,17 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
                        (const uint32_t *)c->d_boff.p, nb, nr, (uint8_t *)c->d_hash.p);
     HIPCHK(c, hipGetLastError());
   }
-  // the rows are the resident batch from here on, exactly as ibft_seals_stage would have left them
-  c->staged_n = nr;
+  // the rows are the resident batch from here on, exactly as ibft_seals_stage would have left them (not under a family: rows
+  // judged against the union are nothing ibft_seals_launch could re-judge under the single set)
+  c->staged_n = sets ? 0 : nr;
   c->staged_pre = pre_flags != nullptr;
   if (nr) {
     if (c->ev_used >= 4096) c->ev_used = 0;
     const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
     if ((rc = enqueue_recover(c, nr, c->staged_pre, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
-    if ((rc = enqueue_block_tally(c, nb, nr, widest, c->dh_mask, c->dh_btally ? c->dh_btally : (uint64_t *)c->d_btally.p))) return rc;
+    uint64_t *const records = c->dh_btally ? c->dh_btally : (uint64_t *)c->d_btally.p;
+    if ((rc = sets ? enqueue_block_tally_sets(c, nb, nr, widest, c->dh_mask, records) : enqueue_block_tally(c, nb, nr, widest, c->dh_mask, records)))
+      return rc;
     if (bare && (rc = copy_emitted(c, nr, out_signer20, out_vidx))) return rc;
     c->host_direct = false;
     const size_t mw = (size_t)mask_words(nr);
@@ -2907,8 +3195,9 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
     for (uint32_t b = 0; b < nb; b++) {  // (no rows at all: every block is empty, power 0 < quorum)
       ibft_tally_t &t = out_tally[b];
       memset(&t, 0, sizeof t);
-      t.quorum_lo = c->quorum_w[0];
-      t.quorum_hi = c->quorum_w[1];
+      const uint64_t *q = sets ? &c->fam.quorum[(size_t)block_set[b] * ibftk::TALLY_SUM_WORDS] : c->quorum_w;
+      t.quorum_lo = q[0];
+      t.quorum_hi = q[1];
       if (!nr) continue;
       const uint64_t *r = c->h_btally + 4ull * b;
       t.power_lo = r[0];
@@ -2918,6 +3207,19 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
       t.has_quorum = (uint32_t)r[3];
     }
   return IBFT_OK;
+}
+
+int ibft_verify_block_seals_sets(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, const uint32_t *block_set,
+                                 size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags,
+                                 uint64_t *out_mask, ibft_tally_t *out_tally) {
+  return block_seals_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally,
+                          true, block_set);
+}
+int ibft_recover_block_seals_sets(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, const uint32_t *block_set,
+                                  size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags, uint8_t *out_signer20,
+                                  int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally) {
+  return block_seals_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally,
+                          true, block_set);
 }
 
 // Streamed chain sync: the same batch as ibft_verify_block_seals, enqueued and not waited for.  Up to two batches in flight;

@@ -17,6 +17,7 @@
 //   verify_known_wave_kernel        same, one wavefront per signature in the row layout of wave_fe_dev.h
 //   tally_kernel                a8  HasQuorum             (core/validator_manager.go:77-96)
 //   block_rows_kernel, block_tally_kernel   chain sync: each block's hash → its rows, one HasQuorum per block
+//   block_tally_sets_kernel         … one HasQuorum per block under the block's OWN validator set (a family of sets)
 //   gtab_build_kernel, qtab_build_kernel, qtab_commit_kernel   one-time fixed-base tables
 //   lookup_kernel                   sender → validator index for ibft_tally()
 //   wire_parse_kernel, wire_stage_seals_kernel   §8f rank 3: wire bytes → columns on the device (wire_dev.h)
@@ -2128,6 +2129,141 @@ __global__ void __launch_bounds__(THREADS) block_tally_kernel(block_tally_args a
   const uint32_t words = (a.n + 63) / 64;
   for (uint32_t i = tid; i < words; i += THREADS) {
     const uint64_t w = a.work_mask[i];
+    a.work_mask[i] = 0;
+    a.mask[i] = w;
+    if (a.host_mask) a.host_mask[i] = w;
+  }
+  if (tid == 0) __hip_atomic_store(a.acc + TALLY_MAX_PIECES + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The same over a FAMILY of validator sets (ibft_verify_block_seals_sets): the verdict kernels judged every row against the
+// union of the family's addresses and left the signer's UNION index; block b is judged under set block_set[b].  Per row one
+// dependent load more than above — setidx[set][union index] → the index in the block's set (recover_dev.h: valsets_row), issued
+// for the BTALLY_RPT rows of a step together, in front of the powers.  A row whose signer is in the union but not in the
+// block's set loses its verdict bit: an atomic AND on its word of the work mask — other workgroups read other bits of that word
+// and never see theirs change — before the row is counted; the last workgroup (the ticket) then moves the words, which it reads
+// past its compute unit's cache, so no clear of another workgroup is missed.  The index column is rewritten from union to set
+// index (−1: no member of the block's set), which is what the emitting form delivers as out_vidx and what the HBM-bitmap
+// form's clean-up pass reads.  Bitmap, powers and quorum are the SET's: powers of set s start at entry set_meta[s].x of
+// vpower32, its distinct addresses number set_meta[s].y.
+struct block_tally_sets_args {
+  uint64_t *work_mask;
+  uint64_t *mask, *host_mask;
+  int32_t *vidx;              // n: in — union index where the verdict bit is set; out — index in the block's set or −1
+  const uint32_t *vpower32;   // Σ set sizes × 2·PW pieces
+  const uint32_t *off;        // n_blocks + 1 row offsets
+  const uint32_t *block_set;  // n_blocks, every entry < n_sets (checked on the host)
+  const int32_t *setidx;      // n_sets × n_union
+  const uint2 *set_meta;      // n_sets × {first power entry, distinct addresses}
+  const uint64_t *quorum;     // n_sets × TALLY_SUM_WORDS
+  uint32_t n, n_blocks, n_union;
+  uint32_t lds_bitmap;        // ⌈largest set/32⌉ words of dynamic LDS; 0: `seen` in HBM, and the grid is one workgroup
+  uint32_t *seen;             // ⌈largest set/32⌉ words, zero between launches (HBM form only)
+  uint64_t *acc;              // TALLY_ACC_WORDS, zero between launches (the ticket)
+  uint64_t *out;              // n_blocks × 4 u64
+};
+template <int PW, int THREADS>
+__global__ void __launch_bounds__(THREADS) block_tally_sets_kernel(block_tally_sets_args a) {
+  constexpr int NP = 2 * PW;
+  constexpr int WAVES = THREADS / 64;
+  constexpr uint32_t STEP = (uint32_t)THREADS * BTALLY_RPT;
+  extern __shared__ uint32_t lseen[];
+  __shared__ uint64_t part[NP + 1][WAVES];
+  __shared__ uint32_t last_flag;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  uint32_t *bm = a.lds_bitmap ? lseen : a.seen;
+  for (uint32_t b = blockIdx.x; b < a.n_blocks; b += gridDim.x) {
+    const uint32_t r0 = a.off[b], r1 = a.off[b + 1];
+    const uint32_t set = a.block_set[b];
+    const uint2 meta = a.set_meta[set];
+    if (a.lds_bitmap)
+      for (uint32_t i = tid; i < (meta.y + 31) / 32; i += THREADS) lseen[i] = 0;
+    __syncthreads();
+    uint64_t p[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) p[k] = 0;
+    uint64_t valid = 0, distinct = 0;
+    for (uint32_t base = r0; base < r1; base += STEP) {
+      bool bit[BTALLY_RPT];
+      int ui[BTALLY_RPT];
+      valsets_row_t sr[BTALLY_RPT];
+      uint32_t pw[BTALLY_RPT][NP];
+      // Row mapping: row r of the block belongs to thread (r − r0) mod THREADS (STEP is a multiple of THREADS).  The HBM-bitmap
+      // clean-up below REQUIRES the same mapping: there every thread re-reads the set indices it stored itself.
+      // The verdict word is read with a relaxed atomic load: other workgroups may atomic-AND other bits of the same word.
+#pragma unroll
+      for (int j = 0; j < BTALLY_RPT; j++) {
+        const uint32_t r = base + (uint32_t)j * THREADS + tid;
+        bit[j] = r < r1 && ((__hip_atomic_load(a.work_mask + (r >> 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (r & 63)) & 1ull);
+        ui[j] = r < r1 ? a.vidx[r] : -1;
+      }
+#pragma unroll
+      for (int j = 0; j < BTALLY_RPT; j++) sr[j] = valsets_row(bit[j], ui[j], a.setidx, a.n_union, set);
+#pragma unroll
+      for (int j = 0; j < BTALLY_RPT; j++) {
+#pragma unroll
+        for (int k = 0; k < NP; k++) pw[j][k] = sr[j].si >= 0 ? a.vpower32[((size_t)meta.x + (uint32_t)sr[j].si) * NP + k] : 0u;
+      }
+#pragma unroll
+      for (int j = 0; j < BTALLY_RPT; j++) {
+        const uint32_t r = base + (uint32_t)j * THREADS + tid;
+        if (r < r1) a.vidx[r] = sr[j].si;
+        if (sr[j].clear) atomicAnd(reinterpret_cast<unsigned long long *>(a.work_mask + (r >> 6)), ~(1ull << (r & 63)));
+        valid += sr[j].bit;
+        if (sr[j].si < 0) continue;  // unknown signers contribute 0 (validator_manager.go:88-92)
+        const uint32_t m = 1u << (sr[j].si & 31);
+        if (atomicOr(&bm[sr[j].si >> 5], m) & m) continue;  // a signer's power counts once per block (:147-155)
+        distinct++;
+#pragma unroll
+        for (int k = 0; k < NP; k++) p[k] += pw[j][k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+      const uint64_t s = wave_sum_u64(p[k]);
+      if (lane == 0) part[k][wave] = s;
+    }
+    const uint64_t cnt = wave_sum_u64(valid | (distinct << 32));
+    if (lane == 0) part[NP][wave] = cnt;
+    __syncthreads();
+    if (!a.lds_bitmap)  // the HBM bitmap is left zero for the next block: clear the words this block set (vidx holds set indices,
+      for (uint32_t r = r0 + tid; r < r1; r += THREADS) {  // −1 wherever the row set nothing).  Same row → thread mapping as the
+                                                           // main loop, as required there: each thread re-reads its own stores
+        const int v = a.vidx[r];
+        if (v >= 0) bm[v >> 5] = 0u;
+      }
+    if (tid == 0) {
+      uint64_t piece[TALLY_MAX_PIECES], c = 0;
+#pragma unroll
+      for (int k = 0; k < TALLY_MAX_PIECES; k++) {
+        piece[k] = 0;
+        if (k < NP)
+          for (int w = 0; w < WAVES; w++) piece[k] += part[k][w];
+      }
+      for (int w = 0; w < WAVES; w++) c += part[NP][w];
+      uint64_t wd[TALLY_SUM_WORDS];
+      pieces_to_words(piece, NP, wd);
+      uint64_t *o = a.out + 4ull * b;
+      o[0] = wd[0];
+      o[1] = wd[1];
+      o[2] = c;
+      o[3] = words_ge(wd, a.quorum + (size_t)set * TALLY_SUM_WORDS) ? 1ull : 0ull;
+    }
+    __syncthreads();  // part[] and the bitmap are reused by the next block
+  }
+  // ---- every workgroup has read its rows' verdict words and cleared what it had to: the last one moves and zeroes them ----
+  __threadfence();  // (every thread: its atomic ANDs are performed before the ticket is taken)
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES + 2), 1ull);
+    last_flag = (t == (unsigned long long)gridDim.x - 1ull) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!last_flag) return;
+  const uint32_t words = (a.n + 63) / 64;
+  for (uint32_t i = tid; i < words; i += THREADS) {
+    const uint64_t w = __hip_atomic_load(a.work_mask + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     a.work_mask[i] = 0;
     a.mask[i] = w;
     if (a.host_mask) a.host_mask[i] = w;

@@ -55,6 +55,31 @@ __host__ __device__ __forceinline__ int valset_lookup(const uint32_t *__restrict
   return -1;
 }
 
+// ---- a family of validator sets (ibft_set_validator_sets): the row's signer under the set of ITS block --------------------
+// The verdict kernels look a signer up in ONE table over the union of the family's addresses and leave its union index;
+// setidx is n_sets × n_union int32, setidx[s][u] = index of union address u in set s (the position of its first occurrence in
+// that set's list, repeated addresses skipped — what valset_lookup returns under ibft_set_validators(set s)) or −1.
+// union_idx < 0 (no member of any set / nothing recovered) stays −1: no load is issued for it.
+__host__ __device__ __forceinline__ int valsets_set_index(const int32_t *__restrict__ setidx, uint32_t n_union, uint32_t set,
+                                                          int union_idx) {
+  return union_idx >= 0 ? setidx[(size_t)set * n_union + (uint32_t)union_idx] : -1;
+}
+// What the segmented tally decides for one row from its verdict bit and the union index the verdict kernel left.
+struct valsets_row_t {
+  int si;      // index in the block's set, −1: no member of it
+  bool bit;    // the row's verdict under the block's set
+  bool clear;  // the verdict kernel set the bit for a member of the union that is no member of this set: the bit goes
+};
+__host__ __device__ __forceinline__ valsets_row_t valsets_row(bool bit, int union_idx, const int32_t *__restrict__ setidx,
+                                                              uint32_t n_union, uint32_t set) {
+  valsets_row_t r;
+  const int u = bit ? union_idx : -1;  // (the index column is only meaningful where the verdict bit is set)
+  r.si = valsets_set_index(setidx, n_union, set, u);
+  r.clear = u >= 0 && r.si < 0;
+  r.bit = bit && !r.clear;
+  return r;
+}
+
 // ---- emitting form of the cold kernels (ibft_recover_seals): what a row stores once the curve is done ----------------
 // rec: a key was recovered (r, s, v in range, a curve point, not the point at infinity) and `got` is its address; pre: the
 // caller's pre_flags ruled the row out.  The address goes out as recovered — a non-member's too —, twenty zero bytes where there

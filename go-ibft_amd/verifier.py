@@ -45,14 +45,19 @@ EXPORTS = [
     "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
     "ibft_recover_seals", "ibft_recover_block_seals",
     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
+    "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
+    "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
-# ibft_recover_seals / ibft_recover_block_seals and ibft_proposal_hashes / the two _raw block calls came without a version step: an
+# ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
+# (ibft_set_validator_sets …, the two _sets block calls) came without a version step: an
 # older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
 EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
 OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
                     "ibft_recover_seals", "ibft_recover_block_seals",
-                    "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw"}
+                    "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
+                    "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
+                    "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets"}
 COMM_ID_BYTES = 128
 E_RCCL = -8
 
@@ -198,6 +203,16 @@ def load_library() -> C.CDLL:
         L.ibft_verify_block_seals_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "ibft_recover_block_seals_raw"):
         L.ibft_recover_block_seals_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_set_validator_sets"):
+        L.ibft_set_validator_sets.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
+    if hasattr(L, "ibft_set_validator_sets_u256"):
+        L.ibft_set_validator_sets_u256.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
+    if hasattr(L, "ibft_validator_sets_info"):
+        L.ibft_validator_sets_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    if hasattr(L, "ibft_verify_block_seals_sets"):
+        L.ibft_verify_block_seals_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_recover_block_seals_sets"):
+        L.ibft_recover_block_seals_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "ibft_block_seals_submit"):
         L.ibft_block_seals_submit.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
     if hasattr(L, "ibft_block_seals_collect"):
@@ -513,6 +528,94 @@ class BatchVerifier:
         tallies = (Tally * max(nb, 1))()
         self._chk(self._L.ibft_recover_block_seals(self._h, _p(bh), _p(off), nb, _p(s), _p(pre), _p(signer), _p(vidx), _p(mask),
                                                    tallies), "ibft_recover_block_seals")
+        self._staged = 0
+        return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb]
+
+    # chain sync across validator-set changes: a family of sets on the context, a set per block
+    def _need(self, name: str):
+        if not hasattr(self._L, name):
+            raise GpuUnavailable(f"this build of the library has no {name} — rebuild")
+
+    @staticmethod
+    def _set_columns(sets, u256: bool):
+        """sets: a list of (addrs20, powers) or (height, addrs20, powers) → (heights u64[n_sets], set_off u32[n_sets + 1],
+        addrs (total, 20) u8, powers)"""
+        heights, off, addrs, powers = [], [0], [], []
+        for k, st in enumerate(sets):
+            h, a, p = st if len(st) == 3 else (k, st[0], st[1])
+            a = _u8(a, (-1, 20))
+            p = powers_be32(p) if u256 else np.ascontiguousarray(p, dtype=np.uint64)
+            if len(a) != len(p):
+                raise ValueError("a set needs one power per address")
+            heights.append(int(h)); off.append(off[-1] + len(a)); addrs.append(a); powers.append(p)
+        a = np.concatenate(addrs) if addrs else np.zeros((0, 20), dtype=np.uint8)
+        p = np.concatenate(powers) if powers else np.zeros((0, 32) if u256 else 0, dtype=np.uint8 if u256 else np.uint64)
+        return (np.asarray(heights, dtype=np.uint64), np.asarray(off, dtype=np.uint32), np.ascontiguousarray(a),
+                np.ascontiguousarray(p))
+
+    def try_set_validator_sets(self, sets, u256: bool = False) -> int:
+        name = "ibft_set_validator_sets_u256" if u256 else "ibft_set_validator_sets"
+        self._need(name)
+        h, off, a, p = self._set_columns(sets, u256)
+        return getattr(self._L, name)(self._h, len(h), _p(h), _p(off), _p(a) if len(a) else None, _p(p) if len(p) else None)
+
+    def set_validator_sets(self, sets) -> None:
+        """ibft_set_validator_sets: install a family of validator sets — a list of (addrs20, powers) or (height, addrs20,
+        powers) — next to the single set of set_validators; block b of a _sets call names its set by its index here"""
+        self._chk(self.try_set_validator_sets(sets, False), "ibft_set_validator_sets")
+
+    def set_validator_sets_u256(self, sets) -> None:
+        """the same with powers as Python ints < 2^256"""
+        self._chk(self.try_set_validator_sets(sets, True), "ibft_set_validator_sets_u256")
+
+    def validator_sets_info(self):
+        """→ (sets, union addresses, device bytes) of the installed family; (0, 0, 0) without one"""
+        self._need("ibft_validator_sets_info")
+        n, u, b = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._chk(self._L.ibft_validator_sets_info(self._h, C.byref(n), C.byref(u), C.byref(b)), "ibft_validator_sets_info")
+        return n.value, u.value, b.value
+
+    def verify_block_seals_sets(self, block_hash32, seal_off, block_set, sig65, signer20, pre_flags=None):
+        """ibft_verify_block_seals_sets: verify_block_seals with block b judged under set block_set[b] of the installed family
+        → (verdict bool[n], Tally list[n_blocks]; quorum is the block's set's)"""
+        self._need("ibft_verify_block_seals_sets")
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
+        n = len(s)
+        if len(bh) != nb or len(bs) != nb or len(f) != n or int(off[-1]) != n:
+            raise ValueError("block_hash32 / block_set need one row per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        tallies = (Tally * max(nb, 1))()
+        self._chk(self._L.ibft_verify_block_seals_sets(self._h, _p(bh), _p(off), _p(bs), nb, _p(s), _p(f), _p(pre), _p(mask),
+                                                       tallies), "ibft_verify_block_seals_sets")
+        self._staged = 0
+        return mask_to_bool(mask, n), list(tallies)[:nb]
+
+    def recover_block_seals_sets(self, block_hash32, seal_off, block_set, sig65, pre_flags=None):
+        """ibft_recover_block_seals_sets: recover_block_seals with a set per block → (signer20 (n, 20), vidx int32[n] — the index
+        in the BLOCK's set or -1 —, verdict bool[n], Tally list[n_blocks])"""
+        self._need("ibft_recover_block_seals_sets")
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65))
+        n = len(s)
+        if len(bh) != nb or len(bs) != nb or int(off[-1]) != n:
+            raise ValueError("block_hash32 / block_set need one row per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        signer = np.zeros((max(n, 1), 20), dtype=np.uint8)
+        vidx = np.full(max(n, 1), -1, dtype=np.int32)
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        tallies = (Tally * max(nb, 1))()
+        self._chk(self._L.ibft_recover_block_seals_sets(self._h, _p(bh), _p(off), _p(bs), nb, _p(s), _p(pre), _p(signer), _p(vidx),
+                                                        _p(mask), tallies), "ibft_recover_block_seals_sets")
         self._staged = 0
         return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb]
 

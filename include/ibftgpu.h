@@ -357,6 +357,71 @@ int ibft_recover_block_seals_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32
                                  uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask,
                                  ibft_tally_t *out_tally);
 
+/* Chain sync ACROSS validator-set changes: a FAMILY of validator sets on the context, and block calls that judge every
+ * block under the set the caller names for it — one call, one verdict launch, whatever the sets do between the blocks.
+ * A syncer collects the distinct sets of the run it fetched (GetVotingPowers per height), installs them once and passes
+ * block_set[b]; it no longer cuts its batch where the set changes.
+ *
+ * ibft_set_validator_sets[_u256]: n_sets sets; set s is entries [set_off[s], set_off[s+1]) of addrs20 / power (set_off has
+ *   n_sets + 1 entries, set_off[0] = 0, non-decreasing).  height[s]: informational, as in ibft_set_validators; may be NULL.
+ *   Within a set a repeated address keeps its LAST power and its FIRST position, exactly as ibft_set_validators treats its
+ *   list; the index of an address in set s (out_vidx below) is the index ibft_set_validators(set s) would give it.
+ *   The library builds one lookup table over the UNION of the family's addresses, a dense n_sets × union table of int32
+ *   (the index of union address u in set s, or −1) and per-set powers, quorum and size.
+ *   Checked in this order: IBFT_E_INVAL NULL ctx, n_sets = 0, NULL set_off, set_off[0] ≠ 0, decreasing offsets, a NULL column
+ *   with entries; IBFT_E_TOOBIG a set's list or the union holds more than cfg.max_rows addresses, or the family's device
+ *   tables exceed the byte budget (environment IBFT_VALSETS_BYTES_MAX, read at ibft_ctx_create; default 512 MiB =
+ *   536870912: 1 024 sets over a union of 8 192 take 32 MiB for the dense table and at most 64 MiB (u64) / 256 MiB (u256)
+ *   of powers); IBFT_E_POWER when ANY set's total power is zero, an empty set included.  All of it is decided on the host.
+ *   Installing a family replaces the previous family whole; a refused install leaves the previous one in place.
+ * ibft_validator_sets_info: sets and union addresses of the installed family and the device bytes it holds now (0, 0, 0
+ *   without one): the CAPACITIES of its buffers — the tables the budget counts (there by their computed sizes; a buffer is
+ *   never smaller than 256 bytes), plus the key-cache slot column of the union and the block_set column the _sets calls
+ *   upload, which grows with their n_blocks and is not part of the budget.  Any pointer may be NULL.
+ *
+ * ibft_verify_block_seals_sets / ibft_recover_block_seals_sets: ibft_verify_block_seals / ibft_recover_block_seals plus
+ *   block_set (n_blocks entries, each < n_sets): the set block b is judged under.
+ * Defining property: for every block b the mask bits of its rows, its ibft_tally_t (all fields; quorum_* is the quorum of
+ * set block_set[b]) and, in the recover form, its out_signer20 / out_vidx rows are bit for bit what
+ * ibft_set_validators(set block_set[b]) followed by ibft_verify_seals / ibft_recover_seals over that block's rows returns —
+ * cold and warm, under every ibft_set_seal_digest convention, with IBFT_FLAG_STRICT_LOW_S on and off, for u64 and u256
+ * powers (low 128 bits and the exact has_quorum, as the block calls document; ibft_last_tally_wide is not updated).  A block
+ * without rows has has_quorum = 0 and its set's quorum.  A validator that is in the family but not in the block's set gets
+ * bit 0 and no power in that block, and out_vidx −1 — its address in out_signer20 is delivered like any non-member's.
+ * Rules:
+ *  - The family is separate state.  ibft_set_validators and every other entry point neither read nor change it and behave
+ *    exactly as without one; the _sets calls never read the context's single set and do not need one: IBFT_E_NOVALSET
+ *    from them means "no family installed".
+ *  - Errors: those of ibft_verify_block_seals / ibft_recover_block_seals in their order; IBFT_E_INVAL for a NULL block_set
+ *    with n_blocks > 0 (with the NULL columns) and, behind IBFT_E_NOVALSET, for an entry ≥ n_sets — decided on the host,
+ *    before anything is launched.  Nothing is written to any out buffer of a refused call.
+ *  - After a _sets call the rows are NOT a resident staged batch (as after the recover forms: ibft_seals_launch finds no
+ *    rows).  Towards the two pipelines the calls behave as ibft_verify_block_seals does.  ibft_last_dispatch,
+ *    ibft_last_kernel_ms and ibft_cache_stats see a normal verify pass; the AUTO rule sees the total row count.
+ *  - Key cache (IBFT_FLAG_PUBKEY_CACHE): the union's addresses hold key-cache slots while the family is installed (the family
+ *    counts as a referrer of a slot next to the contexts' single sets: ibft_cache_memory); a _sets verify call teaches keys,
+ *    and later calls — _sets or single-set, on this context or another of the device — are warm for those addresses.  A
+ *    signer in the union but not in its block's set is verified like any row and its bit then cleared: the verdict (0) of
+ *    the per-set call's non-member early-out.
+ * When the single-set call is still the right one: a run judged under ONE set — it does without the per-row load of the
+ * dense table and one upload.  What the _sets call gains over a cut batch and what it costs over the single-set call:
+ * DESIGN.md §5.11, which also says what of it has been measured.  Out of scope: streamed (submit / collect) and _raw forms of the _sets calls (a
+ * syncer hashes with ibft_proposal_hashes first), the sharded group calls, and a family for the message-set / wire entry
+ * points (consensus runs at one height).                                                                              */
+int ibft_set_validator_sets(ibft_ctx *ctx, size_t n_sets, const uint64_t *height, const uint32_t *set_off,
+                            const uint8_t *addrs20, const uint64_t *power);
+int ibft_set_validator_sets_u256(ibft_ctx *ctx, size_t n_sets, const uint64_t *height, const uint32_t *set_off,
+                                 const uint8_t *addrs20, const uint8_t *power_be32);
+int ibft_validator_sets_info(ibft_ctx *ctx, uint32_t *n_sets, uint32_t *union_size, uint64_t *device_bytes);
+int ibft_verify_block_seals_sets(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off,
+                                 const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
+                                 const uint8_t *signer20, const uint8_t *pre_flags, uint64_t *out_mask,
+                                 ibft_tally_t *out_tally);
+int ibft_recover_block_seals_sets(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off,
+                                  const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
+                                  const uint8_t *pre_flags, uint8_t *out_signer20, int32_t *out_vidx,
+                                  uint64_t *out_mask, ibft_tally_t *out_tally);
+
 /* a3. payload = concatenated PayloadNoSig bytes; row i is payload[off[i]..off[i+1]);
  * off has n+1 entries.                                                             */
 int ibft_verify_senders(ibft_ctx *ctx, const uint8_t *payload, const uint32_t *off,

@@ -230,7 +230,8 @@ func (c *Ctx) VerifySeals(hash32, sig65, signer20, preFlags []byte) ([]uint64, T
 // VerifyBlockSeals = IsValidCommittedSeal + HasQuorum for the committed seals of many finalized blocks in one call
 // (ibft_verify_block_seals): the seals of block b are rows [sealOff[b], sealOff[b+1]) and sign
 // blockHash32[32b:32b+32].  mask bit i is row i's verdict, tallies[b] block b's HasQuorum — what one VerifySeals
-// per block returns.  One validator set per call: a syncer splits its batch where the set changes.
+// per block returns.  One validator set per call, the context's: a batch that crosses validator-set changes goes through
+// SetValidatorSets + VerifyBlockSealsSets instead of being split where the set changes.
 func (c *Ctx) VerifyBlockSeals(blockHash32 []byte, sealOff []uint32, sig65, signer20, preFlags []byte) ([]uint64, []Tally, error) {
 	if len(sealOff) == 0 {
 		return nil, nil, fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
@@ -292,6 +293,118 @@ func (c *Ctx) RecoverBlockSeals(blockHash32 []byte, sealOff []uint32, sig65, pre
 	mask = make([]uint64, (n+63)/64+1)
 	ct := make([]C.ibft_tally_t, nb+1)
 	rc := C.ibft_recover_block_seals(c.h, ptr8(blockHash32), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), C.size_t(nb),
+		ptr8(sig65), ptr8(preFlags), ptr8(signer20), (*C.int32_t)(unsafe.Pointer(&vidx[0])),
+		(*C.uint64_t)(unsafe.Pointer(&mask[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err := c.check(rc); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	tallies = make([]Tally, nb)
+	for b := range tallies {
+		tallies[b] = tally(ct[b])
+	}
+	return signer20[:20*n], vidx[:n], mask, tallies, nil
+}
+
+// SetValidatorSets installs a FAMILY of validator sets next to the single set of SetValidators (ibft_set_validator_sets):
+// set s is entries [setOff[s], setOff[s+1]) of addrs20 / power, height[s] is informational.  A syncer collects the distinct
+// sets of the run of blocks it fetched (GetVotingPowers per height), installs them once and names each block's set by its
+// index here.  Installing replaces the previous family whole; a refused install leaves it in place.
+func (c *Ctx) SetValidatorSets(height []uint64, setOff []uint32, addrs20 []byte, power []uint64) error {
+	if len(setOff) < 2 || len(height) != len(setOff)-1 {
+		return fmt.Errorf("%w: setOff needs n_sets + 1 entries, height n_sets", ErrFallback)
+	}
+	ns := len(setOff) - 1
+	n := int(setOff[ns])
+	if len(addrs20) < 20*n || len(power) < n {
+		return fmt.Errorf("%w: columns shorter than setOff says", ErrFallback)
+	}
+	var pp *C.uint64_t
+	if n > 0 {
+		pp = (*C.uint64_t)(unsafe.Pointer(&power[0]))
+	}
+	return c.check(C.ibft_set_validator_sets(c.h, C.size_t(ns), (*C.uint64_t)(unsafe.Pointer(&height[0])),
+		(*C.uint32_t)(unsafe.Pointer(&setOff[0])), ptr8(addrs20), pp))
+}
+
+// SetValidatorSetsBig is SetValidatorSets for *big.Int powers (every one must fit 256 bits, as for SetValidatorsBig).
+func (c *Ctx) SetValidatorSetsBig(height []uint64, setOff []uint32, addrs20 []byte, power []*big.Int) error {
+	if len(setOff) < 2 || len(height) != len(setOff)-1 {
+		return fmt.Errorf("%w: setOff needs n_sets + 1 entries, height n_sets", ErrFallback)
+	}
+	ns := len(setOff) - 1
+	n := int(setOff[ns])
+	if len(addrs20) < 20*n || len(power) < n {
+		return fmt.Errorf("%w: columns shorter than setOff says", ErrFallback)
+	}
+	be := make([]byte, 32*n)
+	for i, p := range power[:n] {
+		if p.Sign() < 0 || p.BitLen() > 256 {
+			return fmt.Errorf("%w: voting power %d does not fit 256 bits", ErrFallback, i)
+		}
+		p.FillBytes(be[32*i : 32*i+32])
+	}
+	return c.check(C.ibft_set_validator_sets_u256(c.h, C.size_t(ns), (*C.uint64_t)(unsafe.Pointer(&height[0])),
+		(*C.uint32_t)(unsafe.Pointer(&setOff[0])), ptr8(addrs20), ptr8(be)))
+}
+
+// ValidatorSetsInfo reports the installed family: its sets, the addresses of their union and the device bytes its tables hold.
+func (c *Ctx) ValidatorSetsInfo() (sets, unionSize uint32, deviceBytes uint64, err error) {
+	var ns, nu C.uint32_t
+	var nb C.uint64_t
+	err = c.check(C.ibft_validator_sets_info(c.h, &ns, &nu, &nb))
+	return uint32(ns), uint32(nu), uint64(nb), err
+}
+
+// VerifyBlockSealsSets = VerifyBlockSeals with a validator set PER BLOCK (ibft_verify_block_seals_sets): block b is judged
+// under set blockSet[b] of the family SetValidatorSets installed; tallies[b] carries that set's quorum.  Bit for bit what
+// SetValidators(set blockSet[b]) + VerifySeals over block b's rows returns, in one call and one verdict launch.
+func (c *Ctx) VerifyBlockSealsSets(blockHash32 []byte, sealOff, blockSet []uint32, sig65, signer20, preFlags []byte) ([]uint64, []Tally, error) {
+	if len(sealOff) == 0 {
+		return nil, nil, fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(blockHash32) < 32*nb || len(blockSet) < nb || len(sig65) < 65*n || len(signer20) < 20*n || (preFlags != nil && len(preFlags) < n) {
+		return nil, nil, fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	var bs *C.uint32_t
+	if nb > 0 {
+		bs = (*C.uint32_t)(unsafe.Pointer(&blockSet[0]))
+	}
+	mask := make([]uint64, (n+63)/64+1)
+	ct := make([]C.ibft_tally_t, nb+1)
+	rc := C.ibft_verify_block_seals_sets(c.h, ptr8(blockHash32), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), bs, C.size_t(nb),
+		ptr8(sig65), ptr8(signer20), ptr8(preFlags), (*C.uint64_t)(unsafe.Pointer(&mask[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err := c.check(rc); err != nil {
+		return nil, nil, err
+	}
+	tallies := make([]Tally, nb)
+	for b := range tallies {
+		tallies[b] = tally(ct[b])
+	}
+	return mask, tallies, nil
+}
+
+// RecoverBlockSealsSets = RecoverBlockSeals with a validator set per block (ibft_recover_block_seals_sets): vidx[i] is the
+// index of row i's signer in ITS block's set (-1: no member of that set; the address is delivered all the same).
+func (c *Ctx) RecoverBlockSealsSets(blockHash32 []byte, sealOff, blockSet []uint32, sig65, preFlags []byte) (signer20 []byte, vidx []int32, mask []uint64, tallies []Tally, err error) {
+	if len(sealOff) == 0 {
+		return nil, nil, nil, nil, fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(blockHash32) < 32*nb || len(blockSet) < nb || len(sig65) < 65*n || (preFlags != nil && len(preFlags) < n) {
+		return nil, nil, nil, nil, fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	var bs *C.uint32_t
+	if nb > 0 {
+		bs = (*C.uint32_t)(unsafe.Pointer(&blockSet[0]))
+	}
+	signer20 = make([]byte, 20*n+20)
+	vidx = make([]int32, n+1)
+	mask = make([]uint64, (n+63)/64+1)
+	ct := make([]C.ibft_tally_t, nb+1)
+	rc := C.ibft_recover_block_seals_sets(c.h, ptr8(blockHash32), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), bs, C.size_t(nb),
 		ptr8(sig65), ptr8(preFlags), ptr8(signer20), (*C.int32_t)(unsafe.Pointer(&vidx[0])),
 		(*C.uint64_t)(unsafe.Pointer(&mask[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
 	if err := c.check(rc); err != nil {
