@@ -209,5 +209,18 @@ def build_block_sets_harness(force: bool = False) -> str:
     return BLOCK_SETS_HARNESS
 
 
+BLOCK_HEAD_HARNESS = os.path.join(CSRC, "libdev_block_head_host.so")
+
+
+def build_block_head_harness(force: bool = False) -> str:
+    """TEST-ONLY: the per-row body of block_head_kernel (recover_dev.h: block_of_row, block_head_row) on the CPU."""
+    deps = ["host_block_head_harness.hip", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
+    if force or _stale(BLOCK_HEAD_HARNESS, deps):
+        subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
+                               "-o", BLOCK_HEAD_HARNESS, os.path.join(CSRC, "host_block_head_harness.hip")], cwd=CSRC)
+        _mark(BLOCK_HEAD_HARNESS, deps)
+    return BLOCK_HEAD_HARNESS
+
+
 if __name__ == "__main__":
     print(build_lib(verbose=True))

@@ -187,6 +187,24 @@ struct ibft_ctx {
   hipEvent_t ev_bs[2] = {nullptr, nullptr};
   uint32_t bs_issued = 0, bs_collected = 0, bs_rows[2] = {0, 0}, bs_blocks[2] = {0, 0};
   uint64_t bs_quorum[2][2] = {{0, 0}, {0, 0}};  // the quorum a batch was judged under (the set current at its submit)
+  // The streamed submits that take proposals or bare seals (ibft_block_seals_submit_raw, ibft_recover_block_seals_submit[_raw];
+  // bs_kind: IBFT_BATCH_* of the batch in each slot, 0 for a batch of ibft_block_seals_submit).  What such a batch reads and
+  // delivers beyond verdict words and records is PRIVATE to its slot, so the kernels of batch k + 1 never write what batch k
+  // still has to deliver: the proposals as given (bytes with 256 of slack, offsets, rounds: two slots double the device bytes
+  // proposals take, each slot bounded by IBFT_PROPOSAL_BYTES_MAX), the blocks' digests (computed, or the uploaded hashes of a
+  // bare batch) that block_head_kernel reads and never writes, and for a recover batch the columns the emitting kernels fill —
+  // swapped in for d_signer_out / d_vidx while the batch's kernels are enqueued.  Digests, signers and indices come back on
+  // ostream — NOT the copy stream, whose next command is the upload of batch k + 1 and must not wait for batch k's tally —
+  // behind ev_bs_dig (the digests exist) and ev_bs (the tally is done) into page-locked buffers; ev_bs_out is behind the last copy.
+  DevBuf bs_praw[2], bs_proff[2], bs_pround[2], bs_phash[2], bs_signer[2], bs_vidx[2];
+  uint8_t *bs_h_hash[2] = {nullptr, nullptr}, *bs_h_signer[2] = {nullptr, nullptr};
+  int32_t *bs_h_vidx[2] = {nullptr, nullptr};
+  size_t bs_h_hash_blocks[2] = {0, 0}, bs_h_rows[2] = {0, 0}, bs_h_vidx_rows[2] = {0, 0};
+  uint32_t bs_kind[2] = {0, 0};
+  bool bs_has_out[2] = {false, false};  // the batch put copies on ostream: its collect waits for ev_bs_out too
+  hipStream_t ostream = nullptr;
+  hipEvent_t ev_bs_dig[2] = {nullptr, nullptr}, ev_bs_out[2] = {nullptr, nullptr};
+  bool stream_digest_copy = false;  // IBFT_STREAM_DIGEST=copy|main: the stream proposal_digest_kernel of a streamed batch runs on
   // Chain sync from the proposals (ibft_proposal_hashes, the _raw block calls): the caller's proposals as they are — bytes,
   // offsets, rounds — in buffers of their own (grown on demand and kept, like d_payload; the bytes carry 256 of slack), the n
   // digests proposal_digest_kernel writes (what block_rows_kernel then reads in place of an uploaded d_bhash), and the pinned
@@ -1546,6 +1564,7 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
     const int g = atoi(e);
     if (g == 1 || g == 64) c->proposal_lanes_force = (uint32_t)g;
   }
+  if (const char *e = getenv("IBFT_STREAM_DIGEST")) c->stream_digest_copy = strcmp(e, "copy") == 0;
   if (const char *e = getenv("IBFT_PROPOSAL_LANE_ROWS")) c->proposal_lane_rows = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_PROPOSAL_BYTES_MAX"))  // (offsets are 32-bit; room is kept for the round and the slack)
     c->proposal_bytes_max = std::min<uint64_t>(strtoull(e, nullptr, 10), 0xFFFFFE00ull);
@@ -1621,6 +1640,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
   if (c->hstream) (void)hipStreamSynchronize(c->hstream);
   if (c->tstream) (void)hipStreamSynchronize(c->tstream);
   if (c->cstream) (void)hipStreamSynchronize(c->cstream);  // block batches in flight are drained, never delivered
+  if (c->ostream) (void)hipStreamSynchronize(c->ostream);  // … their digests and emitted columns on the way out too
   for (DevBuf *b : {&c->d_hash, &c->d_sig, &c->d_signer, &c->d_signer_out, &c->d_pre, &c->d_hash_len, &c->d_payload,
                     &c->d_off, &c->d_raw, &c->d_mask, &c->d_mask_out, &c->d_vidx, &c->d_tally, &c->d_H,
                     &c->d_vtab, &c->d_vpower, &c->d_vslot,
@@ -1630,7 +1650,8 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_cert_slot, &c->d_cert_tiles, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
                     &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally,
                     &c->d_bhash_nx, &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
-                    &c->d_phash, &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
+                    &c->d_phash, &c->bs_praw[0], &c->bs_praw[1], &c->bs_proff[0], &c->bs_proff[1], &c->bs_pround[0], &c->bs_pround[1],
+                    &c->bs_phash[0], &c->bs_phash[1], &c->bs_signer[0], &c->bs_signer[1], &c->bs_vidx[0], &c->bs_vidx[1], &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
                     &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset})
     release(*b);
   if (c->h_phash) (void)hipHostFree(c->h_phash);
@@ -1676,7 +1697,13 @@ void ibft_ctx_destroy(ibft_ctx *c) {
   for (int i = 0; i < 2; i++) {
     if (c->bs_tally[i]) (void)hipHostFree(c->bs_tally[i]);
     if (c->ev_bs[i]) (void)hipEventDestroy(c->ev_bs[i]);
+    if (c->bs_h_hash[i]) (void)hipHostFree(c->bs_h_hash[i]);
+    if (c->bs_h_signer[i]) (void)hipHostFree(c->bs_h_signer[i]);
+    if (c->bs_h_vidx[i]) (void)hipHostFree(c->bs_h_vidx[i]);
+    if (c->ev_bs_dig[i]) (void)hipEventDestroy(c->ev_bs_dig[i]);
+    if (c->ev_bs_out[i]) (void)hipEventDestroy(c->ev_bs_out[i]);
   }
+  if (c->ostream) (void)hipStreamDestroy(c->ostream);
   if (c->h_tally) (void)hipHostFree(c->h_tally);
   if (c->h_digest) (void)hipHostFree(c->h_digest);
   if (c->h_set) (void)hipHostFree(c->h_set);
@@ -2840,6 +2867,7 @@ int ibft_sync(ibft_ctx *c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->xstream) HIPCHK(c, hipStreamSynchronize(c->xstream));  // exchanges in flight (ibft_seals_exchange)
   if (c->cstream) HIPCHK(c, hipStreamSynchronize(c->cstream));  // a batch on its way into the spare slot (ibft_seals_stage_next)
+  if (c->ostream) HIPCHK(c, hipStreamSynchronize(c->ostream));  // digests / emitted columns of streamed block batches on their way out
   return IBFT_OK;
 }
 
@@ -3026,18 +3054,25 @@ static int stage_proposals(ibft_ctx *c, ColumnCopies &cc, const proposal_batch &
   cc.add(c->d_pround.p, p.round, n * 8);
   return IBFT_OK;
 }
-static int enqueue_proposal_digests(ibft_ctx *c, const proposal_batch &p, size_t n) {
+// (the launch itself, over any set of proposal buffers and on any stream: the streamed submits have a set per slot)
+static int launch_proposal_digests(ibft_ctx *c, uint32_t form, const void *d_raw, const void *d_off, const void *d_round, void *d_out,
+                                   size_t n, hipStream_t stream) {
   ibftk::proposal_digest_args a{};
-  a.raw = (const uint8_t *)c->d_praw.p;
-  a.raw_off = (const uint32_t *)c->d_proff.p;
-  a.round = (const uint64_t *)c->d_pround.p;
-  a.out32 = (uint8_t *)c->d_phash.p;
+  a.raw = (const uint8_t *)d_raw;
+  a.raw_off = (const uint32_t *)d_off;
+  a.round = (const uint64_t *)d_round;
+  a.out32 = (uint8_t *)d_out;
   a.n = (uint32_t)n;
-  if (proposal_form(c, p, n) == 1)
-    hipLaunchKernelGGL(ibftk::proposal_digest_kernel<1>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, a);
+  if (form == 1)
+    hipLaunchKernelGGL(ibftk::proposal_digest_kernel<1>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, a);
   else
-    hipLaunchKernelGGL(ibftk::proposal_digest_kernel<64>, dim3((unsigned)n), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(ibftk::proposal_digest_kernel<64>, dim3((unsigned)n), dim3(64), 0, stream, a);
   HIPCHK(c, hipGetLastError());
+  return IBFT_OK;
+}
+static int enqueue_proposal_digests(ibft_ctx *c, const proposal_batch &p, size_t n) {
+  int rc;
+  if ((rc = launch_proposal_digests(c, proposal_form(c, p, n), c->d_praw.p, c->d_proff.p, c->d_pround.p, c->d_phash.p, n, c->stream))) return rc;
   if (p.out_hash32) HIPCHK(c, hipMemcpyAsync(c->h_phash, c->d_phash.p, n * 32, hipMemcpyDeviceToHost, c->stream));
   return IBFT_OK;
 }
@@ -3222,6 +3257,45 @@ int ibft_recover_block_seals_sets(ibft_ctx *c, const uint8_t *block_hash32, cons
                           true, block_set);
 }
 
+// The refusals every streamed block submit makes once its arguments are in order (c->mu held); a refused call takes no slot.
+static int block_pipeline_refusal(ibft_ctx *c) {
+  if (c->pass_issued != c->pass_collected || c->next_valid) {  // the two pipelines share the result slots and the spare columns
+    c->last_error = c->next_valid ? "a batch staged by ibft_seals_stage_next awaits its ibft_seals_swap"
+                                  : "seal passes in flight: call ibft_seals_collect first";
+    return IBFT_E_INVAL;
+  }
+  if (c->bs_issued - c->bs_collected >= 2) {
+    c->last_error = "two block batches already in flight: call ibft_block_seals_collect first";
+    return IBFT_E_INVAL;
+  }
+  if (c->learn_rc != IBFT_OK) {  // the table build behind an already delivered batch failed (ibft_block_seals_collect): say so once
+    const int rc = c->learn_rc;
+    c->learn_rc = IBFT_OK;
+    return rc;
+  }
+  return IBFT_OK;
+}
+// The per-block records of slot s, for nb blocks (mapped where the device can write them, through bs_dtally[s] otherwise).
+static int ensure_block_records(ibft_ctx *c, uint32_t s, uint32_t nb) {
+  int rc;
+    // the records of slot s: the batch that used them last (k − 2) has been collected, nothing writes them now
+    if (nb > c->bs_tally_blocks[s]) {
+      if (c->bs_tally[s]) (void)hipHostFree(c->bs_tally[s]);
+      c->bs_tally[s] = c->bs_dtally_map[s] = nullptr;
+      c->bs_tally_blocks[s] = 0;
+      const size_t want = std::max<size_t>(nb, 256);
+      if (hipHostMalloc((void **)&c->bs_tally[s], want * 32) != hipSuccess) {
+        c->bs_tally[s] = nullptr;
+        return IBFT_E_NOMEM;
+      }
+      c->bs_tally_blocks[s] = want;
+      void *d = nullptr;  // (IBFT_NO_HOST_DIRECT: records and verdict words through device buffers and copies behind the tally)
+      if (c->dh_mask && hipHostGetDevicePointer(&d, c->bs_tally[s], 0) == hipSuccess) c->bs_dtally_map[s] = (uint64_t *)d;
+    }
+    if (!c->bs_dtally_map[s] && (rc = ensure(c, c->bs_dtally[s], (size_t)nb * 32))) return rc;
+  return IBFT_OK;
+}
+
 // Streamed chain sync: the same batch as ibft_verify_block_seals, enqueued and not waited for.  Up to two batches in flight;
 // the copy of batch k + 1 (copy stream, into the spare column set) runs under the kernels of batch k (main stream).
 int ibft_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
@@ -3238,20 +3312,7 @@ int ibft_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint
   if (n && (!block_hash32 || !sig65 || !signer20)) return IBFT_E_INVAL;
   std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself; side-stream tallies are joined below)
   if (!c->have_valset) return IBFT_E_NOVALSET;
-  if (c->pass_issued != c->pass_collected || c->next_valid) {  // the two pipelines share the result slots and the spare columns
-    c->last_error = c->next_valid ? "a batch staged by ibft_seals_stage_next awaits its ibft_seals_swap"
-                                  : "seal passes in flight: call ibft_seals_collect first";
-    return IBFT_E_INVAL;
-  }
-  if (c->bs_issued - c->bs_collected >= 2) {
-    c->last_error = "two block batches already in flight: call ibft_block_seals_collect first";
-    return IBFT_E_INVAL;
-  }
-  if (c->learn_rc != IBFT_OK) {  // the table build behind an already delivered batch failed (ibft_block_seals_collect): say so once
-    const int rc = c->learn_rc;
-    c->learn_rc = IBFT_OK;
-    return rc;
-  }
+  if (int rf = block_pipeline_refusal(c)) return rf;
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   if ((rc = join_side(c))) return rc;  // tallies of collected seal passes may still be on the side stream
@@ -3263,21 +3324,7 @@ int ibft_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint
     // (hipFree waits for the device: a buffer that grows here is read by nothing any more)
     if ((rc = ensure(c, c->d_boff_nx, ((size_t)nb + 1) * 4))) return rc;
     if ((rc = ensure(c, c->d_bhash_nx, (size_t)nb * 32))) return rc;
-    // the records of slot s: the batch that used them last (k − 2) has been collected, nothing writes them now
-    if (nb > c->bs_tally_blocks[s]) {
-      if (c->bs_tally[s]) (void)hipHostFree(c->bs_tally[s]);
-      c->bs_tally[s] = c->bs_dtally_map[s] = nullptr;
-      c->bs_tally_blocks[s] = 0;
-      const size_t want = std::max<size_t>(nb, 256);
-      if (hipHostMalloc((void **)&c->bs_tally[s], want * 32) != hipSuccess) {
-        c->bs_tally[s] = nullptr;
-        return IBFT_E_NOMEM;
-      }
-      c->bs_tally_blocks[s] = want;
-      void *d = nullptr;  // (IBFT_NO_HOST_DIRECT: records and verdict words through device buffers and copies behind the tally)
-      if (c->dh_mask && hipHostGetDevicePointer(&d, c->bs_tally[s], 0) == hipSuccess) c->bs_dtally_map[s] = (uint64_t *)d;
-    }
-    if (!c->bs_dtally_map[s] && (rc = ensure(c, c->bs_dtally[s], (size_t)nb * 32))) return rc;
+    if ((rc = ensure_block_records(c, s, nb))) return rc;
     // The spare set was the resident one until the previous swap: batch k − 2's kernels — its tally reads the offsets — may
     // still be at it.  ev_cols_read was recorded behind them.
     HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_cols_read, 0));
@@ -3326,21 +3373,235 @@ int ibft_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint
   c->bs_blocks[s] = nb;
   c->bs_quorum[s][0] = c->quorum_w[0];
   c->bs_quorum[s][1] = c->quorum_w[1];
+  c->bs_kind[s] = 0;
+  c->bs_has_out[s] = false;
   c->bs_issued++;
   return IBFT_OK;
 }
 
-int ibft_block_seals_collect(ibft_ctx *c, uint64_t *out_mask, ibft_tally_t *out_tally) {
+// ---- streamed chain sync from proposals and from bare seals ---------------------------------------------------------------
+// ibft_block_seals_submit_raw, ibft_recover_block_seals_submit, ibft_recover_block_seals_submit_raw: the batches of
+// ibft_verify_block_seals_raw, ibft_recover_block_seals and ibft_recover_block_seals_raw, enqueued and not waited for, in the two
+// slots of ibft_block_seals_submit.  Checks: the synchronous sibling's, in its order, minus the out buffers; then the
+// pipeline's refusals.  What differs from ibft_block_seals_submit: the blocks' digests (bs_phash[s]) are private to the slot
+// and only read — block_head_kernel applies the seal-digest convention while it spreads them over the rows —, a recover batch
+// emits into columns of its slot, and digests / signers / indices leave on ostream (see the context's fields).
+static int grow_pinned(void **p, size_t *cap, size_t want, size_t elem) {
+  if (want <= *cap) return IBFT_OK;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t n = std::max<size_t>(want, 256);
+  if (hipHostMalloc(p, n * elem) != hipSuccess) {
+    *p = nullptr;
+    return IBFT_E_NOMEM;
+  }
+  *cap = n;
+  return IBFT_OK;
+}
+// d_signer_out / d_vidx ↔ the emit columns of slot s while a recover batch's kernels are enqueued (make_args and the tally
+// read the context's fields); put back on every way out
+struct emit_columns_view {
+  ibft_ctx *c;
+  uint32_t s;
+  bool on;
+  void exchange() {
+    std::swap(c->d_signer_out, c->bs_signer[s]);
+    std::swap(c->d_vidx, c->bs_vidx[s]);
+  }
+  emit_columns_view(ibft_ctx *cc, uint32_t ss, bool on_) : c(cc), s(ss), on(on_) {
+    if (on) exchange();
+  }
+  ~emit_columns_view() {
+    if (on) exchange();
+  }
+  emit_columns_view(const emit_columns_view &) = delete;
+  emit_columns_view &operator=(const emit_columns_view &) = delete;
+};
+static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off,
+                                   size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare) {
+  if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
+  if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;
+  uint32_t widest = 0;
+  for (size_t b = 0; b < n_blocks; b++) {
+    if (seal_off[b + 1] < seal_off[b]) return IBFT_E_INVAL;
+    widest = std::max(widest, seal_off[b + 1] - seal_off[b]);
+  }
+  const size_t n = seal_off[n_blocks];
+  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  if (n && ((!props && !block_hash32) || !sig65 || (!bare && !signer20))) return IBFT_E_INVAL;
+  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself; side-stream tallies are joined below)
+  if (!c->have_valset) return IBFT_E_NOVALSET;
+  int rc;
+  if (props && (rc = check_proposals(c, *props, n_blocks))) return rc;
+  if ((rc = block_pipeline_refusal(c))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = join_side(c))) return rc;
+  const uint32_t s = c->bs_issued & 1u, nb = (uint32_t)n_blocks, nr = (uint32_t)n;
+  const uint32_t kind = (bare ? IBFT_BATCH_RECOVER : 0u) | (props ? IBFT_BATCH_RAW : 0u);
+  // submitted raw: the proposals are hashed whether or not rows wait for the hashes — the collect may ask for them
+  const bool hash_here = props && nb;
+  bool has_out = false;
+  if (!c->ev_bs[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bs[s], hipEventDisableTiming));
+  if (!c->ev_bs_dig[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bs_dig[s], hipEventDisableTiming));
+  if (!c->ev_bs_out[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bs_out[s], hipEventDisableTiming));
+  if (!c->ostream) HIPCHK(c, hipStreamCreateWithFlags(&c->ostream, hipStreamNonBlocking));
+  if (nr || hash_here) {
+    if ((rc = ensure_result_slots(c))) return rc;
+    if ((rc = ensure_spare_columns(c))) return rc;
+    // Everything of slot s: the batch that used it last (k − 2) has been collected — its kernels and its copies out are done
+    // (hipFree waits for the device besides: a buffer that grows here is read by nothing any more).
+    if ((rc = ensure(c, c->bs_phash[s], (size_t)nb * 32))) return rc;
+    const size_t raw_bytes = hash_here ? props->raw_off[nb] : 0;
+    if (hash_here) {
+      if ((rc = ensure(c, c->bs_praw[s], raw_bytes + 256))) return rc;
+      if ((rc = ensure(c, c->bs_proff[s], ((size_t)nb + 1) * 4))) return rc;
+      if ((rc = ensure(c, c->bs_pround[s], (size_t)nb * 8))) return rc;
+      if ((rc = grow_pinned((void **)&c->bs_h_hash[s], &c->bs_h_hash_blocks[s], nb, 32))) return rc;
+    }
+    if (nr) {
+      if ((rc = ensure(c, c->d_boff_nx, ((size_t)nb + 1) * 4))) return rc;
+      if ((rc = ensure_block_records(c, s, nb))) return rc;
+      if (bare) {
+        const size_t m = std::max<size_t>(c->max_rows, c->row_cap);  // (the sizes alloc_rows gives d_signer_out / d_vidx)
+        if ((rc = ensure(c, c->bs_signer[s], m * 20))) return rc;
+        if ((rc = ensure(c, c->bs_vidx[s], m * 4))) return rc;
+        if ((rc = grow_pinned((void **)&c->bs_h_signer[s], &c->bs_h_rows[s], nr, 20))) return rc;
+        if ((rc = grow_pinned((void **)&c->bs_h_vidx[s], &c->bs_h_vidx_rows[s], nr, 4))) return rc;
+      }
+    }
+    // ---- the copy stream: proposals (and, where told to, their digests), then the seal columns into the spare set
+    if (hash_here) {
+      if (raw_bytes) HIPCHK(c, hipMemcpyAsync(c->bs_praw[s].p, props->raw, raw_bytes, hipMemcpyHostToDevice, c->cstream));
+      HIPCHK(c, hipMemcpyAsync(c->bs_proff[s].p, props->raw_off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, c->cstream));
+      HIPCHK(c, hipMemcpyAsync(c->bs_pround[s].p, props->round, (size_t)nb * 8, hipMemcpyHostToDevice, c->cstream));
+    } else if (!props) {
+      HIPCHK(c, hipMemcpyAsync(c->bs_phash[s].p, block_hash32, (size_t)nb * 32, hipMemcpyHostToDevice, c->cstream));
+    }
+    const uint32_t form = hash_here ? proposal_form(c, *props, nb) : 0u;  // (the form is chosen here: pinned at the submit)
+    if (hash_here && c->stream_digest_copy) {
+      // behind the copy of its bytes, next to whatever the main stream runs: batch k's verdict kernel in a loop that keeps one in flight
+      if ((rc = launch_proposal_digests(c, form, c->bs_praw[s].p, c->bs_proff[s].p, c->bs_pround[s].p, c->bs_phash[s].p, nb, c->cstream)))
+        return rc;
+      HIPCHK(c, hipEventRecord(c->ev_bs_dig[s], c->cstream));
+    }
+    if (nr) {
+      // The spare set was the resident one until the previous swap: kernels enqueued before it — a tally reads the offsets —
+      // may still be at it.  ev_cols_read was recorded behind them.
+      HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_cols_read, 0));
+      HIPCHK(c, hipMemcpyAsync(c->d_boff_nx.p, seal_off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, c->cstream));
+      HIPCHK(c, hipMemcpyAsync(c->d_sig_nx.p, sig65, n * 65, hipMemcpyHostToDevice, c->cstream));
+      if (!bare) HIPCHK(c, hipMemcpyAsync(c->d_signer_nx.p, signer20, n * 20, hipMemcpyHostToDevice, c->cstream));
+      if (pre_flags) HIPCHK(c, hipMemcpyAsync(c->d_pre_nx.p, pre_flags, n, hipMemcpyHostToDevice, c->cstream));
+    }
+    HIPCHK(c, hipEventRecord(c->ev_staged, c->cstream));
+    if (nr) HIPCHK(c, hipEventRecord(c->ev_cols_read, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_staged, 0));
+    // from here on a failure leaves commands of this batch on the streams: nothing of it is delivered, the slot stays free
+    if (hash_here && !c->stream_digest_copy) {
+      if ((rc = launch_proposal_digests(c, form, c->bs_praw[s].p, c->bs_proff[s].p, c->bs_pround[s].p, c->bs_phash[s].p, nb, c->stream)))
+        return rc;
+      HIPCHK(c, hipEventRecord(c->ev_bs_dig[s], c->stream));
+    }
+    if (hash_here) {  // the digests go out as computed, next to everything that follows on the main stream
+      HIPCHK(c, hipStreamWaitEvent(c->ostream, c->ev_bs_dig[s], 0));
+      HIPCHK(c, hipMemcpyAsync(c->bs_h_hash[s], c->bs_phash[s].p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->ostream));
+      has_out = true;
+    }
+    if (nr) {
+      std::swap(c->d_sig, c->d_sig_nx);
+      std::swap(c->d_signer, c->d_signer_nx);
+      std::swap(c->d_pre, c->d_pre_nx);
+      std::swap(c->d_boff, c->d_boff_nx);
+      c->wire_valid = false;
+      // verify kind: the rows are the resident batch from here on; bare rows are none (as after the synchronous siblings)
+      c->staged_n = bare ? 0 : nr;
+      c->staged_pre = pre_flags != nullptr;
+      ibftk::block_head_args h{};
+      h.digest_words = (const uint64_t *)c->bs_phash[s].p;
+      h.off = (const uint32_t *)c->d_boff.p;
+      h.hash32 = (uint8_t *)c->d_hash.p;
+      h.n_blocks = nb;
+      h.n = nr;
+      h.convert = c->seal_digest_mode != 0 ? 1u : 0u;
+      memcpy(h.suffix_words, c->seal_suffix_words, sizeof h.suffix_words);
+      hipLaunchKernelGGL(ibftk::block_head_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, h);
+      HIPCHK(c, hipGetLastError());
+      if (c->ev_used >= 4096) c->ev_used = 0;
+      const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
+      const bool direct = c->bs_dtally_map[s] != nullptr;
+      {
+        emit_columns_view ev(c, s, bare);
+        if ((rc = enqueue_recover(c, nr, pre_flags != nullptr, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
+        if ((rc = enqueue_block_tally(c, nb, nr, widest, direct ? c->dp_mask[s] : nullptr,
+                                      direct ? c->bs_dtally_map[s] : (uint64_t *)c->bs_dtally[s].p)))
+          return rc;
+      }
+      c->host_direct = false;
+      if (!direct) {
+        HIPCHK(c, hipMemcpyAsync(c->p_mask[s], c->d_mask_out.p, (size_t)mask_words(nr) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->bs_tally[s], c->bs_dtally[s].p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->stream));
+      }
+      if (c->cache_on) HIPCHK(c, hipMemcpyAsync(c->p_tally[s] + 4, c->dev->d_learned.p, 8, hipMemcpyDeviceToHost, c->stream));
+    }
+  }
+  HIPCHK(c, hipEventRecord(c->ev_bs[s], c->stream));
+  if (bare && nr) {  // signers and indices: behind the tally, off the main stream — the next batch's kernels do not wait for 24 B per row
+    HIPCHK(c, hipStreamWaitEvent(c->ostream, c->ev_bs[s], 0));
+    HIPCHK(c, hipMemcpyAsync(c->bs_h_signer[s], c->bs_signer[s].p, n * 20, hipMemcpyDeviceToHost, c->ostream));
+    HIPCHK(c, hipMemcpyAsync(c->bs_h_vidx[s], c->bs_vidx[s].p, n * 4, hipMemcpyDeviceToHost, c->ostream));
+    has_out = true;
+  }
+  if (has_out) HIPCHK(c, hipEventRecord(c->ev_bs_out[s], c->ostream));
+  c->bs_rows[s] = nr;
+  c->bs_blocks[s] = nb;
+  c->bs_quorum[s][0] = c->quorum_w[0];
+  c->bs_quorum[s][1] = c->quorum_w[1];
+  c->bs_kind[s] = kind;
+  c->bs_has_out[s] = has_out;
+  c->bs_issued++;
+  return IBFT_OK;
+}
+int ibft_block_seals_submit_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round, const uint32_t *seal_off,
+                                size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags) {
+  proposal_batch p{raw, raw_off, round, nullptr};
+  return block_seals_submit_impl(c, nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, false);
+}
+int ibft_recover_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                                    const uint8_t *sig65, const uint8_t *pre_flags) {
+  return block_seals_submit_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, true);
+}
+int ibft_recover_block_seals_submit_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                        const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags) {
+  proposal_batch p{raw, raw_off, round, nullptr};
+  return block_seals_submit_impl(c, nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, true);
+}
+
+// The oldest batch in flight → the caller.  ex: ibft_block_seals_collect_ex (digests, signers and indices where the batch's
+// kind carries them); the old call delivers verdict words and records only and refuses a recover batch with rows.
+static int block_seals_collect_impl(ibft_ctx *c, bool ex, uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx,
+                                    uint64_t *out_mask, ibft_tally_t *out_tally) {
   if (!c) return IBFT_E_INVAL;
   std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself)
   if (c->bs_collected == c->bs_issued) {
-    c->last_error = "ibft_block_seals_collect without a submitted batch";
+    c->last_error = ex ? "ibft_block_seals_collect_ex without a submitted batch" : "ibft_block_seals_collect without a submitted batch";
     return IBFT_E_INVAL;
   }
-  const uint32_t s = c->bs_collected & 1u, nr = c->bs_rows[s], nb = c->bs_blocks[s];
+  const uint32_t s = c->bs_collected & 1u, nr = c->bs_rows[s], nb = c->bs_blocks[s], kind = c->bs_kind[s];
   if (nr && !out_mask) return IBFT_E_INVAL;
+  if ((kind & IBFT_BATCH_RECOVER) && nr) {  // refused before anything is written: the batch stays in flight
+    if (!ex) {
+      c->last_error = "the oldest batch recovers signers: collect it with ibft_block_seals_collect_ex";
+      return IBFT_E_INVAL;
+    }
+    if (!out_signer20) {
+      c->last_error = "ibft_block_seals_collect_ex: a recover batch with rows needs out_signer20";
+      return IBFT_E_INVAL;
+    }
+  }
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventSynchronize(c->ev_bs[s]));
+  if (c->bs_has_out[s]) HIPCHK(c, hipEventSynchronize(c->ev_bs_out[s]));
   if (nr) {
     const size_t mw = (size_t)mask_words(nr);
     memcpy(out_mask, c->p_mask[s], mw * 8);
@@ -3360,6 +3621,11 @@ int ibft_block_seals_collect(ibft_ctx *c, uint64_t *out_mask, ibft_tally_t *out_
       t.distinct_senders = (uint32_t)(r[2] >> 32);
       t.has_quorum = (uint32_t)r[3];
     }
+  if (ex && (kind & IBFT_BATCH_RAW) && out_block_hash32 && nb) memcpy(out_block_hash32, c->bs_h_hash[s], (size_t)nb * 32);
+  if (ex && (kind & IBFT_BATCH_RECOVER) && nr) {
+    memcpy(out_signer20, c->bs_h_signer[s], (size_t)nr * 20);
+    if (out_vidx) memcpy(out_vidx, c->bs_h_vidx[s], (size_t)nr * 4);
+  }
   // The batch is DELIVERED before anything else can fail (the rule of ibft_seals_collect).
   c->bs_collected++;
   if (c->cache_on && nr) {  // keys this batch taught the device → tables (build_new_tables drains the main stream when there
@@ -3370,16 +3636,28 @@ int ibft_block_seals_collect(ibft_ctx *c, uint64_t *out_mask, ibft_tally_t *out_
   }
   return IBFT_OK;
 }
+int ibft_block_seals_collect(ibft_ctx *c, uint64_t *out_mask, ibft_tally_t *out_tally) {
+  return block_seals_collect_impl(c, false, nullptr, nullptr, nullptr, out_mask, out_tally);
+}
+int ibft_block_seals_collect_ex(ibft_ctx *c, uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask,
+                                ibft_tally_t *out_tally) {
+  return block_seals_collect_impl(c, true, out_block_hash32, out_signer20, out_vidx, out_mask, out_tally);
+}
 
-// Batches in flight, rows and blocks of the oldest (0 when none): a binding sizes its verdict and tally buffers from these.
-int ibft_block_seals_pending(ibft_ctx *c, uint32_t *batches_in_flight, uint32_t *oldest_rows, uint32_t *oldest_blocks) {
+// Batches in flight, rows, blocks and kind of the oldest (0 when none): a binding sizes its buffers from these.
+int ibft_block_seals_pending_ex(ibft_ctx *c, uint32_t *batches_in_flight, uint32_t *oldest_rows, uint32_t *oldest_blocks,
+                                uint32_t *oldest_kind) {
   if (!c) return IBFT_E_INVAL;
   std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself)
   const bool any = c->bs_collected != c->bs_issued;
   if (batches_in_flight) *batches_in_flight = c->bs_issued - c->bs_collected;
   if (oldest_rows) *oldest_rows = any ? c->bs_rows[c->bs_collected & 1u] : 0u;
   if (oldest_blocks) *oldest_blocks = any ? c->bs_blocks[c->bs_collected & 1u] : 0u;
+  if (oldest_kind) *oldest_kind = any ? c->bs_kind[c->bs_collected & 1u] : 0u;
   return IBFT_OK;
+}
+int ibft_block_seals_pending(ibft_ctx *c, uint32_t *batches_in_flight, uint32_t *oldest_rows, uint32_t *oldest_blocks) {
+  return ibft_block_seals_pending_ex(c, batches_in_flight, oldest_rows, oldest_blocks, nullptr);
 }
 
 // a3 up to and including the tally (c->mu held)

@@ -18,6 +18,7 @@
 //   tally_kernel                a8  HasQuorum             (core/validator_manager.go:77-96)
 //   block_rows_kernel, block_tally_kernel   chain sync: each block's hash → its rows, one HasQuorum per block
 //   block_tally_sets_kernel         … one HasQuorum per block under the block's OWN validator set (a family of sets)
+//   block_head_kernel               streamed chain sync from proposals / bare seals: digests → rows, seal-digest convention fused
 //   gtab_build_kernel, qtab_build_kernel, qtab_commit_kernel   one-time fixed-base tables
 //   lookup_kernel                   sender → validator index for ibft_tally()
 //   wire_parse_kernel, wire_stage_seals_kernel   §8f rank 3: wire bytes → columns on the device (wire_dev.h)
@@ -2010,6 +2011,29 @@ __global__ void block_rows_kernel(const uint8_t *__restrict__ block_hash32, cons
   uint4 *d = reinterpret_cast<uint4 *>(hash32 + 32ull * row);
   d[0] = s[0];
   d[1] = s[1];
+}
+
+// The streamed submits that take proposals or bare seals (ibft_block_seals_submit_raw, ibft_recover_block_seals_submit[_raw]):
+// seal-digest convention and spreading over the rows in ONE launch, the blocks' digests left as they are.  The synchronous
+// path converts the digests in place (seal_digest_kernel) and then spreads them (block_rows_kernel); in the streamed form the
+// digests leave for the host on another stream while the main stream goes on, so nothing may write them — and one launch
+// less is one dependency gap less per batch.  One thread per row; under a non-identity convention every row hashes its
+// block's digest itself (one permutation: nothing next to an ECDSA recover).  The per-row body is recover_dev.h's
+// block_head_row, which tests/test_dev_block_head_host.py drives on the CPU.
+struct block_head_args {
+  const uint64_t *digest_words;  // n_blocks × 4: the blocks' digests (proposal_digest_kernel's, or uploaded hashes), read only
+  const uint32_t *off;           // n_blocks + 1 row offsets
+  uint8_t *hash32;               // n × 32: the hash column the verdict kernels read
+  uint32_t n_blocks, n, convert;
+  uint64_t suffix_words[9];
+};
+__global__ void __launch_bounds__(256) block_head_kernel(block_head_args a) {
+  const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= a.n) return;
+  const block_head_t h = block_head_row(a.digest_words, a.off, a.n_blocks, row, a.convert, a.suffix_words);
+  uint4 *d = reinterpret_cast<uint4 *>(a.hash32 + 32ull * row);
+  d[0] = make_uint4((uint32_t)h.w[0], (uint32_t)(h.w[0] >> 32), (uint32_t)h.w[1], (uint32_t)(h.w[1] >> 32));
+  d[1] = make_uint4((uint32_t)h.w[2], (uint32_t)(h.w[2] >> 32), (uint32_t)h.w[3], (uint32_t)(h.w[3] >> 32));
 }
 
 // Segmented HasQuorum: one verdict launch judged the rows of every block, this kernel answers HasQuorum per block against

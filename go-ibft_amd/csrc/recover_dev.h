@@ -80,6 +80,42 @@ __host__ __device__ __forceinline__ valsets_row_t valsets_row(bool bit, int unio
   return r;
 }
 
+// ---- streamed chain sync (block_head_kernel): the hash a row's seal signs, from the digests of the blocks ------------------
+// The block of a row: the LAST b with off[b] ≤ row (empty blocks repeat an offset; off[0] = 0 ≤ row < off[n_blocks]).
+__host__ __device__ __forceinline__ uint32_t block_of_row(const uint32_t *__restrict__ off, uint32_t n_blocks, uint32_t row) {
+  uint32_t lo = 0, hi = n_blocks - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= row) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+// What block_head_kernel writes for one row: its block's digest as it is (convert = 0, the identity convention) or
+// keccak256(digest ‖ suffix) — suffix_words is the suffix ‖ 0x01 ‖ 0… as little-endian words, bytes 32..103 of the one Keccak
+// block (ibft_set_seal_digest).  The digests are only READ: they may be on their way to the host while this runs.
+struct block_head_t {
+  uint64_t w[4];
+};
+__host__ __device__ __forceinline__ block_head_t block_head_row(const uint64_t *__restrict__ digest_words, const uint32_t *__restrict__ off,
+                                                                uint32_t n_blocks, uint32_t row, uint32_t convert,
+                                                                const uint64_t suffix_words[9]) {
+  const uint64_t *d = digest_words + 4ull * block_of_row(off, n_blocks, row);
+  block_head_t r;
+  if (!convert) {
+    for (int i = 0; i < 4; i++) r.w[i] = d[i];
+    return r;
+  }
+  uint64_t s[25];
+  for (int i = 0; i < 4; i++) s[i] = d[i];
+  for (int j = 0; j < 9; j++) s[4 + j] = suffix_words[j];
+  for (int i = 13; i < 25; i++) s[i] = 0;
+  s[16] ^= 0x8000000000000000ull;  // pad10*1: the last bit of the 136-byte rate
+  keccak::f1600(s);
+  for (int i = 0; i < 4; i++) r.w[i] = s[i];
+  return r;
+}
+
 // ---- emitting form of the cold kernels (ibft_recover_seals): what a row stores once the curve is done ----------------
 // rec: a key was recovered (r, s, v in range, a curve point, not the point at infinity) and `got` is its address; pre: the
 // caller's pre_flags ruled the row out.  The address goes out as recovered — a non-member's too —, twenty zero bytes where there

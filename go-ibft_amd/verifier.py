@@ -43,6 +43,8 @@ EXPORTS = [
     "ibft_seals_stage_next", "ibft_seals_swap", "ibft_last_cold_table", "ibft_seals_submit", "ibft_seals_collect",
     "ibft_comm_preload", "ibft_issue_probe", "ibft_seals_rows", "ibft_pipeline_stats", "ibft_verify_block_seals",
     "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
+    "ibft_block_seals_submit_raw", "ibft_recover_block_seals_submit", "ibft_recover_block_seals_submit_raw",
+    "ibft_block_seals_collect_ex", "ibft_block_seals_pending_ex",
     "ibft_recover_seals", "ibft_recover_block_seals",
     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
@@ -54,6 +56,8 @@ EXPORTS = [
 # older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
 EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
 OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
+                    "ibft_block_seals_submit_raw", "ibft_recover_block_seals_submit", "ibft_recover_block_seals_submit_raw",
+                    "ibft_block_seals_collect_ex", "ibft_block_seals_pending_ex",
                     "ibft_recover_seals", "ibft_recover_block_seals",
                     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
                     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
@@ -219,6 +223,16 @@ def load_library() -> C.CDLL:
         L.ibft_block_seals_collect.argtypes = [vp, vp, vp]
     if hasattr(L, "ibft_block_seals_pending"):
         L.ibft_block_seals_pending.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "ibft_block_seals_submit_raw"):
+        L.ibft_block_seals_submit_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    if hasattr(L, "ibft_recover_block_seals_submit"):
+        L.ibft_recover_block_seals_submit.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "ibft_recover_block_seals_submit_raw"):
+        L.ibft_recover_block_seals_submit_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "ibft_block_seals_collect_ex"):
+        L.ibft_block_seals_collect_ex.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_block_seals_pending_ex"):
+        L.ibft_block_seals_pending_ex.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4
     L.ibft_verify_senders_wire.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.POINTER(Tally)]
     L.ibft_wire_stage_seals.argtypes = [vp]
     L.ibft_verify_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, vp, vp]
@@ -722,6 +736,100 @@ class BatchVerifier:
         a, b, c = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         self._chk(self._L.ibft_block_seals_pending(self._h, C.byref(a), C.byref(b), C.byref(c)), "ibft_block_seals_pending")
         return int(a.value), int(b.value), int(c.value)
+
+    # … from the proposals and from bare seals: the same two slots, collected with block_seals_collect_ex
+    BATCH_RECOVER, BATCH_RAW = 1, 2
+
+    def block_seals_submit_raw(self, raws, rounds, seal_off, sig65, signer20, pre_flags=None) -> int:
+        """ibft_block_seals_submit_raw: the batch of verify_block_seals_raw, enqueued and not waited for → its row count.
+        The arrays (the proposal bytes included) are kept alive here until the batch is collected."""
+        self._need("ibft_block_seals_submit_raw")
+        raw, roff, rnd = proposal_columns(raws, rounds)
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
+        n = len(s)
+        if len(rnd) != nb or len(f) != n or int(off[-1]) != n:
+            raise ValueError("one proposal per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        self._chk(self._L.ibft_block_seals_submit_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(f), _p(pre)),
+                  "ibft_block_seals_submit_raw")
+        self._block_cols = getattr(self, "_block_cols", []) + [(raw, roff, rnd, off, s, f, pre)]
+        if n:
+            self._staged = n
+        return n
+
+    def recover_block_seals_submit(self, block_hash32, seal_off, sig65, pre_flags=None) -> int:
+        """ibft_recover_block_seals_submit: the batch of recover_block_seals, enqueued and not waited for → its row count"""
+        self._need("ibft_recover_block_seals_submit")
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65))
+        n = len(s)
+        if len(bh) != nb or int(off[-1]) != n:
+            raise ValueError("block_hash32 needs one row per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        self._chk(self._L.ibft_recover_block_seals_submit(self._h, _p(bh), _p(off), nb, _p(s), _p(pre)),
+                  "ibft_recover_block_seals_submit")
+        self._block_cols = getattr(self, "_block_cols", []) + [(bh, off, s, pre)]
+        if n:
+            self._staged = 0
+        return n
+
+    def recover_block_seals_submit_raw(self, raws, rounds, seal_off, sig65, pre_flags=None) -> int:
+        """ibft_recover_block_seals_submit_raw: the batch of recover_block_seals_raw, enqueued and not waited for → its row count"""
+        self._need("ibft_recover_block_seals_submit_raw")
+        raw, roff, rnd = proposal_columns(raws, rounds)
+        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
+        nb = len(off) - 1
+        if nb < 0:
+            raise ValueError("seal_off needs n_blocks + 1 entries")
+        s = _u8(sig65, (-1, 65))
+        n = len(s)
+        if len(rnd) != nb or int(off[-1]) != n:
+            raise ValueError("one proposal per block, seal_off[-1] the number of seals")
+        pre = None if pre_flags is None else _u8(pre_flags)
+        self._chk(self._L.ibft_recover_block_seals_submit_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(pre)),
+                  "ibft_recover_block_seals_submit_raw")
+        self._block_cols = getattr(self, "_block_cols", []) + [(raw, roff, rnd, off, s, pre)]
+        if n:
+            self._staged = 0
+        return n
+
+    def block_seals_collect_ex(self) -> dict:
+        """ibft_block_seals_collect_ex: the OLDEST submitted batch of any kind → a dict with what its kind carries: always
+        "kind", "verdict" (bool[n]) and "tallies" (Tally list[n_blocks]); "block_hash32" (n_blocks, 32) for a batch submitted
+        raw; "signer20" (n, 20) and "vidx" (int32[n]) for a recover batch.  Buffers are sized from block_seals_pending_ex."""
+        self._need("ibft_block_seals_collect_ex")
+        _, n, nb, kind = self.block_seals_pending_ex()
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        tallies = (Tally * max(nb, 1))()
+        bh = np.zeros((max(nb, 1), 32), dtype=np.uint8) if kind & self.BATCH_RAW else None
+        signer = np.zeros((max(n, 1), 20), dtype=np.uint8) if kind & self.BATCH_RECOVER else None
+        vidx = np.full(max(n, 1), -1, dtype=np.int32) if kind & self.BATCH_RECOVER else None
+        self._chk(self._L.ibft_block_seals_collect_ex(self._h, _p(bh), _p(signer), _p(vidx), _p(mask), tallies),
+                  "ibft_block_seals_collect_ex")
+        if getattr(self, "_block_cols", None):
+            self._block_cols.pop(0)
+        out = {"kind": kind, "verdict": mask_to_bool(mask, n), "tallies": list(tallies)[:nb]}
+        if bh is not None:
+            out["block_hash32"] = bh[:nb]
+        if signer is not None:
+            out["signer20"] = signer[:n]
+            out["vidx"] = vidx[:n]
+        return out
+
+    def block_seals_pending_ex(self):
+        """ibft_block_seals_pending_ex: (batches in flight, rows, blocks and kind — BATCH_* bits — of the oldest)"""
+        self._need("ibft_block_seals_pending_ex")
+        a, b, c, k = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.ibft_block_seals_pending_ex(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(k)),
+                  "ibft_block_seals_pending_ex")
+        return int(a.value), int(b.value), int(c.value), int(k.value)
 
     # Verifier.IsValidValidator, batched
     def is_valid_validator(self, payload: bytes, off, sig65, from20, pre_flags=None):

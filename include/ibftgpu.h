@@ -308,7 +308,7 @@ int ibft_recover_seals(ibft_ctx *ctx, const uint8_t *hash32, const uint8_t *sig6
  * the signer20 column, plus out_signer20 (n×20, NULL with n > 0: IBFT_E_INVAL) and out_vidx (n, may be NULL); out_tally
  * n_blocks entries, may be NULL.  Equal to one ibft_recover_seals per block: a signer counts once per block, in every block
  * it signed; a seal placed in another block recovers some other address and counts only if that address is a member.
- * There is no streamed (submit / collect) form of this call.                                                         */
+ * Streamed form: ibft_recover_block_seals_submit, below the _raw calls.                                                */
 int ibft_recover_block_seals(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
                              const uint8_t *sig65, const uint8_t *pre_flags,
                              uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally);
@@ -346,8 +346,8 @@ int ibft_proposal_hashes(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_
  * the resident staged batch after the verify form and not after the recover form, behaviour towards the two pipelines, key
  * learning.  Errors: those of the hashes-given call in its order (minus the NULL block_hash32), then those of
  * ibft_proposal_hashes' arguments in its order; nothing is written to any out buffer of a refused call.  With no seal rows at
- * all the proposals are hashed only if out_block_hash32 is given.  There is no streamed (submit / collect) form of these calls:
- * a node that streams hashes the next batch with ibft_proposal_hashes and submits the hashes.                              */
+ * all the proposals are hashed only if out_block_hash32 is given.  Streamed forms: ibft_block_seals_submit_raw and
+ * ibft_recover_block_seals_submit_raw, below.                                                                              */
 int ibft_verify_block_seals_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
                                 const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20,
                                 const uint8_t *pre_flags, uint8_t *out_block_hash32, uint64_t *out_mask,
@@ -356,6 +356,67 @@ int ibft_recover_block_seals_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32
                                  const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags,
                                  uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask,
                                  ibft_tally_t *out_tally);
+
+/* Streamed chain sync FROM THE PROPOSALS and FROM BARE SEALS: the submit / collect pipeline of ibft_block_seals_submit with
+ * the reach of the synchronous calls.  A syncer streams the (Proposal, []CommittedSeal) pairs it holds — no synchronous
+ * ibft_proposal_hashes between two submits, which would wait for the batches in flight — and a chain whose headers carry
+ * only 65-byte signatures streams too.
+ *   ibft_block_seals_submit_raw          sibling: ibft_verify_block_seals_raw
+ *   ibft_recover_block_seals_submit      sibling: ibft_recover_block_seals
+ *   ibft_recover_block_seals_submit_raw  sibling: ibft_recover_block_seals_raw
+ * Defining property: each submit, collected with ibft_block_seals_collect_ex, delivers bit for bit what its synchronous
+ * sibling returns for the same arguments — mask words, every field of every ibft_tally_t, out_signer20, out_vidx and
+ * out_block_hash32 (the hashes BEFORE the seal-digest convention) — cold and warm, under every ibft_set_seal_digest convention,
+ * with IBFT_FLAG_STRICT_LOW_S on and off, for u64 and u256 powers, in both forms of the digest kernel.
+ * Rules:
+ *  - Argument checks: those of the synchronous sibling, in the sibling's order, minus the out buffers; then the pipeline's
+ *    refusals as ibft_block_seals_submit documents them (IBFT_E_INVAL: two batches in flight, seal passes in flight, a staged
+ *    batch awaiting its swap; the code of a deferred table-build error).  A refused call takes no slot.
+ *  - Shared slots: the three submits share the two slots with ibft_block_seals_submit.  Batches of different kinds may be in
+ *    flight together; they are collected oldest first; ibft_block_seals_pending counts them all.
+ *  - Pinned state: a batch is judged under the validator set, the seal-digest convention and the form of the digest kernel
+ *    current at ITS submit.
+ *  - Caller buffers: sig65, signer20, pre_flags, seal_off, block_hash32 and raw / raw_off / round stay untouched until the
+ *    collect of that batch has returned.  Pageable sources give the same results without the overlap, as for
+ *    ibft_block_seals_submit.
+ *  - Device memory: each of the two slots keeps the proposals of its batch (grown on demand, each slot bounded by
+ *    IBFT_PROPOSAL_BYTES_MAX): two slots DOUBLE the device bytes proposals can take.
+ *  - ibft_block_seals_collect_ex waits for the OLDEST batch, whatever its kind.  out_mask and out_tally as in
+ *    ibft_block_seals_collect.  out_block_hash32 (n_blocks × 32) may be NULL and is written only for a batch with
+ *    IBFT_BATCH_RAW; with no seal rows at all the proposals are hashed only if the batch was submitted raw, and the hashes
+ *    are then delivered if asked for.  out_signer20 (n × 20) must be non-NULL for a recover batch with rows: IBFT_E_INVAL
+ *    otherwise, the batch stays in flight and nothing is written.  out_vidx (n) may be NULL.  For a verify batch out_signer20
+ *    and out_vidx are not written.
+ *  - ibft_block_seals_collect (the old call): a verify batch submitted raw is collected normally, its hashes are dropped; a
+ *    recover batch with rows gets IBFT_E_INVAL, stays in flight and ibft_last_error names ibft_block_seals_collect_ex; batches
+ *    of ibft_block_seals_submit as before.
+ *  - Resident rows: after a verify-kind submit the rows are the resident staged batch, as after ibft_block_seals_submit; after
+ *    a recover-kind submit they are not (ibft_seals_launch finds no rows), as after the synchronous siblings.
+ *  - Key cache: a recover batch teaches keys; tables are built at its collect, as for the batches of ibft_block_seals_submit,
+ *    and a failed build is reported by the next submit of any kind.
+ *  - ibft_sync, ibft_ctx_destroy and every other entry point behave towards these batches as towards those of
+ *    ibft_block_seals_submit.
+ *  - ibft_block_seals_pending_ex: ibft_block_seals_pending plus the kind of the oldest batch (IBFT_BATCH_* bits, 0 for a batch
+ *    of ibft_block_seals_submit and when none is in flight).  Any pointer may be NULL.
+ * Where the digests are computed: environment IBFT_STREAM_DIGEST=copy|main, read at ibft_ctx_create — `copy` puts
+ * proposal_digest_kernel of batch k + 1 on the copy stream behind the copy of its bytes, next to the verdict kernel of batch
+ * k; `main` puts it on the main stream in front of its own batch's kernels.  Results are the same bits.  The default is
+ * `main`: the A/B of the two placements (tools/block_seals_stream_raw_rate.py) HAS NOT BEEN RUN on a device, and no gain of
+ * the streamed raw / recover forms over the synchronous calls is claimed.                               */
+#define IBFT_BATCH_RECOVER 1u /* bit 0 of a batch's kind: bare seals, signers are emitted */
+#define IBFT_BATCH_RAW 2u     /* bit 1: proposals were given, hashes are computed and can be delivered */
+int ibft_block_seals_submit_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20,
+                                const uint8_t *pre_flags);
+int ibft_recover_block_seals_submit(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                                    const uint8_t *sig65, const uint8_t *pre_flags);
+int ibft_recover_block_seals_submit_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                        const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65,
+                                        const uint8_t *pre_flags);
+int ibft_block_seals_collect_ex(ibft_ctx *ctx, uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx,
+                                uint64_t *out_mask, ibft_tally_t *out_tally);
+int ibft_block_seals_pending_ex(ibft_ctx *ctx, uint32_t *batches_in_flight, uint32_t *oldest_rows, uint32_t *oldest_blocks,
+                                uint32_t *oldest_kind);
 
 /* Chain sync ACROSS validator-set changes: a FAMILY of validator sets on the context, and block calls that judge every
  * block under the set the caller names for it — one call, one verdict launch, whatever the sets do between the blocks.
@@ -403,6 +464,8 @@ int ibft_recover_block_seals_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32
  *    and later calls — _sets or single-set, on this context or another of the device — are warm for those addresses.  A
  *    signer in the union but not in its block's set is verified like any row and its bit then cleared: the verdict (0) of
  *    the per-set call's non-member early-out.
+ *  - There is no streamed (submit / collect) form of these calls: the streamed pipeline (ibft_block_seals_submit and the
+ *    submits from proposals and bare seals) judges every batch under the context's single set.
  * When the single-set call is still the right one: a run judged under ONE set — it does without the per-row load of the
  * dense table and one upload.  What the _sets call gains over a cut batch and what it costs over the single-set call:
  * DESIGN.md §5.11, which also says what of it has been measured.  Out of scope: streamed (submit / collect) and _raw forms of the _sets calls (a

@@ -528,6 +528,9 @@ func (c *Ctx) RecoverBlockSealsRaw(raw []byte, rawOff []uint32, round []uint64, 
 type blockBatch struct {
 	blockHash32, sig65, signer20, preFlags []byte
 	sealOff                                []uint32
+	raw                                    []byte   // the streamed raw forms: the proposals as given,
+	rawOff                                 []uint32 // their offsets
+	round                                  []uint64 // and the shim's own copy of the rounds
 	pin                                    runtime.Pinner
 }
 
@@ -603,6 +606,157 @@ func (c *Ctx) BlockSealsCollect() ([]uint64, []Tally, error) {
 		tallies[b] = tally(ct[b])
 	}
 	return mask, tallies, nil
+}
+
+// Kinds of a streamed block batch (ibft_block_seals_pending_ex): bit 0 bare seals, signers are emitted; bit 1 proposals were
+// given, the computed hashes can be delivered.  0: a batch of BlockSealsSubmit.
+const (
+	BatchRecover = uint32(C.IBFT_BATCH_RECOVER)
+	BatchRaw     = uint32(C.IBFT_BATCH_RAW)
+)
+
+// submitStreamed is the common part of the three streamed submits below: raw == nil && rawOff == nil means hashes given
+// (blockHash32), bare means no signer column.  The slices are held — Go memory pinned, PinnedBytes memory left alone — until
+// the collect of the batch.
+func (c *Ctx) submitStreamed(blockHash32, raw []byte, rawOff []uint32, round []uint64, sealOff []uint32, sig65, signer20, preFlags []byte, fromRaw, bare bool) error {
+	if len(sealOff) == 0 {
+		return fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(sig65) < 65*n || (!bare && len(signer20) < 20*n) || (preFlags != nil && len(preFlags) < n) {
+		return fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	b := &blockBatch{blockHash32: blockHash32, sealOff: sealOff, sig65: sig65, signer20: signer20, preFlags: preFlags}
+	if fromRaw {
+		if len(round) != nb {
+			return fmt.Errorf("%w: one proposal per block", ErrFallback)
+		}
+		if err := checkProposals(raw, rawOff, round); err != nil {
+			return err
+		}
+		b.raw, b.rawOff = raw, rawOff
+		b.round = make([]uint64, nb+1) // (never empty: &b.round[0] below; the library reads it until the collect)
+		copy(b.round, round)
+		b.hold(unsafe.Pointer(ptr8(raw)))
+		b.hold(unsafe.Pointer(&rawOff[0]))
+		b.hold(unsafe.Pointer(&b.round[0]))
+	} else {
+		if len(blockHash32) < 32*nb {
+			return fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+		}
+		b.hold(unsafe.Pointer(ptr8(blockHash32)))
+	}
+	b.hold(unsafe.Pointer(&sealOff[0]))
+	b.hold(unsafe.Pointer(ptr8(sig65)))
+	b.hold(unsafe.Pointer(ptr8(signer20)))
+	b.hold(unsafe.Pointer(ptr8(preFlags)))
+	off := (*C.uint32_t)(unsafe.Pointer(&sealOff[0]))
+	var rc C.int
+	switch {
+	case fromRaw && !bare:
+		rc = C.ibft_block_seals_submit_raw(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
+			(*C.uint64_t)(unsafe.Pointer(&b.round[0])), off, C.size_t(nb), ptr8(sig65), ptr8(signer20), ptr8(preFlags))
+	case fromRaw && bare:
+		rc = C.ibft_recover_block_seals_submit_raw(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
+			(*C.uint64_t)(unsafe.Pointer(&b.round[0])), off, C.size_t(nb), ptr8(sig65), ptr8(preFlags))
+	default:
+		rc = C.ibft_recover_block_seals_submit(c.h, ptr8(blockHash32), off, C.size_t(nb), ptr8(sig65), ptr8(preFlags))
+	}
+	if err := c.check(rc); err != nil {
+		b.pin.Unpin() // a refused submit took no slot and reads nothing
+		return err
+	}
+	c.blocks = append(c.blocks, b)
+	return nil
+}
+
+// BlockSealsSubmitRaw enqueues the batch of VerifyBlockSealsRaw and returns without waiting for the device
+// (ibft_block_seals_submit_raw): the streamed pipeline of BlockSealsSubmit — the same two slots — fed with the PROPOSALS.  The
+// slices, raw included, must not be written to before the collect of their batch (BlockSealsCollectEx); carve them from
+// PinnedBytes for the copy to run under the kernels of the batch before.
+func (c *Ctx) BlockSealsSubmitRaw(raw []byte, rawOff []uint32, round []uint64, sealOff []uint32, sig65, signer20, preFlags []byte) error {
+	return c.submitStreamed(nil, raw, rawOff, round, sealOff, sig65, signer20, preFlags, true, false)
+}
+
+// RecoverBlockSealsSubmit enqueues the batch of RecoverBlockSeals (ibft_recover_block_seals_submit): bare seals, streamed.
+// Collect it with BlockSealsCollectEx; BlockSealsCollect refuses a recover batch with rows and leaves it in flight.
+func (c *Ctx) RecoverBlockSealsSubmit(blockHash32 []byte, sealOff []uint32, sig65, preFlags []byte) error {
+	return c.submitStreamed(blockHash32, nil, nil, nil, sealOff, sig65, nil, preFlags, false, true)
+}
+
+// RecoverBlockSealsSubmitRaw enqueues the batch of RecoverBlockSealsRaw (ibft_recover_block_seals_submit_raw).
+func (c *Ctx) RecoverBlockSealsSubmitRaw(raw []byte, rawOff []uint32, round []uint64, sealOff []uint32, sig65, preFlags []byte) error {
+	return c.submitStreamed(nil, raw, rawOff, round, sealOff, sig65, nil, preFlags, true, true)
+}
+
+// BlockSealsPendingEx = BlockSealsPending plus the kind of the oldest batch (ibft_block_seals_pending_ex): BatchRecover /
+// BatchRaw bits, 0 for a batch of BlockSealsSubmit.
+func (c *Ctx) BlockSealsPendingEx() (inFlight, oldestRows, oldestBlocks int, oldestKind uint32, err error) {
+	var a, r, b, k C.uint32_t
+	if err = c.check(C.ibft_block_seals_pending_ex(c.h, &a, &r, &b, &k)); err != nil {
+		return 0, 0, 0, 0, err
+	}
+	return int(a), int(r), int(b), uint32(k), nil
+}
+
+// BlockBatchResult is what BlockSealsCollectEx delivers: Mask and Tallies always; BlockHash32 (n_blocks × 32, the hashes before
+// the seal-digest convention) for a batch submitted raw, nil otherwise; Signer20 (n × 20) and Vidx (n) for a recover batch,
+// nil otherwise.
+type BlockBatchResult struct {
+	Kind        uint32
+	BlockHash32 []byte
+	Signer20    []byte
+	Vidx        []int32
+	Mask        []uint64
+	Tallies     []Tally
+}
+
+// BlockSealsCollectEx waits for the oldest submitted batch of ANY kind and returns what its synchronous sibling returns for it
+// (ibft_block_seals_collect_ex); buffers are sized from BlockSealsPendingEx.  ErrFallback with nothing in flight.
+func (c *Ctx) BlockSealsCollectEx() (*BlockBatchResult, error) {
+	inFlight, n, nb, kind, err := c.BlockSealsPendingEx()
+	if err != nil {
+		return nil, err
+	}
+	if inFlight == 0 {
+		return nil, ErrFallback // nothing submitted
+	}
+	res := &BlockBatchResult{Kind: kind, Mask: make([]uint64, (n+63)/64+1)}
+	ct := make([]C.ibft_tally_t, nb+1)
+	var hashes, signers []byte
+	var vidx []int32
+	var pv *C.int32_t
+	if kind&BatchRaw != 0 {
+		hashes = make([]byte, 32*nb+32)
+	}
+	if kind&BatchRecover != 0 {
+		signers = make([]byte, 20*n+20)
+		vidx = make([]int32, n+1)
+		pv = (*C.int32_t)(unsafe.Pointer(&vidx[0]))
+	}
+	rc := C.ibft_block_seals_collect_ex(c.h, ptr8(hashes), ptr8(signers), pv, (*C.uint64_t)(unsafe.Pointer(&res.Mask[0])),
+		(*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err := c.check(rc); err != nil {
+		return nil, err
+	}
+	if len(c.blocks) > 0 { // the batch is delivered: the device has read its columns
+		c.blocks[0].pin.Unpin()
+		c.blocks[0] = nil
+		c.blocks = c.blocks[1:]
+	}
+	if hashes != nil {
+		res.BlockHash32 = hashes[:32*nb]
+	}
+	if signers != nil {
+		res.Signer20 = signers[:20*n]
+		res.Vidx = vidx[:n]
+	}
+	res.Tallies = make([]Tally, nb)
+	for b := range res.Tallies {
+		res.Tallies[b] = tally(ct[b])
+	}
+	return res, nil
 }
 
 // VerifySenders = IsValidValidator over a batch (core/ibft.go:1128); payload is the
