@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libibftgpu.so")
 SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "cert_wave_dev.h", "modinv_dev.h",
-           "sign_dev.h", "secp256k1_dev.h", "keccak_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
+           "sign_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
 # Code-generation flags of the product library (part of its build stamp).  max-ilp: the verdict kernels run ONE wavefront per
 # SIMD at the sizes that matter (N ≤ 4 096), where every hazard s_nop is a lost issue slot — scheduling for instruction-level
 # parallelism instead of register pressure takes the s_nops of ecrecover_rows_kernel from 399 to 114 (133 → 174 VGPRs, still
@@ -144,7 +144,7 @@ DEVTEST = os.path.join(CSRC, "libibft_devtest.so")
 
 def build_devtest(force: bool = False) -> str:
     """TEST-ONLY: single arithmetic primitives as gfx950 kernels (tests/test_gpu_arith.py)."""
-    deps = ["devtest.hip", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "wave_fe_dev.h", "verify_dev.h"]
+    deps = ["devtest.hip", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", "wave_fe_dev.h", "verify_dev.h"]
     if force or _stale(DEVTEST, deps):
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-w",
                                "-o", DEVTEST, os.path.join(CSRC, "devtest.hip")], cwd=CSRC)
@@ -165,7 +165,7 @@ def build_host_harness(force: bool = False) -> str:
 def build_wave_harness(force: bool = False) -> str:
     """TEST-ONLY: wave_fe_dev.h (one wavefront per signature) on the CPU through wave_emul.h."""
     deps = ["host_wave_harness.hip", "wave_fe_dev.h", "wave_emul.h", "recover_dev.h", "verify_dev.h",
-            "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
+            "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h"]
     if force or _stale(WAVE_HARNESS, deps):
         subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
                                "-o", WAVE_HARNESS, os.path.join(CSRC, "host_wave_harness.hip")], cwd=CSRC)
@@ -181,6 +181,20 @@ def build_cert_wave_harness(force: bool = False) -> str:
                                "-o", CERT_WAVE_HARNESS, os.path.join(CSRC, "host_cert_wave_harness.hip")], cwd=CSRC)
         _mark(CERT_WAVE_HARNESS, deps)
     return CERT_WAVE_HARNESS
+
+
+ROW_KECCAK_HARNESS = os.path.join(CSRC, "libdev_row_keccak_host.so")
+
+
+def build_row_keccak_harness(force: bool = False) -> str:
+    """TEST-ONLY: keccak_row_dev.h (the address hash with its state spread over a row's lanes) on the CPU through wave_emul.h."""
+    deps = ["host_row_keccak_harness.hip", "keccak_row_dev.h", "wave_fe_dev.h", "wave_emul.h", "recover_dev.h", "verify_dev.h",
+            "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
+    if force or _stale(ROW_KECCAK_HARNESS, deps):
+        subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
+                               "-o", ROW_KECCAK_HARNESS, os.path.join(CSRC, "host_row_keccak_harness.hip")], cwd=CSRC)
+        _mark(ROW_KECCAK_HARNESS, deps)
+    return ROW_KECCAK_HARNESS
 
 
 PROPOSAL_DIGEST_HARNESS = os.path.join(CSRC, "libdev_proposal_digest_host.so")

@@ -193,8 +193,9 @@ __global__ void __launch_bounds__(64) devtest_wave_recover_kernel(const uint32_t
   const int i = blockIdx.x;
   uint32_t addr[5] = {0, 0, 0, 0, 0};
   aff Q;
+  __shared__ uint32_t kscr[wv::KROW_SCRATCH_DWORDS];
   bool ok = wv::recover_pubkey_wave<STOP>(gtab, from_be32(dig + 32 * i), from_be32(sig65 + 65 * i), from_be32(sig65 + 65 * i + 32),
-                                    sig65[65 * i + 64], flags, addr, Q);
+                                    sig65[65 * i + 64], flags, addr, Q, kscr);
   uint8_t *o = out + (size_t)24 * (64 * i + threadIdx.x);
   for (int k = 0; k < 5; k++) reinterpret_cast<uint32_t *>(o)[k] = addr[k];
   o[20] = ok ? 1 : 0;
@@ -366,6 +367,8 @@ extern "C" int devtest_rows_repeat_ms(int n, const uint8_t *dig, const uint8_t *
 // The product kernel's shape (four main wavefronts, their helpers w + 4, one workgroup per compute unit); the pair's barriers
 // go through a SYNC that stamps s_memrealtime (100 MHz) on each side.  Per wavefront, 8 u64 in `stamps`: [0] start,
 // [1] [2] barrier 1 reached / left, [3] [4] barrier 2 reached / left, [5] end.  Stamps go to this buffer only.
+// STOP = 6 ends the main wavefronts behind the closing chain (no address hash; addresses are then junk): "after barrier 2" of
+// that launch is the closing chain alone, and the difference to the complete launch is the hash and the compare.
 struct stamp_sync {
   uint64_t *st;
   uint32_t *cnt;  // (LDS, this wavefront's: how many barriers it has passed)
@@ -381,6 +384,7 @@ struct stamp_sync {
     }
   }
 };
+template <int STOP>
 __global__ void __launch_bounds__(512) devtest_rows_pair_kernel(const uint32_t *gtab, const uint8_t *dig, const uint8_t *sig65,
                                                               uint32_t n, uint8_t *out, uint64_t *stamps) {
   __shared__ uint32_t row_tab[4][wv::ROW_TAB_SLOTS * 64];
@@ -403,7 +407,7 @@ __global__ void __launch_bounds__(512) devtest_rows_pair_kernel(const uint32_t *
   }
   uint32_t addr[5] = {0, 0, 0, 0, 0};
   aff Q;
-  const bool ok = wv::recover_pubkey_row<99, true>(gtab, zero256(), r, s, sig65[65 * i + 64], 0, addr, Q, row_tab[slot], &sh[slot], sync);
+  const bool ok = wv::recover_pubkey_row<STOP, true>(gtab, zero256(), r, s, sig65[65 * i + 64], 0, addr, Q, row_tab[slot], &sh[slot], sync);
   if (lane == 0) st[5] = __builtin_amdgcn_s_memrealtime();
   if ((lane & 15u) == 0 && row_raw < n) {
     uint8_t *o = out + (size_t)24 * i;
@@ -413,8 +417,9 @@ __global__ void __launch_bounds__(512) devtest_rows_pair_kernel(const uint32_t *
 }
 // n rows (a multiple of 16: whole workgroups), three launches; out24 = addresses + ok, stamps8 = (n / 4) · 2 wavefronts × 8
 // u64 of the last launch (main wavefronts of workgroup b at 8b … 8b + 3, helpers at 8b + 4 … 8b + 7); ms = its kernel time
-extern "C" int devtest_rows_pair_stamps(int n, const uint8_t *dig, const uint8_t *sig65, uint8_t *out24, uint64_t *stamps8,
-                                        float *ms) {
+// stop = 6: the launches end behind the closing chain (see STOP above); any other value: the complete recover
+extern "C" int devtest_rows_pair_stamps_stop(int stop, int n, const uint8_t *dig, const uint8_t *sig65, uint8_t *out24,
+                                             uint64_t *stamps8, float *ms) {
   if (n <= 0 || n % 16 != 0) return -3;
   uint32_t *dg;
   size_t gbytes = (size_t)ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES * ibftk::GTAB_ENTRY_DWORDS * 4;
@@ -429,7 +434,10 @@ extern "C" int devtest_rows_pair_stamps(int n, const uint8_t *dig, const uint8_t
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   for (int rep = 0; rep < 3; rep++) {
     (void)hipEventRecord(e0, 0);
-    devtest_rows_pair_kernel<<<blocks, 512>>>(dg, dd, ds, (uint32_t)n, dout, dst);
+    if (stop == 6)
+      devtest_rows_pair_kernel<6><<<blocks, 512>>>(dg, dd, ds, (uint32_t)n, dout, dst);
+    else
+      devtest_rows_pair_kernel<99><<<blocks, 512>>>(dg, dd, ds, (uint32_t)n, dout, dst);
     (void)hipEventRecord(e1, 0);
     (void)hipEventSynchronize(e1);
     (void)hipEventElapsedTime(ms, e0, e1);
@@ -441,4 +449,8 @@ extern "C" int devtest_rows_pair_stamps(int n, const uint8_t *dig, const uint8_t
   }
   (void)hipFree(dd); (void)hipFree(ds); (void)hipFree(dout); (void)hipFree(dst); (void)hipFree(dg);
   return rc;
+}
+extern "C" int devtest_rows_pair_stamps(int n, const uint8_t *dig, const uint8_t *sig65, uint8_t *out24, uint64_t *stamps8,
+                                        float *ms) {
+  return devtest_rows_pair_stamps_stop(99, n, dig, sig65, out24, stamps8, ms);
 }

@@ -77,6 +77,7 @@ void lane_pt(void *vp) {
   if (k.li == 0) o[30] = r.inf ? 1u : 0u;
 }
 
+uint32_t g_kscr[wv::KROW_SCRATCH_DWORDS];  // the address hash's scratch: one emulated wavefront runs at a time
 struct rec_job {
   const uint8_t *hash32, *sig65;
   uint32_t flags;
@@ -88,7 +89,7 @@ void lane_rec(void *vp) {
   u256 z = secp::from_be32(j->hash32), r = secp::from_be32(j->sig65), s = secp::from_be32(j->sig65 + 32);
   uint32_t a[5];
   secp::aff Q;
-  bool ok = wv::recover_pubkey_wave(g_gtab.data(), z, r, s, j->sig65[64], j->flags, a, Q);
+  bool ok = wv::recover_pubkey_wave(g_gtab.data(), z, r, s, j->sig65[64], j->flags, a, Q, g_kscr);
   const int l = wave_emul::lane();
   memcpy(j->addr20 + 20 * l, a, 20);
   j->ok[l] = ok ? 1 : 0;
@@ -112,7 +113,7 @@ void lane_rec2_main(void *vp) {
   u256 z = secp::from_be32(j->hash32), r = secp::from_be32(j->sig65), s = secp::from_be32(j->sig65 + 32);
   uint32_t a[5];
   secp::aff Q;
-  bool ok = wv::recover_pubkey_wave<99, true>(g_gtab.data(), z, r, s, j->sig65[64], j->flags, a, Q, j->sh, wv::no_sync());
+  bool ok = wv::recover_pubkey_wave<99, true>(g_gtab.data(), z, r, s, j->sig65[64], j->flags, a, Q, g_kscr, j->sh, wv::no_sync());
   const int l = wave_emul::lane();
   memcpy(j->addr20 + 20 * l, a, 20);
   j->ok[l] = ok ? 1 : 0;

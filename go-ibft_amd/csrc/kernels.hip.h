@@ -969,7 +969,8 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) ecrecover_wave_kernel(
   }
   uint32_t got[5];
   aff Qa;
-  bool ok = wv::recover_pubkey_wave(a.gtab, z, r, s, v, a.flags, got, Qa);
+  __shared__ uint32_t krow_scr[WAVE_KERNEL_WAVES][wv::KROW_SCRATCH_DWORDS];  // the address hash's transposition: wave-private LDS
+  bool ok = wv::recover_pubkey_wave(a.gtab, z, r, s, v, a.flags, got, Qa, krow_scr[threadIdx.x >> 6]);
   if (MODE == MODE_EMIT) {
     const emitted e = emit_row(ok, false, got, a.vtab, a.vslot_mask);
     if (lane == 0) emit_store(a, row, e);
@@ -996,6 +997,7 @@ constexpr int PAIRS_PER_BLOCK = 2;
 template <int MODE>
 __global__ void __launch_bounds__(128 * PAIRS_PER_BLOCK) ecrecover_wave2_kernel(recover_args a) {
   __shared__ wv::pair_shared sh[PAIRS_PER_BLOCK];
+  __shared__ uint32_t krow_scr[PAIRS_PER_BLOCK][wv::KROW_SCRATCH_DWORDS];  // the main wavefronts' address hash: wave-private LDS
   const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t slot = w % PAIRS_PER_BLOCK;
   const bool helper = w >= PAIRS_PER_BLOCK;
@@ -1038,7 +1040,7 @@ __global__ void __launch_bounds__(128 * PAIRS_PER_BLOCK) ecrecover_wave2_kernel(
   }
   uint32_t got[5];
   aff Qa;
-  bool ok = wv::recover_pubkey_wave<99, true>(a.gtab, z, r, s, v, a.flags, got, Qa, &sh[slot], sync);
+  bool ok = wv::recover_pubkey_wave<99, true>(a.gtab, z, r, s, v, a.flags, got, Qa, krow_scr[slot], &sh[slot], sync);
   if (MODE == MODE_EMIT) {
     const emitted e = emit_row(ok, false, got, a.vtab, a.vslot_mask);
     if (lane == 0) emit_store(a, row, e);

@@ -16,7 +16,8 @@
 //
 // Contents: cross-lane primitives · wfe_mul / linear ops · row ↔ lane layout · group law per row ·
 // √ chain riding on the 3-row prefix doublings · modinv_wave (safegcd, limbs over lanes) ·
-// recover_pubkey_wave (cold path) · verify_known_wave (warm path).  DESIGN.md §4 has the measurements.
+// recover_pubkey_wave (cold path) · verify_known_wave (warm path) · the row-per-signature recover, whose address hash is
+// keccak_row_dev.h (the Keccak state over the lanes of a row).  DESIGN.md §4 has the measurements.
 //
 // RULE: a cross-lane primitive must never sit under lane-dependent control flow (`c ? f(dpp) : x` with
 // a per-row c executes the DPP in some rows only).  The host emulator tags every rendezvous with its
@@ -879,6 +880,10 @@ WVF wjac gen_windows_wave(const uint32_t *__restrict__ gtab, const u256 &u1, wja
 WVF wjac gen_windows_wave(const uint32_t *__restrict__ gtab, const u256 &u1, wjac acc, const wk &k) {
   return gen_windows_wave(gtab, u1, acc, gen_window_point(gtab, u1, 0, k), k);
 }
+}  // namespace wv
+#include "keccak_row_dev.h"  // wv::address_from_xy_row: the address of a row's key, the state spread over the row's lanes
+namespace wv {
+
 // ---- the recover, one signature per wavefront -------------------------------------------------------
 // Same contract and rejection list as ibftk::recover_pubkey (recover_dev.h); every lane of the
 // wavefront passes the same (z, r, s, v) and gets the same answer.
@@ -892,6 +897,8 @@ WVF wjac gen_windows_wave(const uint32_t *__restrict__ gtab, const u256 &u1, wja
 // the G additions runs on (w·x, w², 1) — the isomorphic curve y² = x³ + 7w³ — and the accumulator's Z
 // is multiplied by y once the chain (computed by row 3 during the prefix doublings) has delivered it.
 // STOP < 99 cuts the function short after a stage (devtest timing breakdown only; addr then holds junk).
+// `kscr`: KROW_SCRATCH_DWORDS dwords of wave-private scratch (LDS on the device) for the address hash; the four rows hold the
+// same key after the joins, each hashes it over its own lanes (keccak_row_dev.h) and every lane gets the same address.
 //
 // TWO WAVEFRONTS PER SIGNATURE (round 4, n ≤ 512 — at most half of the chip's SIMDs would otherwise work): PAIR = true is
 // the MAIN wavefront of a pair.  Everything on its critical path stays (√ riding on the prefix doublings, table, the 64
@@ -911,8 +918,8 @@ struct no_sync {
 };
 template <int STOP = 99, bool PAIR = false, class SYNC = no_sync>
 WVF bool recover_pubkey_wave(const uint32_t *__restrict__ gtab, const u256 &z_raw, const u256 &r, const u256 &s,
-                            uint32_t v, uint32_t flags, uint32_t addr[5], aff &Qa, const pair_shared *sh = nullptr,
-                            SYNC sync = SYNC()) {
+                            uint32_t v, uint32_t flags, uint32_t addr[5], aff &Qa, uint32_t *kscr,
+                            const pair_shared *sh = nullptr, SYNC sync = SYNC()) {
 #define WV_STAGE(n, keep)     \
   if (STOP == (n)) {          \
     addr[0] = (keep);         \
@@ -1048,8 +1055,7 @@ WVF bool recover_pubkey_wave(const uint32_t *__restrict__ gtab, const u256 &z_ra
   const jac Q = wjac_gather(acc);
   ok = jac_to_aff_wave(Qa, Q, k) && ok;  // every row holds the same point after the joins
   WV_STAGE(6, Qa.x.n[0] ^ Qa.y.n[1])
-  u256 qx = secp::l26_to_u256(Qa.x), qy = secp::l26_to_u256(Qa.y);
-  keccak::address_from_xy(qx.v, qy.v, addr);
+  address_from_xy_row(Qa.x, Qa.y, addr, kscr);
   return ok;
 #undef WV_STAGE
 }
@@ -1397,8 +1403,9 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
   WV_STAGE(5, acc.x ^ acc.y ^ acc.z ^ accg.x ^ accg.z)
   ok = rows_finish_deferred(Qa, accg, acc, rhs, v, k) && ok;
   WV_STAGE(6, Qa.x.n[0] ^ Qa.y.n[1])
-  u256 qx = secp::l26_to_u256(Qa.x), qy = secp::l26_to_u256(Qa.y);
-  keccak::address_from_xy(qx.v, qy.v, addr);
+  // the window table is dead since the main loop (rows_finish_deferred never sees it): the row Keccak's scratch
+  static_assert(KROW_SCRATCH_DWORDS <= ROW_TAB_SLOTS * 64, "the row Keccak's scratch lives in the window table");
+  address_from_xy_row(Qa.x, Qa.y, addr, wtab);
   return ok;
 #undef WV_STAGE
 }

@@ -3,7 +3,8 @@ Usage: python tools/rows_pair_stages.py [n_rows=4096]
 
 The pair kernel (devtest_rows_pair_kernel: recover_pubkey_row<…, PAIR> + recover_helper_row) stamps s_memrealtime on both
 sides of its two workgroup barriers: per wavefront, the stage before barrier 1, the wait there, the stage between the
-barriers, the wait at barrier 2 and the rest.  Next to it, the single-wavefront form's stage deltas (devtest_rows_stage_ms:
+barriers, the wait at barrier 2 and the rest; a second run whose main wavefronts stop behind the closing chain
+(devtest_rows_pair_stamps_stop, STOP = 6) splits "after barrier 2" into closing chain and address hash.  Next to it, the single-wavefront form's stage deltas (devtest_rows_stage_ms:
 launches cut short after each stage) — its main loop against the pair's main loop, which shares the SIMD with the helper."""
 import ctypes as C
 import os
@@ -49,3 +50,16 @@ for nm, a, b in [("before barrier 1", 0, 1), ("wait at barrier 1", 1, 2), ("betw
 print(f"# main: tables {us(0, 1)[main].mean():.1f} µs (single form {1000 * (st1[2] - st1[1]):.1f}), barrier-1 wait "
       f"{us(1, 2)[main].mean():.1f}, main loop {us(2, 3)[main].mean():.1f} (single form {1000 * (st1[3] - st1[2]):.1f}), barrier-2 wait "
       f"{us(3, 4)[main].mean():.1f}; helper: scalars {us(0, 1)[helper].mean():.1f}, G additions {us(2, 3)[helper].mean():.1f}")
+if hasattr(L, "devtest_rows_pair_stamps_stop"):
+    # the same launches with the main wavefronts ending behind the closing chain: what is left of "after barrier 2" is the hash
+    st6 = np.zeros_like(stamps)
+    pms6 = C.c_float()
+    junk = np.zeros((n, 24), np.uint8)
+    assert L.devtest_rows_pair_stamps_stop(6, n, dig, sig, junk.ctypes.data_as(C.c_void_p), st6.ctypes.data_as(C.c_void_p), C.byref(pms6)) == 0
+    s6 = st6.reshape(blocks, 8, 8).astype(np.int64)
+    chain = np.median(s6[:, :4, 5] - s6[:, :4, 4], axis=0) / 100.0
+    tail = us(4, 5)[main]
+    print(f"  {'  closing chain (STOP 6)':24s} main {' '.join(f'{x:7.1f}' for x in chain)}")
+    print(f"  {'  Keccak, compare':24s} main {' '.join(f'{x:7.1f}' for x in tail - chain)}")
+    print(f"# after barrier 2: closing chain {chain.mean():.1f} µs + Keccak, compare {(tail - chain).mean():.1f} µs; kernel without the hash "
+          f"{pms6.value:.4f} ms, with it {pms.value:.4f} ms")
