@@ -631,8 +631,12 @@ int ibft_cache_stats(ibft_ctx *ctx, uint32_t *tables, uint32_t *warm_passes, uin
  * pool of validator tables keyed by ADDRESS (655 KB per validator, IBFT_QTAB_BUDGET_GB, default 64) — the four contexts a
  * Backend keeps for its four goroutines cost one pool, not four; a key learned through one context is
  * known to all of them; a validator that stays in the set across ibft_set_validators keeps its table (a rotation of 1 % of
- * the validators relearns 1 %), a slot nobody's current set refers to is reused.  This reports the shared object of ctx's
- * device: bytes it holds, slots in use / allocated, and how many contexts share it.                                   */
+ * the validators relearns 1 %), a slot nobody's current set refers to is reused (its state reads "unknown" again before any
+ * kernel can see it: the old key and table left in it are never consulted).  The pool never holds more than
+ * IBFT_QTAB_BUDGET_GB / 655 360 slots: validators of a set beyond that have no slot and are served by the recover path for
+ * good (verdicts unchanged; ibft_cache_stats never reports every table built for such a set), and a budget of 0 turns the
+ * cache off without an error.  This reports the shared object of ctx's device: bytes it holds, slots in use / allocated, and
+ * how many contexts share it (tests/test_gpu_key_cache_lifecycle.py pins all of this in fresh processes).            */
 int ibft_cache_memory(ibft_ctx *ctx, uint64_t *device_bytes, uint32_t *slots_in_use, uint32_t *slots_allocated,
                       uint32_t *contexts_sharing);
 /* Lanes per signature used by the last verdict pass: cold kernel (1 = ecrecover_lane_kernel,
