@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libibftgpu.so")
 SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "cert_wave_dev.h", "modinv_dev.h",
-           "sign_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
+           "sign_dev.h", "sha256_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
 # Code-generation flags of the product library (part of its build stamp).  max-ilp: the verdict kernels run ONE wavefront per
 # SIMD at the sizes that matter (N ≤ 4 096), where every hazard s_nop is a lost issue slot — scheduling for instruction-level
 # parallelism instead of register pressure takes the s_nops of ecrecover_rows_kernel from 399 to 114 (133 → 174 VGPRs, still
@@ -144,7 +144,8 @@ DEVTEST = os.path.join(CSRC, "libibft_devtest.so")
 
 def build_devtest(force: bool = False) -> str:
     """TEST-ONLY: single arithmetic primitives as gfx950 kernels (tests/test_gpu_arith.py)."""
-    deps = ["devtest.hip", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", "wave_fe_dev.h", "verify_dev.h"]
+    deps = ["devtest.hip", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", "wave_fe_dev.h", "verify_dev.h",
+            "sign_dev.h", "sha256_dev.h"]
     if force or _stale(DEVTEST, deps):
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-w",
                                "-o", DEVTEST, os.path.join(CSRC, "devtest.hip")], cwd=CSRC)
@@ -154,7 +155,7 @@ def build_devtest(force: bool = False) -> str:
 
 def build_host_harness(force: bool = False) -> str:
     """TEST-ONLY: the device arithmetic headers compiled for the CPU (hipcc host pass)."""
-    deps = ["host_arith_harness.hip", "sign_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "wire_dev.h", "verify_dev.h"]
+    deps = ["host_arith_harness.hip", "sign_dev.h", "sha256_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "wire_dev.h", "verify_dev.h"]
     if force or _stale(HOST_HARNESS, deps):
         subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
                                "-o", HOST_HARNESS, os.path.join(CSRC, "host_arith_harness.hip")], cwd=CSRC)
@@ -234,6 +235,19 @@ def build_block_head_harness(force: bool = False) -> str:
                                "-o", BLOCK_HEAD_HARNESS, os.path.join(CSRC, "host_block_head_harness.hip")], cwd=CSRC)
         _mark(BLOCK_HEAD_HARNESS, deps)
     return BLOCK_HEAD_HARNESS
+
+
+SIGN_NONCE_HARNESS = os.path.join(CSRC, "libdev_sign_nonce_host.so")
+
+
+def build_sign_nonce_harness(force: bool = False) -> str:
+    """TEST-ONLY: sha256_dev.h and the RFC 6979 nonce rule of sign_dev.h (compression, HMAC, the DRBG, the signing row) on the CPU."""
+    deps = ["host_sign_nonce_harness.hip", "sign_dev.h", "sha256_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
+    if force or _stale(SIGN_NONCE_HARNESS, deps):
+        subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
+                               "-o", SIGN_NONCE_HARNESS, os.path.join(CSRC, "host_sign_nonce_harness.hip")], cwd=CSRC)
+        _mark(SIGN_NONCE_HARNESS, deps)
+    return SIGN_NONCE_HARNESS
 
 
 if __name__ == "__main__":

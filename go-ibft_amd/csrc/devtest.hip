@@ -454,3 +454,31 @@ extern "C" int devtest_rows_pair_stamps(int n, const uint8_t *dig, const uint8_t
                                         float *ms) {
   return devtest_rows_pair_stamps_stop(99, n, dig, sig65, out24, stamps8, ms);
 }
+
+// ---- the RFC 6979 DRBG of sign_dev.h: one lane per row, the first m candidates of each (a reseed between two) ----
+#include "sign_dev.h"
+
+__global__ void __launch_bounds__(64) devtest_rfc6979_kernel(uint32_t n, uint32_t m, const uint8_t *sk, const uint8_t *dig, uint8_t *out) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  u256 z = from_be32(dig + 32ull * i);
+  sub_const_if(z, geq_const(z, NL()), NL());
+  ibftk::rfc6979_drbg g;
+  g.init(from_be32(sk + 32ull * i), z);
+#pragma unroll 1
+  for (uint32_t t = 0; t < m; t++) {
+    if (t) g.reseed();
+    to_be32(out + 32ull * ((size_t)i * m + t), g.candidate());
+  }
+}
+// sk, dig: n × 32 bytes; out: n × m × 32 bytes (row-major: row i's candidates 0 … m − 1)
+extern "C" int devtest_rfc6979(int n, int m, const uint8_t *sk, const uint8_t *dig, uint8_t *out) {
+  if (n <= 0 || m <= 0) return -3;
+  uint8_t *ds = dev_copy(sk, (size_t)32 * n), *dd = dev_copy(dig, (size_t)32 * n), *dout;
+  if (!ds || !dd || hipMalloc(&dout, (size_t)32 * n * m) != hipSuccess) return -1;
+  devtest_rfc6979_kernel<<<(n + 63) / 64, 64>>>((uint32_t)n, (uint32_t)m, ds, dd, dout);
+  int rc = hipDeviceSynchronize() == hipSuccess ? 0 : -2;
+  if (rc == 0) (void)hipMemcpy(out, dout, (size_t)32 * n * m, hipMemcpyDeviceToHost);
+  (void)hipFree(ds); (void)hipFree(dd); (void)hipFree(dout);
+  return rc;
+}

@@ -2792,8 +2792,19 @@ int ibft_verify_messages(ibft_ctx *c, const uint8_t *payload, const uint32_t *of
 // f4: the committed seals of a simulated validator set, one per row.
 int ibft_sign_seals(ibft_ctx *c, const uint8_t *sk32, const uint8_t *hash32, size_t n, uint8_t *out_sig65,
                     uint8_t *out_signer20, uint8_t *out_ok) {
+  return ibft_sign_seals_ex(c, sk32, hash32, n, IBFT_SIGN_NONCE_KECCAK, out_sig65, out_signer20, out_ok);
+}
+
+// the same under a chosen nonce rule: one instantiation of sign_lane_kernel per rule
+int ibft_sign_seals_ex(ibft_ctx *c, const uint8_t *sk32, const uint8_t *hash32, size_t n, uint32_t nonce, uint8_t *out_sig65,
+                       uint8_t *out_signer20, uint8_t *out_ok) {
   if (!c || (n && (!sk32 || !hash32 || !out_sig65))) return IBFT_E_INVAL;
   ctx_lock lk(c);
+  if (nonce != IBFT_SIGN_NONCE_KECCAK && nonce != IBFT_SIGN_NONCE_RFC6979) {
+    c->last_error = "ibft_sign_seals_ex: unknown nonce rule " + std::to_string(nonce) +
+                    " (IBFT_SIGN_NONCE_KECCAK = 0, IBFT_SIGN_NONCE_RFC6979 = 1)";
+    return IBFT_E_INVAL;
+  }
   if (n > c->max_rows) return IBFT_E_TOOBIG;
   HIPCHK(c, hipSetDevice(c->device));
   c->wire_valid = false;
@@ -2812,7 +2823,10 @@ int ibft_sign_seals(ibft_ctx *c, const uint8_t *sk32, const uint8_t *hash32, siz
   a.ok = (uint8_t *)c->d_pre.p;
   a.n = (uint32_t)n;
   const uint32_t blocks = (uint32_t)((n + ibftk::ROWS_PER_BLOCK - 1) / ibftk::ROWS_PER_BLOCK);
-  hipLaunchKernelGGL(ibftk::sign_lane_kernel, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
+  if (nonce == IBFT_SIGN_NONCE_RFC6979)
+    hipLaunchKernelGGL(ibftk::sign_lane_kernel<ibftk::SIGN_NONCE_RFC6979>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(ibftk::sign_lane_kernel<ibftk::SIGN_NONCE_KECCAK>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemsetAsync(c->d_payload.p, 0, n * 32, c->stream));  // the keys do not outlive the call in HBM
   HIPCHK(c, hipMemcpyAsync(out_sig65, c->d_sig.p, n * 65, hipMemcpyDeviceToHost, c->stream));

@@ -196,6 +196,9 @@ struct sign_args {
   uint8_t *ok;             // n out: 1 = signed, 0 = key outside [1, n)
   uint32_t n;
 };
+// NONCE = SIGN_NONCE_KECCAK is the kernel as it always was; SIGN_NONCE_RFC6979 derives the nonce with the HMAC-SHA-256 DRBG
+// (sign_dev.h: rfc6979_drbg) — same arguments, same columns, same stores.
+template <int NONCE>
 __global__ void __launch_bounds__(ROWS_PER_BLOCK) sign_lane_kernel(sign_args a) {
   const uint32_t row = blockIdx.x * (uint32_t)ROWS_PER_BLOCK + threadIdx.x;
   const bool live = row < a.n;
@@ -214,7 +217,7 @@ __global__ void __launch_bounds__(ROWS_PER_BLOCK) sign_lane_kernel(sign_args a) 
   }
   u256 r, s;
   uint32_t v, addr[5];
-  const bool ok = sign_row(a.gtab, sk, dg, r, s, v, addr);
+  const bool ok = sign_row<NONCE>(a.gtab, sk, dg, r, s, v, addr, 0u);
   if (!live) return;
   uint8_t *o = a.sig65 + 65ull * row;  // 65-byte rows are not dword aligned: byte stores
 #pragma unroll

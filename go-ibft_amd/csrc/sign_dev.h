@@ -13,14 +13,21 @@
 // s is negated), i.e. what ibft_verify_seals accepts under every flag.  The nonce is deterministic
 // and is the one the CPU oracle uses (oracle/secp256k1.c:orc_sign):
 //     k = keccak256(sk32 ‖ digest32 ‖ LE32(ctr)) mod n,   ctr = 0, 1, … until (k, r, s) are all usable
-// so that a device signature can be compared byte for byte with the oracle's.  (It is NOT RFC 6979;
-// nothing on the verify side depends on how k was chosen.)
+// so that a device signature can be compared byte for byte with the oracle's.  That rule (SIGN_NONCE_KECCAK) is this
+// repository's own and stays the default.  The second rule, SIGN_NONCE_RFC6979, is RFC 6979 §3.2 with HMAC-SHA-256 at
+// hlen = qlen = 256 and bits2octets(h1) = h1 mod n (rfc6979_drbg below, the restatement of oracle/secp256k1.c:
+// orc_sign_rfc6979): what btcec, bitcoinjs and the published secp256k1 vectors use, so a seal signed under it can be re-derived
+// by third-party tools.  The candidate rules are the same under both: 0 < k < n, r = R.x with 0 < r < n (R.x ≥ n would need
+// recovery id ≥ 2: the next candidate is taken instead), s ≠ 0.  Nothing on the verify side depends on how k was chosen.
 #pragma once
 #include "recover_dev.h"
+#include "sha256_dev.h"
 
 namespace ibftk {
 
 constexpr uint32_t SIGN_MAX_TRIES = 1024;  // same bound as the oracle; a retry has probability ≈2^-128
+constexpr int SIGN_NONCE_KECCAK = 0;       // IBFT_SIGN_NONCE_KECCAK
+constexpr int SIGN_NONCE_RFC6979 = 1;      // IBFT_SIGN_NONCE_RFC6979
 
 // keccak256 of the 68-byte nonce preimage, as a 256-bit big-endian integer
 __host__ __device__ __forceinline__ u256 sign_nonce_hash(const uint8_t *sk32, const uint8_t *digest32, uint32_t ctr) {
@@ -47,17 +54,61 @@ __host__ __device__ __forceinline__ u256 sign_nonce_hash(const uint8_t *sk32, co
   return k;
 }
 
+// RFC 6979 §3.2 (b)–(h), HMAC-SHA-256, for one signature.  Of K only the two pad midstates are kept (sha256_dev.h: every
+// HMAC under K starts from them); they and V are 24 words in registers and never stored.  A signature whose first candidate
+// is usable costs 16 compressions: 2 × (3 for K = HMAC_K(V ‖ tag ‖ x ‖ h1) + 2 for the new K's midstates + 2 for V = HMAC_K(V))
+// + 2 for the candidate (the midstates of the initial all-zero K are constants).
+struct rfc6979_drbg {
+  sha256::hmac_key K;
+  sha256::state V;
+
+  __host__ __device__ static __forceinline__ sha256::state words(const u256 &a) {  // 32 big-endian bytes as words
+    return sha256::state{a.v[7], a.v[6], a.v[5], a.v[4], a.v[3], a.v[2], a.v[1], a.v[0]};
+  }
+  // x = int2octets(secret key), h1 = bits2octets(digest) = the digest mod n
+  __host__ __device__ __forceinline__ void init(const u256 &x, const u256 &h1) {
+    const sha256::state xs = words(x), hs = words(h1);
+    K = sha256::hmac_midstates_zero_key();                                                       // (c) K = 0x00 …
+    V = sha256::state{0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};  // (b)
+#pragma unroll 1
+    for (uint32_t tag = 0; tag < 2; tag++) {                                                     // (d) (e), then (f) (g)
+      K = sha256::hmac_midstates(sha256::hmac_v_tag_x_h(K, V, tag, xs, hs));
+      V = sha256::hmac_v(K, V);
+    }
+  }
+  // (h.2) with tlen = qlen after one block: V = HMAC_K(V), the candidate is V as a big-endian integer
+  __host__ __device__ __forceinline__ u256 candidate() {
+    V = sha256::hmac_v(K, V);
+    u256 k;
+    k.v[7] = V.a, k.v[6] = V.b, k.v[5] = V.c, k.v[4] = V.d, k.v[3] = V.e, k.v[2] = V.f, k.v[1] = V.g, k.v[0] = V.h;
+    return k;
+  }
+  // (h.3) after an unusable candidate: K = HMAC_K(V ‖ 0x00), V = HMAC_K(V)
+  __host__ __device__ __forceinline__ void reseed() {
+    K = sha256::hmac_midstates(sha256::hmac_v_00(K, V));
+    V = sha256::hmac_v(K, V);
+  }
+};
+
 // One row.  Returns false (and writes zeros) for a key outside [1, n) or when no nonce was usable.
 // `tries` lets the caller keep a wavefront convergent: the loop body is executed by every lane until
 // all lanes of the wavefront are done (on the device), lanes that finished discard the extra attempts.
+// NONCE: SIGN_NONCE_KECCAK (the rule above) or SIGN_NONCE_RFC6979.  reject_mask is a test seam of the RFC 6979 rule: bit t set
+// treats candidate t as unusable, which is the only way to reach the reseed step (a real retry has probability ≈2^-128); the
+// kernel passes the constant 0 and the seam folds away.
+template <int NONCE = SIGN_NONCE_KECCAK>
 __host__ __device__ __forceinline__ bool sign_row(const uint32_t *__restrict__ gtab, const uint8_t *sk32,
                                                   const uint8_t *digest32, u256 &r_out, u256 &s_out, uint32_t &v_out,
-                                                  uint32_t addr[5]) {
+                                                  uint32_t addr[5], uint32_t reject_mask = 0) {
+  static_assert(NONCE == SIGN_NONCE_KECCAK || NONCE == SIGN_NONCE_RFC6979, "unknown nonce rule");
   const u256 d = secp::from_be32(sk32);
   const bool key_ok = !secp::is_zero(d) && !secp::geq_const(d, secp::NL());
   u256 z = secp::from_be32(digest32);
   secp::sub_const_if(z, secp::geq_const(z, secp::NL()), secp::NL());  // z mod n (z < 2^256 < 2n)
   const secp::sc d_sc = secp::sc_from_u256(d);
+
+  rfc6979_drbg drbg;
+  if constexpr (NONCE == SIGN_NONCE_RFC6979) drbg.init(d, z);
 
   bool done = !key_ok, ok = false;
   r_out = secp::zero256();
@@ -69,9 +120,18 @@ __host__ __device__ __forceinline__ bool sign_row(const uint32_t *__restrict__ g
 #else
     if (done) break;
 #endif
-    u256 k = sign_nonce_hash(sk32, digest32, ctr);
-    secp::sub_const_if(k, secp::geq_const(k, secp::NL()), secp::NL());
-    bool good = !secp::is_zero(k);
+    u256 k;
+    bool good;
+    if constexpr (NONCE == SIGN_NONCE_RFC6979) {
+      if (ctr) drbg.reseed();  // (uniform: every lane of the wavefront is in the same attempt)
+      k = drbg.candidate();
+      good = !secp::is_zero(k) && !secp::geq_const(k, secp::NL());
+      good = good && !(ctr < 32u && ((reject_mask >> ctr) & 1u));
+    } else {
+      k = sign_nonce_hash(sk32, digest32, ctr);
+      secp::sub_const_if(k, secp::geq_const(k, secp::NL()), secp::NL());
+      good = !secp::is_zero(k);
+    }
     const u256 k_safe = secp::select(good, k, secp::one256());  // keep the inversion's precondition
     // R = k·G
     jac R = ecmult_gen(gtab, k_safe, secp::jac_inf());

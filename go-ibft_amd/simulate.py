@@ -56,14 +56,15 @@ class DeviceRound:
 
 
 def make_round(bv, n: int, seed: int = 1, *, byzantine: bool = False, weighted: bool = False, raw_len: int = 1024,
-               round_: int = 0) -> DeviceRound:
+               round_: int = 0, nonce: str = "keccak") -> DeviceRound:
     """n validators, one COMMIT seal each over keccak256(raw ‖ BE64(round)) — keys, proposal hash and signatures all
-    computed by `bv` (a BatchVerifier: ibft_proposal_hash, ibft_sign_seals).  Leaves bv's staged batch undefined."""
+    computed by `bv` (a BatchVerifier: ibft_proposal_hash, ibft_sign_seals).  Leaves bv's staged batch undefined.
+    nonce: the signer's nonce rule for every seal of the round, "keccak" (default) or "rfc6979" (BatchVerifier.sign_seals)."""
     raw = _splitmix(seed, (raw_len + 7) // 8).tobytes()[:raw_len]
     H = bv.proposal_hash(raw, round_)
     sk = secret_keys(seed, n)
     hcol = np.tile(np.frombuffer(H, dtype=np.uint8), (n, 1))
-    seal, addrs, ok = _sign(bv, sk, hcol)
+    seal, addrs, ok = _sign(bv, sk, hcol, nonce=nonce)
     assert ok.all()
     power = (1 + (_splitmix(seed ^ 0x57A4E, n) % np.uint64(16))).astype(np.uint64) if weighted else np.ones(n, dtype=np.uint64)
     signer = addrs.copy()
@@ -75,8 +76,8 @@ def make_round(bv, n: int, seed: int = 1, *, byzantine: bool = False, weighted: 
         bad = np.flatnonzero(_splitmix(seed ^ 0xB12, n) % np.uint64(5) == 0)
         H2 = bv.proposal_hash(b"other" + raw, round_)
         h2col = np.tile(np.frombuffer(H2, dtype=np.uint8), (len(bad), 1))
-        outsider, _, _ = _sign(bv, secret_keys(seed, len(bad), salt=0x5EED), hcol[: len(bad)])   # keys of no validator
-        other, _, _ = _sign(bv, sk[bad], h2col) if len(bad) else (np.zeros((0, 65), np.uint8), None, None)
+        outsider, _, _ = _sign(bv, secret_keys(seed, len(bad), salt=0x5EED), hcol[: len(bad)], nonce=nonce)   # keys of no validator
+        other, _, _ = _sign(bv, sk[bad], h2col, nonce=nonce) if len(bad) else (np.zeros((0, 65), np.uint8), None, None)
         rnd = _splitmix(seed ^ 0xABCD, 9 * len(bad)).view(np.uint8).reshape(len(bad), 72)
         for j, i in enumerate(bad):
             kind = CORRUPTIONS[j % len(CORRUPTIONS)]
@@ -115,12 +116,12 @@ def make_round(bv, n: int, seed: int = 1, *, byzantine: bool = False, weighted: 
     return DeviceRound(n, raw, round_, H, addrs, power, hash32, seal, signer, pre if byzantine else None, expect, kinds)
 
 
-def _sign(bv, sk, hcol, chunk: int | None = None):
-    """ibft_sign_seals in pieces of at most the context's max_rows"""
+def _sign(bv, sk, hcol, chunk: int | None = None, nonce: str = "keccak"):
+    """ibft_sign_seals (nonce = "keccak") / ibft_sign_seals_ex in pieces of at most the context's max_rows"""
     chunk = chunk or int(bv.max_rows)
     sigs, signers, oks = [], [], []
     for lo in range(0, len(sk), chunk):
-        s, a, ok = bv.sign_seals(sk[lo:lo + chunk], hcol[lo:lo + chunk])
+        s, a, ok = bv.sign_seals(sk[lo:lo + chunk], hcol[lo:lo + chunk], nonce=nonce)
         sigs.append(s); signers.append(a); oks.append(ok)
     if not sigs:
         return np.zeros((0, 65), np.uint8), np.zeros((0, 20), np.uint8), np.zeros(0, bool)

@@ -25,6 +25,8 @@ FLAG_STRICT_LOW_S = 1
 FLAG_PUBKEY_CACHE = 2   # warm path: verify against per-validator tables once a key has been recovered
 ROW_NIL, ROW_BADLEN, ROW_HASH_BAD = 1, 2, 4
 KERNEL_AUTO, KERNEL_LANE, KERNEL_WAVE = 0, 1, 2
+SIGN_NONCE_KECCAK, SIGN_NONCE_RFC6979 = 0, 1   # IBFT_SIGN_NONCE_*
+SIGN_NONCES = {"keccak": SIGN_NONCE_KECCAK, "rfc6979": SIGN_NONCE_RFC6979}
 
 EXPORTS = [
     "ibft_version", "ibft_strerror", "ibft_last_error", "ibft_ctx_create", "ibft_ctx_destroy",
@@ -49,10 +51,11 @@ EXPORTS = [
     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
+    "ibft_sign_seals_ex",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
-# (ibft_set_validator_sets …, the two _sets block calls) came without a version step: an
+# (ibft_set_validator_sets …, the two _sets block calls) and ibft_sign_seals_ex came without a version step: an
 # older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
 EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
 OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
@@ -61,7 +64,8 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_recover_seals", "ibft_recover_block_seals",
                     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
                     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
-                    "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets"}
+                    "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
+                    "ibft_sign_seals_ex"}
 COMM_ID_BYTES = 128
 E_RCCL = -8
 
@@ -197,6 +201,8 @@ def load_library() -> C.CDLL:
         L.ibft_pipeline_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if hasattr(L, "ibft_verify_block_seals"):
         L.ibft_verify_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_sign_seals_ex"):
+        L.ibft_sign_seals_ex.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
     if hasattr(L, "ibft_recover_seals"):
         L.ibft_recover_seals.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Tally)]
     if hasattr(L, "ibft_recover_block_seals"):
@@ -1054,8 +1060,14 @@ class BatchVerifier:
         self._chk(self._L.ibft_seals_run(self._h, _p(self._run_mask), C.byref(t)), "ibft_seals_run")
         return mask_to_bool(self._run_mask, n), t
 
-    def sign_seals(self, sk32, hash32):
-        """ibft_sign_seals (simulators only): (sig65 u8[n,65], signer20 u8[n,20], ok bool[n]); leaves the batch staged"""
+    def sign_seals(self, sk32, hash32, nonce="keccak"):
+        """ibft_sign_seals (simulators only): (sig65 u8[n,65], signer20 u8[n,20], ok bool[n]); leaves the batch staged.
+        nonce: "keccak" (the library's own rule, the default) or "rfc6979" (ibft_sign_seals_ex: RFC 6979 §3.2 with
+        bits2octets(h1) = h1 mod n — the seals btcec / bitcoinjs produce for the same key and digest)"""
+        if nonce not in SIGN_NONCES:
+            raise ValueError(f"nonce must be one of {sorted(SIGN_NONCES)}, not {nonce!r}")
+        if nonce != "keccak" and not hasattr(self._L, "ibft_sign_seals_ex"):
+            raise GpuUnavailable("this build of the library has no ibft_sign_seals_ex — rebuild")
         sk = np.ascontiguousarray(sk32, dtype=np.uint8).reshape(-1, 32)
         hs = np.ascontiguousarray(hash32, dtype=np.uint8).reshape(-1, 32)
         n = len(sk)
@@ -1064,7 +1076,11 @@ class BatchVerifier:
         sig = np.zeros((n, 65), dtype=np.uint8)
         signer = np.zeros((n, 20), dtype=np.uint8)
         ok = np.zeros(n, dtype=np.uint8)
-        self._chk(self._L.ibft_sign_seals(self._h, _p(sk), _p(hs), n, _p(sig), _p(signer), _p(ok)), "ibft_sign_seals")
+        if nonce == "keccak":
+            self._chk(self._L.ibft_sign_seals(self._h, _p(sk), _p(hs), n, _p(sig), _p(signer), _p(ok)), "ibft_sign_seals")
+        else:
+            self._chk(self._L.ibft_sign_seals_ex(self._h, _p(sk), _p(hs), n, SIGN_NONCES[nonce], _p(sig), _p(signer), _p(ok)),
+                      "ibft_sign_seals_ex")
         self._staged = n
         return sig, signer, ok.astype(bool)
 

@@ -45,7 +45,9 @@
  *                           handleRoundChangeMessage ask about the messages NESTED in PREPREPARE / ROUND_CHANGE
  *                           messages (core/ibft.go:470-551, 683-788), from the transport's bytes
  *   ibft_comm_*, ibft_group_*  validator shards over several MI355X, one RCCL all-reduce inside the library
- *   ibft_sign_seals      <- n × Backend.BuildCommitMessage's seal (core/backend.go:12-34), simulators only
+ *   ibft_sign_seals, ibft_sign_seals_ex
+ *                        <- n × Backend.BuildCommitMessage's seal (core/backend.go:12-34), simulators only (_ex: with
+ *                           RFC 6979 nonces, the seals third-party signers reproduce)
  *   ibft_pinned_alloc    page-locked column buffers the device reads itself (one gather launch per call)
  *
  * Conventions (the reference fixes none of the arithmetic; these are the
@@ -800,12 +802,35 @@ int ibft_verify_certificates_wire(ibft_ctx *ctx, const uint8_t *wire, const uint
  * key.  out_signer20 and out_ok may be NULL; out_ok[i] = 0 (zero signature, zero address) for a refused key.
  * The nonce is deterministic: k = keccak256(sk ‖ hash ‖ LE32(ctr)) mod n with the first usable ctr
  * (go-ibft_amd/csrc/sign_dev.h) — the CPU oracle's rule, so device seals are byte-identical to the
- * oracle's; it is not RFC 6979.  NOT for a production validator's key: keys cross PCIe in the clear and sit
+ * oracle's; it is not RFC 6979 (ibft_sign_seals_ex has that rule).  NOT for a production validator's key: keys cross PCIe in the clear and sit
  * in HBM for the duration of the call (the column is zeroed before the call returns), and the kernel is not
  * written to be constant-time.  On return the batch is STAGED (hash32 / sig65 / signer20 columns are resident
  * exactly as after ibft_seals_stage): ibft_seals_run verifies what was just signed without another upload.  */
 int ibft_sign_seals(ibft_ctx *ctx, const uint8_t *sk32, const uint8_t *hash32, size_t n, uint8_t *out_sig65,
                     uint8_t *out_signer20, uint8_t *out_ok);
+/* The same under a chosen nonce rule; ibft_sign_seals is ibft_sign_seals_ex(…, IBFT_SIGN_NONCE_KECCAK, …).  Everything said
+ * above holds for both rules: the seal-digest convention is applied first (the digest a rule sees is the digest the seal
+ * signs), the batch is staged on return, the key column is zeroed before the call returns, a refused key gives ok = 0 with a
+ * zero signature and a zero address, n = 0 is legal, and the key-handling warning applies word for word.
+ *   IBFT_SIGN_NONCE_KECCAK   k = keccak256(sk ‖ digest ‖ LE32(ctr)) mod n — this library's own rule (and its oracle's).
+ *   IBFT_SIGN_NONCE_RFC6979  RFC 6979 §3.2 with HMAC-SHA-256 on the device (hlen = qlen = 256): x = sk32 as given,
+ *                            h1 = the digest, bits2octets(h1) = h1 mod n; K = 0x00…, V = 0x01…; two rounds of
+ *                            K = HMAC_K(V ‖ 0x00 / 0x01 ‖ x ‖ h1 mod n), V = HMAC_K(V); a candidate is V = HMAC_K(V) read as a
+ *                            big-endian integer; after an unusable one K = HMAC_K(V ‖ 0x00), V = HMAC_K(V).  No additional
+ *                            data (no k' variant).  A candidate is usable when 0 < k < n, r = R.x with 0 < r < n, and s ≠ 0.
+ *                            This is what btcec, bitcoinjs and the published secp256k1 RFC 6979 vectors use: such a signer
+ *                            reproduces these seals byte for byte (r ‖ s low-s ‖ v).
+ * What it is not, as far as the maintainers know: libsecp256k1's nonce_function_rfc6979 feeds the 32 message bytes
+ * UNREDUCED into the DRBG, and libsecp256k1 returns recovery ids 2 and 3 for R.x ≥ n where this signer takes the next
+ * candidate.  The two therefore agree except for a digest ≥ n or an R.x ≥ n, each of probability ≈ 2^-128 for a hash.  This
+ * has NOT been checked against a libsecp256k1 build: none was available where this was written.
+ * Checks, in this order: IBFT_E_INVAL for a NULL ctx or a NULL sk32 / hash32 / out_sig65 with n > 0; IBFT_E_INVAL for an
+ * unknown `nonce` (ibft_last_error names it); IBFT_E_TOOBIG for n > max_rows.  A refused call writes nothing to the out
+ * buffers and leaves the staged batch as it was.  No new ibft_version(): a build without the symbol simply lacks it. */
+#define IBFT_SIGN_NONCE_KECCAK  0u  /* ibft_sign_seals' rule */
+#define IBFT_SIGN_NONCE_RFC6979 1u
+int ibft_sign_seals_ex(ibft_ctx *ctx, const uint8_t *sk32, const uint8_t *hash32, size_t n, uint32_t nonce,
+                       uint8_t *out_sig65, uint8_t *out_signer20, uint8_t *out_ok);
 /* Block the host until the context's stream is idle.                               */
 int ibft_sync(ibft_ctx *ctx);
 /* Device canary (diagnostic; no reference counterpart — a Backend may log it at start-up and a bench line carries it):

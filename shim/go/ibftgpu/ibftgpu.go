@@ -1041,6 +1041,27 @@ func (c *Ctx) SignSeals(sk, hashes []byte) (seals, signers, ok []byte, err error
 	return seals, signers, ok, c.check(rc)
 }
 
+// Nonce rules of SignSealsNonce (IBFT_SIGN_NONCE_*).
+const (
+	SignNonceKeccak  uint32 = C.IBFT_SIGN_NONCE_KECCAK  // SignSeals' rule: keccak256(sk ‖ digest ‖ ctr) mod n
+	SignNonceRFC6979 uint32 = C.IBFT_SIGN_NONCE_RFC6979 // RFC 6979 §3.2, HMAC-SHA-256, bits2octets(h1) = h1 mod n (btcec's seals)
+)
+
+// SignSealsNonce = SignSeals under a chosen nonce rule (ibft_sign_seals_ex): with SignNonceRFC6979 the seals are the ones
+// btcec / bitcoinjs produce for the same key and digest, so a rig can compare simulated validators with real ones.
+// Everything SignSeals says holds; an unknown rule is refused (the error names it).
+func (c *Ctx) SignSealsNonce(sk, hashes []byte, nonce uint32) (seals, signers, ok []byte, err error) {
+	n := len(sk) / 32
+	if n == 0 || len(hashes) != 32*n {
+		return nil, nil, nil, ErrFallback
+	}
+	seals, signers, ok = make([]byte, 65*n), make([]byte, 20*n), make([]byte, n)
+	rc := C.ibft_sign_seals_ex(c.h, (*C.uint8_t)(unsafe.Pointer(&sk[0])), (*C.uint8_t)(unsafe.Pointer(&hashes[0])),
+		C.size_t(n), C.uint32_t(nonce), (*C.uint8_t)(unsafe.Pointer(&seals[0])), (*C.uint8_t)(unsafe.Pointer(&signers[0])),
+		(*C.uint8_t)(unsafe.Pointer(&ok[0])))
+	return seals, signers, ok, c.check(rc)
+}
+
 // Group is one process driving several MI355X (ibft_group_*): the rows of a batch are sharded over the
 // devices in 64-aligned ranges and ONE RCCL all-reduce inside the library merges the verdict words and the
 // ranks' distinct-sender bitmaps (a validator with valid rows in two shards is counted once, as HasQuorum's
