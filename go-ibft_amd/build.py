@@ -198,6 +198,20 @@ def build_row_keccak_harness(force: bool = False) -> str:
     return ROW_KECCAK_HARNESS
 
 
+ROW_SCALARS_HARNESS = os.path.join(CSRC, "libdev_row_scalars_host.so")
+
+
+def build_row_scalars_harness(force: bool = False) -> str:
+    """TEST-ONLY: wv::row_scalars (the scalar stage of the row forms, one multiplication for both halves of a row) on the CPU through wave_emul.h."""
+    deps = ["host_row_scalars_harness.hip", "wave_fe_dev.h", "wave_emul.h", "recover_dev.h", "verify_dev.h",
+            "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h"]
+    if force or _stale(ROW_SCALARS_HARNESS, deps):
+        subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
+                               "-o", ROW_SCALARS_HARNESS, os.path.join(CSRC, "host_row_scalars_harness.hip")], cwd=CSRC)
+        _mark(ROW_SCALARS_HARNESS, deps)
+    return ROW_SCALARS_HARNESS
+
+
 PROPOSAL_DIGEST_HARNESS = os.path.join(CSRC, "libdev_proposal_digest_host.so")
 
 

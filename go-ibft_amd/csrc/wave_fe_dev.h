@@ -16,7 +16,8 @@
 //
 // Contents: cross-lane primitives · wfe_mul / linear ops · row ↔ lane layout · group law per row ·
 // √ chain riding on the 3-row prefix doublings · modinv_wave (safegcd, limbs over lanes) ·
-// recover_pubkey_wave (cold path) · verify_known_wave (warm path) · the row-per-signature recover, whose address hash is
+// recover_pubkey_wave (cold path) · verify_known_wave (warm path) · the row-per-signature recover with its scalar stage
+// (row_scalars: the two halves of a row compute different numbers), whose address hash is
 // keccak_row_dev.h (the Keccak state over the lanes of a row).  DESIGN.md §4 has the measurements.
 //
 // RULE: a cross-lane primitive must never sit under lane-dependent control flow (`c ? f(dpp) : x` with
@@ -92,6 +93,18 @@ HD uint32_t row_bcast(uint32_t v) {
 #elif defined(IBFT_WAVE_EMUL)
   const int l = wave_emul::lane();
   return wave_emul::xchg(v, (l & ~15) + N, 0x300u + N);
+#else
+  return v;
+#endif
+}
+// lane k of a row ← lane (k − N) mod 16 of that row (N = 8: the two halves of a row change places)
+template <int N>
+HD uint32_t row_ror(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x120 + N, 0xF, 0xF, true);
+#elif defined(IBFT_WAVE_EMUL)
+  const int l = wave_emul::lane();
+  return wave_emul::xchg(v, (l & ~15) | ((l - N) & 15), 0x800u + N);
 #else
   return v;
 #endif
@@ -1225,12 +1238,103 @@ WVF wjac rows_fixed_base(const uint32_t *__restrict__ gtab, const u256 &u1, cons
   return accg;
 }
 
+// ---- the scalar stage of the row forms: r⁻¹ mod n, u1 = −z/r, u2 = s/r, u2 = k1 + k2·λ -------------------------------
+// The scalar code is lane-layout code (a whole scalar per lane), so the sixteen lanes of a row would all compute the same
+// numbers.  Here the two HALVES of a row compute different ones: lanes li < 8 multiply s by r⁻¹, lanes li ≥ 8 multiply z —
+// ONE multiplication modulo n and ONE canonicalisation give u2 in the lower half and z/r in the upper — and the split of
+// u2 runs the same way: c1 = round(u2·g1/2^384) with its two products in the lower half, c2 with its two in the upper, one
+// exchange across the halves (row_ror<8>) before the subtractions.  What differs between the halves is DATA chosen by a
+// select (a factor, a constant, a carry-in), never control flow: sc_mul is an outlined call and the broadcasts are
+// cross-lane primitives, both need the whole wavefront.
+template <int N>
+WVF u256 row_bcast256(const u256 &a) {
+  u256 r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = row_bcast<N>(a.v[i]);
+  return r;
+}
+WVF u256 row_ror256(const u256 &a) {  // the halves of the row change places
+  u256 r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = row_ror<8>(a.v[i]);
+  return r;
+}
+// every lane of the row: the split of u2 (u2 in [0, n), the same in every lane of the row).  The integers are those of
+// secp::sc_split_lambda: k2 = c1·|b1| − c2·a1 comes out of the lower half, k1 = u2 − (c1·a1 + c2·a2) out of the upper.
+WVF secp::glv_split row_split_lambda(const u256 &u2, const wk &k) {
+  const uint32_t A1[5] = {0x284EB15u, 0x3243924u, 0x2BCDE86u, 0x0869F51u, 0x03086D2u};   // a1 = b2
+  const uint32_t B1M[5] = {0x2BFE4C3u, 0x11FEA42u, 0x08286F5u, 0x358043Au, 0x0E4437Eu};  // −b1
+  const uint32_t A2[5] = {0x144CFD8u, 0x0442367u, 0x33F657Cu, 0x3DEA38Bu, 0x114CA50u};   // a2 (129 bits)
+  const bool lo = k.li < 8;
+  const secp::sc c = secp::mul_shift_384(secp::sc_from_u256(u2), secp::l26_select(lo, secp::GLV_CONST(4), secp::GLV_CONST(5)));
+  uint32_t own[5];
+#pragma unroll
+  for (int i = 0; i < 5; i++) own[i] = lo ? B1M[i] : A2[i];
+  const u256 keep = secp::mul_c_by_const(c, own);           // lower: c1·|b1|   upper: c2·a2
+  const u256 give = row_ror256(secp::mul_c_by_const(c, A1));  // lower: c2·a1 (the upper half's)   upper: c1·a1 (the lower half's)
+  // lower: keep − give = k2     upper: keep + give, then u2 − that = k1     (all modulo 2^256, two's complement)
+  const uint32_t inv = lo ? 0xFFFFFFFFu : 0u;
+  uint32_t cy = lo ? 1u : 0u;
+  u256 t, k1w;
+#pragma unroll
+  for (int i = 0; i < 8; i++) t.v[i] = secp::addc(keep.v[i], give.v[i] ^ inv, cy);
+  secp::sub256(k1w, u2, t);
+  const u256 w = secp::select(lo, t, k1w);
+  const bool neg = (w.v[7] >> 31) != 0;
+  u256 nw;
+  secp::sub256(nw, secp::zero256(), w);
+  const u256 mag = secp::select(neg, nw, w);
+  secp::glv_split sp;
+  sp.k1 = sp.k2 = secp::zero256();
+#pragma unroll
+  for (int i = 0; i < 4; i++) {  // both magnitudes are below 2^128
+    sp.k1.v[i] = row_bcast<8>(mag.v[i]);
+    sp.k2.v[i] = row_bcast<0>(mag.v[i]);
+  }
+  const uint32_t nb = neg ? 1u : 0u;
+  sp.neg1 = row_bcast<8>(nb) != 0;
+  sp.neg2 = row_bcast<0>(nb) != 0;
+  return sp;
+}
+struct row_scalars_out {
+  u256 u1;
+  secp::glv_split sp;
+  uint32_t keep;  // (what a launch cut short inside this stage keeps alive: the STOP variants 21 and 22)
+};
+struct no_handover {
+  HD void operator()(const secp::glv_split &) const {}
+};
+// Every lane of a row gets u1 and the split of u2.  `handover(sp)` runs as soon as the split is known and BEFORE u1 is made
+// row-wide: the helper wavefront of a pair publishes the split there and passes barrier 1, so that its main wavefront
+// waits for nothing it does not use.  STOP = 21 ends behind r⁻¹, STOP = 22 behind u1 and u2 (stage timing only).
+template <int STOP = 99, class HANDOVER = no_handover>
+WVF row_scalars_out row_scalars(const u256 &z_raw, const u256 &r, const u256 &s, const wk &k, HANDOVER handover = HANDOVER()) {
+  row_scalars_out o;
+  o.u1 = o.sp.k1 = o.sp.k2 = secp::zero256();
+  o.sp.neg1 = o.sp.neg2 = false;
+  const secp::sc rinv = secp::sc_from_u256(modinv_wave<secp::ModN>(r, k));
+  o.keep = rinv.n[0] ^ rinv.n[9];
+  if constexpr (STOP != 21) {
+    // lower half: s·r⁻¹ = u2     upper half: z·r⁻¹ = −u1
+    const u256 h = secp::sc_canon(secp::sc_mul(secp::sc_from_u256(secp::select(k.li < 8, s, z_raw)), rinv));
+    const u256 u2 = row_bcast256<0>(h);
+    if constexpr (STOP != 22) {
+      o.sp = row_split_lambda(u2, k);
+      handover(o.sp);
+    }
+    o.u1 = secp::sc_neg_canon(row_bcast256<8>(h));
+    o.keep = o.u1.v[0] ^ u2.v[3];
+  }
+  return o;
+}
+
 // TWO WAVEFRONTS PER FOUR SIGNATURES (2 048 < n ≤ 4 096, where the single form runs one wavefront per SIMD).  PAIR = true
 // is the MAIN wavefront: R′, the window tables (they need only R′), barrier 1, the digits of the split scalars from `sh`,
 // the main loop, barrier 2, u1·G from `sh`, the closing chain, Keccak.  The HELPER wavefront (recover_helper_row) computes
 // what the u2·R chain does not wait for — r⁻¹ mod n, u1, u2, the GLV split, then the sixteen fixed-base additions — for
 // the same four rows, on the same SIMD, meanwhile.  The hand-over holds exactly the values the single form computes
-// itself, by the same code, so the verdicts are the same, rare rows included.
+// itself, by the same code (row_scalars, rows_fixed_base), so the verdicts are the same, rare rows included.  The split
+// is all the main wavefront waits for at barrier 1: row_scalars hands it over before u1 is finished.
 struct rows_pair_shared {
   uint32_t sc[4][9];                          // per row: |k1| (4 words), |k2| (4 words), signs (bit 0: k1 < 0, bit 1: k2 < 0)
   uint32_t gx[64], gy[64], gz[64], ginf[64];  // u1·G in the row layout, per lane
@@ -1273,12 +1377,11 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
   if constexpr (PAIR) {
     u1 = secp::zero256();  // (the helper's; named here by the STOP variants only)
   } else {
-    const secp::sc rinv = secp::sc_from_u256(modinv_wave<secp::ModN>(r, k));
-    WV_STAGE(21, skeep ^ rinv.n[0] ^ rinv.n[9])
-    u1 = secp::sc_neg_canon(secp::sc_canon(secp::sc_mul(secp::sc_from_u256(z_raw), rinv)));
-    const u256 u2 = secp::sc_canon(secp::sc_mul(secp::sc_from_u256(s), rinv));
-    WV_STAGE(22, skeep ^ u1.v[0] ^ u2.v[3])
-    sp = secp::sc_split_lambda(u2);
+    const row_scalars_out rs = row_scalars<STOP>(z_raw, r, s, k);
+    WV_STAGE(21, skeep ^ rs.keep)
+    WV_STAGE(22, skeep ^ rs.keep)
+    u1 = rs.u1;
+    sp = rs.sp;
     WV_STAGE(2, skeep ^ u1.v[0] ^ sp.k1.v[0] ^ sp.k2.v[1])
     digits();
   }
@@ -1410,27 +1513,27 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
 #undef WV_STAGE
 }
 
-// The HELPER wavefront of a rows pair (see rows_pair_shared): for the same four rows as its main wavefront, r⁻¹ mod n, u1,
-// u2 and the GLV split of u2 → `sh`, barrier 1; then u1·G (rows_fixed_base) → `sh`, barrier 2.
+// The HELPER wavefront of a rows pair (see rows_pair_shared): for the same four rows as its main wavefront, r⁻¹ mod n, u2
+// and the GLV split of u2 → `sh`, barrier 1 (inside row_scalars, ahead of u1's last steps); then u1·G (rows_fixed_base) →
+// `sh`, barrier 2.  Every wavefront that gets here passes both barriers, whatever its rows are.
 template <class SYNC>
 WVF void recover_helper_row(const uint32_t *__restrict__ gtab, const u256 &z_raw, const u256 &r, const u256 &s,
                             rows_pair_shared *sh, SYNC sync) {
   const wk k = wk_init();
-  const secp::sc rinv = secp::sc_from_u256(modinv_wave<secp::ModN>(r, k));
-  const u256 u1 = secp::sc_neg_canon(secp::sc_canon(secp::sc_mul(secp::sc_from_u256(z_raw), rinv)));
-  const u256 u2 = secp::sc_canon(secp::sc_mul(secp::sc_from_u256(s), rinv));
-  const secp::glv_split sp = secp::sc_split_lambda(u2);
-  if (k.li == 0) {
-    uint32_t *sr = sh->sc[k.row];
+  // the main wavefront waits for the split alone: it is published, and barrier 1 passed, before u1 is finished
+  const row_scalars_out rs = row_scalars(z_raw, r, s, k, [&](const secp::glv_split &sp) {
+    if (k.li == 0) {
+      uint32_t *sr = sh->sc[k.row];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-      sr[i] = sp.k1.v[i];
-      sr[4 + i] = sp.k2.v[i];
+      for (int i = 0; i < 4; i++) {
+        sr[i] = sp.k1.v[i];
+        sr[4 + i] = sp.k2.v[i];
+      }
+      sr[8] = (sp.neg1 ? 1u : 0u) | (sp.neg2 ? 2u : 0u);
     }
-    sr[8] = (sp.neg1 ? 1u : 0u) | (sp.neg2 ? 2u : 0u);
-  }
-  sync();  // barrier 1
-  const wjac accg = rows_fixed_base<true>(gtab, u1, k);
+    sync();  // barrier 1
+  });
+  const wjac accg = rows_fixed_base<true>(gtab, rs.u1, k);
   const uint32_t l = lane_id();
   sh->gx[l] = accg.x;
   sh->gy[l] = accg.y;
