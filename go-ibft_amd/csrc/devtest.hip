@@ -482,3 +482,87 @@ extern "C" int devtest_rfc6979(int n, int m, const uint8_t *sk, const uint8_t *d
   (void)hipFree(ds); (void)hipFree(dd); (void)hipFree(dout);
   return rc;
 }
+
+// ---- the level scans of the certificate tree (cert_scan_dev.h) on a caller's count column ----
+// Either form at any size, through the product's own launch helper, in buffers with sentinel cells around everything the
+// kernels may write (tests/test_gpu_cert_scan.py).
+#include <stddef.h>
+#include <string.h>
+
+#include <vector>
+
+#include "cert_scan_dev.h"
+
+extern "C" uint32_t devtest_cert_scan_threshold(void) { return ibftk::CERT_SCAN_ONE_GROUP_MAX; }
+
+// tiled = 0: cert_scan_kernel, 1: the three tile kernels.  child_count: n words (bit 31 = deferred).  Out: first_child of rows
+// [lo, lo + n) (n words), cells [slot_base, slot_base + n) of deferred_rows (n words; those behind the deferred rows still hold
+// the sentinel 0xA5A5A5A5), total_dev[2], total_host[2] (pinned host words the kernels write directly; left alone and passed as
+// null when with_total_host = 0).  *sentinels_changed: bit 0 nodes [0, lo), 1 nodes behind lo + n, 2 another field than
+// first_child of a node in between, 3 deferred_rows [0, slot_base), 4 deferred_rows behind the deferred rows, 5 tile cells
+// behind the level's tiles, 6 the words behind either pair of totals.  Returns 0, -3 (arguments), or the HIP status that failed.
+extern "C" int devtest_cert_scan(int tiled, uint32_t n, const uint32_t *child_count, uint32_t lo, uint32_t base, uint32_t slot_base,
+                                 int with_total_host, uint32_t *first_child, uint32_t *deferred_rows, uint32_t *total_dev,
+                                 uint32_t *total_host, uint32_t *sentinels_changed) {
+  constexpr uint32_t PAD = 64, FILL = 0xA5A5A5A5u;
+  if (!n || !child_count || !first_child || !deferred_rows || !total_dev || !total_host || !sentinels_changed) return -3;
+  if ((uint64_t)lo + n + PAD > 0x7FFFFFFFull || (uint64_t)slot_base + n + PAD > 0x7FFFFFFFull) return -3;
+  const size_t n_nodes = (size_t)lo + n + PAD, n_slots = (size_t)slot_base + n + PAD, n_tiles = (size_t)ibftk::cert_scan_tiles(n) + PAD;
+  uint32_t deferred = 0;
+  for (uint32_t i = 0; i < n; i++) deferred += child_count[i] >> 31;
+  uint32_t *d_count = nullptr, *d_slots = nullptr, *d_total = nullptr, *h_total = nullptr;
+  wire::node_info *d_nodes = nullptr;
+  uint2 *d_tiles = nullptr;
+  std::vector<wire::node_info> nodes(n_nodes);
+  std::vector<uint32_t> slots(n_slots), tiles(2 * n_tiles), totals(PAD);
+  uint32_t changed = 0;
+  hipError_t e = hipSuccess;
+#define SCAN_TRY(call)                     \
+  if ((e = (call)) != hipSuccess) goto out
+  SCAN_TRY(hipMalloc(&d_count, (size_t)n * 4));
+  SCAN_TRY(hipMalloc(&d_nodes, n_nodes * sizeof(wire::node_info)));
+  SCAN_TRY(hipMalloc(&d_slots, n_slots * 4));
+  SCAN_TRY(hipMalloc(&d_tiles, n_tiles * 8));
+  SCAN_TRY(hipMalloc(&d_total, PAD * 4));
+  SCAN_TRY(hipHostMalloc((void **)&h_total, PAD * 4));
+  SCAN_TRY(hipMemcpy(d_count, child_count, (size_t)n * 4, hipMemcpyHostToDevice));
+  SCAN_TRY(hipMemset(d_nodes, 0xA5, n_nodes * sizeof(wire::node_info)));
+  SCAN_TRY(hipMemset(d_slots, 0xA5, n_slots * 4));
+  SCAN_TRY(hipMemset(d_tiles, 0xA5, n_tiles * 8));
+  SCAN_TRY(hipMemset(d_total, 0xA5, PAD * 4));
+  memset(h_total, 0xA5, PAD * 4);
+  {
+    uint32_t *host_words = nullptr;
+    if (with_total_host) SCAN_TRY(hipHostGetDevicePointer((void **)&host_words, h_total, 0));
+    ibftk::cert_scan_launch(nullptr, !tiled, d_count, d_nodes, lo, n, base, slot_base, d_slots, d_tiles, d_total, host_words);
+  }
+  SCAN_TRY(hipGetLastError());
+  SCAN_TRY(hipDeviceSynchronize());
+  SCAN_TRY(hipMemcpy(nodes.data(), d_nodes, n_nodes * sizeof(wire::node_info), hipMemcpyDeviceToHost));
+  SCAN_TRY(hipMemcpy(slots.data(), d_slots, n_slots * 4, hipMemcpyDeviceToHost));
+  SCAN_TRY(hipMemcpy(tiles.data(), d_tiles, n_tiles * 8, hipMemcpyDeviceToHost));
+  SCAN_TRY(hipMemcpy(totals.data(), d_total, PAD * 4, hipMemcpyDeviceToHost));
+#undef SCAN_TRY
+  for (size_t k = 0; k < n_nodes; k++) {
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(&nodes[k]);
+    const bool inside = k >= lo && k < (size_t)lo + n;
+    for (size_t j = 0; j < sizeof(wire::node_info) / 4; j++)
+      if (w[j] != FILL && !(inside && j == offsetof(wire::node_info, first_child) / 4)) changed |= inside ? 4u : k < lo ? 1u : 2u;
+    if (inside) first_child[k - lo] = nodes[k].first_child;
+  }
+  for (size_t k = 0; k < n_slots; k++)
+    if (slots[k] != FILL && (k < slot_base || k >= (size_t)slot_base + deferred)) changed |= k < slot_base ? 8u : 16u;
+  memcpy(deferred_rows, slots.data() + slot_base, (size_t)n * 4);
+  for (size_t k = tiled ? 2 * (size_t)ibftk::cert_scan_tiles(n) : 0; k < 2 * n_tiles; k++)
+    if (tiles[k] != FILL) changed |= 32u;
+  for (uint32_t k = 2; k < PAD; k++)
+    if (totals[k] != FILL || h_total[k] != FILL) changed |= 64u;
+  if (!with_total_host && (h_total[0] != FILL || h_total[1] != FILL)) changed |= 64u;
+  total_dev[0] = totals[0], total_dev[1] = totals[1];
+  if (with_total_host) total_host[0] = h_total[0], total_host[1] = h_total[1];
+  *sentinels_changed = changed;
+out:
+  (void)hipFree(d_count); (void)hipFree(d_nodes); (void)hipFree(d_slots); (void)hipFree(d_tiles); (void)hipFree(d_total);
+  if (h_total) (void)hipHostFree(h_total);
+  return (int)e;
+}

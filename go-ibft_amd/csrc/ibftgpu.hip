@@ -3935,18 +3935,8 @@ int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const 
     hipLaunchKernelGGL(ibftk::cert_walk_kernel<false>, dim3(cnt), dim3(64), 0, c->stream, d_wire, d_nodes, d_rows, (const uint2 *)d_span, lo, hi,
                        d_count);
     HIPCHK(c, hipGetLastError());
-    if (cnt <= 8192u) {
-      hipLaunchKernelGGL(ibftk::cert_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t *)d_count, d_nodes, lo, hi, hi, carriers,
-                         d_slot, d_total, c->dh_cert_total);
-    } else {  // a long level: per-tile sums, their scan, per-tile scans 
-      const uint32_t tiles = (cnt + 1023u) / 1024u;
-      uint2 *d_tiles = (uint2 *)c->d_cert_tiles.p;
-      hipLaunchKernelGGL(ibftk::cert_scan_tiles_kernel, dim3(tiles), dim3(1024), 0, c->stream, (const uint32_t *)d_count, cnt, d_tiles);
-      hipLaunchKernelGGL(ibftk::cert_scan_offsets_kernel, dim3(1), dim3(1024), 0, c->stream, d_tiles, tiles, hi, carriers, d_total,
-                         c->dh_cert_total);
-      hipLaunchKernelGGL(ibftk::cert_scan_apply_kernel, dim3(tiles), dim3(1024), 0, c->stream, (const uint32_t *)d_count, d_nodes, lo, cnt,
-                         (const uint2 *)d_tiles, d_slot);
-    }
+    ibftk::cert_scan_launch(c->stream, cnt <= ibftk::CERT_SCAN_ONE_GROUP_MAX, (const uint32_t *)d_count, d_nodes, lo, cnt, hi, carriers, d_slot,
+                            (uint2 *)c->d_cert_tiles.p, d_total, c->dh_cert_total);
     HIPCHK(c, hipGetLastError());
     if (!c->dh_cert_total) HIPCHK(c, hipMemcpyAsync(c->h_cert_total, d_total, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

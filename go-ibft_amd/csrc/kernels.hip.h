@@ -1325,7 +1325,9 @@ __global__ void wire_set_stage_kernel(const wire::row_info *__restrict__ rows, c
 //   cert_walk_kernel<false> a wavefront per message with a certificate: counts (and checks) the nested messages
 //   cert_scan_kernel        exclusive scan of the counts: every row's children become a contiguous row range of the next
 //   (cert_scan_tiles/_offsets/_apply for a long level)  level, in order, and the rows whose digest is deferred are listed;
-//                           the totals go to the host, which sizes the next level's launches
+//                           the totals go to the host, which sizes the next level's launches.  The four kernels, the
+//                           threshold between the two forms and their launch geometry live in cert_scan_dev.h (included
+//                           below, where they stood), so that the test library runs them too
 //   cert_walk_kernel<true>  the same walk again, writing the child rows
 // then, bottom-up, cert_propagate_kernel (a message with a non-canonical message below it is not canonical either),
 // cert_digest_wave_kernel (the deferred digests — messages that carry certificates, long messages — and the proposal hashes:
@@ -1411,119 +1413,10 @@ __global__ void __launch_bounds__(64) cert_walk_kernel(const uint8_t *__restrict
     child_count[row - lo] = count | (ok ? deferred : 0u);
   }
 }
-// first_child of rows [lo, hi) = base + exclusive prefix sum of their child counts; the sum → total[0] (device and host).
-// The rows whose digest is deferred (wire::tree_deferred: they carry a certificate, or are long) are listed the same way:
-// deferred_rows[slot_base + rank] = row, their count → total[1].  child_count[i] bit 31 = row lo + i is deferred.
-__global__ void __launch_bounds__(1024) cert_scan_kernel(const uint32_t *__restrict__ child_count, wire::node_info *__restrict__ nodes,
-                                                         uint32_t lo, uint32_t hi, uint32_t base, uint32_t slot_base,
-                                                         uint32_t *__restrict__ deferred_rows, uint32_t *__restrict__ total_dev,
-                                                         uint32_t *__restrict__ total_host) {
-  __shared__ uint32_t part[1024], part2[1024];
-  const uint32_t n = hi - lo, t = threadIdx.x, per = (n + 1023u) / 1024u;
-  const uint32_t b = t * per < n ? t * per : n, e = b + per < n ? b + per : n;
-  uint32_t sum = 0, sum2 = 0;
-  for (uint32_t i = b; i < e; i++) {
-    const uint32_t c = child_count[i];
-    sum += c & 0x7FFFFFFFu;
-    sum2 += c >> 31;
-  }
-  part[t] = sum;
-  part2[t] = sum2;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024u; o <<= 1) {
-    const uint32_t v = t >= o ? part[t - o] : 0u, v2 = t >= o ? part2[t - o] : 0u;
-    __syncthreads();
-    part[t] += v;
-    part2[t] += v2;
-    __syncthreads();
-  }
-  uint32_t run = base + part[t] - sum, run2 = slot_base + part2[t] - sum2;
-  for (uint32_t i = b; i < e; i++) {
-    const uint32_t c = child_count[i];
-    nodes[lo + i].first_child = run;
-    run += c & 0x7FFFFFFFu;
-    if (c >> 31) deferred_rows[run2++] = lo + i;
-  }
-  if (t == 1023u) {
-    total_dev[0] = part[1023];
-    total_dev[1] = part2[1023];
-    if (total_host) {
-      total_host[0] = part[1023];
-      total_host[1] = part2[1023];
-    }
-  }
-}
-// The same scan for a long level (the single workgroup above walks n/1024 rows per thread: 0.8 ms at 467 k rows): (A) per-tile
-// sums of 1 024 rows, (B) one workgroup scans the tile sums (≤ 1 024 tiles per pass of its loop) and delivers the totals, (C) every
-// tile scans its own rows and adds its offset.
-__global__ void __launch_bounds__(1024) cert_scan_tiles_kernel(const uint32_t *__restrict__ child_count, uint32_t n, uint2 *__restrict__ tile_sum) {
-  __shared__ uint32_t a[1024], b[1024];
-  const uint32_t t = threadIdx.x, i = blockIdx.x * 1024u + t;
-  const uint32_t c = i < n ? child_count[i] : 0u;
-  a[t] = c & 0x7FFFFFFFu;
-  b[t] = c >> 31;
-  __syncthreads();
-  for (uint32_t o = 512u; o; o >>= 1) {
-    if (t < o) {
-      a[t] += a[t + o];
-      b[t] += b[t + o];
-    }
-    __syncthreads();
-  }
-  if (t == 0) tile_sum[blockIdx.x] = make_uint2(a[0], b[0]);
-}
-__global__ void __launch_bounds__(1024) cert_scan_offsets_kernel(uint2 *__restrict__ tile_sum, uint32_t tiles, uint32_t base, uint32_t slot_base,
-                                                                 uint32_t *__restrict__ total_dev, uint32_t *__restrict__ total_host) {
-  __shared__ uint32_t a[1024], b[1024];
-  const uint32_t t = threadIdx.x;
-  uint32_t run = 0, run2 = 0;  // sums of the passes before this one (the same in every thread)
-  for (uint32_t t0 = 0; t0 < tiles; t0 += 1024u) {
-    const uint2 v = t0 + t < tiles ? tile_sum[t0 + t] : make_uint2(0, 0);
-    a[t] = v.x;
-    b[t] = v.y;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024u; o <<= 1) {
-      const uint32_t x = t >= o ? a[t - o] : 0u, y = t >= o ? b[t - o] : 0u;
-      __syncthreads();
-      a[t] += x;
-      b[t] += y;
-      __syncthreads();
-    }
-    if (t0 + t < tiles) tile_sum[t0 + t] = make_uint2(base + run + a[t] - v.x, slot_base + run2 + b[t] - v.y);  // exclusive, with the bases
-    run += a[1023];
-    run2 += b[1023];
-    __syncthreads();
-  }
-  if (t == 0) {
-    total_dev[0] = run;
-    total_dev[1] = run2;
-    if (total_host) {
-      total_host[0] = run;
-      total_host[1] = run2;
-    }
-  }
-}
-__global__ void __launch_bounds__(1024) cert_scan_apply_kernel(const uint32_t *__restrict__ child_count, wire::node_info *__restrict__ nodes,
-                                                               uint32_t lo, uint32_t n, const uint2 *__restrict__ tile_off,
-                                                               uint32_t *__restrict__ deferred_rows) {
-  __shared__ uint32_t a[1024], b[1024];
-  const uint32_t t = threadIdx.x, i = blockIdx.x * 1024u + t;
-  const uint32_t c = i < n ? child_count[i] : 0u, cnt = c & 0x7FFFFFFFu, def = c >> 31;
-  a[t] = cnt;
-  b[t] = def;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024u; o <<= 1) {
-    const uint32_t x = t >= o ? a[t - o] : 0u, y = t >= o ? b[t - o] : 0u;
-    __syncthreads();
-    a[t] += x;
-    b[t] += y;
-    __syncthreads();
-  }
-  if (i >= n) return;
-  const uint2 off = tile_off[blockIdx.x];
-  nodes[lo + i].first_child = off.x + a[t] - cnt;
-  if (def) deferred_rows[off.y + b[t] - 1u] = lo + i;
-}
+}  // namespace ibftk
+// cert_scan_kernel, cert_scan_tiles_kernel, cert_scan_offsets_kernel, cert_scan_apply_kernel and the helper that launches them
+#include "cert_scan_dev.h"
+namespace ibftk {
 __global__ void cert_propagate_kernel(const wire::node_info *__restrict__ nodes, wire::row_info *__restrict__ rows, uint32_t lo,
                                       uint32_t hi) {
   const uint32_t row = lo + blockIdx.x * blockDim.x + threadIdx.x;

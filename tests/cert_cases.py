@@ -212,6 +212,68 @@ def fuzz_batches(r, count, seed):
     return out
 
 
+# ---- long levels: more rows in one level than the single-workgroup scan takes (cert_scan_dev.h) ------------------
+# Children, and deferred rows (the message itself + those below it), of each palette entry: what the seed search used.  The
+# weights put more than 8 192 deferred rows into a tree of 8 192 draws (9/8 per draw) and keep it under 32 768 rows (13/4).
+LONG_LEVEL_WEIGHTS = (1, 2, 2, 2, 2, 4, 2, 1)
+LONG_LEVEL_SEED = 2            # with it the conditions of tests/test_cert_long_cases.py hold at 8 192 and 8 193 draws
+LONG_LEVEL_MAX_ROWS = 32768    # the context the GPU tests judge these trees with
+
+
+def long_level_round():
+    from oracle import workload as W
+    return W.make_round(8, 817, height=5, round_=1, raw_len=40)
+
+
+def long_level_palette(r):
+    """eight ROUND_CHANGE messages, each signed once: what a long level is drawn from"""
+    H, RND = 5, 2
+    big = bytes((7 * i + 3) & 0xFF for i in range(512))          # a proposal that makes its message longer than TREE_DEFER_BYTES
+    last, h1 = wire.Proposal(r.raw, 1), B.proposal_hash(r.raw, 1)
+    pm = preprepare(r, 1, H, 1)
+    forged = prepare(r, 3, H, 1, h=h1, sk=B.keccak256(b"outsider"))
+    return [
+        round_change(r, 0, H, RND).encode(),                                                       # short, nothing below: not deferred
+        round_change(r, 1, H, RND, last, pc_bytes(r, H, 1, 1, [])).encode(),                       # 1 nested message
+        round_change(r, 2, H, RND, last, pc_bytes(r, H, 1, 1, [2])).encode(),                      # 2
+        round_change(r, 3, H, RND, last, pc_bytes(r, H, 1, 1, [2, 3, 4, 5])).encode(),             # 5
+        round_change(r, 4, H, RND, wire.Proposal(big, 1), None).encode(),                          # long: deferred, no children
+        round_change(r, 5, H, RND, wire.Proposal(big, 1), pc_bytes(r, H, 1, 1, [2, 3], raw=big)).encode(),  # a deferred leaf below
+        round_change(r, 6, H, RND, last, wire.prepared_certificate(pm, [prepare(r, 2, H, 1, h=h1), forged,
+                                                                        prepare(r, 4, H, 1, h=h1)])).encode(),
+        dict(handmade(r))["unknown field in the certificate"][0],                                  # NEEDS_HOST: count 0, nothing listed
+    ]
+
+
+def long_level(r, K, seed):
+    """K messages drawn from the palette by a seeded generator (encodings repeat: the device judges rows)"""
+    pal = long_level_palette(r)
+    return [pal[i] for i in random.Random(seed).choices(range(len(pal)), weights=LONG_LEVEL_WEIGHTS, k=K)]
+
+
+_long_trees = {}
+
+
+def long_tree(shape, K):
+    """(round, the call's messages, the oracle's tree, (lo, hi) of the long level), built once per process.
+    "flat": the K messages are the batch, level 0 is the long level.  "nested": two short PREPAREs, a PREPREPARE whose
+    RoundChangeCertificate holds the K messages, a ROUND_CHANGE with an (empty) certificate — level 1 is the K messages at
+    lo = 4 behind two deferred rows of level 0, and level 2 is long again."""
+    if (shape, K) not in _long_trees:
+        r = long_level_round()
+        msgs = long_level(r, K, LONG_LEVEL_SEED)
+        span = (0, K)
+        if shape == "nested":
+            rcc = b"".join(wire._len_field(1, m, emit_empty=True) for m in msgs)
+            msgs = [prepare(r, 1, 5, 2).encode(), prepare(r, 3, 5, 2).encode(), preprepare(r, 2, 5, 2, rcc=rcc).encode(),
+                    round_change(r, 4, 5, 2, wire.Proposal(r.raw, 1), b"").encode()]
+            span = (4, 4 + K)
+        else:
+            assert shape == "flat"
+        _long_trees[(shape, K)] = (r, msgs, WC.expected_tree(msgs, r.addrs, rows_cap=LONG_LEVEL_MAX_ROWS), span)
+    return _long_trees[(shape, K)]
+
+
 # ---- comparison ------------------------------------------------------------------------------------------------
 def compare(label, exp: WC.Tree, n_rows, nodes, rows, cls, sender, hashb, selfb):
     """an implementation's answer (numpy structured arrays / bool arrays) against oracle/wire_cert.Tree"""

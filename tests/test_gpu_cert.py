@@ -12,9 +12,11 @@ from oracle import workload as W
 pytestmark = pytest.mark.gpu
 
 
-def run(bv, r, label, msgs, cap=None):
+def run(bv, r, label, msgs, cap=None, tree=None):
+    """tree: the oracle's tree of msgs where it was made before (None under a rows_cap it does not fit, as expected_tree says)"""
     buf, off = CC.pack(msgs)
-    exp = WC.expected_tree(msgs, r.addrs, rows_cap=min(cap or bv.max_rows, bv.max_rows))
+    limit = min(cap or bv.max_rows, bv.max_rows)
+    exp = WC.expected_tree(msgs, r.addrs, rows_cap=limit) if tree is None else (tree if tree.n_rows <= limit else None)
     if exp is None:
         with pytest.raises(RuntimeError, match="-7"):
             bv.verify_certificates_wire(buf, off, rows_cap=cap)
@@ -56,7 +58,10 @@ def test_longer_than_the_device_hashes(gpu_verifier):
 def test_round_change_certificate_n256(gpu_verifier):
     """BASELINE-style worst case at N = 256: a PREPREPARE whose RoundChangeCertificate holds 171 ROUND_CHANGE messages, each
     with a PreparedCertificate of 1 + 170 messages — 29 412 nested signatures from one 4.1 MB message, one call; then the
-    same with a fifth of the nested PREPAREs corrupted."""
+    same with a fifth of the nested PREPAREs corrupted.  What it covers: parsing, walking and judging a tree of that size.  What
+    it does not: the tiled scan's output.  Its only level of more than CERT_SCAN_ONE_GROUP_MAX rows is the leaf level (171²
+    messages, none deferred, no children), where first_child is not compared and both totals are 0; the levels with children have
+    1 and 171 rows.  The long levels WITH children are test_long_level* below and tests/test_gpu_cert_scan.py."""
     n = 256
     r = W.make_round(n, 815, height=5, round_=1, raw_len=256)
     gpu_verifier.set_validators(5, r.addrs, r.power)
@@ -183,4 +188,122 @@ def test_certificates_sharded_by_carrier_equal_one_call(world):
             g.verify_certificates_wire(*CC.pack(honest), rows_cap=55)
     finally:
         g.close()
+        bv.close()
+
+
+# ---- long levels: more rows with children in one level than the single-workgroup scan takes --------------------------
+# tests/cert_cases.py: long_tree (what these trees are is checked without a device in tests/test_cert_long_cases.py).
+LONG_SHAPES = ["flat", "nested"]
+
+
+@pytest.fixture(scope="module")
+def scan_threshold():
+    import ctypes as C
+    import go_ibft_amd.build as B
+    L = C.CDLL(B.build_devtest())
+    L.devtest_cert_scan_threshold.restype = C.c_uint32
+    return int(L.devtest_cert_scan_threshold())
+
+
+def run_long(bv, label, shape, K, cap=None):
+    r, msgs, tree, _ = CC.long_tree(shape, K)
+    bv.set_validators(5, r.addrs, r.power)
+    buf, off = CC.pack(msgs)
+    if cap is None or cap >= tree.n_rows:
+        # first, the scan's own output where it means something, so that a failure names the scan
+        n, nodes = bv.verify_certificates_wire(buf, off, rows_cap=cap, want_rows=False)[:2]
+        assert n == tree.n_rows, (label, "rows", n, tree.n_rows)
+        want = np.array([nd["first_child"] for nd in tree.nodes], dtype=np.int64)
+        has = np.array([nd["n_children"] > 0 for nd in tree.nodes])
+        kids = np.array([nd["n_children"] for nd in tree.nodes], dtype=np.int64)
+        assert (nodes["n_children"] == kids).all(), (label, "n_children", int(np.nonzero(nodes["n_children"] != kids)[0][0]))
+        bad = np.nonzero(has & (nodes["first_child"] != want))[0]
+        assert bad.size == 0, (label, "first_child (the level's scan)", int(bad[0]), int(nodes["first_child"][bad[0]]), int(want[bad[0]]))
+    return run(bv, r, label, msgs, cap=cap, tree=tree)
+
+
+@pytest.mark.parametrize("overlap", [None, "0"])
+@pytest.mark.parametrize("dk", [0, 1])
+@pytest.mark.parametrize("shape", LONG_SHAPES)
+def test_long_level(shape, dk, overlap, scan_threshold, monkeypatch):
+    """A level of T and of T + 1 rows with children (T = CERT_SCAN_ONE_GROUP_MAX: the single workgroup's last size, and the tiled
+    form with one row in its last tile), at row 0 of the tree and at lo = 4 / slot_base = 2, and a longer level below it; more
+    than 8 192 deferred rows, so with IBFT_CERT_OVERLAP unset their second verdict launch is a group kernel at a row base
+    (cert_carrier_stage_kernel, cert_scatter_kernel), with =0 there is one launch.  Every node field, row, class and mask
+    against the oracle."""
+    import go_ibft_amd.verifier as V
+    if overlap is None:
+        monkeypatch.delenv("IBFT_CERT_OVERLAP", raising=False)
+    else:
+        monkeypatch.setenv("IBFT_CERT_OVERLAP", overlap)
+    bv = V.BatchVerifier(max_rows=CC.LONG_LEVEL_MAX_ROWS)
+    try:
+        assert run_long(bv, f"long {shape} K=T+{dk} overlap={overlap}", shape, scan_threshold + dk) is not None
+    finally:
+        bv.close()
+
+
+@pytest.mark.parametrize("dk", [0, 1])
+@pytest.mark.parametrize("shape", LONG_SHAPES)
+def test_long_level_on_the_warm_kernels(shape, dk, scan_threshold, monkeypatch):
+    """the same trees in a key-caching context, twice: the second call judges both launches with the known-key kernels"""
+    import go_ibft_amd.verifier as V
+    monkeypatch.delenv("IBFT_CERT_OVERLAP", raising=False)
+    bv = V.BatchVerifier(flags=V.FLAG_PUBKEY_CACHE, max_rows=CC.LONG_LEVEL_MAX_ROWS)
+    try:
+        for call in range(2):
+            assert run_long(bv, f"long {shape} K=T+{dk} cached, call {call}", shape, scan_threshold + dk) is not None
+        tables, warm, cold = bv.cache_stats()
+        assert tables >= 7 and warm >= 1, (tables, warm, cold)   # validators 0 … 6 sign in these trees
+    finally:
+        bv.close()
+
+
+@pytest.mark.parametrize("dk", [0, 1])
+def test_long_level_sharded_equals_one_call(dk, scan_threshold, monkeypatch):
+    """The flat tree over three contexts: every shard's levels are short (the single-workgroup scan on each), the library
+    renumbers — field by field the answer of ONE call, whose long levels went through the tiled scan; and the oracle's tree."""
+    import go_ibft_amd.verifier as V
+    monkeypatch.delenv("IBFT_CERT_OVERLAP", raising=False)
+    r, msgs, tree, _ = CC.long_tree("flat", scan_threshold + dk)
+    cap = CC.LONG_LEVEL_MAX_ROWS
+    per = (len(msgs) + 2) // 3                                      # a shard's messages, and the rows of its level 1
+    below = [sum(tree.nodes[k]["n_children"] for k in range(lo, min(lo + per, len(msgs)))) for lo in range(0, len(msgs), per)]
+    assert len(below) == 3 and per <= scan_threshold and max(below) <= scan_threshold < sum(below)   # short on every shard, long in one call
+    bv = V.BatchVerifier(max_rows=cap)
+    g = V.DeviceGroup([0] * 3, max_rows_total=3 * cap)
+    try:
+        bv.set_validators(5, r.addrs, r.power)
+        g.set_validators(5, r.addrs, r.power)
+        buf, off = CC.pack(msgs)
+        one = bv.verify_certificates_wire(buf, off, rows_cap=cap)
+        many = g.verify_certificates_wire(buf, off, rows_cap=cap)
+        assert one[0] == many[0] == tree.n_rows
+        for name in one[1].dtype.names:
+            if name == "first_child":       # means nothing for a leaf (include/ibftgpu.h): compared where there are children
+                has = one[1]["n_children"] > 0
+                assert (one[1][name][has] == many[1][name][has]).all(), name
+                assert (many[1][name][~has] < many[0]).all(), "a leaf's first_child must stay inside the tree"
+            elif name != "pad":
+                assert (one[1][name] == many[1][name]).all(), name
+        assert one[2].tobytes() == many[2].tobytes()
+        for a, b in zip(one[3:], many[3:]):
+            assert (a == b).all()
+        CC.compare(f"long flat K=T+{dk} sharded", tree, *many)
+        CC.compare(f"long flat K=T+{dk} one call", tree, *one)
+    finally:
+        g.close()
+        bv.close()
+
+
+def test_long_level_rows_cap_edge(scan_threshold, monkeypatch):
+    """hi + total > cap with the total from cert_scan_offsets_kernel: exactly n_rows passes, one less is IBFT_E_TOOBIG"""
+    import go_ibft_amd.verifier as V
+    monkeypatch.delenv("IBFT_CERT_OVERLAP", raising=False)
+    tree = CC.long_tree("flat", scan_threshold + 1)[2]
+    bv = V.BatchVerifier(max_rows=CC.LONG_LEVEL_MAX_ROWS)
+    try:
+        assert run_long(bv, "long flat cap exactly", "flat", scan_threshold + 1, cap=tree.n_rows) is not None
+        assert run_long(bv, "long flat cap one short", "flat", scan_threshold + 1, cap=tree.n_rows - 1) is None
+    finally:
         bv.close()
