@@ -112,6 +112,7 @@ struct ibft_ctx {
   // columns in HBM
   DevBuf d_hash, d_sig, d_signer, d_pre, d_hash_len, d_payload, d_off, d_raw;
   DevBuf d_signer_out;  // the address column the emitting cold kernels write (ibft_recover_seals / ibft_recover_block_seals)
+  DevBuf d_msg_cols, d_msg_wire;  // ibft_sign_messages_wire: height ‖ round ‖ type columns in, the wire bytes out
   // the SECOND staging slot of the seal columns (ibft_seals_stage_next / ibft_seals_swap): batch k+1 is copied here on a
   // copy stream of its own while the verdict kernels read batch k from the columns above; a swap exchanges the two sets
   DevBuf d_hash_nx, d_sig_nx, d_signer_nx, d_pre_nx;
@@ -1652,7 +1653,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_bhash_nx, &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
                     &c->d_phash, &c->bs_praw[0], &c->bs_praw[1], &c->bs_proff[0], &c->bs_proff[1], &c->bs_pround[0], &c->bs_pround[1],
                     &c->bs_phash[0], &c->bs_phash[1], &c->bs_signer[0], &c->bs_signer[1], &c->bs_vidx[0], &c->bs_vidx[1], &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
-                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset})
+                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->d_msg_cols, &c->d_msg_wire})
     release(*b);
   if (c->h_phash) (void)hipHostFree(c->h_phash);
   if (c->tstream) {
@@ -2837,6 +2838,82 @@ int ibft_sign_seals_ex(ibft_ctx *c, const uint8_t *sk32, const uint8_t *hash32, 
   // the batch is staged (rows whose key was refused carry a zero signature, which every verifier rejects)
   c->staged_n = (uint32_t)n;
   c->staged_pre = false;
+  return IBFT_OK;
+}
+
+// f4 one layer up: whole PREPARE / COMMIT messages as wire bytes (sign_message_dev.h).  A row's length depends on type, height
+// and round alone, so the offsets are computed here, before anything is launched, and uploaded.
+int ibft_sign_messages_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *type, const uint64_t *height, const uint64_t *round,
+                            const uint8_t *hash32, size_t n, uint32_t nonce, uint8_t *out_wire, size_t wire_cap, uint32_t *out_off,
+                            uint8_t *out_from20, uint8_t *out_ok) {
+  if (!c || (n && (!sk32 || !type || !height || !round || !hash32 || !out_wire || !out_off))) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  if (nonce != IBFT_SIGN_NONCE_KECCAK && nonce != IBFT_SIGN_NONCE_RFC6979) {
+    c->last_error = "ibft_sign_messages_wire: unknown nonce rule " + std::to_string(nonce) +
+                    " (IBFT_SIGN_NONCE_KECCAK = 0, IBFT_SIGN_NONCE_RFC6979 = 1)";
+    return IBFT_E_INVAL;
+  }
+  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  std::vector<uint32_t> off(n + 1);
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (type[i] != ibftk::MSG_TYPE_PREPARE && type[i] != ibftk::MSG_TYPE_COMMIT) {
+      c->last_error = "ibft_sign_messages_wire: row " + std::to_string(i) + " has type " + std::to_string((unsigned)type[i]) +
+                      " (1 = PREPARE, 2 = COMMIT)";
+      return IBFT_E_INVAL;
+    }
+    off[i] = (uint32_t)total;
+    total += ibftk::message_wire_len(type[i], height[i], round[i]);
+  }
+  off[n] = (uint32_t)total;
+  if (total > wire_cap || total > 0xFFFFFFFFull) {
+    c->last_error = "ibft_sign_messages_wire: the messages take " + std::to_string(total) + " bytes, wire_cap is " + std::to_string(wire_cap);
+    return IBFT_E_TOOBIG;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->wire_valid = false;  // the columns below are the wire walker's and the seal batch's
+  c->staged_n = 0;
+  if (n == 0) {
+    if (out_off) out_off[0] = 0;
+    return IBFT_OK;
+  }
+  int rc;
+  const size_t col = (n + 7) & ~(size_t)7;  // the type bytes sit behind two 8-byte columns
+  if ((rc = ensure(c, c->d_msg_cols, 17 * col))) return rc;
+  if ((rc = ensure(c, c->d_msg_wire, (size_t)total))) return rc;
+  uint8_t *cols = (uint8_t *)c->d_msg_cols.p;
+  HIPCHK(c, hipMemcpyAsync(cols, height, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(cols + 8 * col, round, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(cols + 16 * col, type, n, hipMemcpyHostToDevice, c->stream));
+  if ((rc = upload(c, c->d_payload, sk32, n * 32))) return rc;  // the sender-payload column is free here, as in ibft_sign_seals
+  if ((rc = upload(c, c->d_hash, hash32, n * 32))) return rc;
+  if ((rc = upload(c, c->d_off, off.data(), (n + 1) * 4))) return rc;
+  ibftk::sign_message_args a;
+  a.gtab = (const uint32_t *)c->dev->d_gtab.p;
+  a.sk32 = (const uint8_t *)c->d_payload.p;
+  a.type = cols + 16 * col;
+  a.height = (const uint64_t *)cols;
+  a.round = (const uint64_t *)(cols + 8 * col);
+  a.hash32 = (const uint8_t *)c->d_hash.p;
+  a.off = (const uint32_t *)c->d_off.p;
+  a.wire = (uint8_t *)c->d_msg_wire.p;
+  a.from20 = (uint8_t *)c->d_signer.p;
+  a.ok = (uint8_t *)c->d_pre.p;
+  a.n = (uint32_t)n;
+  a.convert = c->seal_digest_mode != 0 ? 1u : 0u;  // the seal signs what the convention says it signs; the envelope never does
+  memcpy(a.suffix_words, c->seal_suffix_words, sizeof a.suffix_words);
+  const uint32_t blocks = (uint32_t)((n + ibftk::ROWS_PER_BLOCK - 1) / ibftk::ROWS_PER_BLOCK);
+  if (nonce == IBFT_SIGN_NONCE_RFC6979)
+    hipLaunchKernelGGL(ibftk::sign_message_lane_kernel<ibftk::SIGN_NONCE_RFC6979>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(ibftk::sign_message_lane_kernel<ibftk::SIGN_NONCE_KECCAK>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemsetAsync(c->d_payload.p, 0, n * 32, c->stream));  // the keys do not outlive the call in HBM
+  HIPCHK(c, hipMemcpyAsync(out_wire, c->d_msg_wire.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+  if (out_from20) HIPCHK(c, hipMemcpyAsync(out_from20, c->d_signer.p, n * 20, hipMemcpyDeviceToHost, c->stream));
+  if (out_ok) HIPCHK(c, hipMemcpyAsync(out_ok, c->d_pre.p, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(out_off, off.data(), (n + 1) * 4);
   return IBFT_OK;
 }
 

@@ -36,6 +36,7 @@
 #include "recover_dev.h"
 #include "verify_dev.h"
 #include "sign_dev.h"
+#include "sign_message_dev.h"
 #include "wave_fe_dev.h"
 #include "wire_dev.h"
 #include "cert_wave_dev.h"
@@ -233,6 +234,58 @@ __global__ void __launch_bounds__(ROWS_PER_BLOCK) sign_lane_kernel(sign_args a) 
 #pragma unroll
   for (int i = 0; i < 5; i++) ad[i] = addr[i];
   a.ok[row] = ok ? 1 : 0;
+}
+
+// ---- f4, one layer up: a whole PREPARE / COMMIT message per lane, as wire bytes (sign_message_dev.h) --------------------
+// One lane per message, one wavefront per 64 rows, as sign_lane_kernel.  off[] comes from the host (a row's length depends on
+// type, height and round only: message_wire_len), so a lane knows where its bytes go without a scan.  The payload is built in
+// LDS (152 bytes per lane) and absorbed from there: no private byte array.  Idle lanes of the last wavefront run the last row
+// again — sign_core votes across the wavefront — and store nothing.
+struct sign_message_args {
+  const uint32_t *gtab;
+  const uint8_t *sk32;      // n × 32, big-endian secret keys
+  const uint8_t *type;      // n: 1 = PREPARE, 2 = COMMIT (checked by the host)
+  const uint64_t *height;   // n
+  const uint64_t *round;    // n
+  const uint8_t *hash32;    // n × 32, the proposal hash each row carries
+  const uint32_t *off;      // n + 1: row i is wire[off[i], off[i+1])
+  uint8_t *wire;            // out
+  uint8_t *from20;          // n × 20 out
+  uint8_t *ok;              // n out: 1 = signed, 0 = key outside [1, n)
+  uint32_t n;
+  uint32_t convert;         // the seal-digest convention: 0 = the seal signs the hash itself
+  uint64_t suffix_words[9];
+};
+template <int NONCE>
+__global__ void __launch_bounds__(ROWS_PER_BLOCK) sign_message_lane_kernel(sign_message_args a) {
+  __shared__ uint64_t lds[ROWS_PER_BLOCK * SIGN_MESSAGE_BUF_WORDS];
+  const uint32_t row = blockIdx.x * (uint32_t)ROWS_PER_BLOCK + threadIdx.x;
+  const bool live = row < a.n;
+  const uint32_t src = live ? row : a.n - 1;
+  uint8_t sk[32], hs[32];
+  const uint32_t *ks = reinterpret_cast<const uint32_t *>(a.sk32 + 32ull * src);
+  const uint32_t *hp = reinterpret_cast<const uint32_t *>(a.hash32 + 32ull * src);
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    uint32_t kw = ks[i], hw = hp[i];
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      sk[4 * i + b] = (uint8_t)(kw >> (8 * b));
+      hs[4 * i + b] = (uint8_t)(hw >> (8 * b));
+    }
+  }
+  const uint32_t type = a.type[src];
+  const uint64_t height = a.height[src], round = a.round[src];
+  uint64_t *buf = lds + (size_t)SIGN_MESSAGE_BUF_WORDS * threadIdx.x;
+  const message_row m = sign_message_row<NONCE>(a.gtab, sk, type, height, round, hs, a.convert, a.suffix_words, buf);
+  if (!live) return;
+  const uint32_t at = a.off[row];
+  const bool fits = a.off[row + 1] - at == m.len + SIGN_MESSAGE_SIG_FIELD;  // (the host computed it with the same function)
+  if (fits) store_message(a.wire + at, buf, m);
+  uint32_t *ad = reinterpret_cast<uint32_t *>(a.from20 + 20ull * row);
+#pragma unroll
+  for (int i = 0; i < 5; i++) ad[i] = m.addr[i];
+  a.ok[row] = (m.ok && fits) ? 1 : 0;
 }
 
 // ---- proposal hash + a1 ---------------------------------------------------------------

@@ -90,19 +90,19 @@ struct rfc6979_drbg {
   }
 };
 
-// One row.  Returns false (and writes zeros) for a key outside [1, n) or when no nonce was usable.
-// `tries` lets the caller keep a wavefront convergent: the loop body is executed by every lane until
-// all lanes of the wavefront are done (on the device), lanes that finished discard the extra attempts.
+// One signature under the key d (sign_key: key_ok says whether it lies in [1, n); sk32 are its bytes, for the nonce).  Returns
+// false (and writes zeros) for a key outside [1, n) or when no nonce was usable.
+// The retry loop keeps a wavefront convergent: its body is executed by every lane until all lanes of the wavefront are done
+// (on the device: EVERY lane of a wavefront must call this, lanes with nothing to sign included), lanes that finished
+// discard the extra attempts.
 // NONCE: SIGN_NONCE_KECCAK (the rule above) or SIGN_NONCE_RFC6979.  reject_mask is a test seam of the RFC 6979 rule: bit t set
 // treats candidate t as unusable, which is the only way to reach the reseed step (a real retry has probability ≈2^-128); the
-// kernel passes the constant 0 and the seam folds away.
+// kernels pass the constant 0 and the seam folds away.
 template <int NONCE = SIGN_NONCE_KECCAK>
-__host__ __device__ __forceinline__ bool sign_row(const uint32_t *__restrict__ gtab, const uint8_t *sk32,
-                                                  const uint8_t *digest32, u256 &r_out, u256 &s_out, uint32_t &v_out,
-                                                  uint32_t addr[5], uint32_t reject_mask = 0) {
+__host__ __device__ __forceinline__ bool sign_core(const uint32_t *__restrict__ gtab, const uint8_t *sk32, const u256 &d, bool key_ok,
+                                                   const uint8_t *digest32, u256 &r_out, u256 &s_out, uint32_t &v_out,
+                                                   uint32_t reject_mask = 0) {
   static_assert(NONCE == SIGN_NONCE_KECCAK || NONCE == SIGN_NONCE_RFC6979, "unknown nonce rule");
-  const u256 d = secp::from_be32(sk32);
-  const bool key_ok = !secp::is_zero(d) && !secp::geq_const(d, secp::NL());
   u256 z = secp::from_be32(digest32);
   secp::sub_const_if(z, secp::geq_const(z, secp::NL()), secp::NL());  // z mod n (z < 2^256 < 2n)
   const secp::sc d_sc = secp::sc_from_u256(d);
@@ -160,7 +160,17 @@ __host__ __device__ __forceinline__ bool sign_row(const uint32_t *__restrict__ g
       done = true;
     }
   }
-  // the signer's address, keccak256(X‖Y)[12..32) of d·G — what the validator set is keyed by
+  return ok;
+}
+
+// The secret key as a number, and whether it lies in [1, n)
+__host__ __device__ __forceinline__ bool sign_key(const uint8_t *sk32, u256 &d) {
+  d = secp::from_be32(sk32);
+  return !secp::is_zero(d) && !secp::geq_const(d, secp::NL());
+}
+
+// The signer's address, keccak256(X‖Y)[12..32) of d·G — what the validator set is keyed by; zeros for a key outside [1, n).
+__host__ __device__ __forceinline__ void sign_address(const uint32_t *__restrict__ gtab, const u256 &d, bool key_ok, uint32_t addr[5]) {
   jac Q = ecmult_gen(gtab, secp::select(key_ok, d, secp::one256()), secp::jac_inf());
   aff Qa;
   (void)secp::jac_to_aff_fast(Qa, Q);
@@ -170,6 +180,17 @@ __host__ __device__ __forceinline__ bool sign_row(const uint32_t *__restrict__ g
 #pragma unroll
     for (int i = 0; i < 5; i++) addr[i] = 0;
   }
+}
+
+// One row of ibft_sign_seals: the signature and the signer's address.
+template <int NONCE = SIGN_NONCE_KECCAK>
+__host__ __device__ __forceinline__ bool sign_row(const uint32_t *__restrict__ gtab, const uint8_t *sk32,
+                                                  const uint8_t *digest32, u256 &r_out, u256 &s_out, uint32_t &v_out,
+                                                  uint32_t addr[5], uint32_t reject_mask = 0) {
+  u256 d;
+  const bool key_ok = sign_key(sk32, d);
+  const bool ok = sign_core<NONCE>(gtab, sk32, d, key_ok, digest32, r_out, s_out, v_out, reject_mask);
+  sign_address(gtab, d, key_ok, addr);
   return ok;
 }
 

@@ -1,4 +1,4 @@
-"""Synthetic consensus rounds signed ON THE DEVICE (ibft_sign_seals, include/ibftgpu.h §f4) — for load generators,
+"""Synthetic consensus rounds signed ON THE DEVICE (ibft_sign_seals, ibft_sign_messages_wire, include/ibftgpu.h §f4) — for load generators,
 simulators and bench.py.  A process that plays n validators needs n committed seals per height
 (Backend.BuildCommitMessage, /root/reference/core/backend.go:12-34); the batch signer produces 65 536 of them in under a
 millisecond, so a benchmark rank can build the WHOLE validator table of a sharded round on its own GPU in milliseconds
@@ -8,7 +8,11 @@ Keys are deterministic in (seed, validator index): sk = SplitMix64 stream of the
 cleared (< 2^255 < n) and forced non-zero.  The Byzantine mix follows SURVEY.md §8d: every fifth row (by a SplitMix64
 stream of seed ^ 0xB12) is corrupted, the kind cycling over the twelve kinds below; `expect` is what every verifier
 must answer by construction (an honest row is valid, a corrupted one is not), and bench.py / the tests additionally
-check the rows against the CPU oracle."""
+check the rows against the CPU oracle.
+
+make_message_round is the same one layer up: the PREPARE or COMMIT MESSAGES of a round as wire bytes — View, From, envelope
+signature, type, proposal hash and (COMMIT) committed seal, encoded and signed by ibft_sign_messages_wire — in the form
+ibft_verify_senders_wire / ibft_verify_messages_wire read, with its own three kinds of spoiled rows (MESSAGE_CORRUPTIONS)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -17,6 +21,8 @@ import numpy as np
 
 CORRUPTIONS = ["random65", "non_validator", "other_hash", "stolen_seal", "r_zero", "s_zero", "r_ge_n", "s_ge_n", "v_two",
                "len64", "wrong_hash_field", "nil_payload"]
+MESSAGE_CORRUPTIONS = ["sig_flip", "outsider", "from_swap"]
+MESSAGE_KINDS = {"prepare": 1, "commit": 2}
 ROW_NIL, ROW_BADLEN, ROW_HASH_BAD = 1, 2, 4
 _N_ORDER = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
 _M64 = (1 << 64) - 1
@@ -126,3 +132,78 @@ def _sign(bv, sk, hcol, chunk: int | None = None, nonce: str = "keccak"):
     if not sigs:
         return np.zeros((0, 65), np.uint8), np.zeros((0, 20), np.uint8), np.zeros(0, bool)
     return np.concatenate(sigs), np.concatenate(signers), np.concatenate(oks)
+
+
+@dataclass
+class MessageRound:
+    n: int
+    kind: str              # "prepare" | "commit"
+    height: int
+    round: int
+    raw: bytes
+    proposal_hash: bytes
+    wire: bytes            # the n messages back to back
+    off: np.ndarray        # n + 1 u32: message i is wire[off[i]:off[i+1]]
+    addrs: np.ndarray      # n × 20 (validator table, row i = validator i = the honest sender of message i)
+    power: np.ndarray      # n u64
+    expect: np.ndarray     # n bool: the sender verdict every row must get
+    kinds: list
+
+
+def _varint_len(v: int) -> int:
+    return max(1, (int(v).bit_length() + 6) // 7)
+
+
+def make_message_round(bv, n: int, seed: int = 1, *, kind: str = "commit", height: int = 1, round_: int = 0,
+                       byzantine: bool = False, nonce: str = "keccak", raw_len: int = 1024) -> MessageRound:
+    """n validators, one PREPARE or COMMIT message each for (height, round_) over keccak256(raw ‖ BE64(round_)) — keys, proposal
+    hash, seals, envelope signatures and the wire bytes all computed by `bv` (ibft_proposal_hash, ibft_sign_messages_wire).
+    With `byzantine`, every fifth row (the selection of make_round) is spoiled on the host after signing, the kind cycling over
+    MESSAGE_CORRUPTIONS: a flipped byte inside the envelope signature, an envelope signed by a key of no validator (the whole
+    message is that key's: From names it), a From swapped for a neighbour's.  Leaves bv's staged batch undefined."""
+    if kind not in MESSAGE_KINDS:
+        raise ValueError(f"kind must be one of {sorted(MESSAGE_KINDS)}, not {kind!r}")
+    raw = _splitmix(seed, (raw_len + 7) // 8).tobytes()[:raw_len]
+    H = bv.proposal_hash(raw, round_)
+    sk = secret_keys(seed, n)
+    hcol = np.tile(np.frombuffer(H, dtype=np.uint8), (n, 1))
+    t = MESSAGE_KINDS[kind]
+    wire, off, addrs, ok = _sign_messages(bv, sk, t, height, round_, hcol, nonce=nonce)
+    assert ok.all()
+    expect = np.ones(n, dtype=bool)
+    kinds = [""] * n
+    if byzantine:
+        bad = np.flatnonzero(_splitmix(seed ^ 0xB12, n) % np.uint64(5) == 0)
+        w = bytearray(wire)
+        # every row of the round has one length and one layout: 0a len View ‖ 12 14 From ‖ 1a 41 Signature ‖ …
+        view = (1 + _varint_len(height) if height else 0) + (1 + _varint_len(round_) if round_ else 0)
+        from_at, sig_at = 2 + view + 2, 2 + view + 22 + 2
+        outsider, o_off, _, _ = _sign_messages(bv, secret_keys(seed, len(bad), salt=0x5EED), t, height, round_, hcol[:len(bad)], nonce=nonce)
+        for j, i in enumerate(bad):
+            k = MESSAGE_CORRUPTIONS[j % len(MESSAGE_CORRUPTIONS)]
+            kinds[i] = k
+            expect[i] = False
+            lo = int(off[i])
+            if k == "sig_flip":
+                w[lo + sig_at + (7 * j) % 64] ^= 0xFF
+            elif k == "outsider":
+                w[lo:int(off[i + 1])] = outsider[int(o_off[j]):int(o_off[j + 1])]
+            elif k == "from_swap":
+                w[lo + from_at:lo + from_at + 20] = addrs[(i + 1) % n].tobytes()
+                if n == 1:
+                    w[lo + from_at] ^= 0xFF
+        wire = bytes(w)
+    return MessageRound(n, kind, height, round_, raw, H, wire, off, addrs, np.ones(n, dtype=np.uint64), expect, kinds)
+
+
+def _sign_messages(bv, sk, type_, height, round_, hcol, chunk: int | None = None, nonce: str = "keccak"):
+    """ibft_sign_messages_wire in pieces of at most the context's max_rows → (wire bytes, off u32[n+1], from20, ok)"""
+    chunk = chunk or int(bv.max_rows)
+    wires, offs, froms, oks, base = [], [np.zeros(1, np.uint32)], [], [], 0
+    for lo in range(0, len(sk), chunk):
+        w, o, f, ok = bv.sign_messages(sk[lo:lo + chunk], type_, height, round_, hcol[lo:lo + chunk], nonce=nonce)
+        wires.append(w); offs.append(o[1:] + np.uint32(base)); froms.append(f); oks.append(ok)
+        base += len(w)
+    if not wires:
+        return b"", np.zeros(1, np.uint32), np.zeros((0, 20), np.uint8), np.zeros(0, bool)
+    return b"".join(wires), np.concatenate(offs), np.concatenate(froms), np.concatenate(oks)

@@ -51,11 +51,11 @@ EXPORTS = [
     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
-    "ibft_sign_seals_ex",
+    "ibft_sign_seals_ex", "ibft_sign_messages_wire",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
-# (ibft_set_validator_sets …, the two _sets block calls) and ibft_sign_seals_ex came without a version step: an
+# (ibft_set_validator_sets …, the two _sets block calls), ibft_sign_seals_ex and ibft_sign_messages_wire came without a version step: an
 # older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
 EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
 OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
@@ -65,7 +65,9 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
                     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
                     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
-                    "ibft_sign_seals_ex"}
+                    "ibft_sign_seals_ex", "ibft_sign_messages_wire"}
+SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
+MSG_PREPARE, MSG_COMMIT = 1, 2
 COMM_ID_BYTES = 128
 E_RCCL = -8
 
@@ -203,6 +205,8 @@ def load_library() -> C.CDLL:
         L.ibft_verify_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
     if hasattr(L, "ibft_sign_seals_ex"):
         L.ibft_sign_seals_ex.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
+    if hasattr(L, "ibft_sign_messages_wire"):
+        L.ibft_sign_messages_wire.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
     if hasattr(L, "ibft_recover_seals"):
         L.ibft_recover_seals.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Tally)]
     if hasattr(L, "ibft_recover_block_seals"):
@@ -1083,6 +1087,34 @@ class BatchVerifier:
                       "ibft_sign_seals_ex")
         self._staged = n
         return sig, signer, ok.astype(bool)
+
+    def sign_messages(self, sk32, type, height, round, hash32, nonce="keccak"):
+        """ibft_sign_messages_wire (simulators only): one PREPARE (type 1) or COMMIT (type 2) message per row, built, hashed,
+        signed and encoded on the device → (wire: bytes, off u32[n+1], from20 u8[n,20], ok bool[n]); row i is
+        wire[off[i]:off[i+1]], the form is_valid_validator_wire / verify_messages_wire take.  type, height and round are
+        columns or scalars (one value for every row).  A COMMIT's seal signs the hash under the context's seal-digest
+        convention.  A refused key (ok False) keeps its row's length and carries a zero From, signature and seal.  Leaves no
+        staged batch."""
+        if nonce not in SIGN_NONCES:
+            raise ValueError(f"nonce must be one of {sorted(SIGN_NONCES)}, not {nonce!r}")
+        if not hasattr(self._L, "ibft_sign_messages_wire"):
+            raise GpuUnavailable("this build of the library has no ibft_sign_messages_wire — rebuild")
+        sk = np.ascontiguousarray(sk32, dtype=np.uint8).reshape(-1, 32)
+        hs = np.ascontiguousarray(hash32, dtype=np.uint8).reshape(-1, 32)
+        n = len(sk)
+        if len(hs) != n:
+            raise ValueError("one hash per key")
+        ty = np.ascontiguousarray(np.broadcast_to(np.asarray(type, dtype=np.uint8), (n,)))
+        hh = np.ascontiguousarray(np.broadcast_to(np.asarray(height, dtype=np.uint64), (n,)))
+        rr = np.ascontiguousarray(np.broadcast_to(np.asarray(round, dtype=np.uint64), (n,)))
+        wire = np.zeros(max(n, 1) * SIGN_MESSAGE_MAX, dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        frm = np.zeros((n, 20), dtype=np.uint8)
+        ok = np.zeros(n, dtype=np.uint8)
+        self._chk(self._L.ibft_sign_messages_wire(self._h, _p(sk), _p(ty), _p(hh), _p(rr), _p(hs), n, SIGN_NONCES[nonce], _p(wire),
+                                                  wire.size, _p(off), _p(frm), _p(ok)), "ibft_sign_messages_wire")
+        self._staged = 0
+        return wire[:int(off[n])].tobytes(), off, frm, ok.astype(bool)
 
     def forget_proposal(self) -> None:
         """the next call that names a proposal hashes it again (a new height has a new proposal)"""

@@ -48,6 +48,9 @@
  *   ibft_sign_seals, ibft_sign_seals_ex
  *                        <- n × Backend.BuildCommitMessage's seal (core/backend.go:12-34), simulators only (_ex: with
  *                           RFC 6979 nonces, the seals third-party signers reproduce)
+ *   ibft_sign_messages_wire
+ *                        <- n × Backend.BuildPrepareMessage / BuildCommitMessage (core/backend.go:12-34) as wire bytes,
+ *                           simulators only: what ibft_verify_senders_wire / ibft_verify_messages_wire read
  *   ibft_pinned_alloc    page-locked column buffers the device reads itself (one gather launch per call)
  *
  * Conventions (the reference fixes none of the arithmetic; these are the
@@ -831,6 +834,36 @@ int ibft_sign_seals(ibft_ctx *ctx, const uint8_t *sk32, const uint8_t *hash32, s
 #define IBFT_SIGN_NONCE_RFC6979 1u
 int ibft_sign_seals_ex(ibft_ctx *ctx, const uint8_t *sk32, const uint8_t *hash32, size_t n, uint32_t nonce,
                        uint8_t *out_sig65, uint8_t *out_signer20, uint8_t *out_ok);
+/* The signing side one layer up, for SIMULATORS as well: whole PREPARE / COMMIT messages, built, hashed, signed and stored on
+ * the device as the wire bytes ibft_verify_senders_wire / ibft_verify_messages_wire read — Backend.BuildPrepareMessage /
+ * BuildCommitMessage (/root/reference/core/backend.go:12-34) for n validators at once.  Row i is (sk32[i], type[i] = 1 PREPARE /
+ * 2 COMMIT, height[i], round[i], hash32[i]) and becomes, in canonical proto3 (go-ibft_amd/csrc/sign_message_dev.h):
+ *     View{height, round} (always present) ‖ From = keccak256(X‖Y)[12..32) of the key ‖ Signature ‖ Type ‖
+ *     PrepareMessage{ProposalHash}  or  CommitMessage{ProposalHash, CommittedSeal}
+ * with CommittedSeal = sign(sk, D), D = hash32[i] under the context's seal-digest convention (ibft_set_seal_digest) — byte for
+ * byte the seal ibft_sign_seals_ex gives for that key, hash and nonce rule — and Signature = sign(sk, keccak256(PayloadNoSig)),
+ * PayloadNoSig being the message without its Signature field (the envelope never applies the seal-digest convention).  `nonce`
+ * is IBFT_SIGN_NONCE_KECCAK or IBFT_SIGN_NONCE_RFC6979, for both signatures of a row.
+ * Outputs: out_off has n + 1 entries, row i is out_wire[out_off[i] .. out_off[i+1]) — the (wire, off, n) triple
+ * ibft_verify_senders_wire takes; a row is 129 … 151 bytes (PREPARE) or 196 … 218 bytes (COMMIT), its length depends on type,
+ * height and round only, and wire_cap = n · IBFT_SIGN_MESSAGE_MAX always suffices.  out_from20 (n × 20) and out_ok (n) may be
+ * NULL.  A key outside [1, n) gives ok = 0 and a row of its NORMAL length with a zero From, a zero Signature and a zero
+ * CommittedSeal (the convention of ibft_sign_seals: lengths stay independent of the keys and the bytes stay canonical
+ * protobuf; every verifier rejects the row).
+ * Checks, in this order: IBFT_E_INVAL for a NULL ctx, or a NULL sk32 / type / height / round / hash32 / out_wire / out_off with
+ * n > 0; IBFT_E_INVAL for an unknown `nonce` (ibft_last_error names it); IBFT_E_TOOBIG for n > max_rows; IBFT_E_INVAL for a
+ * type other than 1 or 2 (ibft_last_error names the first such row); IBFT_E_TOOBIG for wire_cap smaller than the total
+ * length.  A refused call writes nothing to any out buffer; n = 0 is legal and sets out_off[0] = 0.
+ * NOT for a production validator's key — the warning of ibft_sign_seals applies word for word: keys cross PCIe in the clear
+ * and sit in HBM for the duration of the call (the column is zeroed before the call returns), and the kernel is not written
+ * to be constant-time.  Unlike ibft_sign_seals the call leaves NO staged seal batch and NO resident wire batch behind
+ * (ibft_seals_run and ibft_wire_stage_seals have nothing to work on until a batch is staged again): the bytes come back to
+ * the host, a following verify call uploads them.  No new ibft_version(): a build without the symbol simply lacks it.  */
+#define IBFT_SIGN_MESSAGE_MAX 218u   /* longest message this call emits (COMMIT, height = round = 2^64 − 1) */
+int ibft_sign_messages_wire(ibft_ctx *ctx, const uint8_t *sk32, const uint8_t *type, const uint64_t *height,
+                            const uint64_t *round, const uint8_t *hash32, size_t n, uint32_t nonce,
+                            uint8_t *out_wire, size_t wire_cap, uint32_t *out_off,
+                            uint8_t *out_from20, uint8_t *out_ok);
 /* Block the host until the context's stream is idle.                               */
 int ibft_sync(ibft_ctx *ctx);
 /* Device canary (diagnostic; no reference counterpart — a Backend may log it at start-up and a bench line carries it):

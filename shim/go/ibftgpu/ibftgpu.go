@@ -1062,6 +1062,28 @@ func (c *Ctx) SignSealsNonce(sk, hashes []byte, nonce uint32) (seals, signers, o
 	return seals, signers, ok, c.check(rc)
 }
 
+// SignMessages = n × Backend.BuildPrepareMessage / BuildCommitMessage (core/backend.go:12-34) for a SIMULATOR
+// (ibft_sign_messages_wire): row i is (sk[32i:], types[i] = 1 PREPARE / 2 COMMIT, heights[i], rounds[i], hashes[32i:]) and
+// comes back as the wire bytes of its message, wire[off[i]:off[i+1]] — the form VerifySendersWire reads —, with the sender
+// addresses (n×20) and ok[i] == 0 for a key outside [1, n) (a row of its normal length with a zero From, signature and seal).
+// Leaves no batch resident.  Not for a production validator's key (include/ibftgpu.h, ibft_sign_seals).
+func (c *Ctx) SignMessages(sk, types []byte, heights, rounds []uint64, hashes []byte, nonce uint32) (wire []byte, off []uint32, from, ok []byte, err error) {
+	n := len(types)
+	if n == 0 || len(sk) != 32*n || len(heights) != n || len(rounds) != n || len(hashes) != 32*n {
+		return nil, nil, nil, nil, ErrFallback
+	}
+	wire, off, from, ok = make([]byte, int(C.IBFT_SIGN_MESSAGE_MAX)*n), make([]uint32, n+1), make([]byte, 20*n), make([]byte, n)
+	rc := C.ibft_sign_messages_wire(c.h, (*C.uint8_t)(unsafe.Pointer(&sk[0])), (*C.uint8_t)(unsafe.Pointer(&types[0])),
+		(*C.uint64_t)(unsafe.Pointer(&heights[0])), (*C.uint64_t)(unsafe.Pointer(&rounds[0])),
+		(*C.uint8_t)(unsafe.Pointer(&hashes[0])), C.size_t(n), C.uint32_t(nonce), (*C.uint8_t)(unsafe.Pointer(&wire[0])),
+		C.size_t(len(wire)), (*C.uint32_t)(unsafe.Pointer(&off[0])), (*C.uint8_t)(unsafe.Pointer(&from[0])),
+		(*C.uint8_t)(unsafe.Pointer(&ok[0])))
+	if err = c.check(rc); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	return wire[:off[n]], off, from, ok, nil
+}
+
 // Group is one process driving several MI355X (ibft_group_*): the rows of a batch are sharded over the
 // devices in 64-aligned ranges and ONE RCCL all-reduce inside the library merges the verdict words and the
 // ranks' distinct-sender bitmaps (a validator with valid rows in two shards is counted once, as HasQuorum's
