@@ -230,7 +230,7 @@ BLOCK_SETS_HARNESS = os.path.join(CSRC, "libdev_block_sets_host.so")
 
 
 def build_block_sets_harness(force: bool = False) -> str:
-    """TEST-ONLY: the per-row decision of block_tally_sets_kernel (recover_dev.h: valsets_*) on the CPU."""
+    """TEST-ONLY: the per-row decision of block_tally_kernel under a family of sets (recover_dev.h: valsets_*) on the CPU."""
     deps = ["host_block_sets_harness.hip", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
     if force or _stale(BLOCK_SETS_HARNESS, deps):
         subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",

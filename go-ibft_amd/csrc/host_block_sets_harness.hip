@@ -1,4 +1,4 @@
-// host_block_sets_harness.hip — TEST-ONLY: the per-row decision of block_tally_sets_kernel on the CPU, so that
+// host_block_sets_harness.hip — TEST-ONLY: the per-row decision of block_tally_kernel under a family of sets on the CPU, so that
 // tests/test_dev_block_sets_host.py can check the exact device source without a GPU: union table → union index
 // (valset_lookup), union index + set → index in the set (valsets_set_index), and what becomes of a row's verdict bit
 // (valsets_row).  Built with hipcc's host pass; never linked into libibftgpu.so, never a fallback.

@@ -79,7 +79,7 @@ std::map<int, std::weak_ptr<DeviceShared>> g_devices;
 // of members is what the verdict kernels and the key cache know as "the validator set" — one table over the UNION of the
 // family's addresses, the union's key-cache slots; while a _sets call runs these are exchanged with the context's own
 // (family_view), so enqueue_recover, build_new_tables and the key cache serve both without knowing which they serve.  The
-// rest is what only block_tally_sets_kernel reads.
+// rest is what only the sets form of block_tally_kernel reads.
 struct ValFamily {
   DevBuf d_vtab, d_vslot;
   std::vector<uint32_t> vslot;
@@ -174,29 +174,31 @@ struct ibft_ctx {
   uint64_t *h_btally = nullptr, *dh_btally = nullptr;
   size_t h_btally_blocks = 0;
   // Streamed chain sync (ibft_block_seals_submit / _collect): at most two batches in flight.  Batch k is copied on the copy
-  // stream into the SPARE column set — d_sig_nx / d_signer_nx / d_pre_nx of the seal pipeline plus a second pair of offset and
-  // block-hash buffers — while the kernels of batch k − 1 read the resident set; the submit then swaps the two sets, exactly
-  // as ibft_seals_stage_next + ibft_seals_swap would (ev_cols_read: the spare set's last reader, ev_staged: the copy landed).
-  // Every kernel of a batch runs on the MAIN stream: the per-row hash column block_rows_kernel fills, the work mask, the
+  // stream into the SPARE column set — d_sig_nx / d_signer_nx / d_pre_nx of the seal pipeline plus a second offset buffer —
+  // while the kernels of batch k − 1 read the resident set; the submit then swaps the two sets, exactly as
+  // ibft_seals_stage_next + ibft_seals_swap would (ev_cols_read: the spare set's last reader, ev_staged: the copy landed).
+  // Every kernel of a batch runs on the MAIN stream: the per-row hash column block_head_kernel fills, the work mask, the
   // validator indices, d_seen and the ticket word in d_acc exist once and rely on that order — and any other entry point that
   // enqueues on the main stream is behind the batches in flight by the same order, their results already on the way to
   // their slots.  Results: verdict words in the seal pipeline's mapped slots (p_mask; the two pipelines are never mixed),
   // {keys learned, a learned slot} in p_tally[s][4], the per-block records in bs_tally[s] (mapped) or through bs_dtally[s].
-  DevBuf d_bhash_nx, d_boff_nx, bs_dtally[2];
+  DevBuf d_boff_nx, bs_dtally[2];
   uint64_t *bs_tally[2] = {nullptr, nullptr}, *bs_dtally_map[2] = {nullptr, nullptr};
   size_t bs_tally_blocks[2] = {0, 0};
   hipEvent_t ev_bs[2] = {nullptr, nullptr};
   uint32_t bs_issued = 0, bs_collected = 0, bs_rows[2] = {0, 0}, bs_blocks[2] = {0, 0};
   uint64_t bs_quorum[2][2] = {{0, 0}, {0, 0}};  // the quorum a batch was judged under (the set current at its submit)
-  // The streamed submits that take proposals or bare seals (ibft_block_seals_submit_raw, ibft_recover_block_seals_submit[_raw];
-  // bs_kind: IBFT_BATCH_* of the batch in each slot, 0 for a batch of ibft_block_seals_submit).  What such a batch reads and
-  // delivers beyond verdict words and records is PRIVATE to its slot, so the kernels of batch k + 1 never write what batch k
-  // still has to deliver: the proposals as given (bytes with 256 of slack, offsets, rounds: two slots double the device bytes
-  // proposals take, each slot bounded by IBFT_PROPOSAL_BYTES_MAX), the blocks' digests (computed, or the uploaded hashes of a
-  // bare batch) that block_head_kernel reads and never writes, and for a recover batch the columns the emitting kernels fill —
+  // All four streamed submits (ibft_block_seals_submit[_raw], ibft_recover_block_seals_submit[_raw]; bs_kind: IBFT_BATCH_* of the
+  // batch in each slot, 0 for a batch of ibft_block_seals_submit).  What a batch reads and delivers beyond verdict words and
+  // records is PRIVATE to its slot, so the kernels of batch k + 1 never write what batch k still has to deliver: the proposals
+  // as given (bytes with 256 of slack, offsets, rounds: two slots double the device bytes proposals take, each slot bounded by
+  // IBFT_PROPOSAL_BYTES_MAX), the blocks' digests (computed, or the uploaded hashes of a hashes-given batch) that
+  // block_head_kernel reads and never writes, and for a recover batch the columns the emitting kernels fill —
   // swapped in for d_signer_out / d_vidx while the batch's kernels are enqueued.  Digests, signers and indices come back on
   // ostream — NOT the copy stream, whose next command is the upload of batch k + 1 and must not wait for batch k's tally —
   // behind ev_bs_dig (the digests exist) and ev_bs (the tally is done) into page-locked buffers; ev_bs_out is behind the last copy.
+  // ostream, ev_bs_dig and ev_bs_out are created by the first submit of ANY kind: a context that only ever calls
+  // ibft_block_seals_submit has them too and never puts a command on them.
   DevBuf bs_praw[2], bs_proff[2], bs_pround[2], bs_phash[2], bs_signer[2], bs_vidx[2];
   uint8_t *bs_h_hash[2] = {nullptr, nullptr}, *bs_h_signer[2] = {nullptr, nullptr};
   int32_t *bs_h_vidx[2] = {nullptr, nullptr};
@@ -354,6 +356,21 @@ int ensure(ibft_ctx *c, DevBuf &b, size_t bytes) {
   return IBFT_OK;
 }
 
+// The same for a page-locked host array of `elem`-byte entries (at least 256 of them); nothing may still write the old one.
+int grow_pinned(void **p, size_t *cap, size_t want, size_t elem) {
+  if (want <= *cap) return IBFT_OK;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t n = std::max<size_t>(want, 256);
+  if (hipHostMalloc(p, n * elem) != hipSuccess) {
+    *p = nullptr;
+    return IBFT_E_NOMEM;
+  }
+  *cap = n;
+  return IBFT_OK;
+}
+
 void release(DevBuf &b) {
   if (b.p) (void)hipFree(b.p);
   b.p = nullptr;
@@ -435,6 +452,46 @@ int next_events(ibft_ctx *c, hipEvent_t *start, hipEvent_t *stop) {
   c->ev_used++;
   return IBFT_OK;
 }
+// Is the verdict launch about to be enqueued one of the timed ones (every time_every-th)?  Event pairs accumulate until
+// ibft_last_kernel_ms reads (and resets) them; unread, they are reused from the first one on.
+bool next_pass_timed(ibft_ctx *c) {
+  if (c->ev_used >= 4096) c->ev_used = 0;
+  return c->time_every && (c->pass_counter++ % c->time_every) == 0;
+}
+
+// The row offsets of a block batch, checked the way every block call checks them: widest = rows of the largest block (picks
+// the tally's workgroup size), n = rows of the batch.
+int check_seal_offsets(const ibft_ctx *c, const uint32_t *seal_off, size_t n_blocks, uint32_t *widest, size_t *n) {
+  if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
+  if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;  // (max_rows never changes after ibft_ctx_create)
+  *widest = 0;
+  for (size_t b = 0; b < n_blocks; b++) {
+    if (seal_off[b + 1] < seal_off[b]) return IBFT_E_INVAL;
+    *widest = std::max(*widest, seal_off[b + 1] - seal_off[b]);
+  }
+  *n = seal_off[n_blocks];
+  return *n > c->max_rows ? IBFT_E_TOOBIG : IBFT_OK;
+}
+// The segmented tally's records (4 words per block) → the caller's ibft_tally_t; quorum_of_block(b): the two low quorum
+// words block b was judged under.  No rows at all: every block is empty, power 0 < quorum.
+template <class Q>
+void fill_block_tallies(ibft_tally_t *out_tally, uint32_t nb, uint32_t nr, const uint64_t *records, Q quorum_of_block) {
+  if (!out_tally) return;
+  for (uint32_t b = 0; b < nb; b++) {
+    ibft_tally_t &t = out_tally[b];
+    memset(&t, 0, sizeof t);
+    const uint64_t *q = quorum_of_block(b);
+    t.quorum_lo = q[0];
+    t.quorum_hi = q[1];
+    if (!nr) continue;
+    const uint64_t *r = records + 4ull * b;
+    t.power_lo = r[0];
+    t.power_hi = r[1];
+    t.valid_rows = (uint32_t)(r[2] & 0xFFFFFFFFull);
+    t.distinct_senders = (uint32_t)(r[2] >> 32);
+    t.has_quorum = (uint32_t)r[3];
+  }
+}
 
 // zero the work mask unless the last tally already left it zero
 int clean_mask(ibft_ctx *c) {
@@ -473,7 +530,7 @@ struct ctx_lock {
 // as part of "the validator set" belongs in exchange().
 // NOT exchanged — they stay the SINGLE set's while a view lives, and nothing on the _sets path may read them: have_valset,
 // d_vpower, d_quorum, quorum_w, power_words, d_seen, h_vtab, valset_addrs, height, last_wide.  Their family counterparts are
-// read from c->fam directly (enqueue_block_tally_sets: fam.d_power, d_quorum, power_words, d_seen, largest_set; block_seals_impl:
+// read from c->fam directly (enqueue_block_tally: fam.d_power, d_quorum, power_words, d_seen, largest_set; block_seals_impl:
 // fam.have, fam.quorum, fam.n_sets).
 struct family_view {
   ibft_ctx *c;
@@ -1650,7 +1707,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_cert_nodes, &c->d_cert_span, &c->d_cert_count, &c->d_cert_prop, &c->d_cert_masks, &c->d_cert_total,
                     &c->d_cert_slot, &c->d_cert_tiles, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
                     &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally,
-                    &c->d_bhash_nx, &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
+                    &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
                     &c->d_phash, &c->bs_praw[0], &c->bs_praw[1], &c->bs_proff[0], &c->bs_proff[1], &c->bs_pround[0], &c->bs_pround[1],
                     &c->bs_phash[0], &c->bs_phash[1], &c->bs_signer[0], &c->bs_signer[1], &c->bs_vidx[0], &c->bs_vidx[1], &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
                     &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->d_msg_cols, &c->d_msg_wire})
@@ -2395,8 +2452,7 @@ int ibft_seals_submit(ibft_ctx *c) {
     const int rcs = ensure_result_slots(c);
     if (rcs) return rcs;
   }
-  if (c->ev_used >= 4096) c->ev_used = 0;
-  const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
+  const bool time_it = next_pass_timed(c);
   int rc;
   // The verdict launch writes the CURRENT pair of work mask / validator indices; its last reader was the tally of pass k − 2
   // (collected, or the two-in-flight check above would have refused) or something the main stream is already behind.
@@ -2998,52 +3054,11 @@ int ibft_recover_seals(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65,
 }
 
 // The segmented tally of a block batch over the resident work mask / validator indices and the offsets in d_boff, on the main
-// stream.  Work mask, d_seen and the ticket word in d_acc exist once per context: two batches in flight (ibft_block_seals_submit)
-// take turns at them in main-stream order.
-static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t widest, uint64_t *host_mask, uint64_t *out) {
+// stream.  Work mask, the bitmap and the ticket word in d_acc exist once per context: two batches in flight
+// (ibft_block_seals_submit) take turns at them in main-stream order.  sets: under a family of validator sets (the block's set
+// in fam.d_bset) — powers, quorums and bitmap are the family's, the LARGEST set in the place of the one set's size.
+static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t widest, uint64_t *host_mask, uint64_t *out, bool sets) {
   if (c->read_pending) {  // a consumer stream is still copying the previous results (ibft_seals_export_on / exchange)
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
-    c->read_pending = false;
-  }
-  ibftk::block_tally_args t{};
-  t.work_mask = (uint64_t *)c->d_mask.p;
-  t.mask = (uint64_t *)c->d_mask_out.p;
-  t.host_mask = host_mask;
-  t.vidx = (const int32_t *)c->d_vidx.p;
-  t.vpower32 = (const uint32_t *)c->d_vpower.p;
-  t.off = (const uint32_t *)c->d_boff.p;
-  t.n = nr;
-  t.n_blocks = nb;
-  t.n_validators = c->n_validators;
-  const size_t lds = (size_t)((c->n_validators + 31) / 32) * 4;
-  t.lds_bitmap = lds <= 49152 ? 1u : 0u;  // beyond: one workgroup walks every block over the HBM bitmap (tally_kernel's bound)
-  t.seen = (uint32_t *)c->d_seen.p;
-  t.acc = (uint64_t *)c->d_acc.p;
-  t.quorum = (const uint64_t *)c->d_quorum.p;
-  t.out = out;
-  const dim3 grid(t.lds_bitmap ? std::min(nb, ibftk::BTALLY_MAX_GRID) : 1u);
-  const size_t dyn = t.lds_bitmap ? lds : 0;
-  const bool wide = widest > 256u * ibftk::BTALLY_RPT;  // a block that one step of 256 threads does not cover
-  if (c->power_words == 1) {
-    if (wide)
-      hipLaunchKernelGGL((ibftk::block_tally_kernel<1, 1024>), grid, dim3(1024), dyn, c->stream, t);
-    else
-      hipLaunchKernelGGL((ibftk::block_tally_kernel<1, 256>), grid, dim3(256), dyn, c->stream, t);
-  } else {
-    if (wide)
-      hipLaunchKernelGGL((ibftk::block_tally_kernel<4, 1024>), grid, dim3(1024), dyn, c->stream, t);
-    else
-      hipLaunchKernelGGL((ibftk::block_tally_kernel<4, 256>), grid, dim3(256), dyn, c->stream, t);
-  }
-  HIPCHK(c, hipGetLastError());
-  if ((uint32_t)mask_words(nr) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed every word that held bits
-  return IBFT_OK;
-}
-
-// The same under a family of validator sets (the block's set in fam.d_bset): block_tally_sets_kernel, the launch shapes of the
-// tally above with the LARGEST set in the place of the one set's size.
-static int enqueue_block_tally_sets(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t widest, uint64_t *host_mask, uint64_t *out) {
-  if (c->read_pending) {
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
     c->read_pending = false;
   }
@@ -3053,36 +3068,45 @@ static int enqueue_block_tally_sets(ibft_ctx *c, uint32_t nb, uint32_t nr, uint3
   t.mask = (uint64_t *)c->d_mask_out.p;
   t.host_mask = host_mask;
   t.vidx = (int32_t *)c->d_vidx.p;
-  t.vpower32 = (const uint32_t *)f.d_power.p;
+  t.vpower32 = (const uint32_t *)(sets ? f.d_power.p : c->d_vpower.p);
   t.off = (const uint32_t *)c->d_boff.p;
-  t.block_set = (const uint32_t *)f.d_bset.p;
-  t.setidx = (const int32_t *)f.d_setidx.p;
-  t.set_meta = (const uint2 *)f.d_meta.p;
-  t.quorum = (const uint64_t *)f.d_quorum.p;
   t.n = nr;
   t.n_blocks = nb;
-  t.n_union = c->n_validators;  // (under family_view: the union's size)
-  const size_t lds = (size_t)((f.largest_set + 31) / 32) * 4;
-  t.lds_bitmap = lds <= 49152 ? 1u : 0u;
-  t.seen = (uint32_t *)f.d_seen.p;
+  t.n_validators = c->n_validators;  // (under family_view: the union's size)
+  const size_t lds = (size_t)(((sets ? f.largest_set : c->n_validators) + 31) / 32) * 4;
+  t.lds_bitmap = lds <= 49152 ? 1u : 0u;  // beyond: one workgroup walks every block over the HBM bitmap (tally_kernel's bound)
+  t.seen = (uint32_t *)(sets ? f.d_seen.p : c->d_seen.p);
   t.acc = (uint64_t *)c->d_acc.p;
+  t.quorum = (const uint64_t *)(sets ? f.d_quorum.p : c->d_quorum.p);
   t.out = out;
+  t.block_set = (const uint32_t *)f.d_bset.p;  // (these three: read by the sets form alone)
+  t.setidx = (const int32_t *)f.d_setidx.p;
+  t.set_meta = (const uint2 *)f.d_meta.p;
   const dim3 grid(t.lds_bitmap ? std::min(nb, ibftk::BTALLY_MAX_GRID) : 1u);
   const size_t dyn = t.lds_bitmap ? lds : 0;
-  const bool wide = widest > 256u * ibftk::BTALLY_RPT;
-  if (f.power_words == 1) {
+  const bool wide = widest > 256u * ibftk::BTALLY_RPT;  // a block that one step of 256 threads does not cover
+  const ibftk::block_tally_args &plain = t;
+#define LAUNCH_BTALLY(PW, THREADS)                                                                                          \
+  do {                                                                                                                      \
+    if (sets)                                                                                                               \
+      hipLaunchKernelGGL((ibftk::block_tally_kernel<PW, THREADS, true>), grid, dim3(THREADS), dyn, c->stream, t);           \
+    else                                                                                                                    \
+      hipLaunchKernelGGL((ibftk::block_tally_kernel<PW, THREADS, false>), grid, dim3(THREADS), dyn, c->stream, plain);      \
+  } while (0)
+  if ((sets ? f.power_words : c->power_words) == 1) {
     if (wide)
-      hipLaunchKernelGGL((ibftk::block_tally_sets_kernel<1, 1024>), grid, dim3(1024), dyn, c->stream, t);
+      LAUNCH_BTALLY(1, 1024);
     else
-      hipLaunchKernelGGL((ibftk::block_tally_sets_kernel<1, 256>), grid, dim3(256), dyn, c->stream, t);
+      LAUNCH_BTALLY(1, 256);
   } else {
     if (wide)
-      hipLaunchKernelGGL((ibftk::block_tally_sets_kernel<4, 1024>), grid, dim3(1024), dyn, c->stream, t);
+      LAUNCH_BTALLY(4, 1024);
     else
-      hipLaunchKernelGGL((ibftk::block_tally_sets_kernel<4, 256>), grid, dim3(256), dyn, c->stream, t);
+      LAUNCH_BTALLY(4, 256);
   }
+#undef LAUNCH_BTALLY
   HIPCHK(c, hipGetLastError());
-  if ((uint32_t)mask_words(nr) >= c->mask_dirty_words) c->mask_dirty_words = 0;
+  if ((uint32_t)mask_words(nr) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed every word that held bits
   return IBFT_OK;
 }
 
@@ -3129,17 +3153,8 @@ static int stage_proposals(ibft_ctx *c, ColumnCopies &cc, const proposal_batch &
   if ((rc = ensure(c, c->d_proff, (n + 1) * 4))) return rc;
   if ((rc = ensure(c, c->d_pround, n * 8))) return rc;
   if ((rc = ensure(c, c->d_phash, n * 32))) return rc;
-  if (p.out_hash32 && n > c->h_phash_rows) {  // (every call that delivers into it has synchronised before it returned)
-    if (c->h_phash) (void)hipHostFree(c->h_phash);
-    c->h_phash = nullptr;
-    c->h_phash_rows = 0;
-    const size_t want = std::max<size_t>(n, 256);
-    if (hipHostMalloc((void **)&c->h_phash, want * 32) != hipSuccess) {
-      c->h_phash = nullptr;
-      return IBFT_E_NOMEM;
-    }
-    c->h_phash_rows = want;
-  }
+  // (every call that delivers into the mirror has synchronised before it returned)
+  if (p.out_hash32 && (rc = grow_pinned((void **)&c->h_phash, &c->h_phash_rows, n, 32))) return rc;
   cc.add(c->d_praw.p, p.raw, bytes);
   cc.add(c->d_proff.p, p.raw_off, (n + 1) * 4);
   cc.add(c->d_pround.p, p.round, n * 8);
@@ -3223,15 +3238,10 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
                             uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally,
                             bool sets, const uint32_t *block_set) {
-  if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
-  if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;  // (max_rows never changes after ibft_ctx_create)
-  uint32_t widest = 0;  // rows of the largest block: picks the tally's workgroup size
-  for (size_t b = 0; b < n_blocks; b++) {
-    if (seal_off[b + 1] < seal_off[b]) return IBFT_E_INVAL;
-    widest = std::max(widest, seal_off[b + 1] - seal_off[b]);
-  }
-  const size_t n = seal_off[n_blocks];
-  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  uint32_t widest;
+  size_t n;
+  int rc;
+  if ((rc = check_seal_offsets(c, seal_off, n_blocks, &widest, &n))) return rc;
   if (n && ((!props && !block_hash32) || !sig65 || (bare ? !out_signer20 : !signer20) || !out_mask)) return IBFT_E_INVAL;
   if (sets && n_blocks && !block_set) return IBFT_E_INVAL;
   ctx_lock lk(c);
@@ -3241,7 +3251,6 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
       if (block_set[b] >= c->fam.n_sets) return IBFT_E_INVAL;
   // sets: from here to the return "the validator set" of the context is the family's union (table, size, key-cache slots)
   family_view fv(c, sets);
-  int rc;
   if (props && (rc = check_proposals(c, *props, n_blocks))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const uint32_t nb = (uint32_t)n_blocks, nr = (uint32_t)n;
@@ -3255,15 +3264,8 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
     if ((rc = ensure(c, c->d_bhash, (size_t)nb * 32))) return rc;
     if ((rc = ensure(c, c->d_btally, (size_t)nb * 32))) return rc;
     if (nb > c->h_btally_blocks) {  // (every call that delivers into it has synchronised before it returned: nothing writes it now)
-      if (c->h_btally) (void)hipHostFree(c->h_btally);
-      c->h_btally = c->dh_btally = nullptr;
-      c->h_btally_blocks = 0;
-      const size_t want = std::max<size_t>(nb, 256);
-      if (hipHostMalloc((void **)&c->h_btally, want * 32) != hipSuccess) {
-        c->h_btally = nullptr;
-        return IBFT_E_NOMEM;
-      }
-      c->h_btally_blocks = want;
+      c->dh_btally = nullptr;
+      if ((rc = grow_pinned((void **)&c->h_btally, &c->h_btally_blocks, nb, 32))) return rc;
       void *d = nullptr;  // the tally writes the records itself where the verdict words go there too (not under IBFT_NO_HOST_DIRECT)
       if (c->dh_mask && hipHostGetDevicePointer(&d, c->h_btally, 0) == hipSuccess) c->dh_btally = (uint64_t *)d;
     }
@@ -3292,12 +3294,9 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
   c->staged_n = sets ? 0 : nr;
   c->staged_pre = pre_flags != nullptr;
   if (nr) {
-    if (c->ev_used >= 4096) c->ev_used = 0;
-    const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
-    if ((rc = enqueue_recover(c, nr, c->staged_pre, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
+    if ((rc = enqueue_recover(c, nr, c->staged_pre, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, next_pass_timed(c)))) return rc;
     uint64_t *const records = c->dh_btally ? c->dh_btally : (uint64_t *)c->d_btally.p;
-    if ((rc = sets ? enqueue_block_tally_sets(c, nb, nr, widest, c->dh_mask, records) : enqueue_block_tally(c, nb, nr, widest, c->dh_mask, records)))
-      return rc;
+    if ((rc = enqueue_block_tally(c, nb, nr, widest, c->dh_mask, records, sets))) return rc;
     if (bare && (rc = copy_emitted(c, nr, out_signer20, out_vidx))) return rc;
     c->host_direct = false;
     const size_t mw = (size_t)mask_words(nr);
@@ -3317,21 +3316,9 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
   }
   if (hash_here && props->out_hash32) memcpy(props->out_hash32, c->h_phash, (size_t)nb * 32);
   if (bare) c->staged_n = 0;  // (as after ibft_recover_seals: bare rows are no resident batch)
-  if (out_tally)
-    for (uint32_t b = 0; b < nb; b++) {  // (no rows at all: every block is empty, power 0 < quorum)
-      ibft_tally_t &t = out_tally[b];
-      memset(&t, 0, sizeof t);
-      const uint64_t *q = sets ? &c->fam.quorum[(size_t)block_set[b] * ibftk::TALLY_SUM_WORDS] : c->quorum_w;
-      t.quorum_lo = q[0];
-      t.quorum_hi = q[1];
-      if (!nr) continue;
-      const uint64_t *r = c->h_btally + 4ull * b;
-      t.power_lo = r[0];
-      t.power_hi = r[1];
-      t.valid_rows = (uint32_t)(r[2] & 0xFFFFFFFFull);
-      t.distinct_senders = (uint32_t)(r[2] >> 32);
-      t.has_quorum = (uint32_t)r[3];
-    }
+  fill_block_tallies(out_tally, nb, nr, c->h_btally, [&](uint32_t b) -> const uint64_t * {
+    return sets ? &c->fam.quorum[(size_t)block_set[b] * ibftk::TALLY_SUM_WORDS] : c->quorum_w;
+  });
   return IBFT_OK;
 }
 
@@ -3369,127 +3356,25 @@ static int block_pipeline_refusal(ibft_ctx *c) {
 // The per-block records of slot s, for nb blocks (mapped where the device can write them, through bs_dtally[s] otherwise).
 static int ensure_block_records(ibft_ctx *c, uint32_t s, uint32_t nb) {
   int rc;
-    // the records of slot s: the batch that used them last (k − 2) has been collected, nothing writes them now
-    if (nb > c->bs_tally_blocks[s]) {
-      if (c->bs_tally[s]) (void)hipHostFree(c->bs_tally[s]);
-      c->bs_tally[s] = c->bs_dtally_map[s] = nullptr;
-      c->bs_tally_blocks[s] = 0;
-      const size_t want = std::max<size_t>(nb, 256);
-      if (hipHostMalloc((void **)&c->bs_tally[s], want * 32) != hipSuccess) {
-        c->bs_tally[s] = nullptr;
-        return IBFT_E_NOMEM;
-      }
-      c->bs_tally_blocks[s] = want;
-      void *d = nullptr;  // (IBFT_NO_HOST_DIRECT: records and verdict words through device buffers and copies behind the tally)
-      if (c->dh_mask && hipHostGetDevicePointer(&d, c->bs_tally[s], 0) == hipSuccess) c->bs_dtally_map[s] = (uint64_t *)d;
-    }
-    if (!c->bs_dtally_map[s] && (rc = ensure(c, c->bs_dtally[s], (size_t)nb * 32))) return rc;
+  if (nb > c->bs_tally_blocks[s]) {  // the batch that used them last (k − 2) has been collected, nothing writes them now
+    c->bs_dtally_map[s] = nullptr;
+    if ((rc = grow_pinned((void **)&c->bs_tally[s], &c->bs_tally_blocks[s], nb, 32))) return rc;
+    void *d = nullptr;  // (IBFT_NO_HOST_DIRECT: records and verdict words through device buffers and copies behind the tally)
+    if (c->dh_mask && hipHostGetDevicePointer(&d, c->bs_tally[s], 0) == hipSuccess) c->bs_dtally_map[s] = (uint64_t *)d;
+  }
+  if (!c->bs_dtally_map[s] && (rc = ensure(c, c->bs_dtally[s], (size_t)nb * 32))) return rc;
   return IBFT_OK;
 }
 
-// Streamed chain sync: the same batch as ibft_verify_block_seals, enqueued and not waited for.  Up to two batches in flight;
-// the copy of batch k + 1 (copy stream, into the spare column set) runs under the kernels of batch k (main stream).
-int ibft_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
-                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags) {
-  if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
-  if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;
-  uint32_t widest = 0;
-  for (size_t b = 0; b < n_blocks; b++) {
-    if (seal_off[b + 1] < seal_off[b]) return IBFT_E_INVAL;
-    widest = std::max(widest, seal_off[b + 1] - seal_off[b]);
-  }
-  const size_t n = seal_off[n_blocks];
-  if (n > c->max_rows) return IBFT_E_TOOBIG;
-  if (n && (!block_hash32 || !sig65 || !signer20)) return IBFT_E_INVAL;
-  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself; side-stream tallies are joined below)
-  if (!c->have_valset) return IBFT_E_NOVALSET;
-  if (int rf = block_pipeline_refusal(c)) return rf;
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = join_side(c))) return rc;  // tallies of collected seal passes may still be on the side stream
-  const uint32_t s = c->bs_issued & 1u, nb = (uint32_t)n_blocks, nr = (uint32_t)n;
-  if (!c->ev_bs[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bs[s], hipEventDisableTiming));
-  if (nr) {
-    if ((rc = ensure_result_slots(c))) return rc;
-    if ((rc = ensure_spare_columns(c))) return rc;
-    // (hipFree waits for the device: a buffer that grows here is read by nothing any more)
-    if ((rc = ensure(c, c->d_boff_nx, ((size_t)nb + 1) * 4))) return rc;
-    if ((rc = ensure(c, c->d_bhash_nx, (size_t)nb * 32))) return rc;
-    if ((rc = ensure_block_records(c, s, nb))) return rc;
-    // The spare set was the resident one until the previous swap: batch k − 2's kernels — its tally reads the offsets — may
-    // still be at it.  ev_cols_read was recorded behind them.
-    HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_cols_read, 0));
-    HIPCHK(c, hipMemcpyAsync(c->d_boff_nx.p, seal_off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, c->cstream));
-    HIPCHK(c, hipMemcpyAsync(c->d_bhash_nx.p, block_hash32, (size_t)nb * 32, hipMemcpyHostToDevice, c->cstream));
-    HIPCHK(c, hipMemcpyAsync(c->d_sig_nx.p, sig65, n * 65, hipMemcpyHostToDevice, c->cstream));
-    HIPCHK(c, hipMemcpyAsync(c->d_signer_nx.p, signer20, n * 20, hipMemcpyHostToDevice, c->cstream));
-    if (pre_flags) HIPCHK(c, hipMemcpyAsync(c->d_pre_nx.p, pre_flags, n, hipMemcpyHostToDevice, c->cstream));
-    HIPCHK(c, hipEventRecord(c->ev_staged, c->cstream));
-    // everything on the main stream so far (batch k − 1 included) read the set that becomes the spare one now; what follows
-    // reads the other set once its copy has landed
-    HIPCHK(c, hipEventRecord(c->ev_cols_read, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_staged, 0));
-    std::swap(c->d_sig, c->d_sig_nx);
-    std::swap(c->d_signer, c->d_signer_nx);
-    std::swap(c->d_pre, c->d_pre_nx);
-    std::swap(c->d_boff, c->d_boff_nx);
-    std::swap(c->d_bhash, c->d_bhash_nx);
-    c->wire_valid = false;
-    c->staged_n = nr;  // the rows are the resident batch from here on, as after ibft_verify_block_seals
-    c->staged_pre = pre_flags != nullptr;
-    // from here on a failure leaves commands of this batch on the streams: nothing of it is delivered, the slot stays free,
-    // and whatever the main stream gets next is behind them
-    if ((rc = seal_digest_column(c, (uint8_t *)c->d_bhash.p, nb))) return rc;
-    // (the per-row hash column exists once: block_rows_kernel of this batch is behind the verdict kernels of the last one)
-    hipLaunchKernelGGL(ibftk::block_rows_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)c->d_bhash.p,
-                       (const uint32_t *)c->d_boff.p, nb, nr, (uint8_t *)c->d_hash.p);
-    HIPCHK(c, hipGetLastError());
-    if (c->ev_used >= 4096) c->ev_used = 0;
-    const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
-    if ((rc = enqueue_recover(c, nr, c->staged_pre, 0, time_it))) return rc;
-    const bool direct = c->bs_dtally_map[s] != nullptr;
-    if ((rc = enqueue_block_tally(c, nb, nr, widest, direct ? c->dp_mask[s] : nullptr,
-                                  direct ? c->bs_dtally_map[s] : (uint64_t *)c->bs_dtally[s].p)))
-      return rc;
-    c->host_direct = false;
-    if (!direct) {
-      HIPCHK(c, hipMemcpyAsync(c->p_mask[s], c->d_mask_out.p, (size_t)mask_words(nr) * 8, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(c->bs_tally[s], c->bs_dtally[s].p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->stream));
-    }
-    // {keys learned, a learned slot} as of this batch: what its collect builds tables from
-    if (c->cache_on) HIPCHK(c, hipMemcpyAsync(c->p_tally[s] + 4, c->dev->d_learned.p, 8, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipEventRecord(c->ev_bs[s], c->stream));
-  c->bs_rows[s] = nr;
-  c->bs_blocks[s] = nb;
-  c->bs_quorum[s][0] = c->quorum_w[0];
-  c->bs_quorum[s][1] = c->quorum_w[1];
-  c->bs_kind[s] = 0;
-  c->bs_has_out[s] = false;
-  c->bs_issued++;
-  return IBFT_OK;
-}
-
-// ---- streamed chain sync from proposals and from bare seals ---------------------------------------------------------------
-// ibft_block_seals_submit_raw, ibft_recover_block_seals_submit, ibft_recover_block_seals_submit_raw: the batches of
-// ibft_verify_block_seals_raw, ibft_recover_block_seals and ibft_recover_block_seals_raw, enqueued and not waited for, in the two
-// slots of ibft_block_seals_submit.  Checks: the synchronous sibling's, in its order, minus the out buffers; then the
-// pipeline's refusals.  What differs from ibft_block_seals_submit: the blocks' digests (bs_phash[s]) are private to the slot
-// and only read — block_head_kernel applies the seal-digest convention while it spreads them over the rows —, a recover batch
-// emits into columns of its slot, and digests / signers / indices leave on ostream (see the context's fields).
-static int grow_pinned(void **p, size_t *cap, size_t want, size_t elem) {
-  if (want <= *cap) return IBFT_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t n = std::max<size_t>(want, 256);
-  if (hipHostMalloc(p, n * elem) != hipSuccess) {
-    *p = nullptr;
-    return IBFT_E_NOMEM;
-  }
-  *cap = n;
-  return IBFT_OK;
-}
+// ---- streamed chain sync: from hashes, from proposals and from bare seals ----------------------------------------------------
+// ibft_block_seals_submit, ibft_block_seals_submit_raw, ibft_recover_block_seals_submit, ibft_recover_block_seals_submit_raw:
+// the batches of ibft_verify_block_seals, ibft_verify_block_seals_raw, ibft_recover_block_seals and ibft_recover_block_seals_raw,
+// enqueued and not waited for.  Up to two batches in flight; the copy of batch k + 1 (copy stream, into the spare column set)
+// runs under the kernels of batch k (main stream).  Checks: the synchronous sibling's, in its order, minus the out buffers; then
+// the pipeline's refusals.  The blocks' digests (bs_phash[s]: uploaded hashes, or proposal_digest_kernel's) are private to the
+// slot and only read — block_head_kernel applies the seal-digest convention, the one in force at the submit, while it spreads
+// them over the rows —, a recover batch emits into columns of its slot, and digests / signers / indices leave on ostream (see
+// the context's fields).
 // d_signer_out / d_vidx ↔ the emit columns of slot s while a recover batch's kernels are enqueued (make_args and the tally
 // read the context's fields); put back on every way out
 struct emit_columns_view {
@@ -3511,19 +3396,13 @@ struct emit_columns_view {
 };
 static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off,
                                    size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare) {
-  if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
-  if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;
-  uint32_t widest = 0;
-  for (size_t b = 0; b < n_blocks; b++) {
-    if (seal_off[b + 1] < seal_off[b]) return IBFT_E_INVAL;
-    widest = std::max(widest, seal_off[b + 1] - seal_off[b]);
-  }
-  const size_t n = seal_off[n_blocks];
-  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  uint32_t widest;
+  size_t n;
+  int rc;
+  if ((rc = check_seal_offsets(c, seal_off, n_blocks, &widest, &n))) return rc;
   if (n && ((!props && !block_hash32) || !sig65 || (!bare && !signer20))) return IBFT_E_INVAL;
   std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself; side-stream tallies are joined below)
   if (!c->have_valset) return IBFT_E_NOVALSET;
-  int rc;
   if (props && (rc = check_proposals(c, *props, n_blocks))) return rc;
   if ((rc = block_pipeline_refusal(c))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -3618,14 +3497,13 @@ static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, pro
       memcpy(h.suffix_words, c->seal_suffix_words, sizeof h.suffix_words);
       hipLaunchKernelGGL(ibftk::block_head_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, h);
       HIPCHK(c, hipGetLastError());
-      if (c->ev_used >= 4096) c->ev_used = 0;
-      const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
+      const bool time_it = next_pass_timed(c);
       const bool direct = c->bs_dtally_map[s] != nullptr;
       {
         emit_columns_view ev(c, s, bare);
         if ((rc = enqueue_recover(c, nr, pre_flags != nullptr, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
         if ((rc = enqueue_block_tally(c, nb, nr, widest, direct ? c->dp_mask[s] : nullptr,
-                                      direct ? c->bs_dtally_map[s] : (uint64_t *)c->bs_dtally[s].p)))
+                                      direct ? c->bs_dtally_map[s] : (uint64_t *)c->bs_dtally[s].p, false)))
           return rc;
       }
       c->host_direct = false;
@@ -3652,6 +3530,10 @@ static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, pro
   c->bs_has_out[s] = has_out;
   c->bs_issued++;
   return IBFT_OK;
+}
+int ibft_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags) {
+  return block_seals_submit_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, false);
 }
 int ibft_block_seals_submit_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round, const uint32_t *seal_off,
                                 size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags) {
@@ -3698,20 +3580,7 @@ static int block_seals_collect_impl(ibft_ctx *c, bool ex, uint8_t *out_block_has
     memcpy(out_mask, c->p_mask[s], mw * 8);
     if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
   }
-  if (out_tally)
-    for (uint32_t b = 0; b < nb; b++) {  // (no rows at all: every block is empty, power 0 < quorum)
-      ibft_tally_t &t = out_tally[b];
-      memset(&t, 0, sizeof t);
-      t.quorum_lo = c->bs_quorum[s][0];
-      t.quorum_hi = c->bs_quorum[s][1];
-      if (!nr) continue;
-      const uint64_t *r = c->bs_tally[s] + 4ull * b;
-      t.power_lo = r[0];
-      t.power_hi = r[1];
-      t.valid_rows = (uint32_t)(r[2] & 0xFFFFFFFFull);
-      t.distinct_senders = (uint32_t)(r[2] >> 32);
-      t.has_quorum = (uint32_t)r[3];
-    }
+  fill_block_tallies(out_tally, nb, nr, c->bs_tally[s], [&](uint32_t) -> const uint64_t * { return c->bs_quorum[s]; });
   if (ex && (kind & IBFT_BATCH_RAW) && out_block_hash32 && nb) memcpy(out_block_hash32, c->bs_h_hash[s], (size_t)nb * 32);
   if (ex && (kind & IBFT_BATCH_RECOVER) && nr) {
     memcpy(out_signer20, c->bs_h_signer[s], (size_t)nr * 20);

@@ -16,9 +16,9 @@
 //   verify_known_group_kernel<G>    same, G = 2..32 lanes per signature
 //   verify_known_wave_kernel        same, one wavefront per signature in the row layout of wave_fe_dev.h
 //   tally_kernel                a8  HasQuorum             (core/validator_manager.go:77-96)
-//   block_rows_kernel, block_tally_kernel   chain sync: each block's hash → its rows, one HasQuorum per block
-//   block_tally_sets_kernel         … one HasQuorum per block under the block's OWN validator set (a family of sets)
-//   block_head_kernel               streamed chain sync from proposals / bare seals: digests → rows, seal-digest convention fused
+//   block_rows_kernel               chain sync: each block's hash → its rows
+//   block_head_kernel               streamed chain sync (every submit): digests → rows, seal-digest convention fused
+//   block_tally_kernel<PW, THREADS, SETS>   one HasQuorum per block; SETS: under the block's OWN validator set (a family of sets)
 //   gtab_build_kernel, qtab_build_kernel, qtab_commit_kernel   one-time fixed-base tables
 //   lookup_kernel                   sender → validator index for ibft_tally()
 //   wire_parse_kernel, wire_stage_seals_kernel   §8f rank 3: wire bytes → columns on the device (wire_dev.h)
@@ -32,6 +32,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "recover_dev.h"
 #include "verify_dev.h"
@@ -1964,8 +1966,8 @@ __global__ void block_rows_kernel(const uint8_t *__restrict__ block_hash32, cons
   d[1] = s[1];
 }
 
-// The streamed submits that take proposals or bare seals (ibft_block_seals_submit_raw, ibft_recover_block_seals_submit[_raw]):
-// seal-digest convention and spreading over the rows in ONE launch, the blocks' digests left as they are.  The synchronous
+// The streamed submits (ibft_block_seals_submit[_raw], ibft_recover_block_seals_submit[_raw]): seal-digest convention and
+// spreading over the rows in ONE launch, the blocks' digests (computed, or the uploaded hashes) left as they are.  The synchronous
 // path converts the digests in place (seal_digest_kernel) and then spreads them (block_rows_kernel); in the streamed form the
 // digests leave for the host on another stream while the main stream goes on, so nothing may write them — and one launch
 // less is one dependency gap less per batch.  One thread per row; under a non-identity convention every row hashes its
@@ -1990,31 +1992,51 @@ __global__ void __launch_bounds__(256) block_head_kernel(block_head_args a) {
 // Segmented HasQuorum: one verdict launch judged the rows of every block, this kernel answers HasQuorum per block against
 // the one quorum of the context's validator set (core/validator_manager.go:77-96, 128-136, 147-155) — bit for bit what
 // tally_kernel computes for the same rows passed as a batch of their own.  A workgroup takes one block at a time (grid-stride:
-// the HBM-bitmap form runs ONE workgroup over all blocks, the bitmap being the context's single zeroed `seen`): distinct-
-// sender bitmap cleared, the block's rows walked, 2·PW 32-bit power pieces reduced through wave_sum_u64 and LDS, thread 0
-// recombines them and writes the block's record {power_lo, power_hi, valid | distinct << 32, has_quorum}.
+// the HBM-bitmap form runs ONE workgroup over all blocks, the bitmap being a single zeroed `seen`): distinct-sender bitmap
+// cleared, the block's rows walked, 2·PW 32-bit power pieces reduced through wave_sum_u64 and LDS, thread 0 recombines them
+// and writes the block's record {power_lo, power_hi, valid | distinct << 32, has_quorum}.
 // The work mask is read by several workgroups (block boundaries do not fall on verdict words), so it is moved and zeroed by
 // the LAST workgroup to finish (a ticket in acc[TALLY_MAX_PIECES + 2], left zero again): no word is cleared under a reader.
 // THREADS: 256 for blocks of chain-sized seal sets, 1024 when a block has more rows than that (the host picks); a thread
 // takes BTALLY_RPT rows per step and issues their loads together (verdict word, validator index, then the powers of the rows
-// whose bit is set) — one dependent round trip per step instead of one per row.
+// whose bit is set) — one dependent round trip per step instead of one per row.  Row r of a block belongs to thread
+// (r − r0) mod THREADS (STEP is a multiple of THREADS), in the main loop and in the HBM-bitmap clean-up alike.
+//
+// Under a family of sets: (SETS, ibft_verify_block_seals_sets) the verdict kernels judged every row against the union of the
+// family's addresses and left the signer's UNION index; block b is judged under set block_set[b].  Per row one dependent load
+// more — setidx[set][union index] → the index in the block's set (recover_dev.h: valsets_row), issued for the BTALLY_RPT rows
+// of a step together, in front of the powers.  A row whose signer is in the union but not in the block's set loses its verdict
+// bit: an atomic AND on its word of the work mask — other workgroups read other bits of that word (with relaxed atomic loads)
+// and never see theirs change — before the row is counted; every thread fences its ANDs before the ticket, and the last
+// workgroup then moves the words, which it reads past its compute unit's cache, so no clear of another workgroup is missed.
+// The index column is rewritten from union to set index (−1: no member of the block's set), which is what the emitting form
+// delivers as out_vidx and ALL the HBM-bitmap clean-up reads: there every thread re-reads the set indices it stored itself
+// (the row mapping above), no verdict bit.  Bitmap, powers and quorum are the SET's: powers of set s start at entry
+// set_meta[s].x of vpower32, its distinct addresses number set_meta[s].y, its quorum is quorum[s].
 constexpr int BTALLY_RPT = 4;
 constexpr uint32_t BTALLY_MAX_GRID = 2048;  // workgroups of one launch (each takes blocks b, b + grid, …): few ticket arrivals
 struct block_tally_args {
   uint64_t *work_mask;        // verdict words of the launch; consumed (moved to mask / host_mask, zeroed) here
   uint64_t *mask, *host_mask; // host_mask: mapped pinned host memory or null
-  const int32_t *vidx;        // n: validator index of the row's signer (meaningful where the verdict bit is set)
-  const uint32_t *vpower32;   // n_validators × 2·PW pieces
+  int32_t *vidx;              // n: validator index of the row's signer (meaningful where the verdict bit is set), read only;
+                              // sets: in — union index, out — index in the block's set or −1
+  const uint32_t *vpower32;   // n_validators (sets: Σ set sizes) × 2·PW pieces
   const uint32_t *off;        // n_blocks + 1 row offsets
-  uint32_t n, n_blocks, n_validators;
-  uint32_t lds_bitmap;        // ⌈n_validators/32⌉ words of dynamic LDS; 0: `seen` in HBM, and the grid is one workgroup
-  uint32_t *seen;             // ⌈n_validators/32⌉ words, zero between launches (HBM form only)
+  uint32_t n, n_blocks, n_validators;  // (sets: n_validators is the union's size)
+  uint32_t lds_bitmap;        // ⌈n_validators (sets: largest set)/32⌉ words of dynamic LDS; 0: `seen` in HBM, and the grid is one workgroup
+  uint32_t *seen;             // as many words, zero between launches (HBM form only)
   uint64_t *acc;              // TALLY_ACC_WORDS, zero between launches (the ticket)
-  const uint64_t *quorum;     // TALLY_SUM_WORDS
+  const uint64_t *quorum;     // TALLY_SUM_WORDS (sets: n_sets of them)
   uint64_t *out;              // n_blocks × 4 u64 (device memory or mapped pinned host memory)
 };
-template <int PW, int THREADS>
-__global__ void __launch_bounds__(THREADS) block_tally_kernel(block_tally_args a) {
+struct block_tally_sets_args : block_tally_args {
+  const uint32_t *block_set;  // n_blocks, every entry < n_sets (checked on the host)
+  const int32_t *setidx;      // n_sets × n_validators
+  const uint2 *set_meta;      // n_sets × {first power entry, distinct addresses}
+};
+template <int PW, int THREADS, bool SETS>
+__global__ void __launch_bounds__(THREADS)
+    block_tally_kernel(std::conditional_t<SETS, block_tally_sets_args, block_tally_args> a) {
   constexpr int NP = 2 * PW;
   constexpr int WAVES = THREADS / 64;
   constexpr uint32_t STEP = (uint32_t)THREADS * BTALLY_RPT;
@@ -2022,12 +2044,25 @@ __global__ void __launch_bounds__(THREADS) block_tally_kernel(block_tally_args a
   __shared__ uint64_t part[NP + 1][WAVES];
   __shared__ uint32_t last_flag;
   const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-  const uint32_t seen_words = (a.n_validators + 31) / 32;
   uint32_t *bm = a.lds_bitmap ? lseen : a.seen;
+  // a verdict word: under a family other workgroups may atomic-AND other bits of the same word
+  auto mask_word = [&](uint32_t i) -> uint64_t {
+    if constexpr (SETS) return __hip_atomic_load(a.work_mask + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return a.work_mask[i];
+  };
+  // does the row add to its block's power?  (the index is only meaningful where the verdict bit is set; valsets_row says −1 elsewhere)
+  auto counts = [](const valsets_row_t &s) { return (SETS || s.bit) && s.si >= 0; };
   for (uint32_t b = blockIdx.x; b < a.n_blocks; b += gridDim.x) {
     const uint32_t r0 = a.off[b], r1 = a.off[b + 1];
+    uint32_t set = 0, first = 0, members = a.n_validators;  // the block's set: its first power entry, its distinct addresses
+    if constexpr (SETS) {
+      set = a.block_set[b];
+      const uint2 meta = a.set_meta[set];
+      first = meta.x;
+      members = meta.y;
+    }
     if (a.lds_bitmap)
-      for (uint32_t i = tid; i < seen_words; i += THREADS) lseen[i] = 0;
+      for (uint32_t i = tid; i < (members + 31) / 32; i += THREADS) lseen[i] = 0;
     __syncthreads();
     uint64_t p[NP];
 #pragma unroll
@@ -2036,156 +2071,33 @@ __global__ void __launch_bounds__(THREADS) block_tally_kernel(block_tally_args a
     for (uint32_t base = r0; base < r1; base += STEP) {
       bool bit[BTALLY_RPT];
       int vi[BTALLY_RPT];
+      valsets_row_t sr[BTALLY_RPT];  // what the block's tally makes of the row: its verdict bit, the signer's index in the set
       uint32_t pw[BTALLY_RPT][NP];
 #pragma unroll
       for (int j = 0; j < BTALLY_RPT; j++) {
         const uint32_t r = base + (uint32_t)j * THREADS + tid;
-        bit[j] = r < r1 && ((a.work_mask[r >> 6] >> (r & 63)) & 1ull);
+        bit[j] = r < r1 && ((mask_word(r >> 6) >> (r & 63)) & 1ull);
         vi[j] = r < r1 ? a.vidx[r] : -1;
+        if constexpr (!SETS) sr[j] = valsets_row_t{vi[j], bit[j], false};  // the one set: the row as the verdict kernel left it
+      }
+      if constexpr (SETS) {  // union index → index in the block's set: the dependent loads of the step's rows, issued together
+#pragma unroll
+        for (int j = 0; j < BTALLY_RPT; j++) sr[j] = valsets_row(bit[j], vi[j], a.setidx, a.n_validators, set);
       }
 #pragma unroll
       for (int j = 0; j < BTALLY_RPT; j++) {
-        const bool use = bit[j] && vi[j] >= 0;  // (vidx is only meaningful where the verdict bit is set)
 #pragma unroll
-        for (int k = 0; k < NP; k++) pw[j][k] = use ? a.vpower32[(size_t)vi[j] * NP + k] : 0u;
+        for (int k = 0; k < NP; k++) pw[j][k] = counts(sr[j]) ? a.vpower32[((size_t)first + (uint32_t)sr[j].si) * NP + k] : 0u;
       }
 #pragma unroll
       for (int j = 0; j < BTALLY_RPT; j++) {
-        valid += bit[j];
-        if (!bit[j] || vi[j] < 0) continue;  // unknown signers contribute 0 (validator_manager.go:88-92)
-        const uint32_t m = 1u << (vi[j] & 31);
-        if (atomicOr(&bm[vi[j] >> 5], m) & m) continue;  // a signer's power counts once per block (:147-155)
-        distinct++;
-#pragma unroll
-        for (int k = 0; k < NP; k++) p[k] += pw[j][k];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < NP; k++) {
-      const uint64_t s = wave_sum_u64(p[k]);
-      if (lane == 0) part[k][wave] = s;
-    }
-    const uint64_t cnt = wave_sum_u64(valid | (distinct << 32));
-    if (lane == 0) part[NP][wave] = cnt;
-    __syncthreads();
-    if (!a.lds_bitmap)  // the HBM bitmap is left zero for the next block: clear exactly the words this block set
-      for (uint32_t r = r0 + tid; r < r1; r += THREADS)
-        if ((a.work_mask[r >> 6] >> (r & 63)) & 1ull) {
-          const int v = a.vidx[r];
-          if (v >= 0) bm[v >> 5] = 0u;
+        if constexpr (SETS) {
+          const uint32_t r = base + (uint32_t)j * THREADS + tid;
+          if (r < r1) a.vidx[r] = sr[j].si;
+          if (sr[j].clear) atomicAnd(reinterpret_cast<unsigned long long *>(a.work_mask + (r >> 6)), ~(1ull << (r & 63)));
         }
-    if (tid == 0) {
-      uint64_t piece[TALLY_MAX_PIECES], c = 0;
-#pragma unroll
-      for (int k = 0; k < TALLY_MAX_PIECES; k++) {
-        piece[k] = 0;
-        if (k < NP)
-          for (int w = 0; w < WAVES; w++) piece[k] += part[k][w];
-      }
-      for (int w = 0; w < WAVES; w++) c += part[NP][w];
-      uint64_t wd[TALLY_SUM_WORDS];
-      pieces_to_words(piece, NP, wd);
-      uint64_t *o = a.out + 4ull * b;
-      o[0] = wd[0];
-      o[1] = wd[1];
-      o[2] = c;
-      o[3] = words_ge(wd, a.quorum) ? 1ull : 0ull;
-    }
-    __syncthreads();  // part[] and the bitmap are reused by the next block
-  }
-  // ---- every workgroup has read its rows' verdict words: the last one to get here moves and zeroes them ----
-  if (tid == 0) {
-    __threadfence();
-    const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES + 2), 1ull);
-    last_flag = (t == (unsigned long long)gridDim.x - 1ull) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!last_flag) return;
-  const uint32_t words = (a.n + 63) / 64;
-  for (uint32_t i = tid; i < words; i += THREADS) {
-    const uint64_t w = a.work_mask[i];
-    a.work_mask[i] = 0;
-    a.mask[i] = w;
-    if (a.host_mask) a.host_mask[i] = w;
-  }
-  if (tid == 0) __hip_atomic_store(a.acc + TALLY_MAX_PIECES + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The same over a FAMILY of validator sets (ibft_verify_block_seals_sets): the verdict kernels judged every row against the
-// union of the family's addresses and left the signer's UNION index; block b is judged under set block_set[b].  Per row one
-// dependent load more than above — setidx[set][union index] → the index in the block's set (recover_dev.h: valsets_row), issued
-// for the BTALLY_RPT rows of a step together, in front of the powers.  A row whose signer is in the union but not in the
-// block's set loses its verdict bit: an atomic AND on its word of the work mask — other workgroups read other bits of that word
-// and never see theirs change — before the row is counted; the last workgroup (the ticket) then moves the words, which it reads
-// past its compute unit's cache, so no clear of another workgroup is missed.  The index column is rewritten from union to set
-// index (−1: no member of the block's set), which is what the emitting form delivers as out_vidx and what the HBM-bitmap
-// form's clean-up pass reads.  Bitmap, powers and quorum are the SET's: powers of set s start at entry set_meta[s].x of
-// vpower32, its distinct addresses number set_meta[s].y.
-struct block_tally_sets_args {
-  uint64_t *work_mask;
-  uint64_t *mask, *host_mask;
-  int32_t *vidx;              // n: in — union index where the verdict bit is set; out — index in the block's set or −1
-  const uint32_t *vpower32;   // Σ set sizes × 2·PW pieces
-  const uint32_t *off;        // n_blocks + 1 row offsets
-  const uint32_t *block_set;  // n_blocks, every entry < n_sets (checked on the host)
-  const int32_t *setidx;      // n_sets × n_union
-  const uint2 *set_meta;      // n_sets × {first power entry, distinct addresses}
-  const uint64_t *quorum;     // n_sets × TALLY_SUM_WORDS
-  uint32_t n, n_blocks, n_union;
-  uint32_t lds_bitmap;        // ⌈largest set/32⌉ words of dynamic LDS; 0: `seen` in HBM, and the grid is one workgroup
-  uint32_t *seen;             // ⌈largest set/32⌉ words, zero between launches (HBM form only)
-  uint64_t *acc;              // TALLY_ACC_WORDS, zero between launches (the ticket)
-  uint64_t *out;              // n_blocks × 4 u64
-};
-template <int PW, int THREADS>
-__global__ void __launch_bounds__(THREADS) block_tally_sets_kernel(block_tally_sets_args a) {
-  constexpr int NP = 2 * PW;
-  constexpr int WAVES = THREADS / 64;
-  constexpr uint32_t STEP = (uint32_t)THREADS * BTALLY_RPT;
-  extern __shared__ uint32_t lseen[];
-  __shared__ uint64_t part[NP + 1][WAVES];
-  __shared__ uint32_t last_flag;
-  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-  uint32_t *bm = a.lds_bitmap ? lseen : a.seen;
-  for (uint32_t b = blockIdx.x; b < a.n_blocks; b += gridDim.x) {
-    const uint32_t r0 = a.off[b], r1 = a.off[b + 1];
-    const uint32_t set = a.block_set[b];
-    const uint2 meta = a.set_meta[set];
-    if (a.lds_bitmap)
-      for (uint32_t i = tid; i < (meta.y + 31) / 32; i += THREADS) lseen[i] = 0;
-    __syncthreads();
-    uint64_t p[NP];
-#pragma unroll
-    for (int k = 0; k < NP; k++) p[k] = 0;
-    uint64_t valid = 0, distinct = 0;
-    for (uint32_t base = r0; base < r1; base += STEP) {
-      bool bit[BTALLY_RPT];
-      int ui[BTALLY_RPT];
-      valsets_row_t sr[BTALLY_RPT];
-      uint32_t pw[BTALLY_RPT][NP];
-      // Row mapping: row r of the block belongs to thread (r − r0) mod THREADS (STEP is a multiple of THREADS).  The HBM-bitmap
-      // clean-up below REQUIRES the same mapping: there every thread re-reads the set indices it stored itself.
-      // The verdict word is read with a relaxed atomic load: other workgroups may atomic-AND other bits of the same word.
-#pragma unroll
-      for (int j = 0; j < BTALLY_RPT; j++) {
-        const uint32_t r = base + (uint32_t)j * THREADS + tid;
-        bit[j] = r < r1 && ((__hip_atomic_load(a.work_mask + (r >> 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (r & 63)) & 1ull);
-        ui[j] = r < r1 ? a.vidx[r] : -1;
-      }
-#pragma unroll
-      for (int j = 0; j < BTALLY_RPT; j++) sr[j] = valsets_row(bit[j], ui[j], a.setidx, a.n_union, set);
-#pragma unroll
-      for (int j = 0; j < BTALLY_RPT; j++) {
-#pragma unroll
-        for (int k = 0; k < NP; k++) pw[j][k] = sr[j].si >= 0 ? a.vpower32[((size_t)meta.x + (uint32_t)sr[j].si) * NP + k] : 0u;
-      }
-#pragma unroll
-      for (int j = 0; j < BTALLY_RPT; j++) {
-        const uint32_t r = base + (uint32_t)j * THREADS + tid;
-        if (r < r1) a.vidx[r] = sr[j].si;
-        if (sr[j].clear) atomicAnd(reinterpret_cast<unsigned long long *>(a.work_mask + (r >> 6)), ~(1ull << (r & 63)));
         valid += sr[j].bit;
-        if (sr[j].si < 0) continue;  // unknown signers contribute 0 (validator_manager.go:88-92)
+        if (!counts(sr[j])) continue;  // unknown signers contribute 0 (validator_manager.go:88-92)
         const uint32_t m = 1u << (sr[j].si & 31);
         if (atomicOr(&bm[sr[j].si >> 5], m) & m) continue;  // a signer's power counts once per block (:147-155)
         distinct++;
@@ -2201,11 +2113,14 @@ __global__ void __launch_bounds__(THREADS) block_tally_sets_kernel(block_tally_s
     const uint64_t cnt = wave_sum_u64(valid | (distinct << 32));
     if (lane == 0) part[NP][wave] = cnt;
     __syncthreads();
-    if (!a.lds_bitmap)  // the HBM bitmap is left zero for the next block: clear the words this block set (vidx holds set indices,
-      for (uint32_t r = r0 + tid; r < r1; r += THREADS) {  // −1 wherever the row set nothing).  Same row → thread mapping as the
-                                                           // main loop, as required there: each thread re-reads its own stores
-        const int v = a.vidx[r];
-        if (v >= 0) bm[v >> 5] = 0u;
+    if (!a.lds_bitmap)  // the HBM bitmap is left zero for the next block: clear exactly the words this block set
+      for (uint32_t r = r0 + tid; r < r1; r += THREADS) {
+        bool counted = true;  // (sets: vidx holds set indices, −1 wherever the row set nothing)
+        if constexpr (!SETS) counted = (a.work_mask[r >> 6] >> (r & 63)) & 1ull;
+        if (counted) {
+          const int v = a.vidx[r];
+          if (v >= 0) bm[v >> 5] = 0u;
+        }
       }
     if (tid == 0) {
       uint64_t piece[TALLY_MAX_PIECES], c = 0;
@@ -2226,9 +2141,11 @@ __global__ void __launch_bounds__(THREADS) block_tally_sets_kernel(block_tally_s
     }
     __syncthreads();  // part[] and the bitmap are reused by the next block
   }
-  // ---- every workgroup has read its rows' verdict words and cleared what it had to: the last one moves and zeroes them ----
-  __threadfence();  // (every thread: its atomic ANDs are performed before the ticket is taken)
-  __syncthreads();
+  // ---- every workgroup has read its rows' verdict words (and cleared what it had to): the last one moves and zeroes them ----
+  if constexpr (SETS) {
+    __threadfence();  // (every thread: its atomic ANDs are performed before the ticket is taken)
+    __syncthreads();
+  }
   if (tid == 0) {
     __threadfence();
     const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES + 2), 1ull);
@@ -2238,7 +2155,7 @@ __global__ void __launch_bounds__(THREADS) block_tally_sets_kernel(block_tally_s
   if (!last_flag) return;
   const uint32_t words = (a.n + 63) / 64;
   for (uint32_t i = tid; i < words; i += THREADS) {
-    const uint64_t w = __hip_atomic_load(a.work_mask + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t w = mask_word(i);
     a.work_mask[i] = 0;
     a.mask[i] = w;
     if (a.host_mask) a.host_mask[i] = w;

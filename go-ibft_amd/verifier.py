@@ -491,22 +491,47 @@ class BatchVerifier:
         return mask_to_bool(mask, n), t
 
     # chain sync: IsValidCommittedSeal + HasQuorum for many finalized blocks in one call
-    def verify_block_seals(self, block_hash32, seal_off, sig65, signer20, pre_flags=None):
-        """ibft_verify_block_seals: block b's seals are rows [seal_off[b], seal_off[b+1]) and sign block_hash32[b] →
-        (verdict bool[n], Tally array[n_blocks]) — what one is_valid_committed_seal call per block returns"""
-        if not hasattr(self._L, "ibft_verify_block_seals"):
-            raise GpuUnavailable("this build of the library has no ibft_verify_block_seals — rebuild")
+    def _need(self, name: str):
+        if not hasattr(self._L, name):
+            raise GpuUnavailable(f"this build of the library has no {name} — rebuild")
+
+    @staticmethod
+    def _block_columns(seal_off, sig65, pre_flags, *, hashes=None, proposals=None, signer20=None, bare=False, block_set=None):
+        """the columns of a block batch as the C ABI wants them, lengths checked → (head, off, sig, signer, pre, n, n_blocks).
+        head: (block_hash32,) from `hashes`, or (raw, raw_off, round) from `proposals` = (raws, rounds); signer is None for
+        `bare` seals; block_set: the uint32 column of a _sets call, checked to have one entry per block"""
+        head = None if proposals is None else proposal_columns(*proposals)
         off = np.ascontiguousarray(seal_off, dtype=np.uint32)
         nb = len(off) - 1
         if nb < 0:
             raise ValueError("seal_off needs n_blocks + 1 entries")
-        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
+        if head is None:
+            head = (_u8(hashes, (-1, 32)),)
+        s = _u8(sig65, (-1, 65))
+        f = None if bare else _u8(signer20, (-1, 20))
         n = len(s)
-        if len(bh) != nb or len(f) != n or int(off[-1]) != n:
-            raise ValueError("block_hash32 needs one row per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
-        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
-        tallies = (Tally * max(nb, 1))()
+        if (len(head[-1]) != nb or (block_set is not None and len(block_set) != nb) or (f is not None and len(f) != n)
+                or int(off[-1]) != n):
+            what = ("one proposal per block" if proposals is not None else
+                    "block_hash32 / block_set need one row per block" if block_set is not None else
+                    "block_hash32 needs one row per block")
+            raise ValueError(what + ", seal_off[-1] the number of seals")
+        return head, off, s, f, (None if pre_flags is None else _u8(pre_flags)), n, nb
+
+    @staticmethod
+    def _block_outputs(n, nb, emit=False, hashes=False):
+        """what a block batch delivers into → (mask, tallies, signer20, vidx, block_hash32), the last three None unless asked for"""
+        return (np.zeros((n + 63) // 64 or 1, dtype=np.uint64), (Tally * max(nb, 1))(),
+                np.zeros((max(n, 1), 20), dtype=np.uint8) if emit else None,
+                np.full(max(n, 1), -1, dtype=np.int32) if emit else None,
+                np.zeros((max(nb, 1), 32), dtype=np.uint8) if hashes else None)
+
+    def verify_block_seals(self, block_hash32, seal_off, sig65, signer20, pre_flags=None):
+        """ibft_verify_block_seals: block b's seals are rows [seal_off[b], seal_off[b+1]) and sign block_hash32[b] →
+        (verdict bool[n], Tally array[n_blocks]) — what one is_valid_committed_seal call per block returns"""
+        self._need("ibft_verify_block_seals")
+        (bh,), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20)
+        mask, tallies, _, _, _ = self._block_outputs(n, nb)
         self._chk(self._L.ibft_verify_block_seals(self._h, _p(bh), _p(off), nb, _p(s), _p(f), _p(pre), _p(mask), tallies),
                   "ibft_verify_block_seals")
         self._staged = n
@@ -535,31 +560,15 @@ class BatchVerifier:
     def recover_block_seals(self, block_hash32, seal_off, sig65, pre_flags=None):
         """ibft_recover_block_seals: recover_seals for many finalized blocks in one call (rows and offsets as
         verify_block_seals, no signer column) → (signer20 (n, 20), vidx int32[n], verdict bool[n], Tally list[n_blocks])"""
-        if not hasattr(self._L, "ibft_recover_block_seals"):
-            raise GpuUnavailable("this build of the library has no ibft_recover_block_seals — rebuild")
-        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
-        nb = len(off) - 1
-        if nb < 0:
-            raise ValueError("seal_off needs n_blocks + 1 entries")
-        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65))
-        n = len(s)
-        if len(bh) != nb or int(off[-1]) != n:
-            raise ValueError("block_hash32 needs one row per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
-        signer = np.zeros((max(n, 1), 20), dtype=np.uint8)
-        vidx = np.full(max(n, 1), -1, dtype=np.int32)
-        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
-        tallies = (Tally * max(nb, 1))()
+        self._need("ibft_recover_block_seals")
+        (bh,), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, bare=True)
+        mask, tallies, signer, vidx, _ = self._block_outputs(n, nb, emit=True)
         self._chk(self._L.ibft_recover_block_seals(self._h, _p(bh), _p(off), nb, _p(s), _p(pre), _p(signer), _p(vidx), _p(mask),
                                                    tallies), "ibft_recover_block_seals")
         self._staged = 0
         return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb]
 
     # chain sync across validator-set changes: a family of sets on the context, a set per block
-    def _need(self, name: str):
-        if not hasattr(self._L, name):
-            raise GpuUnavailable(f"this build of the library has no {name} — rebuild")
-
     @staticmethod
     def _set_columns(sets, u256: bool):
         """sets: a list of (addrs20, powers) or (height, addrs20, powers) → (heights u64[n_sets], set_off u32[n_sets + 1],
@@ -603,18 +612,10 @@ class BatchVerifier:
         """ibft_verify_block_seals_sets: verify_block_seals with block b judged under set block_set[b] of the installed family
         → (verdict bool[n], Tally list[n_blocks]; quorum is the block's set's)"""
         self._need("ibft_verify_block_seals_sets")
-        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
         bs = np.ascontiguousarray(block_set, dtype=np.uint32)
-        nb = len(off) - 1
-        if nb < 0:
-            raise ValueError("seal_off needs n_blocks + 1 entries")
-        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
-        n = len(s)
-        if len(bh) != nb or len(bs) != nb or len(f) != n or int(off[-1]) != n:
-            raise ValueError("block_hash32 / block_set need one row per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
-        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
-        tallies = (Tally * max(nb, 1))()
+        (bh,), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20,
+                                                           block_set=bs)
+        mask, tallies, _, _, _ = self._block_outputs(n, nb)
         self._chk(self._L.ibft_verify_block_seals_sets(self._h, _p(bh), _p(off), _p(bs), nb, _p(s), _p(f), _p(pre), _p(mask),
                                                        tallies), "ibft_verify_block_seals_sets")
         self._staged = 0
@@ -624,20 +625,9 @@ class BatchVerifier:
         """ibft_recover_block_seals_sets: recover_block_seals with a set per block → (signer20 (n, 20), vidx int32[n] — the index
         in the BLOCK's set or -1 —, verdict bool[n], Tally list[n_blocks])"""
         self._need("ibft_recover_block_seals_sets")
-        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
         bs = np.ascontiguousarray(block_set, dtype=np.uint32)
-        nb = len(off) - 1
-        if nb < 0:
-            raise ValueError("seal_off needs n_blocks + 1 entries")
-        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65))
-        n = len(s)
-        if len(bh) != nb or len(bs) != nb or int(off[-1]) != n:
-            raise ValueError("block_hash32 / block_set need one row per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
-        signer = np.zeros((max(n, 1), 20), dtype=np.uint8)
-        vidx = np.full(max(n, 1), -1, dtype=np.int32)
-        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
-        tallies = (Tally * max(nb, 1))()
+        (bh,), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, bare=True, block_set=bs)
+        mask, tallies, signer, vidx, _ = self._block_outputs(n, nb, emit=True)
         self._chk(self._L.ibft_recover_block_seals_sets(self._h, _p(bh), _p(off), _p(bs), nb, _p(s), _p(pre), _p(signer), _p(vidx),
                                                         _p(mask), tallies), "ibft_recover_block_seals_sets")
         self._staged = 0
@@ -658,21 +648,10 @@ class BatchVerifier:
     def verify_block_seals_raw(self, raws, rounds, seal_off, sig65, signer20, pre_flags=None, want_hashes: bool = True):
         """ibft_verify_block_seals_raw: verify_block_seals with the blocks' PROPOSALS (raws, rounds as for proposal_hashes) in
         place of their hashes → (verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
-        if not hasattr(self._L, "ibft_verify_block_seals_raw"):
-            raise GpuUnavailable("this build of the library has no ibft_verify_block_seals_raw — rebuild")
-        raw, roff, rnd = proposal_columns(raws, rounds)
-        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
-        nb = len(off) - 1
-        if nb < 0:
-            raise ValueError("seal_off needs n_blocks + 1 entries")
-        s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
-        n = len(s)
-        if len(rnd) != nb or len(f) != n or int(off[-1]) != n:
-            raise ValueError("one proposal per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
-        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
-        tallies = (Tally * max(nb, 1))()
-        bh = np.zeros((max(nb, 1), 32), dtype=np.uint8) if want_hashes else None
+        self._need("ibft_verify_block_seals_raw")
+        (raw, roff, rnd), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds),
+                                                                      signer20=signer20)
+        mask, tallies, _, _, bh = self._block_outputs(n, nb, hashes=want_hashes)
         self._chk(self._L.ibft_verify_block_seals_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(f), _p(pre),
                                                       _p(bh), _p(mask), tallies), "ibft_verify_block_seals_raw")
         self._staged = n
@@ -681,23 +660,9 @@ class BatchVerifier:
     def recover_block_seals_raw(self, raws, rounds, seal_off, sig65, pre_flags=None, want_hashes: bool = True):
         """ibft_recover_block_seals_raw: recover_block_seals with the blocks' PROPOSALS in place of their hashes →
         (signer20 (n, 20), vidx int32[n], verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
-        if not hasattr(self._L, "ibft_recover_block_seals_raw"):
-            raise GpuUnavailable("this build of the library has no ibft_recover_block_seals_raw — rebuild")
-        raw, roff, rnd = proposal_columns(raws, rounds)
-        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
-        nb = len(off) - 1
-        if nb < 0:
-            raise ValueError("seal_off needs n_blocks + 1 entries")
-        s = _u8(sig65, (-1, 65))
-        n = len(s)
-        if len(rnd) != nb or int(off[-1]) != n:
-            raise ValueError("one proposal per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
-        signer = np.zeros((max(n, 1), 20), dtype=np.uint8)
-        vidx = np.full(max(n, 1), -1, dtype=np.int32)
-        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
-        tallies = (Tally * max(nb, 1))()
-        bh = np.zeros((max(nb, 1), 32), dtype=np.uint8) if want_hashes else None
+        self._need("ibft_recover_block_seals_raw")
+        (raw, roff, rnd), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds), bare=True)
+        mask, tallies, signer, vidx, bh = self._block_outputs(n, nb, emit=True, hashes=want_hashes)
         self._chk(self._L.ibft_recover_block_seals_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(pre), _p(bh),
                                                        _p(signer), _p(vidx), _p(mask), tallies), "ibft_recover_block_seals_raw")
         self._staged = 0
@@ -714,15 +679,7 @@ class BatchVerifier:
         are kept alive here until the batch is collected; pass ibft_pinned_alloc memory — pinned_copy() — for the copy to
         run under the kernels of the batch before."""
         self._need_block_stream()
-        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
-        nb = len(off) - 1
-        if nb < 0:
-            raise ValueError("seal_off needs n_blocks + 1 entries")
-        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
-        n = len(s)
-        if len(bh) != nb or len(f) != n or int(off[-1]) != n:
-            raise ValueError("block_hash32 needs one row per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
+        (bh,), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20)
         self._chk(self._L.ibft_block_seals_submit(self._h, _p(bh), _p(off), nb, _p(s), _p(f), _p(pre)), "ibft_block_seals_submit")
         self._block_cols = getattr(self, "_block_cols", []) + [(bh, off, s, f, pre)]
         self._staged = n
@@ -754,16 +711,8 @@ class BatchVerifier:
         """ibft_block_seals_submit_raw: the batch of verify_block_seals_raw, enqueued and not waited for → its row count.
         The arrays (the proposal bytes included) are kept alive here until the batch is collected."""
         self._need("ibft_block_seals_submit_raw")
-        raw, roff, rnd = proposal_columns(raws, rounds)
-        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
-        nb = len(off) - 1
-        if nb < 0:
-            raise ValueError("seal_off needs n_blocks + 1 entries")
-        s = _u8(sig65, (-1, 65)); f = _u8(signer20, (-1, 20))
-        n = len(s)
-        if len(rnd) != nb or len(f) != n or int(off[-1]) != n:
-            raise ValueError("one proposal per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
+        (raw, roff, rnd), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds),
+                                                                      signer20=signer20)
         self._chk(self._L.ibft_block_seals_submit_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(f), _p(pre)),
                   "ibft_block_seals_submit_raw")
         self._block_cols = getattr(self, "_block_cols", []) + [(raw, roff, rnd, off, s, f, pre)]
@@ -774,15 +723,7 @@ class BatchVerifier:
     def recover_block_seals_submit(self, block_hash32, seal_off, sig65, pre_flags=None) -> int:
         """ibft_recover_block_seals_submit: the batch of recover_block_seals, enqueued and not waited for → its row count"""
         self._need("ibft_recover_block_seals_submit")
-        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
-        nb = len(off) - 1
-        if nb < 0:
-            raise ValueError("seal_off needs n_blocks + 1 entries")
-        bh = _u8(block_hash32, (-1, 32)); s = _u8(sig65, (-1, 65))
-        n = len(s)
-        if len(bh) != nb or int(off[-1]) != n:
-            raise ValueError("block_hash32 needs one row per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
+        (bh,), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, bare=True)
         self._chk(self._L.ibft_recover_block_seals_submit(self._h, _p(bh), _p(off), nb, _p(s), _p(pre)),
                   "ibft_recover_block_seals_submit")
         self._block_cols = getattr(self, "_block_cols", []) + [(bh, off, s, pre)]
@@ -793,16 +734,7 @@ class BatchVerifier:
     def recover_block_seals_submit_raw(self, raws, rounds, seal_off, sig65, pre_flags=None) -> int:
         """ibft_recover_block_seals_submit_raw: the batch of recover_block_seals_raw, enqueued and not waited for → its row count"""
         self._need("ibft_recover_block_seals_submit_raw")
-        raw, roff, rnd = proposal_columns(raws, rounds)
-        off = np.ascontiguousarray(seal_off, dtype=np.uint32)
-        nb = len(off) - 1
-        if nb < 0:
-            raise ValueError("seal_off needs n_blocks + 1 entries")
-        s = _u8(sig65, (-1, 65))
-        n = len(s)
-        if len(rnd) != nb or int(off[-1]) != n:
-            raise ValueError("one proposal per block, seal_off[-1] the number of seals")
-        pre = None if pre_flags is None else _u8(pre_flags)
+        (raw, roff, rnd), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds), bare=True)
         self._chk(self._L.ibft_recover_block_seals_submit_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(pre)),
                   "ibft_recover_block_seals_submit_raw")
         self._block_cols = getattr(self, "_block_cols", []) + [(raw, roff, rnd, off, s, pre)]

@@ -1,4 +1,4 @@
-"""The per-row decision of block_tally_sets_kernel (recover_dev.h: valset_lookup over the union table, valsets_set_index,
+"""The per-row decision of block_tally_kernel under a family of sets (recover_dev.h: valset_lookup over the union table, valsets_set_index,
 valsets_row), compiled for the host (csrc/host_block_sets_harness.hip), against a Python restatement that knows nothing of
 tables: a set is an ordered list of (address, power) in which a repeated address keeps its FIRST position and its LAST power,
 and the index of an address in a set is its position among the distinct addresses — or −1.  Families are built to hit: an

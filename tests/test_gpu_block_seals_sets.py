@@ -345,7 +345,7 @@ def test_row_counts_of_every_auto_form(total, lo, hi, wide, kernel):
 
 
 def test_largest_set_beyond_the_lds_bitmap():
-    """block_tally_sets_kernel keeps the distinct-signer bitmap of a block in LDS while ⌈largest set / 32⌉ words fit 49 152
+    """block_tally_kernel (its sets form) keeps the distinct-signer bitmap of a block in LDS while ⌈largest set / 32⌉ words fit 49 152
     bytes (the bound of enqueue_block_tally / tally_kernel in csrc/ibftgpu.hip): 393 216 validators.  A set beyond it sends the
     whole launch through the one-workgroup form with the bitmap in HBM."""
     from oracle import binding as B, workload as W

@@ -189,6 +189,56 @@ def test_two_batches_of_different_kinds_in_flight():
         S.same(g, w, f"{k}/{c.name}")
 
 
+def _nine_rows(suffix):
+    """4 validators, blocks of 4, 0 and 5 rows: one seal with r = 0, one by a signer outside the set, one signer twice"""
+    from oracle import binding as B, workload as W
+    r = S.round_of(4)
+    outsider = W.make_round(1, S.SEED + 99, raw_len=64)
+    raws, rounds = [b"nine rows, block %d" % b for b in range(3)], [0, 3, 2**40 + 3]
+    bh = np.frombuffer(b"".join(B.proposal_hash(x, q) for x, q in zip(raws, rounds)), np.uint8).reshape(3, 32).copy()
+    off = np.array([0, 4, 4, 9], np.uint32)
+    sig, signer = np.zeros((9, 65), np.uint8), np.zeros((9, 20), np.uint8)
+    for row, (b, i) in enumerate([(0, 0), (0, 1), (0, 2), (0, 3), (2, 0), (2, 1), (2, None), (2, 3), (2, 0)]):
+        sk, a = (outsider.sks[0], outsider.addrs[0]) if i is None else (r.sks[i], r.addrs[i])
+        s = bytearray(B.sign(sk, S.seal_digest(bytes(bh[b]), suffix)))
+        if row == 2:
+            s[:32] = bytes(32)
+        sig[row] = np.frombuffer(bytes(s), np.uint8)
+        signer[row] = np.frombuffer(bytes(a), np.uint8)
+    return S.Case("v4_nine_rows", r, raws, rounds, bh, off, sig, signer, None)
+
+
+@pytest.mark.parametrize("suffix", [None, S.SUFFIX], ids=["identity", "suffix"])
+def test_a_hashes_given_batch_in_flight_with_a_raw_or_a_recover_batch(suffix):
+    """ibft_block_seals_submit shares slots, streams and kernels with the three newer submits: a batch of it in flight together
+    with a raw / a recover batch, the first collected with ibft_block_seals_collect and the second with _collect_ex, is what
+    the synchronous siblings return"""
+    c = _nine_rows(suffix)
+    V = _V()
+    bv, ref = V.BatchVerifier(max_rows=S.MAX_ROWS), V.BatchVerifier(max_rows=S.MAX_ROWS)
+    try:
+        for x in (bv, ref):
+            x.set_seal_digest(suffix)
+            x.set_validators(c.r.height, c.r.addrs, c.r.power)
+        want = {k: S.sibling(ref, k, c) for k in ("verify", "recover_raw", "verify_raw", "recover")}
+        for second in ("recover_raw", "verify_raw", "recover"):
+            assert S.submit(bv, "verify", c) == 9 and S.submit(bv, second, c) == 9
+            assert bv.block_seals_pending_ex() == (2, 9, 3, 0)
+            m, tl = bv.block_seals_collect()
+            assert bv.block_seals_pending_ex() == (1, 9, 3, S.kind_bits(second))
+            S.same({"kind": 0, "verdict": m, "tallies": tl}, want["verify"], f"verify in front of {second}")
+            S.same(bv.block_seals_collect_ex(), want[second], f"{second} behind verify")
+        assert bv.block_seals_pending_ex() == (0, 0, 0, 0)
+    finally:
+        bv.close()
+        ref.close()
+    v = want["verify"]["verdict"]
+    assert v.tolist() == [True, True, False, True, True, True, False, True, True]
+    assert [t.valid_rows for t in want["verify"]["tallies"]] == [3, 0, 4]
+    assert [t.distinct_senders for t in want["verify"]["tallies"]] == [3, 0, 3]
+    assert (want["recover"]["vidx"] == [0, 1, -1, 3, 0, 1, -1, 3, 0]).all()
+
+
 @pytest.mark.parametrize("kind", S.KINDS)
 def test_pinned_and_pageable_sources_give_the_same(kind):
     seq = [S.cases(None)[i] for i in (5, 7, 4)]

@@ -24,6 +24,9 @@ tuned recovery of every row on --threads cores (orc_verify_seals_tuned_mt: it re
 thread pool of its own and compares the address, which is the cost of recovering it), then ibft_verify_block_seals.  Kernel times are ibft_last_kernel_ms of the
 verdict launch alone.  --parent-lib OLD.so adds a fourth figure: the cold verify launch of ANOTHER build of the library (the
 parent commit's) over the same rows, in child processes that alternate with child processes of this build (IBFT_GPU_LIB).
+With --stream, --parent-lib OLD.so runs the three legs under BOTH builds instead: per alternation one child process of the
+other build, then one of this build, each doing one round of the legs on a context of its own (IBFT_GPU_LIB); median and
+min … max over the alternations per build, and whether this build's streamed median lies inside the other build's spread.
 The lease's ibft_issue_probe value is printed beside every configuration.
 One JSON line per configuration, then a table."""
 import argparse
@@ -339,10 +342,65 @@ def main_recover(a):
               f"{r['kernel_recover_over_verify']:>9.3f} {pv:>12} {pr:>12} {r['host_recover_M_per_s']:>12.3f}")
 
 
+STREAM_LEGS = ("sync_pageable", "sync_pinned", "stream")
+
+
+def stream_child(lib, V_, nb, mode, repeat):
+    """one round of the --stream legs in a fresh process under the library `lib` (None: this build) → its JSON line"""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k != "IBFT_GPU_LIB"}
+    if lib:
+        env["IBFT_GPU_LIB"] = lib
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--stream-child", "--v", str(V_), "--blocks", str(nb), "--modes", mode,
+                        "--repeat", str(repeat)], capture_output=True, text=True, timeout=300, env=env)
+    if p.returncode != 0:   # (nothing more is started on the device after a child that failed)
+        raise RuntimeError(f"stream child under {lib or 'this build'} failed ({p.returncode}): {p.stdout[-500:]}{p.stderr[-1500:]}")
+    return json.loads(p.stdout.strip().split("\n")[-1])
+
+
+def measure_stream_ab(parent_lib, V_, nb, mode, repeat, alternations):
+    got = {"parent": {k: [] for k in STREAM_LEGS}, "this": {k: [] for k in STREAM_LEGS}}
+    for _ in range(alternations):
+        for side, lib in (("parent", parent_lib), ("this", None)):
+            r = stream_child(lib, V_, nb, mode, repeat)
+            for k in STREAM_LEGS:
+                got[side][k].append(r[k + "_ms"])
+    res = {"v": V_, "blocks": nb, "rows": r["rows"], "mode": mode, "alternations": alternations, "cold_lanes": r["cold_lanes"],
+           "warm_lanes": r["warm_lanes"]}
+    for side in got:
+        for k, ts in got[side].items():
+            res[f"{k}_{side}_ms"] = float(np.median(ts))
+            res[f"{k}_{side}_min_ms"] = min(ts)
+            res[f"{k}_{side}_max_ms"] = max(ts)
+            res[f"{k}_{side}_all_ms"] = [round(t, 4) for t in ts]
+    res["stream_this_over_parent"] = res["stream_this_ms"] / res["stream_parent_ms"]
+    res["stream_this_inside_parent_spread"] = res["stream_parent_min_ms"] <= res["stream_this_ms"] <= res["stream_parent_max_ms"]
+    return res
+
+
 def main_stream(a):
     shapes = [(4, 16), (4, 16384), (100, 1), (100, 16), (100, 256), (100, 655), (1024, 16), (1024, 64)]
     if a.v != [4, 100, 1024] or a.blocks != ["1", "16", "256", "max"]:
         shapes = [(V_, 65536 // (V_ * a.repeat) if bs == "max" else int(bs)) for V_ in a.v for bs in a.blocks]
+    if a.parent_lib:
+        rows = []
+        for V_, nb in shapes:
+            if nb < 1 or nb * V_ * a.repeat > 65536:
+                continue
+            for mode in a.modes:
+                rows.append(measure_stream_ab(a.parent_lib, V_, nb, mode, a.repeat, a.alternations))
+                print(json.dumps(rows[-1]), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                for res in rows:
+                    f.write(json.dumps(res) + "\n")
+        cell = lambda r, k: f"{r[k + '_ms']:.3f} ({r[k + '_min_ms']:.3f}…{r[k + '_max_ms']:.3f})"
+        print(f"{'V':>5} {'blocks':>6} {'mode':>5} {'sync pinned: parent':>22} {'this':>22} {'streamed: parent':>22} {'this':>22} {'this/parent':>11} {'inside':>6}")
+        for r in rows:
+            print(f"{r['v']:>5} {r['blocks']:>6} {r['mode']:>5} {cell(r, 'sync_pinned_parent'):>22} {cell(r, 'sync_pinned_this'):>22} "
+                  f"{cell(r, 'stream_parent'):>22} {cell(r, 'stream_this'):>22} {r['stream_this_over_parent']:>11.3f} "
+                  f"{'yes' if r['stream_this_inside_parent_spread'] else 'NO':>6}")
+        return
     rows = []
     for V_, nb in shapes:
         if nb < 1 or nb * V_ * a.repeat > 65536:
@@ -377,11 +435,16 @@ def main():
     ap.add_argument("--rows", type=int, nargs="*", default=[4096, 16384, 65500], help="--recover: rows per call (rounded down to whole blocks)")
     ap.add_argument("--threads", type=int, default=16, help="--recover: cores of the host route's recovery")
     ap.add_argument("--parent-lib", type=str, default=None, help="--recover: another build of libibftgpu.so whose cold verify "
-                    "launch is timed over the same rows in alternating child processes")
+                    "launch is timed over the same rows in alternating child processes; --stream: the legs under both builds, "
+                    "in alternating child processes")
+    ap.add_argument("--stream-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--kernel-leg", type=str, default=None, choices=["recover", "verify"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.kernel_leg:
         return kernel_leg(a.v[0], a.rows[0], a.kernel_leg)
+    if a.stream_child:
+        print(json.dumps(measure_stream(a.v[0], int(a.blocks[0]), a.modes[0] == "warm", a.repeat, 1)), flush=True)
+        return
     if a.recover:
         return main_recover(a)
     if a.stream:
