@@ -249,15 +249,12 @@ uint32_t dev_addr_hash(const uint8_t *addr20) {
   return ibftk::addr_hash(a);
 }
 
-// The emitting cold kernels' epilogue (recover_dev.h: emit_row) behind the lane kernel's recovery, over a validator table built
-// as ibft_set_validators builds it (open addressing, 6 dwords per slot, a repeated address keeps its first index).
-// out_addr20: what the row stores; *out_vidx: its validator index; returns the verdict bit.
-int dev_emit_row(const uint8_t *digest32, const uint8_t *sig65, uint32_t flags, int pre, const uint8_t *addrs20, uint32_t n_validators,
-                 uint8_t *out_addr20, int32_t *out_vidx) {
-  dev_gtab_init();
+// A validator table built as ibft_set_validators builds it (open addressing, 6 dwords per slot, a repeated address keeps its first
+// index); returns the slot mask.
+static uint32_t build_vtab(const uint8_t *addrs20, uint32_t n_validators, std::vector<uint32_t> &tab) {
   uint32_t slots = 64;
   while (slots < 2 * n_validators + 2) slots <<= 1;
-  std::vector<uint32_t> tab((size_t)slots * 6, 0u);
+  tab.assign((size_t)slots * 6, 0u);
   uint32_t next = 0;
   for (uint32_t i = 0; i < n_validators; i++) {
     uint32_t a[5];
@@ -274,14 +271,37 @@ int dev_emit_row(const uint8_t *digest32, const uint8_t *sig65, uint32_t flags, 
       s = (s + 1) & (slots - 1);
     }
   }
-  uint32_t got[5];
+  return slots - 1;
+}
+static bool recover_row(const uint8_t *digest32, const uint8_t *sig65, uint32_t flags, uint32_t got[5]) {
+  dev_gtab_init();
   ibftk::aff Qa;
-  const bool rec = ibftk::recover_pubkey_with(g_gtab.data(), secp::from_be32(digest32), secp::from_be32(sig65), secp::from_be32(sig65 + 32),
-                                              sig65[64], flags, got, Qa, ibftk::var_mult_private<false>{});
-  const ibftk::emitted e = ibftk::emit_row(rec, pre != 0, got, tab.data(), slots - 1);
+  return ibftk::recover_pubkey_with(g_gtab.data(), secp::from_be32(digest32), secp::from_be32(sig65), secp::from_be32(sig65 + 32), sig65[64],
+                                    flags, got, Qa, ibftk::var_mult_private<false>{});
+}
+// The cold kernels' decision behind the lane kernel's recovery (recover_dev.h).  dev_emit_row: the emitting form (emit_row) —
+// out_addr20: what the row stores; *out_vidx: its validator index; returns the verdict bit.  dev_claim_row: the claimed-signer
+// form (claim_row) for a row that claims claimed20 — *out_vidx: the index of the CLAIMED address; returns the verdict bit.
+int dev_emit_row(const uint8_t *digest32, const uint8_t *sig65, uint32_t flags, int pre, const uint8_t *addrs20, uint32_t n_validators,
+                 uint8_t *out_addr20, int32_t *out_vidx) {
+  std::vector<uint32_t> tab;
+  const uint32_t slot_mask = build_vtab(addrs20, n_validators, tab);
+  uint32_t got[5];
+  const bool rec = recover_row(digest32, sig65, flags, got);
+  const ibftk::emitted e = ibftk::emit_row(rec, pre != 0, got, tab.data(), slot_mask);
   memcpy(out_addr20, e.addr, 20);
   *out_vidx = e.vi;
   return e.bit ? 1 : 0;
+}
+int dev_claim_row(const uint8_t *digest32, const uint8_t *sig65, uint32_t flags, int pre, const uint8_t *addrs20, uint32_t n_validators,
+                  const uint8_t *claimed20, int32_t *out_vidx) {
+  std::vector<uint32_t> tab;
+  const uint32_t slot_mask = build_vtab(addrs20, n_validators, tab);
+  uint32_t got[5], want[5];
+  memcpy(want, claimed20, 20);
+  const bool rec = recover_row(digest32, sig65, flags, got);
+  *out_vidx = ibftk::valset_lookup(tab.data(), slot_mask, want);
+  return ibftk::claim_row(rec, pre != 0, got, want, *out_vidx) ? 1 : 0;
 }
 
 // §8f rank 3: the device wire walker on the CPU.  out: row_info (80 B) ‖ digest (32) ‖ sig (65) ‖ from (20)

@@ -572,6 +572,80 @@ void recount_built(ibft_ctx *c) {  // c->dev->mu held
   c->seen_build_epoch = c->dev->build_epoch;
 }
 
+// A runtime choice — the mode, the lanes per signature, where a table lives — as the template argument of a kernel:
+// f(std::integral_constant<int, V>{}) for the V of the list that equals v, for the LAST of the list when none does.
+template <int V, int... Rest, class F>
+void with_int(int v, F &&f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, V>{});
+  else if (v == V) f(std::integral_constant<int, V>{});
+  else with_int<Rest...>(v, f);
+}
+template <class F>
+void with_cold_mode(int mode, F &&f) { with_int<ibftk::MODE_SEALS, ibftk::MODE_EMIT, ibftk::MODE_SENDERS>(mode, f); }
+template <class F>
+void with_warm_mode(int mode, F &&f) { with_int<ibftk::MODE_SEALS, ibftk::MODE_SENDERS>(mode, f); }  // (the verify kernels know no MODE_EMIT)
+
+// one verdict kernel over `items` rows (or wavefronts), per_block of them in a workgroup of `threads`
+template <class K>
+void launch_verdict(ibft_ctx *c, const ibftk::recover_args &a, K kernel, uint32_t items, uint32_t per_block, uint32_t threads) {
+  hipLaunchKernelGGL(kernel, dim3((items + per_block - 1) / per_block), dim3(threads), 0, c->stream, a);
+}
+
+// the warm kernel with G lanes per signature: 1 the LDS-staged lane kernel, 64 one wavefront per signature, groups between
+void launch_warm(ibft_ctx *c, const ibftk::recover_args &a, uint32_t n, int mode, uint32_t G) {
+  with_warm_mode(mode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    if (G == 1)
+      launch_verdict(c, a, ibftk::verify_known_lane_kernel<MODE>, n, ibftk::ROWS_PER_BLOCK, ibftk::ROWS_PER_BLOCK);
+    else if (G == 64)
+      launch_verdict(c, a, ibftk::verify_known_wave_kernel<MODE>, n, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
+    else
+      with_int<32, 16, 8, 4, 2>((int)G, [&](auto GG) {
+        constexpr int LANES = decltype(GG)::value;
+        launch_verdict(c, a, ibftk::verify_known_group_kernel<MODE, LANES>, n, 64 / LANES, 64);
+      });
+  });
+}
+
+// the cold kernel with CG lanes per signature: 128 two wavefronts, 64 one, 16 the row forms (four signatures per wavefront, with
+// or without a helper wavefront), 8 / 4 / 2 lane groups, 1 the LDS-staged lane kernel; sets what ibft_last_cold_table reports
+void launch_cold(ibft_ctx *c, const ibftk::recover_args &a, uint32_t n, int mode, uint32_t CG) {
+  with_cold_mode(mode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    if (CG == 128) {
+      launch_verdict(c, a, ibftk::ecrecover_wave2_kernel<MODE>, n, ibftk::PAIRS_PER_BLOCK, 128 * ibftk::PAIRS_PER_BLOCK);
+    } else if (CG == 64) {
+      launch_verdict(c, a, ibftk::ecrecover_wave_kernel<MODE>, n, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
+    } else if (CG == 16) {
+      const uint32_t waves = (n + 3) / 4;
+      const bool pair = c->rows_pair_force >= 0 ? c->rows_pair_force != 0 : (uint64_t)n <= c->rows_pair_max;
+      if (pair)
+        launch_verdict(c, a, ibftk::ecrecover_rows_pair_kernel<MODE>, waves, ibftk::ROWS_PAIRS_PER_BLOCK, 128 * ibftk::ROWS_PAIRS_PER_BLOCK);
+      else
+        launch_verdict(c, a, ibftk::ecrecover_rows_kernel<MODE>, waves, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
+    } else if (CG > 1) {
+      // the lanes' window tables: LDS (no private segment) unless pinned otherwise (IBFT_COLD_TABLE=private: round 4's form, A/B)
+      const bool lds_tab = c->cold_table_force != 2;
+      with_int<8, 4, 2>((int)CG, [&](auto GG) {
+        with_int<ibftk::TAB_LDS, ibftk::TAB_PRIVATE_PREFETCH>(lds_tab ? ibftk::TAB_LDS : ibftk::TAB_PRIVATE_PREFETCH, [&](auto TT) {
+          constexpr int LANES = decltype(GG)::value, TAB = decltype(TT)::value;
+          launch_verdict(c, a, ibftk::ecrecover_group_kernel<MODE, LANES, TAB>, n, 64 / LANES, 64);
+        });
+      });
+      c->last_cold_table = lds_tab ? 1 : 2;
+    } else {
+      // one lane per signature: up to one wavefront per SIMD offered (n ≤ 65 536) the table lives in LDS; beyond, in the private
+      // segment WITHOUT the prefetch — 256 registers, two resident wavefronts per SIMD (15 against 18 ns per verify)
+      const uint32_t tab = c->cold_table_force ? c->cold_table_force : ((uint64_t)n <= 65536ull ? 1u : 3u);
+      with_int<ibftk::TAB_LDS, ibftk::TAB_PRIVATE_PREFETCH, ibftk::TAB_PRIVATE>(
+          tab == 1 ? ibftk::TAB_LDS : tab == 2 ? ibftk::TAB_PRIVATE_PREFETCH : ibftk::TAB_PRIVATE, [&](auto TT) {
+            launch_verdict(c, a, ibftk::ecrecover_lane_kernel<MODE, decltype(TT)::value>, n, ibftk::ROWS_PER_BLOCK, ibftk::ROWS_PER_BLOCK);
+          });
+      c->last_cold_table = tab;
+    }
+  });
+}
+
 // Batches just beyond what one wavefront per SIMD can take (65 536 rows through the lane kernel with its tables in LDS): the
 // private-segment form that serves everything larger keeps TWO wavefronts on as many SIMDs as there are rows beyond 65 536 — and
 // the launch lasts as long as those: 1.72 ms for 70 000 rows where 65 536 take 0.92 (profiles/r06j_kernel_ab.txt).  Up to
@@ -636,37 +710,8 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
     } else if (c->kernel != IBFT_KERNEL_LANE) {
       while (G < 64 && (uint64_t)n * (G * 2) <= 65536ull) G *= 2;
     }
-    if (G > 1) {
-      if ((rc_clean = clean_mask(c))) return rc_clean;
-      const uint32_t rows_per_wave = 64 / G;
-      dim3 grid((n + rows_per_wave - 1) / rows_per_wave), block(64);
-#define IBFT_LAUNCH_GROUP(GG)                                                                                  \
-  if (mode == 0)                                                                                               \
-    hipLaunchKernelGGL((ibftk::verify_known_group_kernel<0, GG>), grid, block, 0, c->stream, a);               \
-  else                                                                                                         \
-    hipLaunchKernelGGL((ibftk::verify_known_group_kernel<1, GG>), grid, block, 0, c->stream, a);
-      const dim3 wgrid((n + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES), wblock(64 * ibftk::WAVE_KERNEL_WAVES);
-      switch (G) {
-        case 64:
-          if (mode == 0)
-            hipLaunchKernelGGL(ibftk::verify_known_wave_kernel<0>, wgrid, wblock, 0, c->stream, a);
-          else
-            hipLaunchKernelGGL(ibftk::verify_known_wave_kernel<1>, wgrid, wblock, 0, c->stream, a);
-          break;
-        case 32: IBFT_LAUNCH_GROUP(32) break;
-        case 16: IBFT_LAUNCH_GROUP(16) break;
-        case 8: IBFT_LAUNCH_GROUP(8) break;
-        case 4: IBFT_LAUNCH_GROUP(4) break;
-        default: IBFT_LAUNCH_GROUP(2) break;
-      }
-#undef IBFT_LAUNCH_GROUP
-    } else {
-      dim3 grid((n + ibftk::ROWS_PER_BLOCK - 1) / ibftk::ROWS_PER_BLOCK), block(ibftk::ROWS_PER_BLOCK);
-      if (mode == 0)
-        hipLaunchKernelGGL(ibftk::verify_known_lane_kernel<0>, grid, block, 0, c->stream, a);
-      else
-        hipLaunchKernelGGL(ibftk::verify_known_lane_kernel<1>, grid, block, 0, c->stream, a);
-    }
+    if (G > 1 && (rc_clean = clean_mask(c))) return rc_clean;  // (the lane kernel stores whole verdict words)
+    launch_warm(c, a, n, mode, G);
     c->last_group = G;
     HIPCHK(c, hipGetLastError());
     c->warm_passes++;
@@ -679,9 +724,7 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
     c->last_cold_group = 0;
     return IBFT_OK;
   }
-  // cold kernel: lane groups when the batch is too small to fill the chip (and nothing is warm:
-  // with a warm kernel in front only the stragglers are left and the group kernel's atomicOr
-  // merge needs the mask it already holds)
+  // cold kernel: lane groups when the batch is too small to fill the chip
   uint32_t CG = 1;
   if (c->cold_group_force) {
     CG = c->cold_group_force;
@@ -693,93 +736,10 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
     else if ((uint64_t)n * 4 <= 65536ull) CG = 4;
     else if ((uint64_t)n * 2 <= 65536ull) CG = 2;
   }
-  if (CG == 16) {
-    if (!warm && (rc_clean = clean_mask(c))) return rc_clean;
-    const uint32_t waves = (n + 3) / 4;
-    const bool pair = c->rows_pair_force >= 0 ? c->rows_pair_force != 0 : (uint64_t)n <= c->rows_pair_max;
-    if (pair) {
-      const dim3 pgrid((waves + ibftk::ROWS_PAIRS_PER_BLOCK - 1) / ibftk::ROWS_PAIRS_PER_BLOCK), pblock(128 * ibftk::ROWS_PAIRS_PER_BLOCK);
-      if (mode == 0)
-        hipLaunchKernelGGL(ibftk::ecrecover_rows_pair_kernel<0>, pgrid, pblock, 0, c->stream, a);
-      else if (mode == ibftk::MODE_EMIT)
-        hipLaunchKernelGGL(ibftk::ecrecover_rows_pair_kernel<ibftk::MODE_EMIT>, pgrid, pblock, 0, c->stream, a);
-      else
-        hipLaunchKernelGGL(ibftk::ecrecover_rows_pair_kernel<1>, pgrid, pblock, 0, c->stream, a);
-    } else {
-      const dim3 rgrid((waves + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES), rblock(64 * ibftk::WAVE_KERNEL_WAVES);
-      if (mode == 0)
-        hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<0>, rgrid, rblock, 0, c->stream, a);
-      else if (mode == ibftk::MODE_EMIT)
-        hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<ibftk::MODE_EMIT>, rgrid, rblock, 0, c->stream, a);
-      else
-        hipLaunchKernelGGL(ibftk::ecrecover_rows_kernel<1>, rgrid, rblock, 0, c->stream, a);
-    }
-  } else if (CG == 128) {
-    if (!warm && (rc_clean = clean_mask(c))) return rc_clean;
-    const dim3 pgrid((n + ibftk::PAIRS_PER_BLOCK - 1) / ibftk::PAIRS_PER_BLOCK), pblock(128 * ibftk::PAIRS_PER_BLOCK);
-    if (mode == 0)
-      hipLaunchKernelGGL(ibftk::ecrecover_wave2_kernel<0>, pgrid, pblock, 0, c->stream, a);
-    else if (mode == ibftk::MODE_EMIT)
-      hipLaunchKernelGGL(ibftk::ecrecover_wave2_kernel<ibftk::MODE_EMIT>, pgrid, pblock, 0, c->stream, a);
-    else
-      hipLaunchKernelGGL(ibftk::ecrecover_wave2_kernel<1>, pgrid, pblock, 0, c->stream, a);
-  } else if (CG == 64) {
-    if (!warm && (rc_clean = clean_mask(c))) return rc_clean;
-    if (mode == 0)
-      hipLaunchKernelGGL(ibftk::ecrecover_wave_kernel<0>, dim3((n + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES),
-                         dim3(64 * ibftk::WAVE_KERNEL_WAVES), 0, c->stream, a);
-    else if (mode == ibftk::MODE_EMIT)
-      hipLaunchKernelGGL(ibftk::ecrecover_wave_kernel<ibftk::MODE_EMIT>, dim3((n + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES),
-                         dim3(64 * ibftk::WAVE_KERNEL_WAVES), 0, c->stream, a);
-    else
-      hipLaunchKernelGGL(ibftk::ecrecover_wave_kernel<1>, dim3((n + ibftk::WAVE_KERNEL_WAVES - 1) / ibftk::WAVE_KERNEL_WAVES),
-                         dim3(64 * ibftk::WAVE_KERNEL_WAVES), 0, c->stream, a);
-  } else if (CG > 1) {
-    if (!warm && (rc_clean = clean_mask(c))) return rc_clean;
-    const uint32_t rows_per_wave = 64 / CG;
-    dim3 cgrid((n + rows_per_wave - 1) / rows_per_wave), cblock(64);
-    // the lanes' window tables: LDS (no private segment) unless pinned otherwise (IBFT_COLD_TABLE=private: round 4's form, A/B)
-    const bool lds_tab = c->cold_table_force != 2;
-#define IBFT_LAUNCH_COLD(GG)                                                                                          \
-  if (mode == 0 && lds_tab)                                                                                           \
-    hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<0, GG, ibftk::TAB_LDS>), cgrid, cblock, 0, c->stream, a);       \
-  else if (mode == 0)                                                                                                 \
-    hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<0, GG, ibftk::TAB_PRIVATE_PREFETCH>), cgrid, cblock, 0, c->stream, a); \
-  else if (mode == ibftk::MODE_EMIT && lds_tab)                                                                       \
-    hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<ibftk::MODE_EMIT, GG, ibftk::TAB_LDS>), cgrid, cblock, 0, c->stream, a); \
-  else if (mode == ibftk::MODE_EMIT)                                                                                  \
-    hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<ibftk::MODE_EMIT, GG, ibftk::TAB_PRIVATE_PREFETCH>), cgrid, cblock, 0, c->stream, a); \
-  else if (lds_tab)                                                                                                   \
-    hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<1, GG, ibftk::TAB_LDS>), cgrid, cblock, 0, c->stream, a);       \
-  else                                                                                                                \
-    hipLaunchKernelGGL((ibftk::ecrecover_group_kernel<1, GG, ibftk::TAB_PRIVATE_PREFETCH>), cgrid, cblock, 0, c->stream, a);
-    switch (CG) {
-      case 8: IBFT_LAUNCH_COLD(8) break;
-      case 4: IBFT_LAUNCH_COLD(4) break;
-      default: IBFT_LAUNCH_COLD(2) break;
-    }
-#undef IBFT_LAUNCH_COLD
-    c->last_cold_table = lds_tab ? 1 : 2;
-  } else {
-    dim3 grid((n + ibftk::ROWS_PER_BLOCK - 1) / ibftk::ROWS_PER_BLOCK), block(ibftk::ROWS_PER_BLOCK);
-    // one lane per signature: up to one wavefront per SIMD offered (n ≤ 65 536) the table lives in LDS; beyond, in the private
-    // segment WITHOUT the prefetch — 256 registers, two resident wavefronts per SIMD (15 against 18 ns per verify)
-    const uint32_t tab = c->cold_table_force ? c->cold_table_force : ((uint64_t)n <= 65536ull ? 1u : 3u);
-#define IBFT_LAUNCH_LANE(TT)                                                                       \
-  if (mode == 0)                                                                                   \
-    hipLaunchKernelGGL((ibftk::ecrecover_lane_kernel<0, TT>), grid, block, 0, c->stream, a);       \
-  else if (mode == ibftk::MODE_EMIT)                                                               \
-    hipLaunchKernelGGL((ibftk::ecrecover_lane_kernel<ibftk::MODE_EMIT, TT>), grid, block, 0, c->stream, a); \
-  else                                                                                             \
-    hipLaunchKernelGGL((ibftk::ecrecover_lane_kernel<1, TT>), grid, block, 0, c->stream, a);
-    switch (tab) {
-      case 1: IBFT_LAUNCH_LANE(ibftk::TAB_LDS) break;
-      case 2: IBFT_LAUNCH_LANE(ibftk::TAB_PRIVATE_PREFETCH) break;
-      default: IBFT_LAUNCH_LANE(ibftk::TAB_PRIVATE) break;
-    }
-#undef IBFT_LAUNCH_LANE
-    c->last_cold_table = tab;
-  }
+  // every form but the lane kernel ORs its bits into the mask: clean unless a warm kernel in front has already cleaned and
+  // written it (the lane kernel merges the bits of decided rows into its whole words instead)
+  if (CG > 1 && !warm && (rc_clean = clean_mask(c))) return rc_clean;
+  launch_cold(c, a, n, mode, CG);
   c->last_cold_group = CG;
   HIPCHK(c, hipGetLastError());
   if (time_it) HIPCHK(c, hipEventRecord(e1, c->stream));
@@ -2456,7 +2416,7 @@ int ibft_seals_submit(ibft_ctx *c) {
   int rc;
   // The verdict launch writes the CURRENT pair of work mask / validator indices; its last reader was the tally of pass k − 2
   // (collected, or the two-in-flight check above would have refused) or something the main stream is already behind.
-  if ((rc = enqueue_recover(c, c->staged_n, c->staged_pre, 0, time_it))) return rc;
+  if ((rc = enqueue_recover(c, c->staged_n, c->staged_pre, ibftk::MODE_SEALS, time_it))) return rc;
   // Side-stream tally: not for a rank of a sharded batch (its exchange follows the tally on the main stream) and not while
   // keys are still being learned (the tally passes the device's learned-key counter on; with every table built nothing moves it)
   const bool all_warm = c->cache_on && c->my_built >= c->n_validators;
@@ -2790,7 +2750,7 @@ static int messages_launch_locked(ibft_ctx *c, const uint8_t *payload, const uin
   if (converted && (rc = apply_seal_digest(c, half, (uint32_t)n, true))) return rc;
   c->ev_used = 0;
   const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
-  if ((rc = enqueue_recover(c, rows, false, 0, time_it))) return rc;
+  if ((rc = enqueue_recover(c, rows, false, ibftk::MODE_SEALS, time_it))) return rc;
   ibftk::set_args sa{};
   sa.sender_pre = sender_pre ? d_pre : nullptr;
   sa.valid_pre = valid_pre ? d_pre + half : nullptr;
@@ -3644,7 +3604,7 @@ static int senders_launch_locked(ibft_ctx *c, const uint8_t *payload, const uint
   c->staged_n = (uint32_t)n;
   c->staged_pre = pre_flags != nullptr;
   c->ev_used = 0;
-  if ((rc = enqueue_recover(c, (uint32_t)n, pre_flags != nullptr, 1, true))) return rc;
+  if ((rc = enqueue_recover(c, (uint32_t)n, pre_flags != nullptr, ibftk::MODE_SENDERS, true))) return rc;
   return enqueue_tally(c, (uint32_t)n);
 }
 
@@ -3689,7 +3649,7 @@ int ibft_verify_senders_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint3
     HIPCHK(c, hipGetLastError());
   }
   // the digest column now holds keccak256(PayloadNoSig): the sender check is the seal-style pass (mode 0)
-  if ((rc = enqueue_recover(c, (uint32_t)n, true, 0, true))) return rc;
+  if ((rc = enqueue_recover(c, (uint32_t)n, true, ibftk::MODE_SEALS, true))) return rc;
   if ((rc = enqueue_tally(c, (uint32_t)n))) return rc;
   if (out_rows && n)
     HIPCHK(c, hipMemcpyAsync(out_rows, c->d_wire_rows.p, n * sizeof(ibft_wire_row_t), hipMemcpyDeviceToHost, c->stream));
@@ -3770,7 +3730,7 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
   c->ev_used = 0;
   const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
   // with the pre column: wavefronts whose rows are all dead (the seal rows of PREPAREs, other views, odd encodings) exit at once
-  if ((rc = enqueue_recover(c, half + (uint32_t)n, true, 0, time_it))) return rc;
+  if ((rc = enqueue_recover(c, half + (uint32_t)n, true, ibftk::MODE_SEALS, time_it))) return rc;
   ibftk::set_args sa{};
   sa.hash32 = converted ? (const uint8_t *)c->d_hash_copy.p : d_hash + 32ull * half;
   sa.hash_len = (const uint8_t *)c->d_hash_len.p;
@@ -3938,12 +3898,12 @@ int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const 
   c->ev_used = 0;
   // the verdict launch over all rows of all levels: the digest column holds keccak256(PayloadNoSig) — the seal-style pass; rows that
   // are not judged here (and, with two launches, the deferred rows) are pre-flagged
-  if ((rc = enqueue_recover(c, rows, true, 0, false))) return rc;
+  if ((rc = enqueue_recover(c, rows, true, ibftk::MODE_SEALS, false))) return rc;
   if (two) {
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_cert_join, 0));
     // the deferred rows' verdict words: zero whatever an earlier call left there (the first launch only vouches for its own words)
     HIPCHK(c, hipMemsetAsync((uint64_t *)c->d_mask.p + region / 64, 0, (size_t)mask_words(carriers) * 8, c->stream));
-    if ((rc = enqueue_recover(c, carriers, true, 0, false, region, true))) return rc;
+    if ((rc = enqueue_recover(c, carriers, true, ibftk::MODE_SEALS, false, region, true))) return rc;
     hipLaunchKernelGGL(ibftk::cert_scatter_kernel, dim3((carriers + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)d_slot, carriers, region,
                        (uint64_t *)c->d_mask.p);
     HIPCHK(c, hipGetLastError());

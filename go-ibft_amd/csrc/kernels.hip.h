@@ -10,6 +10,7 @@
 //   ecrecover_lane_kernel       a2  IsValidCommittedSeal  (core/ibft.go:943)      cold path,
 //   ecrecover_group_kernel<G>   a3  IsValidValidator      (core/ibft.go:1128)     1 / 2,4,8 lanes per signature
 //   ecrecover_wave_kernel           same, one wavefront per signature (limbs spread over lanes, wave_fe_dev.h)
+//   ecrecover_wave2_kernel          same, plus a helper wavefront per signature (scalars, u1·G)
 //   ecrecover_rows_kernel           same, sixteen lanes (one DPP row) per signature, four signatures per wavefront
 //   ecrecover_rows_pair_kernel      same, plus a helper wavefront per four signatures (scalars, u1·G) on the same SIMD
 //   verify_known_lane_kernel    a2/a3 against the validator's known key (warm path), 1 lane per signature
@@ -27,6 +28,9 @@
 // pre_flags N) — structure-of-arrays at field granularity.  The lane kernels stage a block's
 // 64 rows through LDS with coalesced dword loads and each lane unpacks its own row into limbs held
 // in VGPRs; the group kernels read their row directly (the G lanes of a group share the address).
+// The verdict kernels (ecrecover_*, verify_known_*) share their row head (row_sig, row_digest, claimed_signer, row_pre /
+// row_done), the warm decision (warm_decide, warm_mark) and the cold verdict tail (cold_tail): below recover_args.  Two of the nine
+// still spell their own: ecrecover_lane_kernel (LDS-staged rows, whole verdict words) and verify_known_group_kernel.
 // Rule for every kernel here: no call to an outlined device function under a partial EXEC mask
 // (see secp256k1_dev.h:wave_any) — idle lanes compute on dummy operands and skip only stores.
 #pragma once
@@ -51,15 +55,9 @@ using secp::u256;
 
 constexpr int ROWS_PER_BLOCK = 64; // one wavefront per block in the lane kernel
 
-// (validator table lookup — valset_lookup — and the emitting form's decision — emit_row — live in recover_dev.h: the CPU harness
-// compiles them too)
+// (validator table lookup — valset_lookup — and a row's decision once the curve is done — emit_row, claim_row — live in
+// recover_dev.h: the CPU harness compiles them too)
 
-// ---- warm path: remember a recovered key, exactly once per validator ---------------------------
-// Several valid rows of the SAME validator in one cold batch are normal (PREPARE + COMMIT of one
-// sender, round-change envelopes + certificate messages): the 0→1 transition of pub_state is claimed
-// with a compare-and-swap and only the winner stores the key and counts it, so that `learned` is the
-// number of validators with a key — the host compares it with n_validators to drop the cold kernel
-// (learn_key, below recover_args).
 // ---- host columns → HBM in one launch --------------------------------------------------------------------
 // A batch arrives as 4–9 separate byte columns.  One hipMemcpyAsync per column costs ≈8 µs of host time each and the
 // copies run one behind the other (profiles/r02h_seq_*: 134 µs before the first kernel of a COMMIT set).  When the
@@ -405,6 +403,11 @@ __device__ __forceinline__ int key_slot(const recover_args &a, int vi) { return 
 // (claimed by one build pass: keys that become KNOWN while the pass runs wait for the next one) → BUILT (the table is complete)
 constexpr uint32_t KEY_UNKNOWN = 0, KEY_KNOWN = 1, KEY_BUILT = 2, KEY_WRITING = 3, KEY_BUILDING = 5;
 
+// ---- warm path: remember a recovered key, exactly once per validator ---------------------------
+// Several valid rows of the SAME validator in one cold batch are normal (PREPARE + COMMIT of one
+// sender, round-change envelopes + certificate messages): the 0→1 transition of pub_state is claimed
+// with a compare-and-swap and only the winner stores the key and counts it, so that `learned` is the
+// number of validators with a key — the host compares it with n_validators to drop the cold kernel.
 __device__ __forceinline__ void learn_key(const recover_args &a, int vi, const aff &Qa) {
   if (!a.pub_state) return;
   const int sl = key_slot(a, vi);
@@ -430,6 +433,101 @@ __device__ __forceinline__ void emit_store(const recover_args &a, uint32_t row, 
 __device__ __forceinline__ void emit_store_none(const recover_args &a, uint32_t row) {
   const uint32_t none[5] = {0u, 0u, 0u, 0u, 0u};
   emit_store(a, row, emit_row(false, true, none, a.vtab, a.vslot_mask));
+}
+
+// ---- what every verdict kernel does around its own arithmetic, written once ------------------------------------------------------
+// ROW HEAD: a row's operands straight from the HBM columns (the lane kernels stage theirs through LDS instead: stage_rows).
+__device__ __forceinline__ void row_sig(const recover_args &a, uint32_t row, u256 &r, u256 &s) {
+  r = secp::from_be32(a.sig65 + 65ull * row);
+  s = secp::from_be32(a.sig65 + 65ull * row + 32);
+}
+__device__ __forceinline__ uint32_t row_recid(const recover_args &a, uint32_t row) { return a.sig65[65ull * row + 64]; }
+__device__ __forceinline__ void row_sig(const recover_args &a, uint32_t row, u256 &r, u256 &s, uint32_t &v) {
+  row_sig(a, row, r, s);
+  v = row_recid(a, row);
+}
+// the digest the row's signature is over: its hash32 row, or (MODE_SENDERS) keccak256 of its payload row
+template <int MODE>
+__device__ __forceinline__ u256 row_digest(const recover_args &a, uint32_t row) {
+  u256 z;
+  if (MODE != MODE_SENDERS) {
+    z = secp::from_be32(a.hash32 + 32ull * row);
+  } else {
+    uint64_t d[4];
+    hash_range_dwords(a.payload + a.off[row], a.off[row + 1] - a.off[row], d);
+    keccak::digest_to_limbs(d, z.v);
+  }
+  return z;
+}
+// the address the row claims (MODE_EMIT claims none: zeros) ...
+template <int MODE>
+__device__ __forceinline__ void claimed_address(const recover_args &a, uint32_t row, uint32_t want[5]) {
+#pragma unroll
+  for (int i = 0; i < 5; i++) want[i] = MODE != MODE_EMIT ? reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i] : 0u;
+}
+// ... and its index in the validator set: membership is "the signer address is one of the validators" (backend.go:44, 53-54); -1: no
+// member (MODE_EMIT: not known before the curve)
+template <int MODE>
+__device__ __forceinline__ int claimed_signer(const recover_args &a, uint32_t row, uint32_t want[5]) {
+  claimed_address<MODE>(a, row, want);
+  return MODE != MODE_EMIT ? valset_lookup(a.vtab, a.vslot_mask, want) : -1;
+}
+// pre: the caller's pre_flags ruled the row out; done: the warm kernel in front already produced its verdict
+__device__ __forceinline__ bool row_pre(const recover_args &a, uint32_t row) { return a.pre_flags && a.pre_flags[row] != 0; }
+__device__ __forceinline__ bool row_done(const recover_args &a, uint32_t row) { return a.warm_done && a.warm_done[row] != 0; }
+// a row that still needs a verdict (need = live && !done) has to go over the curve unless it is pre-flagged or claims a non-member
+template <int MODE>
+__device__ __forceinline__ bool needs_curve(bool need, bool pre, int vi) {
+  return need && !pre && (MODE == MODE_EMIT || vi >= 0);
+}
+// every kernel but the lane kernels ORs its rows' bits into a mask the host cleaned
+__device__ __forceinline__ void verdict_or(const recover_args &a, uint32_t row) {
+  atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
+}
+
+// WARM DECISION: decided by the warm kernel are pre-flagged rows and non-members (verdict false) and rows whose validator has a
+// table (slot sl); the cold kernel behind it skips the rows marked here.
+struct warm_row {
+  int vi, sl;
+  bool have_table, decided;
+};
+__device__ __forceinline__ warm_row warm_decide(const recover_args &a, bool pre, const uint32_t want[5]) {
+  warm_row w;
+  w.vi = valset_lookup(a.vtab, a.vslot_mask, want);
+  w.sl = w.vi >= 0 ? key_slot(a, w.vi) : -1;
+  w.have_table = w.sl >= 0 && a.pub_state[w.sl] == KEY_BUILT;
+  w.decided = pre || w.vi < 0 || w.have_table;
+  return w;
+}
+__device__ __forceinline__ void warm_mark(const recover_args &a, uint32_t row, const warm_row &w) {
+  a.warm_done[row] = w.decided ? 1 : 0;
+  if (w.decided) a.vidx[row] = w.vi;
+}
+
+// VERDICT TAIL of the cold kernels.  rec: the curve gave a key and `got` is its address; report: this lane speaks for the row; need
+// false (the warm kernel decided the row, or it lies past n and recomputed row n − 1): no bit and no store.
+// cold_decide: the row's bit.  MODE_EMIT: from the recovered address — stored here, its index left in vi (recover_dev.h:
+// emit_row); otherwise: got == want of a member (recover_dev.h: claim_row), the index column is the caller's.
+template <int MODE>
+__device__ __forceinline__ bool cold_decide(const recover_args &a, uint32_t row, bool report, bool rec, bool pre, bool need,
+                                            const uint32_t got[5], const uint32_t want[5], int &vi) {
+  if (MODE == MODE_EMIT) {
+    const emitted e = emit_row(rec, pre, got, a.vtab, a.vslot_mask);
+    if (report && need) emit_store(a, row, e);
+    vi = e.vi;
+    return need && e.bit;
+  }
+  return claim_row(rec && need, pre, got, want, vi);
+}
+// ... and what a set bit brings with it: the key (it hashes to a member's address) is remembered for the warm path
+template <int MODE>
+__device__ __forceinline__ void cold_tail(const recover_args &a, uint32_t row, bool report, bool rec, bool pre, bool need,
+                                          const uint32_t got[5], const uint32_t want[5], int vi, const aff &Qa) {
+  const bool ok = cold_decide<MODE>(a, row, report, rec, pre, need, got, want, vi);
+  if (report && ok) {
+    learn_key(a, vi, Qa);
+    verdict_or(a, row);
+  }
 }
 
 // Stage the block's rows through LDS (coalesced dword loads) and unpack this lane's row.
@@ -548,21 +646,14 @@ __global__ void __launch_bounds__(ROWS_PER_BLOCK) verify_known_lane_kernel(recov
   __shared__ __attribute__((aligned(16))) uint8_t lds[ROWS_PER_BLOCK * (65 + 32 + 20)];
   row_regs q = stage_rows<MODE>(a, lds);
   const uint32_t lane = threadIdx.x;
-  int vi = valset_lookup(a.vtab, a.vslot_mask, q.want);
-  const int sl = vi >= 0 ? key_slot(a, vi) : -1;
-  const bool have_table = sl >= 0 && a.pub_state[sl] == KEY_BUILT;
-  // decided here: pre-flagged rows and non-members (verdict false), and rows whose validator has a table
-  const bool decided = q.live && (q.pre || vi < 0 || have_table);
-  const bool crypto = q.live && !q.pre && have_table;
+  const warm_row w = warm_decide(a, q.pre, q.want);
+  const bool crypto = q.live && !q.pre && w.have_table;
   bool ok = false;
   if (__any(crypto ? 1 : 0)) {  // wave-uniform: every lane runs the arithmetic, idle ones on a dummy table
-    const uint32_t tv = crypto ? (uint32_t)sl : a.dummy_validator;
+    const uint32_t tv = crypto ? (uint32_t)w.sl : a.dummy_validator;
     ok = verify_known(a.gtab, a.qtab + QTAB_DWORDS_PER_VALIDATOR * tv, q.z, q.r, q.s, q.v, a.flags) && crypto;
   }
-  if (q.live) {
-    a.warm_done[q.row] = decided ? 1 : 0;
-    if (decided) a.vidx[q.row] = vi;
-  }
+  if (q.live) warm_mark(a, q.row, w);
   uint64_t bal = __ballot(ok);
   if (lane == 0) a.mask[blockIdx.x * (uint32_t)ROWS_PER_BLOCK >> 6] = bal;
 }
@@ -606,7 +697,7 @@ __global__ void __launch_bounds__(64) verify_known_group_kernel(recover_args a) 
   u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
   const uint32_t v = a.sig65[65ull * row + 64];
   u256 z;
-  if (MODE == 0) {
+  if (MODE == MODE_SEALS) {
     z = secp::from_be32(a.hash32 + 32ull * row);
   } else {
     uint64_t d[4];
@@ -712,32 +803,17 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) verify_known_wave_kern
   const uint32_t row = blockIdx.x * WAVE_KERNEL_WAVES + (threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63u;
   if (row >= a.n) return;  // whole wavefront
-  const bool pre = a.pre_flags && a.pre_flags[row] != 0;
-  const u256 r = secp::from_be32(a.sig65 + 65ull * row);
-  const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
-  const uint32_t v = a.sig65[65ull * row + 64];
-  u256 z;
-  if (MODE == 0) {
-    z = secp::from_be32(a.hash32 + 32ull * row);
-  } else {
-    uint64_t d[4];
-    hash_range_dwords(a.payload + a.off[row], a.off[row + 1] - a.off[row], d);
-    keccak::digest_to_limbs(d, z.v);
-  }
-  uint32_t want[5];
-#pragma unroll
-  for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
-  const int vi = valset_lookup(a.vtab, a.vslot_mask, want);
-  const int sl = vi >= 0 ? key_slot(a, vi) : -1;
-  const bool have_table = sl >= 0 && a.pub_state[sl] == KEY_BUILT;
-  const bool decided = pre || vi < 0 || have_table;
-  if (lane == 0) {
-    a.warm_done[row] = decided ? 1 : 0;
-    if (decided) a.vidx[row] = vi;
-  }
-  if (pre || !have_table) return;  // wave-uniform: the wavefront holds one row
-  const bool ok = wv::verify_known_wave(a.gtab, a.qtab + QTAB_DWORDS_PER_VALIDATOR * (uint32_t)sl, z, r, s, v, a.flags);
-  if (lane == 0 && ok) atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
+  const bool pre = row_pre(a, row);
+  u256 r, s;
+  uint32_t v, want[5];
+  row_sig(a, row, r, s, v);
+  const u256 z = row_digest<MODE>(a, row);
+  claimed_address<MODE>(a, row, want);
+  const warm_row w = warm_decide(a, pre, want);
+  if (lane == 0) warm_mark(a, row, w);
+  if (pre || !w.have_table) return;  // wave-uniform: the wavefront holds one row
+  const bool ok = wv::verify_known_wave(a.gtab, a.qtab + QTAB_DWORDS_PER_VALIDATOR * (uint32_t)w.sl, z, r, s, v, a.flags);
+  if (lane == 0 && ok) verdict_or(a, row);
 }
 
 // ---- cold path with G = 2, 4 or 8 lanes per signature ----------------------------------------
@@ -762,25 +838,16 @@ __global__ void __launch_bounds__(64) ecrecover_group_kernel(recover_args a) {
   const uint32_t row_raw = blockIdx.x * ROWS + lane / G;
   const bool live = row_raw < a.n;
   const uint32_t row = live ? row_raw : a.n - 1;
-  const bool pre = a.pre_flags && a.pre_flags[row] != 0;
-  const bool done = a.warm_done && a.warm_done[row] != 0;
+  const bool pre = row_pre(a, row);
+  const bool done = row_done(a, row);
   const bool need = live && !done;
   if (!__any(need ? 1 : 0)) return;
 
-  u256 r = secp::from_be32(a.sig65 + 65ull * row);
-  u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
-  const uint32_t v = a.sig65[65ull * row + 64];
-  u256 z;
-  if (MODE != MODE_SENDERS) {
-    z = secp::from_be32(a.hash32 + 32ull * row);
-  } else {
-    uint64_t d[4];
-    hash_range_dwords(a.payload + a.off[row], a.off[row + 1] - a.off[row], d);
-    keccak::digest_to_limbs(d, z.v);
-  }
-  uint32_t want[5];
-#pragma unroll
-  for (int i = 0; i < 5; i++) want[i] = MODE != MODE_EMIT ? reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i] : 0u;
+  u256 r, s;
+  uint32_t v, want[5];
+  row_sig(a, row, r, s, v);
+  const u256 z = row_digest<MODE>(a, row);
+  claimed_address<MODE>(a, row, want);  // (looked up behind the curve: the index is not held in a register across it)
 
   bool ok = sig_in_range(r, s, v, a.flags);
   // R = (r, y), y² = r³ + 7, parity(y) = v
@@ -966,24 +1033,9 @@ __global__ void __launch_bounds__(64) ecrecover_group_kernel(recover_args a) {
   u256 qx = secp::l26_to_u256(Qa.x), qy = secp::l26_to_u256(Qa.y);
   uint32_t got[5];
   keccak::address_from_xy(qx.v, qy.v, got);
-  int vi;
-  if (MODE == MODE_EMIT) {
-    const emitted e = emit_row(ok, pre, got, a.vtab, a.vslot_mask);
-    if (sub == 0 && need) emit_store(a, row, e);
-    ok = e.bit;
-    vi = e.vi;
-  } else {
-    ok = ok && need && !pre;
-#pragma unroll
-    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
-    vi = valset_lookup(a.vtab, a.vslot_mask, want);
-    ok = ok && vi >= 0;
-    if (sub == 0 && need) a.vidx[row] = vi;
-  }
-  if (sub == 0 && need) {
-    if (ok) learn_key(a, vi, Qa);
-    if (ok) atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
-  }
+  const int vi = MODE != MODE_EMIT ? valset_lookup(a.vtab, a.vslot_mask, want) : -1;
+  if (MODE != MODE_EMIT && sub == 0 && need) a.vidx[row] = vi;
+  cold_tail<MODE>(a, row, sub == 0, ok, pre, need, got, want, vi, Qa);
 }
 
 // ---- cold path, ONE WAVEFRONT PER SIGNATURE (wave_fe_dev.h) --------------------------------------
@@ -996,52 +1048,26 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) ecrecover_wave_kernel(
   const uint32_t row = blockIdx.x * WAVE_KERNEL_WAVES + (threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63u;
   if (row >= a.n) return;                            // whole wavefront
-  if (a.warm_done && a.warm_done[row] != 0) return;  // decided by the warm kernel
+  if (row_done(a, row)) return;                      // decided by the warm kernel
   uint32_t want[5];
-  int vi = -1;
-  if (MODE != MODE_EMIT) {
-#pragma unroll
-    for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
-    vi = valset_lookup(a.vtab, a.vslot_mask, want);
+  const int vi = claimed_signer<MODE>(a, row, want);
+  const bool pre = row_pre(a, row);
+  // the wavefront holds ONE row: the index goes out first, and a row that does not need the curve leaves here — its verdict
+  // stays 0 (the mask was cleared by the host before the launch), MODE_EMIT stores zeros and -1 for a pre-flagged one
+  if (MODE != MODE_EMIT && lane == 0) a.vidx[row] = vi;
+  if (!needs_curve<MODE>(true, pre, vi)) {
+    if (MODE == MODE_EMIT && lane == 0) emit_store_none(a, row);
+    return;
   }
-  const bool pre = a.pre_flags && a.pre_flags[row] != 0;
-  if (MODE == MODE_EMIT) {
-    if (pre) {  // nothing to recover: zeros, -1, verdict 0
-      if (lane == 0) emit_store_none(a, row);
-      return;
-    }
-  } else {
-    if (lane == 0) a.vidx[row] = vi;
-    if (pre || vi < 0) return;  // verdict stays 0 (mask was cleared by the host before the launch)
-  }
-  const u256 r = secp::from_be32(a.sig65 + 65ull * row);
-  const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
-  const uint32_t v = a.sig65[65ull * row + 64];
-  u256 z;
-  if (MODE != MODE_SENDERS) {
-    z = secp::from_be32(a.hash32 + 32ull * row);
-  } else {
-    uint64_t d[4];
-    hash_range_dwords(a.payload + a.off[row], a.off[row + 1] - a.off[row], d);
-    keccak::digest_to_limbs(d, z.v);
-  }
+  u256 r, s;
+  uint32_t v;
+  row_sig(a, row, r, s, v);
+  const u256 z = row_digest<MODE>(a, row);
   uint32_t got[5];
   aff Qa;
   __shared__ uint32_t krow_scr[WAVE_KERNEL_WAVES][wv::KROW_SCRATCH_DWORDS];  // the address hash's transposition: wave-private LDS
-  bool ok = wv::recover_pubkey_wave(a.gtab, z, r, s, v, a.flags, got, Qa, krow_scr[threadIdx.x >> 6]);
-  if (MODE == MODE_EMIT) {
-    const emitted e = emit_row(ok, false, got, a.vtab, a.vslot_mask);
-    if (lane == 0) emit_store(a, row, e);
-    ok = e.bit;
-    vi = e.vi;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
-  }
-  if (lane == 0 && ok) {
-    learn_key(a, vi, Qa);
-    atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
-  }
+  const bool rec = wv::recover_pubkey_wave(a.gtab, z, r, s, v, a.flags, got, Qa, krow_scr[threadIdx.x >> 6]);
+  cold_tail<MODE>(a, row, lane == 0, rec, false, true, got, want, vi, Qa);
 }
 
 // ---- cold path, TWO WAVEFRONTS PER SIGNATURE (n ≤ 512: round 4) ----------------------------------------------------
@@ -1062,56 +1088,33 @@ __global__ void __launch_bounds__(128 * PAIRS_PER_BLOCK) ecrecover_wave2_kernel(
   const uint32_t row_raw = blockIdx.x * PAIRS_PER_BLOCK + slot;
   const bool live = row_raw < a.n;
   const uint32_t row = live ? row_raw : a.n - 1;
-  const bool done = a.warm_done && a.warm_done[row] != 0;
+  const bool done = row_done(a, row);
+  const bool need = live && !done;
+  const bool report = !helper && lane == 0;  // helper wavefronts never store
   uint32_t want[5];
-  int vi = -1;
-  if (MODE != MODE_EMIT) {
-#pragma unroll
-    for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
-    vi = valset_lookup(a.vtab, a.vslot_mask, want);
-  }
-  const bool pre = a.pre_flags && a.pre_flags[row] != 0;
-  if (MODE != MODE_EMIT && !helper && lane == 0 && live && !done) a.vidx[row] = vi;
-  // the same for both wavefronts of the pair (MODE_EMIT: membership is not known before the recovery)
-  const bool active = live && !done && !pre && (MODE == MODE_EMIT || vi >= 0);
+  const int vi = claimed_signer<MODE>(a, row, want);
+  const bool pre = row_pre(a, row);
+  if (MODE != MODE_EMIT && report && need) a.vidx[row] = vi;
   auto sync = [] { __syncthreads(); };
-  if (!active) {  // (wave-uniform) nothing to recover: keep the workgroup's barrier count
-    if (MODE == MODE_EMIT && !helper && lane == 0 && live && !done) emit_store_none(a, row);  // (a pre_flags row)
+  // (wave-uniform, the same for both wavefronts of the pair) nothing to recover: keep the workgroup's barrier count
+  if (!needs_curve<MODE>(need, pre, vi)) {
+    if (MODE == MODE_EMIT && report && need) emit_store_none(a, row);  // (a pre_flags row)
     sync();
     sync();
     return;
   }
-  const u256 r = secp::from_be32(a.sig65 + 65ull * row);
-  const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
-  const uint32_t v = a.sig65[65ull * row + 64];
-  u256 z;
-  if (MODE != MODE_SENDERS) {
-    z = secp::from_be32(a.hash32 + 32ull * row);
-  } else {
-    uint64_t d[4];
-    hash_range_dwords(a.payload + a.off[row], a.off[row + 1] - a.off[row], d);
-    keccak::digest_to_limbs(d, z.v);
-  }
+  u256 r, s;
+  uint32_t v;
+  row_sig(a, row, r, s, v);
+  const u256 z = row_digest<MODE>(a, row);
   if (helper) {
     wv::recover_helper_wave(a.gtab, z, r, s, &sh[slot], sync);
     return;
   }
   uint32_t got[5];
   aff Qa;
-  bool ok = wv::recover_pubkey_wave<99, true>(a.gtab, z, r, s, v, a.flags, got, Qa, krow_scr[slot], &sh[slot], sync);
-  if (MODE == MODE_EMIT) {
-    const emitted e = emit_row(ok, false, got, a.vtab, a.vslot_mask);
-    if (lane == 0) emit_store(a, row, e);
-    ok = e.bit;
-    vi = e.vi;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
-  }
-  if (lane == 0 && ok) {
-    learn_key(a, vi, Qa);
-    atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
-  }
+  const bool rec = wv::recover_pubkey_wave<99, true>(a.gtab, z, r, s, v, a.flags, got, Qa, krow_scr[slot], &sh[slot], sync);
+  cold_tail<MODE>(a, row, lane == 0, rec, false, true, got, want, vi, Qa);
 }
 
 // ---- cold path, SIXTEEN LANES PER SIGNATURE: every row of a wavefront recovers its own signature ------
@@ -1128,50 +1131,27 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) __attribute__((amdgpu_
   const uint32_t row_raw = wave * 4u + (lane >> 4);
   const bool live = row_raw < a.n;
   const uint32_t row = live ? row_raw : a.n - 1;
+  const bool report = (lane & 15u) == 0;  // the first lane of a DPP row speaks for its signature
   uint32_t want[5];
-  int vi = -1;
-  if (MODE != MODE_EMIT) {
-#pragma unroll
-    for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
-    vi = valset_lookup(a.vtab, a.vslot_mask, want);
-  }
-  const bool pre = a.pre_flags && a.pre_flags[row] != 0;
-  const bool done = a.warm_done && a.warm_done[row] != 0;
+  const int vi = claimed_signer<MODE>(a, row, want);
+  const bool pre = row_pre(a, row);
+  const bool done = row_done(a, row);
   const bool need = live && !done;
-  if (MODE != MODE_EMIT && need && (lane & 15u) == 0) a.vidx[row] = vi;
-  if (!__any((need && !pre && (MODE == MODE_EMIT || vi >= 0)) ? 1 : 0)) {  // nothing in this wavefront needs the curve
-    if (MODE == MODE_EMIT && need && (lane & 15u) == 0) emit_store_none(a, row);  // (every row left is a pre_flags row)
+  if (MODE != MODE_EMIT && report && need) a.vidx[row] = vi;
+  if (!__any(needs_curve<MODE>(need, pre, vi) ? 1 : 0)) {  // nothing in this wavefront needs the curve
+    if (MODE == MODE_EMIT && report && need) emit_store_none(a, row);  // (every row left is a pre_flags row)
     return;
   }
-  const u256 r = secp::from_be32(a.sig65 + 65ull * row);
-  const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
-  const uint32_t v = a.sig65[65ull * row + 64];
-  u256 z;
-  if (MODE != MODE_SENDERS) {
-    z = secp::from_be32(a.hash32 + 32ull * row);
-  } else {
-    uint64_t d[4];
-    hash_range_dwords(a.payload + a.off[row], a.off[row + 1] - a.off[row], d);
-    keccak::digest_to_limbs(d, z.v);
-  }
+  u256 r, s;
+  uint32_t v;
+  row_sig(a, row, r, s, v);
+  const u256 z = row_digest<MODE>(a, row);
   uint32_t got[5];
   aff Qa;
   __shared__ uint32_t row_tab[WAVE_KERNEL_WAVES][wv::ROW_TAB_SLOTS * 64];  // the window tables: wave-private LDS
-  bool ok = wv::recover_pubkey_row(a.gtab, z, r, s, v, a.flags, got, Qa, row_tab[threadIdx.x >> 6]);
-  if (MODE == MODE_EMIT) {  // (rows past n recomputed the last row: `need` keeps them from storing it again)
-    const emitted e = emit_row(ok, pre, got, a.vtab, a.vslot_mask);
-    if (need && (lane & 15u) == 0) emit_store(a, row, e);
-    ok = need && e.bit;
-    vi = e.vi;
-  } else {
-    ok = ok && need && !pre && vi >= 0;
-#pragma unroll
-    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
-  }
-  if ((lane & 15u) == 0 && ok) {
-    learn_key(a, vi, Qa);
-    atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
-  }
+  const bool rec = wv::recover_pubkey_row(a.gtab, z, r, s, v, a.flags, got, Qa, row_tab[threadIdx.x >> 6]);
+  // (rows past n recomputed the last row: `need` keeps them from storing it again)
+  cold_tail<MODE>(a, row, report, rec, pre, need, got, want, vi, Qa);
 }
 
 // ---- the same, TWO WAVEFRONTS PER FOUR SIGNATURES (2 048 < n ≤ 4 096, where the kernel above runs one wavefront per SIMD) --
@@ -1193,57 +1173,33 @@ __global__ void __launch_bounds__(128 * ROWS_PAIRS_PER_BLOCK) ecrecover_rows_pai
   const uint32_t row_raw = wave * 4u + (lane >> 4);
   const bool live = row_raw < a.n;
   const uint32_t row = live ? row_raw : a.n - 1;
+  const bool report = !helper && (lane & 15u) == 0;  // helper wavefronts never store
   uint32_t want[5];
-  int vi = -1;
-  if (MODE != MODE_EMIT) {
-#pragma unroll
-    for (int i = 0; i < 5; i++) want[i] = reinterpret_cast<const uint32_t *>(a.signer20 + 20ull * row)[i];
-    vi = valset_lookup(a.vtab, a.vslot_mask, want);
-  }
-  const bool pre = a.pre_flags && a.pre_flags[row] != 0;
-  const bool done = a.warm_done && a.warm_done[row] != 0;
+  const int vi = claimed_signer<MODE>(a, row, want);
+  const bool pre = row_pre(a, row);
+  const bool done = row_done(a, row);
   const bool need = live && !done;
-  if (MODE != MODE_EMIT && !helper && need && (lane & 15u) == 0) a.vidx[row] = vi;
+  if (MODE != MODE_EMIT && report && need) a.vidx[row] = vi;
   auto sync = [] { __syncthreads(); };
   // (wave-uniform, the same for both wavefronts of the pair: in MODE_EMIT from pre_flags and `live` alone)
-  if (!__any((need && !pre && (MODE == MODE_EMIT || vi >= 0)) ? 1 : 0)) {
-    if (MODE == MODE_EMIT && !helper && need && (lane & 15u) == 0) emit_store_none(a, row);  // (every row left is a pre_flags row)
+  if (!__any(needs_curve<MODE>(need, pre, vi) ? 1 : 0)) {
+    if (MODE == MODE_EMIT && report && need) emit_store_none(a, row);  // (every row left is a pre_flags row)
     sync();
     sync();
     return;
   }
-  const u256 r = secp::from_be32(a.sig65 + 65ull * row);
-  const u256 s = secp::from_be32(a.sig65 + 65ull * row + 32);
-  if (helper) {
-    u256 z;
-    if (MODE != MODE_SENDERS) {
-      z = secp::from_be32(a.hash32 + 32ull * row);
-    } else {
-      uint64_t d[4];
-      hash_range_dwords(a.payload + a.off[row], a.off[row + 1] - a.off[row], d);
-      keccak::digest_to_limbs(d, z.v);
-    }
-    wv::recover_helper_row(a.gtab, z, r, s, &sh[slot], sync);
+  u256 r, s;
+  row_sig(a, row, r, s);
+  if (helper) {  // only the helper needs the digest ...
+    wv::recover_helper_row(a.gtab, row_digest<MODE>(a, row), r, s, &sh[slot], sync);
     return;
   }
-  const uint32_t v = a.sig65[65ull * row + 64];
+  const uint32_t v = row_recid(a, row);  // ... and only the main wavefront the recovery id
   uint32_t got[5];
   aff Qa;
-  bool ok = wv::recover_pubkey_row<99, true>(a.gtab, secp::zero256(), r, s, v, a.flags, got, Qa, row_tab[slot], &sh[slot], sync);
-  if (MODE == MODE_EMIT) {  // (rows past n recomputed the last row: `need` keeps them from storing it again)
-    const emitted e = emit_row(ok, pre, got, a.vtab, a.vslot_mask);
-    if (need && (lane & 15u) == 0) emit_store(a, row, e);
-    ok = need && e.bit;
-    vi = e.vi;
-  } else {
-    ok = ok && need && !pre && vi >= 0;
-#pragma unroll
-    for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
-  }
-  if ((lane & 15u) == 0 && ok) {
-    learn_key(a, vi, Qa);
-    atomicOr(reinterpret_cast<unsigned long long *>(a.mask + (row >> 6)), 1ull << (row & 63));
-  }
+  const bool rec = wv::recover_pubkey_row<99, true>(a.gtab, secp::zero256(), r, s, v, a.flags, got, Qa, row_tab[slot], &sh[slot], sync);
+  // (rows past n recomputed the last row: `need` keeps them from storing it again)
+  cold_tail<MODE>(a, row, (lane & 15u) == 0, rec, pre, need, got, want, vi, Qa);
 }
 
 // ---- warm path table build -------------------------------------------------------------------

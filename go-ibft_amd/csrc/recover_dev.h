@@ -136,6 +136,15 @@ __host__ __device__ __forceinline__ emitted emit_row(bool rec, bool pre, const u
   e.bit = e.vi >= 0;
   return e;
 }
+// ---- claimed-signer form (IsValidCommittedSeal / IsValidValidator): the row's verdict once the curve is done ----------------
+// want: the address the row claims, vi: its index in the validator set (-1: no member).  The bit: a key was recovered, the row is
+// not pre-flagged, the recovered address IS the claimed one, and that address is a member.
+__host__ __device__ __forceinline__ bool claim_row(bool rec, bool pre, const uint32_t got[5], const uint32_t want[5], int vi) {
+  bool ok = rec && !pre && vi >= 0;
+#pragma unroll
+  for (int i = 0; i < 5; i++) ok = ok && (got[i] == want[i]);
+  return ok;
+}
 
 // ---- fixed-base table: gtab[w][e] = e * 2^(B·w) * G, affine ------------------------------
 // Each entry is 20 dwords: x then y, ten 26-bit limbs each (the kernels' native form, so a

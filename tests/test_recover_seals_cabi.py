@@ -2,7 +2,8 @@
 header declares the two symbols, the C entry points refuse NULL arguments before touching the device and leave the out buffers
 alone, the binding names the symbols and raises GpuUnavailable against a library without them, and the emitting kernels' shared
 epilogue (recover_dev.h: emit_row), compiled for the host, equals oracle.recover_address + ValSet.index on honest rows, on
-every rejection class, on a non-member's valid signature and on a pre-flagged row."""
+every rejection class, on a non-member's valid signature and on a pre-flagged row.  Its sibling for the rows that CLAIM a signer
+(recover_dev.h: claim_row, the decision of the other two modes of the same kernels) is held to oracle.verify_seals the same way."""
 import ctypes as C
 import os
 import re
@@ -32,6 +33,8 @@ def dev():
     L = C.CDLL(build.build_host_harness())
     L.dev_emit_row.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(C.c_int32)]
     L.dev_emit_row.restype = C.c_int
+    L.dev_claim_row.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_char_p, C.POINTER(C.c_int32)]
+    L.dev_claim_row.restype = C.c_int
     return L
 
 
@@ -193,3 +196,45 @@ def test_epilogue_rejection_classes_non_member_and_pre_flag(dev):
     vs_rep = B.ValSet(rep, np.ones(len(rep), np.uint64))
     s1 = B.sign(sks[1], d)
     assert _emit(dev, d, s1, 0, 0, rep) == _expect(vs_rep, d, s1, 0, 0)
+
+
+# ---- the claimed-signer form of the same epilogue ----------------------------------------------------------------------
+def _claim(dev, digest, sig, flags, pre, addrs, claimed):
+    vi = C.c_int32(12345)
+    bit = dev.dev_claim_row(digest, sig, flags, pre, addrs.ctypes.data, len(addrs), claimed, C.byref(vi))
+    return vi.value, bit
+
+
+def test_claimed_signer_decision_equals_the_oracle(dev):
+    sks, addrs = _keys(6, 21)
+    vs = B.ValSet(addrs, np.ones(len(addrs), np.uint64))
+    outsider, oaddrs = _keys(1, 22)
+    rng = np.random.default_rng(23)
+    d, d2 = rng.bytes(32), rng.bytes(32)
+
+    def check(digest, sig, claimed, flags=0, pre=0):
+        exp = int(B.verify_seals(vs, np.frombuffer(digest, np.uint8), np.frombuffer(sig, np.uint8), np.frombuffer(claimed, np.uint8),
+                                 np.array([pre], np.uint8), flags=flags)[0])
+        vi, bit = _claim(dev, digest, sig, flags, pre, addrs, claimed)
+        assert vi == set_index(vs, claimed) and bit == exp, (vi, bit, exp)
+        return bit
+
+    for i, sk in enumerate(sks):                                                   # honest rows
+        assert check(d, B.sign(sk, d), addrs[i].tobytes()) == 1
+    sig = B.sign(sks[2], d)
+    me, other = addrs[2].tobytes(), addrs[3].tobytes()
+    assert check(d, sig, other) == 0                                               # a stolen seal: valid, but not the claimed member's
+    assert check(d2, sig, me) == 0                                                 # over another digest
+    assert check(d, sig, me, pre=1) == 0                                           # pre-flagged although valid
+    osig, oaddr = B.sign(outsider[0], d), oaddrs[0].tobytes()
+    assert check(d, osig, oaddr) == 0 and _claim(dev, d, osig, 0, 0, addrs, oaddr) == (-1, 0)   # a non-member, signed correctly
+    assert check(d, osig, me) == 0                                                 # ... and claiming to be a member
+    for bad in (bytes(32) + sig[32:], sig[:32] + bytes(32) + sig[64:], sig[:64] + b"\x02", sig[:64] + bytes([sig[64] ^ 1])):
+        assert check(d, bad, me) == 0                                              # r = 0, s = 0, v = 2, the other recovery id
+    s_int = int.from_bytes(sig[32:64], "big")                                      # the high-s twin under both policies
+    twin = sig[:32] + (R.N - s_int).to_bytes(32, "big") + bytes([sig[64] ^ 1])
+    high = twin if s_int <= R.N // 2 else sig
+    assert check(d, high, me, flags=0) == 1 and check(d, high, me, flags=STRICT_LOW_S) == 0
+    # a validator whose address is twenty zero bytes: a row that recovered nothing does not become "its" row
+    with_zero = np.concatenate([np.zeros((1, 20), np.uint8), addrs])
+    assert _claim(dev, d, sig[:64] + b"\x02", 0, 0, with_zero, bytes(20)) == (0, 0)

@@ -4,6 +4,7 @@ separate processes alternating (IBFT_GPU_LIB), HIP-event kernel time behind 150 
 serves with a different kernel: 64 (two wavefronts per signature), 1 024 (one wavefront), 4 096 (rows), 16 384 (4-lane
 groups), 32 768 (2-lane groups), 65 536 (lane); a size written wN is the WARM path at N rows (keys known).  Also prints the device canary of every process (ibft_issue_probe) so that a
 slow device is not mistaken for a slow build, and — the lease's kind — the old build's 16 384-row time.
+Stops at the first child with a non-zero exit status (or none within its time limit): prints what it has, exits non-zero.
 
     python tools/kernel_ab.py ab/libibftgpu_r05.so go-ibft_amd/csrc/libibftgpu.so 3 > gpurun_out/profiles/r06a_kernel_ab.txt"""
 import json
@@ -44,17 +45,21 @@ old, new = sys.argv[1], sys.argv[2]
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 sizes = sys.argv[4:] or ["64", "1024", "4096", "16384", "32768", "65536", "w1024", "w4096", "w16384", "w65536"]
 acc = {"old": {}, "new": {}}
-for rd in range(rounds):
-    for name, lib in (("old", old), ("new", new)):
-        env = dict(os.environ, IBFT_GPU_LIB=os.path.abspath(lib), IBFT_MIN_ABI="3")   # (an older build: without the exports that came later)
+failed = None   # the first child that did not end well: nothing more is started on the card after it (a fault must not be met twice)
+for rd, name, lib in ((rd, name, lib) for rd in range(rounds) for name, lib in (("old", old), ("new", new))):
+    env = dict(os.environ, IBFT_GPU_LIB=os.path.abspath(lib), IBFT_MIN_ABI="3")   # (an older build: without the exports that came later)
+    try:
         p = subprocess.run([sys.executable, "-c", CHILD] + sizes, env=env, capture_output=True, text=True, timeout=600)
-        line = p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
-        print(name, line or p.stderr[-400:], flush=True)
-        try:
-            for k, v in json.loads(line).items():
-                acc[name].setdefault(k, []).append(v)
-        except ValueError:
-            pass
+    except subprocess.TimeoutExpired:
+        failed = f"{name} (round {rd}): no end within 600 s"
+        break
+    line = p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
+    print(name, line or p.stderr[-400:], flush=True)
+    if p.returncode != 0:
+        failed = f"{name} (round {rd}): exit status {p.returncode}: {p.stderr[-400:]}"
+        break
+    for k, v in json.loads(line).items():
+        acc[name].setdefault(k, []).append(v)
 print("# median kernel ms: N  old  new  new/old")
 for k in sizes + ["canary_ns"]:
     if k in acc["old"] and k in acc["new"]:
@@ -63,3 +68,5 @@ for k in sizes + ["canary_ns"]:
 if "16384" in acc["old"]:
     m = float(np.median(acc["old"]["16384"]))
     print(f"# lease kind by the OLD build's 16 384-row kernel ({m:.3f} ms): {'fast' if m < 0.77 else 'slow'} (0.70 / 0.85 ms, DESIGN.md §5.8)")
+if failed:
+    sys.exit(f"kernel_ab: stopped at the first child that failed, {failed}")
