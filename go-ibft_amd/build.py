@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libibftgpu.so")
 SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "cert_wave_dev.h", "cert_scan_dev.h", "modinv_dev.h",
-           "sign_dev.h", "sign_message_dev.h", "sha256_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
+           "sign_dev.h", "sign_message_dev.h", "sign_envelope_dev.h", "sha256_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
 # Code-generation flags of the product library (part of its build stamp).  max-ilp: the verdict kernels run ONE wavefront per
 # SIMD at the sizes that matter (N ≤ 4 096), where every hazard s_nop is a lost issue slot — scheduling for instruction-level
 # parallelism instead of register pressure takes the s_nops of ecrecover_rows_kernel from 399 to 114 (133 → 174 VGPRs, still
@@ -277,6 +277,20 @@ def build_sign_message_harness(force: bool = False) -> str:
                                "-o", SIGN_MESSAGE_HARNESS, os.path.join(CSRC, "host_sign_message_harness.hip")], cwd=CSRC)
         _mark(SIGN_MESSAGE_HARNESS, deps)
     return SIGN_MESSAGE_HARNESS
+
+
+SIGN_ENVELOPE_HARNESS = os.path.join(CSRC, "libdev_sign_envelope_host.so")
+
+
+def build_sign_envelope_harness(force: bool = False) -> str:
+    """TEST-ONLY: sign_envelope_dev.h (head, body copy, both digest forms, signature: the steps of ibft_sign_envelopes_wire) on the CPU."""
+    deps = ["host_sign_envelope_harness.hip", "sign_envelope_dev.h", "sign_message_dev.h", "sign_dev.h", "cert_wave_dev.h", "wave_emul.h",
+            "wire_dev.h", "sha256_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
+    if force or _stale(SIGN_ENVELOPE_HARNESS, deps):
+        subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
+                               "-o", SIGN_ENVELOPE_HARNESS, os.path.join(CSRC, "host_sign_envelope_harness.hip")], cwd=CSRC)
+        _mark(SIGN_ENVELOPE_HARNESS, deps)
+    return SIGN_ENVELOPE_HARNESS
 
 
 if __name__ == "__main__":

@@ -113,6 +113,7 @@ struct ibft_ctx {
   DevBuf d_hash, d_sig, d_signer, d_pre, d_hash_len, d_payload, d_off, d_raw;
   DevBuf d_signer_out;  // the address column the emitting cold kernels write (ibft_recover_seals / ibft_recover_block_seals)
   DevBuf d_msg_cols, d_msg_wire;  // ibft_sign_messages_wire: height ‖ round ‖ type columns in, the wire bytes out
+  DevBuf d_env_cols, d_env_body, d_env_wire;  // ibft_sign_envelopes_wire: the row columns, the bodies in, the wire bytes out (grown on demand, kept)
   // the SECOND staging slot of the seal columns (ibft_seals_stage_next / ibft_seals_swap): batch k+1 is copied here on a
   // copy stream of its own while the verdict kernels read batch k from the columns above; a swap exchanges the two sets
   DevBuf d_hash_nx, d_sig_nx, d_signer_nx, d_pre_nx;
@@ -217,6 +218,7 @@ struct ibft_ctx {
   size_t h_phash_rows = 0;
   uint64_t proposal_bytes_max = 256ull << 20;  // IBFT_PROPOSAL_BYTES_MAX: the most raw_off[n] may be (IBFT_E_TOOBIG beyond)
   uint32_t proposal_lanes_force = 0;           // IBFT_PROPOSAL_LANES=1|64 pins the form of proposal_digest_kernel (tests, A/B)
+  uint32_t envelope_lanes_force = 0;           // IBFT_ENVELOPE_LANES=1|64 pins the form of envelope_digest_kernel (tests, A/B)
   uint32_t proposal_lane_rows = 8192;          // AUTO: the lane form from this many proposals of the longest one's length on
   ValFamily fam;                                     // ibft_set_validator_sets / the _sets block calls
   uint64_t valsets_bytes_max = 512ull << 20;         // IBFT_VALSETS_BYTES_MAX: the most a family's device tables may take
@@ -1583,6 +1585,10 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
     if (g == 1 || g == 64) c->proposal_lanes_force = (uint32_t)g;
   }
   if (const char *e = getenv("IBFT_STREAM_DIGEST")) c->stream_digest_copy = strcmp(e, "copy") == 0;
+  if (const char *e = getenv("IBFT_ENVELOPE_LANES")) {
+    const int g = atoi(e);
+    if (g == 1 || g == 64) c->envelope_lanes_force = (uint32_t)g;
+  }
   if (const char *e = getenv("IBFT_PROPOSAL_LANE_ROWS")) c->proposal_lane_rows = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_PROPOSAL_BYTES_MAX"))  // (offsets are 32-bit; room is kept for the round and the slack)
     c->proposal_bytes_max = std::min<uint64_t>(strtoull(e, nullptr, 10), 0xFFFFFE00ull);
@@ -1670,7 +1676,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
                     &c->d_phash, &c->bs_praw[0], &c->bs_praw[1], &c->bs_proff[0], &c->bs_proff[1], &c->bs_pround[0], &c->bs_pround[1],
                     &c->bs_phash[0], &c->bs_phash[1], &c->bs_signer[0], &c->bs_signer[1], &c->bs_vidx[0], &c->bs_vidx[1], &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
-                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->d_msg_cols, &c->d_msg_wire})
+                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
     release(*b);
   if (c->h_phash) (void)hipHostFree(c->h_phash);
   if (c->tstream) {
@@ -2930,6 +2936,130 @@ int ibft_sign_messages_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *typ
   if (out_ok) HIPCHK(c, hipMemcpyAsync(out_ok, c->d_pre.p, n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   memcpy(out_off, off.data(), (n + 1) * 4);
+  return IBFT_OK;
+}
+
+// f4 two layers up: PREPREPARE / ROUND_CHANGE envelopes around bodies the caller encoded (sign_envelope_dev.h).  A row's length
+// depends on type, height, round and body length alone, so offsets, body destinations and the copy kernel's pieces are computed
+// here, before anything is launched.  Four launches on the main stream: heads, body copy, digests, signatures.
+int ibft_sign_envelopes_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *type, const uint64_t *height, const uint64_t *round,
+                             const uint8_t *body, size_t body_bytes, const uint32_t *body_at, const uint32_t *body_len, size_t n,
+                             uint32_t nonce, uint8_t *out_wire, size_t wire_cap, uint32_t *out_off, uint8_t *out_from20, uint8_t *out_ok) {
+  if (!c || (n && (!sk32 || !type || !height || !round || !body_at || !body_len || !out_wire || !out_off))) return IBFT_E_INVAL;
+  if (!body && body_bytes) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  if (nonce != IBFT_SIGN_NONCE_KECCAK && nonce != IBFT_SIGN_NONCE_RFC6979) {
+    c->last_error = "ibft_sign_envelopes_wire: unknown nonce rule " + std::to_string(nonce) +
+                    " (IBFT_SIGN_NONCE_KECCAK = 0, IBFT_SIGN_NONCE_RFC6979 = 1)";
+    return IBFT_E_INVAL;
+  }
+  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  for (size_t i = 0; i < n; i++) {
+    if (type[i] != ibftk::MSG_TYPE_PREPREPARE && type[i] != ibftk::MSG_TYPE_ROUND_CHANGE) {
+      c->last_error = "ibft_sign_envelopes_wire: row " + std::to_string(i) + " has type " + std::to_string((unsigned)type[i]) +
+                      " (0 = PREPREPARE, 3 = ROUND_CHANGE)";
+      return IBFT_E_INVAL;
+    }
+  }
+  for (size_t i = 0; i < n; i++) {
+    if ((uint64_t)body_at[i] + body_len[i] > body_bytes) {  // (64-bit: at + len may pass 2^32)
+      c->last_error = "ibft_sign_envelopes_wire: row " + std::to_string(i) + " names body bytes [" + std::to_string(body_at[i]) + ", " +
+                      std::to_string((uint64_t)body_at[i] + body_len[i]) + ") of " + std::to_string(body_bytes);
+      return IBFT_E_INVAL;
+    }
+  }
+  uint64_t total = 0, total_blocks = 0, max_blocks = 0;
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t len = ibftk::envelope_wire_len(type[i], height[i], round[i], body_len[i]);
+    const uint64_t blocks = (len - ibftk::SIGN_MESSAGE_SIG_FIELD) / 136u + 1u;
+    total += len;  // (n ≤ max_rows rows of < 2^33 bytes: no overflow)
+    total_blocks += blocks;
+    max_blocks = std::max(max_blocks, blocks);
+  }
+  if (body_bytes > c->proposal_bytes_max || total > c->proposal_bytes_max) {
+    c->last_error = "ibft_sign_envelopes_wire: " + std::to_string(body_bytes) + " body bytes in, " + std::to_string(total) +
+                    " bytes out: more than the proposal byte budget of " + std::to_string(c->proposal_bytes_max) + " (IBFT_PROPOSAL_BYTES_MAX)";
+    return IBFT_E_TOOBIG;
+  }
+  if (total > wire_cap) {
+    c->last_error = "ibft_sign_envelopes_wire: the messages take " + std::to_string(total) + " bytes, wire_cap is " + std::to_string(wire_cap);
+    return IBFT_E_TOOBIG;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->wire_valid = false;  // the columns below are the wire walker's and the seal batch's
+  c->staged_n = 0;
+  if (n == 0) {
+    if (out_off) out_off[0] = 0;
+    return IBFT_OK;
+  }
+  // host columns, one upload: height ‖ round (8-byte entries) ‖ body_at ‖ body_len ‖ dst_at ‖ off[n+1] ‖ piece_first[n+1] ‖ type
+  const size_t col = (n + 8) & ~(size_t)7;  // entries per column, room for the n + 1 of the last two
+  std::vector<uint64_t> cols((16 * col + 20 * col + col + 7) / 8);
+  uint8_t *h = (uint8_t *)cols.data();
+  uint64_t *h_height = (uint64_t *)h, *h_round = h_height + col;
+  uint32_t *h_at = (uint32_t *)(h + 16 * col), *h_len = h_at + col, *h_dst = h_len + col, *h_off = h_dst + col, *h_piece = h_off + col;
+  uint8_t *h_type = h + 36 * col;
+  memcpy(h_height, height, n * 8);
+  memcpy(h_round, round, n * 8);
+  memcpy(h_at, body_at, n * 4);
+  memcpy(h_len, body_len, n * 4);
+  memcpy(h_type, type, n);
+  uint64_t at = 0, pieces = 0;
+  for (size_t i = 0; i < n; i++) {
+    h_off[i] = (uint32_t)at;
+    h_dst[i] = (uint32_t)at + ibftk::envelope_head_len(type[i], height[i], round[i], body_len[i]);
+    h_piece[i] = (uint32_t)pieces;
+    pieces += ibftk::envelope_copy_pieces(h_dst[i], body_len[i]);
+    at += ibftk::envelope_wire_len(type[i], height[i], round[i], body_len[i]);
+  }
+  h_off[n] = (uint32_t)at;
+  h_piece[n] = (uint32_t)pieces;  // (≤ total / 4 096 + 2 n)
+  int rc;
+  if ((rc = ensure(c, c->d_env_body, body_bytes + 256))) return rc;  // the copy and the sponges read a few bytes past a range
+  if ((rc = ensure(c, c->d_env_wire, (size_t)total + 256))) return rc;
+  if ((rc = ensure(c, c->d_hash, n * 32))) return rc;
+  if ((rc = upload(c, c->d_env_cols, h, 37 * col))) return rc;
+  if (body_bytes) HIPCHK(c, hipMemcpyAsync(c->d_env_body.p, body, body_bytes, hipMemcpyHostToDevice, c->stream));
+  if ((rc = upload(c, c->d_payload, sk32, n * 32))) return rc;  // the sender-payload column is free here, as in ibft_sign_seals
+  const uint8_t *d = (const uint8_t *)c->d_env_cols.p;
+  ibftk::sign_envelope_args a;
+  a.gtab = (const uint32_t *)c->dev->d_gtab.p;
+  a.sk32 = (const uint8_t *)c->d_payload.p;
+  a.type = d + 36 * col;
+  a.height = (const uint64_t *)d;
+  a.round = (const uint64_t *)(d + 8 * col);
+  a.body = (const uint8_t *)c->d_env_body.p;
+  a.body_at = (const uint32_t *)(d + 16 * col);
+  a.body_len = a.body_at + col;
+  a.dst_at = a.body_len + col;
+  a.off = a.dst_at + col;
+  a.piece_first = a.off + col;
+  a.wire = (uint8_t *)c->d_env_wire.p;
+  a.digest32 = (uint8_t *)c->d_hash.p;
+  a.from20 = (uint8_t *)c->d_signer.p;
+  a.ok = (uint8_t *)c->d_pre.p;
+  a.n = (uint32_t)n;
+  const uint32_t blocks = (uint32_t)((n + ibftk::ROWS_PER_BLOCK - 1) / ibftk::ROWS_PER_BLOCK);
+  hipLaunchKernelGGL(ibftk::envelope_head_kernel, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
+  if (pieces) hipLaunchKernelGGL(ibftk::envelope_copy_kernel, dim3((uint32_t)pieces), dim3(ibftk::ENVELOPE_COPY_THREADS), 0, c->stream, a);
+  // the digest's form by proposal_form's rule: the batch's size in messages of the longest one's length
+  const uint32_t form = c->envelope_lanes_force ? c->envelope_lanes_force
+                        : (n >= 64 && total_blocks >= (uint64_t)c->proposal_lane_rows * max_blocks) ? 1u : 64u;
+  if (form == 1)
+    hipLaunchKernelGGL(ibftk::envelope_digest_kernel<1>, dim3(blocks), dim3(64), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(ibftk::envelope_digest_kernel<64>, dim3((uint32_t)n), dim3(64), 0, c->stream, a);
+  if (nonce == IBFT_SIGN_NONCE_RFC6979)
+    hipLaunchKernelGGL(ibftk::sign_envelope_lane_kernel<ibftk::SIGN_NONCE_RFC6979>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(ibftk::sign_envelope_lane_kernel<ibftk::SIGN_NONCE_KECCAK>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemsetAsync(c->d_payload.p, 0, n * 32, c->stream));  // the keys do not outlive the call in HBM
+  HIPCHK(c, hipMemcpyAsync(out_wire, c->d_env_wire.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+  if (out_from20) HIPCHK(c, hipMemcpyAsync(out_from20, c->d_signer.p, n * 20, hipMemcpyDeviceToHost, c->stream));
+  if (out_ok) HIPCHK(c, hipMemcpyAsync(out_ok, c->d_pre.p, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  memcpy(out_off, h_off, (n + 1) * 4);
   return IBFT_OK;
 }
 

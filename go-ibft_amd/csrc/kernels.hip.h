@@ -16,6 +16,7 @@
 //   verify_known_lane_kernel    a2/a3 against the validator's known key (warm path), 1 lane per signature
 //   verify_known_group_kernel<G>    same, G = 2..32 lanes per signature
 //   verify_known_wave_kernel        same, one wavefront per signature in the row layout of wave_fe_dev.h
+//   envelope_head / _copy / _digest<1|64> / sign_envelope_lane_kernel   f4: PREPREPARE / ROUND_CHANGE envelopes (sign_envelope_dev.h)
 //   tally_kernel                a8  HasQuorum             (core/validator_manager.go:77-96)
 //   block_rows_kernel               chain sync: each block's hash → its rows
 //   block_head_kernel               streamed chain sync (every submit): digests → rows, seal-digest convention fused
@@ -43,6 +44,7 @@
 #include "verify_dev.h"
 #include "sign_dev.h"
 #include "sign_message_dev.h"
+#include "sign_envelope_dev.h"
 #include "wave_fe_dev.h"
 #include "wire_dev.h"
 #include "cert_wave_dev.h"
@@ -286,6 +288,122 @@ __global__ void __launch_bounds__(ROWS_PER_BLOCK) sign_message_lane_kernel(sign_
 #pragma unroll
   for (int i = 0; i < 5; i++) ad[i] = m.addr[i];
   a.ok[row] = (m.ok && fits) ? 1 : 0;
+}
+
+// ---- f4, two layers up: a PREPREPARE / ROUND_CHANGE envelope around a given body, as wire bytes (sign_envelope_dev.h) ------
+// A body is any length (≈106 KB for the ROUND_CHANGE of 1 024 validators), so a row is not one lane's work: four launches on one
+// stream, each the shape its step wants.  off[], dst_at[] and piece_first[] come from the host (a row's length depends on type,
+// height, round and body length only: envelope_wire_len).
+//   envelope_head_kernel          a lane per row: From from the key (one fixed-base multiplication), the head built in LDS and
+//                                 stored with a zero signature field; no sign_core here
+//   envelope_copy_kernel          256 threads per 4 096 bytes of output: the bodies behind their heads (copy_body_piece)
+//   envelope_digest_kernel<1|64>  keccak256 of the stored message minus its signature field: a lane per message (wire::hash_pieces),
+//                                 or a wavefront per message with the state over 25 lanes (cw::sponge_message) — the verifier's own
+//                                 two routines for "bytes minus the signature field"; the host picks as proposal_form does
+//   sign_envelope_lane_kernel     a lane per row: sign_core over that digest, the signature into its place — sign_lane_kernel
+//                                 without the address, so its code stays below sign_lane_kernel's
+// Idle lanes of the last wavefront run the last row again (sign_core votes across the wavefront) and store nothing.
+struct sign_envelope_args {
+  const uint32_t *gtab;
+  const uint8_t *sk32;          // n × 32, big-endian secret keys
+  const uint8_t *type;          // n: 0 = PREPREPARE, 3 = ROUND_CHANGE (checked by the host)
+  const uint64_t *height;       // n
+  const uint64_t *round;        // n
+  const uint8_t *body;          // the bodies' buffer (256 bytes of slack behind it)
+  const uint32_t *body_at;      // n: row i's body is body[body_at[i], body_at[i] + body_len[i]) — ranges may repeat or overlap
+  const uint32_t *body_len;     // n
+  const uint32_t *dst_at;       // n: where row i's body goes, off[i] + its head's length
+  const uint32_t *piece_first;  // n + 1: row i owns the copy workgroups [piece_first[i], piece_first[i+1])
+  const uint32_t *off;          // n + 1: row i is wire[off[i], off[i+1])
+  uint8_t *wire;                // out (256 bytes of slack behind it)
+  uint8_t *digest32;            // n × 32: keccak256(PayloadNoSig), between the digest and the sign launch
+  uint8_t *from20;              // n × 20 out
+  uint8_t *ok;                  // n out: 1 = signed, 0 = key outside [1, n)
+  uint32_t n;
+};
+__global__ void __launch_bounds__(ROWS_PER_BLOCK) envelope_head_kernel(sign_envelope_args a) {
+  __shared__ uint64_t lds[ROWS_PER_BLOCK * ENVELOPE_HEAD_WORDS];
+  const uint32_t row = blockIdx.x * (uint32_t)ROWS_PER_BLOCK + threadIdx.x;
+  const bool live = row < a.n;
+  const uint32_t src = live ? row : a.n - 1;
+  uint8_t sk[32];
+  const uint32_t *ks = reinterpret_cast<const uint32_t *>(a.sk32 + 32ull * src);
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t kw = ks[i];
+#pragma unroll
+    for (int b = 0; b < 4; b++) sk[4 * i + b] = (uint8_t)(kw >> (8 * b));
+  }
+  u256 d;
+  const bool key_ok = sign_key(sk, d);
+  uint32_t addr[5];
+  sign_address(a.gtab, d, key_ok, addr);
+  uint8_t *p = reinterpret_cast<uint8_t *>(lds + (size_t)ENVELOPE_HEAD_WORDS * threadIdx.x);
+  const uint32_t body_len = a.body_len[src];
+  const uint32_t head = envelope_head(p, a.type[src], a.height[src], a.round[src], addr, body_len);
+  if (!live) return;
+  const uint32_t at = a.off[row];
+  if (a.off[row + 1] - at == head + body_len) store_envelope_head(a.wire + at, p, head);  // (the host computed it with the same function)
+  uint32_t *ad = reinterpret_cast<uint32_t *>(a.from20 + 20ull * row);
+#pragma unroll
+  for (int i = 0; i < 5; i++) ad[i] = addr[i];
+}
+__global__ void __launch_bounds__(ENVELOPE_COPY_THREADS) envelope_copy_kernel(sign_envelope_args a) {
+  // the row that owns this workgroup: the last one whose first piece is not behind it (rows without a body own none)
+  uint32_t lo = 0, hi = a.n;
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a.piece_first[mid] <= blockIdx.x) lo = mid; else hi = mid;
+  }
+  copy_body_piece(a.wire, a.body, a.dst_at[lo], a.body_at[lo], a.body_len[lo], blockIdx.x - a.piece_first[lo], threadIdx.x);
+}
+template <int LANES>
+__global__ void __launch_bounds__(64) envelope_digest_kernel(sign_envelope_args a) {
+  if constexpr (LANES == 1) {
+    const uint32_t row = blockIdx.x * 64u + threadIdx.x;
+    const bool live = row < a.n;
+    const uint32_t src = live ? row : a.n - 1;
+    const uint32_t o0 = a.off[src], len = a.off[src + 1] - o0;
+    uint64_t d[4];
+    envelope_digest_lane(a.wire + o0, len, envelope_cut(a.height[src], a.round[src]), live, d);  // idle lanes: the empty message
+    if (live) {
+      uint4 *o = reinterpret_cast<uint4 *>(a.digest32 + 32ull * row);
+      o[0] = make_uint4((uint32_t)d[0], (uint32_t)(d[0] >> 32), (uint32_t)d[1], (uint32_t)(d[1] >> 32));
+      o[1] = make_uint4((uint32_t)d[2], (uint32_t)(d[2] >> 32), (uint32_t)d[3], (uint32_t)(d[3] >> 32));
+    }
+  } else {
+    __shared__ uint64_t A[32], B[32];
+    const uint32_t row = blockIdx.x, lane = threadIdx.x;  // (grid = n: block-uniform, always a live row)
+    const uint32_t o0 = a.off[row], len = a.off[row + 1] - o0;
+    const uint64_t word = envelope_digest_wave(a.wire + o0, len, envelope_cut(a.height[row], a.round[row]), lane, A, B);
+    if (lane < 4u) *reinterpret_cast<uint64_t *>(a.digest32 + 32ull * row + 8u * lane) = word;
+  }
+}
+template <int NONCE>
+__global__ void __launch_bounds__(ROWS_PER_BLOCK) sign_envelope_lane_kernel(sign_envelope_args a) {
+  const uint32_t row = blockIdx.x * (uint32_t)ROWS_PER_BLOCK + threadIdx.x;
+  const bool live = row < a.n;
+  const uint32_t src = live ? row : a.n - 1;
+  uint8_t sk[32], dg[32];
+  const uint32_t *ks = reinterpret_cast<const uint32_t *>(a.sk32 + 32ull * src);
+  const uint32_t *ds = reinterpret_cast<const uint32_t *>(a.digest32 + 32ull * src);
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    uint32_t kw = ks[i], dw = ds[i];
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      sk[4 * i + b] = (uint8_t)(kw >> (8 * b));
+      dg[4 * i + b] = (uint8_t)(dw >> (8 * b));
+    }
+  }
+  u256 r, s;
+  uint32_t v;
+  const bool ok = sign_envelope_row<NONCE>(a.gtab, sk, dg, r, s, v);
+  if (!live) return;
+  const uint32_t at = a.off[row], cut = envelope_cut(a.height[row], a.round[row]);
+  const bool fits = a.off[row + 1] - at == envelope_head_len(a.type[row], a.height[row], a.round[row], a.body_len[row]) + a.body_len[row];
+  if (fits) store_envelope_signature(a.wire + at, cut, r, s, v);
+  a.ok[row] = (ok && fits) ? 1 : 0;
 }
 
 // ---- proposal hash + a1 ---------------------------------------------------------------

@@ -51,7 +51,7 @@ EXPORTS = [
     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
-    "ibft_sign_seals_ex", "ibft_sign_messages_wire",
+    "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
@@ -65,8 +65,9 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
                     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
                     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
-                    "ibft_sign_seals_ex", "ibft_sign_messages_wire"}
+                    "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
+ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
 COMM_ID_BYTES = 128
 E_RCCL = -8
@@ -207,6 +208,8 @@ def load_library() -> C.CDLL:
         L.ibft_sign_seals_ex.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
     if hasattr(L, "ibft_sign_messages_wire"):
         L.ibft_sign_messages_wire.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
+    if hasattr(L, "ibft_sign_envelopes_wire"):
+        L.ibft_sign_envelopes_wire.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
     if hasattr(L, "ibft_recover_seals"):
         L.ibft_recover_seals.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Tally)]
     if hasattr(L, "ibft_recover_block_seals"):
@@ -1045,6 +1048,36 @@ class BatchVerifier:
         ok = np.zeros(n, dtype=np.uint8)
         self._chk(self._L.ibft_sign_messages_wire(self._h, _p(sk), _p(ty), _p(hh), _p(rr), _p(hs), n, SIGN_NONCES[nonce], _p(wire),
                                                   wire.size, _p(off), _p(frm), _p(ok)), "ibft_sign_messages_wire")
+        self._staged = 0
+        return wire[:int(off[n])].tobytes(), off, frm, ok.astype(bool)
+
+    def sign_envelopes(self, sk32, type, height, round, body, body_at, body_len, nonce="keccak"):
+        """ibft_sign_envelopes_wire (simulators only): one PREPREPARE (type 0) or ROUND_CHANGE (type 3) message per row around the
+        already-encoded body bytes body[body_at[i]:body_at[i] + body_len[i]] — rows may name the same or overlapping ranges —,
+        From derived, the envelope hashed and signed on the device → (wire: bytes, off u32[n+1], from20 u8[n,20], ok bool[n]); row i
+        is wire[off[i]:off[i+1]], the form verify_certificates_wire takes.  type, height, round, body_at and body_len are columns
+        or scalars (one value for every row).  A refused key (ok False) keeps its row's length and carries a zero From and
+        signature around its body.  Leaves no staged batch."""
+        if nonce not in SIGN_NONCES:
+            raise ValueError(f"nonce must be one of {sorted(SIGN_NONCES)}, not {nonce!r}")
+        if not hasattr(self._L, "ibft_sign_envelopes_wire"):
+            raise GpuUnavailable("this build of the library has no ibft_sign_envelopes_wire — rebuild")
+        sk = np.ascontiguousarray(sk32, dtype=np.uint8).reshape(-1, 32)
+        n = len(sk)
+        bb = np.frombuffer(bytes(body), dtype=np.uint8) if not isinstance(body, np.ndarray) else np.ascontiguousarray(body, dtype=np.uint8)
+        ty = np.ascontiguousarray(np.broadcast_to(np.asarray(type, dtype=np.uint8), (n,)))
+        hh = np.ascontiguousarray(np.broadcast_to(np.asarray(height, dtype=np.uint64), (n,)))
+        rr = np.ascontiguousarray(np.broadcast_to(np.asarray(round, dtype=np.uint64), (n,)))
+        at = np.ascontiguousarray(np.broadcast_to(np.asarray(body_at, dtype=np.uint32), (n,)))
+        ln = np.ascontiguousarray(np.broadcast_to(np.asarray(body_len, dtype=np.uint32), (n,)))
+        cap = int(ln.astype(np.uint64).sum()) + ENVELOPE_HEAD_MAX * max(n, 1)
+        wire = np.zeros(cap, dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        frm = np.zeros((n, 20), dtype=np.uint8)
+        ok = np.zeros(n, dtype=np.uint8)
+        self._chk(self._L.ibft_sign_envelopes_wire(self._h, _p(sk), _p(ty), _p(hh), _p(rr), _p(bb) if bb.size else None, bb.size, _p(at),
+                                                   _p(ln), n, SIGN_NONCES[nonce], _p(wire), wire.size, _p(off), _p(frm), _p(ok)),
+                  "ibft_sign_envelopes_wire")
         self._staged = 0
         return wire[:int(off[n])].tobytes(), off, frm, ok.astype(bool)
 

@@ -51,6 +51,9 @@
  *   ibft_sign_messages_wire
  *                        <- n × Backend.BuildPrepareMessage / BuildCommitMessage (core/backend.go:12-34) as wire bytes,
  *                           simulators only: what ibft_verify_senders_wire / ibft_verify_messages_wire read
+ *   ibft_sign_envelopes_wire
+ *                        <- n × Backend.BuildPrePrepareMessage / BuildRoundChangeMessage around given bodies, simulators
+ *                           only: what ibft_verify_certificates_wire reads
  *   ibft_pinned_alloc    page-locked column buffers the device reads itself (one gather launch per call)
  *
  * Conventions (the reference fixes none of the arithmetic; these are the
@@ -864,6 +867,42 @@ int ibft_sign_messages_wire(ibft_ctx *ctx, const uint8_t *sk32, const uint8_t *t
                             const uint64_t *round, const uint8_t *hash32, size_t n, uint32_t nonce,
                             uint8_t *out_wire, size_t wire_cap, uint32_t *out_off,
                             uint8_t *out_from20, uint8_t *out_ok);
+/* The signing side two layers up, for SIMULATORS as well: the PREPREPARE / ROUND_CHANGE envelope around a body the caller encoded —
+ * Backend.BuildPrePrepareMessage / BuildRoundChangeMessage (/root/reference/core/backend.go:12-34) for n validators at once, as the
+ * wire bytes ibft_verify_certificates_wire / ibft_verify_senders_wire read.  Row i is (sk32[i], type[i] = 0 PREPREPARE /
+ * 3 ROUND_CHANGE, height[i], round[i], body[body_at[i] .. body_at[i] + body_len[i])); the body is the already-encoded oneof message
+ * (PrePrepareMessage / RoundChangeMessage bytes: Proposal, hash, certificates — the nested messages signed before, e.g. by
+ * ibft_sign_messages_wire and by this call).  The row becomes, in canonical proto3 (go-ibft_amd/csrc/sign_envelope_dev.h):
+ *     View{height, round} (always present) ‖ From = keccak256(X‖Y)[12..32) of the key ‖ Signature ‖ Type (absent for PREPREPARE,
+ *     a zero scalar; 20 03 for ROUND_CHANGE) ‖ field 5 / field 8: varint(body_len) ‖ body (emitted even when body_len = 0)
+ * with Signature = sign(sk, keccak256(PayloadNoSig)), PayloadNoSig being the message without its Signature field (the envelope
+ * never applies the seal-digest convention).  `nonce` is IBFT_SIGN_NONCE_KECCAK or IBFT_SIGN_NONCE_RFC6979.
+ * Bodies are named by (body_at, body_len) columns and NOT by the n + 1 offsets of the other calls because rows MAY name the same
+ * or overlapping ranges of `body`: the Q round-change senders that carry one PreparedCertificate upload it once.
+ * Outputs: out_off has n + 1 entries, row i is out_wire[out_off[i] .. out_off[i+1]); a row's length depends on type, height, round
+ * and body_len only (head ≤ 121 bytes + body_len).  out_from20 (n × 20) and out_ok (n) may be NULL.  A key outside [1, n) gives
+ * ok = 0 and a row of its NORMAL length with a zero From and a zero Signature; the body is still copied (lengths stay independent of
+ * the keys and the bytes stay canonical protobuf; every verifier rejects the row).  A message longer than
+ * IBFT_CERT_DIGEST_MAX_BYTES is still signed; ibft_verify_certificates_wire classes it IBFT_CERT_CLASS_DIGEST_BY_HOST.
+ * The envelope digest is hashed on the device from the stored bytes, a lane per message or a wavefront per message, chosen by the
+ * rule of ibft_proposal_hashes (batch size in messages of the longest one's length); environment IBFT_ENVELOPE_LANES=1|64, read at
+ * ibft_ctx_create, pins a form (tests, A/B) as IBFT_PROPOSAL_LANES does.
+ * Checks, in this order: IBFT_E_INVAL for a NULL ctx; IBFT_E_INVAL for a NULL sk32 / type / height / round / body_at / body_len /
+ * out_wire / out_off with n > 0; IBFT_E_INVAL for a NULL body with body_bytes > 0; IBFT_E_INVAL for an unknown `nonce`
+ * (ibft_last_error names it); IBFT_E_TOOBIG for n > max_rows; IBFT_E_INVAL for a type other than 0 or 3 (ibft_last_error names the
+ * first such row); IBFT_E_INVAL for a body range that leaves [0, body_bytes) (computed in 64 bits); IBFT_E_TOOBIG when body_bytes
+ * or the total output exceeds the context's proposal byte budget (IBFT_PROPOSAL_BYTES_MAX — the device buffers for bodies and
+ * output grow on demand up to it and are kept), or the total output exceeds wire_cap.  A refused call writes nothing to any out
+ * buffer; n = 0 is legal and sets out_off[0] = 0.
+ * NOT for a production validator's key — the warning of ibft_sign_seals applies word for word: keys cross PCIe in the clear
+ * and sit in HBM for the duration of the call (the column is zeroed before the call returns), and the kernels are not written
+ * to be constant-time.  Like ibft_sign_messages_wire the call leaves NO staged seal batch and NO resident wire batch behind.
+ * No new ibft_version(): a build without the symbol simply lacks it.  */
+int ibft_sign_envelopes_wire(ibft_ctx *ctx, const uint8_t *sk32, const uint8_t *type, const uint64_t *height,
+                             const uint64_t *round, const uint8_t *body, size_t body_bytes,
+                             const uint32_t *body_at, const uint32_t *body_len, size_t n, uint32_t nonce,
+                             uint8_t *out_wire, size_t wire_cap, uint32_t *out_off,
+                             uint8_t *out_from20, uint8_t *out_ok);
 /* Block the host until the context's stream is idle.                               */
 int ibft_sync(ibft_ctx *ctx);
 /* Device canary (diagnostic; no reference counterpart — a Backend may log it at start-up and a bench line carries it):

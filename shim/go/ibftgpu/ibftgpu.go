@@ -1084,6 +1084,38 @@ func (c *Ctx) SignMessages(sk, types []byte, heights, rounds []uint64, hashes []
 	return wire[:off[n]], off, from, ok, nil
 }
 
+// SignEnvelopes = n × Backend.BuildPrePrepareMessage / BuildRoundChangeMessage (core/backend.go:12-34) for a SIMULATOR
+// (ibft_sign_envelopes_wire): row i is (sk[32i:], types[i] = 0 PREPREPARE / 3 ROUND_CHANGE, heights[i], rounds[i], the encoded
+// PrePrepareMessage / RoundChangeMessage body[bodyAt[i]:bodyAt[i]+bodyLen[i]]) — rows may name the same or overlapping ranges, a
+// certificate many senders carry is passed once — and comes back as the wire bytes of its message, wire[off[i]:off[i+1]] — the
+// form VerifyCertificatesWire reads —, with the sender addresses (n×20) and ok[i] == 0 for a key outside [1, n) (a row of its
+// normal length with a zero From and signature around its body).  Leaves no batch resident.  Not for a production validator's
+// key (include/ibftgpu.h, ibft_sign_seals).
+func (c *Ctx) SignEnvelopes(sk, types []byte, heights, rounds []uint64, body []byte, bodyAt, bodyLen []uint32, nonce uint32) (wire []byte, off []uint32, from, ok []byte, err error) {
+	n := len(types)
+	if n == 0 || len(sk) != 32*n || len(heights) != n || len(rounds) != n || len(bodyAt) != n || len(bodyLen) != n {
+		return nil, nil, nil, nil, ErrFallback
+	}
+	total := 0
+	for _, l := range bodyLen {
+		total += 121 + int(l) // the head in front of a body is at most 121 bytes
+	}
+	var bp *C.uint8_t
+	if len(body) > 0 {
+		bp = (*C.uint8_t)(unsafe.Pointer(&body[0]))
+	}
+	wire, off, from, ok = make([]byte, total), make([]uint32, n+1), make([]byte, 20*n), make([]byte, n)
+	rc := C.ibft_sign_envelopes_wire(c.h, (*C.uint8_t)(unsafe.Pointer(&sk[0])), (*C.uint8_t)(unsafe.Pointer(&types[0])),
+		(*C.uint64_t)(unsafe.Pointer(&heights[0])), (*C.uint64_t)(unsafe.Pointer(&rounds[0])), bp, C.size_t(len(body)),
+		(*C.uint32_t)(unsafe.Pointer(&bodyAt[0])), (*C.uint32_t)(unsafe.Pointer(&bodyLen[0])), C.size_t(n), C.uint32_t(nonce),
+		(*C.uint8_t)(unsafe.Pointer(&wire[0])), C.size_t(len(wire)), (*C.uint32_t)(unsafe.Pointer(&off[0])),
+		(*C.uint8_t)(unsafe.Pointer(&from[0])), (*C.uint8_t)(unsafe.Pointer(&ok[0])))
+	if err = c.check(rc); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	return wire[:off[n]], off, from, ok, nil
+}
+
 // Group is one process driving several MI355X (ibft_group_*): the rows of a batch are sharded over the
 // devices in 64-aligned ranges and ONE RCCL all-reduce inside the library merges the verdict words and the
 // ranks' distinct-sender bitmaps (a validator with valid rows in two shards is counted once, as HasQuorum's
