@@ -257,7 +257,7 @@ SIGN_NONCE_HARNESS = os.path.join(CSRC, "libdev_sign_nonce_host.so")
 
 def build_sign_nonce_harness(force: bool = False) -> str:
     """TEST-ONLY: sha256_dev.h and the RFC 6979 nonce rule of sign_dev.h (compression, HMAC, the DRBG, the signing row) on the CPU."""
-    deps = ["host_sign_nonce_harness.hip", "sign_dev.h", "sha256_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
+    deps = ["host_sign_nonce_harness.hip", "host_gtab.h", "sign_dev.h", "sha256_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
     if force or _stale(SIGN_NONCE_HARNESS, deps):
         subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
                                "-o", SIGN_NONCE_HARNESS, os.path.join(CSRC, "host_sign_nonce_harness.hip")], cwd=CSRC)
@@ -270,7 +270,7 @@ SIGN_MESSAGE_HARNESS = os.path.join(CSRC, "libdev_sign_message_host.so")
 
 def build_sign_message_harness(force: bool = False) -> str:
     """TEST-ONLY: sign_message_dev.h (the row of sign_message_lane_kernel: encode, hash, sign, store) on the CPU."""
-    deps = ["host_sign_message_harness.hip", "sign_message_dev.h", "sign_dev.h", "sha256_dev.h", "recover_dev.h", "modinv_dev.h",
+    deps = ["host_sign_message_harness.hip", "host_gtab.h", "sign_message_dev.h", "sign_dev.h", "sha256_dev.h", "recover_dev.h", "modinv_dev.h",
             "secp256k1_dev.h", "keccak_dev.h"]
     if force or _stale(SIGN_MESSAGE_HARNESS, deps):
         subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
@@ -284,7 +284,7 @@ SIGN_ENVELOPE_HARNESS = os.path.join(CSRC, "libdev_sign_envelope_host.so")
 
 def build_sign_envelope_harness(force: bool = False) -> str:
     """TEST-ONLY: sign_envelope_dev.h (head, body copy, both digest forms, signature: the steps of ibft_sign_envelopes_wire) on the CPU."""
-    deps = ["host_sign_envelope_harness.hip", "sign_envelope_dev.h", "sign_message_dev.h", "sign_dev.h", "cert_wave_dev.h", "wave_emul.h",
+    deps = ["host_sign_envelope_harness.hip", "host_gtab.h", "sign_envelope_dev.h", "sign_message_dev.h", "sign_dev.h", "cert_wave_dev.h", "wave_emul.h",
             "wire_dev.h", "sha256_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
     if force or _stale(SIGN_ENVELOPE_HARNESS, deps):
         subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",

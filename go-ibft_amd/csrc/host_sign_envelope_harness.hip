@@ -8,19 +8,10 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <vector>
-
 #include "sign_envelope_dev.h"
+#include "host_gtab.h"
 
 namespace {
-
-std::vector<uint32_t> g_gtab;
-void gtab_init() {
-  if (!g_gtab.empty()) return;
-  g_gtab.resize((size_t)ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES * ibftk::GTAB_ENTRY_DWORDS);
-  for (int t = 0; t < ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES; t++)
-    ibftk::gtab_entry(t / ibftk::GTAB_ENTRIES, t % ibftk::GTAB_ENTRIES, g_gtab.data() + ibftk::GTAB_ENTRY_DWORDS * t);
-}
 
 // what is LDS on the device: memory shared by the 64 coroutines
 alignas(16) uint64_t g_A[32], g_B[32];
@@ -41,6 +32,12 @@ void lane_digest(void *p) {
 extern "C" {
 
 uint32_t dev_envelope_cut(uint64_t height, uint64_t round) { return ibftk::envelope_cut(height, round); }
+// View ‖ From as put_message_front writes them: out holds 46 bytes; returns the offset behind From
+uint32_t dev_message_front(uint64_t height, uint64_t round, const uint8_t *addr20, uint8_t *out) {
+  uint32_t addr[5];
+  memcpy(addr, addr20, 20);
+  return ibftk::put_message_front(out, height, round, addr);
+}
 uint32_t dev_envelope_head_len(uint32_t type, uint64_t height, uint64_t round, uint32_t body_len) {
   return ibftk::envelope_head_len(type, height, round, body_len);
 }
@@ -86,9 +83,9 @@ int dev_sign_envelope(uint32_t nonce, uint32_t form, const uint8_t *sk32, uint32
   ibftk::u256 r, s;
   uint32_t v;
   const bool ok = nonce == (uint32_t)ibftk::SIGN_NONCE_RFC6979
-                      ? ibftk::sign_envelope_row<ibftk::SIGN_NONCE_RFC6979>(g_gtab.data(), sk, digest32, r, s, v)
-                      : ibftk::sign_envelope_row<ibftk::SIGN_NONCE_KECCAK>(g_gtab.data(), sk, digest32, r, s, v);
-  ibftk::store_envelope_signature(wire + dst_at, cut, r, s, v);
+                      ? ibftk::sign_digest<ibftk::SIGN_NONCE_RFC6979>(g_gtab.data(), sk, digest32, r, s, v)
+                      : ibftk::sign_digest<ibftk::SIGN_NONCE_KECCAK>(g_gtab.data(), sk, digest32, r, s, v);
+  ibftk::put_sig65(wire + dst_at + cut + 2, r, s, v);
   *wire_len = len;
   memcpy(from20, addr, 20);
   return ok ? 1 : 0;

@@ -6,17 +6,8 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <vector>
-
 #include "sign_message_dev.h"
-
-static std::vector<uint32_t> g_gtab;
-static void gtab_init() {
-  if (!g_gtab.empty()) return;
-  g_gtab.resize((size_t)ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES * ibftk::GTAB_ENTRY_DWORDS);
-  for (int t = 0; t < ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES; t++)
-    ibftk::gtab_entry(t / ibftk::GTAB_ENTRIES, t % ibftk::GTAB_ENTRIES, g_gtab.data() + ibftk::GTAB_ENTRY_DWORDS * t);
-}
+#include "host_gtab.h"
 
 extern "C" {
 

@@ -7,19 +7,11 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <vector>
-
 #include "sign_dev.h"
+#include "host_gtab.h"
 
 using secp::u256;
 
-static std::vector<uint32_t> g_gtab;
-static void gtab_init() {
-  if (!g_gtab.empty()) return;
-  g_gtab.resize((size_t)ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES * ibftk::GTAB_ENTRY_DWORDS);
-  for (int t = 0; t < ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES; t++)
-    ibftk::gtab_entry(t / ibftk::GTAB_ENTRIES, t % ibftk::GTAB_ENTRIES, g_gtab.data() + ibftk::GTAB_ENTRY_DWORDS * t);
-}
 static uint32_t be32(const uint8_t *p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
 static sha256::state words32(const uint8_t *p) {
   return sha256::state{be32(p), be32(p + 4), be32(p + 8), be32(p + 12), be32(p + 16), be32(p + 20), be32(p + 24), be32(p + 28)};
@@ -77,9 +69,7 @@ int dev_sign_rfc6979(const uint8_t *sk32, const uint8_t *digest32, uint32_t reje
   u256 r, s;
   uint32_t v, a[5];
   const bool ok = ibftk::sign_row<ibftk::SIGN_NONCE_RFC6979>(g_gtab.data(), sk32, digest32, r, s, v, a, reject_mask);
-  secp::to_be32(sig65, r);
-  secp::to_be32(sig65 + 32, s);
-  sig65[64] = (uint8_t)v;
+  ibftk::put_sig65(sig65, r, s, v);
   memcpy(addr20, a, 20);
   return ok ? 1 : 0;
 }

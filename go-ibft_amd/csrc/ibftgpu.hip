@@ -1438,6 +1438,56 @@ int comm_attach(ibft_ctx *c, ncclComm_t comm, uint32_t rank, uint32_t world) {
   return IBFT_OK;
 }
 
+// One call of the device signer (ibft_sign_seals_ex, ibft_sign_messages_wire, ibft_sign_envelopes_wire), the context locked: what the
+// three share around their own columns and kernels.  The secret keys go to d_payload (free during a signing call) and do not outlive
+// the call in HBM: finish() zeroes them behind the last launch, the destructor on every way out between upload_keys() and finish().
+struct sign_call {
+  ibft_ctx *c;
+  uint32_t nonce;
+  size_t n;
+  bool keys_up = false;
+  ~sign_call() {
+    if (!keys_up || !c->d_payload.p) return;
+    (void)hipMemsetAsync(c->d_payload.p, 0, n * 32, c->stream);
+    (void)hipStreamSynchronize(c->stream);
+  }
+  int check(const char *fn_name) {
+    if (nonce != IBFT_SIGN_NONCE_KECCAK && nonce != IBFT_SIGN_NONCE_RFC6979) {
+      c->last_error = std::string(fn_name) + ": unknown nonce rule " + std::to_string(nonce) + " (IBFT_SIGN_NONCE_KECCAK = 0, IBFT_SIGN_NONCE_RFC6979 = 1)";
+      return IBFT_E_INVAL;
+    }
+    return n > c->max_rows ? IBFT_E_TOOBIG : IBFT_OK;
+  }
+  int begin() {
+    HIPCHK(c, hipSetDevice(c->device));
+    c->wire_valid = false;  // the columns used from here on are the wire walker's and the seal batch's
+    c->staged_n = 0;
+    return IBFT_OK;
+  }
+  int upload_keys(const uint8_t *sk32) {
+    keys_up = true;  // (from here on: a copy that fails may have moved some of them)
+    return upload(c, c->d_payload, sk32, n * 32);
+  }
+  uint32_t blocks() const { return (uint32_t)((n + ibftk::ROWS_PER_BLOCK - 1) / ibftk::ROWS_PER_BLOCK); }
+  // a lane kernel of the signer, one wavefront per 64 rows, instantiated for the call's nonce rule: pick(N) names kernel<N>
+  template <class Pick, class Args>
+  void launch_signed(Pick pick, const Args &a) {
+    with_int<ibftk::SIGN_NONCE_KECCAK, ibftk::SIGN_NONCE_RFC6979>((int)nonce, [&](auto N) {
+      hipLaunchKernelGGL(pick(N), dim3(blocks()), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
+    });
+  }
+  int finish(uint8_t *out_bytes, const void *d_bytes, size_t n_bytes, uint8_t *out_from20, uint8_t *out_ok) {
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemsetAsync(c->d_payload.p, 0, n * 32, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_bytes, d_bytes, n_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (out_from20) HIPCHK(c, hipMemcpyAsync(out_from20, c->d_signer.p, n * 20, hipMemcpyDeviceToHost, c->stream));
+    if (out_ok) HIPCHK(c, hipMemcpyAsync(out_ok, c->d_pre.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    keys_up = false;  // (zeroed, and the stream has drained)
+    return IBFT_OK;
+  }
+};
+
 }  // namespace
 
 // One host thread per device of a group: staging and launching a shard costs tens of microseconds of host time per
@@ -2823,19 +2873,11 @@ int ibft_sign_seals_ex(ibft_ctx *c, const uint8_t *sk32, const uint8_t *hash32, 
                        uint8_t *out_signer20, uint8_t *out_ok) {
   if (!c || (n && (!sk32 || !hash32 || !out_sig65))) return IBFT_E_INVAL;
   ctx_lock lk(c);
-  if (nonce != IBFT_SIGN_NONCE_KECCAK && nonce != IBFT_SIGN_NONCE_RFC6979) {
-    c->last_error = "ibft_sign_seals_ex: unknown nonce rule " + std::to_string(nonce) +
-                    " (IBFT_SIGN_NONCE_KECCAK = 0, IBFT_SIGN_NONCE_RFC6979 = 1)";
-    return IBFT_E_INVAL;
-  }
-  if (n > c->max_rows) return IBFT_E_TOOBIG;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->wire_valid = false;
-  c->staged_n = 0;
-  if (n == 0) return IBFT_OK;
+  sign_call sc{c, nonce, n};
   int rc;
-  if ((rc = upload(c, c->d_payload, sk32, n * 32))) return rc;  // the sender-payload column is free during a seal batch
-  if ((rc = upload(c, c->d_hash, hash32, n * 32))) return rc;
+  if ((rc = sc.check("ibft_sign_seals_ex")) || (rc = sc.begin())) return rc;
+  if (n == 0) return IBFT_OK;
+  if ((rc = sc.upload_keys(sk32)) || (rc = upload(c, c->d_hash, hash32, n * 32))) return rc;
   if ((rc = apply_seal_digest(c, 0, (uint32_t)n, false))) return rc;  // a seal signs what the convention says it signs
   ibftk::sign_args a;
   a.gtab = (const uint32_t *)c->dev->d_gtab.p;
@@ -2845,17 +2887,8 @@ int ibft_sign_seals_ex(ibft_ctx *c, const uint8_t *sk32, const uint8_t *hash32, 
   a.signer20 = (uint8_t *)c->d_signer.p;
   a.ok = (uint8_t *)c->d_pre.p;
   a.n = (uint32_t)n;
-  const uint32_t blocks = (uint32_t)((n + ibftk::ROWS_PER_BLOCK - 1) / ibftk::ROWS_PER_BLOCK);
-  if (nonce == IBFT_SIGN_NONCE_RFC6979)
-    hipLaunchKernelGGL(ibftk::sign_lane_kernel<ibftk::SIGN_NONCE_RFC6979>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
-  else
-    hipLaunchKernelGGL(ibftk::sign_lane_kernel<ibftk::SIGN_NONCE_KECCAK>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemsetAsync(c->d_payload.p, 0, n * 32, c->stream));  // the keys do not outlive the call in HBM
-  HIPCHK(c, hipMemcpyAsync(out_sig65, c->d_sig.p, n * 65, hipMemcpyDeviceToHost, c->stream));
-  if (out_signer20) HIPCHK(c, hipMemcpyAsync(out_signer20, c->d_signer.p, n * 20, hipMemcpyDeviceToHost, c->stream));
-  if (out_ok) HIPCHK(c, hipMemcpyAsync(out_ok, c->d_pre.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  sc.launch_signed([](auto N) { return ibftk::sign_lane_kernel<decltype(N)::value>; }, a);
+  if ((rc = sc.finish(out_sig65, c->d_sig.p, n * 65, out_signer20, out_ok))) return rc;
   // hash32 / sig65 / signer20 now hold exactly what ibft_seals_stage would have uploaded for these seals:
   // the batch is staged (rows whose key was refused carry a zero signature, which every verifier rejects)
   c->staged_n = (uint32_t)n;
@@ -2870,12 +2903,9 @@ int ibft_sign_messages_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *typ
                             uint8_t *out_from20, uint8_t *out_ok) {
   if (!c || (n && (!sk32 || !type || !height || !round || !hash32 || !out_wire || !out_off))) return IBFT_E_INVAL;
   ctx_lock lk(c);
-  if (nonce != IBFT_SIGN_NONCE_KECCAK && nonce != IBFT_SIGN_NONCE_RFC6979) {
-    c->last_error = "ibft_sign_messages_wire: unknown nonce rule " + std::to_string(nonce) +
-                    " (IBFT_SIGN_NONCE_KECCAK = 0, IBFT_SIGN_NONCE_RFC6979 = 1)";
-    return IBFT_E_INVAL;
-  }
-  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  sign_call sc{c, nonce, n};
+  int rc;
+  if ((rc = sc.check("ibft_sign_messages_wire"))) return rc;
   std::vector<uint32_t> off(n + 1);
   uint64_t total = 0;
   for (size_t i = 0; i < n; i++) {
@@ -2892,14 +2922,11 @@ int ibft_sign_messages_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *typ
     c->last_error = "ibft_sign_messages_wire: the messages take " + std::to_string(total) + " bytes, wire_cap is " + std::to_string(wire_cap);
     return IBFT_E_TOOBIG;
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  c->wire_valid = false;  // the columns below are the wire walker's and the seal batch's
-  c->staged_n = 0;
+  if ((rc = sc.begin())) return rc;
   if (n == 0) {
     if (out_off) out_off[0] = 0;
     return IBFT_OK;
   }
-  int rc;
   const size_t col = (n + 7) & ~(size_t)7;  // the type bytes sit behind two 8-byte columns
   if ((rc = ensure(c, c->d_msg_cols, 17 * col))) return rc;
   if ((rc = ensure(c, c->d_msg_wire, (size_t)total))) return rc;
@@ -2907,8 +2934,7 @@ int ibft_sign_messages_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *typ
   HIPCHK(c, hipMemcpyAsync(cols, height, n * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(cols + 8 * col, round, n * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(cols + 16 * col, type, n, hipMemcpyHostToDevice, c->stream));
-  if ((rc = upload(c, c->d_payload, sk32, n * 32))) return rc;  // the sender-payload column is free here, as in ibft_sign_seals
-  if ((rc = upload(c, c->d_hash, hash32, n * 32))) return rc;
+  if ((rc = sc.upload_keys(sk32)) || (rc = upload(c, c->d_hash, hash32, n * 32))) return rc;
   if ((rc = upload(c, c->d_off, off.data(), (n + 1) * 4))) return rc;
   ibftk::sign_message_args a;
   a.gtab = (const uint32_t *)c->dev->d_gtab.p;
@@ -2924,36 +2950,24 @@ int ibft_sign_messages_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *typ
   a.n = (uint32_t)n;
   a.convert = c->seal_digest_mode != 0 ? 1u : 0u;  // the seal signs what the convention says it signs; the envelope never does
   memcpy(a.suffix_words, c->seal_suffix_words, sizeof a.suffix_words);
-  const uint32_t blocks = (uint32_t)((n + ibftk::ROWS_PER_BLOCK - 1) / ibftk::ROWS_PER_BLOCK);
-  if (nonce == IBFT_SIGN_NONCE_RFC6979)
-    hipLaunchKernelGGL(ibftk::sign_message_lane_kernel<ibftk::SIGN_NONCE_RFC6979>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
-  else
-    hipLaunchKernelGGL(ibftk::sign_message_lane_kernel<ibftk::SIGN_NONCE_KECCAK>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemsetAsync(c->d_payload.p, 0, n * 32, c->stream));  // the keys do not outlive the call in HBM
-  HIPCHK(c, hipMemcpyAsync(out_wire, c->d_msg_wire.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
-  if (out_from20) HIPCHK(c, hipMemcpyAsync(out_from20, c->d_signer.p, n * 20, hipMemcpyDeviceToHost, c->stream));
-  if (out_ok) HIPCHK(c, hipMemcpyAsync(out_ok, c->d_pre.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  sc.launch_signed([](auto N) { return ibftk::sign_message_lane_kernel<decltype(N)::value>; }, a);
+  if ((rc = sc.finish(out_wire, c->d_msg_wire.p, (size_t)total, out_from20, out_ok))) return rc;
   memcpy(out_off, off.data(), (n + 1) * 4);
   return IBFT_OK;
 }
 
 // f4 two layers up: PREPREPARE / ROUND_CHANGE envelopes around bodies the caller encoded (sign_envelope_dev.h).  A row's length
 // depends on type, height, round and body length alone, so offsets, body destinations and the copy kernel's pieces are computed
-// here, before anything is launched.  Four launches on the main stream: heads, body copy, digests, signatures.
+// here, in one pass, before anything is launched.  Four launches on the main stream: heads, body copy, digests, signatures.
 int ibft_sign_envelopes_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *type, const uint64_t *height, const uint64_t *round,
                              const uint8_t *body, size_t body_bytes, const uint32_t *body_at, const uint32_t *body_len, size_t n,
                              uint32_t nonce, uint8_t *out_wire, size_t wire_cap, uint32_t *out_off, uint8_t *out_from20, uint8_t *out_ok) {
   if (!c || (n && (!sk32 || !type || !height || !round || !body_at || !body_len || !out_wire || !out_off))) return IBFT_E_INVAL;
   if (!body && body_bytes) return IBFT_E_INVAL;
   ctx_lock lk(c);
-  if (nonce != IBFT_SIGN_NONCE_KECCAK && nonce != IBFT_SIGN_NONCE_RFC6979) {
-    c->last_error = "ibft_sign_envelopes_wire: unknown nonce rule " + std::to_string(nonce) +
-                    " (IBFT_SIGN_NONCE_KECCAK = 0, IBFT_SIGN_NONCE_RFC6979 = 1)";
-    return IBFT_E_INVAL;
-  }
-  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  sign_call sc{c, nonce, n};
+  int rc;
+  if ((rc = sc.check("ibft_sign_envelopes_wire"))) return rc;
   for (size_t i = 0; i < n; i++) {
     if (type[i] != ibftk::MSG_TYPE_PREPREPARE && type[i] != ibftk::MSG_TYPE_ROUND_CHANGE) {
       c->last_error = "ibft_sign_envelopes_wire: row " + std::to_string(i) + " has type " + std::to_string((unsigned)type[i]) +
@@ -2968,11 +2982,22 @@ int ibft_sign_envelopes_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *ty
       return IBFT_E_INVAL;
     }
   }
-  uint64_t total = 0, total_blocks = 0, max_blocks = 0;
-  for (size_t i = 0; i < n; i++) {
-    const uint64_t len = ibftk::envelope_wire_len(type[i], height[i], round[i], body_len[i]);
-    const uint64_t blocks = (len - ibftk::SIGN_MESSAGE_SIG_FIELD) / 136u + 1u;
-    total += len;  // (n ≤ max_rows rows of < 2^33 bytes: no overflow)
+  // host columns, one upload: height ‖ round (8-byte entries) ‖ body_at ‖ body_len ‖ dst_at ‖ off[n+1] ‖ piece_first[n+1] ‖ type
+  const size_t col = (n + 8) & ~(size_t)7;  // entries per column, room for the n + 1 of the last two
+  std::vector<uint64_t> cols((16 * col + 20 * col + col + 7) / 8);
+  uint8_t *h = (uint8_t *)cols.data();
+  uint64_t *h_height = (uint64_t *)h, *h_round = h_height + col;
+  uint32_t *h_at = (uint32_t *)(h + 16 * col), *h_len = h_at + col, *h_dst = h_len + col, *h_off = h_dst + col, *h_piece = h_off + col;
+  uint8_t *h_type = h + 36 * col;
+  uint64_t total = 0, total_blocks = 0, max_blocks = 0, pieces = 0;
+  for (size_t i = 0; i < n; i++) {  // (dst_at, off and piece_first in front of the size checks, which read this pass's totals)
+    const uint32_t head = ibftk::envelope_head_len(type[i], height[i], round[i], body_len[i]);
+    const uint64_t blocks = ((uint64_t)head + body_len[i] - ibftk::SIGN_MESSAGE_SIG_FIELD) / 136u + 1u;
+    h_off[i] = (uint32_t)total;
+    h_dst[i] = (uint32_t)total + head;
+    h_piece[i] = (uint32_t)pieces;
+    pieces += ibftk::envelope_copy_pieces(h_dst[i], body_len[i]);  // (≤ total / 4 096 + 2 n in all)
+    total += (uint64_t)head + body_len[i];                         // (n ≤ max_rows rows of < 2^33 bytes: no overflow)
     total_blocks += blocks;
     max_blocks = std::max(max_blocks, blocks);
   }
@@ -2985,42 +3010,24 @@ int ibft_sign_envelopes_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *ty
     c->last_error = "ibft_sign_envelopes_wire: the messages take " + std::to_string(total) + " bytes, wire_cap is " + std::to_string(wire_cap);
     return IBFT_E_TOOBIG;
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  c->wire_valid = false;  // the columns below are the wire walker's and the seal batch's
-  c->staged_n = 0;
+  if ((rc = sc.begin())) return rc;
   if (n == 0) {
     if (out_off) out_off[0] = 0;
     return IBFT_OK;
   }
-  // host columns, one upload: height ‖ round (8-byte entries) ‖ body_at ‖ body_len ‖ dst_at ‖ off[n+1] ‖ piece_first[n+1] ‖ type
-  const size_t col = (n + 8) & ~(size_t)7;  // entries per column, room for the n + 1 of the last two
-  std::vector<uint64_t> cols((16 * col + 20 * col + col + 7) / 8);
-  uint8_t *h = (uint8_t *)cols.data();
-  uint64_t *h_height = (uint64_t *)h, *h_round = h_height + col;
-  uint32_t *h_at = (uint32_t *)(h + 16 * col), *h_len = h_at + col, *h_dst = h_len + col, *h_off = h_dst + col, *h_piece = h_off + col;
-  uint8_t *h_type = h + 36 * col;
+  h_off[n] = (uint32_t)total;
+  h_piece[n] = (uint32_t)pieces;
   memcpy(h_height, height, n * 8);
   memcpy(h_round, round, n * 8);
   memcpy(h_at, body_at, n * 4);
   memcpy(h_len, body_len, n * 4);
   memcpy(h_type, type, n);
-  uint64_t at = 0, pieces = 0;
-  for (size_t i = 0; i < n; i++) {
-    h_off[i] = (uint32_t)at;
-    h_dst[i] = (uint32_t)at + ibftk::envelope_head_len(type[i], height[i], round[i], body_len[i]);
-    h_piece[i] = (uint32_t)pieces;
-    pieces += ibftk::envelope_copy_pieces(h_dst[i], body_len[i]);
-    at += ibftk::envelope_wire_len(type[i], height[i], round[i], body_len[i]);
-  }
-  h_off[n] = (uint32_t)at;
-  h_piece[n] = (uint32_t)pieces;  // (≤ total / 4 096 + 2 n)
-  int rc;
   if ((rc = ensure(c, c->d_env_body, body_bytes + 256))) return rc;  // the copy and the sponges read a few bytes past a range
   if ((rc = ensure(c, c->d_env_wire, (size_t)total + 256))) return rc;
   if ((rc = ensure(c, c->d_hash, n * 32))) return rc;
   if ((rc = upload(c, c->d_env_cols, h, 37 * col))) return rc;
   if (body_bytes) HIPCHK(c, hipMemcpyAsync(c->d_env_body.p, body, body_bytes, hipMemcpyHostToDevice, c->stream));
-  if ((rc = upload(c, c->d_payload, sk32, n * 32))) return rc;  // the sender-payload column is free here, as in ibft_sign_seals
+  if ((rc = sc.upload_keys(sk32))) return rc;
   const uint8_t *d = (const uint8_t *)c->d_env_cols.p;
   ibftk::sign_envelope_args a;
   a.gtab = (const uint32_t *)c->dev->d_gtab.p;
@@ -3039,26 +3046,17 @@ int ibft_sign_envelopes_wire(ibft_ctx *c, const uint8_t *sk32, const uint8_t *ty
   a.from20 = (uint8_t *)c->d_signer.p;
   a.ok = (uint8_t *)c->d_pre.p;
   a.n = (uint32_t)n;
-  const uint32_t blocks = (uint32_t)((n + ibftk::ROWS_PER_BLOCK - 1) / ibftk::ROWS_PER_BLOCK);
-  hipLaunchKernelGGL(ibftk::envelope_head_kernel, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
+  hipLaunchKernelGGL(ibftk::envelope_head_kernel, dim3(sc.blocks()), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
   if (pieces) hipLaunchKernelGGL(ibftk::envelope_copy_kernel, dim3((uint32_t)pieces), dim3(ibftk::ENVELOPE_COPY_THREADS), 0, c->stream, a);
   // the digest's form by proposal_form's rule: the batch's size in messages of the longest one's length
   const uint32_t form = c->envelope_lanes_force ? c->envelope_lanes_force
                         : (n >= 64 && total_blocks >= (uint64_t)c->proposal_lane_rows * max_blocks) ? 1u : 64u;
   if (form == 1)
-    hipLaunchKernelGGL(ibftk::envelope_digest_kernel<1>, dim3(blocks), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(ibftk::envelope_digest_kernel<1>, dim3(sc.blocks()), dim3(64), 0, c->stream, a);
   else
     hipLaunchKernelGGL(ibftk::envelope_digest_kernel<64>, dim3((uint32_t)n), dim3(64), 0, c->stream, a);
-  if (nonce == IBFT_SIGN_NONCE_RFC6979)
-    hipLaunchKernelGGL(ibftk::sign_envelope_lane_kernel<ibftk::SIGN_NONCE_RFC6979>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
-  else
-    hipLaunchKernelGGL(ibftk::sign_envelope_lane_kernel<ibftk::SIGN_NONCE_KECCAK>, dim3(blocks), dim3(ibftk::ROWS_PER_BLOCK), 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemsetAsync(c->d_payload.p, 0, n * 32, c->stream));  // the keys do not outlive the call in HBM
-  HIPCHK(c, hipMemcpyAsync(out_wire, c->d_env_wire.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
-  if (out_from20) HIPCHK(c, hipMemcpyAsync(out_from20, c->d_signer.p, n * 20, hipMemcpyDeviceToHost, c->stream));
-  if (out_ok) HIPCHK(c, hipMemcpyAsync(out_ok, c->d_pre.p, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  sc.launch_signed([](auto N) { return ibftk::sign_envelope_lane_kernel<decltype(N)::value>; }, a);
+  if ((rc = sc.finish(out_wire, c->d_env_wire.p, (size_t)total, out_from20, out_ok))) return rc;
   memcpy(out_off, h_off, (n + 1) * 4);
   return IBFT_OK;
 }

@@ -56,6 +56,7 @@ using secp::jac;
 using secp::u256;
 
 constexpr int ROWS_PER_BLOCK = 64; // one wavefront per block in the lane kernel
+static_assert(ROWS_PER_BLOCK == 64, "sign_dev.h: lane_row frames a workgroup of one wavefront");
 
 // (validator table lookup — valset_lookup — and a row's decision once the curve is done — emit_row, claim_row — live in
 // recover_dev.h: the CPU harness compiles them too)
@@ -203,39 +204,17 @@ struct sign_args {
 // (sign_dev.h: rfc6979_drbg) — same arguments, same columns, same stores.
 template <int NONCE>
 __global__ void __launch_bounds__(ROWS_PER_BLOCK) sign_lane_kernel(sign_args a) {
-  const uint32_t row = blockIdx.x * (uint32_t)ROWS_PER_BLOCK + threadIdx.x;
-  const bool live = row < a.n;
-  const uint32_t src = live ? row : a.n - 1;  // idle lanes sign the last row again and store nothing
+  const lane_row l(a.n);
   uint8_t sk[32], dg[32];
-  const uint32_t *ks = reinterpret_cast<const uint32_t *>(a.sk32 + 32ull * src);
-  const uint32_t *ds = reinterpret_cast<const uint32_t *>(a.hash32 + 32ull * src);
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    uint32_t kw = ks[i], dw = ds[i];
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-      sk[4 * i + b] = (uint8_t)(kw >> (8 * b));
-      dg[4 * i + b] = (uint8_t)(dw >> (8 * b));
-    }
-  }
+  load_row32(a.sk32, l.src, sk);
+  load_row32(a.hash32, l.src, dg);
   u256 r, s;
   uint32_t v, addr[5];
   const bool ok = sign_row<NONCE>(a.gtab, sk, dg, r, s, v, addr, 0u);
-  if (!live) return;
-  uint8_t *o = a.sig65 + 65ull * row;  // 65-byte rows are not dword aligned: byte stores
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-      o[4 * (7 - i) + b] = (uint8_t)(r.v[i] >> (8 * (3 - b)));
-      o[32 + 4 * (7 - i) + b] = (uint8_t)(s.v[i] >> (8 * (3 - b)));
-    }
-  }
-  o[64] = (uint8_t)v;
-  uint32_t *ad = reinterpret_cast<uint32_t *>(a.signer20 + 20ull * row);
-#pragma unroll
-  for (int i = 0; i < 5; i++) ad[i] = addr[i];
-  a.ok[row] = ok ? 1 : 0;
+  if (!l.live) return;
+  put_sig65(a.sig65 + 65ull * l.row, r, s, v);  // 65-byte rows are not dword aligned: byte stores
+  store_addr20(a.signer20, l.row, addr);
+  a.ok[l.row] = ok ? 1 : 0;
 }
 
 // ---- f4, one layer up: a whole PREPARE / COMMIT message per lane, as wire bytes (sign_message_dev.h) --------------------
@@ -261,33 +240,18 @@ struct sign_message_args {
 template <int NONCE>
 __global__ void __launch_bounds__(ROWS_PER_BLOCK) sign_message_lane_kernel(sign_message_args a) {
   __shared__ uint64_t lds[ROWS_PER_BLOCK * SIGN_MESSAGE_BUF_WORDS];
-  const uint32_t row = blockIdx.x * (uint32_t)ROWS_PER_BLOCK + threadIdx.x;
-  const bool live = row < a.n;
-  const uint32_t src = live ? row : a.n - 1;
+  const lane_row l(a.n);
   uint8_t sk[32], hs[32];
-  const uint32_t *ks = reinterpret_cast<const uint32_t *>(a.sk32 + 32ull * src);
-  const uint32_t *hp = reinterpret_cast<const uint32_t *>(a.hash32 + 32ull * src);
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    uint32_t kw = ks[i], hw = hp[i];
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-      sk[4 * i + b] = (uint8_t)(kw >> (8 * b));
-      hs[4 * i + b] = (uint8_t)(hw >> (8 * b));
-    }
-  }
-  const uint32_t type = a.type[src];
-  const uint64_t height = a.height[src], round = a.round[src];
+  load_row32(a.sk32, l.src, sk);
+  load_row32(a.hash32, l.src, hs);
   uint64_t *buf = lds + (size_t)SIGN_MESSAGE_BUF_WORDS * threadIdx.x;
-  const message_row m = sign_message_row<NONCE>(a.gtab, sk, type, height, round, hs, a.convert, a.suffix_words, buf);
-  if (!live) return;
-  const uint32_t at = a.off[row];
-  const bool fits = a.off[row + 1] - at == m.len + SIGN_MESSAGE_SIG_FIELD;  // (the host computed it with the same function)
+  const message_row m = sign_message_row<NONCE>(a.gtab, sk, a.type[l.src], a.height[l.src], a.round[l.src], hs, a.convert, a.suffix_words, buf);
+  if (!l.live) return;
+  const uint32_t at = a.off[l.row];
+  const bool fits = a.off[l.row + 1] - at == m.len + SIGN_MESSAGE_SIG_FIELD;  // (the host computed it with the same function)
   if (fits) store_message(a.wire + at, buf, m);
-  uint32_t *ad = reinterpret_cast<uint32_t *>(a.from20 + 20ull * row);
-#pragma unroll
-  for (int i = 0; i < 5; i++) ad[i] = m.addr[i];
-  a.ok[row] = (m.ok && fits) ? 1 : 0;
+  store_addr20(a.from20, l.row, m.addr);
+  a.ok[l.row] = (m.ok && fits) ? 1 : 0;
 }
 
 // ---- f4, two layers up: a PREPREPARE / ROUND_CHANGE envelope around a given body, as wire bytes (sign_envelope_dev.h) ------
@@ -323,30 +287,20 @@ struct sign_envelope_args {
 };
 __global__ void __launch_bounds__(ROWS_PER_BLOCK) envelope_head_kernel(sign_envelope_args a) {
   __shared__ uint64_t lds[ROWS_PER_BLOCK * ENVELOPE_HEAD_WORDS];
-  const uint32_t row = blockIdx.x * (uint32_t)ROWS_PER_BLOCK + threadIdx.x;
-  const bool live = row < a.n;
-  const uint32_t src = live ? row : a.n - 1;
+  const lane_row l(a.n);
   uint8_t sk[32];
-  const uint32_t *ks = reinterpret_cast<const uint32_t *>(a.sk32 + 32ull * src);
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const uint32_t kw = ks[i];
-#pragma unroll
-    for (int b = 0; b < 4; b++) sk[4 * i + b] = (uint8_t)(kw >> (8 * b));
-  }
+  load_row32(a.sk32, l.src, sk);
   u256 d;
   const bool key_ok = sign_key(sk, d);
   uint32_t addr[5];
   sign_address(a.gtab, d, key_ok, addr);
   uint8_t *p = reinterpret_cast<uint8_t *>(lds + (size_t)ENVELOPE_HEAD_WORDS * threadIdx.x);
-  const uint32_t body_len = a.body_len[src];
-  const uint32_t head = envelope_head(p, a.type[src], a.height[src], a.round[src], addr, body_len);
-  if (!live) return;
-  const uint32_t at = a.off[row];
-  if (a.off[row + 1] - at == head + body_len) store_envelope_head(a.wire + at, p, head);  // (the host computed it with the same function)
-  uint32_t *ad = reinterpret_cast<uint32_t *>(a.from20 + 20ull * row);
-#pragma unroll
-  for (int i = 0; i < 5; i++) ad[i] = addr[i];
+  const uint32_t body_len = a.body_len[l.src];
+  const uint32_t head = envelope_head(p, a.type[l.src], a.height[l.src], a.round[l.src], addr, body_len);
+  if (!l.live) return;
+  const uint32_t at = a.off[l.row];
+  if (a.off[l.row + 1] - at == head + body_len) store_envelope_head(a.wire + at, p, head);  // (the host computed it with the same function)
+  store_addr20(a.from20, l.row, addr);
 }
 __global__ void __launch_bounds__(ENVELOPE_COPY_THREADS) envelope_copy_kernel(sign_envelope_args a) {
   // the row that owns this workgroup: the last one whose first piece is not behind it (rows without a body own none)
@@ -360,14 +314,12 @@ __global__ void __launch_bounds__(ENVELOPE_COPY_THREADS) envelope_copy_kernel(si
 template <int LANES>
 __global__ void __launch_bounds__(64) envelope_digest_kernel(sign_envelope_args a) {
   if constexpr (LANES == 1) {
-    const uint32_t row = blockIdx.x * 64u + threadIdx.x;
-    const bool live = row < a.n;
-    const uint32_t src = live ? row : a.n - 1;
-    const uint32_t o0 = a.off[src], len = a.off[src + 1] - o0;
+    const lane_row l(a.n);
+    const uint32_t o0 = a.off[l.src], len = a.off[l.src + 1] - o0;
     uint64_t d[4];
-    envelope_digest_lane(a.wire + o0, len, envelope_cut(a.height[src], a.round[src]), live, d);  // idle lanes: the empty message
-    if (live) {
-      uint4 *o = reinterpret_cast<uint4 *>(a.digest32 + 32ull * row);
+    envelope_digest_lane(a.wire + o0, len, envelope_cut(a.height[l.src], a.round[l.src]), l.live, d);  // idle lanes: the empty message
+    if (l.live) {
+      uint4 *o = reinterpret_cast<uint4 *>(a.digest32 + 32ull * l.row);
       o[0] = make_uint4((uint32_t)d[0], (uint32_t)(d[0] >> 32), (uint32_t)d[1], (uint32_t)(d[1] >> 32));
       o[1] = make_uint4((uint32_t)d[2], (uint32_t)(d[2] >> 32), (uint32_t)d[3], (uint32_t)(d[3] >> 32));
     }
@@ -381,28 +333,17 @@ __global__ void __launch_bounds__(64) envelope_digest_kernel(sign_envelope_args 
 }
 template <int NONCE>
 __global__ void __launch_bounds__(ROWS_PER_BLOCK) sign_envelope_lane_kernel(sign_envelope_args a) {
-  const uint32_t row = blockIdx.x * (uint32_t)ROWS_PER_BLOCK + threadIdx.x;
-  const bool live = row < a.n;
-  const uint32_t src = live ? row : a.n - 1;
+  const lane_row l(a.n);
   uint8_t sk[32], dg[32];
-  const uint32_t *ks = reinterpret_cast<const uint32_t *>(a.sk32 + 32ull * src);
-  const uint32_t *ds = reinterpret_cast<const uint32_t *>(a.digest32 + 32ull * src);
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    uint32_t kw = ks[i], dw = ds[i];
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-      sk[4 * i + b] = (uint8_t)(kw >> (8 * b));
-      dg[4 * i + b] = (uint8_t)(dw >> (8 * b));
-    }
-  }
+  load_row32(a.sk32, l.src, sk);
+  load_row32(a.digest32, l.src, dg);
   u256 r, s;
   uint32_t v;
-  const bool ok = sign_envelope_row<NONCE>(a.gtab, sk, dg, r, s, v);
-  if (!live) return;
-  const uint32_t at = a.off[row], cut = envelope_cut(a.height[row], a.round[row]);
+  const bool ok = sign_digest<NONCE>(a.gtab, sk, dg, r, s, v);
+  if (!l.live) return;
+  const uint32_t row = l.row, at = a.off[row], cut = envelope_cut(a.height[row], a.round[row]);
   const bool fits = a.off[row + 1] - at == envelope_head_len(a.type[row], a.height[row], a.round[row], a.body_len[row]) + a.body_len[row];
-  if (fits) store_envelope_signature(a.wire + at, cut, r, s, v);
+  if (fits) put_sig65(a.wire + at + cut + 2u, r, s, v);  // into the field the head left zero
   a.ok[row] = (ok && fits) ? 1 : 0;
 }
 
@@ -2408,17 +2349,9 @@ __global__ void seal_digest_kernel(seal_digest_args a) {
     q[0] = x;
     q[1] = y;
   }
-  uint64_t s[25];
-#pragma unroll
-  for (int i = 0; i < 25; i++) s[i] = 0;
-  s[0] = (uint64_t)x.x | ((uint64_t)x.y << 32);
-  s[1] = (uint64_t)x.z | ((uint64_t)x.w << 32);
-  s[2] = (uint64_t)y.x | ((uint64_t)y.y << 32);
-  s[3] = (uint64_t)y.z | ((uint64_t)y.w << 32);
-#pragma unroll
-  for (int j = 0; j < 9; j++) s[4 + j] = a.suffix_words[j];
-  s[16] ^= 0x8000000000000000ull;  // pad10*1: the last bit of the 136-byte rate
-  keccak::f1600(s);
+  uint64_t s[4] = {(uint64_t)x.x | ((uint64_t)x.y << 32), (uint64_t)x.z | ((uint64_t)x.w << 32), (uint64_t)y.x | ((uint64_t)y.y << 32),
+                   (uint64_t)y.z | ((uint64_t)y.w << 32)};
+  seal_digest_words(s, a.suffix_words);
   p[0] = make_uint4((uint32_t)s[0], (uint32_t)(s[0] >> 32), (uint32_t)s[1], (uint32_t)(s[1] >> 32));
   p[1] = make_uint4((uint32_t)s[2], (uint32_t)(s[2] >> 32), (uint32_t)s[3], (uint32_t)(s[3] >> 32));
 }

@@ -91,9 +91,23 @@ __host__ __device__ __forceinline__ uint32_t block_of_row(const uint32_t *__rest
   }
   return lo;
 }
+// The seal-digest convention (ibft_set_seal_digest) as the one-block sponge it is: w = keccak256(w ‖ suffix), four little-endian
+// words in, four out.  suffix_words is the suffix ‖ 0x01 ‖ 0… as little-endian words, bytes 32..103 of the one Keccak block.
+__host__ __device__ __forceinline__ void seal_digest_words(uint64_t w[4], const uint64_t suffix_words[9]) {
+  uint64_t s[25];
+#pragma unroll
+  for (int i = 0; i < 4; i++) s[i] = w[i];
+#pragma unroll
+  for (int j = 0; j < 9; j++) s[4 + j] = suffix_words[j];
+#pragma unroll
+  for (int i = 13; i < 25; i++) s[i] = 0;
+  s[16] ^= 0x8000000000000000ull;  // pad10*1: the last bit of the 136-byte rate
+  keccak::f1600(s);
+#pragma unroll
+  for (int i = 0; i < 4; i++) w[i] = s[i];
+}
 // What block_head_kernel writes for one row: its block's digest as it is (convert = 0, the identity convention) or
-// keccak256(digest ‖ suffix) — suffix_words is the suffix ‖ 0x01 ‖ 0… as little-endian words, bytes 32..103 of the one Keccak
-// block (ibft_set_seal_digest).  The digests are only READ: they may be on their way to the host while this runs.
+// keccak256(digest ‖ suffix).  The digests are only READ: they may be on their way to the host while this runs.
 struct block_head_t {
   uint64_t w[4];
 };
@@ -102,17 +116,8 @@ __host__ __device__ __forceinline__ block_head_t block_head_row(const uint64_t *
                                                                 const uint64_t suffix_words[9]) {
   const uint64_t *d = digest_words + 4ull * block_of_row(off, n_blocks, row);
   block_head_t r;
-  if (!convert) {
-    for (int i = 0; i < 4; i++) r.w[i] = d[i];
-    return r;
-  }
-  uint64_t s[25];
-  for (int i = 0; i < 4; i++) s[i] = d[i];
-  for (int j = 0; j < 9; j++) s[4 + j] = suffix_words[j];
-  for (int i = 13; i < 25; i++) s[i] = 0;
-  s[16] ^= 0x8000000000000000ull;  // pad10*1: the last bit of the 136-byte rate
-  keccak::f1600(s);
-  for (int i = 0; i < 4; i++) r.w[i] = s[i];
+  for (int i = 0; i < 4; i++) r.w[i] = d[i];
+  if (convert) seal_digest_words(r.w, suffix_words);
   return r;
 }
 

@@ -182,7 +182,19 @@ __host__ __device__ __forceinline__ void sign_address(const uint32_t *__restrict
   }
 }
 
-// One row of ibft_sign_seals: the signature and the signer's address.
+// One signature over a digest under the key sk32: sign_key + sign_core.  What the envelope kernel and the CPU harnesses call;
+// sign_message_row keeps the two apart (one key, two digests).  On the device every lane of a wavefront must call it.
+template <int NONCE = SIGN_NONCE_KECCAK>
+__host__ __device__ __forceinline__ bool sign_digest(const uint32_t *__restrict__ gtab, const uint8_t *sk32, const uint8_t *digest32,
+                                                     u256 &r_out, u256 &s_out, uint32_t &v_out, uint32_t reject_mask = 0) {
+  u256 d;
+  const bool key_ok = sign_key(sk32, d);
+  return sign_core<NONCE>(gtab, sk32, d, key_ok, digest32, r_out, s_out, v_out, reject_mask);
+}
+
+// One row of ibft_sign_seals: the signature and the signer's address — sign_digest, then sign_address under the same key.  Spelled
+// with the key derived once: composed from the two calls it is derived twice, and sign_lane_kernel, which sits just below the
+// 64 KB of the instruction cache, pays 7 registers and 0.3 KB for that.
 template <int NONCE = SIGN_NONCE_KECCAK>
 __host__ __device__ __forceinline__ bool sign_row(const uint32_t *__restrict__ gtab, const uint8_t *sk32,
                                                   const uint8_t *digest32, u256 &r_out, u256 &s_out, uint32_t &v_out,
@@ -192,6 +204,43 @@ __host__ __device__ __forceinline__ bool sign_row(const uint32_t *__restrict__ g
   const bool ok = sign_core<NONCE>(gtab, sk32, d, key_ok, digest32, r_out, s_out, v_out, reject_mask);
   sign_address(gtab, d, key_ok, addr);
   return ok;
+}
+
+// ---- the row frame of the signer's lane kernels (kernels.hip.h): one lane per row, one wavefront per workgroup ----------------
+// Idle lanes of the last wavefront run the last row again (sign_core votes across the wavefront) and store nothing: `src` is the row
+// a lane reads, `row` the one it may write when `live`.
+struct lane_row {
+  uint32_t row, src;
+  bool live;
+  __device__ explicit lane_row(uint32_t n) : row(blockIdx.x * 64u + threadIdx.x), src(row < n ? row : n - 1), live(row < n) {}
+};
+// row `src` of a column of 32-byte entries as a private byte array: dword loads, unpacked
+__host__ __device__ __forceinline__ void load_row32(const uint8_t *__restrict__ col, uint32_t src, uint8_t out[32]) {
+  const uint32_t *w = reinterpret_cast<const uint32_t *>(col + 32ull * src);
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t x = w[i];
+#pragma unroll
+    for (int b = 0; b < 4; b++) out[4 * i + b] = (uint8_t)(x >> (8 * b));
+  }
+}
+// an address into row `row` of a column of 20-byte entries
+__host__ __device__ __forceinline__ void store_addr20(uint8_t *__restrict__ col, uint32_t row, const uint32_t addr[5]) {
+  uint32_t *ad = reinterpret_cast<uint32_t *>(col + 20ull * row);
+#pragma unroll
+  for (int i = 0; i < 5; i++) ad[i] = addr[i];
+}
+// r ‖ s ‖ v (big-endian; the 0x41-byte body of a signature field, or a 65-byte seal) at p — byte stores: p is anywhere
+__host__ __device__ __forceinline__ void put_sig65(uint8_t *p, const u256 &r, const u256 &s, uint32_t v) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      p[4 * (7 - i) + b] = (uint8_t)(r.v[i] >> (8 * (3 - b)));
+      p[32 + 4 * (7 - i) + b] = (uint8_t)(s.v[i] >> (8 * (3 - b)));
+    }
+  }
+  p[64] = (uint8_t)v;
 }
 
 }  // namespace ibftk

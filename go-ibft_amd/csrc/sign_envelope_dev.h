@@ -1,16 +1,12 @@
 // sign_envelope_dev.h — the signing side two layers up: a PREPREPARE / ROUND_CHANGE envelope around a body the caller encoded.
 //
-// Product code (__host__ __device__ like sign_message_dev.h: tests/test_sign_envelopes_host.py runs this very source on the CPU;
-// the shipped library only runs it on gfx950).  What the reference's Backend.BuildPrePrepareMessage / BuildRoundChangeMessage do
-// for one validator (/root/reference/core/backend.go:12-34), for the thousands of validators a simulator plays — the same
-// simulators-only entry point as sign_dev.h, with the same handling of keys.
+// Product code, __host__ __device__ and for simulators only, as sign_dev.h says (tests/test_sign_envelopes_host.py runs this source
+// on the CPU).  What the reference's Backend.BuildPrePrepareMessage / BuildRoundChangeMessage do for one validator
+// (/root/reference/core/backend.go:12-34).
 //
-// A row is (sk, type, height, round, body bytes).  Its message, in canonical proto3 (messages.proto:24-110, the rules wire_dev.h
-// checks):
+// A row is (sk, type, height, round, body bytes).  Its message is sign_message_dev.h's View ‖ From (put_message_front) and
+// signature field, then
 //
-//     0a <len> [08 varint(height)] [10 varint(round)]      View (field 1), present even when empty
-//     12 14 <From, 20 bytes>                               keccak256(X‖Y)[12..32) of sk·G
-//     1a 41 <signature, 65 bytes>                          ← NOT part of PayloadNoSig
 //     [20 03]                                              Type: absent for PREPREPARE (a zero scalar), 20 03 for ROUND_CHANGE
 //     2a | 42  varint(body_len)  <body>                    PrePrepareMessage (field 5) / RoundChangeMessage (field 8), emitted
 //                                                          even when the body is empty
@@ -22,7 +18,7 @@
 //   2. copy_body_piece   the bodies → behind the heads: a bandwidth copy between byte-granular offsets;
 //   3. the digest        keccak256 of the STORED message minus its signature field — the verifier's own code for exactly that:
 //                        wire::hash_pieces per lane (envelope_digest_lane) or cw::sponge_message per wavefront;
-//   4. sign_envelope_row sign the digest (sign_dev.h: sign_core), the signature goes into its place.
+//   4. sign_digest       sign the digest (sign_dev.h), the signature goes into its place.
 // The head is never spliced into a sponge on its own: step 3 reads what steps 1 and 2 stored.
 #pragma once
 #include "cert_wave_dev.h"
@@ -51,22 +47,7 @@ __host__ __device__ __forceinline__ uint64_t envelope_wire_len(uint32_t type, ui
 // zero; returns its length.
 __host__ __device__ __forceinline__ uint32_t envelope_head(uint8_t *p, uint32_t type, uint64_t height, uint64_t round,
                                                            const uint32_t addr[5], uint32_t body_len) {
-  uint32_t at = 0;
-  p[at++] = 0x0a;
-  p[at++] = (uint8_t)message_view_len(height, round);
-  if (height) {
-    p[at++] = 0x08;
-    at = put_varint(p, at, height);
-  }
-  if (round) {
-    p[at++] = 0x10;
-    at = put_varint(p, at, round);
-  }
-  p[at++] = 0x12;
-  p[at++] = 0x14;
-#pragma unroll
-  for (int i = 0; i < 20; i++) p[at + i] = (uint8_t)(addr[i >> 2] >> (8 * (i & 3)));
-  at += 20;
+  uint32_t at = put_message_front(p, height, round, addr);
   p[at++] = 0x1a;
   p[at++] = 0x41;
   for (int i = 0; i < 65; i++) p[at + i] = 0;
@@ -143,19 +124,5 @@ __host__ __device__ __forceinline__ uint64_t envelope_digest_wave(const uint8_t 
   return cw::sponge_message(m, cut, SIGN_MESSAGE_SIG_FIELD, len - SIGN_MESSAGE_SIG_FIELD, 0ull, false, lane, A, B);
 }
 
-// 4. The envelope signature over the digest of step 3.  On the device every lane of a wavefront must call this (sign_core votes
-// across the wavefront); false, and zeros, for a key outside [1, n).
-template <int NONCE>
-__host__ __device__ __forceinline__ bool sign_envelope_row(const uint32_t *__restrict__ gtab, const uint8_t *sk32, const uint8_t *digest32,
-                                                           secp::u256 &r, secp::u256 &s, uint32_t &v) {
-  secp::u256 d;
-  const bool key_ok = sign_key(sk32, d);
-  return sign_core<NONCE>(gtab, sk32, d, key_ok, digest32, r, s, v, 0u);
-}
-// into the field the head left zero: m is the row's first byte
-__host__ __device__ __forceinline__ void store_envelope_signature(uint8_t *__restrict__ m, uint32_t cut, const secp::u256 &r, const secp::u256 &s,
-                                                                  uint32_t v) {
-  put_sig65(m + cut + 2u, r, s, v);
-}
-
+// 4. The signature over that digest: sign_dev.h's sign_digest, stored by put_sig65 at cut + 2 of the row (the field the head left zero).
 }  // namespace ibftk

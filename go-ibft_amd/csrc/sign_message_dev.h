@@ -1,15 +1,14 @@
 // sign_message_dev.h — the signing side one layer up: a whole PREPARE / COMMIT message per row, as wire bytes.
 //
-// Product code (__host__ __device__ like sign_dev.h: tests/test_sign_messages_host.py runs this very source on the CPU; the
-// shipped library only runs it on gfx950).  What the reference's Backend.BuildPrepareMessage / BuildCommitMessage do for one
-// validator (/root/reference/core/backend.go:12-34), for the thousands of validators a simulator plays — the same simulators-only
-// entry point as sign_dev.h, with the same handling of keys.
+// Product code, __host__ __device__ and for simulators only, as sign_dev.h says (tests/test_sign_messages_host.py runs this source on
+// the CPU).  What the reference's Backend.BuildPrepareMessage / BuildCommitMessage do for one validator
+// (/root/reference/core/backend.go:12-34).
 //
 // A row is (sk, type, height, round, proposal hash).  Its message, in canonical proto3 (fields in field-number order, minimal
 // varints, zero scalars omitted, the View always present — messages.proto:24-110, the rules wire_dev.h checks):
 //
-//     0a <len> [08 varint(height)] [10 varint(round)]      View (field 1), present even when empty
-//     12 14 <From, 20 bytes>                               keccak256(X‖Y)[12..32) of sk·G
+//     0a <len> [08 varint(height)] [10 varint(round)]      View (field 1), present even when empty     ┐ put_message_front
+//     12 14 <From, 20 bytes>                               keccak256(X‖Y)[12..32) of sk·G              ┘
 //     1a 41 <signature, 65 bytes>                          ← NOT part of PayloadNoSig
 //     20 <type>                                            1 = PREPARE, 2 = COMMIT
 //     32 22 0a 20 <hash>                                   PREPARE: PrepareMessage (field 6)
@@ -18,10 +17,9 @@
 // PayloadNoSig (what the envelope signature signs the Keccak-256 of) is these bytes without the third line: 62 … 84 bytes for
 // a PREPARE, 129 … 151 for a COMMIT — so a COMMIT's hash is one Keccak block or two, with the 135-byte case (pad10*1 = the
 // single byte 0x81) in between.  The committed seal signs the proposal hash under the seal-digest convention
-// (ibft_set_seal_digest), the envelope never does.
-//
-// The payload is built in a buffer of the caller's (19 words per row: LDS on the device, never a private byte array), which
-// also is what the sponge absorbs; the wire form goes out from there with the signature spliced in.
+// (ibft_set_seal_digest), the envelope never does.  The payload is built in a buffer of the caller's (19 words per row: LDS on the
+// device, never a private byte array), which also is what the sponge absorbs; the wire form goes out from there with the
+// signature spliced in.
 #pragma once
 #include "sign_dev.h"
 
@@ -55,17 +53,25 @@ __host__ __device__ __forceinline__ uint32_t put_varint(uint8_t *p, uint32_t at,
   p[at++] = (uint8_t)v;
   return at;
 }
-// 0x41-byte field body r ‖ s ‖ v (big-endian) at p
-__host__ __device__ __forceinline__ void put_sig65(uint8_t *p, const u256 &r, const u256 &s, uint32_t v) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-      p[4 * (7 - i) + b] = (uint8_t)(r.v[i] >> (8 * (3 - b)));
-      p[32 + 4 * (7 - i) + b] = (uint8_t)(s.v[i] >> (8 * (3 - b)));
-    }
+// The front of every message the signer builds: View ‖ From at p.  Returns the offset behind From, which is where the signature
+// field goes on the wire — envelope_cut(height, round) in closed form (sign_envelope_dev.h).
+__host__ __device__ __forceinline__ uint32_t put_message_front(uint8_t *p, uint64_t height, uint64_t round, const uint32_t addr[5]) {
+  uint32_t at = 0;
+  p[at++] = 0x0a;
+  p[at++] = (uint8_t)message_view_len(height, round);
+  if (height) {
+    p[at++] = 0x08;
+    at = put_varint(p, at, height);
   }
-  p[64] = (uint8_t)v;
+  if (round) {
+    p[at++] = 0x10;
+    at = put_varint(p, at, round);
+  }
+  p[at++] = 0x12;
+  p[at++] = 0x14;
+#pragma unroll
+  for (int i = 0; i < 20; i++) p[at + i] = (uint8_t)(addr[i >> 2] >> (8 * (i & 3)));
+  return at + 20;
 }
 
 struct message_row {
@@ -95,23 +101,7 @@ __host__ __device__ __forceinline__ message_row sign_message_row(const uint32_t 
   // c. everything of PayloadNoSig but the seal
 #pragma unroll
   for (int i = 0; i < SIGN_MESSAGE_BUF_WORDS; i++) buf[i] = 0;
-  uint32_t at = 0;
-  p[at++] = 0x0a;
-  p[at++] = (uint8_t)message_view_len(height, round);
-  if (height) {
-    p[at++] = 0x08;
-    at = put_varint(p, at, height);
-  }
-  if (round) {
-    p[at++] = 0x10;
-    at = put_varint(p, at, round);
-  }
-  p[at++] = 0x12;
-  p[at++] = 0x14;
-#pragma unroll
-  for (int i = 0; i < 20; i++) p[at + i] = (uint8_t)(m.addr[i >> 2] >> (8 * (i & 3)));
-  at += 20;
-  m.cut = at;
+  uint32_t at = m.cut = put_message_front(p, height, round, m.addr);
   p[at++] = 0x20;
   p[at++] = (uint8_t)type;
   p[at++] = commit ? 0x3a : 0x32;
@@ -129,22 +119,16 @@ __host__ __device__ __forceinline__ message_row sign_message_row(const uint32_t 
 #pragma unroll
   for (int i = 0; i < 32; i++) dg[i] = hash32[i];
   if (convert) {
-    uint64_t st[25];
+    uint64_t w[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      uint64_t w = 0;
+      w[j] = 0;
 #pragma unroll
-      for (int t = 0; t < 8; t++) w |= (uint64_t)hash32[8 * j + t] << (8 * t);
-      st[j] = w;
+      for (int t = 0; t < 8; t++) w[j] |= (uint64_t)hash32[8 * j + t] << (8 * t);
     }
+    seal_digest_words(w, suffix_words);
 #pragma unroll
-    for (int j = 0; j < 9; j++) st[4 + j] = suffix_words[j];
-#pragma unroll
-    for (int i = 13; i < 25; i++) st[i] = 0;
-    st[16] ^= 0x8000000000000000ULL;
-    keccak::f1600(st);
-#pragma unroll
-    for (int i = 0; i < 32; i++) dg[i] = (uint8_t)(st[i >> 3] >> (8 * (i & 7)));
+    for (int i = 0; i < 32; i++) dg[i] = (uint8_t)(w[i >> 3] >> (8 * (i & 7)));
   }
 
   // pass 0 signs the seal digest, pass 1 the digest of PayloadNoSig: ONE copy of sign_core in the instruction stream.  A

@@ -999,17 +999,26 @@ class BatchVerifier:
         self._chk(self._L.ibft_seals_run(self._h, _p(self._run_mask), C.byref(t)), "ibft_seals_run")
         return mask_to_bool(self._run_mask, n), t
 
+    def _sign_prepare(self, fn_name, nonce, sk32):
+        """what every sign_* call starts with: the nonce rule is known, the library has fn_name → (keys u8[n,32], n)"""
+        if nonce not in SIGN_NONCES:
+            raise ValueError(f"nonce must be one of {sorted(SIGN_NONCES)}, not {nonce!r}")
+        if not hasattr(self._L, fn_name):
+            raise GpuUnavailable(f"this build of the library has no {fn_name} — rebuild")
+        sk = np.ascontiguousarray(sk32, dtype=np.uint8).reshape(-1, 32)
+        return sk, len(sk)
+
+    @staticmethod
+    def _row_columns(n, *columns):
+        """(value, dtype) pairs → contiguous columns of n entries each; a scalar is one value for every row"""
+        return [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (n,))) for v, dt in columns]
+
     def sign_seals(self, sk32, hash32, nonce="keccak"):
         """ibft_sign_seals (simulators only): (sig65 u8[n,65], signer20 u8[n,20], ok bool[n]); leaves the batch staged.
         nonce: "keccak" (the library's own rule, the default) or "rfc6979" (ibft_sign_seals_ex: RFC 6979 §3.2 with
         bits2octets(h1) = h1 mod n — the seals btcec / bitcoinjs produce for the same key and digest)"""
-        if nonce not in SIGN_NONCES:
-            raise ValueError(f"nonce must be one of {sorted(SIGN_NONCES)}, not {nonce!r}")
-        if nonce != "keccak" and not hasattr(self._L, "ibft_sign_seals_ex"):
-            raise GpuUnavailable("this build of the library has no ibft_sign_seals_ex — rebuild")
-        sk = np.ascontiguousarray(sk32, dtype=np.uint8).reshape(-1, 32)
+        sk, n = self._sign_prepare("ibft_sign_seals" if nonce == "keccak" else "ibft_sign_seals_ex", nonce, sk32)
         hs = np.ascontiguousarray(hash32, dtype=np.uint8).reshape(-1, 32)
-        n = len(sk)
         if len(hs) != n:
             raise ValueError("one hash per key")
         sig = np.zeros((n, 65), dtype=np.uint8)
@@ -1030,18 +1039,11 @@ class BatchVerifier:
         columns or scalars (one value for every row).  A COMMIT's seal signs the hash under the context's seal-digest
         convention.  A refused key (ok False) keeps its row's length and carries a zero From, signature and seal.  Leaves no
         staged batch."""
-        if nonce not in SIGN_NONCES:
-            raise ValueError(f"nonce must be one of {sorted(SIGN_NONCES)}, not {nonce!r}")
-        if not hasattr(self._L, "ibft_sign_messages_wire"):
-            raise GpuUnavailable("this build of the library has no ibft_sign_messages_wire — rebuild")
-        sk = np.ascontiguousarray(sk32, dtype=np.uint8).reshape(-1, 32)
+        sk, n = self._sign_prepare("ibft_sign_messages_wire", nonce, sk32)
         hs = np.ascontiguousarray(hash32, dtype=np.uint8).reshape(-1, 32)
-        n = len(sk)
         if len(hs) != n:
             raise ValueError("one hash per key")
-        ty = np.ascontiguousarray(np.broadcast_to(np.asarray(type, dtype=np.uint8), (n,)))
-        hh = np.ascontiguousarray(np.broadcast_to(np.asarray(height, dtype=np.uint64), (n,)))
-        rr = np.ascontiguousarray(np.broadcast_to(np.asarray(round, dtype=np.uint64), (n,)))
+        ty, hh, rr = self._row_columns(n, (type, np.uint8), (height, np.uint64), (round, np.uint64))
         wire = np.zeros(max(n, 1) * SIGN_MESSAGE_MAX, dtype=np.uint8)
         off = np.zeros(n + 1, dtype=np.uint32)
         frm = np.zeros((n, 20), dtype=np.uint8)
@@ -1058,18 +1060,10 @@ class BatchVerifier:
         is wire[off[i]:off[i+1]], the form verify_certificates_wire takes.  type, height, round, body_at and body_len are columns
         or scalars (one value for every row).  A refused key (ok False) keeps its row's length and carries a zero From and
         signature around its body.  Leaves no staged batch."""
-        if nonce not in SIGN_NONCES:
-            raise ValueError(f"nonce must be one of {sorted(SIGN_NONCES)}, not {nonce!r}")
-        if not hasattr(self._L, "ibft_sign_envelopes_wire"):
-            raise GpuUnavailable("this build of the library has no ibft_sign_envelopes_wire — rebuild")
-        sk = np.ascontiguousarray(sk32, dtype=np.uint8).reshape(-1, 32)
-        n = len(sk)
+        sk, n = self._sign_prepare("ibft_sign_envelopes_wire", nonce, sk32)
         bb = np.frombuffer(bytes(body), dtype=np.uint8) if not isinstance(body, np.ndarray) else np.ascontiguousarray(body, dtype=np.uint8)
-        ty = np.ascontiguousarray(np.broadcast_to(np.asarray(type, dtype=np.uint8), (n,)))
-        hh = np.ascontiguousarray(np.broadcast_to(np.asarray(height, dtype=np.uint64), (n,)))
-        rr = np.ascontiguousarray(np.broadcast_to(np.asarray(round, dtype=np.uint64), (n,)))
-        at = np.ascontiguousarray(np.broadcast_to(np.asarray(body_at, dtype=np.uint32), (n,)))
-        ln = np.ascontiguousarray(np.broadcast_to(np.asarray(body_len, dtype=np.uint32), (n,)))
+        ty, hh, rr, at, ln = self._row_columns(n, (type, np.uint8), (height, np.uint64), (round, np.uint64), (body_at, np.uint32),
+                                               (body_len, np.uint32))
         cap = int(ln.astype(np.uint64).sum()) + ENVELOPE_HEAD_MAX * max(n, 1)
         wire = np.zeros(cap, dtype=np.uint8)
         off = np.zeros(n + 1, dtype=np.uint32)

@@ -27,6 +27,8 @@ def dev():
     L = C.CDLL(build.build_sign_envelope_harness())
     L.dev_envelope_cut.argtypes = [C.c_uint64, C.c_uint64]
     L.dev_envelope_cut.restype = C.c_uint32
+    L.dev_message_front.argtypes = [C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p]
+    L.dev_message_front.restype = C.c_uint32
     L.dev_envelope_head_len.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32]
     L.dev_envelope_head_len.restype = C.c_uint32
     L.dev_envelope_wire_len.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32]
@@ -99,6 +101,26 @@ def test_length_function(dev):
                 assert dev.dev_envelope_wire_len(typ, height, round_, blen) == len(m.encode()), (typ, height, round_, blen)
                 assert dev.dev_envelope_head_len(typ, height, round_, blen) == len(m.encode()) - blen
     assert dev.dev_envelope_head_len(3, SE.M64, SE.M64, 2**32 - 1) == 121       # ENVELOPE_HEAD_MAX
+
+
+def test_message_front_is_the_front_of_both_signers_messages(dev):
+    """put_message_front (View ‖ From, shared by sign_message_row and envelope_head) under the nine views of the message
+    signer's row cases and under height = round = 2^64 − 1: the offset it returns is envelope_cut, and its bytes open the oracle's
+    PREPARE and the oracle's ROUND_CHANGE of that row"""
+    import sign_message_cases as SM
+    sk = SE.good_keys(3)[2]
+    frm = O.address(O.pubkey(sk))
+    views = [(h, r) for _, h, r, _, _ in SM.ROW_CASES] + [(SE.M64, SE.M64)]
+    assert len(views) == 10
+    for height, round_ in views:
+        out = C.create_string_buffer(b"\xee" * 64, 64)
+        cut = dev.dev_message_front(height, round_, frm, out)
+        assert cut == dev.dev_envelope_cut(height, round_), (height, round_)
+        assert out.raw[cut:] == b"\xee" * (64 - cut), "stores behind From"
+        prepare = SM.expected(sk, SM.PREPARE, height, round_, bytes(range(32)), "keccak")[0]
+        round_change = SE.expected(sk, SE.ROUND_CHANGE, height, round_, SE.make_body(SE.ROUND_CHANGE, 40)[0], "keccak")[0]
+        assert out.raw[:cut] == prepare[:cut], (height, round_)
+        assert out.raw[:cut] == round_change[:cut], (height, round_)
 
 
 @pytest.mark.parametrize("form", FORMS, ids=["lane", "wave"])
