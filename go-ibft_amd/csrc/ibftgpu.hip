@@ -311,6 +311,7 @@ struct ibft_ctx {
   // child counts of the level being expanded, proposal digests, hash / self words; the row count of the next level
   // comes back through one mapped word
   DevBuf d_cert_nodes, d_cert_span, d_cert_count, d_cert_prop, d_cert_masks, d_cert_total, d_cert_slot, d_cert_tiles;
+  DevBuf d_cert_rec, d_cert_recbase;  // ibft_judge_certificates_wire: one record per carrier, the roots' first records
   uint32_t *h_cert_total = nullptr, *dh_cert_total = nullptr;
   hipEvent_t ev_cert_fork = nullptr, ev_cert_join = nullptr;  // the side stream (hstream) hashes the deferred rows next to the verdict launch
   bool cert_overlap = true;                                   // IBFT_CERT_OVERLAP=0: everything on one stream, one verdict launch
@@ -1721,7 +1722,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_warm_done, &c->d_seen, &c->d_acc, &c->d_quorum, &c->d_wire_rows, &c->d_seal,
                     &c->d_xbuf[0], &c->d_xbuf[1], &c->d_xres[0], &c->d_xres[1], &c->d_set, &c->d_noseal, &c->d_class,
                     &c->d_cert_nodes, &c->d_cert_span, &c->d_cert_count, &c->d_cert_prop, &c->d_cert_masks, &c->d_cert_total,
-                    &c->d_cert_slot, &c->d_cert_tiles, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
+                    &c->d_cert_slot, &c->d_cert_tiles, &c->d_cert_rec, &c->d_cert_recbase, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
                     &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally,
                     &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
                     &c->d_phash, &c->bs_praw[0], &c->bs_praw[1], &c->bs_proff[0], &c->bs_proff[1], &c->bs_pround[0], &c->bs_pround[1],
@@ -3898,22 +3899,38 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
 // §8f rank 2 from the transport's bytes: the whole certificate tree of a batch of PREPREPARE / ROUND_CHANGE messages —
 // every nested message a row — expanded level by level on the device (kernels.hip.h: cert_*_kernel), then ONE verdict
 // launch over all rows.  The host takes part once per level: it reads the next level's row count to size the launches.
-int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap,
+//
+// judge (ibft_judge_certificates_wire): the same path, then one record per carrier — validPC and the RoundChangeCertificate rules
+// (cert_verdict_dev.h) over the rows where they lie (kernels.hip.h: cert_judge_kernel); every per-row output is optional then.
+static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap,
                                   size_t *out_n_rows, ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows,
                                   uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
-                                  uint64_t *out_self_mask) {
+                                  uint64_t *out_self_mask, bool judge, size_t certs_cap, size_t *out_n_certs,
+                                  ibft_cert_verdict_t *out_cert) {
   static_assert(sizeof(ibft_cert_node_t) == sizeof(wire::node_info), "ABI");
   static_assert(IBFT_CERT_DIGEST_MAX_BYTES == wire::TREE_DIGEST_MAX_BYTES, "ABI");
-  if (!c || !out_n_rows || (n && (!off || !out_sender_mask))) return IBFT_E_INVAL;
+  static_assert(sizeof(ibft_cert_verdict_t) == sizeof(certv::record) && sizeof(ibft_cert_verdict_t) == 128, "ABI");
+  static_assert(offsetof(ibft_cert_verdict_t, pc) == offsetof(certv::record, pc) && offsetof(ibft_cert_verdict_t, height) == offsetof(certv::record, height) &&
+                    offsetof(ibft_cert_verdict_t, from) == offsetof(certv::record, from) &&
+                    offsetof(ibft_cert_verdict_t, pc_hash) == offsetof(certv::record, pc_hash),
+                "ABI");
+  static_assert(IBFT_CERT_NO_RECORD == certv::NO_RECORD && IBFT_CERT_BIT_SENDER == certv::BIT_SENDER && IBFT_CERT_BIT_HASH == certv::BIT_HASH &&
+                    IBFT_CERT_BIT_SELF == certv::BIT_SELF && IBFT_CERT_BIT_HAS_PROPOSAL == certv::BIT_HAS_PROPOSAL &&
+                    IBFT_CERT_BIT_HAS_CERTIFICATE == certv::BIT_HAS_CERTIFICATE,
+                "ABI");
+  if (!c || !out_n_rows || (n && (!off || (!judge && !out_sender_mask)))) return IBFT_E_INVAL;
+  if (judge && (!out_n_certs || (n && !out_cert))) return IBFT_E_INVAL;
   for (size_t i = 0; i < n; i++)
     if (off[i + 1] < off[i]) return IBFT_E_INVAL;
   if (n && off[n] && !wire_bytes) return IBFT_E_INVAL;
   *out_n_rows = 0;
+  if (judge) *out_n_certs = 0;
   ctx_lock lk(c);
   const size_t cap = std::min<size_t>(rows_cap, c->max_rows);
   if (n > cap) return IBFT_E_TOOBIG;
   if (!c->have_valset) return IBFT_E_NOVALSET;
   if (n == 0) return IBFT_OK;
+  if (judge && n > certs_cap) return IBFT_E_TOOBIG;
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   c->wire_valid = false;
@@ -3929,6 +3946,8 @@ int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const 
   if ((rc = ensure(c, c->d_cert_masks, (size_t)mask_words(m) * 16))) return rc;
   if ((rc = ensure(c, c->d_cert_total, 64))) return rc;
   if ((rc = ensure(c, c->d_cert_tiles, (m / 1024 + 2) * 8))) return rc;
+  if (judge && (rc = ensure(c, c->d_cert_rec, m * sizeof(certv::record)))) return rc;
+  if (judge && (rc = ensure(c, c->d_cert_recbase, (m + 1) * 4))) return rc;
   if (!c->h_cert_total) {
     if (hipHostMalloc((void **)&c->h_cert_total, 64) != hipSuccess) return IBFT_E_NOMEM;
     void *d = nullptr;
@@ -3972,7 +3991,7 @@ int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const 
     ibftk::cert_scan_launch(c->stream, cnt <= ibftk::CERT_SCAN_ONE_GROUP_MAX, (const uint32_t *)d_count, d_nodes, lo, cnt, hi, carriers, d_slot,
                             (uint2 *)c->d_cert_tiles.p, d_total, c->dh_cert_total);
     HIPCHK(c, hipGetLastError());
-    if (!c->dh_cert_total) HIPCHK(c, hipMemcpyAsync(c->h_cert_total, d_total, 8, hipMemcpyDeviceToHost, c->stream));
+    if (!c->dh_cert_total) HIPCHK(c, hipMemcpyAsync(c->h_cert_total, d_total, judge && level == 1 ? 12 : 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     levels.push_back({lo, hi});
     const uint32_t total = ((volatile uint32_t *)c->h_cert_total)[0];
@@ -3984,8 +4003,20 @@ int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const 
     HIPCHK(c, hipGetLastError());
     lo = hi;
     hi += total;
+    if (judge && level == 0) {  // level 1 is listed: which of its rows get a record (the next level's synchronisation delivers their number)
+      hipLaunchKernelGGL(ibftk::cert_record_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const wire::node_info *)d_nodes, (uint32_t)n, hi,
+                         (uint32_t *)c->d_cert_recbase.p, d_total, c->dh_cert_total);
+      HIPCHK(c, hipGetLastError());
+    }
   }
   const uint32_t rows = hi;
+  // records: every level-0 row, every level-1 row of a RoundChangeCertificate
+  const uint32_t records = judge ? (levels.size() > 1 ? ((volatile uint32_t *)c->h_cert_total)[2] : (uint32_t)n) : 0u;
+  if (judge && (records < n || records > rows)) {
+    c->last_error = "certificate records: a count outside [n, rows]";
+    return IBFT_E_HIP;
+  }
+  if (judge && records > certs_cap) return IBFT_E_TOOBIG;
   for (size_t l = levels.size(); l-- > 1;) {
     const uint32_t cnt = levels[l].second - levels[l].first;
     hipLaunchKernelGGL(ibftk::cert_propagate_kernel, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, (const wire::node_info *)d_nodes, d_rows,
@@ -4040,6 +4071,49 @@ int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const 
   hipLaunchKernelGGL(ibftk::cert_compare_kernel, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const wire::node_info *)d_nodes,
                      (const wire::row_info *)d_rows, (const uint8_t *)d_prop, rows, d_hash_mask, d_self_mask, (uint8_t *)c->d_class.p);
   HIPCHK(c, hipGetLastError());
+  if (judge) {
+    ibftk::cert_judge_args ja{};
+    ja.nodes = d_nodes;
+    ja.rows = d_rows;
+    ja.cls = (const uint8_t *)c->d_class.p;
+    ja.sender_mask = (const uint64_t *)c->d_mask.p;
+    ja.hash_mask = d_hash_mask;
+    ja.self_mask = d_self_mask;
+    ja.vtab = (const uint32_t *)c->d_vtab.p;
+    ja.vpower32 = (const uint32_t *)c->d_vpower.p;
+    ja.quorum = (const uint64_t *)c->d_quorum.p;
+    ja.rec_base = levels.size() > 1 ? (const uint32_t *)c->d_cert_recbase.p : nullptr;
+    ja.vslot_mask = c->vslot_mask;
+    ja.n_validators = c->n_validators;
+    ja.n_roots = (uint32_t)n;
+    ja.n_rows = rows;
+    ja.n_records = records;
+    const size_t lds = (size_t)((c->n_validators + 31) / 32) * 4;
+    ja.lds_bitmap = lds <= ibftk::CERT_JUDGE_LDS_MAX ? 1u : 0u;  // beyond: one workgroup walks every record over the HBM bitmap
+    ja.seen = (uint32_t *)c->d_seen.p;
+    ja.out = (certv::record *)c->d_cert_rec.p;
+    const dim3 grid(ja.lds_bitmap ? std::min(records, ibftk::CERT_JUDGE_MAX_GRID) : 1u);
+    const size_t dyn = ja.lds_bitmap ? lds : 0;
+    // (the verdict launches of this path are not timed: with kernel timing on, ibft_last_kernel_ms after this call is the two
+    // record kernels' time)
+    hipEvent_t j0 = nullptr, j1 = nullptr;
+    if (c->time_every) {
+      if ((rc = next_events(c, &j0, &j1))) return rc;
+      HIPCHK(c, hipEventRecord(j0, c->stream));
+    }
+    if (c->power_words == 1)
+      hipLaunchKernelGGL(ibftk::cert_judge_kernel<1>, grid, dim3(64), dyn, c->stream, ja);
+    else
+      hipLaunchKernelGGL(ibftk::cert_judge_kernel<4>, grid, dim3(64), dyn, c->stream, ja);
+    HIPCHK(c, hipGetLastError());
+    if (ja.rec_base) {
+      hipLaunchKernelGGL(ibftk::cert_judge_children_kernel, dim3(std::min((uint32_t)n, ibftk::CERT_JUDGE_MAX_GRID)), dim3(64), 0, c->stream, ja.out,
+                         (uint32_t)n);
+      HIPCHK(c, hipGetLastError());
+    }
+    if (j1) HIPCHK(c, hipEventRecord(j1, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_cert, ja.out, (size_t)records * sizeof(certv::record), hipMemcpyDeviceToHost, c->stream));
+  }
   const size_t mw = (size_t)mask_words(rows);
   if (out_nodes) HIPCHK(c, hipMemcpyAsync(out_nodes, d_nodes, (size_t)rows * sizeof(wire::node_info), hipMemcpyDeviceToHost, c->stream));
   if (out_rows) HIPCHK(c, hipMemcpyAsync(out_rows, d_rows, (size_t)rows * sizeof(wire::row_info), hipMemcpyDeviceToHost, c->stream));
@@ -4049,7 +4123,22 @@ int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const 
   // no tally: the rows of a tree belong to many certificates; their quorum rules are the caller's (From / type / view columns)
   if ((rc = fetch_results(c, rows, out_sender_mask, nullptr, false))) return rc;
   *out_n_rows = rows;
+  if (judge) *out_n_certs = records;
   return IBFT_OK;
+}
+int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap,
+                                  size_t *out_n_rows, ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows,
+                                  uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
+                                  uint64_t *out_self_mask) {
+  return certificates_wire_impl(c, wire_bytes, off, n, rows_cap, out_n_rows, out_nodes, out_rows, out_class, out_sender_mask, out_hash_mask,
+                                out_self_mask, false, 0, nullptr, nullptr);
+}
+int ibft_judge_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap, size_t certs_cap,
+                                 size_t *out_n_rows, size_t *out_n_certs, ibft_cert_verdict_t *out_cert, ibft_cert_node_t *out_nodes,
+                                 ibft_wire_row_t *out_rows, uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
+                                 uint64_t *out_self_mask) {
+  return certificates_wire_impl(c, wire_bytes, off, n, rows_cap, out_n_rows, out_nodes, out_rows, out_class, out_sender_mask, out_hash_mask,
+                                out_self_mask, true, certs_cap, out_n_certs, out_cert);
 }
 
 int ibft_wire_stage_seals(ibft_ctx *c) {

@@ -48,6 +48,7 @@
 #include "wave_fe_dev.h"
 #include "wire_dev.h"
 #include "cert_wave_dev.h"
+#include "cert_verdict_dev.h"
 
 namespace ibftk {
 
@@ -2176,6 +2177,190 @@ __global__ void __launch_bounds__(THREADS)
     if (a.host_mask) a.host_mask[i] = w;
   }
   if (tid == 0) __hip_atomic_store(a.acc + TALLY_MAX_PIECES + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- certificates: one record per carrier (ibft_judge_certificates_wire; the rules: cert_verdict_dev.h) ---------------------
+// Records exist for every level-0 row and for every level-1 row of role ROLE_RCC_MESSAGE (the ROUND_CHANGE messages inside a
+// root PREPREPARE's RoundChangeCertificate), in ascending row order: record i < n_roots is row i; the records of root i's
+// certificate are [rec_base[i], rec_base[i + 1]) — its children are a contiguous row range and share one role.
+__device__ __forceinline__ uint32_t cert_rcc_children(const wire::node_info *__restrict__ nodes, uint32_t root, uint32_t rows_bound) {
+  const uint32_t lo = nodes[root].first_child, n = nodes[root].n_children;
+  if (n == 0 || (uint64_t)lo + n > rows_bound) return 0;
+  return nodes[lo].role == wire::ROLE_RCC_MESSAGE ? n : 0;
+}
+// rec_base[0 .. n_roots]: n_roots + the exclusive prefix count of the roots' certificate children; the record total goes to
+// total_dev[2] (and total_host[2]) next to the level totals of cert_scan_kernel.  One workgroup, as cert_scan_kernel: it runs once
+// per call, after level 1 has been listed (cert_walk_kernel<true> over level 0 has written the children's roles).
+__global__ void __launch_bounds__(1024) cert_record_scan_kernel(const wire::node_info *__restrict__ nodes, uint32_t n_roots, uint32_t rows_bound,
+                                                                uint32_t *__restrict__ rec_base, uint32_t *__restrict__ total_dev,
+                                                                uint32_t *__restrict__ total_host) {
+  __shared__ uint32_t part[1024];
+  const uint32_t t = threadIdx.x, per = (n_roots + 1023u) / 1024u;
+  const uint32_t b = t * per < n_roots ? t * per : n_roots, e = b + per < n_roots ? b + per : n_roots;
+  uint32_t sum = 0;
+  for (uint32_t i = b; i < e; i++) sum += cert_rcc_children(nodes, i, rows_bound);
+  part[t] = sum;
+  __syncthreads();
+  for (uint32_t o = 1; o < 1024u; o <<= 1) {
+    const uint32_t v = t >= o ? part[t - o] : 0u;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = n_roots + part[t] - sum;
+  for (uint32_t i = b; i < e; i++) {
+    rec_base[i] = run;
+    run += cert_rcc_children(nodes, i, rows_bound);
+  }
+  if (t == 1023u) {
+    const uint32_t total = n_roots + part[1023];
+    rec_base[n_roots] = total;
+    total_dev[2] = total;
+    if (total_host) total_host[2] = total;
+  }
+}
+
+constexpr uint32_t CERT_JUDGE_LDS_MAX = 49152;     // bytes of LDS the distinct-validator bitmap may take (393 216 validators)
+constexpr uint32_t CERT_JUDGE_MAX_GRID = 1u << 16;  // workgroups of one launch (each takes records r, r + grid, …)
+struct cert_judge_args {
+  const wire::node_info *nodes;
+  const wire::row_info *rows;
+  const uint8_t *cls;
+  const uint64_t *sender_mask, *hash_mask, *self_mask;  // verdict words over the tree's rows
+  const uint32_t *vtab;                                 // the validator table (valset_lookup)
+  const uint32_t *vpower32;                             // n_validators × 2·PW pieces
+  const uint64_t *quorum;                               // TALLY_SUM_WORDS
+  const uint32_t *rec_base;                             // n_roots + 1 (cert_record_scan_kernel); null: no level-1 records
+  uint32_t vslot_mask, n_validators;
+  uint32_t n_roots, n_rows, n_records;
+  uint32_t lds_bitmap;  // ⌈n_validators/32⌉ words of dynamic LDS; 0: `seen` in HBM, and the grid is one workgroup
+  uint32_t *seen;       // as many words, zero between launches (HBM form only)
+  certv::record *out;
+};
+__device__ __forceinline__ bool cert_mask_bit(const uint64_t *__restrict__ mask, uint32_t row) { return (mask[row >> 6] >> (row & 63u)) & 1ull; }
+__device__ __forceinline__ int cert_row_validator(const cert_judge_args &a, const wire::row_info &w) {
+  uint32_t addr[5];
+#pragma unroll
+  for (int i = 0; i < 5; i++)
+    addr[i] = (uint32_t)w.from[4 * i] | ((uint32_t)w.from[4 * i + 1] << 8) | ((uint32_t)w.from[4 * i + 2] << 16) | ((uint32_t)w.from[4 * i + 3] << 24);
+  return valset_lookup(a.vtab, a.vslot_mask, addr);
+}
+// One wavefront per record, the lanes stride over the carrier's children: the flag words of certv::pc_child / rcc_child are
+// OR-reduced, the children whose sender bit is set are counted once per validator index through a bitmap (LDS; in HBM when the
+// set's bitmap does not fit, one workgroup then walks all records and clears what it set, as block_tally_kernel), their power
+// is summed in 2·PW 32-bit pieces and compared with the quorum, the fold gives the verdict.  A root PREPREPARE's rcc still
+// lacks its children's pc: cert_judge_children_kernel.
+template <int PW>
+__global__ void __launch_bounds__(64) cert_judge_kernel(cert_judge_args a) {
+  constexpr int NP = 2 * PW;
+  extern __shared__ uint32_t jseen[];
+  const uint32_t lane = threadIdx.x;
+  uint32_t *bm = a.lds_bitmap ? jseen : a.seen;
+  const uint32_t bm_words = (a.n_validators + 31u) / 32u;
+  for (uint32_t rec = blockIdx.x; rec < a.n_records; rec += gridDim.x) {
+    uint32_t row = rec, parent = wire::NO_PARENT;
+    if (rec >= a.n_roots) {  // the LAST root whose first record is ≤ rec (roots without such children repeat a base)
+      uint32_t lo = 0, hi = a.n_roots - 1;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1) >> 1;
+        if (a.rec_base[mid] <= rec) lo = mid;
+        else hi = mid - 1;
+      }
+      parent = lo;
+      row = a.nodes[lo].first_child + (rec - a.rec_base[lo]);
+    }
+    const bool root = parent == wire::NO_PARENT;
+    const wire::node_info nd = a.nodes[row];
+    const wire::row_info &ri = a.rows[row];
+    // a root ROUND_CHANGE: its own view, with proposalMatchesCertificate; inside a root PREPREPARE's certificate: the PREPREPARE's view
+    const uint64_t height = root ? ri.height : a.rows[parent].height, limit = root ? ri.round : a.rows[parent].round;
+    int pc = certv::pc_head(a.nodes, a.rows, a.cls, a.n_rows, row, root);
+    int rcc = root ? certv::rcc_head(a.nodes, a.rows, a.cls, a.n_rows, row) : certv::UNDECIDED;
+    const bool walk_pc = pc == certv::GO, walk_rcc = rcc == certv::GO;  // never both: one is a ROUND_CHANGE, the other a PREPREPARE
+    uint32_t rcc_rows = 0;
+    if (walk_pc || walk_rcc) {  // wave-uniform
+      const uint32_t lo = nd.first_child, n = nd.n_children;
+      if (a.lds_bitmap) {
+        for (uint32_t i = lane; i < bm_words; i += 64u) jseen[i] = 0;
+        __syncthreads();
+      }
+      certv::pc_params p{height, limit, 0, nullptr, root};
+      if (walk_pc) {
+        p.ref_round = a.rows[lo].round;
+        p.ref_hash = a.rows[lo].proposal_hash;
+      }
+      uint32_t flags = 0;
+      uint64_t counts = 0;  // distinct validators | rows below << 32
+      uint64_t pw[NP];
+#pragma unroll
+      for (int k = 0; k < NP; k++) pw[k] = 0;
+      for (uint32_t c = lo + lane; c < lo + n; c += 64u) {
+        const wire::row_info &w = a.rows[c];
+        const wire::node_info &cn = a.nodes[c];
+        const bool sb = cert_mask_bit(a.sender_mask, c);
+        flags |= walk_pc ? certv::pc_child(w, cn, a.cls[c], sb, cert_mask_bit(a.hash_mask, c), c == lo, p)
+                         : certv::rcc_child(w, cn, a.cls[c], sb, ri.height, ri.round);
+        counts += (uint64_t)(1u + cn.n_children) << 32;
+        if (!sb) continue;
+        const int vi = cert_row_validator(a, w);
+        if (vi < 0 || (uint32_t)vi >= a.n_validators) continue;
+        const uint32_t m = 1u << (vi & 31);
+        if (atomicOr(&bm[vi >> 5], m) & m) continue;  // the same validator twice
+        counts += 1;
+#pragma unroll
+        for (int k = 0; k < NP; k++) pw[k] += a.vpower32[(size_t)vi * NP + k];
+      }
+      __syncthreads();
+      if (!a.lds_bitmap) {  // the HBM bitmap is left zero for the next record: clear exactly the words this one set
+        for (uint32_t c = lo + lane; c < lo + n; c += 64u) {
+          if (!cert_mask_bit(a.sender_mask, c)) continue;
+          const int vi = cert_row_validator(a, a.rows[c]);
+          if (vi >= 0 && (uint32_t)vi < a.n_validators) bm[vi >> 5] = 0u;
+        }
+        __syncthreads();
+      }
+      for (int o = 32; o; o >>= 1) flags |= (uint32_t)__shfl_xor((int)flags, o, 64);
+      counts = wave_sum_u64(counts);
+      uint64_t piece[TALLY_MAX_PIECES];
+#pragma unroll
+      for (int k = 0; k < TALLY_MAX_PIECES; k++) piece[k] = 0;
+#pragma unroll
+      for (int k = 0; k < NP; k++) piece[k] = wave_sum_u64(pw[k]);
+      uint64_t wd[TALLY_SUM_WORDS];
+      pieces_to_words(piece, NP, wd);
+      const bool all_distinct = (uint32_t)counts == n, power_ok = words_ge(wd, a.quorum);
+      if (walk_pc) pc = certv::pc_fold(flags, all_distinct, power_ok);
+      else {
+        rcc = certv::rcc_fold(flags, n, all_distinct, power_ok);
+        if (rcc != certv::UNDECIDED) rcc_rows = (uint32_t)(counts >> 32);
+      }
+    }
+    if (lane == 0) {
+      certv::record r;
+      certv::record_head(r, row, nd, ri, a.cls[row], cert_mask_bit(a.sender_mask, row), cert_mask_bit(a.hash_mask, row),
+                         cert_mask_bit(a.self_mask, row));
+      r.pc = (int8_t)pc;
+      r.rcc = (int8_t)rcc;
+      r.rcc_rows = rcc_rows;
+      if (root && a.rec_base && a.rec_base[row + 1] != a.rec_base[row]) r.first_child_cert = a.rec_base[row];
+      if (pc == certv::VALID) certv::record_pc_proposal(r, a.rows[nd.first_child]);
+      a.out[rec] = r;
+    }
+  }
+}
+// A root PREPREPARE whose certificate holds (rcc == 1): the prepared certificate of every ROUND_CHANGE message in it must be
+// decided — one with pc == −1 leaves rcc undecided (proposalVerdictFromRows returns "not decided" there, after all its other
+// clauses).  A wavefront per root; the children's records were written by the launch before this one.
+__global__ void __launch_bounds__(64) cert_judge_children_kernel(certv::record *__restrict__ out, uint32_t n_roots) {
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t root = blockIdx.x; root < n_roots; root += gridDim.x) {
+    const certv::record &r = out[root];
+    if (r.rcc != certv::VALID || r.first_child_cert == certv::NO_RECORD) continue;  // wave-uniform
+    bool undecided = false;
+    for (uint32_t k = lane; k < r.n_children; k += 64u) undecided = undecided || out[r.first_child_cert + k].pc == certv::UNDECIDED;
+    const int rcc = certv::rcc_with_children(certv::VALID, __any(undecided));
+    if (lane == 0 && rcc != certv::VALID) out[root].rcc = (int8_t)rcc;
+  }
 }
 
 // ---- multi-GPU: the one exchange step -------------------------------------------------

@@ -51,11 +51,11 @@ EXPORTS = [
     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
-    "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire",
+    "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
-# (ibft_set_validator_sets …, the two _sets block calls), ibft_sign_seals_ex and ibft_sign_messages_wire came without a version step: an
+# (ibft_set_validator_sets …, the two _sets block calls), ibft_sign_seals_ex, ibft_sign_messages_wire and ibft_judge_certificates_wire came without a version step: an
 # older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
 EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
 OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
@@ -65,7 +65,7 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
                     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
                     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
-                    "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire"}
+                    "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
 ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
@@ -86,6 +86,14 @@ CERT_NODE = np.dtype([("off", "<u4"), ("len", "<u4"), ("parent", "<u4"), ("ordin
 assert CERT_NODE.itemsize == 56
 CERT_CLASS_NEEDS_HOST, CERT_CLASS_DIGEST_BY_HOST, CERT_CLASS_PROPOSAL_BY_HOST = 1, 2, 4
 CERT_NO_PARENT = 0xFFFFFFFF
+# ibft_cert_verdict_t (include/ibftgpu.h): one record per carrier of ibft_judge_certificates_wire
+CERT_VERDICT = np.dtype([("row", "<u4"), ("first_child", "<u4"), ("n_children", "<u4"), ("first_child_cert", "<u4"), ("rcc_rows", "<u4"),
+                         ("pc", "i1"), ("rcc", "i1"), ("cls", "u1"), ("bits", "u1"), ("type", "u1"), ("role", "u1"), ("level", "u1"),
+                         ("from_len", "u1"), ("reserved", "<u4"), ("height", "<u8"), ("round", "<u8"), ("pc_round", "<u8"),
+                         ("from", "u1", 20), ("pc_from", "u1", 20), ("pc_hash", "u1", 32)])
+assert CERT_VERDICT.itemsize == 128
+CERT_NO_RECORD = 0xFFFFFFFF
+CERT_BIT_SENDER, CERT_BIT_HASH, CERT_BIT_SELF, CERT_BIT_HAS_PROPOSAL, CERT_BIT_HAS_CERTIFICATE = 1, 2, 4, 8, 16
 
 
 class GpuUnavailable(RuntimeError):
@@ -249,6 +257,9 @@ def load_library() -> C.CDLL:
     L.ibft_verify_senders_wire.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.POINTER(Tally)]
     L.ibft_wire_stage_seals.argtypes = [vp]
     L.ibft_verify_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_judge_certificates_wire"):
+        L.ibft_judge_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                                   vp, vp, vp, vp, vp, vp, vp]
     L.ibft_set_validators_u256.argtypes = [vp, C.c_uint64, vp, vp, C.c_size_t]
     L.ibft_last_tally_wide.argtypes = [vp, C.POINTER(TallyWide)]
     L.ibft_shard_range.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -282,6 +293,34 @@ def load_library() -> C.CDLL:
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _judge_certificates_wire(L, handle, chk, wire, off, rows_cap: int, certs_cap: int | None, per_row: bool):
+    """ibft_judge_certificates_wire on one context → (certs[CERT_VERDICT], n_rows, per-row outputs or None); the per-row outputs
+    are verify_certificates_wire's tuple without its first element"""
+    if not hasattr(L, "ibft_judge_certificates_wire"):
+        raise GpuUnavailable("this build of libibftgpu.so has no ibft_judge_certificates_wire — rebuild")
+    wb = _bytes_col(wire)
+    off = np.ascontiguousarray(off, dtype=np.uint32)
+    n = len(off) - 1
+    cap = int(rows_cap)
+    ccap = cap if certs_cap is None else int(certs_cap)
+    certs = np.zeros(max(ccap, 1), dtype=CERT_VERDICT)
+    nodes = rows = cls = ms = mh = mself = None
+    if per_row:
+        words = (cap + 63) // 64 or 1
+        nodes = np.zeros(max(cap, 1), dtype=CERT_NODE)
+        rows = np.zeros(max(cap, 1), dtype=WIRE_ROW)
+        cls = np.zeros(max(cap, 1), dtype=np.uint8)
+        ms, mh, mself = (np.zeros(words, dtype=np.uint64) for _ in range(3))
+    n_rows, n_certs = C.c_size_t(0), C.c_size_t(0)
+    chk(L.ibft_judge_certificates_wire(handle, _p(wb), _p(off), n, cap, ccap, C.byref(n_rows), C.byref(n_certs), _p(certs), _p(nodes),
+                                       _p(rows), _p(cls), _p(ms), _p(mh), _p(mself)), "ibft_judge_certificates_wire")
+    k = int(n_rows.value)
+    out = None
+    if per_row:
+        out = (nodes[:k], rows[:k], cls[:k], mask_to_bool(ms, k), mask_to_bool(mh, k), mask_to_bool(mself, k))
+    return certs[:int(n_certs.value)], k, out
 
 
 class _PinnedOwner:
@@ -900,6 +939,16 @@ class BatchVerifier:
         return (k, nodes[:k], rows[:k] if want_rows else None, cls[:k], mask_to_bool(ms, k), mask_to_bool(mh, k),
                 mask_to_bool(mself, k))
 
+    def judge_certificates_wire(self, wire, off, rows_cap: int | None = None, certs_cap: int | None = None, per_row: bool = False):
+        """the certificate trees of a batch of raw messages judged PER CARRIER on the device (ibft_judge_certificates_wire):
+        → (certs[CERT_VERDICT], n_rows, per_row outputs) — one record per level-0 row and per ROUND_CHANGE message of a root
+        PREPREPARE's certificate, with validPC (pc) and the RoundChangeCertificate rules (rcc) decided up to IsProposer; see
+        include/ibftgpu.h for how a caller finishes.  per_row: also (nodes, rows, class, sender, hash, self) exactly as
+        verify_certificates_wire returns them, else None and nothing per row is copied out.  Raises RuntimeError
+        (IBFT_E_TOOBIG) when the tree exceeds rows_cap or the records exceed certs_cap (default: rows_cap)."""
+        return _judge_certificates_wire(self._L, self._h, self._chk, wire, off, int(rows_cap if rows_cap is not None else self.max_rows),
+                                        certs_cap, per_row)
+
     def wire_stage_seals(self):
         """the COMMIT seals of the last is_valid_validator_wire batch become the resident seal batch"""
         self._chk(self._L.ibft_wire_stage_seals(self._h), "ibft_wire_stage_seals")
@@ -1251,6 +1300,11 @@ class DeviceGroup:
         k = int(n_rows.value)
         return (k, nodes[:k], rows[:k] if want_rows else None, cls[:k], mask_to_bool(ms, k), mask_to_bool(mh, k),
                 mask_to_bool(mself, k))
+
+    def judge_certificates_wire(self, wire, off, rows_cap: int = 65536, certs_cap: int | None = None, per_row: bool = False):
+        """BatchVerifier.judge_certificates_wire on the group's FIRST context (there is no sharded form of this call: a
+        carrier's children must lie on the device that judges it); same results"""
+        return _judge_certificates_wire(self._L, self._L.ibft_group_ctx(self._g, 0), self._chk, wire, off, int(rows_cap), certs_cap, per_row)
 
     def verify_messages(self, payload: bytes, off, msg_sig65, from20, hash32, hash_len, seal65=None, sender_pre=None,
                         valid_pre=None, raw: bytes | None = None, round_: int = 0, digest32: bytes | None = None,

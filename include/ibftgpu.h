@@ -44,6 +44,10 @@
  *                        <- every IsValidValidator / IsValidProposalHash that validateProposal, validPC and
  *                           handleRoundChangeMessage ask about the messages NESTED in PREPREPARE / ROUND_CHANGE
  *                           messages (core/ibft.go:470-551, 683-788), from the transport's bytes
+ *   ibft_judge_certificates_wire
+ *                        <- the same, and validPC / AreValidPCMessages / HasUniqueSenders (core/ibft.go:1162-1231,
+ *                           messages/helpers.go:148-213) and the RoundChangeCertificate half of validateProposal
+ *                           (core/ibft.go:697-778) themselves, per certificate, up to IsProposer: one record per carrier
  *   ibft_comm_*, ibft_group_*  validator shards over several MI355X, one RCCL all-reduce inside the library
  *   ibft_sign_seals, ibft_sign_seals_ex
  *                        <- n × Backend.BuildCommitMessage's seal (core/backend.go:12-34), simulators only (_ex: with
@@ -798,6 +802,75 @@ int ibft_verify_certificates_wire(ibft_ctx *ctx, const uint8_t *wire, const uint
                                   size_t *out_n_rows, ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows,
                                   uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
                                   uint64_t *out_self_mask);
+
+/* ---- certificates judged per carrier -----------------------------------------------------------------------------
+ * The same call, and on top of it what the reference asks PER CERTIFICATE, computed on the device: one fixed-size record
+ * for every message that can carry a certificate the caller has to decide —
+ *
+ *   every level-0 row (the call's n messages), and
+ *   every level-1 row of role IBFT_CERT_ROLE_RCC_MESSAGE (the ROUND_CHANGE messages in a root PREPREPARE's
+ *   RoundChangeCertificate; deeper certificates — a PreparedCertificate's proposal message carrying an RCC of its own —
+ *   get no record),
+ *
+ * in ascending row order (out_cert[i].row == i for i < n).  *out_n_certs = their number; more than certs_cap:
+ * IBFT_E_TOOBIG.  A record holds
+ *
+ *   pc    validPC (core/ibft.go:1162-1231) with AreValidPCMessages / HasUniqueSenders (messages/helpers.go:148-213) for the
+ *         PreparedCertificate of a ROUND_CHANGE row, everything but the proposer rule: −1 undecided here (an irregular shape —
+ *         a nested message that is not judged, has no view, a From longer than 20 bytes, a payload that disagrees with its
+ *         type, nested messages of its own …: decide it by the walk over the decoded message), 0 invalid, 1 valid up to
+ *         IsProposer, 2 the message carries no certificate.  A root ROUND_CHANGE is judged against its own view (round limit =
+ *         its round) and with proposalMatchesCertificate (:516-551: every hash bit of the certificate); a ROUND_CHANGE inside a
+ *         root PREPREPARE's certificate against the PREPREPARE's height and round, without (validateProposal, :746-778).
+ *         When pc == 1: pc_round, pc_from, pc_hash = view round, From and carried hash of the certificate's proposal message.
+ *   rcc   a root PREPREPARE's RoundChangeCertificate (validateProposal, :697-778): unique senders, their quorum, every message
+ *         a validly signed ROUND_CHANGE of the PREPREPARE's view, every prepared certificate below decided: −1 / 0 / 1 / 2 as
+ *         above (−1 too when a child's pc is −1); rcc_rows = the rows of the certificate's subtree down to level 2 (meaningful
+ *         for rcc ≥ 0).  −1 for every other record.
+ *   first_child_cert  for a root PREPREPARE with a RoundChangeCertificate: out_cert[first_child_cert + k] is the record of its
+ *         k-th nested message (k < n_children); IBFT_CERT_NO_RECORD otherwise.
+ *   row, first_child, n_children, cls, the row's own type / role / level / height / round / from, and in bits its own sender,
+ *   hash and self bit with IBFT_CERT_HAS_PROPOSAL / _CERTIFICATE of its node.
+ *
+ * How a caller finishes:
+ *   validPC(latestPC, limit, height)   pc == 2: true.  pc == 1: IsProposer(pc_from, height, pc_round).  0: false.
+ *   handleRoundChangeMessage's closure (:478-489)   the same, and for pc == 2: the message must carry no proposal either
+ *         (bits & IBFT_CERT_BIT_HAS_PROPOSAL → false).
+ *   validateProposal's certificate half   rcc == 1: walk the records of the certificate; among those whose validPC holds the
+ *         highest pc_round wins, the LAST one among equals: (pc_round, pc_hash) is the prepared proposal's — O(Q), no row read.
+ * THE CONTRACT this rests on: IsProposer accepts at most one address per (height, round).  validPC also demands that no PREPARE
+ * of the certificate comes from the proposer; with unique senders (part of pc == 1) and a proposal message from THE proposer no
+ * other message can.  A Backend whose IsProposer may accept several addresses of one view keeps the per-row route
+ * (ibft_verify_certificates_wire and its own walk).
+ *
+ * Every per-row output — out_nodes, out_rows, out_class and all three masks, out_sender_mask included — may be NULL, and then
+ * nothing per row crosses the bus; what is requested equals ibft_verify_certificates_wire's output bit for bit.  Errors: those
+ * of that call, in its order; IBFT_E_INVAL for a NULL out_n_certs or a NULL out_cert with n > 0.  A refused call writes
+ * nothing to any out buffer.                                                                                         */
+#define IBFT_CERT_NO_RECORD 0xFFFFFFFFu
+#define IBFT_CERT_BIT_SENDER 0x01u          /* bits: the row's own IsValidValidator bit                  */
+#define IBFT_CERT_BIT_HASH 0x02u            /*       its hash bit                                        */
+#define IBFT_CERT_BIT_SELF 0x04u            /*       its self bit                                        */
+#define IBFT_CERT_BIT_HAS_PROPOSAL 0x08u    /*       IBFT_CERT_HAS_PROPOSAL of its node                  */
+#define IBFT_CERT_BIT_HAS_CERTIFICATE 0x10u /*       IBFT_CERT_HAS_CERTIFICATE of its node               */
+typedef struct {
+  uint32_t row, first_child, n_children;
+  uint32_t first_child_cert;
+  uint32_t rcc_rows;
+  int8_t pc, rcc;
+  uint8_t cls, bits;
+  uint8_t type, role, level, from_len;
+  uint32_t reserved;
+  uint64_t height, round;
+  uint64_t pc_round;
+  uint8_t from[20];
+  uint8_t pc_from[20];
+  uint8_t pc_hash[32];
+} ibft_cert_verdict_t; /* 128 bytes */
+int ibft_judge_certificates_wire(ibft_ctx *ctx, const uint8_t *wire, const uint32_t *off, size_t n, size_t rows_cap,
+                                 size_t certs_cap, size_t *out_n_rows, size_t *out_n_certs, ibft_cert_verdict_t *out_cert,
+                                 ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows, uint8_t *out_class,
+                                 uint64_t *out_sender_mask, uint64_t *out_hash_mask, uint64_t *out_self_mask);
 
 /* ---- f4: the signing side, for SIMULATORS ----------------------------------
  * Replaces, for a process that plays n validators at once, the n calls of Backend.BuildCommitMessage

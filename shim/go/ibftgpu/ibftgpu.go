@@ -848,6 +848,54 @@ func (c *Ctx) VerifyCertificatesWire(wire []byte, off []uint32, rowsCap int) (no
 	return nodes[:int(rows)], class[:int(rows)], sender, hash, self, c.check(rc)
 }
 
+// CertVerdict mirrors ibft_cert_verdict_t: what the reference asks about ONE certificate carrier, decided on the device
+// (JudgeCertificatesWire).  PC / RCC: -1 undecided here (decide by the walk over the decoded message), 0 invalid, 1 valid,
+// 2 the message carries no certificate.
+type CertVerdict struct {
+	Row, FirstChild, NChildren uint32 // the carrier's row and its nested messages' rows
+	FirstChildCert             uint32 // a root PREPREPARE: index of the record of its first nested ROUND_CHANGE (CertNoRecord: none)
+	RCCRows                    uint32 // rows of the certificate's subtree (RCC >= 0)
+	PC, RCC                    int8
+	Class, Bits                uint8 // the row's routing byte; CertBit*
+	Type, Role, Level, FromLen uint8
+	Reserved                   uint32
+	Height, Round              uint64
+	PCRound                    uint64 // PC == 1: view round, From and carried hash of the certificate's proposal message
+	From                       [20]byte
+	PCFrom                     [20]byte
+	PCHash                     [32]byte
+}
+
+// The struct is exactly as large as the C one: unsafe.Sizeof is a constant, and a uintptr constant below zero does not compile.
+const (
+	_ = unsafe.Sizeof(CertVerdict{}) - 128
+	_ = 128 - unsafe.Sizeof(CertVerdict{})
+)
+
+const (
+	CertNoRecord          = uint32(C.IBFT_CERT_NO_RECORD)
+	CertBitSender         = uint8(C.IBFT_CERT_BIT_SENDER)
+	CertBitHash           = uint8(C.IBFT_CERT_BIT_HASH)
+	CertBitSelf           = uint8(C.IBFT_CERT_BIT_SELF)
+	CertBitHasProposal    = uint8(C.IBFT_CERT_BIT_HAS_PROPOSAL)
+	CertBitHasCertificate = uint8(C.IBFT_CERT_BIT_HAS_CERTIFICATE)
+)
+
+// JudgeCertificatesWire = VerifyCertificatesWire's tree, and on top of it validPC and the RoundChangeCertificate rules of
+// validateProposal (core/ibft.go:1162-1231, 697-778) decided PER CARRIER on the device (ibft_judge_certificates_wire): one
+// record for each of the call's messages and for each ROUND_CHANGE message inside a root PREPREPARE's certificate, in row
+// order.  No per-row output crosses the bus.  The caller finishes with IsProposer(PCFrom, height, PCRound) where PC == 1 —
+// which rests on IsProposer accepting at most one address per view (include/ibftgpu.h); a Backend without that property
+// keeps VerifyCertificatesWire.
+func (c *Ctx) JudgeCertificatesWire(wire []byte, off []uint32, rowsCap, certsCap int) (certs []CertVerdict, rows int, err error) {
+	n := len(off) - 1
+	certs = make([]CertVerdict, certsCap+1)
+	var nRows, nCerts C.size_t
+	rc := C.ibft_judge_certificates_wire(c.h, ptr8(wire), (*C.uint32_t)(unsafe.Pointer(&off[0])), C.size_t(n), C.size_t(rowsCap),
+		C.size_t(certsCap), &nRows, &nCerts, (*C.ibft_cert_verdict_t)(unsafe.Pointer(&certs[0])), nil, nil, nil, nil, nil, nil)
+	return certs[:int(nCerts)], int(nRows), c.check(rc)
+}
+
 // PinnedBytes returns n bytes of page-locked memory (ibft_pinned_alloc) as a Go slice: column buffers the
 // flatten step writes into once and reuses every round.  When every column of a call lies in such buffers the
 // library reads them with one gather launch instead of one copy command per column.  C memory: invisible to
