@@ -315,6 +315,12 @@ struct ibft_ctx {
   uint32_t *h_cert_total = nullptr, *dh_cert_total = nullptr;
   hipEvent_t ev_cert_fork = nullptr, ev_cert_join = nullptr;  // the side stream (hstream) hashes the deferred rows next to the verdict launch
   bool cert_overlap = true;                                   // IBFT_CERT_OVERLAP=0: everything on one stream, one verdict launch
+  // IBFT_FLAG_CERT_DEDUP / IBFT_CERT_DEDUP=0|1: the (first) verdict launch of a certificate call judges each distinct
+  // (digest, signature, From) once (cert_dedup_dev.h): the table, every row's slot, every representative's dense position
+  bool cert_dedup = false;
+  uint32_t cert_dedup_slots_cap = 0;  // IBFT_CERT_DEDUP_SLOTS (test hook): at most that many table slots; 0 = no cap
+  DevBuf d_cert_dd_table, d_cert_dd_slot, d_cert_dd_pos;
+  uint32_t cert_stat[4] = {0, 0, 0, 0};  // ibft_cert_stats: rows, judged, given to the verdict kernels, unplaced — of the last certificate call
   bool gather_pinned = true;  // columns in ibft_pinned_alloc buffers are read by one gather launch (IBFT_NO_GATHER=1: never)
   // … whose extra blocks can hash PayloadNoSig straight from the host column (IBFT_DIGEST_FUSION=1).  Off by default: it
   // saves nothing measurable (gather + digest ≈ 46 µs either way) and the 8 192-row known-key kernel of a COMMIT set ran
@@ -1627,6 +1633,9 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   if (getenv("IBFT_NO_GATHER")) c->gather_pinned = false;
   if (const char *e = getenv("IBFT_PROPOSAL_HASH")) c->hash_on_host = strcmp(e, "device") != 0;
   if (const char *e = getenv("IBFT_CERT_OVERLAP")) c->cert_overlap = atoi(e) != 0;
+  c->cert_dedup = (c->flags & IBFT_FLAG_CERT_DEDUP) != 0;
+  if (const char *e = getenv("IBFT_CERT_DEDUP")) c->cert_dedup = atoi(e) != 0;
+  if (const char *e = getenv("IBFT_CERT_DEDUP_SLOTS")) c->cert_dedup_slots_cap = (uint32_t)strtoul(e, nullptr, 10);
   if (getenv("IBFT_DIGEST_FUSION")) c->digest_in_gather = true;
   if (const char *e = getenv("IBFT_WAVE_ROWS_MAX")) c->wave_rows_max = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_PAIR_ROWS_MAX")) c->pair_rows_max = (uint32_t)strtoul(e, nullptr, 10);
@@ -1722,7 +1731,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_warm_done, &c->d_seen, &c->d_acc, &c->d_quorum, &c->d_wire_rows, &c->d_seal,
                     &c->d_xbuf[0], &c->d_xbuf[1], &c->d_xres[0], &c->d_xres[1], &c->d_set, &c->d_noseal, &c->d_class,
                     &c->d_cert_nodes, &c->d_cert_span, &c->d_cert_count, &c->d_cert_prop, &c->d_cert_masks, &c->d_cert_total,
-                    &c->d_cert_slot, &c->d_cert_tiles, &c->d_cert_rec, &c->d_cert_recbase, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
+                    &c->d_cert_slot, &c->d_cert_tiles, &c->d_cert_rec, &c->d_cert_recbase, &c->d_cert_dd_table, &c->d_cert_dd_slot, &c->d_cert_dd_pos, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
                     &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally,
                     &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
                     &c->d_phash, &c->bs_praw[0], &c->bs_praw[1], &c->bs_proff[0], &c->bs_proff[1], &c->bs_pround[0], &c->bs_pround[1],
@@ -3944,8 +3953,15 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
   if ((rc = ensure(c, c->d_cert_slot, m * 4))) return rc;
   if ((rc = ensure(c, c->d_cert_prop, m * 32))) return rc;
   if ((rc = ensure(c, c->d_cert_masks, (size_t)mask_words(m) * 16))) return rc;
+  const bool fresh_total = !c->d_cert_total.p;
   if ((rc = ensure(c, c->d_cert_total, 64))) return rc;
+  if (fresh_total) HIPCHK(c, hipMemset(c->d_cert_total.p, 0, 64));  // (words 8..10: cert_dedup_count_kernel's sums, zero between launches)
   if ((rc = ensure(c, c->d_cert_tiles, (m / 1024 + 2) * 8))) return rc;
+  const bool dedup = c->cert_dedup;
+  const uint32_t dd_slots = dedup ? cdd::table_slots((uint32_t)m, c->cert_dedup_slots_cap) : 0u;
+  if (dedup && (rc = ensure(c, c->d_cert_dd_table, (size_t)dd_slots * 4))) return rc;
+  if (dedup && (rc = ensure(c, c->d_cert_dd_slot, m * 4))) return rc;
+  if (dedup && (rc = ensure(c, c->d_cert_dd_pos, m * 4))) return rc;
   if (judge && (rc = ensure(c, c->d_cert_rec, m * sizeof(certv::record)))) return rc;
   if (judge && (rc = ensure(c, c->d_cert_recbase, (m + 1) * 4))) return rc;
   if (!c->h_cert_total) {
@@ -3957,8 +3973,10 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_cert_fork, hipEventDisableTiming));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_cert_join, hipEventDisableTiming));
   }
-  // the columns hold the tree's rows and, with two verdict launches, the batch of the deferred rows behind them (64-aligned)
-  if (c->cert_overlap && (rc = alloc_rows(c, 2 * (((uint32_t)c->max_rows + 63u) & ~63u)))) return rc;
+  // the columns hold the tree's rows and, with two verdict launches, the batch of the deferred rows behind them (64-aligned);
+  // with the dedup, the dense batch of the representatives behind both
+  const uint32_t rows_al = ((uint32_t)c->max_rows + 63u) & ~63u;
+  if ((c->cert_overlap || dedup) && (rc = alloc_rows(c, (dedup ? 3u : 2u) * rows_al))) return rc;
   const uint8_t *d_wire = (const uint8_t *)c->d_payload.p;
   wire::node_info *d_nodes = (wire::node_info *)c->d_cert_nodes.p;
   wire::row_info *d_rows = (wire::row_info *)c->d_wire_rows.p;
@@ -4057,7 +4075,55 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
   c->ev_used = 0;
   // the verdict launch over all rows of all levels: the digest column holds keccak256(PayloadNoSig) — the seal-style pass; rows that
   // are not judged here (and, with two launches, the deferred rows) are pre-flagged
-  if ((rc = enqueue_recover(c, rows, true, ibftk::MODE_SEALS, false))) return rc;
+  uint32_t *d_stat = d_total + 4, *dh_stat = c->dh_cert_total ? c->dh_cert_total + 4 : nullptr;  // dense rows, unplaced rows, judged rows (tree, deferred batch)
+  volatile uint32_t *h_stat = (volatile uint32_t *)c->h_cert_total + 4;
+  if (!dedup) {
+    if ((rc = enqueue_recover(c, rows, true, ibftk::MODE_SEALS, false))) return rc;
+  } else {
+    // The same verdicts from one launch over the distinct (digest, signature, From) of the rows without a pre-flag
+    // (cert_dedup_dev.h): table, representatives, their dense batch behind the tree's rows and the deferred batch, its
+    // verdict launch (the AUTO rule and learn_key see the dense batch), every row its representative's bit.
+    const uint32_t slots = cdd::table_slots(rows, c->cert_dedup_slots_cap), tiles = ibftk::cert_scan_tiles(rows);
+    const uint32_t dense_base = two ? ((region + carriers + 63u) & ~63u) : ((rows + 63u) & ~63u);
+    uint32_t *d_table = (uint32_t *)c->d_cert_dd_table.p, *d_dd_slot = (uint32_t *)c->d_cert_dd_slot.p, *d_dd_pos = (uint32_t *)c->d_cert_dd_pos.p;
+    const cdd::columns cols{d_digest, d_sig, d_from, d_pre};
+    // with kernel timing on, two event pairs: table + compaction, scatter (the verdict launch between them is not timed on this
+    // path) — ibft_last_kernel_ms after a flag-on ibft_verify_certificates_wire is the time of the dedup's own kernels
+    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
+    if (c->time_every && ((rc = next_events(c, &t0, &t1)) || (rc = next_events(c, &t2, &t3)))) return rc;
+    if (t0) HIPCHK(c, hipEventRecord(t0, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_table, 0xFF, (size_t)slots * 4, c->stream));
+    hipLaunchKernelGGL(ibftk::cert_dedup_insert_kernel, dim3((rows + 255) / 256), dim3(256), 0, c->stream, cols, rows, d_table, slots - 1u, d_dd_slot);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(ibftk::cert_dedup_mark_kernel, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)d_table,
+                       (const uint32_t *)d_dd_slot, rows, d_count);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(ibftk::cert_scan_tiles_kernel, dim3(tiles), dim3(ibftk::CERT_SCAN_TILE_ROWS), 0, c->stream, (const uint32_t *)d_count, rows,
+                       (uint2 *)c->d_cert_tiles.p);
+    hipLaunchKernelGGL(ibftk::cert_scan_offsets_kernel, dim3(1), dim3(ibftk::CERT_SCAN_TILE_ROWS), 0, c->stream, (uint2 *)c->d_cert_tiles.p, tiles, 0u, 0u,
+                       d_stat, dh_stat);
+    hipLaunchKernelGGL(ibftk::cert_dedup_apply_kernel, dim3(tiles), dim3(ibftk::CERT_SCAN_TILE_ROWS), 0, c->stream, (const uint32_t *)d_count, rows,
+                       (const uint2 *)c->d_cert_tiles.p, cols, dense_base, d_dd_pos);
+    HIPCHK(c, hipGetLastError());
+    if (t1) HIPCHK(c, hipEventRecord(t1, c->stream));
+    if (!dh_stat) HIPCHK(c, hipMemcpyAsync(c->h_cert_total + 4, d_stat, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t dense = h_stat[0];
+    if (dense > rows) {
+      c->last_error = "certificate dedup: more representatives than rows";
+      return IBFT_E_HIP;
+    }
+    uint64_t *d_dense_mask = (uint64_t *)c->d_mask.p + dense_base / 64;
+    // the dense batch's verdict words: zero whatever an earlier call left there; the tree's own words are stored whole below
+    if (dense) HIPCHK(c, hipMemsetAsync(d_dense_mask, 0, (size_t)mask_words(dense) * 8, c->stream));
+    if ((rc = enqueue_recover(c, dense, true, ibftk::MODE_SEALS, false, dense_base, true))) return rc;
+    if (t2) HIPCHK(c, hipEventRecord(t2, c->stream));
+    hipLaunchKernelGGL(ibftk::cert_dedup_scatter_kernel, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)d_table,
+                       (const uint32_t *)d_dd_slot, (const uint32_t *)d_dd_pos, (const uint64_t *)d_dense_mask, rows, (uint64_t *)c->d_mask.p);
+    HIPCHK(c, hipGetLastError());
+    if (t3) HIPCHK(c, hipEventRecord(t3, c->stream));
+    c->mask_dirty_words = std::max(c->mask_dirty_words, (uint32_t)mask_words(rows));
+  }
   if (two) {
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_cert_join, 0));
     // the deferred rows' verdict words: zero whatever an earlier call left there (the first launch only vouches for its own words)
@@ -4067,6 +4133,11 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
                        (uint64_t *)c->d_mask.p);
     HIPCHK(c, hipGetLastError());
   }
+  // ibft_cert_stats: how many rows the verdict launches judged (no pre-flag), the tree's rows and the deferred batch apart
+  hipLaunchKernelGGL(ibftk::cert_dedup_count_kernel, dim3(std::min(ibftk::CERT_DEDUP_COUNT_GRID, (rows + (two ? carriers : 0u) + 255u) / 256u)), dim3(256), 0, c->stream, (const uint8_t *)d_pre,
+                     rows, (const uint8_t *)d_pre + region, two ? carriers : 0u, d_total + 8, d_stat + 2, dh_stat ? dh_stat + 2 : nullptr);
+  HIPCHK(c, hipGetLastError());
+  if (!dh_stat) HIPCHK(c, hipMemcpyAsync(c->h_cert_total + 6, d_stat + 2, 8, hipMemcpyDeviceToHost, c->stream));
   uint64_t *d_hash_mask = (uint64_t *)c->d_cert_masks.p, *d_self_mask = d_hash_mask + mask_words(m);
   hipLaunchKernelGGL(ibftk::cert_compare_kernel, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const wire::node_info *)d_nodes,
                      (const wire::row_info *)d_rows, (const uint8_t *)d_prop, rows, d_hash_mask, d_self_mask, (uint8_t *)c->d_class.p);
@@ -4124,6 +4195,20 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
   if ((rc = fetch_results(c, rows, out_sender_mask, nullptr, false))) return rc;
   *out_n_rows = rows;
   if (judge) *out_n_certs = records;
+  const uint32_t judged = h_stat[2] + h_stat[3];
+  c->cert_stat[0] = rows;
+  c->cert_stat[1] = judged;
+  c->cert_stat[2] = dedup ? h_stat[0] + h_stat[3] : judged;
+  c->cert_stat[3] = dedup ? h_stat[1] : 0u;
+  return IBFT_OK;
+}
+int ibft_cert_stats(ibft_ctx *c, uint32_t *rows, uint32_t *judged_rows, uint32_t *verdict_rows, uint32_t *unplaced_rows) {
+  if (!c) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  if (rows) *rows = c->cert_stat[0];
+  if (judged_rows) *judged_rows = c->cert_stat[1];
+  if (verdict_rows) *verdict_rows = c->cert_stat[2];
+  if (unplaced_rows) *unplaced_rows = c->cert_stat[3];
   return IBFT_OK;
 }
 int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap,

@@ -23,6 +23,7 @@ from .build import LIB
 
 FLAG_STRICT_LOW_S = 1
 FLAG_PUBKEY_CACHE = 2   # warm path: verify against per-validator tables once a key has been recovered
+FLAG_CERT_DEDUP = 4     # certificate calls judge each distinct (digest, signature, From) once (IBFT_CERT_DEDUP=0|1 overrides)
 ROW_NIL, ROW_BADLEN, ROW_HASH_BAD = 1, 2, 4
 KERNEL_AUTO, KERNEL_LANE, KERNEL_WAVE = 0, 1, 2
 SIGN_NONCE_KECCAK, SIGN_NONCE_RFC6979 = 0, 1   # IBFT_SIGN_NONCE_*
@@ -52,6 +53,7 @@ EXPORTS = [
     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
+    "ibft_cert_stats",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
@@ -65,7 +67,8 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
                     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
                     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
-                    "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire"}
+                    "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
+                    "ibft_cert_stats"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
 ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
@@ -260,6 +263,8 @@ def load_library() -> C.CDLL:
     if hasattr(L, "ibft_judge_certificates_wire"):
         L.ibft_judge_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                                    vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_cert_stats"):
+        L.ibft_cert_stats.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4
     L.ibft_set_validators_u256.argtypes = [vp, C.c_uint64, vp, vp, C.c_size_t]
     L.ibft_last_tally_wide.argtypes = [vp, C.POINTER(TallyWide)]
     L.ibft_shard_range.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -948,6 +953,15 @@ class BatchVerifier:
         (IBFT_E_TOOBIG) when the tree exceeds rows_cap or the records exceed certs_cap (default: rows_cap)."""
         return _judge_certificates_wire(self._L, self._h, self._chk, wire, off, int(rows_cap if rows_cap is not None else self.max_rows),
                                         certs_cap, per_row)
+
+    def cert_stats(self):
+        """ibft_cert_stats, of the last verify_ / judge_certificates_wire call: (rows of the tree, rows judged — no pre-flag —,
+        rows given to the verdict kernels, rows the dedup table could not place).  FLAG_CERT_DEDUP off: judged == given, 0."""
+        if not hasattr(self._L, "ibft_cert_stats"):
+            raise GpuUnavailable("this build of libibftgpu.so has no ibft_cert_stats — rebuild")
+        v = [C.c_uint32() for _ in range(4)]
+        self._chk(self._L.ibft_cert_stats(self._h, *(C.byref(x) for x in v)), "ibft_cert_stats")
+        return tuple(int(x.value) for x in v)
 
     def wire_stage_seals(self):
         """the COMMIT seals of the last is_valid_validator_wire batch become the resident seal batch"""

@@ -81,7 +81,11 @@ type Options struct {
 	MaxRows    uint32
 	StrictLowS bool
 	KeyCache   bool
+	CertDedup  bool // FlagCertDedup: certificate calls judge each distinct (digest, signature, From) once
 }
+
+// FlagCertDedup is IBFT_FLAG_CERT_DEDUP (Options.CertDedup sets it; the environment variable IBFT_CERT_DEDUP=0|1 overrides it).
+const FlagCertDedup = uint32(C.IBFT_FLAG_CERT_DEDUP)
 
 // abiVersion is what this binding was written against (include/ibftgpu.h: ibft_version; 2 = ibft_tally_t with
 // proposer_rows, 56 bytes: an older library would write a shorter struct; 3 = the staged / pipelined pass calls,
@@ -98,6 +102,9 @@ func New(o Options) (*Ctx, error) {
 	}
 	if o.KeyCache {
 		cfg.flags |= C.IBFT_FLAG_PUBKEY_CACHE
+	}
+	if o.CertDedup {
+		cfg.flags |= C.IBFT_FLAG_CERT_DEDUP
 	}
 	var h *C.ibft_ctx
 	if rc := C.ibft_ctx_create(&cfg, &h); rc != C.IBFT_OK {
@@ -896,6 +903,15 @@ func (c *Ctx) JudgeCertificatesWire(wire []byte, off []uint32, rowsCap, certsCap
 	return certs[:int(nCerts)], int(nRows), c.check(rc)
 }
 
+// CertStats reports on the context's last certificate call (ibft_cert_stats): the tree's rows, the rows that were judged (no
+// pre-flag), the rows actually given to the verdict kernels, and the rows the dedup table could not place.  Without
+// FlagCertDedup verdict == judged and unplaced == 0.
+func (c *Ctx) CertStats() (rows, judged, verdict, unplaced uint32, err error) {
+	var r, j, v, u C.uint32_t
+	rc := C.ibft_cert_stats(c.h, &r, &j, &v, &u)
+	return uint32(r), uint32(j), uint32(v), uint32(u), c.check(rc)
+}
+
 // PinnedBytes returns n bytes of page-locked memory (ibft_pinned_alloc) as a Go slice: column buffers the
 // flatten step writes into once and reuses every round.  When every column of a call lies in such buffers the
 // library reads them with one gather launch instead of one copy command per column.  C memory: invisible to
@@ -1177,6 +1193,9 @@ func NewGroup(devices []int32, o Options) (*Group, error) {
 	}
 	if o.KeyCache {
 		flags |= C.IBFT_FLAG_PUBKEY_CACHE
+	}
+	if o.CertDedup {
+		flags |= C.IBFT_FLAG_CERT_DEDUP
 	}
 	var g *C.ibft_group
 	rc := C.ibft_group_create((*C.int32_t)(unsafe.Pointer(&devices[0])), C.uint32_t(len(devices)), flags,
