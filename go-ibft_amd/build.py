@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libibftgpu.so")
-SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "cert_wave_dev.h", "cert_scan_dev.h", "cert_verdict_dev.h", "cert_dedup_dev.h", "modinv_dev.h",
+SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "cert_wave_dev.h", "cert_scan_dev.h", "cert_verdict_dev.h", "cert_dedup_dev.h", "cert_dedup_kernels.h", "modinv_dev.h",
            "sign_dev.h", "sign_message_dev.h", "sign_envelope_dev.h", "sha256_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
 # Code-generation flags of the product library (part of its build stamp).  max-ilp: the verdict kernels run ONE wavefront per
 # SIMD at the sizes that matter (N ≤ 4 096), where every hazard s_nop is a lost issue slot — scheduling for instruction-level
@@ -143,10 +143,10 @@ DEVTEST = os.path.join(CSRC, "libibft_devtest.so")
 
 
 def build_devtest(force: bool = False) -> str:
-    """TEST-ONLY: single arithmetic primitives (tests/test_gpu_arith.py) and the certificate tree's level scans
-    (tests/test_gpu_cert_scan.py) as gfx950 kernels."""
+    """TEST-ONLY: single arithmetic primitives (tests/test_gpu_arith.py), the certificate tree's level scans
+    (tests/test_gpu_cert_scan.py) and its dedup kernels (tests/test_gpu_cert_dedup_kernels.py) as gfx950 kernels."""
     deps = ["devtest.hip", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", "wave_fe_dev.h", "verify_dev.h",
-            "sign_dev.h", "sha256_dev.h", "cert_scan_dev.h", "wire_dev.h"]
+            "sign_dev.h", "sha256_dev.h", "cert_scan_dev.h", "wire_dev.h", "cert_dedup_dev.h", "cert_dedup_kernels.h"]
     if force or _stale(DEVTEST, deps):
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-w",
                                "-o", DEVTEST, os.path.join(CSRC, "devtest.hip")], cwd=CSRC)

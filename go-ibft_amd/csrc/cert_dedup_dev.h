@@ -1,4 +1,4 @@
-// cert_dedup_dev.h — the certificate tree's opt-in dedup (IBFT_FLAG_CERT_DEDUP; kernels.hip.h §8f: cert_dedup_*_kernel): the
+// cert_dedup_dev.h — the certificate tree's opt-in dedup (IBFT_FLAG_CERT_DEDUP; cert_dedup_kernels.h: cert_dedup_*_kernel): the
 // rows of a verdict launch that carry the same (digest, signature, From) are one signature to check.  The row logic lives
 // here as __host__ __device__ functions, so that host_cert_dedup_harness.hip runs the exact source on the CPU:
 //

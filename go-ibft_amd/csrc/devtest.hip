@@ -566,3 +566,199 @@ out:
   if (h_total) (void)hipHostFree(h_total);
   return (int)e;
 }
+
+// ---- the certificate dedup's kernels (cert_dedup_kernels.h) on a caller's key columns ----
+// The GPU counterpart of host_cert_dedup_harness.hip's cdh_run: the product's kernels through the product's launch helpers,
+// in buffers with sentinel cells around everything they may write (tests/test_gpu_cert_dedup_kernels.py).
+#include "cert_dedup_kernels.h"
+
+namespace {
+constexpr uint32_t DD_PAD = 64, DD_FILL = 0xA5A5A5A5u;
+struct dd_bufs {
+  std::vector<void *> dev;
+  uint32_t *h_total = nullptr, *d_total = nullptr, *host_words = nullptr;
+  ~dd_bufs() {
+    for (void *p : dev) (void)hipFree(p);
+    if (h_total) (void)hipHostFree(h_total);
+  }
+  // `count` elements (and one more, so that nothing is ever empty) of 0xA5 bytes
+  template <class T>
+  hipError_t filled(T **p, size_t count) {
+    void *q = nullptr;
+    const hipError_t e = hipMalloc(&q, (count + 1) * sizeof(T));
+    if (e != hipSuccess) return e;
+    dev.push_back(q);
+    *p = (T *)q;
+    return hipMemset(q, 0xA5, (count + 1) * sizeof(T));
+  }
+  // the words the library keeps at d_cert_total / h_cert_total: [4..5] {dense, unplaced}, [6..7] the two counts, [8..10] the
+  // count kernel's accumulators (zero between launches); every other word a sentinel
+  hipError_t totals() {
+    hipError_t e = filled(&d_total, DD_PAD);
+    if (e != hipSuccess || (e = hipMemset(d_total + 8, 0, 12)) != hipSuccess) return e;
+    if ((e = hipHostMalloc((void **)&h_total, DD_PAD * 4)) != hipSuccess) return e;
+    memset(h_total, 0xA5, DD_PAD * 4);
+    return hipHostGetDevicePointer((void **)&host_words, h_total, 0);
+  }
+  // bit 8 of sentinels_changed: a word of either set of totals that no kernel may write
+  hipError_t totals_changed(uint32_t *changed) {
+    uint32_t w[DD_PAD];
+    const hipError_t e = hipMemcpy(w, d_total, DD_PAD * 4, hipMemcpyDeviceToHost);
+    for (uint32_t k = 0; k < DD_PAD && e == hipSuccess; k++)
+      if ((w[k] != DD_FILL && !(k >= 4 && k <= 10)) || (h_total[k] != DD_FILL && !(k >= 4 && k <= 7))) *changed |= 256u;
+    return e;
+  }
+};
+#define DD_TRY(call) \
+  if ((e = (call)) != hipSuccess) return (int)e
+
+// cert_dedup_count_kernel twice in a row over flag columns on the device → out14: per launch {the two counts on the device, the
+// two in the host's words, the three accumulator words after it}.  The result words are set back to the sentinel before each
+// launch, so every launch has to deliver its own.
+int dd_count_twice(dd_bufs &B, const uint8_t *d_a, uint32_t n_a, const uint8_t *d_b, uint32_t n_b, uint32_t *out14) {
+  hipError_t e = hipSuccess;
+  for (int pass = 0; pass < 2; pass++) {
+    uint32_t w[5];
+    DD_TRY(hipMemset(B.d_total + 6, 0xA5, 8));
+    B.h_total[6] = B.h_total[7] = DD_FILL;
+    ibftk::cert_dedup_count_launch(nullptr, d_a, n_a, d_b, n_b, B.d_total + 8, B.d_total + 6, B.host_words + 6);
+    DD_TRY(hipGetLastError());
+    DD_TRY(hipDeviceSynchronize());
+    DD_TRY(hipMemcpy(w, B.d_total + 6, 20, hipMemcpyDeviceToHost));
+    uint32_t *o = out14 + 7 * pass;
+    o[0] = w[0], o[1] = w[1], o[2] = B.h_total[6], o[3] = B.h_total[7], o[4] = w[2], o[5] = w[3], o[6] = w[4];
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" uint32_t devtest_cert_dedup_max_probes(void) { return cdd::MAX_PROBES; }
+extern "C" uint32_t devtest_cert_dedup_table_slots(uint32_t rows, uint32_t cap) { return cdd::table_slots(rows, cap); }
+
+// The count kernel alone: flag columns of n_a and n_b bytes (either may be empty, not both) → out14 as dd_count_twice gives it.
+// *sentinels_changed: bit 8 only.  Returns 0, -3 (arguments), or the HIP status that failed.
+extern "C" int devtest_cert_dedup_count(uint32_t n_a, const uint8_t *pre_a, uint32_t n_b, const uint8_t *pre_b, uint32_t *out14,
+                                        uint32_t *sentinels_changed) {
+  if ((uint64_t)n_a + n_b == 0 || (uint64_t)n_a + n_b > 0x7FFFFFFFull || (n_a && !pre_a) || (n_b && !pre_b) || !out14 || !sentinels_changed) return -3;
+  dd_bufs B;
+  hipError_t e = hipSuccess;
+  uint8_t *d_a = nullptr, *d_b = nullptr;
+  DD_TRY(B.filled(&d_a, n_a));
+  DD_TRY(B.filled(&d_b, n_b));
+  if (n_a) DD_TRY(hipMemcpy(d_a, pre_a, n_a, hipMemcpyHostToDevice));
+  if (n_b) DD_TRY(hipMemcpy(d_b, pre_b, n_b, hipMemcpyHostToDevice));
+  DD_TRY(B.totals());
+  if (const int rc = dd_count_twice(B, d_a, n_a, d_b, n_b, out14)) return rc;
+  *sentinels_changed = 0;
+  DD_TRY(B.totals_changed(sentinels_changed));
+  return 0;
+}
+
+// n rows of (digest32, sig65, from20, pre) and a slot cap (0: none) through the front (table clear, insert, mark, tile sums,
+// offsets, apply), then a verdict word per 64 dense rows built HERE from the gathered bytes alone — dense row d's bit is 1 iff
+// its gathered pre is 0 and the low bit of its gathered digest byte 0 is set — then the scatter, then the count twice over
+// pre[0, n) and pre_b[0, n_b).  Out: rep[n] (cdd::rep_of over the final table; cdd::NO_REP for pre-flagged rows), slot_of[n],
+// dense_pos[n] (the sentinel where the kernel wrote nothing), the gathered rows (only the first `dense` rows of g_* are
+// written), mask[⌈n/64⌉] (pre-filled with all ones before the scatter), stat4 {dense, unplaced} on the device and in the
+// host's words, count14 (dd_count_twice).  *sentinels_changed: bit 0 cells around the table, 1 around slot_of, 2 around
+// dense_pos, 3 around the tile cells, 4 around the scan words, 5 column rows between the tree's rows and the dense batch or
+// behind it, 6 a source row, 7 mask words around ⌈n/64⌉, 8 another word of the totals.
+// Returns 0, -3 (arguments), -4 (more representatives than rows: nothing behind the front ran), or the HIP status that failed.
+extern "C" int devtest_cert_dedup(uint32_t n, const uint8_t *digest32, const uint8_t *sig65, const uint8_t *from20, const uint8_t *pre,
+                                  uint32_t slots_cap, uint32_t n_b, const uint8_t *pre_b, uint32_t *rep, uint32_t *slot_of, uint32_t *dense_pos,
+                                  uint8_t *g_digest32, uint8_t *g_sig65, uint8_t *g_from20, uint8_t *g_pre, uint64_t *mask, uint32_t *stat4,
+                                  uint32_t *count14, uint32_t *sentinels_changed) {
+  constexpr uint32_t PAD = DD_PAD;
+  if (!n || n > 0x20000000u || n_b > 0x20000000u || !digest32 || !sig65 || !from20 || !pre || (n_b && !pre_b) || !rep || !slot_of || !dense_pos ||
+      !g_digest32 || !g_sig65 || !g_from20 || !g_pre || !mask || !stat4 || !count14 || !sentinels_changed)
+    return -3;
+  const uint32_t slots = cdd::table_slots(n, slots_cap), tiles = ibftk::cert_scan_tiles(n), dense_base = (n + 63u) & ~63u, words = (n + 63u) / 64u;
+  const size_t col_rows = (size_t)dense_base + n + PAD;  // the tree's rows, a dense batch of up to n rows behind them, sentinel rows
+  const size_t widths[4] = {32, 65, 20, 1};
+  const uint8_t *src[4] = {digest32, sig65, from20, pre};
+  uint8_t *g_out[4] = {g_digest32, g_sig65, g_from20, g_pre};
+  dd_bufs B;
+  hipError_t e = hipSuccess;
+  uint8_t *d_col[4] = {}, *d_pre_b = nullptr;
+  uint32_t *d_table = nullptr, *d_slot = nullptr, *d_word = nullptr, *d_pos = nullptr;
+  uint2 *d_tiles = nullptr;
+  uint64_t *d_mask = nullptr, *d_dense_mask = nullptr;
+  uint32_t changed = 0;
+  for (int k = 0; k < 4; k++) {
+    DD_TRY(B.filled(&d_col[k], col_rows * widths[k]));
+    DD_TRY(hipMemcpy(d_col[k], src[k], (size_t)n * widths[k], hipMemcpyHostToDevice));
+  }
+  DD_TRY(B.filled(&d_pre_b, n_b));
+  if (n_b) DD_TRY(hipMemcpy(d_pre_b, pre_b, n_b, hipMemcpyHostToDevice));
+  DD_TRY(B.filled(&d_table, (size_t)slots + 2 * PAD));
+  DD_TRY(B.filled(&d_slot, (size_t)n + 2 * PAD));
+  DD_TRY(B.filled(&d_word, (size_t)n + 2 * PAD));
+  DD_TRY(B.filled(&d_pos, (size_t)n + 2 * PAD));
+  DD_TRY(B.filled(&d_tiles, (size_t)tiles + 2 * PAD));
+  DD_TRY(B.filled(&d_mask, (size_t)words + 2 * PAD));
+  DD_TRY(B.totals());
+  const cdd::columns cols{d_col[0], d_col[1], d_col[2], d_col[3]};
+  DD_TRY(ibftk::cert_dedup_front_launch(nullptr, cols, n, slots, dense_base, d_table + PAD, d_slot + PAD, d_word + PAD, d_tiles + PAD, d_pos + PAD,
+                                        B.d_total + 4, B.host_words + 4));
+  DD_TRY(hipGetLastError());
+  DD_TRY(hipDeviceSynchronize());
+  std::vector<uint32_t> table((size_t)slots + 2 * PAD), slot((size_t)n + 2 * PAD), word((size_t)n + 2 * PAD), pos((size_t)n + 2 * PAD),
+      tile(2 * ((size_t)tiles + 2 * PAD));
+  uint32_t stat_dev[2];
+  DD_TRY(hipMemcpy(table.data(), d_table, table.size() * 4, hipMemcpyDeviceToHost));
+  DD_TRY(hipMemcpy(slot.data(), d_slot, slot.size() * 4, hipMemcpyDeviceToHost));
+  DD_TRY(hipMemcpy(word.data(), d_word, word.size() * 4, hipMemcpyDeviceToHost));
+  DD_TRY(hipMemcpy(pos.data(), d_pos, pos.size() * 4, hipMemcpyDeviceToHost));
+  DD_TRY(hipMemcpy(tile.data(), d_tiles, tile.size() * 4, hipMemcpyDeviceToHost));
+  DD_TRY(hipMemcpy(stat_dev, B.d_total + 4, 8, hipMemcpyDeviceToHost));
+  const uint32_t dense = stat_dev[0];
+  stat4[0] = stat_dev[0], stat4[1] = stat_dev[1], stat4[2] = B.h_total[4], stat4[3] = B.h_total[5];
+  if (dense > n) return -4;
+  const auto around = [&](const std::vector<uint32_t> &v, size_t inner, size_t pad) {  // `pad` words before and behind `inner` words
+    for (size_t k = 0; k < pad; k++)
+      if (v[k] != DD_FILL || v[pad + inner + k] != DD_FILL) return true;
+    return false;
+  };
+  if (around(table, slots, PAD)) changed |= 1u;
+  if (around(slot, n, PAD)) changed |= 2u;
+  if (around(pos, n, PAD)) changed |= 4u;
+  if (around(tile, 2 * (size_t)tiles, 2 * PAD)) changed |= 8u;  // (two words per cell)
+  if (around(word, n, PAD)) changed |= 16u;
+  std::vector<uint8_t> col[4];
+  for (int k = 0; k < 4; k++) {
+    const size_t w = widths[k];
+    col[k].resize(col_rows * w);
+    DD_TRY(hipMemcpy(col[k].data(), d_col[k], col_rows * w, hipMemcpyDeviceToHost));
+    if (memcmp(col[k].data(), src[k], (size_t)n * w) != 0) changed |= 64u;
+    for (size_t i = (size_t)n * w; i < col_rows * w; i++)
+      if (col[k][i] != 0xA5 && (i < (size_t)dense_base * w || i >= ((size_t)dense_base + dense) * w)) changed |= 32u;
+    memcpy(g_out[k], col[k].data() + (size_t)dense_base * w, (size_t)dense * w);
+  }
+  // the dense batch's verdict words, from the gathered bytes and nothing else
+  std::vector<uint64_t> dense_mask((dense + 63u) / 64u + 1u, 0);
+  for (uint32_t d = 0; d < dense; d++)
+    if (g_pre[d] == 0 && (g_digest32[32ull * d] & 1u)) dense_mask[d >> 6] |= 1ull << (d & 63u);
+  DD_TRY(B.filled(&d_dense_mask, dense_mask.size()));
+  DD_TRY(hipMemcpy(d_dense_mask, dense_mask.data(), dense_mask.size() * 8, hipMemcpyHostToDevice));
+  DD_TRY(hipMemset(d_mask + PAD, 0xFF, (size_t)words * 8));  // the tree's own words: the scatter has to store each of them whole
+  ibftk::cert_dedup_scatter_launch(nullptr, d_table + PAD, d_slot + PAD, d_pos + PAD, d_dense_mask, n, d_mask + PAD);
+  DD_TRY(hipGetLastError());
+  DD_TRY(hipDeviceSynchronize());
+  std::vector<uint64_t> m((size_t)words + 2 * PAD);
+  DD_TRY(hipMemcpy(m.data(), d_mask, m.size() * 8, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < PAD; k++)
+    if (m[k] != 0xA5A5A5A5A5A5A5A5ull || m[PAD + words + k] != 0xA5A5A5A5A5A5A5A5ull) changed |= 128u;
+  memcpy(mask, m.data() + PAD, (size_t)words * 8);
+  for (uint32_t r = 0; r < n; r++) {
+    slot_of[r] = slot[PAD + r];
+    dense_pos[r] = pos[PAD + r];
+    const bool placed = slot_of[r] != cdd::SLOT_SKIP && slot_of[r] != cdd::SLOT_UNPLACED;
+    if (placed && slot_of[r] >= slots) return -4;  // (never index the copy of the table with it)
+    rep[r] = cdd::rep_of(table.data() + PAD, slot_of[r], r);
+  }
+  if (const int rc = dd_count_twice(B, d_col[3], n, d_pre_b, n_b, count14)) return rc;
+  DD_TRY(B.totals_changed(&changed));
+  *sentinels_changed = changed;
+  return 0;
+}
+#undef DD_TRY

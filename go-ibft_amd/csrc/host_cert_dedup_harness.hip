@@ -1,8 +1,9 @@
 // host_cert_dedup_harness.hip — TEST-ONLY: cert_dedup_dev.h (the certificate dedup's row logic: table insert, representatives,
 // gather, scatter) on the CPU, so that tests/test_dev_cert_dedup_host.py can check the exact device source without a GPU.
 // cdh_run walks the steps certificates_wire_impl enqueues, one row after the other — the two atomics are plain operations
-// here, and the rows are inserted in the order the test gives.  Built with hipcc's host pass; never linked into
-// libibftgpu.so, never a fallback.
+// here, and the rows are inserted in the order the test gives (the atomics themselves, with thousands of lanes on one table
+// word: devtest.hip's devtest_cert_dedup, tests/test_gpu_cert_dedup_kernels.py).  Built with hipcc's host pass; never linked
+// into libibftgpu.so, never a fallback.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>

@@ -4083,7 +4083,7 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
     // The same verdicts from one launch over the distinct (digest, signature, From) of the rows without a pre-flag
     // (cert_dedup_dev.h): table, representatives, their dense batch behind the tree's rows and the deferred batch, its
     // verdict launch (the AUTO rule and learn_key see the dense batch), every row its representative's bit.
-    const uint32_t slots = cdd::table_slots(rows, c->cert_dedup_slots_cap), tiles = ibftk::cert_scan_tiles(rows);
+    const uint32_t slots = cdd::table_slots(rows, c->cert_dedup_slots_cap);
     const uint32_t dense_base = two ? ((region + carriers + 63u) & ~63u) : ((rows + 63u) & ~63u);
     uint32_t *d_table = (uint32_t *)c->d_cert_dd_table.p, *d_dd_slot = (uint32_t *)c->d_cert_dd_slot.p, *d_dd_pos = (uint32_t *)c->d_cert_dd_pos.p;
     const cdd::columns cols{d_digest, d_sig, d_from, d_pre};
@@ -4092,18 +4092,8 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
     hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
     if (c->time_every && ((rc = next_events(c, &t0, &t1)) || (rc = next_events(c, &t2, &t3)))) return rc;
     if (t0) HIPCHK(c, hipEventRecord(t0, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_table, 0xFF, (size_t)slots * 4, c->stream));
-    hipLaunchKernelGGL(ibftk::cert_dedup_insert_kernel, dim3((rows + 255) / 256), dim3(256), 0, c->stream, cols, rows, d_table, slots - 1u, d_dd_slot);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(ibftk::cert_dedup_mark_kernel, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)d_table,
-                       (const uint32_t *)d_dd_slot, rows, d_count);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(ibftk::cert_scan_tiles_kernel, dim3(tiles), dim3(ibftk::CERT_SCAN_TILE_ROWS), 0, c->stream, (const uint32_t *)d_count, rows,
-                       (uint2 *)c->d_cert_tiles.p);
-    hipLaunchKernelGGL(ibftk::cert_scan_offsets_kernel, dim3(1), dim3(ibftk::CERT_SCAN_TILE_ROWS), 0, c->stream, (uint2 *)c->d_cert_tiles.p, tiles, 0u, 0u,
-                       d_stat, dh_stat);
-    hipLaunchKernelGGL(ibftk::cert_dedup_apply_kernel, dim3(tiles), dim3(ibftk::CERT_SCAN_TILE_ROWS), 0, c->stream, (const uint32_t *)d_count, rows,
-                       (const uint2 *)c->d_cert_tiles.p, cols, dense_base, d_dd_pos);
+    HIPCHK(c, ibftk::cert_dedup_front_launch(c->stream, cols, rows, slots, dense_base, d_table, d_dd_slot, d_count, (uint2 *)c->d_cert_tiles.p, d_dd_pos,
+                                             d_stat, dh_stat));
     HIPCHK(c, hipGetLastError());
     if (t1) HIPCHK(c, hipEventRecord(t1, c->stream));
     if (!dh_stat) HIPCHK(c, hipMemcpyAsync(c->h_cert_total + 4, d_stat, 8, hipMemcpyDeviceToHost, c->stream));
@@ -4118,8 +4108,8 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
     if (dense) HIPCHK(c, hipMemsetAsync(d_dense_mask, 0, (size_t)mask_words(dense) * 8, c->stream));
     if ((rc = enqueue_recover(c, dense, true, ibftk::MODE_SEALS, false, dense_base, true))) return rc;
     if (t2) HIPCHK(c, hipEventRecord(t2, c->stream));
-    hipLaunchKernelGGL(ibftk::cert_dedup_scatter_kernel, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)d_table,
-                       (const uint32_t *)d_dd_slot, (const uint32_t *)d_dd_pos, (const uint64_t *)d_dense_mask, rows, (uint64_t *)c->d_mask.p);
+    ibftk::cert_dedup_scatter_launch(c->stream, (const uint32_t *)d_table, (const uint32_t *)d_dd_slot, (const uint32_t *)d_dd_pos,
+                                     (const uint64_t *)d_dense_mask, rows, (uint64_t *)c->d_mask.p);
     HIPCHK(c, hipGetLastError());
     if (t3) HIPCHK(c, hipEventRecord(t3, c->stream));
     c->mask_dirty_words = std::max(c->mask_dirty_words, (uint32_t)mask_words(rows));
@@ -4134,8 +4124,8 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
     HIPCHK(c, hipGetLastError());
   }
   // ibft_cert_stats: how many rows the verdict launches judged (no pre-flag), the tree's rows and the deferred batch apart
-  hipLaunchKernelGGL(ibftk::cert_dedup_count_kernel, dim3(std::min(ibftk::CERT_DEDUP_COUNT_GRID, (rows + (two ? carriers : 0u) + 255u) / 256u)), dim3(256), 0, c->stream, (const uint8_t *)d_pre,
-                     rows, (const uint8_t *)d_pre + region, two ? carriers : 0u, d_total + 8, d_stat + 2, dh_stat ? dh_stat + 2 : nullptr);
+  ibftk::cert_dedup_count_launch(c->stream, (const uint8_t *)d_pre, rows, (const uint8_t *)d_pre + region, two ? carriers : 0u, d_total + 8, d_stat + 2,
+                                 dh_stat ? dh_stat + 2 : nullptr);
   HIPCHK(c, hipGetLastError());
   if (!dh_stat) HIPCHK(c, hipMemcpyAsync(c->h_cert_total + 6, d_stat + 2, 8, hipMemcpyDeviceToHost, c->stream));
   uint64_t *d_hash_mask = (uint64_t *)c->d_cert_masks.p, *d_self_mask = d_hash_mask + mask_words(m);

@@ -1570,91 +1570,10 @@ __global__ void cert_scatter_kernel(const uint32_t *__restrict__ deferred_rows, 
   const uint32_t src = region + k, row = deferred_rows[k];
   if ((mask[src >> 6] >> (src & 63u)) & 1ull) atomicOr((unsigned long long *)(mask + (row >> 6)), 1ull << (row & 63u));
 }
-// ---- the certificate tree's opt-in dedup (IBFT_FLAG_CERT_DEDUP; the row logic: cert_dedup_dev.h) ----------------------------
-// In place of the verdict launch over rows [0, n): cert_dedup_insert_kernel (every row without a pre-flag into the table),
-// cert_dedup_mark_kernel (bit 0: the row is its key's lowest row, bit 31: it gave up — the count words the tiled scan of
-// cert_scan_dev.h takes: cert_scan_tiles_kernel, cert_scan_offsets_kernel), cert_dedup_apply_kernel (every representative's
-// position in the dense batch, ascending, and its columns gathered there), the verdict launch over the dense batch (the host
-// reads its size), cert_dedup_scatter_kernel (whole verdict words of the tree).
-__global__ void __launch_bounds__(256) cert_dedup_insert_kernel(cdd::columns k, uint32_t n, uint32_t *__restrict__ table, uint32_t slot_mask,
-                                                                uint32_t *__restrict__ slot_of) {
-  const uint32_t row = blockIdx.x * 256u + threadIdx.x;
-  if (row < n) slot_of[row] = cdd::insert_row(k, row, table, slot_mask);
-}
-__global__ void __launch_bounds__(256) cert_dedup_mark_kernel(const uint32_t *__restrict__ table, const uint32_t *__restrict__ slot_of, uint32_t n,
-                                                              uint32_t *__restrict__ scan_word) {
-  const uint32_t row = blockIdx.x * 256u + threadIdx.x;
-  if (row < n) scan_word[row] = cdd::scan_word(table, slot_of[row], row);
-}
-// tile_off[tile].x: representatives in the tiles before this one (cert_scan_offsets_kernel with base 0)
-__global__ void __launch_bounds__(1024) cert_dedup_apply_kernel(const uint32_t *__restrict__ scan_word, uint32_t n, const uint2 *__restrict__ tile_off,
-                                                                cdd::columns k, uint32_t dense_base, uint32_t *__restrict__ dense_pos) {
-  __shared__ uint32_t a[1024];
-  const uint32_t t = threadIdx.x, i = blockIdx.x * 1024u + t;
-  const uint32_t rep = i < n ? scan_word[i] & 1u : 0u;
-  a[t] = rep;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024u; o <<= 1) {
-    const uint32_t x = t >= o ? a[t - o] : 0u;
-    __syncthreads();
-    a[t] += x;
-    __syncthreads();
-  }
-  if (!rep) return;
-  const uint32_t d = tile_off[blockIdx.x].x + a[t] - 1u;
-  dense_pos[i] = d;
-  cdd::gather_row(k, i, dense_base + d);
-}
-// dense_mask: the verdict words of the dense batch; mask: those of the tree's rows [0, n), every one of them stored whole
-__global__ void __launch_bounds__(256) cert_dedup_scatter_kernel(const uint32_t *__restrict__ table, const uint32_t *__restrict__ slot_of,
-                                                                 const uint32_t *__restrict__ dense_pos, const uint64_t *__restrict__ dense_mask,
-                                                                 uint32_t n, uint64_t *__restrict__ mask) {
-  const uint32_t row = blockIdx.x * 256u + threadIdx.x;
-  const bool bit = row < n && cdd::scatter_bit(table, slot_of, dense_pos, dense_mask, row);
-  const uint64_t word = __ballot(bit);
-  if ((threadIdx.x & 63u) == 0 && row < n) mask[row >> 6] = word;
-}
-// ibft_cert_stats: the rows without a pre-flag among pre_a[0, n_a) (the tree's rows) and pre_b[0, n_b) (the batch of the deferred
-// rows) → out[0], out[1] (device, and the mapped host words when not null).  acc: three words that are zero between launches —
-// the workgroup that draws the last ticket delivers the sums and zeroes them again.
-constexpr uint32_t CERT_DEDUP_COUNT_GRID = 64;
-__global__ void __launch_bounds__(256) cert_dedup_count_kernel(const uint8_t *__restrict__ pre_a, uint32_t n_a, const uint8_t *__restrict__ pre_b,
-                                                               uint32_t n_b, uint32_t *__restrict__ acc, uint32_t *__restrict__ out_dev,
-                                                               uint32_t *__restrict__ out_host) {
-  // at most CERT_DEDUP_COUNT_GRID workgroups stride the rows and add ONE pair of sums each (a device-scope atomic per wavefront
-  // of a grid over all rows — 7 300 on one address at 467 172 rows — took 0.15 ms)
-  __shared__ uint32_t part[2];
-  if (threadIdx.x < 2u) part[threadIdx.x] = 0;
-  __syncthreads();
-  uint32_t ca = 0, cb = 0;
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_a + n_b; i += gridDim.x * 256u) {
-    if (i < n_a) ca += pre_a[i] == 0;
-    else cb += pre_b[i - n_a] == 0;
-  }
-  for (int o = 32; o; o >>= 1) {
-    ca += (uint32_t)__shfl_xor((int)ca, o, 64);
-    cb += (uint32_t)__shfl_xor((int)cb, o, 64);
-  }
-  if ((threadIdx.x & 63u) == 0) {
-    atomicAdd(part, ca);
-    atomicAdd(part + 1, cb);
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  if (part[0]) atomicAdd(acc, part[0]);
-  if (part[1]) atomicAdd(acc + 1, part[1]);
-  __threadfence();
-  if (atomicAdd(acc + 2, 1u) != gridDim.x - 1u) return;
-  __threadfence();
-  const uint32_t sa = atomicExch(acc, 0u), sb = atomicExch(acc + 1, 0u);
-  atomicExch(acc + 2, 0u);
-  out_dev[0] = sa;
-  out_dev[1] = sb;
-  if (out_host) {
-    out_host[0] = sa;
-    out_host[1] = sb;
-  }
-}
+}  // namespace ibftk
+// the five cert_dedup_*_kernels (IBFT_FLAG_CERT_DEDUP, ibft_cert_stats) and the helpers that launch them
+#include "cert_dedup_kernels.h"
+namespace ibftk {
 // hash / self bits and the routing byte of every row (wire::tree_compare_row), one verdict word per wavefront
 __global__ void __launch_bounds__(256) cert_compare_kernel(const wire::node_info *__restrict__ nodes, const wire::row_info *__restrict__ rows,
                                                            const uint8_t *__restrict__ prop_digest32, uint32_t n,

@@ -233,3 +233,130 @@ def columns(keys, pre):
         d[r], s[r], f[r] = np.frombuffer(k[:32], np.uint8), np.frombuffer(k[32:97], np.uint8), np.frombuffer(k[97:], np.uint8)
     p[:n, 0] = pre
     return d, s, f, p
+
+
+# ---- the same in numpy: key columns of up to 262 145 rows for tests/test_gpu_cert_dedup_kernels.py ---------------------
+# Keys are (n, 117) uint8 arrays here.  tests/test_dev_cert_dedup_host.py holds np_key_hash and np_longest_run to key_hash
+# and longest_run above, and checks that the table of every input the GPU test demands exact results for is roomy.
+NP_NO_REP = 0xFFFFFFFF
+
+
+def np_key_hash(keys):
+    """key_hash of every row → uint32[n]"""
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    w = np.ascontiguousarray(keys[:, :96]).view("<u4").astype(np.uint64)
+
+    def mix(h, x):
+        h = ((h ^ x) * np.uint64(0x85EBCA6B)) & np.uint64(M32)
+        return ((h << np.uint64(13)) | (h >> np.uint64(19))) & np.uint64(M32)
+    h = np.full(len(keys), 0x9E3779B9, dtype=np.uint64)
+    for i in range(24):
+        h = mix(h, w[:, i])
+    h = mix(h, keys[:, 96].astype(np.uint64))
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0xC2B2AE35)) & np.uint64(M32)
+    return (h ^ (h >> np.uint64(15))).astype(np.uint32)
+
+
+def np_distinct(keys):
+    """→ (the distinct rows of keys, every row's index among them)"""
+    v = np.ascontiguousarray(keys, dtype=np.uint8).view(np.dtype((np.void, keys.shape[1])))[:, 0]
+    u, inv = np.unique(v, return_inverse=True)
+    return u.view(np.uint8).reshape(len(u), keys.shape[1]), inv.reshape(-1)
+
+
+def np_longest_run(distinct_keys, slots):
+    """longest_run for an array of distinct keys"""
+    if len(distinct_keys) == 0:
+        return 0
+    if len(distinct_keys) >= slots:
+        return slots
+    home = np.sort((np.uint64(slots - 1) & np.asarray(np_key_hash(distinct_keys), dtype=np.uint64)).astype(np.int64))
+    # linear probing on an unbounded line: the i-th key in order of its home slot sits at max_{j ≤ i}(home_j + i − j); keys
+    # pushed past the end come in again from slot 0 and push what sits there, which may push more past the end: repeat with
+    # that many keys in front until the number is stable (fewer keys than slots leave a free slot that cuts every run)
+    over = 0
+    while True:
+        home2 = np.concatenate([np.zeros(over, np.int64), home])      # the wrapped keys probe from slot 0 on
+        i = np.arange(len(home2), dtype=np.int64)
+        pos = i + np.maximum.accumulate(home2 - i)
+        now_over = int((pos >= slots).sum())
+        if now_over == over:
+            break
+        over = now_over
+    pos = pos[pos < slots]                                             # those that fall off the end are the ones in front
+    taken = np.zeros(slots, dtype=bool)
+    taken[pos] = True
+    free = np.nonzero(~taken)[0]
+    return int((np.diff(np.concatenate([free, [free[0] + slots]])) - 1).max())
+
+
+def np_reference(keys, pre):
+    """→ (rep per row, NP_NO_REP for a pre-flagged one; the dense batch's source rows, ascending; every row's verdict bit when a
+    dense row's bit is: no pre-flag and the low bit of digest byte 0)"""
+    n = len(keys)
+    judged = np.asarray(pre) == 0
+    _, inv = np_distinct(keys)
+    first = np.full(int(inv.max()) + 1, n, dtype=np.int64)
+    np.minimum.at(first, inv[judged], np.nonzero(judged)[0])
+    rep = np.where(judged, first[inv], NP_NO_REP).astype(np.int64)
+    dense_rows = np.nonzero(judged & (rep == np.arange(n)))[0]
+    rep_bit = (keys[np.where(judged, rep, 0), 0] & 1).astype(bool)
+    return rep, dense_rows, judged & rep_bit
+
+
+KERNEL_SIZES = {"words": [1, 63, 64, 65], "workgroup": [255, 256, 257], "tiles": [1023, 1024, 1025, 2049],
+                "count": [16383, 16384, 16385],      # 64 count workgroups exactly, then the second pass of its loop
+                "65 tiles": [65537], "257 tiles": [262145]}
+KERNEL_KINDS = ["one_key", "one_key_bit0", "mod16", "mirror", "all_distinct", "v_only", "from_byte", "digest_byte", "pre_lowest", "pre_wavefront",
+                "pre_all"]
+KERNEL_SEED = 31      # tests/test_dev_cert_dedup_host.py fails if a table is not roomy: change it then
+
+
+def kernel_input(kind, n, seed=KERNEL_SEED):
+    """→ (keys (n, 117) uint8, pre uint8[n]) of tests/test_gpu_cert_dedup_kernels.py, built without row loops"""
+    rng = np.random.default_rng([seed, n, KERNEL_KINDS.index(kind)])
+    r = np.arange(n)
+    pre = np.zeros(n, dtype=np.uint8)
+    base = rng.integers(0, 256, 117, dtype=np.uint8)
+
+    def pool(count):
+        p = rng.integers(0, 256, (count, 117), dtype=np.uint8)
+        p[:, 0] = (p[:, 0] & 0xFE) | (np.arange(count) & 1)            # every second key's bit is 0: all its copies must read 0
+        return p
+    if kind in ("one_key", "one_key_bit0"):                             # n lanes contend on one word; the representative is row 0
+        base[0] = (base[0] & 0xFE) | (kind == "one_key")
+        keys = np.tile(base, (n, 1))
+    elif kind in ("mod16", "pre_lowest"):                               # every wavefront touches every slot
+        keys = pool(16)[r % 16]
+        if kind == "pre_lowest":
+            pre[:16] = 1 + (r[:16] % 3)                                 # the lowest row of every key: the next one up represents it
+    elif kind in ("mirror", "pre_wavefront"):                           # rows r and n − 1 − r: the upper half's representative lies tiles away
+        keys = pool((n + 1) // 2)[np.minimum(r, n - 1 - r)]
+        if kind == "pre_wavefront":
+            pre[64:128] = 2                                             # (a whole wavefront where there is a second one …
+            if n <= 64:
+                pre[:] = 2                                              # … else the only one)
+    elif kind == "all_distinct":
+        keys = pool(n)
+    elif kind == "pre_all":                                             # dense = 0: nothing gathered, all bits 0
+        keys = pool(16)[r % 16]
+        pre[:] = 1 + (r % 3)
+    elif kind == "v_only":                                              # equal in digest, r, s and From
+        keys = np.tile(base, (n, 1))
+        keys[:, 96] = r % 4
+    elif kind == "from_byte":                                           # equal in digest and signature: the hash does not tell them apart
+        keys = np.tile(base, (n, 1))
+        keys[r, 97 + r % 20] ^= (1 + r % 2).astype(np.uint8)
+    elif kind == "digest_byte":
+        keys = np.tile(base, (n, 1))
+        keys[r, r % 32] ^= (1 + r % 3).astype(np.uint8)
+    else:
+        raise ValueError(kind)
+    return np.ascontiguousarray(keys), pre
+
+
+def kernel_input_run(keys, pre, cap=0):
+    """(longest run of occupied slots in the table the input gets, MAX_PROBES)"""
+    distinct, _ = np_distinct(keys[np.asarray(pre) == 0]) if (np.asarray(pre) == 0).any() else (keys[:0], None)
+    return np_longest_run(distinct, table_slots(len(keys), cap)), MAX_PROBES

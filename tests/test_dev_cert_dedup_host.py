@@ -127,6 +127,80 @@ def test_gpu_test_inputs_have_roomy_tables():
         assert run_len < bound, (label, run_len)
 
 
+def test_numpy_hash_and_run_length_agree_with_the_model():
+    """cert_dedup_model.np_key_hash / np_longest_run (what the inputs of tests/test_gpu_cert_dedup_kernels.py are measured with)
+    against key_hash / longest_run, the run lengths also in tables so full that runs go around the end"""
+    rng = np.random.default_rng(17)
+    keys = rng.integers(0, 256, (300, 117), dtype=np.uint8)
+    keys[:40, :97] = keys[0, :97]                                          # equal digest and signature: one home slot for 40 keys
+    as_bytes = [k.tobytes() for k in keys]
+    assert M.np_key_hash(keys).tolist() == [M.key_hash(k) for k in as_bytes]
+    distinct, inv = M.np_distinct(np.concatenate([keys, keys[::-1]]))
+    assert len(distinct) == 300 and sorted(d.tobytes() for d in distinct) == sorted(as_bytes)
+    assert (distinct[inv] == np.concatenate([keys, keys[::-1]])).all()
+    for count, slots in ((1, 64), (63, 64), (64, 64), (40, 64), (200, 256), (255, 256), (300, 512), (300, 1024), (300, 65536)):
+        for shift in range(4):
+            sub = keys[shift:shift + count]
+            want = M.longest_run({k.tobytes() for k in sub}, slots)
+            assert M.np_longest_run(sub, slots) == want, (count, slots, shift)
+            assert count + 1 != slots or want == count          # one free slot: the run goes around the end unless that slot is the last
+    assert M.np_longest_run(keys[:0], 64) == 0
+
+
+def test_reference_of_the_kernel_inputs_agrees_with_the_model():
+    """np_reference against representatives / scattered_bits on every kind at small sizes"""
+    for kind in M.KERNEL_KINDS:
+        for n in (1, 17, 65, 130, 300):
+            keys, pre = M.kernel_input(kind, n)
+            as_bytes = [k.tobytes() for k in keys]
+            rep, dense_rows, bit = M.np_reference(keys, pre)
+            want_rep, want_dense = M.representatives(as_bytes, pre.tolist())
+            assert [None if x == M.NP_NO_REP else int(x) for x in rep] == want_rep, (kind, n)
+            assert dense_rows.tolist() == want_dense, (kind, n)
+            row_bit = [int(p == 0 and k[0] & 1) for k, p in zip(as_bytes, pre)]
+            assert bit.tolist() == M.scattered_bits(as_bytes, pre.tolist(), row_bit), (kind, n)
+
+
+def test_shapes_of_the_kernel_inputs():
+    """what the kinds of cert_dedup_model.kernel_input are there for"""
+    n = 2049
+    count = lambda kind: len(M.np_distinct(M.kernel_input(kind, n)[0])[0])
+    assert count("one_key") == 1 and count("mod16") == 16 and count("mirror") == 1025 and count("all_distinct") == n
+    assert count("v_only") == 4 and count("from_byte") == 20 and count("digest_byte") == 96
+    for kind, what in (("v_only", slice(96, 97)), ("from_byte", slice(97, 117)), ("digest_byte", slice(0, 32))):
+        keys, _ = M.kernel_input(kind, n)
+        rest = np.delete(keys, np.arange(117)[what], axis=1)
+        assert (rest == rest[0]).all(), kind
+    assert M.kernel_input("one_key", n)[0][0, 0] & 1 == 1 and M.kernel_input("one_key_bit0", n)[0][0, 0] & 1 == 0
+    keys, pre = M.kernel_input("mirror", n)
+    assert (keys == keys[::-1]).all()
+    rep, dense_rows, bit = M.np_reference(keys, pre)
+    assert (rep[1025:] == np.arange(1023, -1, -1)).all() and not bit.all() and bit.any()      # copies of keys whose bit is 0
+    keys, pre = M.kernel_input("pre_lowest", n)
+    rep, dense_rows, _ = M.np_reference(keys, pre)
+    assert pre[:16].all() and dense_rows.tolist() == list(range(16, 32)) and (rep[:16] == M.NP_NO_REP).all()
+    keys, pre = M.kernel_input("pre_wavefront", n)
+    rep, dense_rows, _ = M.np_reference(keys, pre)
+    assert pre[64:128].all() and pre.sum() == 128 and (rep[n - 128:n - 64] == np.arange(n - 128, n - 64)).all()
+    keys, pre = M.kernel_input("pre_all", n)
+    assert pre.all() and len(M.np_reference(keys, pre)[1]) == 0
+
+
+@pytest.mark.parametrize("klass", list(M.KERNEL_SIZES))
+def test_gpu_kernel_test_inputs_have_roomy_tables(klass):
+    """the same condition for the key columns of tests/test_gpu_cert_dedup_kernels.py under the default slot count: no row can
+    give up, so that test demands exact results; a seed that breaks it has to be changed (cert_dedup_model.KERNEL_SEED)"""
+    for n in M.KERNEL_SIZES[klass]:
+        for kind in M.KERNEL_KINDS:
+            run_len, bound = M.kernel_input_run(*M.kernel_input(kind, n))
+            assert run_len < bound, (kind, n, run_len)
+            assert M.table_slots(n) >= 2 * n
+    # the one capped input of that test with no more keys than slots: nothing gives up there either
+    for n in (1025, 16385):
+        run_len, bound = M.kernel_input_run(*M.kernel_input("mod16", n), cap=64)
+        assert run_len <= 16 < bound and M.table_slots(n, 64) == 64
+
+
 def test_counts_the_gpu_test_demands():
     """the model's own numbers for the count inputs: at 40 validators fewer than a quarter of the judged rows are distinct"""
     for n in M.COUNT_SEEDS:
