@@ -146,10 +146,24 @@ struct ibft_ctx {
   int side_tally = 2;
   bool side_pending = false;
   hipStream_t tstream = nullptr;
-  hipEvent_t ev_rec[2] = {nullptr, nullptr};   // pass k's verdict kernels are done (recorded on the main stream)
+  hipEvent_t ev_rec[2] = {nullptr, nullptr};   // pass k's verdict kernels are done (recorded on the stream that carried them)
   DevBuf d_mask_b, d_vidx_b;
   uint32_t mask_dirty_words_b = ~0u;
   uint32_t side_tallies = 0;                   // passes whose tally ran on the side stream (ibft_last_dispatch-style counter)
+  // Pipelined passes on two verdict streams (round 21): consecutive ibft_seals_submit passes put their verdict launch (mask
+  // clearing, warm and cold stage, the event pair of a timed pass) alternately on the main stream and on hstream — idle while
+  // the pipeline runs — so that pass k + 1 may start in the tail of pass k instead of behind it.  The pass's tally follows an
+  // event on the stream that carried its verdict launch, and ev_pass[s] is behind that tally: whoever waits for both ev_pass
+  // (join_side) is behind everything either verdict stream carries.  0 never, 1 wherever the side-stream tally's conditions
+  // hold (A/B, tests), 2 = AUTO (alt_verdict_applies); IBFT_ALT_VERDICT=0|1 pins it.  DESIGN §5.10.
+  int alt_verdict = 2;
+  bool last_on_alt = false;                    // the pass submitted last took hstream
+  // the main stream may carry work since hstream last waited for it that a verdict launch on hstream must not overtake: any
+  // entry point outside the pipeline (ctx_lock), a tally the pipeline left on the main stream, a digest pass behind a swap
+  bool main_touched = true;
+  bool alt_used = false;                       // hstream has carried a verdict launch (what a timing read / a swap must cover)
+  uint32_t alt_passes = 0;                     // passes whose verdict launch took hstream (ibft_pipeline_stats_ex)
+  hipEvent_t ev_cols_read_b = nullptr;         // ev_cols_read's twin on hstream
   uint32_t launched_n = 0;  // rows of the last ibft_seals_launch: what ibft_seals_fetch delivers (a swap may have changed staged_n since)
   DevBuf d_mask, d_vidx, d_tally, d_H;
   DevBuf d_mask_out;        // verdict words after the tally consumed d_mask (what fetch / export read)
@@ -503,19 +517,26 @@ void fill_block_tallies(ibft_tally_t *out_tally, uint32_t nb, uint32_t nr, const
 }
 
 // zero the work mask unless the last tally already left it zero
-int clean_mask(ibft_ctx *c) {
+int clean_mask(ibft_ctx *c, hipStream_t vs) {
   if (c->mask_dirty_words == 0) return IBFT_OK;
-  HIPCHK(c, hipMemsetAsync(c->d_mask.p, 0, (size_t)mask_words(c->row_cap) * 8, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_mask.p, 0, (size_t)mask_words(c->row_cap) * 8, vs));
   c->mask_dirty_words = 0;
   return IBFT_OK;
 }
 
-// The main stream behind every tally the pipeline put on the side stream (a device-side wait; nothing when none is pending).
+// Host-side drain of what the pipeline put beside the main stream: the tally stream and the second verdict stream.
+void drain_pipeline_streams(ibft_ctx *c) {
+  if (c->alt_used) (void)hipStreamSynchronize(c->hstream);
+  if (c->tstream) (void)hipStreamSynchronize(c->tstream);
+}
+// The main stream behind every tally the pipeline put on the side stream, and with it behind every verdict launch the
+// pipeline put on the second verdict stream — each pass's tally follows its verdict launch, and ev_pass follows the tally
+// (a device-side wait; nothing when none is pending).
 int join_side(ibft_ctx *c) {
   if (!c->side_pending) return IBFT_OK;
   HIPCHK(c, hipSetDevice(c->device));
   for (int i = 0; i < 2; i++)
-    if (c->ev_pass[i] && hipStreamWaitEvent(c->stream, c->ev_pass[i], 0) != hipSuccess) HIPCHK(c, hipStreamSynchronize(c->tstream));
+    if (c->ev_pass[i] && hipStreamWaitEvent(c->stream, c->ev_pass[i], 0) != hipSuccess) drain_pipeline_streams(c);
   c->side_pending = false;
   return IBFT_OK;
 }
@@ -525,8 +546,9 @@ int join_side(ibft_ctx *c) {
 struct ctx_lock {
   std::lock_guard<std::mutex> g;
   explicit ctx_lock(ibft_ctx *c) : g(c->mu) {
-    if (c->side_pending && join_side(c) != IBFT_OK) {  // (cannot report from here: drain the side stream the hard way)
-      (void)hipStreamSynchronize(c->tstream);
+    c->main_touched = true;
+    if (c->side_pending && join_side(c) != IBFT_OK) {  // (cannot report from here: drain the side streams the hard way)
+      drain_pipeline_streams(c);
       c->side_pending = false;
     }
   }
@@ -596,49 +618,63 @@ void with_warm_mode(int mode, F &&f) { with_int<ibftk::MODE_SEALS, ibftk::MODE_S
 
 // one verdict kernel over `items` rows (or wavefronts), per_block of them in a workgroup of `threads`
 template <class K>
-void launch_verdict(ibft_ctx *c, const ibftk::recover_args &a, K kernel, uint32_t items, uint32_t per_block, uint32_t threads) {
-  hipLaunchKernelGGL(kernel, dim3((items + per_block - 1) / per_block), dim3(threads), 0, c->stream, a);
+void launch_verdict(hipStream_t vs, const ibftk::recover_args &a, K kernel, uint32_t items, uint32_t per_block, uint32_t threads) {
+  hipLaunchKernelGGL(kernel, dim3((items + per_block - 1) / per_block), dim3(threads), 0, vs, a);
 }
 
 // the warm kernel with G lanes per signature: 1 the LDS-staged lane kernel, 64 one wavefront per signature, groups between
-void launch_warm(ibft_ctx *c, const ibftk::recover_args &a, uint32_t n, int mode, uint32_t G) {
+void launch_warm(hipStream_t vs, const ibftk::recover_args &a, uint32_t n, int mode, uint32_t G) {
   with_warm_mode(mode, [&](auto M) {
     constexpr int MODE = decltype(M)::value;
     if (G == 1)
-      launch_verdict(c, a, ibftk::verify_known_lane_kernel<MODE>, n, ibftk::ROWS_PER_BLOCK, ibftk::ROWS_PER_BLOCK);
+      launch_verdict(vs, a, ibftk::verify_known_lane_kernel<MODE>, n, ibftk::ROWS_PER_BLOCK, ibftk::ROWS_PER_BLOCK);
     else if (G == 64)
-      launch_verdict(c, a, ibftk::verify_known_wave_kernel<MODE>, n, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
+      launch_verdict(vs, a, ibftk::verify_known_wave_kernel<MODE>, n, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
     else
       with_int<32, 16, 8, 4, 2>((int)G, [&](auto GG) {
         constexpr int LANES = decltype(GG)::value;
-        launch_verdict(c, a, ibftk::verify_known_group_kernel<MODE, LANES>, n, 64 / LANES, 64);
+        launch_verdict(vs, a, ibftk::verify_known_group_kernel<MODE, LANES>, n, 64 / LANES, 64);
       });
   });
 }
 
+// lanes per signature of the cold kernel a batch of n rows gets (what launch_cold takes): pinned, or by the batch's size
+uint32_t cold_lanes_for(const ibft_ctx *c, uint32_t n) {
+  if (c->cold_group_force) return c->cold_group_force;
+  if (!c->cold_group_auto) return 1;
+  if ((uint64_t)n <= c->pair_rows_max) return 128;
+  if ((uint64_t)n <= c->wave_rows_max) return 64;
+  if ((uint64_t)n <= c->rows_kernel_max) return 16;
+  if ((uint64_t)n * 8 <= 65536ull) return 8;
+  if ((uint64_t)n * 4 <= 65536ull) return 4;
+  if ((uint64_t)n * 2 <= 65536ull) return 2;
+  return 1;
+}
+// ... and, of the row forms (16 lanes), the one with a helper wavefront per four signatures
+bool rows_pair_for(const ibft_ctx *c, uint32_t n) { return c->rows_pair_force >= 0 ? c->rows_pair_force != 0 : (uint64_t)n <= c->rows_pair_max; }
+
 // the cold kernel with CG lanes per signature: 128 two wavefronts, 64 one, 16 the row forms (four signatures per wavefront, with
 // or without a helper wavefront), 8 / 4 / 2 lane groups, 1 the LDS-staged lane kernel; sets what ibft_last_cold_table reports
-void launch_cold(ibft_ctx *c, const ibftk::recover_args &a, uint32_t n, int mode, uint32_t CG) {
+void launch_cold(ibft_ctx *c, hipStream_t vs, const ibftk::recover_args &a, uint32_t n, int mode, uint32_t CG) {
   with_cold_mode(mode, [&](auto M) {
     constexpr int MODE = decltype(M)::value;
     if (CG == 128) {
-      launch_verdict(c, a, ibftk::ecrecover_wave2_kernel<MODE>, n, ibftk::PAIRS_PER_BLOCK, 128 * ibftk::PAIRS_PER_BLOCK);
+      launch_verdict(vs, a, ibftk::ecrecover_wave2_kernel<MODE>, n, ibftk::PAIRS_PER_BLOCK, 128 * ibftk::PAIRS_PER_BLOCK);
     } else if (CG == 64) {
-      launch_verdict(c, a, ibftk::ecrecover_wave_kernel<MODE>, n, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
+      launch_verdict(vs, a, ibftk::ecrecover_wave_kernel<MODE>, n, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
     } else if (CG == 16) {
       const uint32_t waves = (n + 3) / 4;
-      const bool pair = c->rows_pair_force >= 0 ? c->rows_pair_force != 0 : (uint64_t)n <= c->rows_pair_max;
-      if (pair)
-        launch_verdict(c, a, ibftk::ecrecover_rows_pair_kernel<MODE>, waves, ibftk::ROWS_PAIRS_PER_BLOCK, 128 * ibftk::ROWS_PAIRS_PER_BLOCK);
+      if (rows_pair_for(c, n))
+        launch_verdict(vs, a, ibftk::ecrecover_rows_pair_kernel<MODE>, waves, ibftk::ROWS_PAIRS_PER_BLOCK, 128 * ibftk::ROWS_PAIRS_PER_BLOCK);
       else
-        launch_verdict(c, a, ibftk::ecrecover_rows_kernel<MODE>, waves, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
+        launch_verdict(vs, a, ibftk::ecrecover_rows_kernel<MODE>, waves, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
     } else if (CG > 1) {
       // the lanes' window tables: LDS (no private segment) unless pinned otherwise (IBFT_COLD_TABLE=private: round 4's form, A/B)
       const bool lds_tab = c->cold_table_force != 2;
       with_int<8, 4, 2>((int)CG, [&](auto GG) {
         with_int<ibftk::TAB_LDS, ibftk::TAB_PRIVATE_PREFETCH>(lds_tab ? ibftk::TAB_LDS : ibftk::TAB_PRIVATE_PREFETCH, [&](auto TT) {
           constexpr int LANES = decltype(GG)::value, TAB = decltype(TT)::value;
-          launch_verdict(c, a, ibftk::ecrecover_group_kernel<MODE, LANES, TAB>, n, 64 / LANES, 64);
+          launch_verdict(vs, a, ibftk::ecrecover_group_kernel<MODE, LANES, TAB>, n, 64 / LANES, 64);
         });
       });
       c->last_cold_table = lds_tab ? 1 : 2;
@@ -648,7 +684,7 @@ void launch_cold(ibft_ctx *c, const ibftk::recover_args &a, uint32_t n, int mode
       const uint32_t tab = c->cold_table_force ? c->cold_table_force : ((uint64_t)n <= 65536ull ? 1u : 3u);
       with_int<ibftk::TAB_LDS, ibftk::TAB_PRIVATE_PREFETCH, ibftk::TAB_PRIVATE>(
           tab == 1 ? ibftk::TAB_LDS : tab == 2 ? ibftk::TAB_PRIVATE_PREFETCH : ibftk::TAB_PRIVATE, [&](auto TT) {
-            launch_verdict(c, a, ibftk::ecrecover_lane_kernel<MODE, decltype(TT)::value>, n, ibftk::ROWS_PER_BLOCK, ibftk::ROWS_PER_BLOCK);
+            launch_verdict(vs, a, ibftk::ecrecover_lane_kernel<MODE, decltype(TT)::value>, n, ibftk::ROWS_PER_BLOCK, ibftk::ROWS_PER_BLOCK);
           });
       c->last_cold_table = tab;
     }
@@ -664,7 +700,9 @@ void launch_cold(ibft_ctx *c, const ibftk::recover_args &a, uint32_t n, int mode
 // pinned kernels only (round 6).
 constexpr uint32_t SPLIT_ROWS_MIN = 65536u, SPLIT_ROWS_MAX = 98304u;
 
-int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_it, uint32_t row_base = 0, bool keep_mask = false) {
+int enqueue_recover(ibft_ctx *c, hipStream_t vs, uint32_t n, bool with_pre, int mode, bool time_it, uint32_t row_base = 0,
+                    bool keep_mask = false, hipEvent_t *stop_out = nullptr) {
+  if (stop_out) *stop_out = nullptr;
   if (n == 0) return IBFT_OK;
   if (n > SPLIT_ROWS_MIN && n <= SPLIT_ROWS_MAX && !c->cache_on && c->cold_group_auto && !c->cold_group_force && !c->cold_table_force &&
       row_base % 64 == 0 && c->split_large) {
@@ -672,17 +710,20 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
     if (time_it) {
       int rc = next_events(c, &e0, &e1);
       if (rc) return rc;
-      HIPCHK(c, hipEventRecord(e0, c->stream));
+      HIPCHK(c, hipEventRecord(e0, vs));
     }
     // The work mask is cleared HERE, once, for both launches: the lane kernel of the first part stores whole verdict words and
     // never asks for a clean mask, the kernel of the second part ORs its bits into words it expects to be zero (a dirty or
     // freshly allocated mask gave wrong verdicts in the rows beyond 65 536: caught by the Byzantine parity test, not by the
     // all-valid A/B rounds).
-    int rc = keep_mask ? (int)IBFT_OK : clean_mask(c);
+    int rc = keep_mask ? (int)IBFT_OK : clean_mask(c, vs);
     if (rc) return rc;
-    if ((rc = enqueue_recover(c, SPLIT_ROWS_MIN, with_pre, mode, false, row_base, true))) return rc;
-    if ((rc = enqueue_recover(c, n - SPLIT_ROWS_MIN, with_pre, mode, false, row_base + SPLIT_ROWS_MIN, true))) return rc;
-    if (time_it) HIPCHK(c, hipEventRecord(e1, c->stream));
+    if ((rc = enqueue_recover(c, vs, SPLIT_ROWS_MIN, with_pre, mode, false, row_base, true))) return rc;
+    if ((rc = enqueue_recover(c, vs, n - SPLIT_ROWS_MIN, with_pre, mode, false, row_base + SPLIT_ROWS_MIN, true))) return rc;
+    if (time_it) {
+      HIPCHK(c, hipEventRecord(e1, vs));
+      if (stop_out) *stop_out = e1;
+    }
     c->last_cold_group = 1;   // (what ibft_last_dispatch reports for a split batch: the lane kernel took the bulk)
     c->last_cold_table = 1;
     c->split_launches++;
@@ -699,13 +740,13 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
     uint32_t words;
     ~dirty_on_exit() { c->mask_dirty_words = std::max(c->mask_dirty_words, words); }
   } mark_dirty{c, (uint32_t)mask_words((size_t)row_base + n)};
-  auto clean_mask = [keep_mask](ibft_ctx *cc) { return keep_mask ? (int)IBFT_OK : ::clean_mask(cc); };
+  auto clean_mask = [keep_mask, vs](ibft_ctx *cc) { return keep_mask ? (int)IBFT_OK : ::clean_mask(cc, vs); };
   int rc_clean = 0;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (time_it) {
     int rc = next_events(c, &e0, &e1);
     if (rc) return rc;
-    HIPCHK(c, hipEventRecord(e0, c->stream));
+    HIPCHK(c, hipEventRecord(e0, vs));
   }
   const bool warm = c->cache_on && c->my_built > 0 && mode != ibftk::MODE_EMIT;
   if (warm) {
@@ -720,7 +761,7 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
       while (G < 64 && (uint64_t)n * (G * 2) <= 65536ull) G *= 2;
     }
     if (G > 1 && (rc_clean = clean_mask(c))) return rc_clean;  // (the lane kernel stores whole verdict words)
-    launch_warm(c, a, n, mode, G);
+    launch_warm(vs, a, n, mode, G);
     c->last_group = G;
     HIPCHK(c, hipGetLastError());
     c->warm_passes++;
@@ -729,29 +770,25 @@ int enqueue_recover(ibft_ctx *c, uint32_t n, bool with_pre, int mode, bool time_
   }
   if (warm && c->my_built >= c->n_validators) {
     // every validator has a table: the warm kernel decides every row (non-members included)
-    if (time_it) HIPCHK(c, hipEventRecord(e1, c->stream));
+    if (time_it) {
+      HIPCHK(c, hipEventRecord(e1, vs));
+      if (stop_out) *stop_out = e1;
+    }
     c->last_cold_group = 0;
     return IBFT_OK;
   }
   // cold kernel: lane groups when the batch is too small to fill the chip
-  uint32_t CG = 1;
-  if (c->cold_group_force) {
-    CG = c->cold_group_force;
-  } else if (c->cold_group_auto) {
-    if ((uint64_t)n <= c->pair_rows_max) CG = 128;
-    else if ((uint64_t)n <= c->wave_rows_max) CG = 64;
-    else if ((uint64_t)n <= c->rows_kernel_max) CG = 16;
-    else if ((uint64_t)n * 8 <= 65536ull) CG = 8;
-    else if ((uint64_t)n * 4 <= 65536ull) CG = 4;
-    else if ((uint64_t)n * 2 <= 65536ull) CG = 2;
-  }
+  const uint32_t CG = cold_lanes_for(c, n);
   // every form but the lane kernel ORs its bits into the mask: clean unless a warm kernel in front has already cleaned and
   // written it (the lane kernel merges the bits of decided rows into its whole words instead)
   if (CG > 1 && !warm && (rc_clean = clean_mask(c))) return rc_clean;
-  launch_cold(c, a, n, mode, CG);
+  launch_cold(c, vs, a, n, mode, CG);
   c->last_cold_group = CG;
   HIPCHK(c, hipGetLastError());
-  if (time_it) HIPCHK(c, hipEventRecord(e1, c->stream));
+  if (time_it) {
+    HIPCHK(c, hipEventRecord(e1, vs));
+    if (stop_out) *stop_out = e1;
+  }
   return IBFT_OK;
 }
 
@@ -1615,6 +1652,7 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   c->cold_group_auto = c->kernel != IBFT_KERNEL_LANE;
   if (const char *e = getenv("IBFT_SPLIT_LARGE")) c->split_large = strcmp(e, "0") != 0;
   if (const char *e = getenv("IBFT_SIDE_TALLY")) c->side_tally = strcmp(e, "0") == 0 ? 0 : strcmp(e, "1") == 0 ? 1 : 2;
+  if (const char *e = getenv("IBFT_ALT_VERDICT")) c->alt_verdict = strcmp(e, "0") == 0 ? 0 : strcmp(e, "1") == 0 ? 1 : 2;
   if (const char *e = getenv("IBFT_COLD_TABLE")) {
     if (!strcmp(e, "lds")) c->cold_table_force = 1;
     else if (!strcmp(e, "private")) c->cold_table_force = 2;
@@ -1751,6 +1789,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
   }
   if (c->ev_staged) (void)hipEventDestroy(c->ev_staged);
   if (c->ev_cols_read) (void)hipEventDestroy(c->ev_cols_read);
+  if (c->ev_cols_read_b) (void)hipEventDestroy(c->ev_cols_read_b);
   if (c->dev) {
     {
       std::lock_guard<std::mutex> dlk(c->dev->mu);
@@ -2379,6 +2418,7 @@ int ibft_seals_stage_next(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig
   if ((rc = ensure_spare_columns(c))) return rc;
   // the spare slot was the resident one until the last swap: kernels enqueued before that swap may still read it
   HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_cols_read, 0));
+  if (c->ev_cols_read_b) HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_cols_read_b, 0));
   if (n) {
     HIPCHK(c, hipMemcpyAsync(c->d_hash_nx.p, hash32, n * 32, hipMemcpyHostToDevice, c->cstream));
     HIPCHK(c, hipMemcpyAsync(c->d_sig_nx.p, sig65, n * 65, hipMemcpyHostToDevice, c->cstream));
@@ -2404,6 +2444,13 @@ int ibft_seals_swap(ibft_ctx *c, int wait_for_copy) {
   // other set, once its copy has landed (a device-side wait: the host does not block unless asked to)
   HIPCHK(c, hipEventRecord(c->ev_cols_read, c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_staged, 0));
+  // ... on either verdict stream: hstream's launches so far are readers of the old set too, its next ones of the new
+  if (c->alt_used) {
+    if (!c->ev_cols_read_b) HIPCHK(c, hipEventCreateWithFlags(&c->ev_cols_read_b, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_cols_read_b, c->hstream));
+  }
+  if (c->alt_verdict != 0) HIPCHK(c, hipStreamWaitEvent(c->hstream, c->ev_staged, 0));
+  if (c->seal_digest_mode != 0) c->main_touched = true;  // (apply_seal_digest below rewrites the hash column on the main stream)
   std::swap(c->d_hash, c->d_hash_nx);
   std::swap(c->d_sig, c->d_sig_nx);
   std::swap(c->d_signer, c->d_signer_nx);
@@ -2427,7 +2474,7 @@ static int seals_launch_locked(ibft_ctx *c, uint32_t repeat, int mode = ibftk::M
   for (uint32_t k = 0; k < repeat; k++) {
     int rc;
     const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
-    if ((rc = enqueue_recover(c, c->staged_n, c->staged_pre, mode, time_it))) return rc;
+    if ((rc = enqueue_recover(c, c->stream, c->staged_n, c->staged_pre, mode, time_it))) return rc;
     if ((rc = enqueue_tally(c, c->staged_n))) return rc;
   }
   return IBFT_OK;
@@ -2453,36 +2500,39 @@ static int ensure_result_slots(ibft_ctx *c) {
   return IBFT_OK;
 }
 
-// Pipelined passes over the resident batch: submit enqueues one pass whose results go to one of two host-visible slots,
-// collect waits for the OLDEST submitted pass only (the event behind its tally, not the stream).
-int ibft_seals_submit(ibft_ctx *c) {
-  if (!c) return IBFT_E_INVAL;
-  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself: no join_side)
-  if (!c->have_valset) return IBFT_E_NOVALSET;
-  if (c->pass_issued - c->pass_collected >= 2) {
-    c->last_error = "two passes already in flight: call ibft_seals_collect first";
-    return IBFT_E_INVAL;
-  }
-  if (c->bs_issued != c->bs_collected) {  // the two pipelines share the result slots and the spare columns
-    c->last_error = "block batches in flight: call ibft_block_seals_collect first";
-    return IBFT_E_INVAL;
-  }
-  if (c->learn_rc != IBFT_OK) {  // the table build behind an already delivered pass failed (ibft_seals_collect): say so once
-    const int rc = c->learn_rc;
-    c->learn_rc = IBFT_OK;
-    return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
+// AUTO for the second verdict stream of the pipeline (ibft_seals_submit): only where a side-stream tally may
+// follow (no communicator, no local group, key cache off or every table built — never while keys are being learned: both
+// learn through one device-wide counter and claim slots), and by default only for the kernel forms the A/B showed a gain for.
+static bool alt_verdict_applies(const ibft_ctx *c, uint32_t n) {
+  if (c->alt_verdict == 0 || c->side_tally == 0 || n == 0 || c->comm || c->xlocal) return false;
+  // (my_built as of the last recount: it only grows until the context's own set changes — a key-cache slot is reused only once
+  // no context maps it — so "every table built" still holds when enqueue_recover recounts; d_warm_done exists once and relies on it)
+  if (c->cache_on && c->my_built < c->n_validators) return false;
+  if (c->alt_verdict == 1) return true;
+  // AUTO, measured (profiles/r21_alt_verdict_ab.txt): every warm form, and the cold forms that leave a second workgroup room
+  // on a compute unit — two wavefronts / one wavefront / a DPP row per signature, with or without the helper wavefront; NOT
+  // the lane / group cold kernels, whose window tables fill the LDS (no side-stream tally behind them either)
+  return c->cache_on || cold_lanes_for(c, n) >= 16;
+}
+
+// One pipelined pass over the resident batch, its verdict launch on `vs` (the main stream or hstream)
+static int seals_submit_on(ibft_ctx *c, hipStream_t vs) {
   const uint32_t s = c->pass_issued & 1u;
-  {
-    const int rcs = ensure_result_slots(c);
-    if (rcs) return rcs;
-  }
+  const bool on_alt = vs != c->stream;
   const bool time_it = next_pass_timed(c);
   int rc;
   // The verdict launch writes the CURRENT pair of work mask / validator indices; its last reader was the tally of pass k − 2
-  // (collected, or the two-in-flight check above would have refused) or something the main stream is already behind.
-  if ((rc = enqueue_recover(c, c->staged_n, c->staged_pre, ibftk::MODE_SEALS, time_it))) return rc;
+  // (collected, or the two-in-flight check of the caller would have refused) or something the main stream is already behind —
+  // which hstream has to get behind as well, once, before it carries a verdict launch (main_touched).
+  if (on_alt && c->main_touched) {
+    for (int i = 0; i < 2; i++)
+      if (!c->ev_rec[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_rec[i], hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_rec[s], c->stream));
+    HIPCHK(c, hipStreamWaitEvent(vs, c->ev_rec[s], 0));
+    c->main_touched = false;
+  }
+  hipEvent_t after = nullptr;  // right behind this pass's verdict kernels, on vs: the stop event of a timed pass, when it recorded one
+  if ((rc = enqueue_recover(c, vs, c->staged_n, c->staged_pre, ibftk::MODE_SEALS, time_it, 0, false, &after))) return rc;
   // Side-stream tally: not for a rank of a sharded batch (its exchange follows the tally on the main stream) and not while
   // keys are still being learned (the tally passes the device's learned-key counter on; with every table built nothing moves it)
   const bool all_warm = c->cache_on && c->my_built >= c->n_validators;
@@ -2490,16 +2540,16 @@ int ibft_seals_submit(ibft_ctx *c) {
   // of the LDS, a third of the registers) — NOT behind the lane / group kernels whose tables fill the LDS (see side_tally above)
   const bool side = !c->comm && !c->xlocal && (!c->cache_on || all_warm) &&
                     (c->side_tally == 1 || (c->side_tally == 2 && (all_warm || (!c->cache_on && c->last_cold_group >= 16))));
-  if (side) {
-    if (!c->tstream) HIPCHK(c, hipStreamCreateWithFlags(&c->tstream, hipStreamNonBlocking));
+  if (side || on_alt) {
     for (int i = 0; i < 2; i++)
       if (!c->ev_rec[i]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_rec[i], hipEventDisableTiming));
-    // (a timed pass already has an event right behind its verdict kernels — the stop event of the pair: one marker less)
-    hipEvent_t after = time_it && c->ev_used > 0 ? c->ev[(size_t)(c->ev_used - 1) * 2 + 1] : nullptr;
-    if (!after) {
+    if (!after) {  // (an untimed pass, and an empty one: nothing was recorded behind the verdict kernels)
       after = c->ev_rec[s];
-      HIPCHK(c, hipEventRecord(after, c->stream));
+      HIPCHK(c, hipEventRecord(after, vs));
     }
+  }
+  if (side) {
+    if (!c->tstream) HIPCHK(c, hipStreamCreateWithFlags(&c->tstream, hipStreamNonBlocking));
     HIPCHK(c, hipStreamWaitEvent(c->tstream, after, 0));
     c->tally_slot = (int)s;
     rc = enqueue_tally(c, c->staged_n, nullptr, c->tstream);
@@ -2520,6 +2570,8 @@ int ibft_seals_submit(ibft_ctx *c) {
     c->side_tallies++;
   } else {
     if ((rc = join_side(c))) return rc;   // a main-stream tally shares the sums and verdict words with the side stream's
+    if (on_alt) HIPCHK(c, hipStreamWaitEvent(c->stream, after, 0));  // (IBFT_ALT_VERDICT=1 where the side tally does not apply)
+    c->main_touched = true;  // this tally reads and zeroes the pair the next verdict launch writes
     c->tally_slot = (int)s;
     rc = enqueue_tally(c, c->staged_n);
     c->tally_slot = -1;
@@ -2529,7 +2581,45 @@ int ibft_seals_submit(ibft_ctx *c) {
   c->pass_n[s] = c->staged_n;
   c->launched_n = c->staged_n;  // (an ibft_seals_fetch behind a submit delivers this pass through the copy route)
   c->pass_issued++;
+  c->last_on_alt = on_alt;
+  if (on_alt) c->alt_passes++;
   return IBFT_OK;
+}
+
+// Pipelined passes over the resident batch: submit enqueues one pass whose results go to one of two host-visible slots,
+// collect waits for the OLDEST submitted pass only (the event behind its tally, not the stream).
+int ibft_seals_submit(ibft_ctx *c) {
+  if (!c) return IBFT_E_INVAL;
+  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself: no join_side)
+  if (!c->have_valset) return IBFT_E_NOVALSET;
+  if (c->pass_issued - c->pass_collected >= 2) {
+    c->last_error = "two passes already in flight: call ibft_seals_collect first";
+    return IBFT_E_INVAL;
+  }
+  if (c->bs_issued != c->bs_collected) {  // the two pipelines share the result slots and the spare columns
+    c->last_error = "block batches in flight: call ibft_block_seals_collect first";
+    return IBFT_E_INVAL;
+  }
+  if (c->learn_rc != IBFT_OK) {  // the table build behind an already delivered pass failed (ibft_seals_collect): say so once
+    const int rc = c->learn_rc;
+    c->learn_rc = IBFT_OK;
+    return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  {
+    const int rcs = ensure_result_slots(c);
+    if (rcs) return rcs;
+  }
+  // consecutive passes alternate between the two verdict streams where that applies (alt_verdict_applies): a pass takes the
+  // second one when the pass before it is still in flight and took the main stream
+  const bool alt = c->pass_issued != c->pass_collected && !c->last_on_alt && alt_verdict_applies(c, c->staged_n);
+  const hipStream_t vs = alt ? c->hstream : c->stream;
+  if (alt) c->alt_used = true;
+  const int rc = seals_submit_on(c, vs);
+  // a failure half way leaves nothing in flight that nobody can wait for: what this call put on hstream (and a tally behind it)
+  // has no event a later join could wait for
+  if (rc != IBFT_OK && alt) drain_pipeline_streams(c);
+  return rc;
 }
 
 int ibft_seals_collect(ibft_ctx *c, uint64_t *out_mask, ibft_tally_t *tally) {
@@ -2652,6 +2742,7 @@ int ibft_last_kernel_ms(ibft_ctx *c, float *ms, uint32_t *launches) {
   std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself: no join_side)
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->alt_used) HIPCHK(c, hipStreamSynchronize(c->hstream));  // (a timed pass's event pair is on the stream that carried it)
   float total = 0.f;
   for (uint32_t i = 0; i < c->ev_used; i++) {
     float t = 0.f;
@@ -2716,6 +2807,15 @@ int ibft_pipeline_stats(ibft_ctx *c, uint32_t *side_tallies, uint32_t *split_bat
   std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself: no join_side)
   if (side_tallies) *side_tallies = c->side_tallies;
   if (split_batches) *split_batches = c->split_launches;
+  return IBFT_OK;
+}
+
+int ibft_pipeline_stats_ex(ibft_ctx *c, uint32_t *side_tallies, uint32_t *split_batches, uint32_t *alt_verdicts) {
+  if (!c) return IBFT_E_INVAL;
+  std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself: no join_side)
+  if (side_tallies) *side_tallies = c->side_tallies;
+  if (split_batches) *split_batches = c->split_launches;
+  if (alt_verdicts) *alt_verdicts = c->alt_passes;
   return IBFT_OK;
 }
 
@@ -2816,7 +2916,7 @@ static int messages_launch_locked(ibft_ctx *c, const uint8_t *payload, const uin
   if (converted && (rc = apply_seal_digest(c, half, (uint32_t)n, true))) return rc;
   c->ev_used = 0;
   const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
-  if ((rc = enqueue_recover(c, rows, false, ibftk::MODE_SEALS, time_it))) return rc;
+  if ((rc = enqueue_recover(c, c->stream, rows, false, ibftk::MODE_SEALS, time_it))) return rc;
   ibftk::set_args sa{};
   sa.sender_pre = sender_pre ? d_pre : nullptr;
   sa.valid_pre = valid_pre ? d_pre + half : nullptr;
@@ -3110,6 +3210,7 @@ int ibft_sync(ibft_ctx *c) {
   ctx_lock lk(c);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->alt_used) HIPCHK(c, hipStreamSynchronize(c->hstream));  // (the main stream is behind it already: ctx_lock → join_side)
   if (c->xstream) HIPCHK(c, hipStreamSynchronize(c->xstream));  // exchanges in flight (ibft_seals_exchange)
   if (c->cstream) HIPCHK(c, hipStreamSynchronize(c->cstream));  // a batch on its way into the spare slot (ibft_seals_stage_next)
   if (c->ostream) HIPCHK(c, hipStreamSynchronize(c->ostream));  // digests / emitted columns of streamed block batches on their way out
@@ -3392,7 +3493,7 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
   c->staged_n = sets ? 0 : nr;
   c->staged_pre = pre_flags != nullptr;
   if (nr) {
-    if ((rc = enqueue_recover(c, nr, c->staged_pre, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, next_pass_timed(c)))) return rc;
+    if ((rc = enqueue_recover(c, c->stream, nr, c->staged_pre, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, next_pass_timed(c)))) return rc;
     uint64_t *const records = c->dh_btally ? c->dh_btally : (uint64_t *)c->d_btally.p;
     if ((rc = enqueue_block_tally(c, nb, nr, widest, c->dh_mask, records, sets))) return rc;
     if (bare && (rc = copy_emitted(c, nr, out_signer20, out_vidx))) return rc;
@@ -3599,7 +3700,7 @@ static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, pro
       const bool direct = c->bs_dtally_map[s] != nullptr;
       {
         emit_columns_view ev(c, s, bare);
-        if ((rc = enqueue_recover(c, nr, pre_flags != nullptr, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
+        if ((rc = enqueue_recover(c, c->stream, nr, pre_flags != nullptr, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
         if ((rc = enqueue_block_tally(c, nb, nr, widest, direct ? c->dp_mask[s] : nullptr,
                                       direct ? c->bs_dtally_map[s] : (uint64_t *)c->bs_dtally[s].p, false)))
           return rc;
@@ -3742,7 +3843,7 @@ static int senders_launch_locked(ibft_ctx *c, const uint8_t *payload, const uint
   c->staged_n = (uint32_t)n;
   c->staged_pre = pre_flags != nullptr;
   c->ev_used = 0;
-  if ((rc = enqueue_recover(c, (uint32_t)n, pre_flags != nullptr, ibftk::MODE_SENDERS, true))) return rc;
+  if ((rc = enqueue_recover(c, c->stream, (uint32_t)n, pre_flags != nullptr, ibftk::MODE_SENDERS, true))) return rc;
   return enqueue_tally(c, (uint32_t)n);
 }
 
@@ -3787,7 +3888,7 @@ int ibft_verify_senders_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint3
     HIPCHK(c, hipGetLastError());
   }
   // the digest column now holds keccak256(PayloadNoSig): the sender check is the seal-style pass (mode 0)
-  if ((rc = enqueue_recover(c, (uint32_t)n, true, ibftk::MODE_SEALS, true))) return rc;
+  if ((rc = enqueue_recover(c, c->stream, (uint32_t)n, true, ibftk::MODE_SEALS, true))) return rc;
   if ((rc = enqueue_tally(c, (uint32_t)n))) return rc;
   if (out_rows && n)
     HIPCHK(c, hipMemcpyAsync(out_rows, c->d_wire_rows.p, n * sizeof(ibft_wire_row_t), hipMemcpyDeviceToHost, c->stream));
@@ -3868,7 +3969,7 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
   c->ev_used = 0;
   const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
   // with the pre column: wavefronts whose rows are all dead (the seal rows of PREPAREs, other views, odd encodings) exit at once
-  if ((rc = enqueue_recover(c, half + (uint32_t)n, true, ibftk::MODE_SEALS, time_it))) return rc;
+  if ((rc = enqueue_recover(c, c->stream, half + (uint32_t)n, true, ibftk::MODE_SEALS, time_it))) return rc;
   ibftk::set_args sa{};
   sa.hash32 = converted ? (const uint8_t *)c->d_hash_copy.p : d_hash + 32ull * half;
   sa.hash_len = (const uint8_t *)c->d_hash_len.p;
@@ -4078,7 +4179,7 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
   uint32_t *d_stat = d_total + 4, *dh_stat = c->dh_cert_total ? c->dh_cert_total + 4 : nullptr;  // dense rows, unplaced rows, judged rows (tree, deferred batch)
   volatile uint32_t *h_stat = (volatile uint32_t *)c->h_cert_total + 4;
   if (!dedup) {
-    if ((rc = enqueue_recover(c, rows, true, ibftk::MODE_SEALS, false))) return rc;
+    if ((rc = enqueue_recover(c, c->stream, rows, true, ibftk::MODE_SEALS, false))) return rc;
   } else {
     // The same verdicts from one launch over the distinct (digest, signature, From) of the rows without a pre-flag
     // (cert_dedup_dev.h): table, representatives, their dense batch behind the tree's rows and the deferred batch, its
@@ -4106,7 +4207,7 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
     uint64_t *d_dense_mask = (uint64_t *)c->d_mask.p + dense_base / 64;
     // the dense batch's verdict words: zero whatever an earlier call left there; the tree's own words are stored whole below
     if (dense) HIPCHK(c, hipMemsetAsync(d_dense_mask, 0, (size_t)mask_words(dense) * 8, c->stream));
-    if ((rc = enqueue_recover(c, dense, true, ibftk::MODE_SEALS, false, dense_base, true))) return rc;
+    if ((rc = enqueue_recover(c, c->stream, dense, true, ibftk::MODE_SEALS, false, dense_base, true))) return rc;
     if (t2) HIPCHK(c, hipEventRecord(t2, c->stream));
     ibftk::cert_dedup_scatter_launch(c->stream, (const uint32_t *)d_table, (const uint32_t *)d_dd_slot, (const uint32_t *)d_dd_pos,
                                      (const uint64_t *)d_dense_mask, rows, (uint64_t *)c->d_mask.p);
@@ -4118,7 +4219,7 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_cert_join, 0));
     // the deferred rows' verdict words: zero whatever an earlier call left there (the first launch only vouches for its own words)
     HIPCHK(c, hipMemsetAsync((uint64_t *)c->d_mask.p + region / 64, 0, (size_t)mask_words(carriers) * 8, c->stream));
-    if ((rc = enqueue_recover(c, carriers, true, ibftk::MODE_SEALS, false, region, true))) return rc;
+    if ((rc = enqueue_recover(c, c->stream, carriers, true, ibftk::MODE_SEALS, false, region, true))) return rc;
     hipLaunchKernelGGL(ibftk::cert_scatter_kernel, dim3((carriers + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)d_slot, carriers, region,
                        (uint64_t *)c->d_mask.p);
     HIPCHK(c, hipGetLastError());

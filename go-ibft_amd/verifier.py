@@ -53,7 +53,7 @@ EXPORTS = [
     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
-    "ibft_cert_stats",
+    "ibft_cert_stats", "ibft_pipeline_stats_ex",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
@@ -68,7 +68,7 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
                     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
                     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
-                    "ibft_cert_stats"}
+                    "ibft_cert_stats", "ibft_pipeline_stats_ex"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
 ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
@@ -213,6 +213,8 @@ def load_library() -> C.CDLL:
     L.ibft_seals_rows.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if hasattr(L, "ibft_pipeline_stats"):
         L.ibft_pipeline_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "ibft_pipeline_stats_ex"):
+        L.ibft_pipeline_stats_ex.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 3
     if hasattr(L, "ibft_verify_block_seals"):
         L.ibft_verify_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
     if hasattr(L, "ibft_sign_seals_ex"):
@@ -1041,6 +1043,14 @@ class BatchVerifier:
             return 0, 0
         self._chk(self._L.ibft_pipeline_stats(self._h, C.byref(a), C.byref(b)), "ibft_pipeline_stats")
         return int(a.value), int(b.value)
+
+    def alt_verdict_passes(self) -> int:
+        """ibft_pipeline_stats_ex: submitted passes whose verdict launch took the second verdict stream"""
+        if not hasattr(self._L, "ibft_pipeline_stats_ex"):  # (an older build: it has one verdict stream)
+            return 0
+        a = C.c_uint32(0)
+        self._chk(self._L.ibft_pipeline_stats_ex(self._h, None, None, C.byref(a)), "ibft_pipeline_stats_ex")
+        return int(a.value)
 
     def seals_launch(self, repeat: int = 1) -> None:
         self._chk(self._L.ibft_seals_launch(self._h, repeat), "ibft_seals_launch")

@@ -617,6 +617,14 @@ int ibft_seals_rows(ibft_ctx *ctx, uint32_t *resident_rows, uint32_t *oldest_pas
  * ibft_pipeline_stats: passes whose tally took the side stream, and batches of 65 537 … 98 304 rows that went out as two
  * launches (both since the context was created; either pointer may be NULL).                                             */
 int ibft_pipeline_stats(ibft_ctx *ctx, uint32_t *side_tallies, uint32_t *split_batches);
+/* Round 21: consecutive submitted passes may put their VERDICT launch alternately on the context's main stream and on a
+ * second stream, so that pass k+1 starts in the tail of pass k (whose helper wavefronts have left their registers) instead
+ * of behind it.  Same results, slot for slot; applies only where the side-stream tally applies, and by default only to the
+ * kernel forms it was measured to pay for.  IBFT_ALT_VERDICT=0 keeps every verdict launch on the main
+ * stream, =1 alternates wherever the conditions hold (A/B, tests).  Every other entry point is behind both streams.
+ * ibft_pipeline_stats_ex: ibft_pipeline_stats plus the passes whose verdict launch took the second stream (any pointer may
+ * be NULL).  No new ibft_version(): a build without the symbol simply lacks it.                                          */
+int ibft_pipeline_stats_ex(ibft_ctx *ctx, uint32_t *side_tallies, uint32_t *split_batches, uint32_t *alt_verdicts);
 int ibft_seals_stage_next(ibft_ctx *ctx, const uint8_t *hash32, const uint8_t *sig65,
                           const uint8_t *signer20, const uint8_t *pre_flags, size_t n);
 int ibft_seals_swap(ibft_ctx *ctx, int wait_for_copy);

@@ -1008,6 +1008,16 @@ func (c *Ctx) PipelineStats() (sideTallies, splitBatches int, err error) {
 	return int(a), int(b), nil
 }
 
+// AltVerdictPasses reports how many submitted passes put their verdict launch on the second verdict stream
+// (ibft_pipeline_stats_ex; IBFT_ALT_VERDICT, DESIGN.md §5.10), since the context was created.
+func (c *Ctx) AltVerdictPasses() (int, error) {
+	var a C.uint32_t
+	if err := c.check(C.ibft_pipeline_stats_ex(c.h, nil, nil, &a)); err != nil {
+		return 0, err
+	}
+	return int(a), nil
+}
+
 // SealsRows = rows of the resident seal batch as the library counts them.
 func (c *Ctx) SealsRows() (int, error) {
 	n, _, err := c.sealRows()
