@@ -319,5 +319,19 @@ def build_cert_dedup_harness(force: bool = False) -> str:
     return CERT_DEDUP_HARNESS
 
 
+QTAB_GLV_HARNESS = os.path.join(CSRC, "libdev_qtab_glv_host.so")
+
+
+def build_qtab_glv_harness(force: bool = False) -> str:
+    """TEST-ONLY: the GLV table form of the warm path (verify_dev.h, wave_fe_dev.h) on the CPU; the wavefront form through wave_emul.h."""
+    deps = ["host_qtab_glv_harness.hip", "wave_fe_dev.h", "wave_emul.h", "recover_dev.h", "verify_dev.h",
+            "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h"]
+    if force or _stale(QTAB_GLV_HARNESS, deps):
+        subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
+                               "-o", QTAB_GLV_HARNESS, os.path.join(CSRC, "host_qtab_glv_harness.hip")], cwd=CSRC)
+        _mark(QTAB_GLV_HARNESS, deps)
+    return QTAB_GLV_HARNESS
+
+
 if __name__ == "__main__":
     print(build_lib(verbose=True))

@@ -58,7 +58,11 @@ struct DeviceShared {
   std::mutex mu;  // taken around every launch that reads the pointers below and around every change of them
   int device = 0;
   DevBuf d_gtab;
-  // key cache: slot s holds pub (80 B), state (0 unknown, 1 key known, 2 table built) and a 655 KB table
+  // key cache: slot s holds pub (80 B), state (0 unknown, 1 key known, 2 table built) and a table of slot_bytes: 655 360 B in
+  // the wide form, 174 080 B in the GLV form (verify_dev.h).  The pool is one array of equal slots shared by every context, so
+  // the form is the POOL's: IBFT_QTAB_FORM=wide|glv, read once, when this object is created.
+  int form = ibftk::QTAB_WIDE;
+  size_t slot_bytes = (size_t)ibftk::QTAB_DWORDS_PER_VALIDATOR * 4;
   DevBuf d_pub, d_state, d_qtab, d_learned;  // d_learned: {keys learned, a learned slot} (two u32), bumped by the kernels
   uint32_t cap = 0;                          // slots allocated
   std::unordered_map<KeyAddr, uint32_t, KeyAddrHash> slot_of;
@@ -74,6 +78,16 @@ struct DeviceShared {
 };
 std::mutex g_devices_mu;
 std::map<int, std::weak_ptr<DeviceShared>> g_devices;
+// why the calling thread's last ibft_ctx_create failed, "" after one that succeeded (ibft_last_error(NULL)): per thread, so a
+// create failing on another thread never touches the string a reader holds
+thread_local std::string g_create_error;
+// IBFT_QTAB_FORM → the table form; -1 for a value that is neither
+int qtab_form_from_env() {
+  const char *e = getenv("IBFT_QTAB_FORM");
+  if (!e || !strcmp(e, "wide")) return ibftk::QTAB_WIDE;
+  if (!strcmp(e, "glv")) return ibftk::QTAB_GLV;
+  return -1;
+}
 
 // A FAMILY of validator sets (ibft_set_validator_sets): state of its own next to the context's single set.  The first block
 // of members is what the verdict kernels and the key cache know as "the validator set" — one table over the UNION of the
@@ -615,6 +629,8 @@ template <class F>
 void with_cold_mode(int mode, F &&f) { with_int<ibftk::MODE_SEALS, ibftk::MODE_EMIT, ibftk::MODE_SENDERS>(mode, f); }
 template <class F>
 void with_warm_mode(int mode, F &&f) { with_int<ibftk::MODE_SEALS, ibftk::MODE_SENDERS>(mode, f); }  // (the verify kernels know no MODE_EMIT)
+template <class F>
+void with_qtab_form(int form, F &&f) { with_int<ibftk::QTAB_GLV, ibftk::QTAB_WIDE>(form, f); }
 
 // one verdict kernel over `items` rows (or wavefronts), per_block of them in a workgroup of `threads`
 template <class K>
@@ -623,18 +639,21 @@ void launch_verdict(hipStream_t vs, const ibftk::recover_args &a, K kernel, uint
 }
 
 // the warm kernel with G lanes per signature: 1 the LDS-staged lane kernel, 64 one wavefront per signature, groups between
-void launch_warm(hipStream_t vs, const ibftk::recover_args &a, uint32_t n, int mode, uint32_t G) {
+// form: the pool's table form (DeviceShared::form) — every width exists in both
+void launch_warm(hipStream_t vs, const ibftk::recover_args &a, uint32_t n, int mode, uint32_t G, int form) {
   with_warm_mode(mode, [&](auto M) {
-    constexpr int MODE = decltype(M)::value;
-    if (G == 1)
-      launch_verdict(vs, a, ibftk::verify_known_lane_kernel<MODE>, n, ibftk::ROWS_PER_BLOCK, ibftk::ROWS_PER_BLOCK);
-    else if (G == 64)
-      launch_verdict(vs, a, ibftk::verify_known_wave_kernel<MODE>, n, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
-    else
-      with_int<32, 16, 8, 4, 2>((int)G, [&](auto GG) {
-        constexpr int LANES = decltype(GG)::value;
-        launch_verdict(vs, a, ibftk::verify_known_group_kernel<MODE, LANES>, n, 64 / LANES, 64);
-      });
+    with_qtab_form(form, [&](auto F) {
+      constexpr int MODE = decltype(M)::value, FORM = decltype(F)::value;
+      if (G == 1)
+        launch_verdict(vs, a, ibftk::verify_known_lane_kernel<MODE, FORM>, n, ibftk::ROWS_PER_BLOCK, ibftk::ROWS_PER_BLOCK);
+      else if (G == 64)
+        launch_verdict(vs, a, ibftk::verify_known_wave_kernel<MODE, FORM>, n, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
+      else
+        with_int<32, 16, 8, 4, 2>((int)G, [&](auto GG) {
+          constexpr int LANES = decltype(GG)::value;
+          launch_verdict(vs, a, ibftk::verify_known_group_kernel<MODE, LANES, FORM>, n, 64 / LANES, 64);
+        });
+    });
   });
 }
 
@@ -761,7 +780,7 @@ int enqueue_recover(ibft_ctx *c, hipStream_t vs, uint32_t n, bool with_pre, int 
       while (G < 64 && (uint64_t)n * (G * 2) <= 65536ull) G *= 2;
     }
     if (G > 1 && (rc_clean = clean_mask(c))) return rc_clean;  // (the lane kernel stores whole verdict words)
-    launch_warm(vs, a, n, mode, G);
+    launch_warm(vs, a, n, mode, G, c->dev->form);
     c->last_group = G;
     HIPCHK(c, hipGetLastError());
     c->warm_passes++;
@@ -806,8 +825,12 @@ int build_new_tables(ibft_ctx *c, uint32_t learned_total, uint32_t any_slot) {
   const uint32_t ns = d.used;
   hipLaunchKernelGGL(ibftk::qtab_claim_kernel, dim3((ns + 255) / 256), dim3(256), 0, c->stream, (uint32_t *)d.d_state.p, ns);
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(ibftk::qtab_build_kernel, dim3(((ns + 63) / 64) * ibftk::QTAB_WINDOWS), dim3(64), 0, c->stream,
-                     (const uint32_t *)d.d_pub.p, (const uint32_t *)d.d_state.p, (uint32_t *)d.d_qtab.p, ns);
+  with_qtab_form(d.form, [&](auto F) {
+    constexpr int FORM = decltype(F)::value;
+    constexpr uint32_t WINDOWS = FORM == ibftk::QTAB_GLV ? ibftk::QGLV_WINDOWS : ibftk::QTAB_WINDOWS;
+    hipLaunchKernelGGL(ibftk::qtab_build_kernel<FORM>, dim3(((ns + 63) / 64) * WINDOWS), dim3(64), 0, c->stream,
+                       (const uint32_t *)d.d_pub.p, (const uint32_t *)d.d_state.p, (uint32_t *)d.d_qtab.p, ns);
+  });
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(ibftk::qtab_commit_kernel, dim3((ns + 255) / 256), dim3(256), 0, c->stream, (uint32_t *)d.d_state.p, ns);
   HIPCHK(c, hipGetLastError());
@@ -1626,11 +1649,13 @@ const char *ibft_strerror(int code) {
   }
 }
 
-const char *ibft_last_error(const ibft_ctx *ctx) { return ctx ? ctx->last_error.c_str() : ""; }
+// (NULL: why the calling thread's last ibft_ctx_create failed, where it left a reason — there is no context to ask then)
+const char *ibft_last_error(const ibft_ctx *ctx) { return ctx ? ctx->last_error.c_str() : g_create_error.c_str(); }
 
 int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   if (!out) return IBFT_E_INVAL;
   *out = nullptr;
+  g_create_error.clear();
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return IBFT_E_NODEVICE;
   int dev = cfg ? cfg->device : 0;
@@ -1727,8 +1752,16 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
       std::lock_guard<std::mutex> glk(g_devices_mu);
       c->dev = g_devices[c->device].lock();
       if (!c->dev) {
+        const int form = qtab_form_from_env();
+        if (form < 0) {
+          g_create_error = std::string("IBFT_QTAB_FORM=") + getenv("IBFT_QTAB_FORM") + ": the key cache's table form is wide or glv";
+          rc = IBFT_E_INVAL;
+          break;
+        }
         c->dev = std::make_shared<DeviceShared>();
         c->dev->device = c->device;
+        c->dev->form = form;
+        c->dev->slot_bytes = (form == ibftk::QTAB_GLV ? ibftk::QGLV_DWORDS_PER_VALIDATOR : ibftk::QTAB_DWORDS_PER_VALIDATOR) * 4;
         g_devices[c->device] = c->dev;
       }
     }
@@ -1855,7 +1888,8 @@ static void key_cache_unmap(ibft_ctx *c) {  // c->dev->mu held
 }
 
 // Give every validator of the new set its slot (c->dev->mu held).  Grows the pool when the set needs more slots than it
-// has (within IBFT_QTAB_BUDGET_GB, default 64: 655 KB per slot); validators beyond the budget simply have no slot.
+// has (within IBFT_QTAB_BUDGET_GB, default 64: d.slot_bytes per slot — 655 KB wide, 174 KB GLV); validators beyond the budget
+// simply have no slot.
 static int key_cache_map(ibft_ctx *c, const std::vector<KeyAddr> &vaddr) {
   DeviceShared &d = *c->dev;
   const size_t nv = vaddr.size();
@@ -1888,7 +1922,7 @@ static int key_cache_map(ibft_ctx *c, const std::vector<KeyAddr> &vaddr) {
   }
   size_t budget = 64ull << 30;
   if (const char *e = getenv("IBFT_QTAB_BUDGET_GB")) budget = (size_t)strtoull(e, nullptr, 10) << 30;
-  const size_t slot_bytes = (size_t)ibftk::QTAB_DWORDS_PER_VALIDATOR * 4;
+  const size_t slot_bytes = d.slot_bytes;
   const size_t max_slots = budget / slot_bytes;
   const size_t avail = d.free_slots.size() + (d.cap - d.used);
   if (need_new > avail) {  // grow: the existing tables move to the new buffers (device copies), the pointers change
@@ -2784,6 +2818,14 @@ int ibft_cache_memory(ibft_ctx *c, uint64_t *device_bytes, uint32_t *slots_in_us
   if (slots_in_use) *slots_in_use = d.used - (uint32_t)d.free_slots.size();
   if (slots_allocated) *slots_allocated = d.cap;
   if (contexts_sharing) *contexts_sharing = (uint32_t)c->dev.use_count();
+  return IBFT_OK;
+}
+
+int ibft_cache_form(ibft_ctx *c, uint32_t *form, uint64_t *slot_bytes) {
+  if (!c) return IBFT_E_INVAL;
+  // (set when the device's shared object was created, never changed: no lock)
+  if (form) *form = (uint32_t)c->dev->form;
+  if (slot_bytes) *slot_bytes = (uint64_t)c->dev->slot_bytes;
   return IBFT_OK;
 }
 

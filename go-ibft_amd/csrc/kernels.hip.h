@@ -445,7 +445,7 @@ struct recover_args {
   uint32_t *pub;            // n_validators × 20 dwords: recovered public keys (affine, 10×26 limbs)
   uint32_t *pub_state;      // n_validators: 0 unknown, 1 key known (claimed by CAS), 2 table built
   uint32_t *learned;        // counter of keys learned (host reads it with the tally)
-  const uint32_t *qtab;     // n_validators × 32 × 256 × 20 dwords
+  const uint32_t *qtab;     // n_validators × 32 × 256 × 20 dwords (wide form) or × 2 176 × 20 (GLV form: verify_dev.h)
   uint8_t *warm_done;       // n: 1 = the warm kernel already produced this row's verdict
   uint32_t dummy_validator; // a SLOT whose table is built (operand for lanes with no work)
   // The key tables belong to the DEVICE, not to a context (every context of a device shares them, a validator keeps its
@@ -702,7 +702,7 @@ __global__ void __launch_bounds__(ROWS_PER_BLOCK) ecrecover_lane_kernel(recover_
 }
 
 // ---- warm path, one lane per signature ----------------------------------------------------
-template <int MODE>
+template <int MODE, int FORM = QTAB_WIDE>
 __global__ void __launch_bounds__(ROWS_PER_BLOCK) verify_known_lane_kernel(recover_args a) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[ROWS_PER_BLOCK * (65 + 32 + 20)];
   row_regs q = stage_rows<MODE>(a, lds);
@@ -712,7 +712,7 @@ __global__ void __launch_bounds__(ROWS_PER_BLOCK) verify_known_lane_kernel(recov
   bool ok = false;
   if (__any(crypto ? 1 : 0)) {  // wave-uniform: every lane runs the arithmetic, idle ones on a dummy table
     const uint32_t tv = crypto ? (uint32_t)w.sl : a.dummy_validator;
-    ok = verify_known(a.gtab, a.qtab + QTAB_DWORDS_PER_VALIDATOR * tv, q.z, q.r, q.s, q.v, a.flags) && crypto;
+    ok = verify_known<FORM>(a.gtab, a.qtab + qtab_slot_dwords<FORM>() * tv, q.z, q.r, q.s, q.v, a.flags) && crypto;
   }
   if (q.live) warm_mark(a, q.row, w);
   uint64_t bal = __ballot(ok);
@@ -738,7 +738,7 @@ __device__ __forceinline__ jac shfl_xor_jac(const jac &p, int off) {
   return r;
 }
 
-template <int MODE, int G>
+template <int MODE, int G, int FORM = QTAB_WIDE>
 __global__ void __launch_bounds__(64) verify_known_group_kernel(recover_args a) {
   constexpr int ROWS = 64 / G;                    // signatures per wavefront
   constexpr int POINTS = QTAB_WINDOWS + GTAB_WINDOWS;
@@ -794,8 +794,48 @@ __global__ void __launch_bounds__(64) verify_known_group_kernel(recover_args a) 
   } else {
     verify_scalars(z, r, s, u1, u2);
   }
-  const uint32_t *qt = a.qtab + QTAB_DWORDS_PER_VALIDATOR * (crypto ? (uint32_t)sl : a.dummy_validator);
+  const uint32_t *qt = a.qtab + qtab_slot_dwords<FORM>() * (crypto ? (uint32_t)sl : a.dummy_validator);
   jac acc = secp::jac_inf();
+  constexpr int STEPS = (POINTS + G - 1) / G;  // wave-uniform trip count
+  if constexpr (FORM == QTAB_GLV) {
+    // The GLV form (verify_dev.h): points 0…15 the k1 half, 16…31 the k2 half (the same entries, x·β), 32…47 G.  Same deal
+    // (point it·G + sub), same pipelining by one.  A step's lanes may be of different classes, so the β product is formed by
+    // every lane and selected — but only on steps where some lane of the wavefront needs it (wave_any: a uniform branch).
+    const secp::glv_split sp = secp::sc_split_lambda(u2);
+    const u256 b1 = qglv_bias(sp.k1), b2 = qglv_bias(sp.k2);
+    const secp::fe beta = secp::GLV_CONST(1);
+    auto point_of = [&](int it, qglv_operand &op) -> const uint32_t * {
+      const int p = it * G + (int)sub;
+      const bool has = p < POINTS;
+      const int pp = has ? p : 0;
+      if (pp < 2 * QGLV_WINDOWS) {
+        op = qglv_point(pp, b1, b2, sp.neg1, sp.neg2);
+        op.nz = op.nz && has;
+        return qt + (size_t)GTAB_ENTRY_DWORDS * op.index;
+      }
+      const int w = pp - 2 * QGLV_WINDOWS;
+      const uint32_t dgt = (u1.v[(w * GTAB_BITS) >> 5] >> ((w * GTAB_BITS) & 31)) & (uint32_t)(GTAB_ENTRIES - 1);
+      op.index = dgt;
+      op.nz = dgt != 0;
+      op.beta = false;
+      op.neg = false;
+      return a.gtab + (size_t)GTAB_ENTRY_DWORDS * ((size_t)w * GTAB_ENTRIES + dgt);
+    };
+    qglv_operand op;
+    aff cur = load_affine(point_of(0, op));
+#pragma unroll 1
+    for (int it = 0; it < STEPS; it++) {
+      qglv_operand on;
+      const aff nxt = load_affine(point_of(it + 1 < STEPS ? it + 1 : it, on));  // (the last step re-reads its own entry)
+      secp::fe bx = cur.x;
+      if (secp::wave_any(op.beta)) bx = secp::fe_mul(cur.x, beta);
+      const aff q = qglv_apply(cur, bx, op.beta, op.neg);
+      jac sum = secp::jac_add_aff_t<INL_MADD>(acc, q);
+      acc = secp::jac_select(op.nz, sum, acc);
+      cur = nxt;
+      op = on;
+    }
+  } else {
   // this lane's table point of step `it` (point it·G + sub of the 48): where it lies, its digit, whether it exists
   auto point_of = [&](int it, uint32_t &dgt, bool &has) -> const uint32_t * {
     const int p = it * G + (int)sub;
@@ -811,7 +851,6 @@ __global__ void __launch_bounds__(64) verify_known_group_kernel(recover_args a) 
   };
   // Round 6: software-pipelined by one — the entry of step it + 1 is asked for before the addition of step it runs (a
   // dependent read of a validator's table, far beyond any cache, used to open every step: ≈ 2 µs in front of each addition)
-  constexpr int STEPS = (POINTS + G - 1) / G;  // wave-uniform trip count
   uint32_t dgt;
   bool has;
   aff cur = load_affine(point_of(0, dgt, has));
@@ -825,6 +864,7 @@ __global__ void __launch_bounds__(64) verify_known_group_kernel(recover_args a) 
     cur = nxt;
     dgt = dn;
     has = hasn;
+  }
   }
 #pragma unroll 1
   for (int off = G / 2; off >= 1; off >>= 1) {
@@ -859,7 +899,7 @@ __global__ void __launch_bounds__(64) verify_known_group_kernel(recover_args a) 
 constexpr int WAVE_KERNEL_WAVES = 4;
 // ---- warm path, one wavefront per signature with the limbs spread over lanes (wave_fe_dev.h) ----
 // Replaces verify_known_group_kernel<·,64>: same prologue, the point sum runs in the row layout.
-template <int MODE>
+template <int MODE, int FORM = QTAB_WIDE>
 __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) verify_known_wave_kernel(recover_args a) {
   const uint32_t row = blockIdx.x * WAVE_KERNEL_WAVES + (threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63u;
@@ -873,7 +913,7 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) verify_known_wave_kern
   const warm_row w = warm_decide(a, pre, want);
   if (lane == 0) warm_mark(a, row, w);
   if (pre || !w.have_table) return;  // wave-uniform: the wavefront holds one row
-  const bool ok = wv::verify_known_wave(a.gtab, a.qtab + QTAB_DWORDS_PER_VALIDATOR * (uint32_t)w.sl, z, r, s, v, a.flags);
+  const bool ok = wv::verify_known_wave<FORM>(a.gtab, a.qtab + qtab_slot_dwords<FORM>() * (uint32_t)w.sl, z, r, s, v, a.flags);
   if (lane == 0 && ok) verdict_or(a, row);
 }
 
@@ -1274,15 +1314,17 @@ __global__ void qtab_claim_kernel(uint32_t *__restrict__ pub_state, uint32_t n_s
   if (v < n_slots && __hip_atomic_load(pub_state + v, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == KEY_KNOWN)
     pub_state[v] = KEY_BUILDING;  // (the acquire pairs with learn_key's release: `pub` of this slot is complete)
 }
+template <int FORM = QTAB_WIDE>
 __global__ void __launch_bounds__(64) qtab_build_kernel(const uint32_t *__restrict__ pub, const uint32_t *__restrict__ pub_state,
                                                         uint32_t *__restrict__ qtab, uint32_t n_validators) {
-  const uint32_t w = blockIdx.x % QTAB_WINDOWS;
-  const uint32_t v = (blockIdx.x / QTAB_WINDOWS) * 64 + threadIdx.x;
+  constexpr uint32_t WINDOWS = FORM == QTAB_GLV ? QGLV_WINDOWS : QTAB_WINDOWS;  // (the grid: ⌈slots / 64⌉ × WINDOWS workgroups)
+  const uint32_t w = blockIdx.x % WINDOWS;
+  const uint32_t v = (blockIdx.x / WINDOWS) * 64 + threadIdx.x;
   const bool work = v < n_validators && pub_state[v] == KEY_BUILDING;
   if (!__any(work ? 1 : 0)) return;
   aff Q = work ? load_affine(pub + (size_t)GTAB_ENTRY_DWORDS * v) : secp::generator();
-  uint32_t *out = qtab + QTAB_DWORDS_PER_VALIDATOR * (work ? v : 0u) + (size_t)GTAB_ENTRY_DWORDS * QTAB_ENTRIES * w;
-  qtab_build_window(Q, (int)w, out, work);
+  uint32_t *out = qtab + qtab_slot_dwords<FORM>() * (work ? v : 0u) + qtab_window_dwords<FORM>((int)w);
+  qtab_build_window<FORM>(Q, (int)w, out, work);
 }
 __global__ void qtab_commit_kernel(uint32_t *__restrict__ pub_state, uint32_t n_validators) {
   uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;

@@ -1547,6 +1547,9 @@ WVF void recover_helper_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
 // R′.x = r and parity(R′.y) = v.  The 32 + GTAB_WINDOWS table points are dealt to the four rows;
 // a row adds its share with mixed additions (11 multiplications of ≈72 instructions for the four
 // rows together, against 11 × 224 per lane in the lane layout), two row-xor additions join them.
+// FORM (ibftk::QTAB_WIDE / QTAB_GLV, verify_dev.h): in the GLV form the points are dealt so that a step is uniform in its
+// class — steps 0–3 the k1 half, 4–7 the k2 half, 8–11 G —, so the β multiplication is one wfe_mul on four steps.
+template <int FORM = 0>
 WVF bool verify_known_wave(const uint32_t *__restrict__ gtab, const uint32_t *__restrict__ qtab_v, const u256 &z_raw,
                            const u256 &r, const u256 &s, uint32_t v, uint32_t flags) {
   const wk k = wk_init();
@@ -1558,6 +1561,41 @@ WVF bool verify_known_wave(const uint32_t *__restrict__ gtab, const uint32_t *__
   constexpr int POINTS = ibftk::QTAB_WINDOWS + ibftk::GTAB_WINDOWS;
   static_assert(POINTS % 4 == 0, "points are dealt to four rows");
   wjac acc = wjac_inf();
+  if constexpr (FORM == ibftk::QTAB_GLV) {
+    static_assert(ibftk::QGLV_WINDOWS % 4 == 0 && 2 * ibftk::QGLV_WINDOWS + ibftk::GTAB_WINDOWS == POINTS, "four steps per class");
+    const secp::glv_split sp = secp::sc_split_lambda(u2);
+    const u256 b1 = ibftk::qglv_bias(sp.k1), b2 = ibftk::qglv_bias(sp.k2);
+    const uint32_t beta = scatter(secp::GLV_CONST(1), k);
+    // this row's table point of step `it`: point 4·it + row of the order k1 half, k2 half, G
+    auto point_of = [&](int it, ibftk::qglv_operand &op) -> const uint32_t * {
+      const int p = 4 * it + (int)k.row;
+      if (p < 2 * ibftk::QGLV_WINDOWS) {
+        op = ibftk::qglv_point(p, b1, b2, sp.neg1, sp.neg2);
+        return qtab_v + (size_t)ibftk::GTAB_ENTRY_DWORDS * op.index;
+      }
+      const int w = p - 2 * ibftk::QGLV_WINDOWS;
+      const int bit = w * ibftk::GTAB_BITS;
+      const uint32_t dgt = (u1.v[bit >> 5] >> (bit & 31)) & (uint32_t)(ibftk::GTAB_ENTRIES - 1);
+      op.index = dgt;
+      op.nz = dgt != 0;
+      op.beta = false;
+      op.neg = false;
+      return gtab + (size_t)ibftk::GTAB_ENTRY_DWORDS * ((size_t)w * ibftk::GTAB_ENTRIES + dgt);
+    };
+    ibftk::qglv_operand op;
+    waff cur = load_waff(point_of(0, op), k);
+#pragma unroll 1
+    for (int it = 0; it < POINTS / 4; it++) {
+      ibftk::qglv_operand on;
+      const waff nxt = load_waff(point_of(it + 1 < POINTS / 4 ? it + 1 : it, on), k);  // (the last step re-reads its own point)
+      if (it >= ibftk::QGLV_WINDOWS / 4 && it < 2 * ibftk::QGLV_WINDOWS / 4) cur.x = wfe_mul(cur.x, beta, k);  // (uniform: the step's class)
+      cur.y = op.neg ? wfe_neg1(cur.y, k) : cur.y;  // magnitude ≤ 2
+      const wjac sum = wjac_add_aff<true>(acc, cur, k);
+      acc = wjac_select(op.nz, sum, acc);
+      cur = nxt;
+      op = on;
+    }
+  } else {
   // this row's table point of step `it` (point 4·it + row: rows interleave, so every row mixes Q- and G-table points)
   auto point_of = [&](int it, uint32_t &dgt) -> const uint32_t * {
     const int p = 4 * it + (int)k.row;
@@ -1582,6 +1620,7 @@ WVF bool verify_known_wave(const uint32_t *__restrict__ gtab, const uint32_t *__
     acc = wjac_select(dgt != 0, sum, acc);
     cur = nxt;
     dgt = dn;
+  }
   }
   acc = wjac_add(acc, wjac_lane_xor(acc, 16), k);
   acc = wjac_add(acc, wjac_lane_xor(acc, 32), k);

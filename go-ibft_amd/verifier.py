@@ -53,7 +53,7 @@ EXPORTS = [
     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
-    "ibft_cert_stats", "ibft_pipeline_stats_ex",
+    "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
@@ -68,7 +68,7 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
                     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
                     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
-                    "ibft_cert_stats", "ibft_pipeline_stats_ex"}
+                    "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
 ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
@@ -291,6 +291,8 @@ def load_library() -> C.CDLL:
     L.ibft_group_is_local.argtypes = [vp]
     L.ibft_keccak256.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]
     L.ibft_cache_memory.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "ibft_cache_form"):
+        L.ibft_cache_form.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     for name in EXPORTS:  # fail loudly on a stale build that lacks a declared symbol
         if name not in later:
             getattr(L, name)
@@ -1216,6 +1218,15 @@ class BatchVerifier:
         b, u, a, k = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint32()
         self._chk(self._L.ibft_cache_memory(self._h, C.byref(b), C.byref(u), C.byref(a), C.byref(k)), "ibft_cache_memory")
         return b.value, u.value, a.value, k.value
+
+    def cache_form(self):
+        """ibft_cache_form: (table form of the device's key-cache pool — 0 wide, 1 glv: IBFT_QTAB_FORM, read when the first
+        context of the device is created —, bytes of one slot's table)"""
+        if not hasattr(self._L, "ibft_cache_form"):
+            raise GpuUnavailable("this build of libibftgpu.so has no ibft_cache_form — rebuild")
+        f, b = C.c_uint32(), C.c_uint64()
+        self._chk(self._L.ibft_cache_form(self._h, C.byref(f), C.byref(b)), "ibft_cache_form")
+        return f.value, b.value
 
     def last_dispatch(self):
         """(cold lanes per signature, warm lanes per signature) of the last verdict pass."""

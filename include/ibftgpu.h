@@ -171,7 +171,9 @@ typedef struct {
 
 int ibft_version(void);
 const char *ibft_strerror(int code);
-/* last HIP error string seen by this context (thread-unsafe diagnostic) */
+/* last HIP error string seen by this context (thread-unsafe diagnostic).  ctx = NULL: why the CALLING THREAD's last
+ * ibft_ctx_create failed, where the library has a reason to give (IBFT_QTAB_FORM with a value other than wide or glv), else
+ * "" — also after a create that succeeded; the string is the thread's own and stays valid until its next ibft_ctx_create. */
 const char *ibft_last_error(const ibft_ctx *ctx);
 
 int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out);
@@ -663,9 +665,22 @@ int ibft_cache_stats(ibft_ctx *ctx, uint32_t *tables, uint32_t *warm_passes, uin
  * IBFT_QTAB_BUDGET_GB / 655 360 slots: validators of a set beyond that have no slot and are served by the recover path for
  * good (verdicts unchanged; ibft_cache_stats never reports every table built for such a set), and a budget of 0 turns the
  * cache off without an error.  This reports the shared object of ctx's device: bytes it holds, slots in use / allocated, and
- * how many contexts share it (tests/test_gpu_key_cache_lifecycle.py pins all of this in fresh processes).            */
+ * how many contexts share it (tests/test_gpu_key_cache_lifecycle.py pins all of this in fresh processes).
+ *
+ * THE TABLE FORM belongs to the pool, so it is the device's and not a context's: the environment variable
+ * IBFT_QTAB_FORM=wide|glv is read when the FIRST context of a device is created (the device's shared object lives as long as
+ * one context of the device does); unset means wide; any other value makes that ibft_ctx_create fail with IBFT_E_INVAL, and
+ * ibft_last_error(NULL), asked on the same thread, names the variable.  wide: 32 windows × 256 points over u2, 655 360 B per validator.  glv: u2 is split
+ * with the curve's endomorphism and recoded in signed digits, 16 windows (15 × 128 points and one of 256) serve both halves,
+ * 174 080 B per validator — 3.76 times as many slots per IBFT_QTAB_BUDGET_GB (6 168 instead of 1 638 per GiB), the pool, its
+ * growth and ibft_cache_memory's bytes scale with it, and a table build writes that much less.  What the form does NOT change:
+ * every verdict, tally and error code of every entry point, the slot state machine, which kernel width a batch gets
+ * (ibft_last_dispatch), the 84 MB table of G; a signature sums 48 table points in both.                               */
 int ibft_cache_memory(ibft_ctx *ctx, uint64_t *device_bytes, uint32_t *slots_in_use, uint32_t *slots_allocated,
                       uint32_t *contexts_sharing);
+/* The pool's table form: 0 = wide, 1 = glv, and the bytes of one slot's table (655 360 / 174 080).  Any out pointer may be NULL;
+ * IBFT_E_INVAL for a NULL ctx.                                                                                           */
+int ibft_cache_form(ibft_ctx *ctx, uint32_t *form, uint64_t *slot_bytes);
 /* Lanes per signature used by the last verdict pass: cold kernel (1 = ecrecover_lane_kernel,
  * 2/4/8 = ecrecover_group_kernel, 16 = ecrecover_rows_kernel, 64 = ecrecover_wave_kernel, 128 = ecrecover_wave2_kernel)
  * and warm kernel (0 = none ran, 1 = lane, 2..64 = group).                                        */

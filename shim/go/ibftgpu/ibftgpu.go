@@ -912,6 +912,16 @@ func (c *Ctx) CertStats() (rows, judged, verdict, unplaced uint32, err error) {
 	return uint32(r), uint32(j), uint32(v), uint32(u), c.check(rc)
 }
 
+// CacheForm reports the table form of the device's key-cache pool (ibft_cache_form): 0 = wide (655 360 B per validator),
+// 1 = glv (174 080 B per validator), and the bytes of one slot's table.  The form is the pool's, chosen by the environment
+// variable IBFT_QTAB_FORM=wide|glv when the first context of the device is created; it changes no verdict.
+func (c *Ctx) CacheForm() (form uint32, slotBytes uint64, err error) {
+	var f C.uint32_t
+	var b C.uint64_t
+	rc := C.ibft_cache_form(c.h, &f, &b)
+	return uint32(f), uint64(b), c.check(rc)
+}
+
 // PinnedBytes returns n bytes of page-locked memory (ibft_pinned_alloc) as a Go slice: column buffers the
 // flatten step writes into once and reuses every round.  When every column of a call lies in such buffers the
 // library reads them with one gather launch instead of one copy command per column.  C memory: invisible to
