@@ -233,6 +233,15 @@ struct ibft_ctx {
   int32_t *bs_h_vidx[2] = {nullptr, nullptr};
   size_t bs_h_hash_blocks[2] = {0, 0}, bs_h_rows[2] = {0, 0}, bs_h_vidx_rows[2] = {0, 0};
   uint32_t bs_kind[2] = {0, 0};
+  // A batch judged under a family of sets (the _sets submits, IBFT_BATCH_SETS in bs_kind): its block_set column lies in a
+  // buffer of the SLOT — the copy of batch k + 1 must not overwrite what the tally of batch k reads, so fam.d_bset will not
+  // do — and the quorum words its collect hands out are kept on the host, so that what the collect DELIVERS never comes from
+  // c->fam (the family may have been replaced since; only the table build behind the delivery counts against the union
+  // installed then): bs_setq[s] holds the two low quorum words per BLOCK when bs_setidx[s] is empty, per SET of the family
+  // of the submit when bs_setidx[s] holds the blocks' set indices — whichever of the two is smaller for the batch.
+  DevBuf bs_bset[2];
+  std::vector<uint64_t> bs_setq[2];
+  std::vector<uint32_t> bs_setidx[2];
   bool bs_has_out[2] = {false, false};  // the batch put copies on ostream: its collect waits for ev_bs_out too
   hipStream_t ostream = nullptr;
   hipEvent_t ev_bs_dig[2] = {nullptr, nullptr}, ev_bs_out[2] = {nullptr, nullptr};
@@ -1807,7 +1816,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
                     &c->d_phash, &c->bs_praw[0], &c->bs_praw[1], &c->bs_proff[0], &c->bs_proff[1], &c->bs_pround[0], &c->bs_pround[1],
                     &c->bs_phash[0], &c->bs_phash[1], &c->bs_signer[0], &c->bs_signer[1], &c->bs_vidx[0], &c->bs_vidx[1], &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
-                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
+                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->bs_bset[0], &c->bs_bset[1], &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
     release(*b);
   if (c->h_phash) (void)hipHostFree(c->h_phash);
   if (c->tstream) {
@@ -2221,6 +2230,10 @@ static int set_validator_sets_impl(ibft_ctx *c, size_t n_sets, const uint32_t *s
   if (!(rc = upload(c, nf.d_vtab, tab.data(), tab.size() * 4)) && !(rc = upload(c, nf.d_setidx, setidx.data(), setidx.size() * 4)) &&
       !(rc = upload(c, nf.d_meta, meta.data(), meta.size() * 4)) && !(rc = upload(c, nf.d_power, pwv.data(), pwv.size() * 8)) &&
       !(rc = upload(c, nf.d_quorum, quorum.data(), quorum.size() * 8)) && !(rc = ensure(c, nf.d_seen, seen_bytes))) {
+    // The wait for the MAIN stream is more than the end of these uploads: the kernels of streamed _sets batches in flight
+    // read the old family's tables and the key-cache slots of its union, and every one of them runs on the main stream
+    // (block_seals_submit_impl).  The release of the old buffers and key_cache_map below — which drops or remaps the old
+    // union's references — rely on it.
     if (hipMemsetAsync(nf.d_seen.p, 0, nf.d_seen.cap, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
       c->last_error = "ibft_set_validator_sets: upload failed";
       rc = IBFT_E_HIP;
@@ -2231,7 +2244,8 @@ static int set_validator_sets_impl(ibft_ctx *c, size_t n_sets, const uint32_t *s
     for (DevBuf *b : fresh) release(*b);
     return rc;
   }
-  // the new family is whole: the old one goes (no kernel reads it — every _sets call has synchronised before it returned)
+  // The new family is whole: the old one goes.  Streamed _sets batches may be in flight (their results sit in their slots
+  // and stay collectable: what a collect delivers is the slot's, nothing of c->fam); the wait above is what lets it go.
   ValFamily &f = c->fam;
   std::swap(f.d_vtab, nf.d_vtab);
   std::swap(f.d_setidx, nf.d_setidx);
@@ -2289,7 +2303,8 @@ int ibft_validator_sets_info(ibft_ctx *c, uint32_t *n_sets, uint32_t *union_size
   ctx_lock lk(c);
   if (n_sets) *n_sets = c->fam.have ? c->fam.n_sets : 0;
   if (union_size) *union_size = c->fam.have ? c->fam.n_union : 0;
-  if (device_bytes) *device_bytes = c->fam.have ? c->fam.device_bytes + c->fam.d_bset.cap : 0;  // + the calls' block_set column
+  // + the calls' block_set column, and those of the two slots of the streamed _sets submits
+  if (device_bytes) *device_bytes = c->fam.have ? c->fam.device_bytes + c->fam.d_bset.cap + c->bs_bset[0].cap + c->bs_bset[1].cap : 0;
   return IBFT_OK;
 }
 
@@ -3297,8 +3312,11 @@ int ibft_recover_seals(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65,
 // The segmented tally of a block batch over the resident work mask / validator indices and the offsets in d_boff, on the main
 // stream.  Work mask, the bitmap and the ticket word in d_acc exist once per context: two batches in flight
 // (ibft_block_seals_submit) take turns at them in main-stream order.  sets: under a family of validator sets (the block's set
-// in fam.d_bset) — powers, quorums and bitmap are the family's, the LARGEST set in the place of the one set's size.
-static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t widest, uint64_t *host_mask, uint64_t *out, bool sets) {
+// in d_block_set: fam.d_bset, or the column of a streamed batch's slot) — powers, quorums and bitmap are the family's, the
+// LARGEST set in the place of the one set's size.  fam.d_seen exists once: sets tallies stay on the MAIN stream, where two
+// batches in flight take turns at it; the side-tally rule of the seal pipeline (enqueue_tally's `on`) does not apply to them.
+static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t widest, uint64_t *host_mask, uint64_t *out, bool sets,
+                               const void *d_block_set = nullptr) {
   if (c->read_pending) {  // a consumer stream is still copying the previous results (ibft_seals_export_on / exchange)
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
     c->read_pending = false;
@@ -3320,7 +3338,7 @@ static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t w
   t.acc = (uint64_t *)c->d_acc.p;
   t.quorum = (const uint64_t *)(sets ? f.d_quorum.p : c->d_quorum.p);
   t.out = out;
-  t.block_set = (const uint32_t *)f.d_bset.p;  // (these three: read by the sets form alone)
+  t.block_set = (const uint32_t *)(d_block_set ? d_block_set : f.d_bset.p);  // (these three: read by the sets form alone)
   t.setidx = (const int32_t *)f.d_setidx.p;
   t.set_meta = (const uint2 *)f.d_meta.p;
   const dim3 grid(t.lds_bitmap ? std::min(nb, ibftk::BTALLY_MAX_GRID) : 1u);
@@ -3575,6 +3593,24 @@ int ibft_recover_block_seals_sets(ibft_ctx *c, const uint8_t *block_hash32, cons
   return block_seals_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally,
                           true, block_set);
 }
+// … and from the proposals: ibft_proposal_hashes + the call above in one (block_seals_impl's checks: the _sets call's in its
+// order, then those of the proposals' arguments)
+int ibft_verify_block_seals_sets_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                     const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
+                                     const uint8_t *signer20, const uint8_t *pre_flags, uint8_t *out_block_hash32, uint64_t *out_mask,
+                                     ibft_tally_t *out_tally) {
+  proposal_batch p{raw, raw_off, round, out_block_hash32};
+  return block_seals_impl(c, nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally, true,
+                          block_set);
+}
+int ibft_recover_block_seals_sets_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                      const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
+                                      const uint8_t *pre_flags, uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx,
+                                      uint64_t *out_mask, ibft_tally_t *out_tally) {
+  proposal_batch p{raw, raw_off, round, out_block_hash32};
+  return block_seals_impl(c, nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally, true,
+                          block_set);
+}
 
 // The refusals every streamed block submit makes once its arguments are in order (c->mu held); a refused call takes no slot.
 static int block_pipeline_refusal(ibft_ctx *c) {
@@ -3616,6 +3652,10 @@ static int ensure_block_records(ibft_ctx *c, uint32_t s, uint32_t nb) {
 // slot and only read — block_head_kernel applies the seal-digest convention, the one in force at the submit, while it spreads
 // them over the rows —, a recover batch emits into columns of its slot, and digests / signers / indices leave on ostream (see
 // the context's fields).
+// sets: the four _sets submits (ibft_block_seals_submit_sets[_raw], ibft_recover_block_seals_submit_sets[_raw]) — the same
+// path under a family of sets: the verdict kernels judge against the family's union (family_view), block_head_kernel is
+// followed by the SETS form of block_tally_kernel over the slot's own block_set column, and the quorum words the collect hands
+// out are copied into the slot, so the family may be replaced while the batch is in flight.
 // d_signer_out / d_vidx ↔ the emit columns of slot s while a recover batch's kernels are enqueued (make_args and the tally
 // read the context's fields); put back on every way out
 struct emit_columns_view {
@@ -3636,20 +3676,45 @@ struct emit_columns_view {
   emit_columns_view &operator=(const emit_columns_view &) = delete;
 };
 static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off,
-                                   size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare) {
+                                   size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
+                                   bool sets = false, const uint32_t *block_set = nullptr) {
   uint32_t widest;
   size_t n;
   int rc;
   if ((rc = check_seal_offsets(c, seal_off, n_blocks, &widest, &n))) return rc;
   if (n && ((!props && !block_hash32) || !sig65 || (!bare && !signer20))) return IBFT_E_INVAL;
+  if (sets && n_blocks && !block_set) return IBFT_E_INVAL;
   std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself; side-stream tallies are joined below)
-  if (!c->have_valset) return IBFT_E_NOVALSET;
+  if (sets ? !c->fam.have : !c->have_valset) return IBFT_E_NOVALSET;  // each kind of batch needs only its own kind of set
+  if (sets)  // refused on the host, as by the synchronous sibling
+    for (size_t b = 0; b < n_blocks; b++)
+      if (block_set[b] >= c->fam.n_sets) return IBFT_E_INVAL;
   if (props && (rc = check_proposals(c, *props, n_blocks))) return rc;
   if ((rc = block_pipeline_refusal(c))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = join_side(c))) return rc;
+  // sets: from here to the return "the validator set" of the context is the family's union, as in block_seals_impl.  The
+  // batch is judged under the family installed NOW: its kernels read the family's device tables, which an install lets go
+  // only behind them (set_validator_sets_impl), and what the collect needs of the family is copied into the slot below.
+  family_view fv(c, sets);
   const uint32_t s = c->bs_issued & 1u, nb = (uint32_t)n_blocks, nr = (uint32_t)n;
-  const uint32_t kind = (bare ? IBFT_BATCH_RECOVER : 0u) | (props ? IBFT_BATCH_RAW : 0u);
+  const uint32_t kind = (bare ? IBFT_BATCH_RECOVER : 0u) | (props ? IBFT_BATCH_RAW : 0u) | (sets ? IBFT_BATCH_SETS : 0u);
+  // sets: the quorum words the collect hands out, kept in the slot (free: batch k − 2 has been collected) before anything
+  // is enqueued — 16 B per block, or 4 B per block + 16 B per set of the family, whichever is smaller
+  c->bs_setq[s].clear();
+  c->bs_setidx[s].clear();
+  if (sets) {
+    const ValFamily &f = c->fam;
+    const bool per_block = 16ull * nb <= 4ull * nb + 16ull * f.n_sets;
+    const uint32_t entries = per_block ? nb : f.n_sets;
+    c->bs_setq[s].reserve(2 * (size_t)entries);
+    for (uint32_t e = 0; e < entries; e++) {
+      const uint64_t *q = &f.quorum[(size_t)(per_block ? block_set[e] : e) * ibftk::TALLY_SUM_WORDS];
+      c->bs_setq[s].push_back(q[0]);
+      c->bs_setq[s].push_back(q[1]);
+    }
+    if (!per_block) c->bs_setidx[s].assign(block_set, block_set + nb);
+  }
   // submitted raw: the proposals are hashed whether or not rows wait for the hashes — the collect may ask for them
   const bool hash_here = props && nb;
   bool has_out = false;
@@ -3673,6 +3738,7 @@ static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, pro
     if (nr) {
       if ((rc = ensure(c, c->d_boff_nx, ((size_t)nb + 1) * 4))) return rc;
       if ((rc = ensure_block_records(c, s, nb))) return rc;
+      if (sets && (rc = ensure(c, c->bs_bset[s], (size_t)nb * 4))) return rc;
       if (bare) {
         const size_t m = std::max<size_t>(c->max_rows, c->row_cap);  // (the sizes alloc_rows gives d_signer_out / d_vidx)
         if ((rc = ensure(c, c->bs_signer[s], m * 20))) return rc;
@@ -3701,6 +3767,7 @@ static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, pro
       // may still be at it.  ev_cols_read was recorded behind them.
       HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_cols_read, 0));
       HIPCHK(c, hipMemcpyAsync(c->d_boff_nx.p, seal_off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, c->cstream));
+      if (sets) HIPCHK(c, hipMemcpyAsync(c->bs_bset[s].p, block_set, (size_t)nb * 4, hipMemcpyHostToDevice, c->cstream));
       HIPCHK(c, hipMemcpyAsync(c->d_sig_nx.p, sig65, n * 65, hipMemcpyHostToDevice, c->cstream));
       if (!bare) HIPCHK(c, hipMemcpyAsync(c->d_signer_nx.p, signer20, n * 20, hipMemcpyHostToDevice, c->cstream));
       if (pre_flags) HIPCHK(c, hipMemcpyAsync(c->d_pre_nx.p, pre_flags, n, hipMemcpyHostToDevice, c->cstream));
@@ -3725,8 +3792,9 @@ static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, pro
       std::swap(c->d_pre, c->d_pre_nx);
       std::swap(c->d_boff, c->d_boff_nx);
       c->wire_valid = false;
-      // verify kind: the rows are the resident batch from here on; bare rows are none (as after the synchronous siblings)
-      c->staged_n = bare ? 0 : nr;
+      // verify kind: the rows are the resident batch from here on; bare rows are none, and neither are rows judged against a
+      // family's union (as after the synchronous siblings)
+      c->staged_n = bare || sets ? 0 : nr;
       c->staged_pre = pre_flags != nullptr;
       ibftk::block_head_args h{};
       h.digest_words = (const uint64_t *)c->bs_phash[s].p;
@@ -3744,7 +3812,7 @@ static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, pro
         emit_columns_view ev(c, s, bare);
         if ((rc = enqueue_recover(c, c->stream, nr, pre_flags != nullptr, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
         if ((rc = enqueue_block_tally(c, nb, nr, widest, direct ? c->dp_mask[s] : nullptr,
-                                      direct ? c->bs_dtally_map[s] : (uint64_t *)c->bs_dtally[s].p, false)))
+                                      direct ? c->bs_dtally_map[s] : (uint64_t *)c->bs_dtally[s].p, sets, c->bs_bset[s].p)))
           return rc;
       }
       c->host_direct = false;
@@ -3790,6 +3858,27 @@ int ibft_recover_block_seals_submit_raw(ibft_ctx *c, const uint8_t *raw, const u
   proposal_batch p{raw, raw_off, round, nullptr};
   return block_seals_submit_impl(c, nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, true);
 }
+// The same four under a family of sets (IBFT_BATCH_SETS): the streamed forms of the _sets / _sets_raw calls.
+int ibft_block_seals_submit_sets(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, const uint32_t *block_set,
+                                 size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags) {
+  return block_seals_submit_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, false, true, block_set);
+}
+int ibft_block_seals_submit_sets_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                     const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
+                                     const uint8_t *signer20, const uint8_t *pre_flags) {
+  proposal_batch p{raw, raw_off, round, nullptr};
+  return block_seals_submit_impl(c, nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, false, true, block_set);
+}
+int ibft_recover_block_seals_submit_sets(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, const uint32_t *block_set,
+                                         size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags) {
+  return block_seals_submit_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, true, true, block_set);
+}
+int ibft_recover_block_seals_submit_sets_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                             const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
+                                             const uint8_t *pre_flags) {
+  proposal_batch p{raw, raw_off, round, nullptr};
+  return block_seals_submit_impl(c, nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, true, true, block_set);
+}
 
 // The oldest batch in flight → the caller.  ex: ibft_block_seals_collect_ex (digests, signers and indices where the batch's
 // kind carries them); the old call delivers verdict words and records only and refuses a recover batch with rows.
@@ -3821,7 +3910,11 @@ static int block_seals_collect_impl(ibft_ctx *c, bool ex, uint8_t *out_block_has
     memcpy(out_mask, c->p_mask[s], mw * 8);
     if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
   }
-  fill_block_tallies(out_tally, nb, nr, c->bs_tally[s], [&](uint32_t) -> const uint64_t * { return c->bs_quorum[s]; });
+  // (a sets batch: the quorum words kept at its submit — c->fam may be another family by now)
+  fill_block_tallies(out_tally, nb, nr, c->bs_tally[s], [&](uint32_t b) -> const uint64_t * {
+    if (!(kind & IBFT_BATCH_SETS)) return c->bs_quorum[s];
+    return &c->bs_setq[s][2 * (size_t)(c->bs_setidx[s].empty() ? b : c->bs_setidx[s][b])];
+  });
   if (ex && (kind & IBFT_BATCH_RAW) && out_block_hash32 && nb) memcpy(out_block_hash32, c->bs_h_hash[s], (size_t)nb * 32);
   if (ex && (kind & IBFT_BATCH_RECOVER) && nr) {
     memcpy(out_signer20, c->bs_h_signer[s], (size_t)nr * 20);
@@ -3829,6 +3922,10 @@ static int block_seals_collect_impl(ibft_ctx *c, bool ex, uint8_t *out_block_has
   }
   // The batch is DELIVERED before anything else can fail (the rule of ibft_seals_collect).
   c->bs_collected++;
+  // a sets batch taught keys of a family's union.  This — behind the delivery — is the one place where a collect reads
+  // c->fam: the build counts against the union installed NOW (the pool's build pass itself serves every slot of the device,
+  // whoever holds it), which may be another family than the batch's
+  family_view fv(c, (kind & IBFT_BATCH_SETS) != 0);
   if (c->cache_on && nr) {  // keys this batch taught the device → tables (build_new_tables drains the main stream when there
                             // are any — a newer batch in flight included; its results wait in their slot)
     const uint32_t *lw = reinterpret_cast<const uint32_t *>(c->p_tally[s] + 4);

@@ -52,12 +52,14 @@ EXPORTS = [
     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
+    "ibft_verify_block_seals_sets_raw", "ibft_recover_block_seals_sets_raw", "ibft_block_seals_submit_sets",
+    "ibft_block_seals_submit_sets_raw", "ibft_recover_block_seals_submit_sets", "ibft_recover_block_seals_submit_sets_raw",
     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
-# (ibft_set_validator_sets …, the two _sets block calls), ibft_sign_seals_ex, ibft_sign_messages_wire and ibft_judge_certificates_wire came without a version step: an
+# (ibft_set_validator_sets …, the two _sets block calls, their two _raw and four streamed forms), ibft_sign_seals_ex, ibft_sign_messages_wire and ibft_judge_certificates_wire came without a version step: an
 # older build simply lacks them, and the BatchVerifier methods raise GpuUnavailable there)
 EXPORTS_SINCE = {"ibft_pipeline_stats": 4}
 OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_block_seals_collect", "ibft_block_seals_pending",
@@ -67,6 +69,8 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_proposal_hashes", "ibft_verify_block_seals_raw", "ibft_recover_block_seals_raw",
                     "ibft_set_validator_sets", "ibft_set_validator_sets_u256", "ibft_validator_sets_info",
                     "ibft_verify_block_seals_sets", "ibft_recover_block_seals_sets",
+                    "ibft_verify_block_seals_sets_raw", "ibft_recover_block_seals_sets_raw", "ibft_block_seals_submit_sets",
+                    "ibft_block_seals_submit_sets_raw", "ibft_recover_block_seals_submit_sets", "ibft_recover_block_seals_submit_sets_raw",
                     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
                     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
@@ -243,6 +247,18 @@ def load_library() -> C.CDLL:
         L.ibft_verify_block_seals_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
     if hasattr(L, "ibft_recover_block_seals_sets"):
         L.ibft_recover_block_seals_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_verify_block_seals_sets_raw"):
+        L.ibft_verify_block_seals_sets_raw.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_recover_block_seals_sets_raw"):
+        L.ibft_recover_block_seals_sets_raw.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_block_seals_submit_sets"):
+        L.ibft_block_seals_submit_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    if hasattr(L, "ibft_block_seals_submit_sets_raw"):
+        L.ibft_block_seals_submit_sets_raw.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    if hasattr(L, "ibft_recover_block_seals_submit_sets"):
+        L.ibft_recover_block_seals_submit_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
+    if hasattr(L, "ibft_recover_block_seals_submit_sets_raw"):
+        L.ibft_recover_block_seals_submit_sets_raw.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
     if hasattr(L, "ibft_block_seals_submit"):
         L.ibft_block_seals_submit.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
     if hasattr(L, "ibft_block_seals_collect"):
@@ -823,6 +839,71 @@ class BatchVerifier:
         self._chk(self._L.ibft_block_seals_pending_ex(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(k)),
                   "ibft_block_seals_pending_ex")
         return int(a.value), int(b.value), int(c.value), int(k.value)
+
+    # … and under a family of sets, a set per block: the _sets calls from the proposals, and all four as a stream
+    BATCH_SETS = 4
+
+    def verify_block_seals_sets_raw(self, raws, rounds, seal_off, block_set, sig65, signer20, pre_flags=None, want_hashes: bool = True):
+        """ibft_verify_block_seals_sets_raw: verify_block_seals_sets with the blocks' PROPOSALS in place of their hashes →
+        (verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
+        self._need("ibft_verify_block_seals_sets_raw")
+        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
+        (raw, roff, rnd), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds),
+                                                                      signer20=signer20, block_set=bs)
+        mask, tallies, _, _, bh = self._block_outputs(n, nb, hashes=want_hashes)
+        self._chk(self._L.ibft_verify_block_seals_sets_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), _p(bs), nb, _p(s), _p(f),
+                                                           _p(pre), _p(bh), _p(mask), tallies), "ibft_verify_block_seals_sets_raw")
+        self._staged = 0
+        return mask_to_bool(mask, n), list(tallies)[:nb], (bh[:nb] if want_hashes else None)
+
+    def recover_block_seals_sets_raw(self, raws, rounds, seal_off, block_set, sig65, pre_flags=None, want_hashes: bool = True):
+        """ibft_recover_block_seals_sets_raw: recover_block_seals_sets with the blocks' PROPOSALS in place of their hashes →
+        (signer20 (n, 20), vidx int32[n], verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
+        self._need("ibft_recover_block_seals_sets_raw")
+        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
+        (raw, roff, rnd), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds), bare=True,
+                                                                      block_set=bs)
+        mask, tallies, signer, vidx, bh = self._block_outputs(n, nb, emit=True, hashes=want_hashes)
+        self._chk(self._L.ibft_recover_block_seals_sets_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), _p(bs), nb, _p(s), _p(pre),
+                                                            _p(bh), _p(signer), _p(vidx), _p(mask), tallies),
+                  "ibft_recover_block_seals_sets_raw")
+        self._staged = 0
+        return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb], (bh[:nb] if want_hashes else None)
+
+    def _submit_sets(self, name, block_set, seal_off, sig65, pre_flags, *, hashes=None, proposals=None, signer20=None, bare=False) -> int:
+        """one of the four _sets submits: columns checked, the call made, the arrays kept alive until the collect"""
+        self._need(name)
+        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
+        head, off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=hashes, proposals=proposals,
+                                                          signer20=signer20, bare=bare, block_set=bs)
+        args = [_p(x) for x in head] + [_p(off), _p(bs), nb, _p(s)] + ([] if bare else [_p(f)]) + [_p(pre)]
+        self._chk(getattr(self._L, name)(self._h, *args), name)
+        self._block_cols = getattr(self, "_block_cols", []) + [tuple(head) + (off, bs, s, f, pre)]
+        if n:
+            self._staged = 0
+        return n
+
+    def block_seals_submit_sets(self, block_hash32, seal_off, block_set, sig65, signer20, pre_flags=None) -> int:
+        """ibft_block_seals_submit_sets: the batch of verify_block_seals_sets, enqueued and not waited for → its row count.
+        Judged under the family installed NOW, whatever is installed before its collect (block_seals_collect[_ex])."""
+        return self._submit_sets("ibft_block_seals_submit_sets", block_set, seal_off, sig65, pre_flags, hashes=block_hash32,
+                                 signer20=signer20)
+
+    def block_seals_submit_sets_raw(self, raws, rounds, seal_off, block_set, sig65, signer20, pre_flags=None) -> int:
+        """ibft_block_seals_submit_sets_raw: the batch of verify_block_seals_sets_raw, enqueued and not waited for → its row count"""
+        return self._submit_sets("ibft_block_seals_submit_sets_raw", block_set, seal_off, sig65, pre_flags, proposals=(raws, rounds),
+                                 signer20=signer20)
+
+    def recover_block_seals_submit_sets(self, block_hash32, seal_off, block_set, sig65, pre_flags=None) -> int:
+        """ibft_recover_block_seals_submit_sets: the batch of recover_block_seals_sets, enqueued and not waited for → its row count"""
+        return self._submit_sets("ibft_recover_block_seals_submit_sets", block_set, seal_off, sig65, pre_flags, hashes=block_hash32,
+                                 bare=True)
+
+    def recover_block_seals_submit_sets_raw(self, raws, rounds, seal_off, block_set, sig65, pre_flags=None) -> int:
+        """ibft_recover_block_seals_submit_sets_raw: the batch of recover_block_seals_sets_raw, enqueued and not waited for → its
+        row count"""
+        return self._submit_sets("ibft_recover_block_seals_submit_sets_raw", block_set, seal_off, sig65, pre_flags,
+                                 proposals=(raws, rounds), bare=True)
 
     # Verifier.IsValidValidator, batched
     def is_valid_validator(self, payload: bytes, off, sig65, from20, pre_flags=None):

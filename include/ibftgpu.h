@@ -426,6 +426,7 @@ int ibft_recover_block_seals_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32
  * the streamed raw / recover forms over the synchronous calls is claimed.                               */
 #define IBFT_BATCH_RECOVER 1u /* bit 0 of a batch's kind: bare seals, signers are emitted */
 #define IBFT_BATCH_RAW 2u     /* bit 1: proposals were given, hashes are computed and can be delivered */
+#define IBFT_BATCH_SETS 4u    /* bit 2: judged under a set per block (the _sets submits, below the family's calls) */
 int ibft_block_seals_submit_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
                                 const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20,
                                 const uint8_t *pre_flags);
@@ -458,8 +459,9 @@ int ibft_block_seals_pending_ex(ibft_ctx *ctx, uint32_t *batches_in_flight, uint
  *   Installing a family replaces the previous family whole; a refused install leaves the previous one in place.
  * ibft_validator_sets_info: sets and union addresses of the installed family and the device bytes it holds now (0, 0, 0
  *   without one): the CAPACITIES of its buffers — the tables the budget counts (there by their computed sizes; a buffer is
- *   never smaller than 256 bytes), plus the key-cache slot column of the union and the block_set column the _sets calls
- *   upload, which grows with their n_blocks and is not part of the budget.  Any pointer may be NULL.
+ *   never smaller than 256 bytes), plus the key-cache slot column of the union and the block_set columns the _sets calls
+ *   upload (one for the synchronous calls, one per slot of the streamed ones), which grow with their n_blocks and are not
+ *   part of the budget.  Any pointer may be NULL.
  *
  * ibft_verify_block_seals_sets / ibft_recover_block_seals_sets: ibft_verify_block_seals / ibft_recover_block_seals plus
  *   block_set (n_blocks entries, each < n_sets): the set block b is judged under.
@@ -485,13 +487,59 @@ int ibft_block_seals_pending_ex(ibft_ctx *ctx, uint32_t *batches_in_flight, uint
  *    and later calls — _sets or single-set, on this context or another of the device — are warm for those addresses.  A
  *    signer in the union but not in its block's set is verified like any row and its bit then cleared: the verdict (0) of
  *    the per-set call's non-member early-out.
- *  - There is no streamed (submit / collect) form of these calls: the streamed pipeline (ibft_block_seals_submit and the
- *    submits from proposals and bare seals) judges every batch under the context's single set.
- * When the single-set call is still the right one: a run judged under ONE set — it does without the per-row load of the
- * dense table and one upload.  What the _sets call gains over a cut batch and what it costs over the single-set call:
- * DESIGN.md §5.11, which also says what of it has been measured.  Out of scope: streamed (submit / collect) and _raw forms of the _sets calls (a
- * syncer hashes with ibft_proposal_hashes first), the sharded group calls, and a family for the message-set / wire entry
- * points (consensus runs at one height).                                                                              */
+ *  - The install calls (ibft_set_validator_sets[_u256]) are synchronous: there is
+ *    no streamed (submit / collect) form of these calls.  They may be called with _sets batches in flight (below).
+ *
+ * FROM THE PROPOSALS — ibft_verify_block_seals_sets_raw / ibft_recover_block_seals_sets_raw: the _sets calls with raw /
+ *   raw_off / round in the place of block_hash32, as ibft_verify_block_seals_raw has them.  Defining property: each equals
+ *   ibft_proposal_hashes followed by the hashes-given _sets call with those hashes — mask words, every field of every
+ *   ibft_tally_t, out_signer20, out_vidx and out_block_hash32 (the hashes BEFORE the seal-digest convention), cold and warm,
+ *   in both forms of the digest kernel, under every convention, strict-low-s on and off, u64 and u256 families.  Errors:
+ *   those of the hashes-given _sets call in its order, minus the NULL block_hash32; then those of ibft_proposal_hashes'
+ *   arguments in its order.  A refused call writes nothing.  With no seal rows at all the proposals are hashed only if
+ *   out_block_hash32 is given.
+ *
+ * STREAMED — the submit / collect pipeline of ibft_block_seals_submit, a set per block:
+ *   ibft_block_seals_submit_sets              sibling: ibft_verify_block_seals_sets
+ *   ibft_block_seals_submit_sets_raw          sibling: ibft_verify_block_seals_sets_raw
+ *   ibft_recover_block_seals_submit_sets      sibling: ibft_recover_block_seals_sets
+ *   ibft_recover_block_seals_submit_sets_raw  sibling: ibft_recover_block_seals_sets_raw
+ *   Collected with ibft_block_seals_collect[_ex]; ibft_block_seals_pending_ex reports IBFT_BATCH_SETS in oldest_kind.
+ *   Defining property: each submit, collected with ibft_block_seals_collect_ex, delivers bit for bit what its synchronous
+ *   sibling returns for the same arguments under the family that was installed at the submit.
+ *  - Pinned state: a sets batch is judged under the family, the seal-digest convention and the digest-kernel form current at
+ *    ITS submit.  ibft_set_validator_sets[_u256] between a submit and its collect is legal and does not change that batch:
+ *    set membership, out_vidx and the quorum_* fields of its tallies are the old family's.  The install waits for the kernels
+ *    of the batches in flight before the old family's device tables are released and before the key-cache references of the
+ *    old union are dropped; the batches' results already sit in their slots and stay collectable.  A refused install leaves
+ *    the family and the batches untouched.
+ *  - Shared slots: the four submits share the two slots with the four single-set submits; batches of any kinds may be in
+ *    flight together (a single-set batch between two sets batches) and are collected oldest first.  A single-set batch is
+ *    judged under the single set, a sets batch under the family; each needs only its own kind of set: IBFT_E_NOVALSET from a
+ *    sets submit means "no family installed", and a single-set submit with only a family installed keeps returning it.
+ *  - Checks: the synchronous sibling's, in its order, minus the out buffers — the NULL block_set with n_blocks > 0 and,
+ *    behind IBFT_E_NOVALSET, an entry ≥ n_sets included, both decided on the host —; then the pipeline's refusals.  A refused
+ *    call takes no slot and enqueues nothing.
+ *  - Caller buffers: block_set stays untouched until the collect of its batch has returned, like every other column.
+ *  - After a sets submit the rows are not a resident staged batch.  Key learning and the table build at the collect work as
+ *    for the other submits, over the union's slots.  ibft_sync, ibft_ctx_destroy, ibft_block_seals_pending and every other
+ *    entry point behave as towards any batch in flight.  ibft_block_seals_collect (the old call) treats a sets verify batch
+ *    like any verify batch and refuses a sets recover batch with rows, as it refuses any recover batch.
+ *  - Device memory: each slot keeps the block_set column of its batch (4 bytes per block, in ibft_validator_sets_info's
+ *    device_bytes); the collect's quorum words are kept on the host.
+ *
+ * Which form to use: a run judged under ONE set — the single-set calls, which do without the per-row load of the dense
+ * table and one upload.  A run that crosses set changes — the _sets calls; from proposals, the _sets_raw calls; a syncer
+ * that keeps batches in flight, the _sets submits, installing the next run's family while the last batches of this run are
+ * still in flight.  MEASURED (tools/block_seals_sets_stream_rate.py, V = 100, a set change every 64 blocks, 1 KiB proposals,
+ * pinned sources; profiles/r23_block_seals_sets_stream_rate.txt): per batch the streamed sets form with one batch in flight
+ * takes 0.84 × (cold) / 0.95 × (warm) the time of ibft_proposal_hashes + ibft_verify_block_seals_sets at 65 500 rows, and
+ * 1.00 × / 1.02 × at 16 300 rows — it pays from batches of several ten thousand rows on and not below; against batches cut
+ * at every set change and streamed under ibft_set_validators it takes 0.13 … 0.16 × at 65 500 rows and 0.36 … 0.45 × at 16 300.
+ * What the _sets call gains over a cut batch and what it costs over the single-set call: DESIGN.md §5.11.
+ * Out of scope: streamed (submit / collect) forms over a device group, the sharded group calls as a whole, appending to a
+ * family in place, more than two batches in flight, and a family for the message-set / wire entry points (consensus runs
+ * at one height).                                                                                                      */
 int ibft_set_validator_sets(ibft_ctx *ctx, size_t n_sets, const uint64_t *height, const uint32_t *set_off,
                             const uint8_t *addrs20, const uint64_t *power);
 int ibft_set_validator_sets_u256(ibft_ctx *ctx, size_t n_sets, const uint64_t *height, const uint32_t *set_off,
@@ -505,6 +553,27 @@ int ibft_recover_block_seals_sets(ibft_ctx *ctx, const uint8_t *block_hash32, co
                                   const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
                                   const uint8_t *pre_flags, uint8_t *out_signer20, int32_t *out_vidx,
                                   uint64_t *out_mask, ibft_tally_t *out_tally);
+int ibft_verify_block_seals_sets_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                     const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks,
+                                     const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags,
+                                     uint8_t *out_block_hash32, uint64_t *out_mask, ibft_tally_t *out_tally);
+int ibft_recover_block_seals_sets_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                      const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks,
+                                      const uint8_t *sig65, const uint8_t *pre_flags, uint8_t *out_block_hash32,
+                                      uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask,
+                                      ibft_tally_t *out_tally);
+int ibft_block_seals_submit_sets(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off,
+                                 const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
+                                 const uint8_t *signer20, const uint8_t *pre_flags);
+int ibft_block_seals_submit_sets_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                     const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks,
+                                     const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags);
+int ibft_recover_block_seals_submit_sets(ibft_ctx *ctx, const uint8_t *block_hash32, const uint32_t *seal_off,
+                                         const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
+                                         const uint8_t *pre_flags);
+int ibft_recover_block_seals_submit_sets_raw(ibft_ctx *ctx, const uint8_t *raw, const uint32_t *raw_off,
+                                             const uint64_t *round, const uint32_t *seal_off, const uint32_t *block_set,
+                                             size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags);
 
 /* a3. payload = concatenated PayloadNoSig bytes; row i is payload[off[i]..off[i+1]);
  * off has n+1 entries.                                                             */

@@ -535,6 +535,7 @@ func (c *Ctx) RecoverBlockSealsRaw(raw []byte, rawOff []uint32, round []uint64, 
 type blockBatch struct {
 	blockHash32, sig65, signer20, preFlags []byte
 	sealOff                                []uint32
+	blockSet                               []uint32 // the _sets submits: the set of every block
 	raw                                    []byte   // the streamed raw forms: the proposals as given,
 	rawOff                                 []uint32 // their offsets
 	round                                  []uint64 // and the shim's own copy of the rounds
@@ -616,25 +617,27 @@ func (c *Ctx) BlockSealsCollect() ([]uint64, []Tally, error) {
 }
 
 // Kinds of a streamed block batch (ibft_block_seals_pending_ex): bit 0 bare seals, signers are emitted; bit 1 proposals were
-// given, the computed hashes can be delivered.  0: a batch of BlockSealsSubmit.
+// given, the computed hashes can be delivered; bit 2 judged under a set per block (the family installed at the submit).
+// 0: a batch of BlockSealsSubmit.
 const (
 	BatchRecover = uint32(C.IBFT_BATCH_RECOVER)
 	BatchRaw     = uint32(C.IBFT_BATCH_RAW)
+	BatchSets    = uint32(C.IBFT_BATCH_SETS)
 )
 
-// submitStreamed is the common part of the three streamed submits below: raw == nil && rawOff == nil means hashes given
-// (blockHash32), bare means no signer column.  The slices are held — Go memory pinned, PinnedBytes memory left alone — until
-// the collect of the batch.
-func (c *Ctx) submitStreamed(blockHash32, raw []byte, rawOff []uint32, round []uint64, sealOff []uint32, sig65, signer20, preFlags []byte, fromRaw, bare bool) error {
+// submitStreamed is the common part of the streamed submits below: raw == nil && rawOff == nil means hashes given
+// (blockHash32), bare means no signer column, sets means a validator set per block (blockSet, one entry per block; the four
+// _sets submits).  The slices are held — Go memory pinned, PinnedBytes memory left alone — until the collect of the batch.
+func (c *Ctx) submitStreamed(blockHash32, raw []byte, rawOff []uint32, round []uint64, sealOff, blockSet []uint32, sig65, signer20, preFlags []byte, fromRaw, bare, sets bool) error {
 	if len(sealOff) == 0 {
 		return fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
 	}
 	nb := len(sealOff) - 1
 	n := int(sealOff[nb])
-	if len(sig65) < 65*n || (!bare && len(signer20) < 20*n) || (preFlags != nil && len(preFlags) < n) {
+	if (sets && len(blockSet) < nb) || len(sig65) < 65*n || (!bare && len(signer20) < 20*n) || (preFlags != nil && len(preFlags) < n) {
 		return fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
 	}
-	b := &blockBatch{blockHash32: blockHash32, sealOff: sealOff, sig65: sig65, signer20: signer20, preFlags: preFlags}
+	b := &blockBatch{blockHash32: blockHash32, sealOff: sealOff, blockSet: blockSet, sig65: sig65, signer20: signer20, preFlags: preFlags}
 	if fromRaw {
 		if len(round) != nb {
 			return fmt.Errorf("%w: one proposal per block", ErrFallback)
@@ -654,13 +657,29 @@ func (c *Ctx) submitStreamed(blockHash32, raw []byte, rawOff []uint32, round []u
 		}
 		b.hold(unsafe.Pointer(ptr8(blockHash32)))
 	}
+	// (every length check is behind us: from here on the only way out without the batch is the refused submit, which unpins)
 	b.hold(unsafe.Pointer(&sealOff[0]))
+	var bs *C.uint32_t
+	if sets {
+		bs = blockSetPtr(blockSet, nb)
+		b.hold(unsafe.Pointer(bs))
+	}
 	b.hold(unsafe.Pointer(ptr8(sig65)))
 	b.hold(unsafe.Pointer(ptr8(signer20)))
 	b.hold(unsafe.Pointer(ptr8(preFlags)))
 	off := (*C.uint32_t)(unsafe.Pointer(&sealOff[0]))
 	var rc C.int
 	switch {
+	case sets && fromRaw && !bare:
+		rc = C.ibft_block_seals_submit_sets_raw(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
+			(*C.uint64_t)(unsafe.Pointer(&b.round[0])), off, bs, C.size_t(nb), ptr8(sig65), ptr8(signer20), ptr8(preFlags))
+	case sets && fromRaw && bare:
+		rc = C.ibft_recover_block_seals_submit_sets_raw(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
+			(*C.uint64_t)(unsafe.Pointer(&b.round[0])), off, bs, C.size_t(nb), ptr8(sig65), ptr8(preFlags))
+	case sets && bare:
+		rc = C.ibft_recover_block_seals_submit_sets(c.h, ptr8(blockHash32), off, bs, C.size_t(nb), ptr8(sig65), ptr8(preFlags))
+	case sets:
+		rc = C.ibft_block_seals_submit_sets(c.h, ptr8(blockHash32), off, bs, C.size_t(nb), ptr8(sig65), ptr8(signer20), ptr8(preFlags))
 	case fromRaw && !bare:
 		rc = C.ibft_block_seals_submit_raw(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
 			(*C.uint64_t)(unsafe.Pointer(&b.round[0])), off, C.size_t(nb), ptr8(sig65), ptr8(signer20), ptr8(preFlags))
@@ -683,22 +702,128 @@ func (c *Ctx) submitStreamed(blockHash32, raw []byte, rawOff []uint32, round []u
 // slices, raw included, must not be written to before the collect of their batch (BlockSealsCollectEx); carve them from
 // PinnedBytes for the copy to run under the kernels of the batch before.
 func (c *Ctx) BlockSealsSubmitRaw(raw []byte, rawOff []uint32, round []uint64, sealOff []uint32, sig65, signer20, preFlags []byte) error {
-	return c.submitStreamed(nil, raw, rawOff, round, sealOff, sig65, signer20, preFlags, true, false)
+	return c.submitStreamed(nil, raw, rawOff, round, sealOff, nil, sig65, signer20, preFlags, true, false, false)
 }
 
 // RecoverBlockSealsSubmit enqueues the batch of RecoverBlockSeals (ibft_recover_block_seals_submit): bare seals, streamed.
 // Collect it with BlockSealsCollectEx; BlockSealsCollect refuses a recover batch with rows and leaves it in flight.
 func (c *Ctx) RecoverBlockSealsSubmit(blockHash32 []byte, sealOff []uint32, sig65, preFlags []byte) error {
-	return c.submitStreamed(blockHash32, nil, nil, nil, sealOff, sig65, nil, preFlags, false, true)
+	return c.submitStreamed(blockHash32, nil, nil, nil, sealOff, nil, sig65, nil, preFlags, false, true, false)
 }
 
 // RecoverBlockSealsSubmitRaw enqueues the batch of RecoverBlockSealsRaw (ibft_recover_block_seals_submit_raw).
 func (c *Ctx) RecoverBlockSealsSubmitRaw(raw []byte, rawOff []uint32, round []uint64, sealOff []uint32, sig65, preFlags []byte) error {
-	return c.submitStreamed(nil, raw, rawOff, round, sealOff, sig65, nil, preFlags, true, true)
+	return c.submitStreamed(nil, raw, rawOff, round, sealOff, nil, sig65, nil, preFlags, true, true, false)
+}
+
+// blockSetPtr is the block_set column as the C calls take it (nil for a batch without blocks).
+func blockSetPtr(blockSet []uint32, nb int) *C.uint32_t {
+	if nb == 0 {
+		return nil
+	}
+	return (*C.uint32_t)(unsafe.Pointer(&blockSet[0]))
+}
+
+// VerifyBlockSealsSetsRaw = VerifyBlockSealsSets with the blocks' PROPOSALS in place of their hashes
+// (ibft_verify_block_seals_sets_raw): ProposalHashes + VerifyBlockSealsSets in one call; blockHash32 as from VerifyBlockSealsRaw.
+func (c *Ctx) VerifyBlockSealsSetsRaw(raw []byte, rawOff []uint32, round []uint64, sealOff, blockSet []uint32, sig65, signer20, preFlags []byte) (blockHash32 []byte, mask []uint64, tallies []Tally, err error) {
+	if len(sealOff) == 0 {
+		return nil, nil, nil, fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(round) != nb {
+		return nil, nil, nil, fmt.Errorf("%w: one proposal per block", ErrFallback)
+	}
+	if err = checkProposals(raw, rawOff, round); err != nil {
+		return nil, nil, nil, err
+	}
+	if len(blockSet) < nb || len(sig65) < 65*n || len(signer20) < 20*n || (preFlags != nil && len(preFlags) < n) {
+		return nil, nil, nil, fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	blockHash32 = make([]byte, 32*nb+32)
+	mask = make([]uint64, (n+63)/64+1)
+	ct := make([]C.ibft_tally_t, nb+1)
+	roundCol := make([]uint64, nb+1)
+	copy(roundCol, round)
+	rc := C.ibft_verify_block_seals_sets_raw(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
+		(*C.uint64_t)(unsafe.Pointer(&roundCol[0])), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), blockSetPtr(blockSet, nb), C.size_t(nb),
+		ptr8(sig65), ptr8(signer20), ptr8(preFlags), ptr8(blockHash32), (*C.uint64_t)(unsafe.Pointer(&mask[0])),
+		(*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err = c.check(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	tallies = make([]Tally, nb)
+	for b := range tallies {
+		tallies[b] = tally(ct[b])
+	}
+	return blockHash32[:32*nb], mask, tallies, nil
+}
+
+// RecoverBlockSealsSetsRaw = RecoverBlockSealsSets with the blocks' PROPOSALS in place of their hashes
+// (ibft_recover_block_seals_sets_raw).
+func (c *Ctx) RecoverBlockSealsSetsRaw(raw []byte, rawOff []uint32, round []uint64, sealOff, blockSet []uint32, sig65, preFlags []byte) (blockHash32, signer20 []byte, vidx []int32, mask []uint64, tallies []Tally, err error) {
+	if len(sealOff) == 0 {
+		return nil, nil, nil, nil, nil, fmt.Errorf("%w: sealOff needs n_blocks + 1 entries", ErrFallback)
+	}
+	nb := len(sealOff) - 1
+	n := int(sealOff[nb])
+	if len(round) != nb {
+		return nil, nil, nil, nil, nil, fmt.Errorf("%w: one proposal per block", ErrFallback)
+	}
+	if err = checkProposals(raw, rawOff, round); err != nil {
+		return nil, nil, nil, nil, nil, err
+	}
+	if len(blockSet) < nb || len(sig65) < 65*n || (preFlags != nil && len(preFlags) < n) {
+		return nil, nil, nil, nil, nil, fmt.Errorf("%w: columns shorter than sealOff says", ErrFallback)
+	}
+	blockHash32 = make([]byte, 32*nb+32)
+	signer20 = make([]byte, 20*n+20)
+	vidx = make([]int32, n+1)
+	mask = make([]uint64, (n+63)/64+1)
+	ct := make([]C.ibft_tally_t, nb+1)
+	roundCol := make([]uint64, nb+1)
+	copy(roundCol, round)
+	rc := C.ibft_recover_block_seals_sets_raw(c.h, ptr8(raw), (*C.uint32_t)(unsafe.Pointer(&rawOff[0])),
+		(*C.uint64_t)(unsafe.Pointer(&roundCol[0])), (*C.uint32_t)(unsafe.Pointer(&sealOff[0])), blockSetPtr(blockSet, nb), C.size_t(nb),
+		ptr8(sig65), ptr8(preFlags), ptr8(blockHash32), ptr8(signer20), (*C.int32_t)(unsafe.Pointer(&vidx[0])),
+		(*C.uint64_t)(unsafe.Pointer(&mask[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err = c.check(rc); err != nil {
+		return nil, nil, nil, nil, nil, err
+	}
+	tallies = make([]Tally, nb)
+	for b := range tallies {
+		tallies[b] = tally(ct[b])
+	}
+	return blockHash32[:32*nb], signer20[:20*n], vidx[:n], mask, tallies, nil
+}
+
+// BlockSealsSubmitSets enqueues the batch of VerifyBlockSealsSets (ibft_block_seals_submit_sets): the streamed pipeline of
+// BlockSealsSubmit — the same two slots — with a validator set PER BLOCK.  The batch is judged under the family installed at
+// the submit: SetValidatorSets for the next run may be called while it is in flight.  Collect with BlockSealsCollect[Ex].
+func (c *Ctx) BlockSealsSubmitSets(blockHash32 []byte, sealOff, blockSet []uint32, sig65, signer20, preFlags []byte) error {
+	return c.submitStreamed(blockHash32, nil, nil, nil, sealOff, blockSet, sig65, signer20, preFlags, false, false, true)
+}
+
+// BlockSealsSubmitSetsRaw enqueues the batch of VerifyBlockSealsSetsRaw (ibft_block_seals_submit_sets_raw): what a syncer that
+// holds (Proposal, seals, blockSet) streams across validator-set changes.
+func (c *Ctx) BlockSealsSubmitSetsRaw(raw []byte, rawOff []uint32, round []uint64, sealOff, blockSet []uint32, sig65, signer20, preFlags []byte) error {
+	return c.submitStreamed(nil, raw, rawOff, round, sealOff, blockSet, sig65, signer20, preFlags, true, false, true)
+}
+
+// RecoverBlockSealsSubmitSets enqueues the batch of RecoverBlockSealsSets (ibft_recover_block_seals_submit_sets); collect it
+// with BlockSealsCollectEx.
+func (c *Ctx) RecoverBlockSealsSubmitSets(blockHash32 []byte, sealOff, blockSet []uint32, sig65, preFlags []byte) error {
+	return c.submitStreamed(blockHash32, nil, nil, nil, sealOff, blockSet, sig65, nil, preFlags, false, true, true)
+}
+
+// RecoverBlockSealsSubmitSetsRaw enqueues the batch of RecoverBlockSealsSetsRaw (ibft_recover_block_seals_submit_sets_raw).
+func (c *Ctx) RecoverBlockSealsSubmitSetsRaw(raw []byte, rawOff []uint32, round []uint64, sealOff, blockSet []uint32, sig65, preFlags []byte) error {
+	return c.submitStreamed(nil, raw, rawOff, round, sealOff, blockSet, sig65, nil, preFlags, true, true, true)
 }
 
 // BlockSealsPendingEx = BlockSealsPending plus the kind of the oldest batch (ibft_block_seals_pending_ex): BatchRecover /
-// BatchRaw bits, 0 for a batch of BlockSealsSubmit.
+// BatchRaw / BatchSets bits, 0 for a batch of BlockSealsSubmit.
 func (c *Ctx) BlockSealsPendingEx() (inFlight, oldestRows, oldestBlocks int, oldestKind uint32, err error) {
 	var a, r, b, k C.uint32_t
 	if err = c.check(C.ibft_block_seals_pending_ex(c.h, &a, &r, &b, &k)); err != nil {
