@@ -188,6 +188,11 @@ struct ibft_ctx {
   DevBuf d_noseal;             // message sets from wire bytes: rows (PREPAREs) whose closure has no seal
   uint32_t wire_n = 0;         // rows of the last ibft_verify_senders_wire
   bool wire_valid = false;     // its columns are still the resident ones
+  // IBFT_FLAG_WIRE_RECODE / IBFT_WIRE_RECODE=0|1: the flat wire calls run wire_recode_kernel over the rows the canonical walk
+  // marked NEEDS_HOST (wire_recode_dev.h)
+  bool wire_recode = false;
+  uint32_t wire_stat_n = 0;      // ibft_wire_stats: rows of the last flat wire call ...
+  bool wire_stat_valid = false;  // ... whose parse results are still in d_wire_rows
   // fixed-base table for G
   // validator table
   DevBuf d_vtab, d_vpower;
@@ -1707,6 +1712,8 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   if (const char *e = getenv("IBFT_CERT_OVERLAP")) c->cert_overlap = atoi(e) != 0;
   c->cert_dedup = (c->flags & IBFT_FLAG_CERT_DEDUP) != 0;
   if (const char *e = getenv("IBFT_CERT_DEDUP")) c->cert_dedup = atoi(e) != 0;
+  c->wire_recode = (c->flags & IBFT_FLAG_WIRE_RECODE) != 0;
+  if (const char *e = getenv("IBFT_WIRE_RECODE")) c->wire_recode = atoi(e) != 0;
   if (const char *e = getenv("IBFT_CERT_DEDUP_SLOTS")) c->cert_dedup_slots_cap = (uint32_t)strtoul(e, nullptr, 10);
   if (getenv("IBFT_DIGEST_FUSION")) c->digest_in_gather = true;
   if (const char *e = getenv("IBFT_WAVE_ROWS_MAX")) c->wave_rows_max = (uint32_t)strtoul(e, nullptr, 10);
@@ -3996,6 +4003,37 @@ int ibft_verify_senders(ibft_ctx *c, const uint8_t *payload, const uint32_t *off
   return fetch_results(c, (uint32_t)n, out_mask, tally, true);
 }
 
+// IBFT_FLAG_WIRE_RECODE: after wire_parse_kernel, before anything reads its columns (c->mu held, n > 0)
+static int enqueue_wire_recode(ibft_ctx *c, uint32_t n) {
+  if (!c->wire_recode) return IBFT_OK;
+  hipLaunchKernelGGL(ibftk::wire_recode_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const uint8_t *)c->d_payload.p,
+                     (const uint32_t *)c->d_off.p, n, (wire::row_info *)c->d_wire_rows.p, (uint8_t *)c->d_hash.p,
+                     (uint8_t *)c->d_sig.p, (uint8_t *)c->d_signer.p, (uint8_t *)c->d_seal.p, (uint8_t *)c->d_pre.p);
+  HIPCHK(c, hipGetLastError());
+  return IBFT_OK;
+}
+
+int ibft_wire_stats(ibft_ctx *c, uint32_t *rows, uint32_t *recoded_rows, uint32_t *needs_host_rows) {
+  if (!c) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  uint32_t n = 0, recoded = 0, needs = 0;
+  if (c->wire_stat_valid && c->wire_stat_n) {
+    n = c->wire_stat_n;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<wire::row_info> h(n);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(h.data(), c->d_wire_rows.p, (size_t)n * sizeof(wire::row_info), hipMemcpyDeviceToHost));
+    for (const wire::row_info &ri : h) {
+      recoded += ri.status == wire::STATUS_OK && ri.pad[0] == 1;
+      needs += ri.status == wire::STATUS_NEEDS_HOST;
+    }
+  }
+  if (rows) *rows = n;
+  if (recoded_rows) *recoded_rows = recoded;
+  if (needs_host_rows) *needs_host_rows = needs;
+  return IBFT_OK;
+}
+
 int ibft_verify_senders_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, uint64_t *out_mask,
                              ibft_wire_row_t *out_rows, ibft_tally_t *tally) {
   static_assert(sizeof(ibft_wire_row_t) == sizeof(wire::row_info), "ABI");
@@ -4018,6 +4056,7 @@ int ibft_verify_senders_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint3
   c->staged_pre = true;
   c->wire_n = (uint32_t)n;
   c->wire_valid = true;
+  c->wire_stat_valid = false;
   c->ev_used = 0;
   if (n) {
     hipLaunchKernelGGL(ibftk::wire_parse_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
@@ -4025,13 +4064,17 @@ int ibft_verify_senders_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint3
                        (wire::row_info *)c->d_wire_rows.p, (uint8_t *)c->d_hash.p, (uint8_t *)c->d_sig.p,
                        (uint8_t *)c->d_signer.p, (uint8_t *)c->d_seal.p, (uint8_t *)c->d_pre.p);
     HIPCHK(c, hipGetLastError());
+    if ((rc = enqueue_wire_recode(c, (uint32_t)n))) return rc;
   }
   // the digest column now holds keccak256(PayloadNoSig): the sender check is the seal-style pass (mode 0)
   if ((rc = enqueue_recover(c, c->stream, (uint32_t)n, true, ibftk::MODE_SEALS, true))) return rc;
   if ((rc = enqueue_tally(c, (uint32_t)n))) return rc;
   if (out_rows && n)
     HIPCHK(c, hipMemcpyAsync(out_rows, c->d_wire_rows.p, n * sizeof(ibft_wire_row_t), hipMemcpyDeviceToHost, c->stream));
-  return fetch_results(c, (uint32_t)n, out_mask, tally, true);
+  if ((rc = fetch_results(c, (uint32_t)n, out_mask, tally, true))) return rc;
+  c->wire_stat_n = (uint32_t)n;
+  c->wire_stat_valid = true;
+  return IBFT_OK;
 }
 
 // A batch of raw IbftMessages judged completely: the wire walk, then BOTH signatures of every message in one verdict
@@ -4051,6 +4094,7 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   c->wire_valid = false;
+  c->wire_stat_valid = false;
   c->staged_n = 0;
   const uint32_t half = ((uint32_t)n + 63u) & ~63u;
   if ((rc = alloc_rows(c, 2 * (((uint32_t)c->max_rows + 63u) & ~63u)))) return rc;
@@ -4094,6 +4138,7 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
                      (const uint8_t *)c->d_payload.p, (const uint32_t *)c->d_off.p, (uint32_t)n,
                      (wire::row_info *)c->d_wire_rows.p, d_hash, d_sig, d_signer, (uint8_t *)c->d_seal.p, d_pre);
   HIPCHK(c, hipGetLastError());
+  if ((rc = enqueue_wire_recode(c, (uint32_t)n))) return rc;
   hipLaunchKernelGGL(ibftk::wire_set_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
                      (const wire::row_info *)c->d_wire_rows.p, (const uint8_t *)c->d_seal.p, (uint32_t)n, half, height, round,
                      d_hash, (uint8_t *)c->d_hash_len.p, d_sig, d_signer, d_pre, (uint8_t *)c->d_noseal.p,
@@ -4142,6 +4187,8 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
   memcpy(out_sender_mask, c->h_set, mw * 8);
   memcpy(out_valid_mask, c->h_set + mask_words(c->max_rows), mw * 8);
   if (out_class) memcpy(out_class, c->h_class, n);
+  c->wire_stat_n = (uint32_t)n;
+  c->wire_stat_valid = true;
   return IBFT_OK;
 }
 
@@ -4187,6 +4234,7 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
   const size_t wbytes = off[n], m = c->max_rows;
   if ((rc = ensure(c, c->d_payload, wbytes + 256))) return rc;
   if ((rc = ensure(c, c->d_wire_rows, m * sizeof(wire::row_info)))) return rc;
+  c->wire_stat_valid = false;  // the tree's rows take the place of the last flat call's
   if ((rc = ensure(c, c->d_cert_nodes, m * sizeof(wire::node_info)))) return rc;
   if ((rc = ensure(c, c->d_cert_span, m * 8))) return rc;
   if ((rc = ensure(c, c->d_cert_count, m * 4))) return rc;

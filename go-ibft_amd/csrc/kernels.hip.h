@@ -24,6 +24,7 @@
 //   gtab_build_kernel, qtab_build_kernel, qtab_commit_kernel   one-time fixed-base tables
 //   lookup_kernel                   sender → validator index for ibft_tally()
 //   wire_parse_kernel, wire_stage_seals_kernel   §8f rank 3: wire bytes → columns on the device (wire_dev.h)
+//   wire_recode_kernel                            the same for non-canonical encodings, opt-in (wire_recode_dev.h)
 //
 // Layout in HBM: one contiguous byte column per field (hash N×32, sig N×65, signer N×20,
 // pre_flags N) — structure-of-arrays at field granularity.  The lane kernels stage a block's
@@ -47,6 +48,7 @@
 #include "sign_envelope_dev.h"
 #include "wave_fe_dev.h"
 #include "wire_dev.h"
+#include "wire_recode_dev.h"
 #include "cert_wave_dev.h"
 #include "cert_verdict_dev.h"
 #include "cert_dedup_dev.h"
@@ -1357,6 +1359,32 @@ __global__ void __launch_bounds__(64) wire_parse_kernel(const uint8_t *__restric
   const uint8_t *m = staged ? lbuf + (o0 - b0) : wire_bytes + o0;
   wire::process_row(m, o1 - o0, rows + row, digest32 + 32ull * row, sig65 + 65ull * row, from20 + 20ull * row,
                     seal65 + 65ull * row, pre_flags + row);
+}
+// IBFT_FLAG_WIRE_RECODE: the second walk, over the rows wire_parse_kernel marked NEEDS_HOST (wire_recode_dev.h).  The same
+// grid; a wavefront with no such row leaves after one load per lane and a ballot — that is all a batch of canonical rows
+// pays.  Otherwise the wavefront's bytes are staged like above and the flagged lanes decode tolerantly, hash the canonical
+// re-encoding and overwrite their row's columns; a row outside the recode class is left as it was.
+__global__ void __launch_bounds__(64) wire_recode_kernel(const uint8_t *__restrict__ wire_bytes, const uint32_t *__restrict__ off,
+                                                         uint32_t n, wire::row_info *__restrict__ rows,
+                                                         uint8_t *__restrict__ digest32, uint8_t *__restrict__ sig65,
+                                                         uint8_t *__restrict__ from20, uint8_t *__restrict__ seal65,
+                                                         uint8_t *__restrict__ pre_flags) {
+  __shared__ __attribute__((aligned(16))) uint8_t lbuf[WIRE_LDS_BYTES + 16];
+  const uint32_t row0 = blockIdx.x * 64u, lane = threadIdx.x, row = row0 + lane;
+  const bool flagged = row < n && rows[row].status == wire::STATUS_NEEDS_HOST;
+  if (!__any(flagged ? 1 : 0)) return;
+  const uint32_t cnt = n - row0 < 64u ? n - row0 : 64u;
+  const uint32_t b0 = off[row0] & ~15u, b1 = off[row0 + cnt];
+  const bool staged = b1 - b0 <= WIRE_LDS_BYTES;  // wave-uniform
+  if (staged) {
+    cw::stage_bytes(lbuf, wire_bytes + b0, b1 - b0, lane);
+    __syncthreads();
+  }
+  if (!flagged) return;
+  const uint32_t o0 = off[row], o1 = off[row + 1];
+  const uint8_t *m = staged ? lbuf + (o0 - b0) : wire_bytes + o0;
+  wire::recode_row(m, o1 - o0, rows + row, digest32 + 32ull * row, sig65 + 65ull * row, from20 + 20ull * row,
+                   seal65 + 65ull * row, pre_flags + row);
 }
 // After the sender pass: make the COMMIT seals found by wire_parse_kernel the resident seal batch
 // (hash column ← proposal hash, signature column ← committed seal, From stays).  Rows that are not

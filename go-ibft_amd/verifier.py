@@ -24,6 +24,7 @@ from .build import LIB
 FLAG_STRICT_LOW_S = 1
 FLAG_PUBKEY_CACHE = 2   # warm path: verify against per-validator tables once a key has been recovered
 FLAG_CERT_DEDUP = 4     # certificate calls judge each distinct (digest, signature, From) once (IBFT_CERT_DEDUP=0|1 overrides)
+FLAG_WIRE_RECODE = 8    # the flat wire calls also judge non-canonical PREPARE / COMMIT encodings (IBFT_WIRE_RECODE=0|1 overrides)
 ROW_NIL, ROW_BADLEN, ROW_HASH_BAD = 1, 2, 4
 KERNEL_AUTO, KERNEL_LANE, KERNEL_WAVE = 0, 1, 2
 SIGN_NONCE_KECCAK, SIGN_NONCE_RFC6979 = 0, 1   # IBFT_SIGN_NONCE_*
@@ -55,7 +56,7 @@ EXPORTS = [
     "ibft_verify_block_seals_sets_raw", "ibft_recover_block_seals_sets_raw", "ibft_block_seals_submit_sets",
     "ibft_block_seals_submit_sets_raw", "ibft_recover_block_seals_submit_sets", "ibft_recover_block_seals_submit_sets_raw",
     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
-    "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form",
+    "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
@@ -72,7 +73,7 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_verify_block_seals_sets_raw", "ibft_recover_block_seals_sets_raw", "ibft_block_seals_submit_sets",
                     "ibft_block_seals_submit_sets_raw", "ibft_recover_block_seals_submit_sets", "ibft_recover_block_seals_submit_sets_raw",
                     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
-                    "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form"}
+                    "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
 ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
@@ -283,6 +284,8 @@ def load_library() -> C.CDLL:
                                                    vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "ibft_cert_stats"):
         L.ibft_cert_stats.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4
+    if hasattr(L, "ibft_wire_stats"):
+        L.ibft_wire_stats.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 3
     L.ibft_set_validators_u256.argtypes = [vp, C.c_uint64, vp, vp, C.c_size_t]
     L.ibft_last_tally_wide.argtypes = [vp, C.POINTER(TallyWide)]
     L.ibft_shard_range.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -1046,6 +1049,15 @@ class BatchVerifier:
             raise GpuUnavailable("this build of libibftgpu.so has no ibft_cert_stats — rebuild")
         v = [C.c_uint32() for _ in range(4)]
         self._chk(self._L.ibft_cert_stats(self._h, *(C.byref(x) for x in v)), "ibft_cert_stats")
+        return tuple(int(x.value) for x in v)
+
+    def wire_stats(self):
+        """ibft_wire_stats, of the last is_valid_validator_wire / verify_messages_wire call: (rows, rows judged through the recode
+        class — FLAG_WIRE_RECODE; their rows carry pad[0] = 1 —, rows left NEEDS_HOST).  A diagnostic: it copies the parse results."""
+        if not hasattr(self._L, "ibft_wire_stats"):
+            raise GpuUnavailable("this build of libibftgpu.so has no ibft_wire_stats — rebuild")
+        v = [C.c_uint32() for _ in range(3)]
+        self._chk(self._L.ibft_wire_stats(self._h, *(C.byref(x) for x in v)), "ibft_wire_stats")
         return tuple(int(x.value) for x in v)
 
     def wire_stage_seals(self):

@@ -124,6 +124,15 @@ extern "C" {
  * nothing measurable with known keys; where almost everything repeats (a round change at N = 1 024, 467 172 rows) the
  * call takes 6.7 instead of 11.3 ms cold, 6.5 instead of 8.2 ms with known keys.                   */
 #define IBFT_FLAG_CERT_DEDUP 4u
+/* The flat wire calls (ibft_verify_senders_wire, ibft_verify_messages_wire) also judge PREPARE / COMMIT messages in a
+ * non-canonical encoding — fields out of order, padded varints, explicit defaults, repeated fields — instead of marking
+ * them IBFT_WIRE_NEEDS_HOST: see "the recode class" at ibft_verify_senders_wire.  Off by default; the environment variable
+ * IBFT_WIRE_RECODE=0|1, read at ibft_ctx_create, overrides the flag either way.  Off: no extra launch, every output bit
+ * for bit as before.  On: one more small launch per call; a batch of canonical rows gives bit for bit the flag-off
+ * outputs.  N = 4 096 COMMIT messages, known keys: a canonical batch 0.300 ms off, 0.304 ms on (two
+ * flag-off legs of the same loop differ by 0.001); every row in another encoding 0.41 ms, against 1.67 ms through host
+ * decode and re-marshal.  The certificate calls ignore the flag; there is no streamed form.                                      */
+#define IBFT_FLAG_WIRE_RECODE 8u
 
 /* pre_flags bits */
 #define IBFT_ROW_NIL 0x01u
@@ -591,7 +600,34 @@ int ibft_verify_senders(ibft_ctx *ctx, const uint8_t *payload, const uint32_t *o
  * / committed seal and verifies the sender.  out_rows (n entries, may be NULL) tells the host what
  * was found.  A row with status IBFT_WIRE_NEEDS_HOST (PREPREPARE / ROUND_CHANGE payloads, unknown
  * fields, any non-canonical encoding, truncated input) is NOT judged: its verdict bit is 0 and the
- * caller must decode it with the protobuf runtime and use ibft_verify_senders.                  */
+ * caller must decode it with the protobuf runtime and use ibft_verify_senders.
+ *
+ * THE RECODE CLASS (IBFT_FLAG_WIRE_RECODE; csrc/wire_recode_dev.h).  The reference signs proto.Marshal of the DECODED
+ * message with its signature cleared, so a PREPARE / COMMIT message in another encoding is as valid as the canonical one,
+ * and anybody who can reach the transport could otherwise push a whole round onto the per-message host route.  With the
+ * flag on, both flat wire calls run a second walk over the rows the canonical walk marked NEEDS_HOST, before the verdict
+ * launch and on the same stream.  A row in the class is decoded tolerantly, its canonical PayloadNoSig is hashed on the
+ * device, and EVERY output of the call — masks, rows, classes, tally, the columns ibft_wire_stage_seals reads — is what
+ * the flag-off call returns for the same batch with that row replaced by its canonical re-encoding (the message
+ * re-marshalled, signature kept).  The one exception: ibft_wire_row_t.pad[0] is 1 for such a row.  A row outside the class
+ * keeps NEEDS_HOST and verdict 0, exactly as without the flag.  The rule, at each of the three levels of a flat message
+ * (IbftMessage, View, the PrepareMessage / CommitMessage body):
+ *   - every tag is ONE byte and names a field of that message with that field's wire type — IbftMessage: 1, 2, 3, 6, 7
+ *     LEN, 4 VARINT; View: 1, 2 VARINT; body: 1 LEN, and 2 LEN in a CommitMessage only.  Field 5 or 8 anywhere in the
+ *     message, any other field number, a wrong wire type, a multi-byte tag: NEEDS_HOST;
+ *   - varints may be padded: VALUES are 1 to 10 bytes (a tenth byte above 1 or an eleventh byte: NEEDS_HOST), LENGTH
+ *     PREFIXES 1 to 5 bytes (a sixth byte: NEEDS_HOST — protobuf runtimes differ there: upb refuses a longer prefix, Go's
+ *     protowire takes ten); a length that leaves its enclosing message: NEEDS_HOST;
+ *   - fields come in any order and any number of times.  For a scalar or bytes field the last occurrence wins;
+ *     occurrences of View merge, per field the last wins, and a present but empty View is kept (0a 00); an occurrence of
+ *     the other oneof member discards what the earlier member held, a further occurrence of the same member merges into
+ *     it;
+ *   - explicit zero scalars and empty byte strings are defaults and vanish in the re-encoding; an empty signature is no
+ *     signature;
+ *   - after decoding, the canonical walk's own limits: type <= 255 (of the decoded 64-bit value, not truncated), proposal
+ *     hash <= 32 bytes; otherwise NEEDS_HOST.
+ * Unknown fields stay out of the class although Go re-emits them behind the known ones; the restrictions above are where
+ * decoders may differ.                                                                           */
 #define IBFT_WIRE_OK 0u
 #define IBFT_WIRE_NEEDS_HOST 1u
 typedef struct {
@@ -606,7 +642,8 @@ typedef struct {
   uint8_t from_len, sig_len; /* 255 = more                                                   */
   uint8_t from[20];
   uint8_t proposal_hash[32];
-  uint8_t pad[4];
+  uint8_t pad[4];            /* the first byte is `recoded`: 1 when the row was judged through the recode class
+                                (IBFT_FLAG_WIRE_RECODE), else 0; the other three are 0          */
 } ibft_wire_row_t;
 int ibft_verify_senders_wire(ibft_ctx *ctx, const uint8_t *wire, const uint32_t *off, size_t n,
                              uint64_t *out_mask, ibft_wire_row_t *out_rows, ibft_tally_t *tally);
@@ -615,6 +652,13 @@ int ibft_verify_senders_wire(ibft_ctx *ctx, const uint8_t *wire, const uint32_t 
  * ibft_seals_launch + ibft_seals_fetch — a2 without another upload.  Rows that are not canonical
  * COMMIT messages (type COMMIT, 32-byte hash, 65-byte seal, 20-byte From) are pre-flagged.      */
 int ibft_wire_stage_seals(ibft_ctx *ctx);
+/* What the walks made of the rows of the LAST flat wire call of the context that succeeded (ibft_verify_senders_wire or
+ * ibft_verify_messages_wire): rows = n; recoded_rows = rows judged through the recode class (pad[0] = 1; always 0 without
+ * IBFT_FLAG_WIRE_RECODE); needs_host_rows = rows left IBFT_WIRE_NEEDS_HOST.  Counted when asked, from the parse results
+ * still on the device (one copy of 80 bytes per row: a diagnostic, not for the hot path).  Any pointer may be NULL; a NULL
+ * ctx: IBFT_E_INVAL; all zero before the first such call or after a certificate call has reused the rows.  No new
+ * ibft_version(): a build without the symbol simply lacks it.                                                        */
+int ibft_wire_stats(ibft_ctx *ctx, uint32_t *rows, uint32_t *recoded_rows, uint32_t *needs_host_rows);
 
 /* a8 alone: HasQuorum over the rows whose bit is set in mask.                      */
 int ibft_tally(ibft_ctx *ctx, const uint8_t *sender20, const uint64_t *mask, size_t n,

@@ -82,10 +82,17 @@ type Options struct {
 	StrictLowS bool
 	KeyCache   bool
 	CertDedup  bool // FlagCertDedup: certificate calls judge each distinct (digest, signature, From) once
+	WireRecode bool // FlagWireRecode: the flat wire calls also judge non-canonical PREPARE / COMMIT encodings
 }
 
 // FlagCertDedup is IBFT_FLAG_CERT_DEDUP (Options.CertDedup sets it; the environment variable IBFT_CERT_DEDUP=0|1 overrides it).
 const FlagCertDedup = uint32(C.IBFT_FLAG_CERT_DEDUP)
+
+// FlagWireRecode is IBFT_FLAG_WIRE_RECODE (Options.WireRecode sets it; the environment variable IBFT_WIRE_RECODE=0|1 overrides
+// it): VerifySendersWire / VerifyMessagesWire judge a PREPARE / COMMIT message whose encoding is not the canonical one — fields
+// out of order, padded varints, explicit defaults, repeated fields: the recode class of include/ibftgpu.h — as its canonical
+// re-encoding instead of marking it WireNeedsHost.  Off by default.
+const FlagWireRecode = uint32(C.IBFT_FLAG_WIRE_RECODE)
 
 // abiVersion is what this binding was written against (include/ibftgpu.h: ibft_version; 2 = ibft_tally_t with
 // proposer_rows, 56 bytes: an older library would write a shorter struct; 3 = the staged / pipelined pass calls,
@@ -105,6 +112,9 @@ func New(o Options) (*Ctx, error) {
 	}
 	if o.CertDedup {
 		cfg.flags |= C.IBFT_FLAG_CERT_DEDUP
+	}
+	if o.WireRecode {
+		cfg.flags |= C.IBFT_FLAG_WIRE_RECODE
 	}
 	var h *C.ibft_ctx
 	if rc := C.ibft_ctx_create(&cfg, &h); rc != C.IBFT_OK {
@@ -1028,6 +1038,14 @@ func (c *Ctx) JudgeCertificatesWire(wire []byte, off []uint32, rowsCap, certsCap
 	return certs[:int(nCerts)], int(nRows), c.check(rc)
 }
 
+// WireStats reports on the context's last flat wire call (ibft_wire_stats): its rows, the rows judged through the recode class
+// (FlagWireRecode; 0 without it) and the rows left WireNeedsHost.  A diagnostic: the library copies the parse results to count.
+func (c *Ctx) WireStats() (rows, recoded, needsHost uint32, err error) {
+	var r, d, h C.uint32_t
+	rc := C.ibft_wire_stats(c.h, &r, &d, &h)
+	return uint32(r), uint32(d), uint32(h), c.check(rc)
+}
+
 // CertStats reports on the context's last certificate call (ibft_cert_stats): the tree's rows, the rows that were judged (no
 // pre-flag), the rows actually given to the verdict kernels, and the rows the dedup table could not place.  Without
 // FlagCertDedup verdict == judged and unplaced == 0.
@@ -1098,7 +1116,8 @@ type WireRow struct {
 	HashLen, SealLen, FromLen, SigLen        uint8
 	From                                     [20]byte
 	ProposalHash                             [32]byte
-	_                                        [4]byte
+	Recoded                                  uint8 // 1: judged through the recode class (FlagWireRecode), pad[0] of ibft_wire_row_t
+	_                                        [3]byte
 }
 
 // WireNeedsHost marks a row the device did not judge (PREPREPARE / ROUND_CHANGE payloads, unknown
@@ -1341,6 +1360,9 @@ func NewGroup(devices []int32, o Options) (*Group, error) {
 	}
 	if o.CertDedup {
 		flags |= C.IBFT_FLAG_CERT_DEDUP
+	}
+	if o.WireRecode {
+		flags |= C.IBFT_FLAG_WIRE_RECODE
 	}
 	var g *C.ibft_group
 	rc := C.ibft_group_create((*C.int32_t)(unsafe.Pointer(&devices[0])), C.uint32_t(len(devices)), flags,
