@@ -217,6 +217,27 @@ extern "C" int devtest_wave_fe(int op, int jobs, const uint32_t *a, const uint32
   (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
   return rc;
 }
+// modinv_wave (the outlined modinv_wave_fn) by itself: one wavefront per job.  layout 0: the job's one value in the whole
+// wavefront, 1: four values, one per row of sixteen lanes.  Every lane stores its answer: out = jobs × 64 × 32 bytes.
+__global__ void __launch_bounds__(64) devtest_wave_modinv_kernel(int which, int layout, const uint8_t *x, uint8_t *out) {
+  const wv::wk k = wv::wk_init();
+  const uint8_t *src = layout ? x + 128 * (size_t)blockIdx.x + 32 * k.row : x + 32 * (size_t)blockIdx.x;
+  const u256 v = from_be32(src);
+  const u256 r = which == 0 ? wv::modinv_wave<ModP>(v, k) : wv::modinv_wave<ModN>(v, k);  // `which` is uniform
+  to_be32(out + 32 * ((size_t)64 * blockIdx.x + threadIdx.x), r);
+}
+extern "C" int devtest_wave_modinv(int which, int layout, int jobs, const uint8_t *x, uint8_t *out) {
+  if (jobs <= 0 || !x || !out) return -3;
+  const size_t in_bytes = (size_t)(layout ? 128 : 32) * jobs, out_bytes = (size_t)2048 * jobs;
+  uint8_t *dx = dev_copy(x, in_bytes), *dout = nullptr;
+  if (!dx || hipMalloc(&dout, out_bytes) != hipSuccess) return -1;
+  (void)hipMemset(dout, 0xA5, out_bytes);
+  devtest_wave_modinv_kernel<<<jobs, 64>>>(which, layout ? 1 : 0, dx, dout);
+  int rc = hipDeviceSynchronize() == hipSuccess ? 0 : -2;
+  if (rc == 0) (void)hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(dx); (void)hipFree(dout);
+  return rc;
+}
 extern "C" int devtest_wave_pt(int op, int jobs, const uint32_t *p, const uint32_t *q, uint32_t *out) {
   uint32_t *dp = dev_copy(p, (size_t)124 * jobs), *dq = dev_copy(q, (size_t)124 * jobs), *dout;
   if (!dp || !dq || hipMalloc(&dout, (size_t)496 * jobs) != hipSuccess) return -1;

@@ -10,6 +10,22 @@
 
 #include <vector>
 
+// modinv<MOD>'s batches on record: dev_modinv_trace points this at its caller's buffer around one call, every other call
+// of modinv<MOD> (the signer's) finds it null.  Row b: d[9] e[9] f[9] g[9] ζ after batch b.
+static thread_local int32_t *g_modinv_trace = nullptr;
+static void modinv_trace_batch(int b, int32_t zeta, const int32_t *d, const int32_t *e, const int32_t *f, const int32_t *g) {
+  if (!g_modinv_trace) return;
+  int32_t *o = g_modinv_trace + 37 * b;
+  for (int i = 0; i < 9; i++) {
+    o[i] = d[i];
+    o[9 + i] = e[i];
+    o[18 + i] = f[i];
+    o[27 + i] = g[i];
+  }
+  o[36] = zeta;
+}
+#define IBFT_MODINV_TRACE_BATCH(b, zeta, d, e, f, g) modinv_trace_batch(b, zeta, (d).v, (e).v, (f).v, (g).v);
+
 #include "recover_dev.h"
 #include "verify_dev.h"
 #include "sign_dev.h"
@@ -69,6 +85,25 @@ int dev_divsteps_agree(int32_t zeta, uint32_t f0, uint32_t g0) {
          za == zc && a.u == c.u && a.v == c.v && a.q == c.q && a.r == c.r;
 }
 void dev_sc_inv_safegcd(const uint8_t *a, uint8_t *out) { sout(out, secp::sc_inv_safegcd(sin_(a))); }
+// the inversion forms by themselves on a canonical x (which: 0 = p, 1 = n).  form 0: modinv<MOD> (the signer's, devtest ops
+// 9 and 10), 1: modinv_shared<MOD> (the run-time modulus: what the lane and group kernels call)
+void dev_modinv(int form, int which, const uint8_t *x32, uint8_t *out32) {
+  const u256 x = secp::from_be32(x32);
+  u256 r;
+  if (form == 0)
+    r = which == 0 ? secp::modinv<secp::ModP>(x) : secp::modinv<secp::ModN>(x);
+  else
+    r = which == 0 ? secp::modinv_shared<secp::ModP>(x) : secp::modinv_shared<secp::ModN>(x);
+  secp::to_be32(out32, r);
+}
+// modinv<MOD>(x) with the canonical limbs of d, e, f, g and ζ after each of its 20 batches: trace = 20 × 37 int32
+void dev_modinv_trace(int which, const uint8_t *x32, uint8_t *out32, int32_t *trace) {
+  g_modinv_trace = trace;
+  const u256 x = secp::from_be32(x32);
+  const u256 r = which == 0 ? secp::modinv<secp::ModP>(x) : secp::modinv<secp::ModN>(x);
+  g_modinv_trace = nullptr;
+  secp::to_be32(out32, r);
+}
 // GLV split: out = k1(32 BE) ‖ k2(32 BE), returns neg1 | neg2<<1
 int dev_glv_split(const uint8_t *k, uint8_t *out64) {
   secp::glv_split s = secp::sc_split_lambda(secp::from_be32(k));

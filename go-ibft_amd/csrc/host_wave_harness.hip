@@ -10,6 +10,24 @@
 
 #include <vector>
 
+#include "wave_emul.h"
+
+// modinv_wave_body's batches on record: wvh_modinv_trace points this at its caller's buffer around one emulated wavefront,
+// every other run finds it null.  Batch b: d[64] e[64] f[64] g[64] ζ[64], one int32 per lane.
+static thread_local int32_t *g_modinv_trace = nullptr;
+static thread_local int g_modinv_batches = 0;
+static void modinv_wave_trace_batch(int b, int32_t zeta, int32_t d, int32_t e, int32_t f, int32_t g) {
+  if (!g_modinv_trace) return;
+  int32_t *o = g_modinv_trace + 320 * b + wave_emul::lane();
+  o[0] = d;
+  o[64] = e;
+  o[128] = f;
+  o[192] = g;
+  o[256] = zeta;
+  g_modinv_batches = b + 1;
+}
+#define IBFT_MODINV_WAVE_TRACE_BATCH(b, zeta, d, e, f, g) modinv_wave_trace_batch(b, zeta, d, e, f, g);
+
 #include "wave_fe_dev.h"
 
 using secp::u256;
@@ -267,6 +285,25 @@ void wvh_modinv(int which, const uint8_t *x32, uint8_t *out64x32) {
 void wvh_modinv_rows(int which, const uint8_t *x4x32, uint8_t *out64x32) {
   inv_job j{x4x32, out64x32, which};
   wave_emul::run(lane_inv_rows, &j);
+}
+// the same with every lane's d, e, f, g and ζ after each batch the wavefront takes: trace = 20 × 5 × 64 int32; returns
+// the number of batches taken
+int wvh_modinv_trace(int which, const uint8_t *x4x32, uint8_t *out64x32, int32_t *trace) {
+  inv_job j{x4x32, out64x32, which};
+  g_modinv_trace = trace;
+  g_modinv_batches = 0;
+  wave_emul::run(lane_inv_rows, &j);
+  g_modinv_trace = nullptr;
+  return g_modinv_batches;
+}
+// many wavefronts in one call, with the arguments of devtest.hip's devtest_wave_modinv.  layout 0: one value per job for
+// the whole wavefront (x = jobs × 32 bytes), 1: four values, one per row (x = jobs × 4 × 32); out = jobs × 64 × 32
+int wvh_modinv_batch(int which, int layout, int jobs, const uint8_t *x, uint8_t *out) {
+  for (int i = 0; i < jobs; i++) {
+    inv_job j{x + (size_t)(layout ? 128 : 32) * i, out + (size_t)2048 * i, which};
+    wave_emul::run(layout ? lane_inv_rows : lane_inv, &j);
+  }
+  return 0;
 }
 void wvh_verify_known(const uint32_t *qtab, const uint8_t *hash32, const uint8_t *sig65, uint32_t flags, int *ok64) {
   vk_job j{qtab, hash32, sig65, flags, ok64};

@@ -277,6 +277,15 @@ HD void normalize_30(s30 &r, bool neg) {
   }
 }
 
+// (test hooks: the host harnesses define these to record d, e, f, g and ζ after every batch — tests/modinv_model.py is
+// compared with them limb for limb; they expand to nothing in every other build)
+#ifndef IBFT_MODINV_TRACE_BATCH
+#define IBFT_MODINV_TRACE_BATCH(b, zeta, d, e, f, g)
+#endif
+#ifndef IBFT_MODINV_WAVE_TRACE_BATCH
+#define IBFT_MODINV_WAVE_TRACE_BATCH(b, zeta, d, e, f, g)
+#endif
+
 // x⁻¹ mod M for canonical x in [0, M); 0 maps to 0 (like the Fermat chain).
 // Constant-time batches.  (Round 4 tried divsteps_30_lockstep here too: with 64 different values in lockstep a batch
 // needs ≈14 rounds of 33 instructions instead of 30 × 20, but the loop inside the 20 batches pushes the lane / group
@@ -298,6 +307,7 @@ HD u256 modinv(const u256 &x) {
     zeta = divsteps_30(zeta, (uint32_t)f.v[0], (uint32_t)g.v[0], t);
     update_de_30<MOD>(d, e, t);
     update_fg_30(f, g, t);
+    IBFT_MODINV_TRACE_BATCH(b, zeta, d, e, f, g)
   }
   // g = 0 and f = ±gcd; the inverse is d·sign(f)
   normalize_30<MOD>(d, f.v[8] < 0);

@@ -771,6 +771,7 @@ WVF u256 modinv_wave_body(const u256 &x, bool is_p, uint32_t li) {
     e = ne;
     f = nf;
     g = ng;
+    IBFT_MODINV_WAVE_TRACE_BATCH(b, zeta, d, e, f, g)
     if (!any(g != 0)) break;
   }
   // collect d (and the sign of f = ±1: −1 ≡ 3 mod 4 whatever the limb form), ripple the carries once
