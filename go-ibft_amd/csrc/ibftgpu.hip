@@ -33,6 +33,11 @@ struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
 };
+void release(DevBuf &b) {
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+}
 
 }  // namespace
 
@@ -106,6 +111,52 @@ struct ValFamily {
   DevBuf d_setidx, d_meta, d_power, d_quorum, d_seen, d_bset;
   std::vector<uint64_t> quorum;  // n_sets × TALLY_SUM_WORDS
   uint64_t device_bytes = 0;
+};
+
+// The per-block records of a block batch, one 4-word record per block: the tally delivers them into mapped pinned host memory
+// where the device can write it (h, through map; grown on demand), through d and a copy behind the tally otherwise.
+struct BlockRecords {
+  DevBuf d;
+  uint64_t *h = nullptr, *map = nullptr;
+  size_t blocks = 0;
+};
+// One of the two slots of the streamed chain sync (ibft_block_seals_submit … / _collect): everything a batch in flight reads
+// and delivers beyond the verdict words, PRIVATE to its slot, so that the kernels of batch k + 1 never write what batch k
+// still has to deliver.  All of it is free again when batch k − 2 has been collected.
+struct BlockSlot {
+  BlockRecords rec;
+  uint32_t rows = 0, blocks = 0, kind = 0;  // kind: IBFT_BATCH_* of the batch (0 for a batch of ibft_block_seals_submit)
+  uint64_t quorum[2] = {0, 0};       // the quorum a batch was judged under (the set current at its submit)
+  // the proposals as given (bytes with 256 of slack, offsets, rounds: two slots double the device bytes proposals take, each
+  // slot bounded by IBFT_PROPOSAL_BYTES_MAX), the blocks' digests (computed, or the uploaded hashes of a hashes-given batch)
+  // that block_head_kernel reads and never writes, and for a recover batch the columns the emitting kernels fill — swapped
+  // in for d_signer_out / d_vidx while the batch's kernels are enqueued (emit_columns_view)
+  DevBuf praw, proff, pround, phash, signer, vidx;
+  // … and the page-locked buffers digests, signers and indices come back into, on ostream: behind ev_dig (the digests exist)
+  // and ev (the tally is done); ev_out is behind the last copy, and the collect waits for it when has_out says there was one
+  uint8_t *h_hash = nullptr, *h_signer = nullptr;
+  int32_t *h_vidx = nullptr;
+  size_t h_hash_blocks = 0, h_rows = 0, h_vidx_rows = 0;
+  hipEvent_t ev = nullptr, ev_dig = nullptr, ev_out = nullptr;
+  bool has_out = false;
+  // A batch judged under a family of sets (the _sets submits, IBFT_BATCH_SETS in kind): its block_set column lies in a buffer
+  // of the SLOT — the copy of batch k + 1 must not overwrite what the tally of batch k reads, so fam.d_bset will not do — and
+  // the quorum words its collect hands out are kept on the host, so that what the collect DELIVERS never comes from c->fam
+  // (the family may have been replaced since; only the table build behind the delivery counts against the union installed
+  // then): setq holds the two low quorum words per BLOCK when setidx is empty, per SET of the family of the submit when
+  // setidx holds the blocks' set indices — whichever of the two is smaller for the batch.
+  DevBuf bset;
+  std::vector<uint64_t> setq;
+  std::vector<uint32_t> setidx;
+
+  void release_all() {  // device buffers, pinned buffers, events: everything the slot owns (ibft_ctx_destroy)
+    for (DevBuf *b : {&rec.d, &praw, &proff, &pround, &phash, &signer, &vidx, &bset}) release(*b);
+    for (void *h : {(void *)rec.h, (void *)h_hash, (void *)h_signer, (void *)h_vidx})
+      if (h) (void)hipHostFree(h);
+    for (hipEvent_t e : {ev, ev_dig, ev_out})
+      if (e) (void)hipEventDestroy(e);
+  }
+  uint64_t block_set_bytes() const { return bset.cap; }  // (ibft_validator_sets_info)
 };
 
 struct ibft_ctx {
@@ -202,11 +253,9 @@ struct ibft_ctx {
   uint32_t power_words = 1;                          // 64-bit words per voting power: 1 (u64) or 4 (256-bit)
   uint64_t quorum_w[ibftk::TALLY_SUM_WORDS] = {0};   // ⌊2·total/3⌋+1, little-endian words
   DevBuf d_seen, d_acc, d_quorum;                    // tally: distinct-sender bitmap, launch-wide sums + ticket, quorum words
-  // chain sync (ibft_verify_block_seals): the blocks' hashes and row offsets, and one 4-word record per block, delivered into
-  // mapped pinned host memory when the device can write it (h_btally / dh_btally, grown on demand) or through d_btally
-  DevBuf d_bhash, d_boff, d_btally;
-  uint64_t *h_btally = nullptr, *dh_btally = nullptr;
-  size_t h_btally_blocks = 0;
+  // chain sync (ibft_verify_block_seals): the blocks' hashes and row offsets, and the records of the synchronous calls
+  DevBuf d_bhash, d_boff;
+  BlockRecords brec;
   // Streamed chain sync (ibft_block_seals_submit / _collect): at most two batches in flight.  Batch k is copied on the copy
   // stream into the SPARE column set — d_sig_nx / d_signer_nx / d_pre_nx of the seal pipeline plus a second offset buffer —
   // while the kernels of batch k − 1 read the resident set; the submit then swaps the two sets, exactly as
@@ -215,45 +264,18 @@ struct ibft_ctx {
   // validator indices, d_seen and the ticket word in d_acc exist once and rely on that order — and any other entry point that
   // enqueues on the main stream is behind the batches in flight by the same order, their results already on the way to
   // their slots.  Results: verdict words in the seal pipeline's mapped slots (p_mask; the two pipelines are never mixed),
-  // {keys learned, a learned slot} in p_tally[s][4], the per-block records in bs_tally[s] (mapped) or through bs_dtally[s].
-  DevBuf d_boff_nx, bs_dtally[2];
-  uint64_t *bs_tally[2] = {nullptr, nullptr}, *bs_dtally_map[2] = {nullptr, nullptr};
-  size_t bs_tally_blocks[2] = {0, 0};
-  hipEvent_t ev_bs[2] = {nullptr, nullptr};
-  uint32_t bs_issued = 0, bs_collected = 0, bs_rows[2] = {0, 0}, bs_blocks[2] = {0, 0};
-  uint64_t bs_quorum[2][2] = {{0, 0}, {0, 0}};  // the quorum a batch was judged under (the set current at its submit)
-  // All four streamed submits (ibft_block_seals_submit[_raw], ibft_recover_block_seals_submit[_raw]; bs_kind: IBFT_BATCH_* of the
-  // batch in each slot, 0 for a batch of ibft_block_seals_submit).  What a batch reads and delivers beyond verdict words and
-  // records is PRIVATE to its slot, so the kernels of batch k + 1 never write what batch k still has to deliver: the proposals
-  // as given (bytes with 256 of slack, offsets, rounds: two slots double the device bytes proposals take, each slot bounded by
-  // IBFT_PROPOSAL_BYTES_MAX), the blocks' digests (computed, or the uploaded hashes of a hashes-given batch) that
-  // block_head_kernel reads and never writes, and for a recover batch the columns the emitting kernels fill —
-  // swapped in for d_signer_out / d_vidx while the batch's kernels are enqueued.  Digests, signers and indices come back on
-  // ostream — NOT the copy stream, whose next command is the upload of batch k + 1 and must not wait for batch k's tally —
-  // behind ev_bs_dig (the digests exist) and ev_bs (the tally is done) into page-locked buffers; ev_bs_out is behind the last copy.
-  // ostream, ev_bs_dig and ev_bs_out are created by the first submit of ANY kind: a context that only ever calls
-  // ibft_block_seals_submit has them too and never puts a command on them.
-  DevBuf bs_praw[2], bs_proff[2], bs_pround[2], bs_phash[2], bs_signer[2], bs_vidx[2];
-  uint8_t *bs_h_hash[2] = {nullptr, nullptr}, *bs_h_signer[2] = {nullptr, nullptr};
-  int32_t *bs_h_vidx[2] = {nullptr, nullptr};
-  size_t bs_h_hash_blocks[2] = {0, 0}, bs_h_rows[2] = {0, 0}, bs_h_vidx_rows[2] = {0, 0};
-  uint32_t bs_kind[2] = {0, 0};
-  // A batch judged under a family of sets (the _sets submits, IBFT_BATCH_SETS in bs_kind): its block_set column lies in a
-  // buffer of the SLOT — the copy of batch k + 1 must not overwrite what the tally of batch k reads, so fam.d_bset will not
-  // do — and the quorum words its collect hands out are kept on the host, so that what the collect DELIVERS never comes from
-  // c->fam (the family may have been replaced since; only the table build behind the delivery counts against the union
-  // installed then): bs_setq[s] holds the two low quorum words per BLOCK when bs_setidx[s] is empty, per SET of the family
-  // of the submit when bs_setidx[s] holds the blocks' set indices — whichever of the two is smaller for the batch.
-  DevBuf bs_bset[2];
-  std::vector<uint64_t> bs_setq[2];
-  std::vector<uint32_t> bs_setidx[2];
-  bool bs_has_out[2] = {false, false};  // the batch put copies on ostream: its collect waits for ev_bs_out too
+  // {keys learned, a learned slot} in p_tally[s][4], everything else in bs[s] (BlockSlot).  Digests, signers and indices come
+  // back on ostream — NOT the copy stream, whose next command is the upload of batch k + 1 and must not wait for batch k's
+  // tally.  ostream and the slots' events are created by the first submit of ANY kind: a context that only ever calls
+  // ibft_block_seals_submit has them too and never puts a command on ostream.
+  DevBuf d_boff_nx;
+  BlockSlot bs[2];
+  uint32_t bs_issued = 0, bs_collected = 0;
   hipStream_t ostream = nullptr;
-  hipEvent_t ev_bs_dig[2] = {nullptr, nullptr}, ev_bs_out[2] = {nullptr, nullptr};
   bool stream_digest_copy = false;  // IBFT_STREAM_DIGEST=copy|main: the stream proposal_digest_kernel of a streamed batch runs on
   // Chain sync from the proposals (ibft_proposal_hashes, the _raw block calls): the caller's proposals as they are — bytes,
   // offsets, rounds — in buffers of their own (grown on demand and kept, like d_payload; the bytes carry 256 of slack), the n
-  // digests proposal_digest_kernel writes (what block_rows_kernel then reads in place of an uploaded d_bhash), and the pinned
+  // digests proposal_digest_kernel writes (what block_head_kernel then reads in place of an uploaded d_bhash), and the pinned
   // mirror the digests come back through.  None of it is the remembered proposal of ibft_proposal_hash (d_H, hashed_proposal).
   DevBuf d_praw, d_proff, d_pround, d_phash;
   uint8_t *h_phash = nullptr;
@@ -422,12 +444,6 @@ int grow_pinned(void **p, size_t *cap, size_t want, size_t elem) {
   return IBFT_OK;
 }
 
-void release(DevBuf &b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-}
-
 int mask_words(size_t n) { return (int)((n + 63) / 64); }
 
 int alloc_rows(ibft_ctx *c, uint32_t rows) {
@@ -510,19 +526,6 @@ bool next_pass_timed(ibft_ctx *c) {
   return c->time_every && (c->pass_counter++ % c->time_every) == 0;
 }
 
-// The row offsets of a block batch, checked the way every block call checks them: widest = rows of the largest block (picks
-// the tally's workgroup size), n = rows of the batch.
-int check_seal_offsets(const ibft_ctx *c, const uint32_t *seal_off, size_t n_blocks, uint32_t *widest, size_t *n) {
-  if (!c || !seal_off || seal_off[0] != 0) return IBFT_E_INVAL;
-  if (n_blocks > c->max_rows) return IBFT_E_TOOBIG;  // (max_rows never changes after ibft_ctx_create)
-  *widest = 0;
-  for (size_t b = 0; b < n_blocks; b++) {
-    if (seal_off[b + 1] < seal_off[b]) return IBFT_E_INVAL;
-    *widest = std::max(*widest, seal_off[b + 1] - seal_off[b]);
-  }
-  *n = seal_off[n_blocks];
-  return *n > c->max_rows ? IBFT_E_TOOBIG : IBFT_OK;
-}
 // The segmented tally's records (4 words per block) → the caller's ibft_tally_t; quorum_of_block(b): the two low quorum
 // words block b was judged under.  No rows at all: every block is empty, power 0 < quorum.
 template <class Q>
@@ -589,8 +592,8 @@ struct ctx_lock {
 // as part of "the validator set" belongs in exchange().
 // NOT exchanged — they stay the SINGLE set's while a view lives, and nothing on the _sets path may read them: have_valset,
 // d_vpower, d_quorum, quorum_w, power_words, d_seen, h_vtab, valset_addrs, height, last_wide.  Their family counterparts are
-// read from c->fam directly (enqueue_block_tally: fam.d_power, d_quorum, power_words, d_seen, largest_set; block_seals_impl:
-// fam.have, fam.quorum, fam.n_sets).
+// read from c->fam directly (enqueue_block_tally: fam.d_power, d_quorum, power_words, d_seen, largest_set;
+// check_block_batch_locked: fam.have, fam.n_sets; block_seals_impl / the submit: fam.quorum).
 struct family_view {
   ibft_ctx *c;
   static void exchange(ibft_ctx *c) {
@@ -996,30 +999,18 @@ void note_proposer(ibft_ctx *c, const uint8_t *proposer20, bool shard = false) {
 
 int upload(ibft_ctx *c, DevBuf &b, const void *src, size_t bytes);
 
-// rows [row0, row0 + n) of the hash column: carried proposalHash → the digest the seal signs (no-op under the identity
-// convention); keep_copy: the carried hashes stay available in d_hash_copy (rows [0, n)) for the a1 compare
-int apply_seal_digest(ibft_ctx *c, uint32_t row0, uint32_t n, bool keep_copy) {
+// n hashes of a column, in place: carried proposalHash → the digest the seal signs (no-op under the identity convention).
+// The hash column's rows, or the blocks' hashes of a synchronous block call before they are spread over their rows.
+// keep_copy: the carried hashes stay available in d_hash_copy (rows [0, n)) for the a1 compare
+int apply_seal_digest(ibft_ctx *c, void *col, uint32_t n, bool keep_copy = false) {
   if (c->seal_digest_mode == 0 || n == 0) return IBFT_OK;
   ibftk::seal_digest_args a{};
-  a.hash32 = (uint8_t *)c->d_hash.p + 32ull * row0;
+  a.hash32 = (uint8_t *)col;
   if (keep_copy) {
     int rc = ensure(c, c->d_hash_copy, (size_t)n * 32);
     if (rc) return rc;
     a.copy32 = (uint8_t *)c->d_hash_copy.p;
   }
-  a.n = n;
-  memcpy(a.suffix_words, c->seal_suffix_words, sizeof a.suffix_words);
-  hipLaunchKernelGGL(ibftk::seal_digest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  return IBFT_OK;
-}
-
-// the same convention over the n hashes of another column: ibft_verify_block_seals converts the blocks' hashes before they are
-// spread over their rows — one Keccak per block instead of one per row
-int seal_digest_column(ibft_ctx *c, uint8_t *col, uint32_t n) {
-  if (c->seal_digest_mode == 0 || n == 0) return IBFT_OK;
-  ibftk::seal_digest_args a{};
-  a.hash32 = col;
   a.n = n;
   memcpy(a.suffix_words, c->seal_suffix_words, sizeof a.suffix_words);
   hipLaunchKernelGGL(ibftk::seal_digest_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
@@ -1819,11 +1810,10 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_xbuf[0], &c->d_xbuf[1], &c->d_xres[0], &c->d_xres[1], &c->d_set, &c->d_noseal, &c->d_class,
                     &c->d_cert_nodes, &c->d_cert_span, &c->d_cert_count, &c->d_cert_prop, &c->d_cert_masks, &c->d_cert_total,
                     &c->d_cert_slot, &c->d_cert_tiles, &c->d_cert_rec, &c->d_cert_recbase, &c->d_cert_dd_table, &c->d_cert_dd_slot, &c->d_cert_dd_pos, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
-                    &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->d_btally,
-                    &c->d_boff_nx, &c->bs_dtally[0], &c->bs_dtally[1], &c->d_praw, &c->d_proff, &c->d_pround,
-                    &c->d_phash, &c->bs_praw[0], &c->bs_praw[1], &c->bs_proff[0], &c->bs_proff[1], &c->bs_pround[0], &c->bs_pround[1],
-                    &c->bs_phash[0], &c->bs_phash[1], &c->bs_signer[0], &c->bs_signer[1], &c->bs_vidx[0], &c->bs_vidx[1], &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
-                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->bs_bset[0], &c->bs_bset[1], &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
+                    &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->brec.d,
+                    &c->d_boff_nx, &c->d_praw, &c->d_proff, &c->d_pround,
+                    &c->d_phash, &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
+                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
     release(*b);
   if (c->h_phash) (void)hipHostFree(c->h_phash);
   if (c->tstream) {
@@ -1865,16 +1855,8 @@ void ibft_ctx_destroy(ibft_ctx *c) {
     if (c->ev_pass[i]) (void)hipEventDestroy(c->ev_pass[i]);
   }
   if (c->h_mask) (void)hipHostFree(c->h_mask);
-  if (c->h_btally) (void)hipHostFree(c->h_btally);
-  for (int i = 0; i < 2; i++) {
-    if (c->bs_tally[i]) (void)hipHostFree(c->bs_tally[i]);
-    if (c->ev_bs[i]) (void)hipEventDestroy(c->ev_bs[i]);
-    if (c->bs_h_hash[i]) (void)hipHostFree(c->bs_h_hash[i]);
-    if (c->bs_h_signer[i]) (void)hipHostFree(c->bs_h_signer[i]);
-    if (c->bs_h_vidx[i]) (void)hipHostFree(c->bs_h_vidx[i]);
-    if (c->ev_bs_dig[i]) (void)hipEventDestroy(c->ev_bs_dig[i]);
-    if (c->ev_bs_out[i]) (void)hipEventDestroy(c->ev_bs_out[i]);
-  }
+  if (c->brec.h) (void)hipHostFree(c->brec.h);
+  for (BlockSlot &slot : c->bs) slot.release_all();
   if (c->ostream) (void)hipStreamDestroy(c->ostream);
   if (c->h_tally) (void)hipHostFree(c->h_tally);
   if (c->h_digest) (void)hipHostFree(c->h_digest);
@@ -2311,7 +2293,7 @@ int ibft_validator_sets_info(ibft_ctx *c, uint32_t *n_sets, uint32_t *union_size
   if (n_sets) *n_sets = c->fam.have ? c->fam.n_sets : 0;
   if (union_size) *union_size = c->fam.have ? c->fam.n_union : 0;
   // + the calls' block_set column, and those of the two slots of the streamed _sets submits
-  if (device_bytes) *device_bytes = c->fam.have ? c->fam.device_bytes + c->fam.d_bset.cap + c->bs_bset[0].cap + c->bs_bset[1].cap : 0;
+  if (device_bytes) *device_bytes = c->fam.have ? c->fam.device_bytes + c->fam.d_bset.cap + c->bs[0].block_set_bytes() + c->bs[1].block_set_bytes() : 0;
   return IBFT_OK;
 }
 
@@ -2430,7 +2412,7 @@ static int seals_stage_locked(ibft_ctx *c, const uint8_t *hash32, const uint8_t 
   if (!bare) cc.add(c->d_signer.p, signer20, n * 20);
   if (pre_flags) cc.add(c->d_pre.p, pre_flags, n);
   if ((rc = cc.flush(c))) return rc;
-  if ((rc = apply_seal_digest(c, 0, (uint32_t)n, false))) return rc;
+  if ((rc = apply_seal_digest(c, c->d_hash.p, (uint32_t)n))) return rc;
   // ibft_seals_stage promises the caller its buffers back; the one-shot call waits once, at the end
   if (wait) HIPCHK(c, hipStreamSynchronize(c->stream));
   c->staged_n = (uint32_t)n;
@@ -2516,7 +2498,7 @@ int ibft_seals_swap(ibft_ctx *c, int wait_for_copy) {
   c->next_valid = false;
   c->wire_valid = false;
   int rc;
-  if ((rc = apply_seal_digest(c, 0, c->staged_n, false))) return rc;
+  if ((rc = apply_seal_digest(c, c->d_hash.p, c->staged_n))) return rc;
   if (wait_for_copy) HIPCHK(c, hipEventSynchronize(c->ev_staged));  // the caller's source buffers are free again
   return IBFT_OK;
 }
@@ -2977,7 +2959,7 @@ static int messages_launch_locked(ibft_ctx *c, const uint8_t *payload, const uin
   }
   // the seals sign digest(carried hash) under a non-identity convention; a1 still compares the carried hashes (the copy)
   const bool converted = seal65 && c->seal_digest_mode != 0;
-  if (converted && (rc = apply_seal_digest(c, half, (uint32_t)n, true))) return rc;
+  if (converted && (rc = apply_seal_digest(c, (uint8_t *)c->d_hash.p + 32ull * half, (uint32_t)n, true))) return rc;
   c->ev_used = 0;
   const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
   if ((rc = enqueue_recover(c, c->stream, rows, false, ibftk::MODE_SEALS, time_it))) return rc;
@@ -3052,7 +3034,7 @@ int ibft_sign_seals_ex(ibft_ctx *c, const uint8_t *sk32, const uint8_t *hash32, 
   if ((rc = sc.check("ibft_sign_seals_ex")) || (rc = sc.begin())) return rc;
   if (n == 0) return IBFT_OK;
   if ((rc = sc.upload_keys(sk32)) || (rc = upload(c, c->d_hash, hash32, n * 32))) return rc;
-  if ((rc = apply_seal_digest(c, 0, (uint32_t)n, false))) return rc;  // a seal signs what the convention says it signs
+  if ((rc = apply_seal_digest(c, c->d_hash.p, (uint32_t)n))) return rc;  // a seal signs what the convention says it signs
   ibftk::sign_args a;
   a.gtab = (const uint32_t *)c->dev->d_gtab.p;
   a.sk32 = (const uint8_t *)c->d_payload.p;
@@ -3467,59 +3449,92 @@ int ibft_proposal_hashes(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_of
   return IBFT_OK;
 }
 
-// Chain sync: the committed seals of n_blocks finalized blocks — one upload, one verdict launch over every row (the AUTO rule
-// sees the TOTAL row count), one segmented tally (block_tally_kernel), one synchronisation.
-// props: the _raw calls — the blocks' proposals in place of block_hash32; their hashes are computed on the device
-// (proposal_digest_kernel) into d_phash, which then plays d_bhash's part: one code path from there on.
-// bare: ibft_recover_block_seals — no signer20 column; the emitting kernels fill out_signer20 / out_vidx and the validator
-// indices the tally reads.
-static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off, size_t n_blocks,
-                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
-                            uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally,
-                            bool sets = false, const uint32_t *block_set = nullptr);
-int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
-                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, uint64_t *out_mask,
-                            ibft_tally_t *out_tally) {
-  return block_seals_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally);
+// ---- chain sync: the sixteen block calls --------------------------------------------------------------------------------------
+// {verify, recover} × {hashes, proposals} × {one set, a set per block} × {synchronous, streamed}.  Every entry point fills a
+// block_batch with what it was given and hands it to one of two implementations, which share their parts (the checks below,
+// enqueue_block_head, enqueue_recover, enqueue_block_tally) and are NOT one path: the synchronous calls have another latency
+// and another refusal set than a submit + collect.
+constexpr bool BARE = true, SETS = true;
+struct block_batch {
+  const uint8_t *block_hash32;  // the blocks' hashes, or …
+  proposal_batch *props;        // … the _raw calls: their proposals, hashed on the device into what then plays the uploaded hashes' part
+  const uint32_t *seal_off;
+  size_t n_blocks;
+  const uint8_t *sig65, *signer20, *pre_flags;
+  bool bare = false;  // the recover calls: no signer20 column; the emitting kernels fill the columns the caller gets and the tally reads
+  bool sets = false;  // the _sets calls: block b is judged under set block_set[b] of the installed family
+  const uint32_t *block_set = nullptr;
+  uint32_t widest = 0;  // rows of the largest block (picks the tally's workgroup size) and of the batch: check_block_batch's
+  size_t n = 0;
+  uint32_t kind() const { return (bare ? IBFT_BATCH_RECOVER : 0u) | (props ? IBFT_BATCH_RAW : 0u) | (sets ? IBFT_BATCH_SETS : 0u); }
+};
+// The checks every block call makes, in the order it makes them.  Before c->mu is taken (outs_missing: an out buffer of a
+// synchronous call that rows need is null; a submit has none) …
+static int check_block_batch(const ibft_ctx *c, block_batch &b, bool outs_missing) {
+  if (!c || !b.seal_off || b.seal_off[0] != 0) return IBFT_E_INVAL;
+  if (b.n_blocks > c->max_rows) return IBFT_E_TOOBIG;  // (max_rows never changes after ibft_ctx_create)
+  for (size_t i = 0; i < b.n_blocks; i++) {
+    if (b.seal_off[i + 1] < b.seal_off[i]) return IBFT_E_INVAL;
+    b.widest = std::max(b.widest, b.seal_off[i + 1] - b.seal_off[i]);
+  }
+  if ((b.n = b.seal_off[b.n_blocks]) > c->max_rows) return IBFT_E_TOOBIG;
+  if (b.n && ((!b.props && !b.block_hash32) || !b.sig65 || (!b.bare && !b.signer20) || outs_missing)) return IBFT_E_INVAL;
+  if (b.sets && b.n_blocks && !b.block_set) return IBFT_E_INVAL;
+  return IBFT_OK;
 }
-int ibft_recover_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
-                             const uint8_t *sig65, const uint8_t *pre_flags, uint8_t *out_signer20, int32_t *out_vidx,
-                             uint64_t *out_mask, ibft_tally_t *out_tally) {
-  return block_seals_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally);
+// … and under it: each kind of batch needs only its own kind of set; a set the family does not have is refused on the host
+// (no launch ever sees one); then the proposals' arguments.
+static int check_block_batch_locked(const ibft_ctx *c, block_batch &b) {
+  if (b.sets ? !c->fam.have : !c->have_valset) return IBFT_E_NOVALSET;
+  if (b.sets)
+    for (size_t i = 0; i < b.n_blocks; i++)
+      if (b.block_set[i] >= c->fam.n_sets) return IBFT_E_INVAL;
+  return b.props ? check_proposals(c, *b.props, b.n_blocks) : IBFT_OK;
 }
-int ibft_verify_block_seals_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
-                                const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20,
-                                const uint8_t *pre_flags, uint8_t *out_block_hash32, uint64_t *out_mask, ibft_tally_t *out_tally) {
-  proposal_batch p{raw, raw_off, round, out_block_hash32};
-  return block_seals_impl(c, nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally);
+// block_head_kernel on the main stream: the digests of nb blocks over the nr rows of the resident offsets, into the hash column
+// the verdict kernels read.  convert: the seal-digest convention per row, the digests left as they are (a streamed batch, whose
+// digests leave for the host meanwhile); otherwise a plain copy of digests the caller converted once per block.
+static int enqueue_block_head(ibft_ctx *c, const void *d_digests, uint32_t nb, uint32_t nr, bool convert) {
+  ibftk::block_head_args h{(const uint64_t *)d_digests, (const uint32_t *)c->d_boff.p, (uint8_t *)c->d_hash.p, nb, nr,
+                            convert && c->seal_digest_mode != 0 ? 1u : 0u};
+  memcpy(h.suffix_words, c->seal_suffix_words, sizeof h.suffix_words);
+  hipLaunchKernelGGL(ibftk::block_head_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, h);
+  HIPCHK(c, hipGetLastError());
+  return IBFT_OK;
 }
-int ibft_recover_block_seals_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
-                                 const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags,
-                                 uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask,
-                                 ibft_tally_t *out_tally) {
-  proposal_batch p{raw, raw_off, round, out_block_hash32};
-  return block_seals_impl(c, nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally);
-}
-static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off, size_t n_blocks,
-                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
-                            uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally,
-                            bool sets, const uint32_t *block_set) {
-  uint32_t widest;
-  size_t n;
+
+// The per-block records for nb blocks.  Nothing writes the old ones now: a synchronous call that delivered into them has
+// synchronised before it returned, the streamed batch that used them last (k − 2) has been collected.
+static int ensure_block_records(ibft_ctx *c, BlockRecords &r, uint32_t nb) {
   int rc;
-  if ((rc = check_seal_offsets(c, seal_off, n_blocks, &widest, &n))) return rc;
-  if (n && ((!props && !block_hash32) || !sig65 || (bare ? !out_signer20 : !signer20) || !out_mask)) return IBFT_E_INVAL;
-  if (sets && n_blocks && !block_set) return IBFT_E_INVAL;
+  if (nb > r.blocks) {
+    r.map = nullptr;
+    if ((rc = grow_pinned((void **)&r.h, &r.blocks, nb, 32))) return rc;
+    void *d = nullptr;  // the tally writes the records itself where the verdict words go there too (not under IBFT_NO_HOST_DIRECT)
+    if (c->dh_mask && hipHostGetDevicePointer(&d, r.h, 0) == hipSuccess) r.map = (uint64_t *)d;
+  }
+  if (!r.map && (rc = ensure(c, r.d, (size_t)nb * 32))) return rc;
+  return IBFT_OK;
+}
+
+// The synchronous calls: one upload, one verdict launch over every row (the AUTO rule sees the TOTAL row count), one segmented
+// tally (block_tally_kernel), one synchronisation.
+struct block_outputs {
+  uint8_t *signer20;  // (these two: the recover calls)
+  int32_t *vidx;
+  uint64_t *mask;
+  ibft_tally_t *tally;
+};
+static int block_seals_impl(ibft_ctx *c, block_batch b, const block_outputs &o) {
+  int rc;
+  if ((rc = check_block_batch(c, b, (b.bare && !o.signer20) || !o.mask))) return rc;
   ctx_lock lk(c);
-  if (sets ? !c->fam.have : !c->have_valset) return IBFT_E_NOVALSET;
-  if (sets)  // refused on the host: no launch ever sees a set the family does not have
-    for (size_t b = 0; b < n_blocks; b++)
-      if (block_set[b] >= c->fam.n_sets) return IBFT_E_INVAL;
+  if ((rc = check_block_batch_locked(c, b))) return rc;
   // sets: from here to the return "the validator set" of the context is the family's union (table, size, key-cache slots)
-  family_view fv(c, sets);
-  if (props && (rc = check_proposals(c, *props, n_blocks))) return rc;
+  family_view fv(c, b.sets);
   HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t nb = (uint32_t)n_blocks, nr = (uint32_t)n;
+  proposal_batch *const props = b.props;
+  const uint32_t nb = (uint32_t)b.n_blocks, nr = (uint32_t)b.n;
   c->wire_valid = false;
   // the proposals are hashed when rows wait for the hashes or the caller wants them
   const bool hash_here = props && nb && (nr || props->out_hash32);
@@ -3528,96 +3543,115 @@ static int block_seals_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_b
   if (nr) {
     if ((rc = ensure(c, c->d_boff, ((size_t)nb + 1) * 4))) return rc;
     if ((rc = ensure(c, c->d_bhash, (size_t)nb * 32))) return rc;
-    if ((rc = ensure(c, c->d_btally, (size_t)nb * 32))) return rc;
-    if (nb > c->h_btally_blocks) {  // (every call that delivers into it has synchronised before it returned: nothing writes it now)
-      c->dh_btally = nullptr;
-      if ((rc = grow_pinned((void **)&c->h_btally, &c->h_btally_blocks, nb, 32))) return rc;
-      void *d = nullptr;  // the tally writes the records itself where the verdict words go there too (not under IBFT_NO_HOST_DIRECT)
-      if (c->dh_mask && hipHostGetDevicePointer(&d, c->h_btally, 0) == hipSuccess) c->dh_btally = (uint64_t *)d;
-    }
-    cc.add(c->d_boff.p, seal_off, ((size_t)nb + 1) * 4);
-    if (sets) {
+    if ((rc = ensure_block_records(c, c->brec, nb))) return rc;
+    cc.add(c->d_boff.p, b.seal_off, ((size_t)nb + 1) * 4);
+    if (b.sets) {
       if ((rc = ensure(c, c->fam.d_bset, (size_t)nb * 4))) return rc;
-      cc.add(c->fam.d_bset.p, block_set, (size_t)nb * 4);
+      cc.add(c->fam.d_bset.p, b.block_set, (size_t)nb * 4);
     }
-    if (!props) cc.add(c->d_bhash.p, block_hash32, (size_t)nb * 32);
-    cc.add(c->d_sig.p, sig65, n * 65);
-    if (!bare) cc.add(c->d_signer.p, signer20, n * 20);
-    if (pre_flags) cc.add(c->d_pre.p, pre_flags, n);
+    if (!props) cc.add(c->d_bhash.p, b.block_hash32, (size_t)nb * 32);
+    cc.add(c->d_sig.p, b.sig65, b.n * 65);
+    if (!b.bare) cc.add(c->d_signer.p, b.signer20, b.n * 20);
+    if (b.pre_flags) cc.add(c->d_pre.p, b.pre_flags, b.n);
   }
   if ((rc = cc.flush(c))) return rc;
   // (the digests' copy out is enqueued here, in front of the seal-digest convention that converts them in place)
   if (hash_here && (rc = enqueue_proposal_digests(c, *props, nb))) return rc;
-  if (nr) {
-    uint8_t *d_block_hash = (uint8_t *)(props ? c->d_phash.p : c->d_bhash.p);
-    if ((rc = seal_digest_column(c, d_block_hash, nb))) return rc;
-    hipLaunchKernelGGL(ibftk::block_rows_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, (const uint8_t *)d_block_hash,
-                       (const uint32_t *)c->d_boff.p, nb, nr, (uint8_t *)c->d_hash.p);
-    HIPCHK(c, hipGetLastError());
+  if (nr) {  // the convention once per BLOCK — one Keccak per block instead of one per row —, then the plain spread
+    void *d_block_hash = props ? c->d_phash.p : c->d_bhash.p;
+    if ((rc = apply_seal_digest(c, d_block_hash, nb))) return rc;
+    if ((rc = enqueue_block_head(c, d_block_hash, nb, nr, false))) return rc;
   }
   // the rows are the resident batch from here on, exactly as ibft_seals_stage would have left them (not under a family: rows
   // judged against the union are nothing ibft_seals_launch could re-judge under the single set)
-  c->staged_n = sets ? 0 : nr;
-  c->staged_pre = pre_flags != nullptr;
+  c->staged_n = b.sets ? 0 : nr;
+  c->staged_pre = b.pre_flags != nullptr;
   if (nr) {
-    if ((rc = enqueue_recover(c, c->stream, nr, c->staged_pre, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, next_pass_timed(c)))) return rc;
-    uint64_t *const records = c->dh_btally ? c->dh_btally : (uint64_t *)c->d_btally.p;
-    if ((rc = enqueue_block_tally(c, nb, nr, widest, c->dh_mask, records, sets))) return rc;
-    if (bare && (rc = copy_emitted(c, nr, out_signer20, out_vidx))) return rc;
+    if ((rc = enqueue_recover(c, c->stream, nr, c->staged_pre, b.bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, next_pass_timed(c)))) return rc;
+    if ((rc = enqueue_block_tally(c, nb, nr, b.widest, c->dh_mask, c->brec.map ? c->brec.map : (uint64_t *)c->brec.d.p, b.sets))) return rc;
+    if (b.bare && (rc = copy_emitted(c, nr, o.signer20, o.vidx))) return rc;
     c->host_direct = false;
     const size_t mw = (size_t)mask_words(nr);
     if (!c->dh_mask) HIPCHK(c, hipMemcpyAsync(c->h_mask, c->d_mask_out.p, mw * 8, hipMemcpyDeviceToHost, c->stream));
-    if (!c->dh_btally)
-      HIPCHK(c, hipMemcpyAsync(c->h_btally, c->d_btally.p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->stream));
+    if (!c->brec.map) HIPCHK(c, hipMemcpyAsync(c->brec.h, c->brec.d.p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->stream));
     if (c->cache_on) HIPCHK(c, hipMemcpyAsync(c->h_tally + 4, c->dev->d_learned.p, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->cache_on) {  // keys these rows taught the device → tables (the next call is warm)
       const uint32_t *lw = reinterpret_cast<const uint32_t *>(c->h_tally + 4);
       if ((rc = build_new_tables(c, lw[0], lw[1]))) return rc;
     }
-    memcpy(out_mask, c->h_mask, mw * 8);
-    if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
+    memcpy(o.mask, c->h_mask, mw * 8);
+    if (nr & 63) o.mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
   } else if (hash_here) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   if (hash_here && props->out_hash32) memcpy(props->out_hash32, c->h_phash, (size_t)nb * 32);
-  if (bare) c->staged_n = 0;  // (as after ibft_recover_seals: bare rows are no resident batch)
-  fill_block_tallies(out_tally, nb, nr, c->h_btally, [&](uint32_t b) -> const uint64_t * {
-    return sets ? &c->fam.quorum[(size_t)block_set[b] * ibftk::TALLY_SUM_WORDS] : c->quorum_w;
+  if (b.bare) c->staged_n = 0;  // (as after ibft_recover_seals: bare rows are no resident batch)
+  fill_block_tallies(o.tally, nb, nr, c->brec.h, [&](uint32_t blk) -> const uint64_t * {
+    return b.sets ? &c->fam.quorum[(size_t)b.block_set[blk] * ibftk::TALLY_SUM_WORDS] : c->quorum_w;
   });
   return IBFT_OK;
 }
 
+int ibft_verify_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                            const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, uint64_t *out_mask,
+                            ibft_tally_t *out_tally) {
+  return block_seals_impl(c, {block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags}, {nullptr, nullptr, out_mask, out_tally});
+}
+int ibft_recover_block_seals(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
+                             const uint8_t *sig65, const uint8_t *pre_flags, uint8_t *out_signer20, int32_t *out_vidx,
+                             uint64_t *out_mask, ibft_tally_t *out_tally) {
+  return block_seals_impl(c, {block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, BARE}, {out_signer20, out_vidx, out_mask, out_tally});
+}
+int ibft_verify_block_seals_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20,
+                                const uint8_t *pre_flags, uint8_t *out_block_hash32, uint64_t *out_mask, ibft_tally_t *out_tally) {
+  proposal_batch p{raw, raw_off, round, out_block_hash32};
+  return block_seals_impl(c, {nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags}, {nullptr, nullptr, out_mask, out_tally});
+}
+int ibft_recover_block_seals_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
+                                 const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags,
+                                 uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx, uint64_t *out_mask,
+                                 ibft_tally_t *out_tally) {
+  proposal_batch p{raw, raw_off, round, out_block_hash32};
+  return block_seals_impl(c, {nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, BARE}, {out_signer20, out_vidx, out_mask, out_tally});
+}
 int ibft_verify_block_seals_sets(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, const uint32_t *block_set,
                                  size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags,
                                  uint64_t *out_mask, ibft_tally_t *out_tally) {
-  return block_seals_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally,
-                          true, block_set);
+  return block_seals_impl(c, {block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, !BARE, SETS, block_set}, {nullptr, nullptr, out_mask, out_tally});
 }
 int ibft_recover_block_seals_sets(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, const uint32_t *block_set,
                                   size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags, uint8_t *out_signer20,
                                   int32_t *out_vidx, uint64_t *out_mask, ibft_tally_t *out_tally) {
-  return block_seals_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally,
-                          true, block_set);
+  return block_seals_impl(c, {block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, BARE, SETS, block_set}, {out_signer20, out_vidx, out_mask, out_tally});
 }
-// … and from the proposals: ibft_proposal_hashes + the call above in one (block_seals_impl's checks: the _sets call's in its
-// order, then those of the proposals' arguments)
+// … and from the proposals: ibft_proposal_hashes + the call above in one (the _sets call's checks in its order, then those of
+// the proposals' arguments)
 int ibft_verify_block_seals_sets_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
                                      const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
                                      const uint8_t *signer20, const uint8_t *pre_flags, uint8_t *out_block_hash32, uint64_t *out_mask,
                                      ibft_tally_t *out_tally) {
   proposal_batch p{raw, raw_off, round, out_block_hash32};
-  return block_seals_impl(c, nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, false, nullptr, nullptr, out_mask, out_tally, true,
-                          block_set);
+  return block_seals_impl(c, {nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, !BARE, SETS, block_set}, {nullptr, nullptr, out_mask, out_tally});
 }
 int ibft_recover_block_seals_sets_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
                                       const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
                                       const uint8_t *pre_flags, uint8_t *out_block_hash32, uint8_t *out_signer20, int32_t *out_vidx,
                                       uint64_t *out_mask, ibft_tally_t *out_tally) {
   proposal_batch p{raw, raw_off, round, out_block_hash32};
-  return block_seals_impl(c, nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, true, out_signer20, out_vidx, out_mask, out_tally, true,
-                          block_set);
+  return block_seals_impl(c, {nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, BARE, SETS, block_set}, {out_signer20, out_vidx, out_mask, out_tally});
 }
+
+// ---- streamed chain sync: the same eight batches, enqueued and not waited for ------------------------------------------------
+// Up to two batches in flight; the copy of batch k + 1 (copy stream, into the spare column set) runs under the kernels of batch
+// k (main stream).  Checks: the synchronous sibling's, in its order, minus the out buffers; then the pipeline's refusals.  The
+// blocks' digests (the slot's phash: uploaded hashes, or proposal_digest_kernel's) are private to the slot and only read —
+// block_head_kernel applies the seal-digest convention, the one in force at the submit, while it spreads them over the rows —,
+// a recover batch emits into columns of its slot, and digests / signers / indices leave on ostream (see BlockSlot).
+// sets: the same path under a family of sets — the verdict kernels judge against the family's union (family_view),
+// block_head_kernel is followed by the SETS form of block_tally_kernel over the slot's own block_set column, and the quorum
+// words the collect hands out are copied into the slot, so the family may be replaced while the batch is in flight.
 
 // The refusals every streamed block submit makes once its arguments are in order (c->mu held); a refused call takes no slot.
 static int block_pipeline_refusal(ibft_ctx *c) {
@@ -3637,43 +3671,51 @@ static int block_pipeline_refusal(ibft_ctx *c) {
   }
   return IBFT_OK;
 }
-// The per-block records of slot s, for nb blocks (mapped where the device can write them, through bs_dtally[s] otherwise).
-static int ensure_block_records(ibft_ctx *c, uint32_t s, uint32_t nb) {
+// Everything a submit only RESERVES, in one place: the slot's events and ostream (whatever the batch holds), then what a batch
+// with rows or proposals needs.  Nothing of the batch is enqueued here.  Everything of the slot is free: the batch that used
+// it last (k − 2) has been collected — its kernels and its copies out are done (hipFree waits for the device besides: a
+// buffer that grows here is read by nothing any more).
+static int reserve_block_slot(ibft_ctx *c, BlockSlot &sl, const block_batch &b, bool hash_here) {
   int rc;
-  if (nb > c->bs_tally_blocks[s]) {  // the batch that used them last (k − 2) has been collected, nothing writes them now
-    c->bs_dtally_map[s] = nullptr;
-    if ((rc = grow_pinned((void **)&c->bs_tally[s], &c->bs_tally_blocks[s], nb, 32))) return rc;
-    void *d = nullptr;  // (IBFT_NO_HOST_DIRECT: records and verdict words through device buffers and copies behind the tally)
-    if (c->dh_mask && hipHostGetDevicePointer(&d, c->bs_tally[s], 0) == hipSuccess) c->bs_dtally_map[s] = (uint64_t *)d;
+  const uint32_t nb = (uint32_t)b.n_blocks, nr = (uint32_t)b.n;
+  for (hipEvent_t *e : {&sl.ev, &sl.ev_dig, &sl.ev_out})
+    if (!*e) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+  if (!c->ostream) HIPCHK(c, hipStreamCreateWithFlags(&c->ostream, hipStreamNonBlocking));
+  if (!nr && !hash_here) return IBFT_OK;
+  if ((rc = ensure_result_slots(c))) return rc;
+  if ((rc = ensure_spare_columns(c))) return rc;
+  if ((rc = ensure(c, sl.phash, (size_t)nb * 32))) return rc;
+  if (hash_here) {
+    if ((rc = ensure(c, sl.praw, (size_t)b.props->raw_off[nb] + 256))) return rc;
+    if ((rc = ensure(c, sl.proff, ((size_t)nb + 1) * 4))) return rc;
+    if ((rc = ensure(c, sl.pround, (size_t)nb * 8))) return rc;
+    if ((rc = grow_pinned((void **)&sl.h_hash, &sl.h_hash_blocks, nb, 32))) return rc;
   }
-  if (!c->bs_dtally_map[s] && (rc = ensure(c, c->bs_dtally[s], (size_t)nb * 32))) return rc;
+  if (nr) {
+    if ((rc = ensure(c, c->d_boff_nx, ((size_t)nb + 1) * 4))) return rc;
+    if ((rc = ensure_block_records(c, sl.rec, nb))) return rc;
+    if (b.sets && (rc = ensure(c, sl.bset, (size_t)nb * 4))) return rc;
+    if (b.bare) {
+      const size_t m = std::max<size_t>(c->max_rows, c->row_cap);  // (the sizes alloc_rows gives d_signer_out / d_vidx)
+      if ((rc = ensure(c, sl.signer, m * 20))) return rc;
+      if ((rc = ensure(c, sl.vidx, m * 4))) return rc;
+      if ((rc = grow_pinned((void **)&sl.h_signer, &sl.h_rows, nr, 20))) return rc;
+      if ((rc = grow_pinned((void **)&sl.h_vidx, &sl.h_vidx_rows, nr, 4))) return rc;
+    }
+  }
   return IBFT_OK;
 }
-
-// ---- streamed chain sync: from hashes, from proposals and from bare seals ----------------------------------------------------
-// ibft_block_seals_submit, ibft_block_seals_submit_raw, ibft_recover_block_seals_submit, ibft_recover_block_seals_submit_raw:
-// the batches of ibft_verify_block_seals, ibft_verify_block_seals_raw, ibft_recover_block_seals and ibft_recover_block_seals_raw,
-// enqueued and not waited for.  Up to two batches in flight; the copy of batch k + 1 (copy stream, into the spare column set)
-// runs under the kernels of batch k (main stream).  Checks: the synchronous sibling's, in its order, minus the out buffers; then
-// the pipeline's refusals.  The blocks' digests (bs_phash[s]: uploaded hashes, or proposal_digest_kernel's) are private to the
-// slot and only read — block_head_kernel applies the seal-digest convention, the one in force at the submit, while it spreads
-// them over the rows —, a recover batch emits into columns of its slot, and digests / signers / indices leave on ostream (see
-// the context's fields).
-// sets: the four _sets submits (ibft_block_seals_submit_sets[_raw], ibft_recover_block_seals_submit_sets[_raw]) — the same
-// path under a family of sets: the verdict kernels judge against the family's union (family_view), block_head_kernel is
-// followed by the SETS form of block_tally_kernel over the slot's own block_set column, and the quorum words the collect hands
-// out are copied into the slot, so the family may be replaced while the batch is in flight.
-// d_signer_out / d_vidx ↔ the emit columns of slot s while a recover batch's kernels are enqueued (make_args and the tally
+// d_signer_out / d_vidx ↔ the emit columns of a slot while a recover batch's kernels are enqueued (make_args and the tally
 // read the context's fields); put back on every way out
 struct emit_columns_view {
   ibft_ctx *c;
-  uint32_t s;
+  BlockSlot &sl;
   bool on;
   void exchange() {
-    std::swap(c->d_signer_out, c->bs_signer[s]);
-    std::swap(c->d_vidx, c->bs_vidx[s]);
+    std::swap(c->d_signer_out, sl.signer);
+    std::swap(c->d_vidx, sl.vidx);
   }
-  emit_columns_view(ibft_ctx *cc, uint32_t ss, bool on_) : c(cc), s(ss), on(on_) {
+  emit_columns_view(ibft_ctx *cc, BlockSlot &slot, bool on_) : c(cc), sl(slot), on(on_) {
     if (on) exchange();
   }
   ~emit_columns_view() {
@@ -3682,115 +3724,78 @@ struct emit_columns_view {
   emit_columns_view(const emit_columns_view &) = delete;
   emit_columns_view &operator=(const emit_columns_view &) = delete;
 };
-static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, proposal_batch *props, const uint32_t *seal_off,
-                                   size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags, bool bare,
-                                   bool sets = false, const uint32_t *block_set = nullptr) {
-  uint32_t widest;
-  size_t n;
+static int block_seals_submit_impl(ibft_ctx *c, block_batch b) {
   int rc;
-  if ((rc = check_seal_offsets(c, seal_off, n_blocks, &widest, &n))) return rc;
-  if (n && ((!props && !block_hash32) || !sig65 || (!bare && !signer20))) return IBFT_E_INVAL;
-  if (sets && n_blocks && !block_set) return IBFT_E_INVAL;
+  if ((rc = check_block_batch(c, b, false))) return rc;
   std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself; side-stream tallies are joined below)
-  if (sets ? !c->fam.have : !c->have_valset) return IBFT_E_NOVALSET;  // each kind of batch needs only its own kind of set
-  if (sets)  // refused on the host, as by the synchronous sibling
-    for (size_t b = 0; b < n_blocks; b++)
-      if (block_set[b] >= c->fam.n_sets) return IBFT_E_INVAL;
-  if (props && (rc = check_proposals(c, *props, n_blocks))) return rc;
+  if ((rc = check_block_batch_locked(c, b))) return rc;
   if ((rc = block_pipeline_refusal(c))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = join_side(c))) return rc;
   // sets: from here to the return "the validator set" of the context is the family's union, as in block_seals_impl.  The
   // batch is judged under the family installed NOW: its kernels read the family's device tables, which an install lets go
   // only behind them (set_validator_sets_impl), and what the collect needs of the family is copied into the slot below.
-  family_view fv(c, sets);
-  const uint32_t s = c->bs_issued & 1u, nb = (uint32_t)n_blocks, nr = (uint32_t)n;
-  const uint32_t kind = (bare ? IBFT_BATCH_RECOVER : 0u) | (props ? IBFT_BATCH_RAW : 0u) | (sets ? IBFT_BATCH_SETS : 0u);
+  family_view fv(c, b.sets);
+  proposal_batch *const props = b.props;
+  const uint32_t s = c->bs_issued & 1u, nb = (uint32_t)b.n_blocks, nr = (uint32_t)b.n;
+  BlockSlot &sl = c->bs[s];
   // sets: the quorum words the collect hands out, kept in the slot (free: batch k − 2 has been collected) before anything
   // is enqueued — 16 B per block, or 4 B per block + 16 B per set of the family, whichever is smaller
-  c->bs_setq[s].clear();
-  c->bs_setidx[s].clear();
-  if (sets) {
+  sl.setq.clear();
+  sl.setidx.clear();
+  if (b.sets) {
     const ValFamily &f = c->fam;
     const bool per_block = 16ull * nb <= 4ull * nb + 16ull * f.n_sets;
     const uint32_t entries = per_block ? nb : f.n_sets;
-    c->bs_setq[s].reserve(2 * (size_t)entries);
+    sl.setq.reserve(2 * (size_t)entries);
     for (uint32_t e = 0; e < entries; e++) {
-      const uint64_t *q = &f.quorum[(size_t)(per_block ? block_set[e] : e) * ibftk::TALLY_SUM_WORDS];
-      c->bs_setq[s].push_back(q[0]);
-      c->bs_setq[s].push_back(q[1]);
+      const uint64_t *q = &f.quorum[(size_t)(per_block ? b.block_set[e] : e) * ibftk::TALLY_SUM_WORDS];
+      sl.setq.push_back(q[0]);
+      sl.setq.push_back(q[1]);
     }
-    if (!per_block) c->bs_setidx[s].assign(block_set, block_set + nb);
+    if (!per_block) sl.setidx.assign(b.block_set, b.block_set + nb);
   }
   // submitted raw: the proposals are hashed whether or not rows wait for the hashes — the collect may ask for them
   const bool hash_here = props && nb;
   bool has_out = false;
-  if (!c->ev_bs[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bs[s], hipEventDisableTiming));
-  if (!c->ev_bs_dig[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bs_dig[s], hipEventDisableTiming));
-  if (!c->ev_bs_out[s]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bs_out[s], hipEventDisableTiming));
-  if (!c->ostream) HIPCHK(c, hipStreamCreateWithFlags(&c->ostream, hipStreamNonBlocking));
+  if ((rc = reserve_block_slot(c, sl, b, hash_here))) return rc;
   if (nr || hash_here) {
-    if ((rc = ensure_result_slots(c))) return rc;
-    if ((rc = ensure_spare_columns(c))) return rc;
-    // Everything of slot s: the batch that used it last (k − 2) has been collected — its kernels and its copies out are done
-    // (hipFree waits for the device besides: a buffer that grows here is read by nothing any more).
-    if ((rc = ensure(c, c->bs_phash[s], (size_t)nb * 32))) return rc;
     const size_t raw_bytes = hash_here ? props->raw_off[nb] : 0;
-    if (hash_here) {
-      if ((rc = ensure(c, c->bs_praw[s], raw_bytes + 256))) return rc;
-      if ((rc = ensure(c, c->bs_proff[s], ((size_t)nb + 1) * 4))) return rc;
-      if ((rc = ensure(c, c->bs_pround[s], (size_t)nb * 8))) return rc;
-      if ((rc = grow_pinned((void **)&c->bs_h_hash[s], &c->bs_h_hash_blocks[s], nb, 32))) return rc;
-    }
-    if (nr) {
-      if ((rc = ensure(c, c->d_boff_nx, ((size_t)nb + 1) * 4))) return rc;
-      if ((rc = ensure_block_records(c, s, nb))) return rc;
-      if (sets && (rc = ensure(c, c->bs_bset[s], (size_t)nb * 4))) return rc;
-      if (bare) {
-        const size_t m = std::max<size_t>(c->max_rows, c->row_cap);  // (the sizes alloc_rows gives d_signer_out / d_vidx)
-        if ((rc = ensure(c, c->bs_signer[s], m * 20))) return rc;
-        if ((rc = ensure(c, c->bs_vidx[s], m * 4))) return rc;
-        if ((rc = grow_pinned((void **)&c->bs_h_signer[s], &c->bs_h_rows[s], nr, 20))) return rc;
-        if ((rc = grow_pinned((void **)&c->bs_h_vidx[s], &c->bs_h_vidx_rows[s], nr, 4))) return rc;
-      }
-    }
     // ---- the copy stream: proposals (and, where told to, their digests), then the seal columns into the spare set
     if (hash_here) {
-      if (raw_bytes) HIPCHK(c, hipMemcpyAsync(c->bs_praw[s].p, props->raw, raw_bytes, hipMemcpyHostToDevice, c->cstream));
-      HIPCHK(c, hipMemcpyAsync(c->bs_proff[s].p, props->raw_off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, c->cstream));
-      HIPCHK(c, hipMemcpyAsync(c->bs_pround[s].p, props->round, (size_t)nb * 8, hipMemcpyHostToDevice, c->cstream));
+      if (raw_bytes) HIPCHK(c, hipMemcpyAsync(sl.praw.p, props->raw, raw_bytes, hipMemcpyHostToDevice, c->cstream));
+      HIPCHK(c, hipMemcpyAsync(sl.proff.p, props->raw_off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, c->cstream));
+      HIPCHK(c, hipMemcpyAsync(sl.pround.p, props->round, (size_t)nb * 8, hipMemcpyHostToDevice, c->cstream));
     } else if (!props) {
-      HIPCHK(c, hipMemcpyAsync(c->bs_phash[s].p, block_hash32, (size_t)nb * 32, hipMemcpyHostToDevice, c->cstream));
+      HIPCHK(c, hipMemcpyAsync(sl.phash.p, b.block_hash32, (size_t)nb * 32, hipMemcpyHostToDevice, c->cstream));
     }
     const uint32_t form = hash_here ? proposal_form(c, *props, nb) : 0u;  // (the form is chosen here: pinned at the submit)
     if (hash_here && c->stream_digest_copy) {
       // behind the copy of its bytes, next to whatever the main stream runs: batch k's verdict kernel in a loop that keeps one in flight
-      if ((rc = launch_proposal_digests(c, form, c->bs_praw[s].p, c->bs_proff[s].p, c->bs_pround[s].p, c->bs_phash[s].p, nb, c->cstream)))
-        return rc;
-      HIPCHK(c, hipEventRecord(c->ev_bs_dig[s], c->cstream));
+      if ((rc = launch_proposal_digests(c, form, sl.praw.p, sl.proff.p, sl.pround.p, sl.phash.p, nb, c->cstream))) return rc;
+      HIPCHK(c, hipEventRecord(sl.ev_dig, c->cstream));
     }
     if (nr) {
       // The spare set was the resident one until the previous swap: kernels enqueued before it — a tally reads the offsets —
       // may still be at it.  ev_cols_read was recorded behind them.
       HIPCHK(c, hipStreamWaitEvent(c->cstream, c->ev_cols_read, 0));
-      HIPCHK(c, hipMemcpyAsync(c->d_boff_nx.p, seal_off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, c->cstream));
-      if (sets) HIPCHK(c, hipMemcpyAsync(c->bs_bset[s].p, block_set, (size_t)nb * 4, hipMemcpyHostToDevice, c->cstream));
-      HIPCHK(c, hipMemcpyAsync(c->d_sig_nx.p, sig65, n * 65, hipMemcpyHostToDevice, c->cstream));
-      if (!bare) HIPCHK(c, hipMemcpyAsync(c->d_signer_nx.p, signer20, n * 20, hipMemcpyHostToDevice, c->cstream));
-      if (pre_flags) HIPCHK(c, hipMemcpyAsync(c->d_pre_nx.p, pre_flags, n, hipMemcpyHostToDevice, c->cstream));
+      HIPCHK(c, hipMemcpyAsync(c->d_boff_nx.p, b.seal_off, ((size_t)nb + 1) * 4, hipMemcpyHostToDevice, c->cstream));
+      if (b.sets) HIPCHK(c, hipMemcpyAsync(sl.bset.p, b.block_set, (size_t)nb * 4, hipMemcpyHostToDevice, c->cstream));
+      HIPCHK(c, hipMemcpyAsync(c->d_sig_nx.p, b.sig65, b.n * 65, hipMemcpyHostToDevice, c->cstream));
+      if (!b.bare) HIPCHK(c, hipMemcpyAsync(c->d_signer_nx.p, b.signer20, b.n * 20, hipMemcpyHostToDevice, c->cstream));
+      if (b.pre_flags) HIPCHK(c, hipMemcpyAsync(c->d_pre_nx.p, b.pre_flags, b.n, hipMemcpyHostToDevice, c->cstream));
     }
     HIPCHK(c, hipEventRecord(c->ev_staged, c->cstream));
     if (nr) HIPCHK(c, hipEventRecord(c->ev_cols_read, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_staged, 0));
     // from here on a failure leaves commands of this batch on the streams: nothing of it is delivered, the slot stays free
     if (hash_here && !c->stream_digest_copy) {
-      if ((rc = launch_proposal_digests(c, form, c->bs_praw[s].p, c->bs_proff[s].p, c->bs_pround[s].p, c->bs_phash[s].p, nb, c->stream)))
-        return rc;
-      HIPCHK(c, hipEventRecord(c->ev_bs_dig[s], c->stream));
+      if ((rc = launch_proposal_digests(c, form, sl.praw.p, sl.proff.p, sl.pround.p, sl.phash.p, nb, c->stream))) return rc;
+      HIPCHK(c, hipEventRecord(sl.ev_dig, c->stream));
     }
     if (hash_here) {  // the digests go out as computed, next to everything that follows on the main stream
-      HIPCHK(c, hipStreamWaitEvent(c->ostream, c->ev_bs_dig[s], 0));
-      HIPCHK(c, hipMemcpyAsync(c->bs_h_hash[s], c->bs_phash[s].p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->ostream));
+      HIPCHK(c, hipStreamWaitEvent(c->ostream, sl.ev_dig, 0));
+      HIPCHK(c, hipMemcpyAsync(sl.h_hash, sl.phash.p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->ostream));
       has_out = true;
     }
     if (nr) {
@@ -3801,90 +3806,80 @@ static int block_seals_submit_impl(ibft_ctx *c, const uint8_t *block_hash32, pro
       c->wire_valid = false;
       // verify kind: the rows are the resident batch from here on; bare rows are none, and neither are rows judged against a
       // family's union (as after the synchronous siblings)
-      c->staged_n = bare || sets ? 0 : nr;
-      c->staged_pre = pre_flags != nullptr;
-      ibftk::block_head_args h{};
-      h.digest_words = (const uint64_t *)c->bs_phash[s].p;
-      h.off = (const uint32_t *)c->d_boff.p;
-      h.hash32 = (uint8_t *)c->d_hash.p;
-      h.n_blocks = nb;
-      h.n = nr;
-      h.convert = c->seal_digest_mode != 0 ? 1u : 0u;
-      memcpy(h.suffix_words, c->seal_suffix_words, sizeof h.suffix_words);
-      hipLaunchKernelGGL(ibftk::block_head_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, h);
-      HIPCHK(c, hipGetLastError());
+      c->staged_n = b.bare || b.sets ? 0 : nr;
+      c->staged_pre = b.pre_flags != nullptr;
+      if ((rc = enqueue_block_head(c, sl.phash.p, nb, nr, true))) return rc;
       const bool time_it = next_pass_timed(c);
-      const bool direct = c->bs_dtally_map[s] != nullptr;
+      const bool direct = sl.rec.map != nullptr;
       {
-        emit_columns_view ev(c, s, bare);
-        if ((rc = enqueue_recover(c, c->stream, nr, pre_flags != nullptr, bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
-        if ((rc = enqueue_block_tally(c, nb, nr, widest, direct ? c->dp_mask[s] : nullptr,
-                                      direct ? c->bs_dtally_map[s] : (uint64_t *)c->bs_dtally[s].p, sets, c->bs_bset[s].p)))
+        emit_columns_view ev(c, sl, b.bare);
+        if ((rc = enqueue_recover(c, c->stream, nr, b.pre_flags != nullptr, b.bare ? ibftk::MODE_EMIT : ibftk::MODE_SEALS, time_it))) return rc;
+        if ((rc = enqueue_block_tally(c, nb, nr, b.widest, direct ? c->dp_mask[s] : nullptr,
+                                      direct ? sl.rec.map : (uint64_t *)sl.rec.d.p, b.sets, sl.bset.p)))
           return rc;
       }
       c->host_direct = false;
       if (!direct) {
         HIPCHK(c, hipMemcpyAsync(c->p_mask[s], c->d_mask_out.p, (size_t)mask_words(nr) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->bs_tally[s], c->bs_dtally[s].p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(sl.rec.h, sl.rec.d.p, (size_t)nb * 32, hipMemcpyDeviceToHost, c->stream));
       }
       if (c->cache_on) HIPCHK(c, hipMemcpyAsync(c->p_tally[s] + 4, c->dev->d_learned.p, 8, hipMemcpyDeviceToHost, c->stream));
     }
   }
-  HIPCHK(c, hipEventRecord(c->ev_bs[s], c->stream));
-  if (bare && nr) {  // signers and indices: behind the tally, off the main stream — the next batch's kernels do not wait for 24 B per row
-    HIPCHK(c, hipStreamWaitEvent(c->ostream, c->ev_bs[s], 0));
-    HIPCHK(c, hipMemcpyAsync(c->bs_h_signer[s], c->bs_signer[s].p, n * 20, hipMemcpyDeviceToHost, c->ostream));
-    HIPCHK(c, hipMemcpyAsync(c->bs_h_vidx[s], c->bs_vidx[s].p, n * 4, hipMemcpyDeviceToHost, c->ostream));
+  HIPCHK(c, hipEventRecord(sl.ev, c->stream));
+  if (b.bare && nr) {  // signers and indices: behind the tally, off the main stream — the next batch's kernels do not wait for 24 B per row
+    HIPCHK(c, hipStreamWaitEvent(c->ostream, sl.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(sl.h_signer, sl.signer.p, b.n * 20, hipMemcpyDeviceToHost, c->ostream));
+    HIPCHK(c, hipMemcpyAsync(sl.h_vidx, sl.vidx.p, b.n * 4, hipMemcpyDeviceToHost, c->ostream));
     has_out = true;
   }
-  if (has_out) HIPCHK(c, hipEventRecord(c->ev_bs_out[s], c->ostream));
-  c->bs_rows[s] = nr;
-  c->bs_blocks[s] = nb;
-  c->bs_quorum[s][0] = c->quorum_w[0];
-  c->bs_quorum[s][1] = c->quorum_w[1];
-  c->bs_kind[s] = kind;
-  c->bs_has_out[s] = has_out;
+  if (has_out) HIPCHK(c, hipEventRecord(sl.ev_out, c->ostream));
+  sl.rows = nr;
+  sl.blocks = nb;
+  memcpy(sl.quorum, c->quorum_w, sizeof sl.quorum);
+  sl.kind = b.kind();
+  sl.has_out = has_out;
   c->bs_issued++;
   return IBFT_OK;
 }
 int ibft_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
                             const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags) {
-  return block_seals_submit_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, false);
+  return block_seals_submit_impl(c, {block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags});
 }
 int ibft_block_seals_submit_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round, const uint32_t *seal_off,
                                 size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags) {
   proposal_batch p{raw, raw_off, round, nullptr};
-  return block_seals_submit_impl(c, nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, false);
+  return block_seals_submit_impl(c, {nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags});
 }
 int ibft_recover_block_seals_submit(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, size_t n_blocks,
                                     const uint8_t *sig65, const uint8_t *pre_flags) {
-  return block_seals_submit_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, true);
+  return block_seals_submit_impl(c, {block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, BARE});
 }
 int ibft_recover_block_seals_submit_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
                                         const uint32_t *seal_off, size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags) {
   proposal_batch p{raw, raw_off, round, nullptr};
-  return block_seals_submit_impl(c, nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, true);
+  return block_seals_submit_impl(c, {nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, BARE});
 }
 // The same four under a family of sets (IBFT_BATCH_SETS): the streamed forms of the _sets / _sets_raw calls.
 int ibft_block_seals_submit_sets(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, const uint32_t *block_set,
                                  size_t n_blocks, const uint8_t *sig65, const uint8_t *signer20, const uint8_t *pre_flags) {
-  return block_seals_submit_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, false, true, block_set);
+  return block_seals_submit_impl(c, {block_hash32, nullptr, seal_off, n_blocks, sig65, signer20, pre_flags, !BARE, SETS, block_set});
 }
 int ibft_block_seals_submit_sets_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
                                      const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
                                      const uint8_t *signer20, const uint8_t *pre_flags) {
   proposal_batch p{raw, raw_off, round, nullptr};
-  return block_seals_submit_impl(c, nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, false, true, block_set);
+  return block_seals_submit_impl(c, {nullptr, &p, seal_off, n_blocks, sig65, signer20, pre_flags, !BARE, SETS, block_set});
 }
 int ibft_recover_block_seals_submit_sets(ibft_ctx *c, const uint8_t *block_hash32, const uint32_t *seal_off, const uint32_t *block_set,
                                          size_t n_blocks, const uint8_t *sig65, const uint8_t *pre_flags) {
-  return block_seals_submit_impl(c, block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, true, true, block_set);
+  return block_seals_submit_impl(c, {block_hash32, nullptr, seal_off, n_blocks, sig65, nullptr, pre_flags, BARE, SETS, block_set});
 }
 int ibft_recover_block_seals_submit_sets_raw(ibft_ctx *c, const uint8_t *raw, const uint32_t *raw_off, const uint64_t *round,
                                              const uint32_t *seal_off, const uint32_t *block_set, size_t n_blocks, const uint8_t *sig65,
                                              const uint8_t *pre_flags) {
   proposal_batch p{raw, raw_off, round, nullptr};
-  return block_seals_submit_impl(c, nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, true, true, block_set);
+  return block_seals_submit_impl(c, {nullptr, &p, seal_off, n_blocks, sig65, nullptr, pre_flags, BARE, SETS, block_set});
 }
 
 // The oldest batch in flight → the caller.  ex: ibft_block_seals_collect_ex (digests, signers and indices where the batch's
@@ -3897,7 +3892,9 @@ static int block_seals_collect_impl(ibft_ctx *c, bool ex, uint8_t *out_block_has
     c->last_error = ex ? "ibft_block_seals_collect_ex without a submitted batch" : "ibft_block_seals_collect without a submitted batch";
     return IBFT_E_INVAL;
   }
-  const uint32_t s = c->bs_collected & 1u, nr = c->bs_rows[s], nb = c->bs_blocks[s], kind = c->bs_kind[s];
+  const uint32_t s = c->bs_collected & 1u;
+  BlockSlot &sl = c->bs[s];
+  const uint32_t nr = sl.rows, nb = sl.blocks, kind = sl.kind;
   if (nr && !out_mask) return IBFT_E_INVAL;
   if ((kind & IBFT_BATCH_RECOVER) && nr) {  // refused before anything is written: the batch stays in flight
     if (!ex) {
@@ -3910,22 +3907,22 @@ static int block_seals_collect_impl(ibft_ctx *c, bool ex, uint8_t *out_block_has
     }
   }
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->ev_bs[s]));
-  if (c->bs_has_out[s]) HIPCHK(c, hipEventSynchronize(c->ev_bs_out[s]));
+  HIPCHK(c, hipEventSynchronize(sl.ev));
+  if (sl.has_out) HIPCHK(c, hipEventSynchronize(sl.ev_out));
   if (nr) {
     const size_t mw = (size_t)mask_words(nr);
     memcpy(out_mask, c->p_mask[s], mw * 8);
     if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
   }
   // (a sets batch: the quorum words kept at its submit — c->fam may be another family by now)
-  fill_block_tallies(out_tally, nb, nr, c->bs_tally[s], [&](uint32_t b) -> const uint64_t * {
-    if (!(kind & IBFT_BATCH_SETS)) return c->bs_quorum[s];
-    return &c->bs_setq[s][2 * (size_t)(c->bs_setidx[s].empty() ? b : c->bs_setidx[s][b])];
+  fill_block_tallies(out_tally, nb, nr, sl.rec.h, [&](uint32_t b) -> const uint64_t * {
+    if (!(kind & IBFT_BATCH_SETS)) return sl.quorum;
+    return &sl.setq[2 * (size_t)(sl.setidx.empty() ? b : sl.setidx[b])];
   });
-  if (ex && (kind & IBFT_BATCH_RAW) && out_block_hash32 && nb) memcpy(out_block_hash32, c->bs_h_hash[s], (size_t)nb * 32);
+  if (ex && (kind & IBFT_BATCH_RAW) && out_block_hash32 && nb) memcpy(out_block_hash32, sl.h_hash, (size_t)nb * 32);
   if (ex && (kind & IBFT_BATCH_RECOVER) && nr) {
-    memcpy(out_signer20, c->bs_h_signer[s], (size_t)nr * 20);
-    if (out_vidx) memcpy(out_vidx, c->bs_h_vidx[s], (size_t)nr * 4);
+    memcpy(out_signer20, sl.h_signer, (size_t)nr * 20);
+    if (out_vidx) memcpy(out_vidx, sl.h_vidx, (size_t)nr * 4);
   }
   // The batch is DELIVERED before anything else can fail (the rule of ibft_seals_collect).
   c->bs_collected++;
@@ -3955,10 +3952,11 @@ int ibft_block_seals_pending_ex(ibft_ctx *c, uint32_t *batches_in_flight, uint32
   if (!c) return IBFT_E_INVAL;
   std::lock_guard<std::mutex> lk(c->mu);  // (a call of the pipeline itself)
   const bool any = c->bs_collected != c->bs_issued;
+  const BlockSlot &oldest = c->bs[c->bs_collected & 1u];
   if (batches_in_flight) *batches_in_flight = c->bs_issued - c->bs_collected;
-  if (oldest_rows) *oldest_rows = any ? c->bs_rows[c->bs_collected & 1u] : 0u;
-  if (oldest_blocks) *oldest_blocks = any ? c->bs_blocks[c->bs_collected & 1u] : 0u;
-  if (oldest_kind) *oldest_kind = any ? c->bs_kind[c->bs_collected & 1u] : 0u;
+  if (oldest_rows) *oldest_rows = any ? oldest.rows : 0u;
+  if (oldest_blocks) *oldest_blocks = any ? oldest.blocks : 0u;
+  if (oldest_kind) *oldest_kind = any ? oldest.kind : 0u;
   return IBFT_OK;
 }
 int ibft_block_seals_pending(ibft_ctx *c, uint32_t *batches_in_flight, uint32_t *oldest_rows, uint32_t *oldest_blocks) {
@@ -4149,7 +4147,7 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
     HIPCHK(c, hipMemsetAsync(d_pre + n, 1, half - n, c->stream));
   }
   const bool converted = c->seal_digest_mode != 0;
-  if (converted && (rc = apply_seal_digest(c, half, (uint32_t)n, true))) return rc;
+  if (converted && (rc = apply_seal_digest(c, (uint8_t *)c->d_hash.p + 32ull * half, (uint32_t)n, true))) return rc;
   c->ev_used = 0;
   const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
   // with the pre column: wavefronts whose rows are all dead (the seal rows of PREPAREs, other views, odd encodings) exit at once
@@ -4515,7 +4513,7 @@ int ibft_wire_stage_seals(ibft_ctx *c) {
                        (const wire::row_info *)c->d_wire_rows.p, (const uint8_t *)c->d_seal.p, n,
                        (uint8_t *)c->d_hash.p, (uint8_t *)c->d_sig.p, (uint8_t *)c->d_pre.p);
     HIPCHK(c, hipGetLastError());
-    int rc = apply_seal_digest(c, 0, n, false);
+    int rc = apply_seal_digest(c, c->d_hash.p, n);
     if (rc) return rc;
   }
   c->staged_pre = true;

@@ -18,8 +18,7 @@
 //   verify_known_wave_kernel        same, one wavefront per signature in the row layout of wave_fe_dev.h
 //   envelope_head / _copy / _digest<1|64> / sign_envelope_lane_kernel   f4: PREPREPARE / ROUND_CHANGE envelopes (sign_envelope_dev.h)
 //   tally_kernel                a8  HasQuorum             (core/validator_manager.go:77-96)
-//   block_rows_kernel               chain sync: each block's hash → its rows
-//   block_head_kernel               streamed chain sync (every submit): digests → rows, seal-digest convention fused
+//   block_head_kernel               chain sync (every block call): the blocks' digests → their rows, seal-digest convention fused
 //   block_tally_kernel<PW, THREADS, SETS>   one HasQuorum per block; SETS: under the block's OWN validator set (a family of sets)
 //   gtab_build_kernel, qtab_build_kernel, qtab_commit_kernel   one-time fixed-base tables
 //   lookup_kernel                   sender → validator index for ibft_tally()
@@ -2037,33 +2036,16 @@ __global__ void __launch_bounds__(TALLY_THREADS) tally_kernel(tally_args a) {
   }
 }
 
-// ---- chain sync: the committed seals of many finalized blocks in one call (ibft_verify_block_seals) ----------------
-// Only the blocks' hashes (n_blocks × 32 B) and their row offsets cross PCIe; one thread per row finds its block by binary
-// search over the offsets and writes the block's hash into the row's slot of the hash column the verdict kernels read.
-// (Empty blocks repeat an offset: the LAST b with off[b] ≤ row is the one whose range [off[b], off[b+1]) holds the row.)
-__global__ void block_rows_kernel(const uint8_t *__restrict__ block_hash32, const uint32_t *__restrict__ off, uint32_t n_blocks,
-                                  uint32_t n, uint8_t *__restrict__ hash32) {
-  const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= n) return;
-  uint32_t lo = 0, hi = n_blocks - 1;  // off[0] = 0 ≤ row < off[n_blocks] = n: the answer lies in [lo, hi]
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= row) lo = mid;
-    else hi = mid - 1;
-  }
-  const uint4 *s = reinterpret_cast<const uint4 *>(block_hash32 + 32ull * lo);
-  uint4 *d = reinterpret_cast<uint4 *>(hash32 + 32ull * row);
-  d[0] = s[0];
-  d[1] = s[1];
-}
-
-// The streamed submits (ibft_block_seals_submit[_raw], ibft_recover_block_seals_submit[_raw]): seal-digest convention and
-// spreading over the rows in ONE launch, the blocks' digests (computed, or the uploaded hashes) left as they are.  The synchronous
-// path converts the digests in place (seal_digest_kernel) and then spreads them (block_rows_kernel); in the streamed form the
-// digests leave for the host on another stream while the main stream goes on, so nothing may write them — and one launch
-// less is one dependency gap less per batch.  One thread per row; under a non-identity convention every row hashes its
-// block's digest itself (one permutation: nothing next to an ECDSA recover).  The per-row body is recover_dev.h's
-// block_head_row, which tests/test_dev_block_head_host.py drives on the CPU.
+// ---- chain sync: the committed seals of many finalized blocks in one call (ibft_verify_block_seals …) --------------
+// Only the blocks' hashes (n_blocks × 32 B) — or their proposals — and their row offsets cross PCIe; one thread per row finds
+// its block by binary search over the offsets and writes the hash the row's seal signs into the row's slot of the hash
+// column the verdict kernels read.  The per-row body is recover_dev.h's block_head_row (block_of_row: empty blocks repeat an
+// offset, the LAST b with off[b] ≤ row is the one), which tests/test_dev_block_head_host.py drives on the CPU.
+// The streamed submits: convert = 1 under a non-identity seal-digest convention — convention and spreading in ONE launch, the
+// blocks' digests (computed, or the uploaded hashes) left as they are: they leave for the host on another stream while the
+// main stream goes on, so nothing may write them, and one launch less is one dependency gap less per batch; every row hashes
+// its block's digest itself (one permutation: nothing next to an ECDSA recover).  The synchronous calls: convert = 0 — they
+// converted the digests in place once per BLOCK (seal_digest_kernel) in front, and the row body is a plain copy.
 struct block_head_args {
   const uint64_t *digest_words;  // n_blocks × 4: the blocks' digests (proposal_digest_kernel's, or uploaded hashes), read only
   const uint32_t *off;           // n_blocks + 1 row offsets

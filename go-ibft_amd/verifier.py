@@ -148,6 +148,22 @@ def powers_be32(powers) -> np.ndarray:
     return np.frombuffer(b"".join(int(p).to_bytes(32, "big") for p in powers), dtype=np.uint8).reshape(-1, 32).copy()
 
 
+def _block_call_argtypes() -> dict:
+    """export → argtypes of the sixteen block calls (include/ibftgpu.h), from what each is given: the head (hashes: one pointer,
+    proposals: three), seal_off, a block_set column (the _sets calls), n_blocks, sig65, signer20 unless the seals are bare,
+    pre_flags; the synchronous calls go on with their out buffers: the block hashes (_raw), signers and indices (recover),
+    verdict words, tallies"""
+    vp, out = C.c_void_p, {}
+    for raw in (False, True):
+        for sets in (False, True):
+            for bare in (False, True):
+                given = [vp] * (5 if raw else 3) + [vp] * sets + [C.c_size_t, vp] + [vp] * (not bare) + [vp]   # (the context first)
+                suffix = ("_sets" if sets else "") + ("_raw" if raw else "")
+                out["ibft_" + ("recover" if bare else "verify") + "_block_seals" + suffix] = given + [vp] * (raw + 2 * bare + 2)
+                out["ibft_" + ("recover_" if bare else "") + "block_seals_submit" + suffix] = given
+    return out
+
+
 _lib = None
 ABI_VERSION = 4   # include/ibftgpu.h: ibft_version()  (3: the round-5/6 exports; 4: ibft_pipeline_stats)
 
@@ -216,66 +232,26 @@ def load_library() -> C.CDLL:
     L.ibft_sync.argtypes = [vp]
     L.ibft_issue_probe.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.ibft_seals_rows.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    if hasattr(L, "ibft_pipeline_stats"):
-        L.ibft_pipeline_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    if hasattr(L, "ibft_pipeline_stats_ex"):
-        L.ibft_pipeline_stats_ex.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 3
-    if hasattr(L, "ibft_verify_block_seals"):
-        L.ibft_verify_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
-    if hasattr(L, "ibft_sign_seals_ex"):
-        L.ibft_sign_seals_ex.argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]
-    if hasattr(L, "ibft_sign_messages_wire"):
-        L.ibft_sign_messages_wire.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
-    if hasattr(L, "ibft_sign_envelopes_wire"):
-        L.ibft_sign_envelopes_wire.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, vp, vp]
-    if hasattr(L, "ibft_recover_seals"):
-        L.ibft_recover_seals.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Tally)]
-    if hasattr(L, "ibft_recover_block_seals"):
-        L.ibft_recover_block_seals.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "ibft_proposal_hashes"):
-        L.ibft_proposal_hashes.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
-    if hasattr(L, "ibft_verify_block_seals_raw"):
-        L.ibft_verify_block_seals_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "ibft_recover_block_seals_raw"):
-        L.ibft_recover_block_seals_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "ibft_set_validator_sets"):
-        L.ibft_set_validator_sets.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
-    if hasattr(L, "ibft_set_validator_sets_u256"):
-        L.ibft_set_validator_sets_u256.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
-    if hasattr(L, "ibft_validator_sets_info"):
-        L.ibft_validator_sets_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    if hasattr(L, "ibft_verify_block_seals_sets"):
-        L.ibft_verify_block_seals_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
-    if hasattr(L, "ibft_recover_block_seals_sets"):
-        L.ibft_recover_block_seals_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "ibft_verify_block_seals_sets_raw"):
-        L.ibft_verify_block_seals_sets_raw.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "ibft_recover_block_seals_sets_raw"):
-        L.ibft_recover_block_seals_sets_raw.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "ibft_block_seals_submit_sets"):
-        L.ibft_block_seals_submit_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
-    if hasattr(L, "ibft_block_seals_submit_sets_raw"):
-        L.ibft_block_seals_submit_sets_raw.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
-    if hasattr(L, "ibft_recover_block_seals_submit_sets"):
-        L.ibft_recover_block_seals_submit_sets.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
-    if hasattr(L, "ibft_recover_block_seals_submit_sets_raw"):
-        L.ibft_recover_block_seals_submit_sets_raw.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
-    if hasattr(L, "ibft_block_seals_submit"):
-        L.ibft_block_seals_submit.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
-    if hasattr(L, "ibft_block_seals_collect"):
-        L.ibft_block_seals_collect.argtypes = [vp, vp, vp]
-    if hasattr(L, "ibft_block_seals_pending"):
-        L.ibft_block_seals_pending.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    if hasattr(L, "ibft_block_seals_submit_raw"):
-        L.ibft_block_seals_submit_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
-    if hasattr(L, "ibft_recover_block_seals_submit"):
-        L.ibft_recover_block_seals_submit.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
-    if hasattr(L, "ibft_recover_block_seals_submit_raw"):
-        L.ibft_recover_block_seals_submit_raw.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
-    if hasattr(L, "ibft_block_seals_collect_ex"):
-        L.ibft_block_seals_collect_ex.argtypes = [vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "ibft_block_seals_pending_ex"):
-        L.ibft_block_seals_pending_ex.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4
+    optional = _block_call_argtypes()
+    optional.update({   # the other exports an older build may lack
+        "ibft_pipeline_stats": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+        "ibft_pipeline_stats_ex": [vp] + [C.POINTER(C.c_uint32)] * 3,
+        "ibft_sign_seals_ex": [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp],
+        "ibft_sign_messages_wire": [vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, vp, vp],
+        "ibft_sign_envelopes_wire": [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_uint32, vp, C.c_size_t, vp, vp, vp],
+        "ibft_recover_seals": [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Tally)],
+        "ibft_proposal_hashes": [vp, vp, vp, vp, C.c_size_t, vp],
+        "ibft_set_validator_sets": [vp, C.c_size_t, vp, vp, vp, vp],
+        "ibft_set_validator_sets_u256": [vp, C.c_size_t, vp, vp, vp, vp],
+        "ibft_validator_sets_info": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
+        "ibft_block_seals_collect": [vp, vp, vp],
+        "ibft_block_seals_pending": [vp] + [C.POINTER(C.c_uint32)] * 3,
+        "ibft_block_seals_collect_ex": [vp, vp, vp, vp, vp, vp],
+        "ibft_block_seals_pending_ex": [vp] + [C.POINTER(C.c_uint32)] * 4,
+    })
+    for name, argtypes in optional.items():
+        if hasattr(L, name):
+            getattr(L, name).argtypes = argtypes
     L.ibft_verify_senders_wire.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.POINTER(Tally)]
     L.ibft_wire_stage_seals.argtypes = [vp]
     L.ibft_verify_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, vp, vp, vp, vp]
@@ -481,6 +457,7 @@ class BatchVerifier:
             self._h = C.c_void_p()
             raise GpuUnavailable(f"ibft_ctx_create: {self._L.ibft_strerror(rc).decode()} ({rc})")
         self.max_rows = max_rows
+        self._block_cols = []   # the arrays of the streamed block batches in flight, oldest first (kept alive until their collect)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -567,9 +544,10 @@ class BatchVerifier:
 
     @staticmethod
     def _block_columns(seal_off, sig65, pre_flags, *, hashes=None, proposals=None, signer20=None, bare=False, block_set=None):
-        """the columns of a block batch as the C ABI wants them, lengths checked → (head, off, sig, signer, pre, n, n_blocks).
-        head: (block_hash32,) from `hashes`, or (raw, raw_off, round) from `proposals` = (raws, rounds); signer is None for
-        `bare` seals; block_set: the uint32 column of a _sets call, checked to have one entry per block"""
+        """the columns of a block batch as the C ABI wants them, lengths checked → (front, back, n, n_blocks): the columns every
+        block call takes in front of n_blocks — the head: (block_hash32,) from `hashes`, or (raw, raw_off, round) from `proposals`
+        = (raws, rounds); seal_off; the uint32 block_set column of a _sets call, one entry per block — and behind it — sig65,
+        signer20 unless the seals are `bare`, pre_flags (None as given)"""
         head = None if proposals is None else proposal_columns(*proposals)
         off = np.ascontiguousarray(seal_off, dtype=np.uint32)
         nb = len(off) - 1
@@ -586,33 +564,53 @@ class BatchVerifier:
                     "block_hash32 / block_set need one row per block" if block_set is not None else
                     "block_hash32 needs one row per block")
             raise ValueError(what + ", seal_off[-1] the number of seals")
-        return head, off, s, f, (None if pre_flags is None else _u8(pre_flags)), n, nb
+        pre = None if pre_flags is None else _u8(pre_flags)
+        return [*head, off, *([] if block_set is None else [block_set])], [s, *([] if bare else [f]), pre], n, nb
 
-    @staticmethod
-    def _block_outputs(n, nb, emit=False, hashes=False):
-        """what a block batch delivers into → (mask, tallies, signer20, vidx, block_hash32), the last three None unless asked for"""
-        return (np.zeros((n + 63) // 64 or 1, dtype=np.uint64), (Tally * max(nb, 1))(),
-                np.zeros((max(n, 1), 20), dtype=np.uint8) if emit else None,
-                np.full(max(n, 1), -1, dtype=np.int32) if emit else None,
-                np.zeros((max(nb, 1), 32), dtype=np.uint8) if hashes else None)
+    def _block_args(self, name, seal_off, sig65, pre_flags, **kind):
+        """what every block call starts with: the export is there, the columns are in order → (columns, C arguments, n, n_blocks)"""
+        self._need(name)
+        if "block_set" in kind:   # (a _sets call)
+            kind["block_set"] = np.ascontiguousarray(kind["block_set"], dtype=np.uint32)
+        front, back, n, nb = self._block_columns(seal_off, sig65, pre_flags, **kind)
+        return front + back, [self._h, *map(_p, front), nb, *map(_p, back)], n, nb
+
+    def _block_call(self, name, seal_off, sig65, pre_flags, *, want_hashes=False, **kind):
+        """one of the eight synchronous block calls → (signer20, vidx — the recover calls —, verdict bool[n], Tally list[n_blocks],
+        block_hash32 or None — the _raw calls)"""
+        bare, raw = kind.get("bare", False), "proposals" in kind
+        _, args, n, nb = self._block_args(name, seal_off, sig65, pre_flags, **kind)
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        tallies = (Tally * max(nb, 1))()
+        signer = np.zeros((max(n, 1), 20), dtype=np.uint8) if bare else None
+        vidx = np.full(max(n, 1), -1, dtype=np.int32) if bare else None
+        bh = np.zeros((max(nb, 1), 32), dtype=np.uint8) if want_hashes else None
+        outs = ([_p(bh)] if raw else []) + ([_p(signer), _p(vidx)] if bare else []) + [_p(mask), tallies]
+        self._chk(getattr(self._L, name)(*args, *outs), name)
+        # the rows stay the resident batch of a verify call under the one set; bare rows and rows judged under a family do not
+        self._staged = 0 if bare or "block_set" in kind else n
+        out = ((signer[:n], vidx[:n]) if bare else ()) + (mask_to_bool(mask, n), list(tallies)[:nb])
+        return out + ((bh[:nb] if want_hashes else None,) if raw else ())
+
+    def _block_submit(self, name, seal_off, sig65, pre_flags, **kind) -> int:
+        """one of the eight streamed submits: columns checked, the call made, the arrays kept alive until the collect → n"""
+        cols, args, n, _ = self._block_args(name, seal_off, sig65, pre_flags, **kind)
+        self._chk(getattr(self._L, name)(*args), name)
+        self._block_cols.append(tuple(cols))
+        if n:   # (as after the synchronous sibling; a batch without rows leaves the resident batch alone)
+            self._staged = 0 if kind.get("bare") or "block_set" in kind else n
+        return n
 
     def verify_block_seals(self, block_hash32, seal_off, sig65, signer20, pre_flags=None):
         """ibft_verify_block_seals: block b's seals are rows [seal_off[b], seal_off[b+1]) and sign block_hash32[b] →
         (verdict bool[n], Tally array[n_blocks]) — what one is_valid_committed_seal call per block returns"""
-        self._need("ibft_verify_block_seals")
-        (bh,), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20)
-        mask, tallies, _, _, _ = self._block_outputs(n, nb)
-        self._chk(self._L.ibft_verify_block_seals(self._h, _p(bh), _p(off), nb, _p(s), _p(f), _p(pre), _p(mask), tallies),
-                  "ibft_verify_block_seals")
-        self._staged = n
-        return mask_to_bool(mask, n), list(tallies)[:nb]
+        return self._block_call("ibft_verify_block_seals", seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20)
 
     # bare seals (headers that carry only signatures): who signed?
     def recover_seals(self, hash32, sig65, pre_flags=None):
         """ibft_recover_seals: ecrecover in batch → (signer20 (n, 20) uint8 — zeros where nothing is recovered —, vidx int32[n]
         — index in the validator set or -1 —, verdict bool[n] — recovered and a member —, Tally over the distinct members)"""
-        if not hasattr(self._L, "ibft_recover_seals"):
-            raise GpuUnavailable("this build of the library has no ibft_recover_seals — rebuild")
+        self._need("ibft_recover_seals")
         h = _u8(hash32, (-1, 32)); s = _u8(sig65, (-1, 65))
         n = len(s)
         if len(h) != n:
@@ -630,13 +628,7 @@ class BatchVerifier:
     def recover_block_seals(self, block_hash32, seal_off, sig65, pre_flags=None):
         """ibft_recover_block_seals: recover_seals for many finalized blocks in one call (rows and offsets as
         verify_block_seals, no signer column) → (signer20 (n, 20), vidx int32[n], verdict bool[n], Tally list[n_blocks])"""
-        self._need("ibft_recover_block_seals")
-        (bh,), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, bare=True)
-        mask, tallies, signer, vidx, _ = self._block_outputs(n, nb, emit=True)
-        self._chk(self._L.ibft_recover_block_seals(self._h, _p(bh), _p(off), nb, _p(s), _p(pre), _p(signer), _p(vidx), _p(mask),
-                                                   tallies), "ibft_recover_block_seals")
-        self._staged = 0
-        return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb]
+        return self._block_call("ibft_recover_block_seals", seal_off, sig65, pre_flags, hashes=block_hash32, bare=True)
 
     # chain sync across validator-set changes: a family of sets on the context, a set per block
     @staticmethod
@@ -681,34 +673,20 @@ class BatchVerifier:
     def verify_block_seals_sets(self, block_hash32, seal_off, block_set, sig65, signer20, pre_flags=None):
         """ibft_verify_block_seals_sets: verify_block_seals with block b judged under set block_set[b] of the installed family
         → (verdict bool[n], Tally list[n_blocks]; quorum is the block's set's)"""
-        self._need("ibft_verify_block_seals_sets")
-        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
-        (bh,), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20,
-                                                           block_set=bs)
-        mask, tallies, _, _, _ = self._block_outputs(n, nb)
-        self._chk(self._L.ibft_verify_block_seals_sets(self._h, _p(bh), _p(off), _p(bs), nb, _p(s), _p(f), _p(pre), _p(mask),
-                                                       tallies), "ibft_verify_block_seals_sets")
-        self._staged = 0
-        return mask_to_bool(mask, n), list(tallies)[:nb]
+        return self._block_call("ibft_verify_block_seals_sets", seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20,
+                                block_set=block_set)
 
     def recover_block_seals_sets(self, block_hash32, seal_off, block_set, sig65, pre_flags=None):
         """ibft_recover_block_seals_sets: recover_block_seals with a set per block → (signer20 (n, 20), vidx int32[n] — the index
         in the BLOCK's set or -1 —, verdict bool[n], Tally list[n_blocks])"""
-        self._need("ibft_recover_block_seals_sets")
-        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
-        (bh,), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, bare=True, block_set=bs)
-        mask, tallies, signer, vidx, _ = self._block_outputs(n, nb, emit=True)
-        self._chk(self._L.ibft_recover_block_seals_sets(self._h, _p(bh), _p(off), _p(bs), nb, _p(s), _p(pre), _p(signer), _p(vidx),
-                                                        _p(mask), tallies), "ibft_recover_block_seals_sets")
-        self._staged = 0
-        return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb]
+        return self._block_call("ibft_recover_block_seals_sets", seal_off, sig65, pre_flags, hashes=block_hash32, bare=True,
+                                block_set=block_set)
 
     # chain sync from the proposals: the blocks' hashes are computed on the device
     def proposal_hashes(self, raws, rounds) -> np.ndarray:
         """ibft_proposal_hashes: keccak256(raw_i ‖ BE64(round_i)) of n proposals in one call → uint8 (n, 32).  raws: a list of
         bytes, or (raw, raw_off) — see proposal_columns"""
-        if not hasattr(self._L, "ibft_proposal_hashes"):
-            raise GpuUnavailable("this build of the library has no ibft_proposal_hashes — rebuild")
+        self._need("ibft_proposal_hashes")
         raw, off, rnd = proposal_columns(raws, rounds)
         n = len(rnd)
         out = np.zeros((max(n, 1), 32), dtype=np.uint8)
@@ -718,25 +696,14 @@ class BatchVerifier:
     def verify_block_seals_raw(self, raws, rounds, seal_off, sig65, signer20, pre_flags=None, want_hashes: bool = True):
         """ibft_verify_block_seals_raw: verify_block_seals with the blocks' PROPOSALS (raws, rounds as for proposal_hashes) in
         place of their hashes → (verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
-        self._need("ibft_verify_block_seals_raw")
-        (raw, roff, rnd), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds),
-                                                                      signer20=signer20)
-        mask, tallies, _, _, bh = self._block_outputs(n, nb, hashes=want_hashes)
-        self._chk(self._L.ibft_verify_block_seals_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(f), _p(pre),
-                                                      _p(bh), _p(mask), tallies), "ibft_verify_block_seals_raw")
-        self._staged = n
-        return mask_to_bool(mask, n), list(tallies)[:nb], (bh[:nb] if want_hashes else None)
+        return self._block_call("ibft_verify_block_seals_raw", seal_off, sig65, pre_flags, proposals=(raws, rounds), signer20=signer20,
+                                want_hashes=want_hashes)
 
     def recover_block_seals_raw(self, raws, rounds, seal_off, sig65, pre_flags=None, want_hashes: bool = True):
         """ibft_recover_block_seals_raw: recover_block_seals with the blocks' PROPOSALS in place of their hashes →
         (signer20 (n, 20), vidx int32[n], verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
-        self._need("ibft_recover_block_seals_raw")
-        (raw, roff, rnd), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds), bare=True)
-        mask, tallies, signer, vidx, bh = self._block_outputs(n, nb, emit=True, hashes=want_hashes)
-        self._chk(self._L.ibft_recover_block_seals_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(pre), _p(bh),
-                                                       _p(signer), _p(vidx), _p(mask), tallies), "ibft_recover_block_seals_raw")
-        self._staged = 0
-        return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb], (bh[:nb] if want_hashes else None)
+        return self._block_call("ibft_recover_block_seals_raw", seal_off, sig65, pre_flags, proposals=(raws, rounds), bare=True,
+                                want_hashes=want_hashes)
 
     # chain sync as a stream: submit(k + 1), collect(k) — at most two batches in flight
     def _need_block_stream(self):
@@ -749,10 +716,8 @@ class BatchVerifier:
         are kept alive here until the batch is collected; pass ibft_pinned_alloc memory — pinned_copy() — for the copy to
         run under the kernels of the batch before."""
         self._need_block_stream()
-        (bh,), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20)
-        self._chk(self._L.ibft_block_seals_submit(self._h, _p(bh), _p(off), nb, _p(s), _p(f), _p(pre)), "ibft_block_seals_submit")
-        self._block_cols = getattr(self, "_block_cols", []) + [(bh, off, s, f, pre)]
-        self._staged = n
+        n = self._block_submit("ibft_block_seals_submit", seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20)
+        self._staged = n   # this one — the oldest submit — says so even for a batch without rows; its seven siblings only when n > 0
         return n
 
     def block_seals_collect(self):
@@ -763,7 +728,7 @@ class BatchVerifier:
         mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
         tallies = (Tally * max(nb, 1))()
         self._chk(self._L.ibft_block_seals_collect(self._h, _p(mask), tallies), "ibft_block_seals_collect")
-        if getattr(self, "_block_cols", None):
+        if self._block_cols:
             self._block_cols.pop(0)
         return mask_to_bool(mask, n), list(tallies)[:nb]
 
@@ -775,42 +740,20 @@ class BatchVerifier:
         return int(a.value), int(b.value), int(c.value)
 
     # … from the proposals and from bare seals: the same two slots, collected with block_seals_collect_ex
-    BATCH_RECOVER, BATCH_RAW = 1, 2
+    BATCH_RECOVER, BATCH_RAW, BATCH_SETS = 1, 2, 4   # IBFT_BATCH_*: the kind bits of a batch in flight
 
     def block_seals_submit_raw(self, raws, rounds, seal_off, sig65, signer20, pre_flags=None) -> int:
         """ibft_block_seals_submit_raw: the batch of verify_block_seals_raw, enqueued and not waited for → its row count.
         The arrays (the proposal bytes included) are kept alive here until the batch is collected."""
-        self._need("ibft_block_seals_submit_raw")
-        (raw, roff, rnd), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds),
-                                                                      signer20=signer20)
-        self._chk(self._L.ibft_block_seals_submit_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(f), _p(pre)),
-                  "ibft_block_seals_submit_raw")
-        self._block_cols = getattr(self, "_block_cols", []) + [(raw, roff, rnd, off, s, f, pre)]
-        if n:
-            self._staged = n
-        return n
+        return self._block_submit("ibft_block_seals_submit_raw", seal_off, sig65, pre_flags, proposals=(raws, rounds), signer20=signer20)
 
     def recover_block_seals_submit(self, block_hash32, seal_off, sig65, pre_flags=None) -> int:
         """ibft_recover_block_seals_submit: the batch of recover_block_seals, enqueued and not waited for → its row count"""
-        self._need("ibft_recover_block_seals_submit")
-        (bh,), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=block_hash32, bare=True)
-        self._chk(self._L.ibft_recover_block_seals_submit(self._h, _p(bh), _p(off), nb, _p(s), _p(pre)),
-                  "ibft_recover_block_seals_submit")
-        self._block_cols = getattr(self, "_block_cols", []) + [(bh, off, s, pre)]
-        if n:
-            self._staged = 0
-        return n
+        return self._block_submit("ibft_recover_block_seals_submit", seal_off, sig65, pre_flags, hashes=block_hash32, bare=True)
 
     def recover_block_seals_submit_raw(self, raws, rounds, seal_off, sig65, pre_flags=None) -> int:
         """ibft_recover_block_seals_submit_raw: the batch of recover_block_seals_raw, enqueued and not waited for → its row count"""
-        self._need("ibft_recover_block_seals_submit_raw")
-        (raw, roff, rnd), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds), bare=True)
-        self._chk(self._L.ibft_recover_block_seals_submit_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), nb, _p(s), _p(pre)),
-                  "ibft_recover_block_seals_submit_raw")
-        self._block_cols = getattr(self, "_block_cols", []) + [(raw, roff, rnd, off, s, pre)]
-        if n:
-            self._staged = 0
-        return n
+        return self._block_submit("ibft_recover_block_seals_submit_raw", seal_off, sig65, pre_flags, proposals=(raws, rounds), bare=True)
 
     def block_seals_collect_ex(self) -> dict:
         """ibft_block_seals_collect_ex: the OLDEST submitted batch of any kind → a dict with what its kind carries: always
@@ -825,7 +768,7 @@ class BatchVerifier:
         vidx = np.full(max(n, 1), -1, dtype=np.int32) if kind & self.BATCH_RECOVER else None
         self._chk(self._L.ibft_block_seals_collect_ex(self._h, _p(bh), _p(signer), _p(vidx), _p(mask), tallies),
                   "ibft_block_seals_collect_ex")
-        if getattr(self, "_block_cols", None):
+        if self._block_cols:
             self._block_cols.pop(0)
         out = {"kind": kind, "verdict": mask_to_bool(mask, n), "tallies": list(tallies)[:nb]}
         if bh is not None:
@@ -844,69 +787,39 @@ class BatchVerifier:
         return int(a.value), int(b.value), int(c.value), int(k.value)
 
     # … and under a family of sets, a set per block: the _sets calls from the proposals, and all four as a stream
-    BATCH_SETS = 4
-
     def verify_block_seals_sets_raw(self, raws, rounds, seal_off, block_set, sig65, signer20, pre_flags=None, want_hashes: bool = True):
         """ibft_verify_block_seals_sets_raw: verify_block_seals_sets with the blocks' PROPOSALS in place of their hashes →
         (verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
-        self._need("ibft_verify_block_seals_sets_raw")
-        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
-        (raw, roff, rnd), off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds),
-                                                                      signer20=signer20, block_set=bs)
-        mask, tallies, _, _, bh = self._block_outputs(n, nb, hashes=want_hashes)
-        self._chk(self._L.ibft_verify_block_seals_sets_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), _p(bs), nb, _p(s), _p(f),
-                                                           _p(pre), _p(bh), _p(mask), tallies), "ibft_verify_block_seals_sets_raw")
-        self._staged = 0
-        return mask_to_bool(mask, n), list(tallies)[:nb], (bh[:nb] if want_hashes else None)
+        return self._block_call("ibft_verify_block_seals_sets_raw", seal_off, sig65, pre_flags, proposals=(raws, rounds),
+                                signer20=signer20, block_set=block_set, want_hashes=want_hashes)
 
     def recover_block_seals_sets_raw(self, raws, rounds, seal_off, block_set, sig65, pre_flags=None, want_hashes: bool = True):
         """ibft_recover_block_seals_sets_raw: recover_block_seals_sets with the blocks' PROPOSALS in place of their hashes →
         (signer20 (n, 20), vidx int32[n], verdict bool[n], Tally list[n_blocks], block_hash32 (n_blocks, 32) or None)"""
-        self._need("ibft_recover_block_seals_sets_raw")
-        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
-        (raw, roff, rnd), off, s, _, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, proposals=(raws, rounds), bare=True,
-                                                                      block_set=bs)
-        mask, tallies, signer, vidx, bh = self._block_outputs(n, nb, emit=True, hashes=want_hashes)
-        self._chk(self._L.ibft_recover_block_seals_sets_raw(self._h, _p(raw), _p(roff), _p(rnd), _p(off), _p(bs), nb, _p(s), _p(pre),
-                                                            _p(bh), _p(signer), _p(vidx), _p(mask), tallies),
-                  "ibft_recover_block_seals_sets_raw")
-        self._staged = 0
-        return signer[:n], vidx[:n], mask_to_bool(mask, n), list(tallies)[:nb], (bh[:nb] if want_hashes else None)
-
-    def _submit_sets(self, name, block_set, seal_off, sig65, pre_flags, *, hashes=None, proposals=None, signer20=None, bare=False) -> int:
-        """one of the four _sets submits: columns checked, the call made, the arrays kept alive until the collect"""
-        self._need(name)
-        bs = np.ascontiguousarray(block_set, dtype=np.uint32)
-        head, off, s, f, pre, n, nb = self._block_columns(seal_off, sig65, pre_flags, hashes=hashes, proposals=proposals,
-                                                          signer20=signer20, bare=bare, block_set=bs)
-        args = [_p(x) for x in head] + [_p(off), _p(bs), nb, _p(s)] + ([] if bare else [_p(f)]) + [_p(pre)]
-        self._chk(getattr(self._L, name)(self._h, *args), name)
-        self._block_cols = getattr(self, "_block_cols", []) + [tuple(head) + (off, bs, s, f, pre)]
-        if n:
-            self._staged = 0
-        return n
+        return self._block_call("ibft_recover_block_seals_sets_raw", seal_off, sig65, pre_flags, proposals=(raws, rounds), bare=True,
+                                block_set=block_set, want_hashes=want_hashes)
 
     def block_seals_submit_sets(self, block_hash32, seal_off, block_set, sig65, signer20, pre_flags=None) -> int:
         """ibft_block_seals_submit_sets: the batch of verify_block_seals_sets, enqueued and not waited for → its row count.
         Judged under the family installed NOW, whatever is installed before its collect (block_seals_collect[_ex])."""
-        return self._submit_sets("ibft_block_seals_submit_sets", block_set, seal_off, sig65, pre_flags, hashes=block_hash32,
-                                 signer20=signer20)
+        return self._block_submit("ibft_block_seals_submit_sets", seal_off, sig65, pre_flags, hashes=block_hash32, signer20=signer20,
+                                  block_set=block_set)
 
     def block_seals_submit_sets_raw(self, raws, rounds, seal_off, block_set, sig65, signer20, pre_flags=None) -> int:
         """ibft_block_seals_submit_sets_raw: the batch of verify_block_seals_sets_raw, enqueued and not waited for → its row count"""
-        return self._submit_sets("ibft_block_seals_submit_sets_raw", block_set, seal_off, sig65, pre_flags, proposals=(raws, rounds),
-                                 signer20=signer20)
+        return self._block_submit("ibft_block_seals_submit_sets_raw", seal_off, sig65, pre_flags, proposals=(raws, rounds),
+                                  signer20=signer20, block_set=block_set)
 
     def recover_block_seals_submit_sets(self, block_hash32, seal_off, block_set, sig65, pre_flags=None) -> int:
         """ibft_recover_block_seals_submit_sets: the batch of recover_block_seals_sets, enqueued and not waited for → its row count"""
-        return self._submit_sets("ibft_recover_block_seals_submit_sets", block_set, seal_off, sig65, pre_flags, hashes=block_hash32,
-                                 bare=True)
+        return self._block_submit("ibft_recover_block_seals_submit_sets", seal_off, sig65, pre_flags, hashes=block_hash32, bare=True,
+                                  block_set=block_set)
 
     def recover_block_seals_submit_sets_raw(self, raws, rounds, seal_off, block_set, sig65, pre_flags=None) -> int:
         """ibft_recover_block_seals_submit_sets_raw: the batch of recover_block_seals_sets_raw, enqueued and not waited for → its
         row count"""
-        return self._submit_sets("ibft_recover_block_seals_submit_sets_raw", block_set, seal_off, sig65, pre_flags,
-                                 proposals=(raws, rounds), bare=True)
+        return self._block_submit("ibft_recover_block_seals_submit_sets_raw", seal_off, sig65, pre_flags, proposals=(raws, rounds),
+                                  bare=True, block_set=block_set)
 
     # Verifier.IsValidValidator, batched
     def is_valid_validator(self, payload: bytes, off, sig65, from20, pre_flags=None):

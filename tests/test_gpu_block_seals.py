@@ -414,3 +414,64 @@ def test_error_codes_leave_buffers_untouched():
     finally:
         fresh.close()
         small.close()
+
+
+@pytest.mark.parametrize("suffix", [None, b"\x02"])
+@pytest.mark.parametrize("sizes", [[0, 5, 2, 0, 0, 3, 0], [40, 0, 30]])
+def test_synchronous_spread_equals_one_call_per_block(sizes, suffix):
+    """the four synchronous calls under one set — hashes and proposals, verify and recover — bit for bit one
+    is_valid_committed_seal / recover_seals call per block: empty blocks in front, in the middle and at the end, a block
+    boundary inside a verdict word and across one, under the identity convention and under keccak256(hash ‖ 0x02)"""
+    from oracle import binding as B, workload as W
+    r = W.make_round(7, 91, raw_len=64)
+    nb = len(sizes)
+    raws = [b"block %d of the spread test" % b * (b + 1) for b in range(nb)]
+    rounds = list(range(3, 3 + nb))
+    bh = np.array([np.frombuffer(B.proposal_hash(raw, rnd), np.uint8) for raw, rnd in zip(raws, rounds)], np.uint8).reshape(nb, 32)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
+    n = int(off[-1])
+    assert n <= 70
+    digest = (lambda h: h) if suffix is None else (lambda h: B.keccak256(h + suffix))
+    rh = _rows_hash(bh, off)
+    who = np.arange(n) % 7
+    # every 6th row signs something else than the convention says: invalid under its claimed signer, a stranger when recovered
+    sig = np.array([np.frombuffer(B.sign(r.sks[i], digest(bytes(h)) if k % 6 != 5 else B.keccak256(bytes(h) + b"\x09")), np.uint8)
+                    for k, (i, h) in enumerate(zip(who, rh))], np.uint8).reshape(-1, 65)
+    signer = r.addrs[who].copy()
+    bv = _V().BatchVerifier(max_rows=1024)
+    try:
+        bv.set_validators(r.height, r.addrs, r.power)
+        bv.set_seal_digest(suffix)
+        # the reference, once: one call per block
+        ref_v, ref_r = [], []
+        for b in range(nb):
+            lo, hi = int(off[b]), int(off[b + 1])
+            ref_v.append(bv.is_valid_committed_seal(rh[lo:hi], sig[lo:hi], signer[lo:hi]))
+            ref_r.append(bv.recover_seals(rh[lo:hi], sig[lo:hi]) if hi > lo else None)
+        v_hash = bv.verify_block_seals(bh, off, sig, signer)
+        v_raw = bv.verify_block_seals_raw(raws, rounds, off, sig, signer)
+        r_hash = bv.recover_block_seals(bh, off, sig)
+        r_raw = bv.recover_block_seals_raw(raws, rounds, off, sig)
+        assert (v_raw[2] == bh).all() and (r_raw[4] == bh).all()
+        for name, (got, tl) in (("verify_block_seals", v_hash), ("verify_block_seals_raw", v_raw[:2])):
+            assert len(got) == n and len(tl) == nb
+            for b in range(nb):
+                lo, hi = int(off[b]), int(off[b + 1])
+                m, t = ref_v[b]
+                assert (got[lo:hi] == m).all(), f"{name}: block {b}"
+                assert _fields(tl[b]) == _fields(t) and (tl[b].shard_overlap, tl[b].proposer_rows) == (0, 0), f"{name}: block {b}"
+        for name, (sg, vi, got, tl) in (("recover_block_seals", r_hash), ("recover_block_seals_raw", r_raw[:4])):
+            assert len(got) == n and len(tl) == nb and sg.shape == (n, 20) and vi.shape == (n,)
+            for b in range(nb):
+                lo, hi = int(off[b]), int(off[b + 1])
+                if hi == lo:   # no rows: the empty tally of the set
+                    assert _fields(tl[b]) == _fields(ref_v[b][1]) and tl[b].has_quorum == 0, f"{name}: block {b}"
+                    continue
+                sg1, vi1, m1, t1 = ref_r[b]
+                assert (sg[lo:hi] == sg1).all() and (vi[lo:hi] == vi1).all() and (got[lo:hi] == m1).all(), f"{name}: block {b}"
+                assert _fields(tl[b]) == _fields(t1), f"{name}: block {b}"
+        # the cases hold what they claim: valid and invalid rows, blocks with and without quorum
+        assert 0 < v_hash[0].sum() < n and (v_hash[0] == r_hash[2]).all()
+        assert {t.has_quorum for t in v_hash[1]} == {0, 1}
+    finally:
+        bv.close()
