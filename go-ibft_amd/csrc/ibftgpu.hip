@@ -159,6 +159,59 @@ struct BlockSlot {
   uint64_t block_set_bytes() const { return bset.cap; }  // (ibft_validator_sets_info)
 };
 
+// The counter block of a certificate call, 64 bytes: once in HBM (CertState::total), once in pinned memory (h_total; dh_total
+// is that mirror as the device sees it).  The kernels keep their word pointers — each is handed the address of the first
+// field it writes — and the host reads the fields by name.
+struct cert_counters {
+  uint32_t next_rows, carriers;  // cert_scan_launch, once per level: rows of the next level, deferred rows among this level's
+  uint32_t records;              // cert_record_scan_kernel (judge, when level 1 is listed): rows that get a record
+  uint32_t pad0;
+  uint32_t dense, unplaced;               // cert_dedup_front_launch: representatives, rows the table could not place
+  uint32_t judged_tree, judged_deferred;  // cert_dedup_count_launch: rows without a pre-flag, the tree's and the deferred batch's
+  uint32_t count_acc[3];                  // cert_dedup_count_kernel's two sums and its ticket: zero between launches
+  uint32_t pad1[5];
+};
+static_assert(sizeof(cert_counters) == 64, "the counter block the kernels address by word");
+static_assert(offsetof(cert_counters, next_rows) == 0 && offsetof(cert_counters, carriers) == 4 && offsetof(cert_counters, records) == 8 &&
+                  offsetof(cert_counters, pad0) == 12 && offsetof(cert_counters, dense) == 16 && offsetof(cert_counters, unplaced) == 20 &&
+                  offsetof(cert_counters, judged_tree) == 24 && offsetof(cert_counters, judged_deferred) == 28 &&
+                  offsetof(cert_counters, count_acc) == 32 && offsetof(cert_counters, pad1) == 44,
+              "cert_scan_launch writes words 0-1, cert_record_scan_kernel word 2, the dedup front words 4-5, the count launch 6-7 over 8-10");
+
+// Certificates from wire bytes (ibft_verify_certificates_wire, ibft_judge_certificates_wire): everything the route owns beyond
+// the shared columns, grown by the first call that needs it (cert_reserve) and kept.
+struct CertState {
+  // tree nodes, where each row's nested messages lie, child counts of the level being expanded, the deferred rows' list,
+  // proposal digests, hash / self words, the tile scan's cells; the counters come back through one mapped block
+  DevBuf nodes, span, count, slot, prop, masks, total, tiles;
+  DevBuf rec, recbase;            // ibft_judge_certificates_wire: one record per carrier, the roots' first records
+  DevBuf dd_table, dd_slot, dd_pos;  // the dedup: the table, every row's slot, every representative's dense position
+  cert_counters *h_total = nullptr, *dh_total = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the side stream (hstream) hashes the deferred rows next to the verdict launch
+  bool overlap = true;                              // IBFT_CERT_OVERLAP=0: everything on one stream, one verdict launch
+  // IBFT_FLAG_CERT_DEDUP / IBFT_CERT_DEDUP=0|1: the (first) verdict launch of a certificate call judges each distinct
+  // (digest, signature, From) once (cert_dedup_dev.h)
+  bool dedup = false;
+  uint32_t dedup_slots_cap = 0;     // IBFT_CERT_DEDUP_SLOTS (test hook): at most that many table slots; 0 = no cap
+  uint32_t stat[4] = {0, 0, 0, 0};  // ibft_cert_stats: rows, judged, given to the verdict kernels, unplaced — of the last certificate call
+
+  void release_all() {  // device buffers, the pinned block, the two events (ibft_ctx_destroy)
+    for (DevBuf *b : {&nodes, &span, &count, &slot, &prop, &masks, &total, &tiles, &rec, &recbase, &dd_table, &dd_slot, &dd_pos}) release(*b);
+    if (h_total) (void)hipHostFree(h_total);
+    for (hipEvent_t e : {ev_fork, ev_join})
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// What the flat wire calls left in the columns: `rows` rows of the last ibft_verify_senders_wire / ibft_verify_messages_wire.
+// One count serves both flags: only ibft_verify_senders_wire sets `columns`, and whatever sets `parsed` after it either is
+// that same call or has cleared `columns` on its way in.
+struct WireBatch {
+  uint32_t rows = 0;
+  bool columns = false;  // ibft_wire_stage_seals: the senders-wire batch is still the resident one
+  bool parsed = false;   // ibft_wire_stats: its parse results are still in d_wire_rows
+};
+
 struct ibft_ctx {
   std::mutex mu;
   std::shared_ptr<DeviceShared> dev;   // the G table and the key cache of this context's device
@@ -237,13 +290,10 @@ struct ibft_ctx {
   uint32_t mask_dirty_words = ~0u;
   DevBuf d_wire_rows, d_seal;  // §8f rank 3: per-row parse results and the COMMIT seals found in the wire bytes
   DevBuf d_noseal;             // message sets from wire bytes: rows (PREPAREs) whose closure has no seal
-  uint32_t wire_n = 0;         // rows of the last ibft_verify_senders_wire
-  bool wire_valid = false;     // its columns are still the resident ones
+  WireBatch wire;              // what the last flat wire call left resident
   // IBFT_FLAG_WIRE_RECODE / IBFT_WIRE_RECODE=0|1: the flat wire calls run wire_recode_kernel over the rows the canonical walk
   // marked NEEDS_HOST (wire_recode_dev.h)
   bool wire_recode = false;
-  uint32_t wire_stat_n = 0;      // ibft_wire_stats: rows of the last flat wire call ...
-  bool wire_stat_valid = false;  // ... whose parse results are still in d_wire_rows
   // fixed-base table for G
   // validator table
   DevBuf d_vtab, d_vpower;
@@ -371,20 +421,7 @@ struct ibft_ctx {
   DevBuf d_set;
   uint8_t *h_class = nullptr, *dh_class = nullptr;  // one routing byte per wire row (ibft_verify_messages_wire)
   DevBuf d_class;
-  // certificates from wire bytes (ibft_verify_certificates_wire): tree nodes, where each row's nested messages lie,
-  // child counts of the level being expanded, proposal digests, hash / self words; the row count of the next level
-  // comes back through one mapped word
-  DevBuf d_cert_nodes, d_cert_span, d_cert_count, d_cert_prop, d_cert_masks, d_cert_total, d_cert_slot, d_cert_tiles;
-  DevBuf d_cert_rec, d_cert_recbase;  // ibft_judge_certificates_wire: one record per carrier, the roots' first records
-  uint32_t *h_cert_total = nullptr, *dh_cert_total = nullptr;
-  hipEvent_t ev_cert_fork = nullptr, ev_cert_join = nullptr;  // the side stream (hstream) hashes the deferred rows next to the verdict launch
-  bool cert_overlap = true;                                   // IBFT_CERT_OVERLAP=0: everything on one stream, one verdict launch
-  // IBFT_FLAG_CERT_DEDUP / IBFT_CERT_DEDUP=0|1: the (first) verdict launch of a certificate call judges each distinct
-  // (digest, signature, From) once (cert_dedup_dev.h): the table, every row's slot, every representative's dense position
-  bool cert_dedup = false;
-  uint32_t cert_dedup_slots_cap = 0;  // IBFT_CERT_DEDUP_SLOTS (test hook): at most that many table slots; 0 = no cap
-  DevBuf d_cert_dd_table, d_cert_dd_slot, d_cert_dd_pos;
-  uint32_t cert_stat[4] = {0, 0, 0, 0};  // ibft_cert_stats: rows, judged, given to the verdict kernels, unplaced — of the last certificate call
+  CertState cert;  // certificates from wire bytes (ibft_verify_certificates_wire, ibft_judge_certificates_wire)
   bool gather_pinned = true;  // columns in ibft_pinned_alloc buffers are read by one gather launch (IBFT_NO_GATHER=1: never)
   // … whose extra blocks can hash PayloadNoSig straight from the host column (IBFT_DIGEST_FUSION=1).  Off by default: it
   // saves nothing measurable (gather + digest ≈ 46 µs either way) and the 8 192-row known-key kernel of a COMMIT set ran
@@ -1144,6 +1181,15 @@ int upload(ibft_ctx *c, DevBuf &b, const void *src, size_t bytes) {
   return IBFT_OK;
 }
 
+// the n + 1 offsets of a batch of byte strings never decrease (off may be null when n == 0)
+bool offsets_ok(const uint32_t *off, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return false;
+  return true;
+}
+// … and a batch that has bytes comes with them
+bool bytes_ok(const uint32_t *off, size_t n, const void *bytes) { return !(n && off[n] && !bytes); }
+
 // Blocks handed out by ibft_pinned_alloc: a column that lies inside one can be read by the device directly.
 struct PinnedRegistry {
   std::mutex mu;
@@ -1532,7 +1578,7 @@ struct sign_call {
   }
   int begin() {
     HIPCHK(c, hipSetDevice(c->device));
-    c->wire_valid = false;  // the columns used from here on are the wire walker's and the seal batch's
+    c->wire.columns = false;  // the columns used from here on are the wire walker's and the seal batch's
     c->staged_n = 0;
     return IBFT_OK;
   }
@@ -1700,12 +1746,12 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
     if (atoi(e) == 1) c->time_every = 0;
   if (getenv("IBFT_NO_GATHER")) c->gather_pinned = false;
   if (const char *e = getenv("IBFT_PROPOSAL_HASH")) c->hash_on_host = strcmp(e, "device") != 0;
-  if (const char *e = getenv("IBFT_CERT_OVERLAP")) c->cert_overlap = atoi(e) != 0;
-  c->cert_dedup = (c->flags & IBFT_FLAG_CERT_DEDUP) != 0;
-  if (const char *e = getenv("IBFT_CERT_DEDUP")) c->cert_dedup = atoi(e) != 0;
+  if (const char *e = getenv("IBFT_CERT_OVERLAP")) c->cert.overlap = atoi(e) != 0;
+  c->cert.dedup = (c->flags & IBFT_FLAG_CERT_DEDUP) != 0;
+  if (const char *e = getenv("IBFT_CERT_DEDUP")) c->cert.dedup = atoi(e) != 0;
   c->wire_recode = (c->flags & IBFT_FLAG_WIRE_RECODE) != 0;
   if (const char *e = getenv("IBFT_WIRE_RECODE")) c->wire_recode = atoi(e) != 0;
-  if (const char *e = getenv("IBFT_CERT_DEDUP_SLOTS")) c->cert_dedup_slots_cap = (uint32_t)strtoul(e, nullptr, 10);
+  if (const char *e = getenv("IBFT_CERT_DEDUP_SLOTS")) c->cert.dedup_slots_cap = (uint32_t)strtoul(e, nullptr, 10);
   if (getenv("IBFT_DIGEST_FUSION")) c->digest_in_gather = true;
   if (const char *e = getenv("IBFT_WAVE_ROWS_MAX")) c->wave_rows_max = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_PAIR_ROWS_MAX")) c->pair_rows_max = (uint32_t)strtoul(e, nullptr, 10);
@@ -1808,8 +1854,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_vtab, &c->d_vpower, &c->d_vslot,
                     &c->d_warm_done, &c->d_seen, &c->d_acc, &c->d_quorum, &c->d_wire_rows, &c->d_seal,
                     &c->d_xbuf[0], &c->d_xbuf[1], &c->d_xres[0], &c->d_xres[1], &c->d_set, &c->d_noseal, &c->d_class,
-                    &c->d_cert_nodes, &c->d_cert_span, &c->d_cert_count, &c->d_cert_prop, &c->d_cert_masks, &c->d_cert_total,
-                    &c->d_cert_slot, &c->d_cert_tiles, &c->d_cert_rec, &c->d_cert_recbase, &c->d_cert_dd_table, &c->d_cert_dd_slot, &c->d_cert_dd_pos, &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
+                    &c->d_hash_copy, &c->d_seen_out, &c->d_hash_nx, &c->d_sig_nx,
                     &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->brec.d,
                     &c->d_boff_nx, &c->d_praw, &c->d_proff, &c->d_pround,
                     &c->d_phash, &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
@@ -1843,9 +1888,7 @@ void ibft_ctx_destroy(ibft_ctx *c) {
     }
     c->dev.reset();
   }
-  if (c->h_cert_total) (void)hipHostFree(c->h_cert_total);
-  if (c->ev_cert_fork) (void)hipEventDestroy(c->ev_cert_fork);
-  if (c->ev_cert_join) (void)hipEventDestroy(c->ev_cert_join);
+  c->cert.release_all();
   comm_release(c);
   if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
   if (c->ev_read) (void)hipEventDestroy(c->ev_read);
@@ -2344,7 +2387,7 @@ int ibft_proposal_hash(ibft_ctx *c, const uint8_t *raw, size_t raw_len, uint64_t
 
 static int hash_eq_locked(ibft_ctx *c, const uint8_t *hash32, const uint8_t *hash_len, size_t n, uint64_t *out_mask) {
   int rc;
-  c->wire_valid = false;
+  c->wire.columns = false;
   if ((rc = wait_proposal_hash(c))) return rc;
   ColumnCopies cc;
   cc.add(c->d_hash.p, hash32, n * 32);
@@ -2405,7 +2448,7 @@ static int seals_stage_locked(ibft_ctx *c, const uint8_t *hash32, const uint8_t 
   if (n > c->max_rows) return IBFT_E_TOOBIG;
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  c->wire_valid = false;
+  c->wire.columns = false;
   ColumnCopies cc;
   cc.add(c->d_hash.p, hash32, n * 32);
   cc.add(c->d_sig.p, sig65, n * 65);
@@ -2496,7 +2539,7 @@ int ibft_seals_swap(ibft_ctx *c, int wait_for_copy) {
   c->staged_n = c->next_n;
   c->staged_pre = c->next_pre;
   c->next_valid = false;
-  c->wire_valid = false;
+  c->wire.columns = false;
   int rc;
   if ((rc = apply_seal_digest(c, c->d_hash.p, c->staged_n))) return rc;
   if (wait_for_copy) HIPCHK(c, hipEventSynchronize(c->ev_staged));  // the caller's source buffers are free again
@@ -2892,6 +2935,92 @@ void ibft_pinned_free(void *p) {
   (void)hipHostFree(p);
 }
 
+// ---- What the two message-set routes share (columns: messages_launch_locked + ibft_verify_messages; wire bytes:
+// ibft_verify_messages_wire): the proposal in front, the combine step and tally behind the verdict launch, the two endings.
+// c->mu held throughout.
+
+// The proposal the set is checked against: the caller's digest, or raw ‖ BE64(round) hashed once and remembered.
+// *hash_needed: that hash is still to be launched (enqueue_set_tally does; an empty set's caller does it itself)
+static int set_proposal_begin(ibft_ctx *c, const uint8_t *digest32, const uint8_t *raw, size_t raw_len, uint64_t round, bool *hash_needed) {
+  *hash_needed = false;
+  if (!digest32) {
+    *hash_needed = note_proposal(c, raw, raw_len, round);
+    return IBFT_OK;
+  }
+  int rc;
+  if ((rc = wait_proposal_hash(c))) return rc;  // a hash still on its way must not land on top of the caller's digest
+  c->have_H = false;
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the staging buffer is free again
+  memcpy(c->h_digest, digest32, 32);
+  HIPCHK(c, hipMemcpyAsync(c->d_H.p, c->h_digest, 32, hipMemcpyHostToDevice, c->stream));
+  return IBFT_OK;
+}
+
+// what the combine step of a set is told beyond the columns both routes share (device pointers; null / 0 / false: absent)
+struct set_tail {
+  const uint8_t *sender_pre = nullptr, *valid_pre = nullptr;  // rows rejected before any crypto, per verdict
+  const uint8_t *no_seal = nullptr;                           // rows whose closure has no seal (PREPAREs among wire rows)
+  uint32_t half_words = 0;     // where the seal rows' verdict words begin (0: no seal half)
+  bool converted = false;      // a1 compares the carried hashes apply_seal_digest kept in d_hash_copy
+  bool hash_needed = false;    // set_proposal_begin's answer
+  // the wire call notes its proposer HERE, behind the hash wait: a failure in front of it leaves none to a later call
+  bool note_proposer = false;
+  const uint8_t *proposer20 = nullptr;
+};
+// Behind the verdict launch of a set of n rows whose carried hashes are rows [half, half + n) of the hash column: the
+// proposal's hash (launched on the side stream if still needed, waited for), the combine step and tally, the words' way home.
+static int enqueue_set_tally(ibft_ctx *c, size_t n, uint32_t half, const set_tail &t) {
+  int rc;
+  ibftk::set_args sa{};
+  sa.sender_pre = t.sender_pre;
+  sa.valid_pre = t.valid_pre;
+  sa.no_seal = t.no_seal;
+  sa.hash32 = t.converted ? (const uint8_t *)c->d_hash_copy.p : (const uint8_t *)c->d_hash.p + 32ull * half;
+  sa.hash_len = (const uint8_t *)c->d_hash_len.p;
+  sa.H4 = (const uint64_t *)c->d_H.p;
+  sa.n = (uint32_t)n;
+  sa.half_words = t.half_words;
+  sa.sender_out = (uint64_t *)c->d_set.p;
+  sa.valid_out = (uint64_t *)c->d_set.p + mask_words(c->max_rows);
+  sa.host_sender = c->dh_set;
+  sa.host_valid = c->dh_set ? c->dh_set + mask_words(c->max_rows) : nullptr;
+  // the verdict launch did not need the proposal's hash, the combine step does: hashed on the side stream meanwhile
+  if (t.hash_needed && (rc = launch_proposal_hash(c))) return rc;
+  if ((rc = wait_proposal_hash(c))) return rc;
+  if (t.note_proposer) note_proposer(c, t.proposer20);
+  if ((rc = enqueue_tally(c, (uint32_t)n, &sa))) return rc;
+  c->mask_dirty_words = 0;  // the combine kernel zeroed the seal words, the tally the sender words
+  if (!c->dh_set)
+    HIPCHK(c, hipMemcpyAsync(c->h_set, c->d_set.p, (size_t)mask_words(c->max_rows) * 16, hipMemcpyDeviceToHost, c->stream));
+  return IBFT_OK;
+}
+
+// The answer to a set without rows.  With a proposer, HasPrepareQuorum of no messages is still a question (the proposer alone
+// may be a quorum: validator_manager.go:109-126) and the tally the caller enqueued answers it; without one, a zero tally.
+static int answer_empty_set(ibft_ctx *c, const uint8_t *proposer20, ibft_tally_t *tally) {
+  if (proposer20) return fetch_results(c, 0, nullptr, tally, true);
+  if (tally) {
+    memset(tally, 0, sizeof *tally);
+    tally->quorum_lo = c->quorum_w[0];
+    tally->quorum_hi = c->quorum_w[1];
+  }
+  for (int i = 0; i < ibftk::TALLY_SUM_WORDS; i++) c->last_wide[i] = 0;
+  return IBFT_OK;
+}
+
+// … and to one with rows: the tally, then the sender and the valid words out of h_set
+static int fetch_set_masks(ibft_ctx *c, size_t n, uint64_t *out_sender_mask, uint64_t *out_valid_mask, ibft_tally_t *tally) {
+  int rc;
+  if ((rc = fetch_results(c, (uint32_t)n, nullptr, tally, true))) {
+    c->have_H = false;
+    return rc;
+  }
+  const size_t mw = (size_t)mask_words(n);
+  memcpy(out_sender_mask, c->h_set, mw * 8);
+  memcpy(out_valid_mask, c->h_set + mask_words(c->max_rows), mw * 8);
+  return IBFT_OK;
+}
+
 // A whole PREPARE or COMMIT set in one call (kernels.hip.h: "a message set in one pass").
 // a message set up to and including its tally, everything asynchronous past the uploads (c->mu held)
 static int messages_launch_locked(ibft_ctx *c, const uint8_t *payload, const uint32_t *off, const uint8_t *msg_sig65,
@@ -2900,34 +3029,23 @@ static int messages_launch_locked(ibft_ctx *c, const uint8_t *payload, const uin
                                   uint64_t round, const uint8_t *digest32) {
   if (n && (!off || !msg_sig65 || !from20 || !hash32 || !hash_len)) return IBFT_E_INVAL;
   if ((raw_len && !raw) || raw_len > (1ull << 31)) return IBFT_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return IBFT_E_INVAL;
-  if (n && off[n] && !payload) return IBFT_E_INVAL;
+  if (!offsets_ok(off, n) || !bytes_ok(off, n, payload)) return IBFT_E_INVAL;
   if (n > c->max_rows) return IBFT_E_TOOBIG;
   if (!c->have_valset) return IBFT_E_NOVALSET;
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  c->wire_valid = false;
+  c->wire.columns = false;
   c->staged_n = 0;
   c->set_n = (uint32_t)n;
   const uint32_t half = ((uint32_t)n + 63u) & ~63u;
   const uint32_t rows = seal65 ? half + (uint32_t)n : (uint32_t)n;  // verdict rows of the one launch
   if ((rc = alloc_rows(c, 2 * (((uint32_t)c->max_rows + 63u) & ~63u)))) return rc;
-  // the proposal the set is checked against: its digest, or raw ‖ BE64(round) hashed once and remembered
-  bool hash_needed = false;
-  if (digest32) {
-    if ((rc = wait_proposal_hash(c))) return rc;  // a hash still on its way must not land on top of the caller's digest
-    c->have_H = false;
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the staging buffer is free again
-    memcpy(c->h_digest, digest32, 32);
-    HIPCHK(c, hipMemcpyAsync(c->d_H.p, c->h_digest, 32, hipMemcpyHostToDevice, c->stream));
-  } else {
-    hash_needed = note_proposal(c, raw, raw_len, round);
-  }
+  bool hash_needed;
+  if ((rc = set_proposal_begin(c, digest32, raw, raw_len, round, &hash_needed))) return rc;
   if (n == 0) {
     if (hash_needed && (rc = launch_proposal_hash(c))) return rc;
     // an empty shard of a sharded set still contributes (zero) words, an empty bitmap and a zero count to the exchange;
-    // HasPrepareQuorum of no messages is still a question (the proposer alone may be a quorum: validator_manager.go:109-126)
+    // so does the set of a caller that noted a proposer (answer_empty_set)
     if (c->comm || c->xlocal || c->next_prop_on) return enqueue_tally(c, 0);
     return IBFT_OK;
   }
@@ -2962,27 +3080,14 @@ static int messages_launch_locked(ibft_ctx *c, const uint8_t *payload, const uin
   if (converted && (rc = apply_seal_digest(c, (uint8_t *)c->d_hash.p + 32ull * half, (uint32_t)n, true))) return rc;
   c->ev_used = 0;
   const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
-  if ((rc = enqueue_recover(c, c->stream, rows, false, ibftk::MODE_SEALS, time_it))) return rc;
-  ibftk::set_args sa{};
-  sa.sender_pre = sender_pre ? d_pre : nullptr;
-  sa.valid_pre = valid_pre ? d_pre + half : nullptr;
-  sa.hash32 = converted ? (const uint8_t *)c->d_hash_copy.p : d_hash + 32ull * half;
-  sa.hash_len = (const uint8_t *)c->d_hash_len.p;
-  sa.H4 = (const uint64_t *)c->d_H.p;
-  sa.n = (uint32_t)n;
-  sa.half_words = seal65 ? half / 64 : 0;
-  sa.sender_out = (uint64_t *)c->d_set.p;
-  sa.valid_out = (uint64_t *)c->d_set.p + mask_words(c->max_rows);
-  sa.host_sender = c->dh_set;
-  sa.host_valid = c->dh_set ? c->dh_set + mask_words(c->max_rows) : nullptr;
-  // the verdict launch above did not need the proposal's hash, the combine step does: hashed on the side stream meanwhile
-  if (hash_needed && (rc = launch_proposal_hash(c))) return rc;
-  if ((rc = wait_proposal_hash(c))) return rc;
-  if ((rc = enqueue_tally(c, (uint32_t)n, &sa))) return rc;
-  c->mask_dirty_words = 0;  // the combine kernel zeroed the seal words, the tally the sender words
-  if (!c->dh_set)
-    HIPCHK(c, hipMemcpyAsync(c->h_set, c->d_set.p, (size_t)mask_words(c->max_rows) * 16, hipMemcpyDeviceToHost, c->stream));
-  return IBFT_OK;
+  if ((rc = enqueue_recover(c, c->stream, rows, /*with_pre=*/false, ibftk::MODE_SEALS, time_it))) return rc;
+  set_tail t;
+  t.sender_pre = sender_pre ? d_pre : nullptr;
+  t.valid_pre = valid_pre ? d_pre + half : nullptr;
+  t.half_words = seal65 ? half / 64 : 0;
+  t.converted = converted;
+  t.hash_needed = hash_needed;
+  return enqueue_set_tally(c, n, half, t);  // (the proposer, if any, was noted by the caller)
 }
 
 int ibft_verify_messages(ibft_ctx *c, const uint8_t *payload, const uint32_t *off, const uint8_t *msg_sig65,
@@ -2998,24 +3103,8 @@ int ibft_verify_messages(ibft_ctx *c, const uint8_t *payload, const uint32_t *of
                                   raw_len, round, digest32);
   c->next_prop_on = c->next_shard = false;  // (an error in front of the tally must not leave the proposer to a later call)
   if (rc) return rc;
-  if (n == 0) {
-    if (proposer20) return fetch_results(c, 0, nullptr, tally, true);
-    if (tally) {
-      memset(tally, 0, sizeof *tally);
-      tally->quorum_lo = c->quorum_w[0];
-      tally->quorum_hi = c->quorum_w[1];
-    }
-    for (int i = 0; i < ibftk::TALLY_SUM_WORDS; i++) c->last_wide[i] = 0;
-    return IBFT_OK;
-  }
-  const size_t mw = (size_t)mask_words(n);
-  if ((rc = fetch_results(c, (uint32_t)n, nullptr, tally, true))) {
-    c->have_H = false;
-    return rc;
-  }
-  memcpy(out_sender_mask, c->h_set, mw * 8);
-  memcpy(out_valid_mask, c->h_set + mask_words(c->max_rows), mw * 8);
-  return IBFT_OK;
+  if (n == 0) return answer_empty_set(c, proposer20, tally);  // (its tally: messages_launch_locked, the proposer being noted)
+  return fetch_set_masks(c, n, out_sender_mask, out_valid_mask, tally);
 }
 
 // f4: the committed seals of a simulated validator set, one per row.
@@ -3535,7 +3624,7 @@ static int block_seals_impl(ibft_ctx *c, block_batch b, const block_outputs &o) 
   HIPCHK(c, hipSetDevice(c->device));
   proposal_batch *const props = b.props;
   const uint32_t nb = (uint32_t)b.n_blocks, nr = (uint32_t)b.n;
-  c->wire_valid = false;
+  c->wire.columns = false;
   // the proposals are hashed when rows wait for the hashes or the caller wants them
   const bool hash_here = props && nb && (nr || props->out_hash32);
   ColumnCopies cc;
@@ -3803,7 +3892,7 @@ static int block_seals_submit_impl(ibft_ctx *c, block_batch b) {
       std::swap(c->d_signer, c->d_signer_nx);
       std::swap(c->d_pre, c->d_pre_nx);
       std::swap(c->d_boff, c->d_boff_nx);
-      c->wire_valid = false;
+      c->wire.columns = false;
       // verify kind: the rows are the resident batch from here on; bare rows are none, and neither are rows judged against a
       // family's union (as after the synchronous siblings)
       c->staged_n = b.bare || b.sets ? 0 : nr;
@@ -3967,14 +4056,12 @@ int ibft_block_seals_pending(ibft_ctx *c, uint32_t *batches_in_flight, uint32_t 
 static int senders_launch_locked(ibft_ctx *c, const uint8_t *payload, const uint32_t *off, const uint8_t *sig65,
                                  const uint8_t *from20, const uint8_t *pre_flags, size_t n) {
   if (n && (!off || !sig65 || !from20)) return IBFT_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return IBFT_E_INVAL;
-  if (n && off[n] && !payload) return IBFT_E_INVAL;
+  if (!offsets_ok(off, n) || !bytes_ok(off, n, payload)) return IBFT_E_INVAL;
   if (n > c->max_rows) return IBFT_E_TOOBIG;
   if (!c->have_valset) return IBFT_E_NOVALSET;
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  c->wire_valid = false;
+  c->wire.columns = false;
   size_t pbytes = n ? off[n] : 0;
   if ((rc = ensure(c, c->d_payload, pbytes + 256))) return rc;
   ColumnCopies cc;
@@ -4011,12 +4098,29 @@ static int enqueue_wire_recode(ibft_ctx *c, uint32_t n) {
   return IBFT_OK;
 }
 
+// what both flat wire calls need in HBM: the bytes (with 256 of slack), the parse results, the seals the walk finds
+static int ensure_wire_buffers(ibft_ctx *c, size_t wbytes) {
+  int rc;
+  if ((rc = ensure(c, c->d_payload, wbytes + 256))) return rc;
+  if ((rc = ensure(c, c->d_wire_rows, (size_t)c->max_rows * sizeof(wire::row_info)))) return rc;
+  return ensure(c, c->d_seal, (size_t)c->max_rows * 65 + 64);
+}
+
+// the canonical walk over the n > 0 messages in d_payload / d_off, then the recode walk where the flag asks for it
+static int enqueue_wire_parse(ibft_ctx *c, uint32_t n) {
+  hipLaunchKernelGGL(ibftk::wire_parse_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const uint8_t *)c->d_payload.p,
+                     (const uint32_t *)c->d_off.p, n, (wire::row_info *)c->d_wire_rows.p, (uint8_t *)c->d_hash.p,
+                     (uint8_t *)c->d_sig.p, (uint8_t *)c->d_signer.p, (uint8_t *)c->d_seal.p, (uint8_t *)c->d_pre.p);
+  HIPCHK(c, hipGetLastError());
+  return enqueue_wire_recode(c, n);
+}
+
 int ibft_wire_stats(ibft_ctx *c, uint32_t *rows, uint32_t *recoded_rows, uint32_t *needs_host_rows) {
   if (!c) return IBFT_E_INVAL;
   ctx_lock lk(c);
   uint32_t n = 0, recoded = 0, needs = 0;
-  if (c->wire_stat_valid && c->wire_stat_n) {
-    n = c->wire_stat_n;
+  if (c->wire.parsed && c->wire.rows) {
+    n = c->wire.rows;
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<wire::row_info> h(n);
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4036,42 +4140,30 @@ int ibft_verify_senders_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint3
                              ibft_wire_row_t *out_rows, ibft_tally_t *tally) {
   static_assert(sizeof(ibft_wire_row_t) == sizeof(wire::row_info), "ABI");
   if (!c || (n && (!off || !out_mask))) return IBFT_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return IBFT_E_INVAL;
-  if (n && off[n] && !wire_bytes) return IBFT_E_INVAL;
+  if (!offsets_ok(off, n) || !bytes_ok(off, n, wire_bytes)) return IBFT_E_INVAL;
   ctx_lock lk(c);
   if (n > c->max_rows) return IBFT_E_TOOBIG;
   if (!c->have_valset) return IBFT_E_NOVALSET;
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   const size_t wbytes = n ? off[n] : 0;
-  if ((rc = ensure(c, c->d_payload, wbytes + 256))) return rc;
-  if ((rc = ensure(c, c->d_wire_rows, (size_t)c->max_rows * sizeof(wire::row_info)))) return rc;
-  if ((rc = ensure(c, c->d_seal, (size_t)c->max_rows * 65 + 64))) return rc;
+  if ((rc = ensure_wire_buffers(c, wbytes))) return rc;
   if (wbytes) HIPCHK(c, hipMemcpyAsync(c->d_payload.p, wire_bytes, wbytes, hipMemcpyHostToDevice, c->stream));
   if ((rc = upload(c, c->d_off, off, (n + 1) * 4))) return rc;
   c->staged_n = (uint32_t)n;
   c->staged_pre = true;
-  c->wire_n = (uint32_t)n;
-  c->wire_valid = true;
-  c->wire_stat_valid = false;
+  c->wire.rows = (uint32_t)n;
+  c->wire.columns = true;
+  c->wire.parsed = false;
   c->ev_used = 0;
-  if (n) {
-    hipLaunchKernelGGL(ibftk::wire_parse_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
-                       (const uint8_t *)c->d_payload.p, (const uint32_t *)c->d_off.p, (uint32_t)n,
-                       (wire::row_info *)c->d_wire_rows.p, (uint8_t *)c->d_hash.p, (uint8_t *)c->d_sig.p,
-                       (uint8_t *)c->d_signer.p, (uint8_t *)c->d_seal.p, (uint8_t *)c->d_pre.p);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = enqueue_wire_recode(c, (uint32_t)n))) return rc;
-  }
+  if (n && (rc = enqueue_wire_parse(c, (uint32_t)n))) return rc;
   // the digest column now holds keccak256(PayloadNoSig): the sender check is the seal-style pass (mode 0)
   if ((rc = enqueue_recover(c, c->stream, (uint32_t)n, true, ibftk::MODE_SEALS, true))) return rc;
   if ((rc = enqueue_tally(c, (uint32_t)n))) return rc;
   if (out_rows && n)
     HIPCHK(c, hipMemcpyAsync(out_rows, c->d_wire_rows.p, n * sizeof(ibft_wire_row_t), hipMemcpyDeviceToHost, c->stream));
   if ((rc = fetch_results(c, (uint32_t)n, out_mask, tally, true))) return rc;
-  c->wire_stat_n = (uint32_t)n;
-  c->wire_stat_valid = true;
+  c->wire.parsed = true;
   return IBFT_OK;
 }
 
@@ -4083,48 +4175,29 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
                               uint8_t *out_class, ibft_wire_row_t *out_rows, const uint8_t *proposer20, ibft_tally_t *tally) {
   if (!c || (n && (!off || !out_sender_mask || !out_valid_mask))) return IBFT_E_INVAL;
   if ((raw_len && !raw) || raw_len > (1ull << 31)) return IBFT_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return IBFT_E_INVAL;
-  if (n && off[n] && !wire_bytes) return IBFT_E_INVAL;
+  if (!offsets_ok(off, n) || !bytes_ok(off, n, wire_bytes)) return IBFT_E_INVAL;
   ctx_lock lk(c);
   if (n > c->max_rows) return IBFT_E_TOOBIG;
   if (!c->have_valset) return IBFT_E_NOVALSET;
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  c->wire_valid = false;
-  c->wire_stat_valid = false;
+  c->wire.columns = false;
+  c->wire.parsed = false;
   c->staged_n = 0;
   const uint32_t half = ((uint32_t)n + 63u) & ~63u;
   if ((rc = alloc_rows(c, 2 * (((uint32_t)c->max_rows + 63u) & ~63u)))) return rc;
-  bool hash_needed = false;
-  if (digest32) {
-    if ((rc = wait_proposal_hash(c))) return rc;  // a hash still on its way must not land on top of the caller's digest
-    c->have_H = false;
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the staging buffer is free again
-    memcpy(c->h_digest, digest32, 32);
-    HIPCHK(c, hipMemcpyAsync(c->d_H.p, c->h_digest, 32, hipMemcpyHostToDevice, c->stream));
-  } else {
-    hash_needed = note_proposal(c, raw, raw_len, proposal_round);
-  }
+  set_tail t;
+  if ((rc = set_proposal_begin(c, digest32, raw, raw_len, proposal_round, &t.hash_needed))) return rc;
   if (n == 0) {
-    if (hash_needed && (rc = launch_proposal_hash(c))) return rc;
-    if (proposer20) {  // HasPrepareQuorum of no messages: the proposer alone
+    if (t.hash_needed && (rc = launch_proposal_hash(c))) return rc;
+    if (proposer20) {  // HasPrepareQuorum of no messages, the proposer alone: this call notes him and enqueues the tally itself
       note_proposer(c, proposer20);
       if ((rc = enqueue_tally(c, 0))) return rc;
-      return fetch_results(c, 0, nullptr, tally, true);
     }
-    if (tally) {
-      memset(tally, 0, sizeof *tally);
-      tally->quorum_lo = c->quorum_w[0];
-      tally->quorum_hi = c->quorum_w[1];
-    }
-    for (int i = 0; i < ibftk::TALLY_SUM_WORDS; i++) c->last_wide[i] = 0;
-    return IBFT_OK;
+    return answer_empty_set(c, proposer20, tally);
   }
   const size_t wbytes = off[n];
-  if ((rc = ensure(c, c->d_payload, wbytes + 256))) return rc;
-  if ((rc = ensure(c, c->d_wire_rows, (size_t)c->max_rows * sizeof(wire::row_info)))) return rc;
-  if ((rc = ensure(c, c->d_seal, (size_t)c->max_rows * 65 + 64))) return rc;
+  if ((rc = ensure_wire_buffers(c, wbytes))) return rc;
   if ((rc = ensure(c, c->d_noseal, c->max_rows))) return rc;
   ColumnCopies cc;
   cc.add(c->d_payload.p, wire_bytes, wbytes);
@@ -4132,11 +4205,7 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
   if ((rc = cc.flush(c))) return rc;
   uint8_t *d_hash = (uint8_t *)c->d_hash.p, *d_sig = (uint8_t *)c->d_sig.p, *d_signer = (uint8_t *)c->d_signer.p,
           *d_pre = (uint8_t *)c->d_pre.p;
-  hipLaunchKernelGGL(ibftk::wire_parse_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream,
-                     (const uint8_t *)c->d_payload.p, (const uint32_t *)c->d_off.p, (uint32_t)n,
-                     (wire::row_info *)c->d_wire_rows.p, d_hash, d_sig, d_signer, (uint8_t *)c->d_seal.p, d_pre);
-  HIPCHK(c, hipGetLastError());
-  if ((rc = enqueue_wire_recode(c, (uint32_t)n))) return rc;
+  if ((rc = enqueue_wire_parse(c, (uint32_t)n))) return rc;
   hipLaunchKernelGGL(ibftk::wire_set_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
                      (const wire::row_info *)c->d_wire_rows.p, (const uint8_t *)c->d_seal.p, (uint32_t)n, half, height, round,
                      d_hash, (uint8_t *)c->d_hash_len.p, d_sig, d_signer, d_pre, (uint8_t *)c->d_noseal.p,
@@ -4146,47 +4215,27 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
     HIPCHK(c, hipMemsetAsync(d_sig + 65ull * n, 0, 65ull * (half - n), c->stream));
     HIPCHK(c, hipMemsetAsync(d_pre + n, 1, half - n, c->stream));
   }
-  const bool converted = c->seal_digest_mode != 0;
-  if (converted && (rc = apply_seal_digest(c, (uint8_t *)c->d_hash.p + 32ull * half, (uint32_t)n, true))) return rc;
+  t.converted = c->seal_digest_mode != 0;
+  if (t.converted && (rc = apply_seal_digest(c, d_hash + 32ull * half, (uint32_t)n, true))) return rc;
   c->ev_used = 0;
   const bool time_it = c->time_every && (c->pass_counter++ % c->time_every) == 0;
   // with the pre column: wavefronts whose rows are all dead (the seal rows of PREPAREs, other views, odd encodings) exit at once
-  if ((rc = enqueue_recover(c, c->stream, half + (uint32_t)n, true, ibftk::MODE_SEALS, time_it))) return rc;
-  ibftk::set_args sa{};
-  sa.hash32 = converted ? (const uint8_t *)c->d_hash_copy.p : d_hash + 32ull * half;
-  sa.hash_len = (const uint8_t *)c->d_hash_len.p;
-  sa.H4 = (const uint64_t *)c->d_H.p;
-  sa.sender_pre = d_pre;  // not canonical here, or From / Signature of a length no signature check can pass
-  sa.valid_pre = d_pre + half;
-  sa.no_seal = (const uint8_t *)c->d_noseal.p;
-  sa.n = (uint32_t)n;
-  sa.half_words = half / 64;
-  const size_t mw = (size_t)mask_words(n);
-  sa.sender_out = (uint64_t *)c->d_set.p;
-  sa.valid_out = (uint64_t *)c->d_set.p + mask_words(c->max_rows);
-  sa.host_sender = c->dh_set;
-  sa.host_valid = c->dh_set ? c->dh_set + mask_words(c->max_rows) : nullptr;
-  // the verdict launch above did not need the proposal's hash, the combine step does: hashed on the side stream meanwhile
-  if (hash_needed && (rc = launch_proposal_hash(c))) return rc;
-  if ((rc = wait_proposal_hash(c))) return rc;
-  note_proposer(c, proposer20);
-  if ((rc = enqueue_tally(c, (uint32_t)n, &sa))) return rc;
-  c->mask_dirty_words = 0;
-  if (!c->dh_set)
-    HIPCHK(c, hipMemcpyAsync(c->h_set, c->d_set.p, (size_t)mask_words(c->max_rows) * 16, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = enqueue_recover(c, c->stream, half + (uint32_t)n, /*with_pre=*/true, ibftk::MODE_SEALS, time_it))) return rc;
+  t.sender_pre = d_pre;  // not canonical here, or From / Signature of a length no signature check can pass
+  t.valid_pre = d_pre + half;
+  t.no_seal = (const uint8_t *)c->d_noseal.p;
+  t.half_words = half / 64;
+  t.note_proposer = true;
+  t.proposer20 = proposer20;
+  if ((rc = enqueue_set_tally(c, n, half, t))) return rc;
   if (out_class && !c->dh_class)
     HIPCHK(c, hipMemcpyAsync(c->h_class, c->d_class.p, n, hipMemcpyDeviceToHost, c->stream));
   if (out_rows)  // 80 B per row through a copy command: ask for it only when the fields are needed (out_class routes)
     HIPCHK(c, hipMemcpyAsync(out_rows, c->d_wire_rows.p, n * sizeof(ibft_wire_row_t), hipMemcpyDeviceToHost, c->stream));
-  if ((rc = fetch_results(c, (uint32_t)n, nullptr, tally, true))) {
-    c->have_H = false;
-    return rc;
-  }
-  memcpy(out_sender_mask, c->h_set, mw * 8);
-  memcpy(out_valid_mask, c->h_set + mask_words(c->max_rows), mw * 8);
+  if ((rc = fetch_set_masks(c, n, out_sender_mask, out_valid_mask, tally))) return rc;
   if (out_class) memcpy(out_class, c->h_class, n);
-  c->wire_stat_n = (uint32_t)n;
-  c->wire_stat_valid = true;
+  c->wire.rows = (uint32_t)n;
+  c->wire.parsed = true;
   return IBFT_OK;
 }
 
@@ -4196,11 +4245,367 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
 //
 // judge (ibft_judge_certificates_wire): the same path, then one record per carrier — validPC and the RoundChangeCertificate rules
 // (cert_verdict_dev.h) over the rows where they lie (kernels.hip.h: cert_judge_kernel); every per-row output is optional then.
-static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap,
-                                  size_t *out_n_rows, ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows,
-                                  uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
-                                  uint64_t *out_self_mask, bool judge, size_t certs_cap, size_t *out_n_certs,
-                                  ibft_cert_verdict_t *out_cert) {
+//
+// The call runs as stages over one cert_call (what the caller gave) and one cert_plan (what the stages found out), in this
+// order: cert_check, cert_reserve, cert_expand, cert_digests, cert_verdicts, cert_compare_and_judge, cert_deliver.
+struct cert_call {
+  const uint8_t *wire_bytes;
+  const uint32_t *off;
+  size_t n, rows_cap, certs_cap;  // certs_cap: judge only
+  bool judge;
+  size_t *out_n_rows, *out_n_certs;  // out_n_certs, out_cert: judge only
+  ibft_cert_verdict_t *out_cert;
+  ibft_cert_node_t *out_nodes;  // every per-row output may be null (out_sender_mask: with judge only)
+  ibft_wire_row_t *out_rows;
+  uint8_t *out_class;
+  uint64_t *out_sender_mask, *out_hash_mask, *out_self_mask;
+};
+struct cert_plan {
+  size_t cap = 0;                                      // rows the tree may have: min(rows_cap, max_rows)
+  std::vector<std::pair<uint32_t, uint32_t>> levels;   // rows [first, second) of each level
+  uint32_t rows = 0, carriers = 0, records = 0;        // of the whole tree; carriers: the deferred rows (slot list)
+  bool two = false;                                    // the deferred rows get a verdict launch of their own …
+  uint32_t region = 0;                                 // … as rows [region, region + carriers) of the columns
+  uint32_t dense_base = 0;                             // the dedup's dense batch begins here
+  uint8_t *d_digest = nullptr, *d_sig = nullptr, *d_from = nullptr, *d_pre = nullptr;  // the shared columns
+  void read_columns(const ibft_ctx *c) {  // again after every alloc_rows: the columns may have moved
+    d_digest = (uint8_t *)c->d_hash.p, d_sig = (uint8_t *)c->d_sig.p, d_from = (uint8_t *)c->d_signer.p, d_pre = (uint8_t *)c->d_pre.p;
+  }
+};
+constexpr int CERT_NOTHING_TO_DO = 1;  // cert_check: a batch without rows is answered already
+
+// What can be refused.  locked = false: the arguments, before the context's lock is taken (c may be null); the counts are
+// zeroed once the arguments stand.  locked = true: against the context — size, validator set, the empty batch, the records' room.
+static int cert_check(const ibft_ctx *c, const cert_call &k, cert_plan &p, bool locked) {
+  if (!locked) {
+    if (!c || !k.out_n_rows || (k.n && (!k.off || (!k.judge && !k.out_sender_mask)))) return IBFT_E_INVAL;
+    if (k.judge && (!k.out_n_certs || (k.n && !k.out_cert))) return IBFT_E_INVAL;
+    if (!offsets_ok(k.off, k.n) || !bytes_ok(k.off, k.n, k.wire_bytes)) return IBFT_E_INVAL;
+    *k.out_n_rows = 0;
+    if (k.judge) *k.out_n_certs = 0;
+    return IBFT_OK;
+  }
+  p.cap = std::min<size_t>(k.rows_cap, c->max_rows);
+  if (k.n > p.cap) return IBFT_E_TOOBIG;
+  if (!c->have_valset) return IBFT_E_NOVALSET;
+  if (k.n == 0) return CERT_NOTHING_TO_DO;
+  if (k.judge && k.n > k.certs_cap) return IBFT_E_TOOBIG;
+  return IBFT_OK;
+}
+
+// every buffer, the pinned counter block and the two events the call may need, and the rows of the columns
+static int cert_reserve(ibft_ctx *c, const cert_call &k, cert_plan &p) {
+  CertState &s = c->cert;
+  int rc;
+  const size_t wbytes = k.off[k.n], m = c->max_rows;
+  if ((rc = ensure(c, c->d_payload, wbytes + 256))) return rc;
+  if ((rc = ensure(c, c->d_wire_rows, m * sizeof(wire::row_info)))) return rc;
+  c->wire.parsed = false;  // the tree's rows take the place of the last flat call's
+  if ((rc = ensure(c, s.nodes, m * sizeof(wire::node_info)))) return rc;
+  if ((rc = ensure(c, s.span, m * 8))) return rc;
+  if ((rc = ensure(c, s.count, m * 4))) return rc;
+  if ((rc = ensure(c, s.slot, m * 4))) return rc;
+  if ((rc = ensure(c, s.prop, m * 32))) return rc;
+  if ((rc = ensure(c, s.masks, (size_t)mask_words(m) * 16))) return rc;
+  const bool fresh_total = !s.total.p;
+  if ((rc = ensure(c, s.total, sizeof(cert_counters)))) return rc;
+  if (fresh_total) HIPCHK(c, hipMemset(s.total.p, 0, sizeof(cert_counters)));  // (count_acc: zero between launches)
+  if ((rc = ensure(c, s.tiles, (m / 1024 + 2) * 8))) return rc;
+  const uint32_t dd_slots = s.dedup ? cdd::table_slots((uint32_t)m, s.dedup_slots_cap) : 0u;
+  if (s.dedup && (rc = ensure(c, s.dd_table, (size_t)dd_slots * 4))) return rc;
+  if (s.dedup && (rc = ensure(c, s.dd_slot, m * 4))) return rc;
+  if (s.dedup && (rc = ensure(c, s.dd_pos, m * 4))) return rc;
+  if (k.judge && (rc = ensure(c, s.rec, m * sizeof(certv::record)))) return rc;
+  if (k.judge && (rc = ensure(c, s.recbase, (m + 1) * 4))) return rc;
+  if (!s.h_total) {
+    if (hipHostMalloc((void **)&s.h_total, sizeof(cert_counters)) != hipSuccess) return IBFT_E_NOMEM;
+    void *d = nullptr;
+    if (!getenv("IBFT_NO_HOST_DIRECT") && hipHostGetDevicePointer(&d, s.h_total, 0) == hipSuccess) s.dh_total = (cert_counters *)d;
+  }
+  if (!s.ev_fork) {
+    HIPCHK(c, hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&s.ev_join, hipEventDisableTiming));
+  }
+  // the columns hold the tree's rows and, with two verdict launches, the batch of the deferred rows behind them (64-aligned);
+  // with the dedup, the dense batch of the representatives behind both
+  const uint32_t rows_al = ((uint32_t)c->max_rows + 63u) & ~63u;
+  if ((s.overlap || s.dedup) && (rc = alloc_rows(c, (s.dedup ? 3u : 2u) * rows_al))) return rc;
+  p.read_columns(c);
+  return IBFT_OK;
+}
+
+// The bytes and level 0 go up; then level by level: parse, count the children, scan (the host reads the next level's size),
+// list them.  With judge, the records are counted while level 1 is listed.  → p.levels, p.rows, p.carriers, p.records
+static int cert_expand(ibft_ctx *c, const cert_call &k, cert_plan &p) {
+  CertState &s = c->cert;
+  const size_t n = k.n, wbytes = k.off[n];
+  const uint8_t *d_wire = (const uint8_t *)c->d_payload.p;
+  wire::node_info *d_nodes = (wire::node_info *)s.nodes.p;
+  wire::row_info *d_rows = (wire::row_info *)c->d_wire_rows.p;
+  uint2 *d_span = (uint2 *)s.span.p;
+  uint32_t *d_count = (uint32_t *)s.count.p, *d_slot = (uint32_t *)s.slot.p;
+  cert_counters *d_total = (cert_counters *)s.total.p;
+  const volatile cert_counters *h_total = s.h_total;
+  if (wbytes) HIPCHK(c, hipMemcpyAsync(c->d_payload.p, k.wire_bytes, wbytes, hipMemcpyHostToDevice, c->stream));
+  std::vector<wire::node_info> level0(n);
+  for (size_t i = 0; i < n; i++) {
+    wire::node_info nd{};
+    nd.off = k.off[i];
+    nd.len = k.off[i + 1] - k.off[i];
+    nd.parent = wire::NO_PARENT;
+    nd.ordinal = (uint32_t)i;
+    nd.role = wire::ROLE_ROOT;
+    level0[i] = nd;
+  }
+  HIPCHK(c, hipMemcpyAsync(d_nodes, level0.data(), n * sizeof(wire::node_info), hipMemcpyHostToDevice, c->stream));
+  uint32_t lo = 0, hi = (uint32_t)n, carriers = 0;
+  for (uint32_t level = 0;; level++) {
+    const uint32_t cnt = hi - lo;
+    hipLaunchKernelGGL(ibftk::cert_parse_kernel, dim3((cnt + 63) / 64), dim3(64), 0, c->stream, d_wire, d_nodes, lo, hi, d_rows, d_span,
+                       p.d_digest, p.d_sig, p.d_from, p.d_pre);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(ibftk::cert_walk_kernel<false>, dim3(cnt), dim3(64), 0, c->stream, d_wire, d_nodes, d_rows, (const uint2 *)d_span, lo, hi,
+                       d_count);
+    HIPCHK(c, hipGetLastError());
+    ibftk::cert_scan_launch(c->stream, cnt <= ibftk::CERT_SCAN_ONE_GROUP_MAX, (const uint32_t *)d_count, d_nodes, lo, cnt, hi, carriers, d_slot,
+                            (uint2 *)s.tiles.p, &d_total->next_rows, s.dh_total ? &s.dh_total->next_rows : nullptr);
+    HIPCHK(c, hipGetLastError());
+    // next_rows and carriers; behind level 1 of a judge call also the records its listing counted
+    const size_t scan_bytes = k.judge && level == 1 ? offsetof(cert_counters, pad0) : offsetof(cert_counters, records);
+    if (!s.dh_total) HIPCHK(c, hipMemcpyAsync(s.h_total, d_total, scan_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    p.levels.push_back({lo, hi});
+    const uint32_t total = h_total->next_rows;
+    carriers += h_total->carriers;
+    if (total == 0) break;
+    if ((uint64_t)hi + total > p.cap || level == 254) return IBFT_E_TOOBIG;
+    hipLaunchKernelGGL(ibftk::cert_walk_kernel<true>, dim3(cnt), dim3(64), 0, c->stream, d_wire, d_nodes, d_rows, (const uint2 *)d_span, lo, hi,
+                       d_count);
+    HIPCHK(c, hipGetLastError());
+    lo = hi;
+    hi += total;
+    // level 1 is listed: which of its rows get a record (the kernel is handed the block and writes its word 2, `records`; the next
+    // level's synchronisation delivers it)
+    if (k.judge && level == 0) {
+      hipLaunchKernelGGL(ibftk::cert_record_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const wire::node_info *)d_nodes, (uint32_t)n, hi,
+                         (uint32_t *)s.recbase.p, &d_total->next_rows, s.dh_total ? &s.dh_total->next_rows : nullptr);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
+  p.rows = hi;
+  p.carriers = carriers;
+  // records: every level-0 row, every level-1 row of a RoundChangeCertificate
+  p.records = k.judge ? (p.levels.size() > 1 ? h_total->records : (uint32_t)n) : 0u;
+  if (k.judge && (p.records < n || p.records > p.rows)) {
+    c->last_error = "certificate records: a count outside [n, rows]";
+    return IBFT_E_HIP;
+  }
+  if (k.judge && p.records > k.certs_cap) return IBFT_E_TOOBIG;
+  return IBFT_OK;
+}
+
+// What the parents know goes down the levels; then the rows' digests: the proposal digests cleared, the deferred digests a
+// wavefront each, the rest by cert_finish_kernel — on the side stream when the deferred rows get a verdict launch of their own
+// (→ p.two, p.region), which the carrier stage then fills; the join event is left for cert_verdicts to wait on.
+static int cert_digests(ibft_ctx *c, const cert_call &, cert_plan &p) {
+  CertState &s = c->cert;
+  int rc;
+  const uint8_t *d_wire = (const uint8_t *)c->d_payload.p;
+  wire::node_info *d_nodes = (wire::node_info *)s.nodes.p;
+  wire::row_info *d_rows = (wire::row_info *)c->d_wire_rows.p;
+  const uint32_t *d_slot = (const uint32_t *)s.slot.p;
+  uint8_t *d_prop = (uint8_t *)s.prop.p;
+  const uint32_t rows = p.rows, carriers = p.carriers;
+  for (size_t l = p.levels.size(); l-- > 1;) {
+    const uint32_t cnt = p.levels[l].second - p.levels[l].first;
+    hipLaunchKernelGGL(ibftk::cert_propagate_kernel, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, (const wire::node_info *)d_nodes, d_rows,
+                       p.levels[l].first, p.levels[l].second);
+    HIPCHK(c, hipGetLastError());
+  }
+  // The deferred digests (messages that carry certificates, long messages) — a wavefront per message, a sequential sponge each — run
+  // on the side stream NEXT TO the verdict launch over all the other rows; the deferred rows then get a small verdict launch of their
+  // own as rows [region, region + carriers) of the columns.  That pays when the verdict launch is in its throughput regime (many
+  // wavefronts per SIMD: ≥ 4 096 rows, or the known-key kernels): N = 1 024 cold 20.7 → 17.8 ms, warm 12.3 → 10.1; N = 256 warm
+  // 2.04 → 1.89.  A small cold launch is one wavefront per SIMD whose duration is its slowest wavefront, and a wavefront that shares
+  // its SIMD with a digest wavefront runs at ≈55 % speed (N = 64 cold 1.08 → 1.12 ms): one stream, one verdict launch there.
+  // IBFT_CERT_OVERLAP=0: never.
+  p.two = s.overlap && carriers != 0 && (rows >= 4096u || (c->cache_on && c->my_built > 0));
+  p.region = p.two ? ((rows + 63u) & ~63u) : 0u;
+  hipStream_t ds = p.two ? c->hstream : c->stream;
+  if (p.two) {
+    if ((rc = alloc_rows(c, 2 * (((uint32_t)c->max_rows + 63u) & ~63u)))) return rc;
+    p.read_columns(c);
+    HIPCHK(c, hipEventRecord(s.ev_fork, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(ds, s.ev_fork, 0));
+  }
+  HIPCHK(c, hipMemsetAsync(d_prop, 0, (size_t)rows * 32, ds));  // rows without a Proposal: a zero digest (cert_finish_kernel skips them)
+  if (carriers) {
+    hipLaunchKernelGGL(ibftk::cert_digest_wave_kernel, dim3(2 * carriers), dim3(64), 0, ds, d_wire, (const wire::node_info *)d_nodes,
+                       (const wire::row_info *)d_rows, d_slot, p.region, p.d_digest, d_prop);
+    HIPCHK(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(ibftk::cert_finish_kernel, dim3((rows + 63) / 64), dim3(64), 0, ds, d_wire, d_nodes, (const wire::row_info *)d_rows, rows,
+                     p.d_digest, d_prop, p.d_pre, p.two ? 1u : 0u);
+  HIPCHK(c, hipGetLastError());
+  if (p.two) {
+    hipLaunchKernelGGL(ibftk::cert_carrier_stage_kernel, dim3((carriers + 255) / 256), dim3(256), 0, ds, (const wire::node_info *)d_nodes,
+                       (const wire::row_info *)d_rows, d_slot, carriers, p.region, p.d_sig, p.d_from, p.d_pre);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(s.ev_join, ds));
+  }
+  return IBFT_OK;
+}
+
+// The verdict launch over all rows of all levels: the digest column holds keccak256(PayloadNoSig) — the seal-style pass; rows that
+// are not judged here (and, with two launches, the deferred rows) are pre-flagged.  Plain, or through the dedup; then the deferred
+// batch's launch and scatter; then the count of what was judged (ibft_cert_stats).
+static int cert_verdicts(ibft_ctx *c, const cert_call &, cert_plan &p) {
+  CertState &s = c->cert;
+  int rc;
+  cert_counters *d_total = (cert_counters *)s.total.p;
+  const volatile cert_counters *h_total = s.h_total;
+  const uint32_t rows = p.rows, carriers = p.carriers, region = p.region;
+  c->ev_used = 0;
+  if (!s.dedup) {
+    if ((rc = enqueue_recover(c, c->stream, rows, true, ibftk::MODE_SEALS, false))) return rc;
+  } else {
+    // The same verdicts from one launch over the distinct (digest, signature, From) of the rows without a pre-flag
+    // (cert_dedup_dev.h): table, representatives, their dense batch behind the tree's rows and the deferred batch, its
+    // verdict launch (the AUTO rule and learn_key see the dense batch), every row its representative's bit.
+    const uint32_t slots = cdd::table_slots(rows, s.dedup_slots_cap);
+    p.dense_base = p.two ? ((region + carriers + 63u) & ~63u) : ((rows + 63u) & ~63u);
+    uint32_t *d_table = (uint32_t *)s.dd_table.p, *d_dd_slot = (uint32_t *)s.dd_slot.p, *d_dd_pos = (uint32_t *)s.dd_pos.p;
+    const cdd::columns cols{p.d_digest, p.d_sig, p.d_from, p.d_pre};
+    // with kernel timing on, two event pairs: table + compaction, scatter (the verdict launch between them is not timed on this
+    // path) — ibft_last_kernel_ms after a flag-on ibft_verify_certificates_wire is the time of the dedup's own kernels
+    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
+    if (c->time_every && ((rc = next_events(c, &t0, &t1)) || (rc = next_events(c, &t2, &t3)))) return rc;
+    if (t0) HIPCHK(c, hipEventRecord(t0, c->stream));
+    HIPCHK(c, ibftk::cert_dedup_front_launch(c->stream, cols, rows, slots, p.dense_base, d_table, d_dd_slot, (uint32_t *)s.count.p, (uint2 *)s.tiles.p,
+                                             d_dd_pos, &d_total->dense, s.dh_total ? &s.dh_total->dense : nullptr));
+    HIPCHK(c, hipGetLastError());
+    if (t1) HIPCHK(c, hipEventRecord(t1, c->stream));
+    if (!s.dh_total)  // dense, unplaced
+      HIPCHK(c, hipMemcpyAsync(&s.h_total->dense, &d_total->dense, offsetof(cert_counters, judged_tree) - offsetof(cert_counters, dense),
+                               hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t dense = h_total->dense;
+    if (dense > rows) {
+      c->last_error = "certificate dedup: more representatives than rows";
+      return IBFT_E_HIP;
+    }
+    uint64_t *d_dense_mask = (uint64_t *)c->d_mask.p + p.dense_base / 64;
+    // the dense batch's verdict words: zero whatever an earlier call left there; the tree's own words are stored whole below
+    if (dense) HIPCHK(c, hipMemsetAsync(d_dense_mask, 0, (size_t)mask_words(dense) * 8, c->stream));
+    if ((rc = enqueue_recover(c, c->stream, dense, true, ibftk::MODE_SEALS, false, p.dense_base, true))) return rc;
+    if (t2) HIPCHK(c, hipEventRecord(t2, c->stream));
+    ibftk::cert_dedup_scatter_launch(c->stream, (const uint32_t *)d_table, (const uint32_t *)d_dd_slot, (const uint32_t *)d_dd_pos,
+                                     (const uint64_t *)d_dense_mask, rows, (uint64_t *)c->d_mask.p);
+    HIPCHK(c, hipGetLastError());
+    if (t3) HIPCHK(c, hipEventRecord(t3, c->stream));
+    c->mask_dirty_words = std::max(c->mask_dirty_words, (uint32_t)mask_words(rows));
+  }
+  if (p.two) {
+    HIPCHK(c, hipStreamWaitEvent(c->stream, s.ev_join, 0));
+    // the deferred rows' verdict words: zero whatever an earlier call left there (the first launch only vouches for its own words)
+    HIPCHK(c, hipMemsetAsync((uint64_t *)c->d_mask.p + region / 64, 0, (size_t)mask_words(carriers) * 8, c->stream));
+    if ((rc = enqueue_recover(c, c->stream, carriers, true, ibftk::MODE_SEALS, false, region, true))) return rc;
+    hipLaunchKernelGGL(ibftk::cert_scatter_kernel, dim3((carriers + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)s.slot.p, carriers, region,
+                       (uint64_t *)c->d_mask.p);
+    HIPCHK(c, hipGetLastError());
+  }
+  // ibft_cert_stats: how many rows the verdict launches judged (no pre-flag), the tree's rows and the deferred batch apart
+  ibftk::cert_dedup_count_launch(c->stream, (const uint8_t *)p.d_pre, rows, (const uint8_t *)p.d_pre + region, p.two ? carriers : 0u, d_total->count_acc,
+                                 &d_total->judged_tree, s.dh_total ? &s.dh_total->judged_tree : nullptr);
+  HIPCHK(c, hipGetLastError());
+  if (!s.dh_total)  // judged_tree, judged_deferred
+    HIPCHK(c, hipMemcpyAsync(&s.h_total->judged_tree, &d_total->judged_tree, offsetof(cert_counters, count_acc) - offsetof(cert_counters, judged_tree),
+                             hipMemcpyDeviceToHost, c->stream));
+  return IBFT_OK;
+}
+
+// every row's hash / self words and class byte; with judge, one record per carrier over them and their way home
+static int cert_compare_and_judge(ibft_ctx *c, const cert_call &k, cert_plan &p) {
+  CertState &s = c->cert;
+  int rc;
+  const size_t n = k.n;
+  wire::node_info *d_nodes = (wire::node_info *)s.nodes.p;
+  wire::row_info *d_rows = (wire::row_info *)c->d_wire_rows.p;
+  uint64_t *d_hash_mask = (uint64_t *)s.masks.p, *d_self_mask = d_hash_mask + mask_words(c->max_rows);
+  hipLaunchKernelGGL(ibftk::cert_compare_kernel, dim3((p.rows + 255) / 256), dim3(256), 0, c->stream, (const wire::node_info *)d_nodes,
+                     (const wire::row_info *)d_rows, (const uint8_t *)s.prop.p, p.rows, d_hash_mask, d_self_mask, (uint8_t *)c->d_class.p);
+  HIPCHK(c, hipGetLastError());
+  if (!k.judge) return IBFT_OK;
+  ibftk::cert_judge_args ja{};
+  ja.nodes = d_nodes;
+  ja.rows = d_rows;
+  ja.cls = (const uint8_t *)c->d_class.p;
+  ja.sender_mask = (const uint64_t *)c->d_mask.p;
+  ja.hash_mask = d_hash_mask;
+  ja.self_mask = d_self_mask;
+  ja.vtab = (const uint32_t *)c->d_vtab.p;
+  ja.vpower32 = (const uint32_t *)c->d_vpower.p;
+  ja.quorum = (const uint64_t *)c->d_quorum.p;
+  ja.rec_base = p.levels.size() > 1 ? (const uint32_t *)s.recbase.p : nullptr;
+  ja.vslot_mask = c->vslot_mask;
+  ja.n_validators = c->n_validators;
+  ja.n_roots = (uint32_t)n;
+  ja.n_rows = p.rows;
+  ja.n_records = p.records;
+  const size_t lds = (size_t)((c->n_validators + 31) / 32) * 4;
+  ja.lds_bitmap = lds <= ibftk::CERT_JUDGE_LDS_MAX ? 1u : 0u;  // beyond: one workgroup walks every record over the HBM bitmap
+  ja.seen = (uint32_t *)c->d_seen.p;
+  ja.out = (certv::record *)s.rec.p;
+  const dim3 grid(ja.lds_bitmap ? std::min(p.records, ibftk::CERT_JUDGE_MAX_GRID) : 1u);
+  const size_t dyn = ja.lds_bitmap ? lds : 0;
+  // (the verdict launches of this path are not timed: with kernel timing on, ibft_last_kernel_ms after this call is the two
+  // record kernels' time)
+  hipEvent_t j0 = nullptr, j1 = nullptr;
+  if (c->time_every) {
+    if ((rc = next_events(c, &j0, &j1))) return rc;
+    HIPCHK(c, hipEventRecord(j0, c->stream));
+  }
+  if (c->power_words == 1)
+    hipLaunchKernelGGL(ibftk::cert_judge_kernel<1>, grid, dim3(64), dyn, c->stream, ja);
+  else
+    hipLaunchKernelGGL(ibftk::cert_judge_kernel<4>, grid, dim3(64), dyn, c->stream, ja);
+  HIPCHK(c, hipGetLastError());
+  if (ja.rec_base) {
+    hipLaunchKernelGGL(ibftk::cert_judge_children_kernel, dim3(std::min((uint32_t)n, ibftk::CERT_JUDGE_MAX_GRID)), dim3(64), 0, c->stream, ja.out,
+                       (uint32_t)n);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (j1) HIPCHK(c, hipEventRecord(j1, c->stream));
+  HIPCHK(c, hipMemcpyAsync(k.out_cert, ja.out, (size_t)p.records * sizeof(certv::record), hipMemcpyDeviceToHost, c->stream));
+  return IBFT_OK;
+}
+
+// the per-row outputs that were asked for, the sender words (fetch_results waits for the stream), the counts, the stats
+static int cert_deliver(ibft_ctx *c, const cert_call &k, cert_plan &p) {
+  CertState &s = c->cert;
+  int rc;
+  const uint32_t rows = p.rows;
+  const uint64_t *d_hash_mask = (const uint64_t *)s.masks.p, *d_self_mask = d_hash_mask + mask_words(c->max_rows);
+  const size_t mw = (size_t)mask_words(rows);
+  if (k.out_nodes) HIPCHK(c, hipMemcpyAsync(k.out_nodes, s.nodes.p, (size_t)rows * sizeof(wire::node_info), hipMemcpyDeviceToHost, c->stream));
+  if (k.out_rows) HIPCHK(c, hipMemcpyAsync(k.out_rows, c->d_wire_rows.p, (size_t)rows * sizeof(wire::row_info), hipMemcpyDeviceToHost, c->stream));
+  if (k.out_class) HIPCHK(c, hipMemcpyAsync(k.out_class, c->d_class.p, rows, hipMemcpyDeviceToHost, c->stream));
+  if (k.out_hash_mask) HIPCHK(c, hipMemcpyAsync(k.out_hash_mask, d_hash_mask, mw * 8, hipMemcpyDeviceToHost, c->stream));
+  if (k.out_self_mask) HIPCHK(c, hipMemcpyAsync(k.out_self_mask, d_self_mask, mw * 8, hipMemcpyDeviceToHost, c->stream));
+  // no tally: the rows of a tree belong to many certificates; their quorum rules are the caller's (From / type / view columns)
+  if ((rc = fetch_results(c, rows, k.out_sender_mask, nullptr, false))) return rc;
+  *k.out_n_rows = rows;
+  if (k.judge) *k.out_n_certs = p.records;
+  const volatile cert_counters *h = s.h_total;
+  const uint32_t judged = h->judged_tree + h->judged_deferred;
+  s.stat[0] = rows;
+  s.stat[1] = judged;
+  s.stat[2] = s.dedup ? h->dense + h->judged_deferred : judged;
+  s.stat[3] = s.dedup ? h->unplaced : 0u;
+  return IBFT_OK;
+}
+
+static int certificates_wire_impl(ibft_ctx *c, const cert_call &k) {
   static_assert(sizeof(ibft_cert_node_t) == sizeof(wire::node_info), "ABI");
   static_assert(IBFT_CERT_DIGEST_MAX_BYTES == wire::TREE_DIGEST_MAX_BYTES, "ABI");
   static_assert(sizeof(ibft_cert_verdict_t) == sizeof(certv::record) && sizeof(ibft_cert_verdict_t) == 128, "ABI");
@@ -4212,302 +4617,55 @@ static int certificates_wire_impl(ibft_ctx *c, const uint8_t *wire_bytes, const 
                     IBFT_CERT_BIT_SELF == certv::BIT_SELF && IBFT_CERT_BIT_HAS_PROPOSAL == certv::BIT_HAS_PROPOSAL &&
                     IBFT_CERT_BIT_HAS_CERTIFICATE == certv::BIT_HAS_CERTIFICATE,
                 "ABI");
-  if (!c || !out_n_rows || (n && (!off || (!judge && !out_sender_mask)))) return IBFT_E_INVAL;
-  if (judge && (!out_n_certs || (n && !out_cert))) return IBFT_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return IBFT_E_INVAL;
-  if (n && off[n] && !wire_bytes) return IBFT_E_INVAL;
-  *out_n_rows = 0;
-  if (judge) *out_n_certs = 0;
-  ctx_lock lk(c);
-  const size_t cap = std::min<size_t>(rows_cap, c->max_rows);
-  if (n > cap) return IBFT_E_TOOBIG;
-  if (!c->have_valset) return IBFT_E_NOVALSET;
-  if (n == 0) return IBFT_OK;
-  if (judge && n > certs_cap) return IBFT_E_TOOBIG;
-  HIPCHK(c, hipSetDevice(c->device));
+  cert_plan p;
   int rc;
-  c->wire_valid = false;
+  if ((rc = cert_check(c, k, p, /*locked=*/false))) return rc;
+  ctx_lock lk(c);
+  if ((rc = cert_check(c, k, p, /*locked=*/true))) return rc == CERT_NOTHING_TO_DO ? IBFT_OK : rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->wire.columns = false;
   c->staged_n = 0;
-  const size_t wbytes = off[n], m = c->max_rows;
-  if ((rc = ensure(c, c->d_payload, wbytes + 256))) return rc;
-  if ((rc = ensure(c, c->d_wire_rows, m * sizeof(wire::row_info)))) return rc;
-  c->wire_stat_valid = false;  // the tree's rows take the place of the last flat call's
-  if ((rc = ensure(c, c->d_cert_nodes, m * sizeof(wire::node_info)))) return rc;
-  if ((rc = ensure(c, c->d_cert_span, m * 8))) return rc;
-  if ((rc = ensure(c, c->d_cert_count, m * 4))) return rc;
-  if ((rc = ensure(c, c->d_cert_slot, m * 4))) return rc;
-  if ((rc = ensure(c, c->d_cert_prop, m * 32))) return rc;
-  if ((rc = ensure(c, c->d_cert_masks, (size_t)mask_words(m) * 16))) return rc;
-  const bool fresh_total = !c->d_cert_total.p;
-  if ((rc = ensure(c, c->d_cert_total, 64))) return rc;
-  if (fresh_total) HIPCHK(c, hipMemset(c->d_cert_total.p, 0, 64));  // (words 8..10: cert_dedup_count_kernel's sums, zero between launches)
-  if ((rc = ensure(c, c->d_cert_tiles, (m / 1024 + 2) * 8))) return rc;
-  const bool dedup = c->cert_dedup;
-  const uint32_t dd_slots = dedup ? cdd::table_slots((uint32_t)m, c->cert_dedup_slots_cap) : 0u;
-  if (dedup && (rc = ensure(c, c->d_cert_dd_table, (size_t)dd_slots * 4))) return rc;
-  if (dedup && (rc = ensure(c, c->d_cert_dd_slot, m * 4))) return rc;
-  if (dedup && (rc = ensure(c, c->d_cert_dd_pos, m * 4))) return rc;
-  if (judge && (rc = ensure(c, c->d_cert_rec, m * sizeof(certv::record)))) return rc;
-  if (judge && (rc = ensure(c, c->d_cert_recbase, (m + 1) * 4))) return rc;
-  if (!c->h_cert_total) {
-    if (hipHostMalloc((void **)&c->h_cert_total, 64) != hipSuccess) return IBFT_E_NOMEM;
-    void *d = nullptr;
-    if (!getenv("IBFT_NO_HOST_DIRECT") && hipHostGetDevicePointer(&d, c->h_cert_total, 0) == hipSuccess) c->dh_cert_total = (uint32_t *)d;
-  }
-  if (!c->ev_cert_fork) {
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_cert_fork, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_cert_join, hipEventDisableTiming));
-  }
-  // the columns hold the tree's rows and, with two verdict launches, the batch of the deferred rows behind them (64-aligned);
-  // with the dedup, the dense batch of the representatives behind both
-  const uint32_t rows_al = ((uint32_t)c->max_rows + 63u) & ~63u;
-  if ((c->cert_overlap || dedup) && (rc = alloc_rows(c, (dedup ? 3u : 2u) * rows_al))) return rc;
-  const uint8_t *d_wire = (const uint8_t *)c->d_payload.p;
-  wire::node_info *d_nodes = (wire::node_info *)c->d_cert_nodes.p;
-  wire::row_info *d_rows = (wire::row_info *)c->d_wire_rows.p;
-  uint2 *d_span = (uint2 *)c->d_cert_span.p;
-  uint32_t *d_count = (uint32_t *)c->d_cert_count.p, *d_total = (uint32_t *)c->d_cert_total.p, *d_slot = (uint32_t *)c->d_cert_slot.p;
-  uint8_t *d_digest = (uint8_t *)c->d_hash.p, *d_sig = (uint8_t *)c->d_sig.p, *d_from = (uint8_t *)c->d_signer.p,
-          *d_pre = (uint8_t *)c->d_pre.p, *d_prop = (uint8_t *)c->d_cert_prop.p;
-  if (wbytes) HIPCHK(c, hipMemcpyAsync(c->d_payload.p, wire_bytes, wbytes, hipMemcpyHostToDevice, c->stream));
-  std::vector<wire::node_info> level0(n);
-  for (size_t i = 0; i < n; i++) {
-    wire::node_info nd{};
-    nd.off = off[i];
-    nd.len = off[i + 1] - off[i];
-    nd.parent = wire::NO_PARENT;
-    nd.ordinal = (uint32_t)i;
-    nd.role = wire::ROLE_ROOT;
-    level0[i] = nd;
-  }
-  HIPCHK(c, hipMemcpyAsync(d_nodes, level0.data(), n * sizeof(wire::node_info), hipMemcpyHostToDevice, c->stream));
-  std::vector<std::pair<uint32_t, uint32_t>> levels;
-  uint32_t lo = 0, hi = (uint32_t)n, carriers = 0;
-  for (uint32_t level = 0;; level++) {
-    const uint32_t cnt = hi - lo;
-    hipLaunchKernelGGL(ibftk::cert_parse_kernel, dim3((cnt + 63) / 64), dim3(64), 0, c->stream, d_wire, d_nodes, lo, hi, d_rows, d_span,
-                       d_digest, d_sig, d_from, d_pre);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(ibftk::cert_walk_kernel<false>, dim3(cnt), dim3(64), 0, c->stream, d_wire, d_nodes, d_rows, (const uint2 *)d_span, lo, hi,
-                       d_count);
-    HIPCHK(c, hipGetLastError());
-    ibftk::cert_scan_launch(c->stream, cnt <= ibftk::CERT_SCAN_ONE_GROUP_MAX, (const uint32_t *)d_count, d_nodes, lo, cnt, hi, carriers, d_slot,
-                            (uint2 *)c->d_cert_tiles.p, d_total, c->dh_cert_total);
-    HIPCHK(c, hipGetLastError());
-    if (!c->dh_cert_total) HIPCHK(c, hipMemcpyAsync(c->h_cert_total, d_total, judge && level == 1 ? 12 : 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    levels.push_back({lo, hi});
-    const uint32_t total = ((volatile uint32_t *)c->h_cert_total)[0];
-    carriers += ((volatile uint32_t *)c->h_cert_total)[1];
-    if (total == 0) break;
-    if ((uint64_t)hi + total > cap || level == 254) return IBFT_E_TOOBIG;
-    hipLaunchKernelGGL(ibftk::cert_walk_kernel<true>, dim3(cnt), dim3(64), 0, c->stream, d_wire, d_nodes, d_rows, (const uint2 *)d_span, lo, hi,
-                       d_count);
-    HIPCHK(c, hipGetLastError());
-    lo = hi;
-    hi += total;
-    if (judge && level == 0) {  // level 1 is listed: which of its rows get a record (the next level's synchronisation delivers their number)
-      hipLaunchKernelGGL(ibftk::cert_record_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const wire::node_info *)d_nodes, (uint32_t)n, hi,
-                         (uint32_t *)c->d_cert_recbase.p, d_total, c->dh_cert_total);
-      HIPCHK(c, hipGetLastError());
-    }
-  }
-  const uint32_t rows = hi;
-  // records: every level-0 row, every level-1 row of a RoundChangeCertificate
-  const uint32_t records = judge ? (levels.size() > 1 ? ((volatile uint32_t *)c->h_cert_total)[2] : (uint32_t)n) : 0u;
-  if (judge && (records < n || records > rows)) {
-    c->last_error = "certificate records: a count outside [n, rows]";
-    return IBFT_E_HIP;
-  }
-  if (judge && records > certs_cap) return IBFT_E_TOOBIG;
-  for (size_t l = levels.size(); l-- > 1;) {
-    const uint32_t cnt = levels[l].second - levels[l].first;
-    hipLaunchKernelGGL(ibftk::cert_propagate_kernel, dim3((cnt + 255) / 256), dim3(256), 0, c->stream, (const wire::node_info *)d_nodes, d_rows,
-                       levels[l].first, levels[l].second);
-    HIPCHK(c, hipGetLastError());
-  }
-  // The deferred digests (messages that carry certificates, long messages) — a wavefront per message, a sequential sponge each — run
-  // on the side stream NEXT TO the verdict launch over all the other rows; the deferred rows then get a small verdict launch of their
-  // own as rows [region, region + carriers) of the columns.  That pays when the verdict launch is in its throughput regime (many
-  // wavefronts per SIMD: ≥ 4 096 rows, or the known-key kernels): N = 1 024 cold 20.7 → 17.8 ms, warm 12.3 → 10.1; N = 256 warm
-  // 2.04 → 1.89.  A small cold launch is one wavefront per SIMD whose duration is its slowest wavefront, and a wavefront that shares
-  // its SIMD with a digest wavefront runs at ≈55 % speed (N = 64 cold 1.08 → 1.12 ms): one stream, one verdict launch there.
-  // IBFT_CERT_OVERLAP=0: never.
-  const bool two = c->cert_overlap && carriers != 0 && (rows >= 4096u || (c->cache_on && c->my_built > 0));
-  const uint32_t region = two ? ((rows + 63u) & ~63u) : 0u;
-  hipStream_t ds = two ? c->hstream : c->stream;
-  if (two) {
-    if ((rc = alloc_rows(c, 2 * (((uint32_t)c->max_rows + 63u) & ~63u)))) return rc;
-    d_digest = (uint8_t *)c->d_hash.p, d_sig = (uint8_t *)c->d_sig.p, d_from = (uint8_t *)c->d_signer.p, d_pre = (uint8_t *)c->d_pre.p;
-    HIPCHK(c, hipEventRecord(c->ev_cert_fork, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(ds, c->ev_cert_fork, 0));
-  }
-  HIPCHK(c, hipMemsetAsync(d_prop, 0, (size_t)rows * 32, ds));  // rows without a Proposal: a zero digest (cert_finish_kernel skips them)
-  if (carriers) {
-    hipLaunchKernelGGL(ibftk::cert_digest_wave_kernel, dim3(2 * carriers), dim3(64), 0, ds, d_wire, (const wire::node_info *)d_nodes,
-                       (const wire::row_info *)d_rows, (const uint32_t *)d_slot, region, d_digest, d_prop);
-    HIPCHK(c, hipGetLastError());
-  }
-  hipLaunchKernelGGL(ibftk::cert_finish_kernel, dim3((rows + 63) / 64), dim3(64), 0, ds, d_wire, d_nodes, (const wire::row_info *)d_rows, rows,
-                     d_digest, d_prop, d_pre, two ? 1u : 0u);
-  HIPCHK(c, hipGetLastError());
-  if (two) {
-    hipLaunchKernelGGL(ibftk::cert_carrier_stage_kernel, dim3((carriers + 255) / 256), dim3(256), 0, ds, (const wire::node_info *)d_nodes,
-                       (const wire::row_info *)d_rows, (const uint32_t *)d_slot, carriers, region, d_sig, d_from, d_pre);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_cert_join, ds));
-  }
-  c->ev_used = 0;
-  // the verdict launch over all rows of all levels: the digest column holds keccak256(PayloadNoSig) — the seal-style pass; rows that
-  // are not judged here (and, with two launches, the deferred rows) are pre-flagged
-  uint32_t *d_stat = d_total + 4, *dh_stat = c->dh_cert_total ? c->dh_cert_total + 4 : nullptr;  // dense rows, unplaced rows, judged rows (tree, deferred batch)
-  volatile uint32_t *h_stat = (volatile uint32_t *)c->h_cert_total + 4;
-  if (!dedup) {
-    if ((rc = enqueue_recover(c, c->stream, rows, true, ibftk::MODE_SEALS, false))) return rc;
-  } else {
-    // The same verdicts from one launch over the distinct (digest, signature, From) of the rows without a pre-flag
-    // (cert_dedup_dev.h): table, representatives, their dense batch behind the tree's rows and the deferred batch, its
-    // verdict launch (the AUTO rule and learn_key see the dense batch), every row its representative's bit.
-    const uint32_t slots = cdd::table_slots(rows, c->cert_dedup_slots_cap);
-    const uint32_t dense_base = two ? ((region + carriers + 63u) & ~63u) : ((rows + 63u) & ~63u);
-    uint32_t *d_table = (uint32_t *)c->d_cert_dd_table.p, *d_dd_slot = (uint32_t *)c->d_cert_dd_slot.p, *d_dd_pos = (uint32_t *)c->d_cert_dd_pos.p;
-    const cdd::columns cols{d_digest, d_sig, d_from, d_pre};
-    // with kernel timing on, two event pairs: table + compaction, scatter (the verdict launch between them is not timed on this
-    // path) — ibft_last_kernel_ms after a flag-on ibft_verify_certificates_wire is the time of the dedup's own kernels
-    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
-    if (c->time_every && ((rc = next_events(c, &t0, &t1)) || (rc = next_events(c, &t2, &t3)))) return rc;
-    if (t0) HIPCHK(c, hipEventRecord(t0, c->stream));
-    HIPCHK(c, ibftk::cert_dedup_front_launch(c->stream, cols, rows, slots, dense_base, d_table, d_dd_slot, d_count, (uint2 *)c->d_cert_tiles.p, d_dd_pos,
-                                             d_stat, dh_stat));
-    HIPCHK(c, hipGetLastError());
-    if (t1) HIPCHK(c, hipEventRecord(t1, c->stream));
-    if (!dh_stat) HIPCHK(c, hipMemcpyAsync(c->h_cert_total + 4, d_stat, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint32_t dense = h_stat[0];
-    if (dense > rows) {
-      c->last_error = "certificate dedup: more representatives than rows";
-      return IBFT_E_HIP;
-    }
-    uint64_t *d_dense_mask = (uint64_t *)c->d_mask.p + dense_base / 64;
-    // the dense batch's verdict words: zero whatever an earlier call left there; the tree's own words are stored whole below
-    if (dense) HIPCHK(c, hipMemsetAsync(d_dense_mask, 0, (size_t)mask_words(dense) * 8, c->stream));
-    if ((rc = enqueue_recover(c, c->stream, dense, true, ibftk::MODE_SEALS, false, dense_base, true))) return rc;
-    if (t2) HIPCHK(c, hipEventRecord(t2, c->stream));
-    ibftk::cert_dedup_scatter_launch(c->stream, (const uint32_t *)d_table, (const uint32_t *)d_dd_slot, (const uint32_t *)d_dd_pos,
-                                     (const uint64_t *)d_dense_mask, rows, (uint64_t *)c->d_mask.p);
-    HIPCHK(c, hipGetLastError());
-    if (t3) HIPCHK(c, hipEventRecord(t3, c->stream));
-    c->mask_dirty_words = std::max(c->mask_dirty_words, (uint32_t)mask_words(rows));
-  }
-  if (two) {
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_cert_join, 0));
-    // the deferred rows' verdict words: zero whatever an earlier call left there (the first launch only vouches for its own words)
-    HIPCHK(c, hipMemsetAsync((uint64_t *)c->d_mask.p + region / 64, 0, (size_t)mask_words(carriers) * 8, c->stream));
-    if ((rc = enqueue_recover(c, c->stream, carriers, true, ibftk::MODE_SEALS, false, region, true))) return rc;
-    hipLaunchKernelGGL(ibftk::cert_scatter_kernel, dim3((carriers + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)d_slot, carriers, region,
-                       (uint64_t *)c->d_mask.p);
-    HIPCHK(c, hipGetLastError());
-  }
-  // ibft_cert_stats: how many rows the verdict launches judged (no pre-flag), the tree's rows and the deferred batch apart
-  ibftk::cert_dedup_count_launch(c->stream, (const uint8_t *)d_pre, rows, (const uint8_t *)d_pre + region, two ? carriers : 0u, d_total + 8, d_stat + 2,
-                                 dh_stat ? dh_stat + 2 : nullptr);
-  HIPCHK(c, hipGetLastError());
-  if (!dh_stat) HIPCHK(c, hipMemcpyAsync(c->h_cert_total + 6, d_stat + 2, 8, hipMemcpyDeviceToHost, c->stream));
-  uint64_t *d_hash_mask = (uint64_t *)c->d_cert_masks.p, *d_self_mask = d_hash_mask + mask_words(m);
-  hipLaunchKernelGGL(ibftk::cert_compare_kernel, dim3((rows + 255) / 256), dim3(256), 0, c->stream, (const wire::node_info *)d_nodes,
-                     (const wire::row_info *)d_rows, (const uint8_t *)d_prop, rows, d_hash_mask, d_self_mask, (uint8_t *)c->d_class.p);
-  HIPCHK(c, hipGetLastError());
-  if (judge) {
-    ibftk::cert_judge_args ja{};
-    ja.nodes = d_nodes;
-    ja.rows = d_rows;
-    ja.cls = (const uint8_t *)c->d_class.p;
-    ja.sender_mask = (const uint64_t *)c->d_mask.p;
-    ja.hash_mask = d_hash_mask;
-    ja.self_mask = d_self_mask;
-    ja.vtab = (const uint32_t *)c->d_vtab.p;
-    ja.vpower32 = (const uint32_t *)c->d_vpower.p;
-    ja.quorum = (const uint64_t *)c->d_quorum.p;
-    ja.rec_base = levels.size() > 1 ? (const uint32_t *)c->d_cert_recbase.p : nullptr;
-    ja.vslot_mask = c->vslot_mask;
-    ja.n_validators = c->n_validators;
-    ja.n_roots = (uint32_t)n;
-    ja.n_rows = rows;
-    ja.n_records = records;
-    const size_t lds = (size_t)((c->n_validators + 31) / 32) * 4;
-    ja.lds_bitmap = lds <= ibftk::CERT_JUDGE_LDS_MAX ? 1u : 0u;  // beyond: one workgroup walks every record over the HBM bitmap
-    ja.seen = (uint32_t *)c->d_seen.p;
-    ja.out = (certv::record *)c->d_cert_rec.p;
-    const dim3 grid(ja.lds_bitmap ? std::min(records, ibftk::CERT_JUDGE_MAX_GRID) : 1u);
-    const size_t dyn = ja.lds_bitmap ? lds : 0;
-    // (the verdict launches of this path are not timed: with kernel timing on, ibft_last_kernel_ms after this call is the two
-    // record kernels' time)
-    hipEvent_t j0 = nullptr, j1 = nullptr;
-    if (c->time_every) {
-      if ((rc = next_events(c, &j0, &j1))) return rc;
-      HIPCHK(c, hipEventRecord(j0, c->stream));
-    }
-    if (c->power_words == 1)
-      hipLaunchKernelGGL(ibftk::cert_judge_kernel<1>, grid, dim3(64), dyn, c->stream, ja);
-    else
-      hipLaunchKernelGGL(ibftk::cert_judge_kernel<4>, grid, dim3(64), dyn, c->stream, ja);
-    HIPCHK(c, hipGetLastError());
-    if (ja.rec_base) {
-      hipLaunchKernelGGL(ibftk::cert_judge_children_kernel, dim3(std::min((uint32_t)n, ibftk::CERT_JUDGE_MAX_GRID)), dim3(64), 0, c->stream, ja.out,
-                         (uint32_t)n);
-      HIPCHK(c, hipGetLastError());
-    }
-    if (j1) HIPCHK(c, hipEventRecord(j1, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out_cert, ja.out, (size_t)records * sizeof(certv::record), hipMemcpyDeviceToHost, c->stream));
-  }
-  const size_t mw = (size_t)mask_words(rows);
-  if (out_nodes) HIPCHK(c, hipMemcpyAsync(out_nodes, d_nodes, (size_t)rows * sizeof(wire::node_info), hipMemcpyDeviceToHost, c->stream));
-  if (out_rows) HIPCHK(c, hipMemcpyAsync(out_rows, d_rows, (size_t)rows * sizeof(wire::row_info), hipMemcpyDeviceToHost, c->stream));
-  if (out_class) HIPCHK(c, hipMemcpyAsync(out_class, c->d_class.p, rows, hipMemcpyDeviceToHost, c->stream));
-  if (out_hash_mask) HIPCHK(c, hipMemcpyAsync(out_hash_mask, d_hash_mask, mw * 8, hipMemcpyDeviceToHost, c->stream));
-  if (out_self_mask) HIPCHK(c, hipMemcpyAsync(out_self_mask, d_self_mask, mw * 8, hipMemcpyDeviceToHost, c->stream));
-  // no tally: the rows of a tree belong to many certificates; their quorum rules are the caller's (From / type / view columns)
-  if ((rc = fetch_results(c, rows, out_sender_mask, nullptr, false))) return rc;
-  *out_n_rows = rows;
-  if (judge) *out_n_certs = records;
-  const uint32_t judged = h_stat[2] + h_stat[3];
-  c->cert_stat[0] = rows;
-  c->cert_stat[1] = judged;
-  c->cert_stat[2] = dedup ? h_stat[0] + h_stat[3] : judged;
-  c->cert_stat[3] = dedup ? h_stat[1] : 0u;
+  for (auto stage : {cert_reserve, cert_expand, cert_digests, cert_verdicts, cert_compare_and_judge, cert_deliver})
+    if ((rc = stage(c, k, p))) return rc;
   return IBFT_OK;
 }
 int ibft_cert_stats(ibft_ctx *c, uint32_t *rows, uint32_t *judged_rows, uint32_t *verdict_rows, uint32_t *unplaced_rows) {
   if (!c) return IBFT_E_INVAL;
   ctx_lock lk(c);
-  if (rows) *rows = c->cert_stat[0];
-  if (judged_rows) *judged_rows = c->cert_stat[1];
-  if (verdict_rows) *verdict_rows = c->cert_stat[2];
-  if (unplaced_rows) *unplaced_rows = c->cert_stat[3];
+  if (rows) *rows = c->cert.stat[0];
+  if (judged_rows) *judged_rows = c->cert.stat[1];
+  if (verdict_rows) *verdict_rows = c->cert.stat[2];
+  if (unplaced_rows) *unplaced_rows = c->cert.stat[3];
   return IBFT_OK;
 }
 int ibft_verify_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap,
                                   size_t *out_n_rows, ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows,
                                   uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
                                   uint64_t *out_self_mask) {
-  return certificates_wire_impl(c, wire_bytes, off, n, rows_cap, out_n_rows, out_nodes, out_rows, out_class, out_sender_mask, out_hash_mask,
-                                out_self_mask, false, 0, nullptr, nullptr);
+  cert_call k{};
+  k.wire_bytes = wire_bytes, k.off = off, k.n = n, k.rows_cap = rows_cap;
+  k.out_n_rows = out_n_rows, k.out_nodes = out_nodes, k.out_rows = out_rows, k.out_class = out_class;
+  k.out_sender_mask = out_sender_mask, k.out_hash_mask = out_hash_mask, k.out_self_mask = out_self_mask;
+  return certificates_wire_impl(c, k);
 }
 int ibft_judge_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap, size_t certs_cap,
                                  size_t *out_n_rows, size_t *out_n_certs, ibft_cert_verdict_t *out_cert, ibft_cert_node_t *out_nodes,
                                  ibft_wire_row_t *out_rows, uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
                                  uint64_t *out_self_mask) {
-  return certificates_wire_impl(c, wire_bytes, off, n, rows_cap, out_n_rows, out_nodes, out_rows, out_class, out_sender_mask, out_hash_mask,
-                                out_self_mask, true, certs_cap, out_n_certs, out_cert);
+  cert_call k{};
+  k.wire_bytes = wire_bytes, k.off = off, k.n = n, k.rows_cap = rows_cap;
+  k.judge = true, k.certs_cap = certs_cap, k.out_n_certs = out_n_certs, k.out_cert = out_cert;
+  k.out_n_rows = out_n_rows, k.out_nodes = out_nodes, k.out_rows = out_rows, k.out_class = out_class;
+  k.out_sender_mask = out_sender_mask, k.out_hash_mask = out_hash_mask, k.out_self_mask = out_self_mask;
+  return certificates_wire_impl(c, k);
 }
 
 int ibft_wire_stage_seals(ibft_ctx *c) {
   if (!c) return IBFT_E_INVAL;
   ctx_lock lk(c);
-  if (!c->wire_valid) return IBFT_E_INVAL;  // no parsed batch resident (another call restaged the columns)
+  if (!c->wire.columns) return IBFT_E_INVAL;  // no parsed batch resident (another call restaged the columns)
   HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t n = c->wire_n;
+  const uint32_t n = c->wire.rows;
   if (n) {
     hipLaunchKernelGGL(ibftk::wire_stage_seals_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream,
                        (const wire::row_info *)c->d_wire_rows.p, (const uint8_t *)c->d_seal.p, n,
@@ -4539,7 +4697,7 @@ static int tally_impl(ibft_ctx *c, const uint8_t *sender20, const uint64_t *mask
   HIPCHK(c, hipSetDevice(c->device));
   // resolve sender -> validator index with a small lookup pass over the table in HBM
   int rc;
-  c->wire_valid = false;
+  c->wire.columns = false;
   if ((rc = upload(c, c->d_signer, sender20, n * 20))) return rc;
   c->mask_dirty_words = std::max(c->mask_dirty_words, (uint32_t)mask_words(n));
   if ((rc = upload(c, c->d_mask, mask, (size_t)mask_words(n) * 8))) return rc;
@@ -4731,7 +4889,7 @@ int ibft_set_seal_digest(ibft_ctx *c, uint32_t mode, const uint8_t *suffix, size
   c->seal_digest_mode = mode;
   memcpy(c->seal_suffix_words, block, sizeof block);
   c->staged_n = 0;  // a resident batch was staged under the previous convention
-  c->wire_valid = false;
+  c->wire.columns = false;
   return IBFT_OK;
 }
 int ibft_group_set_seal_digest(ibft_group *g, uint32_t mode, const uint8_t *suffix, size_t suffix_len) {
@@ -4818,8 +4976,7 @@ int ibft_group_verify_senders(ibft_group *g, const uint8_t *payload, const uint3
                               const uint8_t *from20, const uint8_t *pre_flags, size_t n, uint64_t *out_mask,
                               ibft_tally_t *tally) {
   if (!g || (n && (!off || !sig65 || !from20 || !out_mask))) return IBFT_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return IBFT_E_INVAL;
+  if (!offsets_ok(off, n)) return IBFT_E_INVAL;
   std::lock_guard<std::mutex> lk(g->mu);
   const uint32_t world = (uint32_t)g->ctx.size();
   std::vector<std::unique_lock<std::mutex>> locks;
@@ -4847,8 +5004,7 @@ int ibft_group_verify_messages(ibft_group *g, const uint8_t *payload, const uint
                                uint64_t *out_sender_mask, uint64_t *out_valid_mask, ibft_tally_t *tally) {
   if (!g || (n && (!off || !msg_sig65 || !from20 || !hash32 || !hash_len || !out_sender_mask || !out_valid_mask)))
     return IBFT_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return IBFT_E_INVAL;
+  if (!offsets_ok(off, n)) return IBFT_E_INVAL;
   std::lock_guard<std::mutex> lk(g->mu);
   const uint32_t world = (uint32_t)g->ctx.size();
   std::vector<std::unique_lock<std::mutex>> locks;
@@ -4887,8 +5043,7 @@ int ibft_group_verify_certificates_wire(ibft_group *g, const uint8_t *wire_bytes
                                         uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
                                         uint64_t *out_self_mask) {
   if (!g || !out_n_rows || (n && (!off || !out_sender_mask))) return IBFT_E_INVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return IBFT_E_INVAL;
+  if (!offsets_ok(off, n)) return IBFT_E_INVAL;
   *out_n_rows = 0;
   if (n == 0) return IBFT_OK;
   std::lock_guard<std::mutex> lk(g->mu);
