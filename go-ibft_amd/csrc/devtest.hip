@@ -387,7 +387,9 @@ extern "C" int devtest_rows_repeat_ms(int n, const uint8_t *dig, const uint8_t *
 // ---- the rows pair (recover_pubkey_row<…, PAIR> + recover_helper_row): where each wavefront's time goes ----
 // The product kernel's shape (four main wavefronts, their helpers w + 4, one workgroup per compute unit); the pair's barriers
 // go through a SYNC that stamps s_memrealtime (100 MHz) on each side.  Per wavefront, 8 u64 in `stamps`: [0] start,
-// [1] [2] barrier 1 reached / left, [3] [4] barrier 2 reached / left, [5] end.  Stamps go to this buffer only.
+// [1] [2] barrier 1 reached / left, [3] [4] barrier 2 reached / left (a MAIN wavefront's; a helper never stands there and
+// leaves both 0), [5] end — of a helper: behind publish_and_leave, the moment it stops being resident.  Stamps go to this
+// buffer only.
 // STOP = 6 ends the main wavefronts behind the closing chain (no address hash; addresses are then junk): "after barrier 2" of
 // that launch is the closing chain alone, and the difference to the complete launch is the hash and the compare.
 struct stamp_sync {
@@ -404,6 +406,8 @@ struct stamp_sync {
       *cnt = i + 1;
     }
   }
+  __device__ void wait() const { (*this)(); }
+  __device__ void publish_and_leave() const { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); }  // (the kernel stamps the end)
 };
 template <int STOP>
 __global__ void __launch_bounds__(512) devtest_rows_pair_kernel(const uint32_t *gtab, const uint8_t *dig, const uint8_t *sig65,
@@ -450,6 +454,7 @@ extern "C" int devtest_rows_pair_stamps_stop(int stop, int n, const uint8_t *dig
   uint8_t *dd = dev_copy(dig, (size_t)32 * n), *ds = dev_copy(sig65, (size_t)65 * n), *dout;
   uint64_t *dst;
   if (!dd || !ds || hipMalloc(&dout, (size_t)24 * n) != hipSuccess || hipMalloc(&dst, st_words * 8) != hipSuccess) return -1;
+  if (hipMemset(dst, 0, st_words * 8) != hipSuccess) return -1;  // (the slots a wavefront never writes read 0)
   devtest_gtab_kernel<<<(ibftk::GTAB_WINDOWS * ibftk::GTAB_ENTRIES + 63) / 64, 64>>>(dg);
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -474,6 +479,74 @@ extern "C" int devtest_rows_pair_stamps_stop(int stop, int n, const uint8_t *dig
 extern "C" int devtest_rows_pair_stamps(int n, const uint8_t *dig, const uint8_t *sig65, uint8_t *out24, uint64_t *stamps8,
                                         float *ms) {
   return devtest_rows_pair_stamps_stop(99, n, dig, sig65, out24, stamps8, ms);
+}
+
+// ---- the hand-over that ends a rows pair, alone (SYNC::publish_and_leave / wait over rows_pair_shared) ----
+// ONE workgroup of the pair kernel's shape.  The main wavefronts poison their `sh`, all eight pass barrier 1; then a helper
+// idles for helper_delay rounds, stores a pattern (a function of salt, slot, field and lane: nothing a former launch left in
+// LDS passes for it) where the product's helper stores u1·G, publishes and ENDS, while a main wavefront idles for main_delay
+// rounds, waits, and copies what it finds in `sh` to `out` (slot-major, fields gx gy gz ginf, 64 lanes each).  A round is one
+// s_sleep of ≈ 1 000 clocks: both loops are bounded by their argument.  Stamps as above, and [3] of a HELPER: its delay is
+// over, the pattern not yet stored.  helper_delay = 0 and a long main_delay: the helpers have ended long before the first main
+// wavefront stands at barrier 2; the other way round the main wavefronts stand there first and are held until the last helper
+// has ended.  Either way the s_barrier counts only the wavefronts that have not ended (kernels.hip.h: rows_pair_handover).
+__device__ __forceinline__ uint32_t handover_word(uint32_t salt, uint32_t slot, uint32_t field, uint32_t lane) {
+  return salt * 0x9E3779B1u ^ (slot << 16 | field << 8 | lane);
+}
+__device__ __forceinline__ void handover_delay(uint32_t rounds) {
+#pragma unroll 1
+  for (uint32_t i = 0; i < rounds; i++) __builtin_amdgcn_s_sleep(16);
+}
+__global__ void __launch_bounds__(512) devtest_handover_kernel(uint32_t helper_delay, uint32_t main_delay, uint32_t salt,
+                                                             uint32_t *out, uint64_t *stamps) {
+  __shared__ wv::rows_pair_shared sh[4];
+  __shared__ uint32_t cnt[8];
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u, slot = w & 3u;
+  uint64_t *st = stamps + (size_t)w * 8;
+  if (lane == 0) {
+    cnt[w] = 0;
+    st[0] = __builtin_amdgcn_s_memrealtime();
+  }
+  const stamp_sync sync{st, &cnt[w]};
+  wv::rows_pair_shared *mine = &sh[slot];
+  if (w < 4) mine->gx[lane] = mine->gy[lane] = mine->gz[lane] = mine->ginf[lane] = 0xDEADDEADu;
+  sync();  // barrier 1: all eight
+  if (w >= 4) {
+    handover_delay(helper_delay);
+    if (lane == 0) st[3] = __builtin_amdgcn_s_memrealtime();
+    mine->gx[lane] = handover_word(salt, slot, 0, lane);
+    mine->gy[lane] = handover_word(salt, slot, 1, lane);
+    mine->gz[lane] = handover_word(salt, slot, 2, lane);
+    mine->ginf[lane] = handover_word(salt, slot, 3, lane);
+    sync.publish_and_leave();
+    if (lane == 0) st[5] = __builtin_amdgcn_s_memrealtime();
+    return;
+  }
+  handover_delay(main_delay);
+  sync.wait();  // barrier 2: the main wavefronts alone
+  uint32_t *o = out + (size_t)slot * 256 + lane;
+  o[0] = mine->gx[lane];
+  o[64] = mine->gy[lane];
+  o[128] = mine->gz[lane];
+  o[192] = mine->ginf[lane];
+  if (lane == 0) st[5] = __builtin_amdgcn_s_memrealtime();
+}
+// out1024: 4 slots × 4 fields × 64 lanes; stamps64: 8 wavefronts × 8 u64 (main wavefronts 0 … 3, helpers 4 … 7)
+extern "C" int devtest_handover(uint32_t helper_delay, uint32_t main_delay, uint32_t salt, uint32_t *out1024, uint64_t *stamps64) {
+  constexpr uint32_t MAX_ROUNDS = 4096;  // (≈ 2 ms)
+  if (helper_delay > MAX_ROUNDS || main_delay > MAX_ROUNDS || !out1024 || !stamps64) return -3;
+  uint32_t *dout;
+  uint64_t *dst;
+  if (hipMalloc(&dout, 1024 * 4) != hipSuccess || hipMalloc(&dst, 64 * 8) != hipSuccess) return -1;
+  if (hipMemset(dout, 0, 1024 * 4) != hipSuccess || hipMemset(dst, 0, 64 * 8) != hipSuccess) return -1;
+  devtest_handover_kernel<<<1, 512>>>(helper_delay, main_delay, salt, dout, dst);
+  int rc = hipDeviceSynchronize() == hipSuccess ? 0 : -2;
+  if (rc == 0) {
+    (void)hipMemcpy(out1024, dout, 1024 * 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(stamps64, dst, 64 * 8, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dout); (void)hipFree(dst);
+  return rc;
 }
 
 // ---- the RFC 6979 DRBG of sign_dev.h: one lane per row, the first m candidates of each (a reseed between two) ----

@@ -390,6 +390,14 @@ struct ibft_ctx {
   // this many rows — where the plain form runs at most one wavefront per SIMD; IBFT_ROWS_PAIR=0|1 pins either form
   uint32_t rows_pair_max = 4096;
   int rows_pair_force = -1;
+  // ... whose helper wavefronts END once they have published u1·G (kernels.hip.h: rows_pair_handover) where the launch covers
+  // at least 5/8 of the device's compute units with a workgroup each: the next pipelined pass then finds room beside this
+  // one's main wavefronts two thirds of a pass sooner.  A smaller launch leaves the next pass idle compute units enough, and
+  // there a helper parked at barrier 2 keeps that pass off this one's SIMDs.  Measured, per step with the helpers gone
+  // (profiles/r27_helper_leave_ab.txt): 129 workgroups of 256 compute units + 0.9 %, 160 − 1.5 %, 188 − 0.8 %, 224 − 2.7 %,
+  // 256 − 5.9 %.  IBFT_PAIR_LEAVE=0|1 pins it.
+  uint32_t compute_units = 0;
+  int pair_leave_force = -1;
 
   // a1: the proposal whose Keccak the device holds in d_H (raw ‖ BE64(round)); the same proposal is checked
   // against every PREPARE and COMMIT set of a round and on every wake-up, so it is hashed once
@@ -737,9 +745,14 @@ void launch_cold(ibft_ctx *c, hipStream_t vs, const ibftk::recover_args &a, uint
       launch_verdict(vs, a, ibftk::ecrecover_wave_kernel<MODE>, n, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
     } else if (CG == 16) {
       const uint32_t waves = (n + 3) / 4;
-      if (rows_pair_for(c, n))
-        launch_verdict(vs, a, ibftk::ecrecover_rows_pair_kernel<MODE>, waves, ibftk::ROWS_PAIRS_PER_BLOCK, 128 * ibftk::ROWS_PAIRS_PER_BLOCK);
-      else
+      if (rows_pair_for(c, n)) {
+        const uint32_t blocks = (waves + ibftk::ROWS_PAIRS_PER_BLOCK - 1) / ibftk::ROWS_PAIRS_PER_BLOCK;
+        const bool leave = c->pair_leave_force >= 0 ? c->pair_leave_force != 0 : (uint64_t)blocks * 8 >= (uint64_t)c->compute_units * 5;
+        if (leave)
+          launch_verdict(vs, a, ibftk::ecrecover_rows_pair_kernel<MODE, false>, waves, ibftk::ROWS_PAIRS_PER_BLOCK, 128 * ibftk::ROWS_PAIRS_PER_BLOCK);
+        else
+          launch_verdict(vs, a, ibftk::ecrecover_rows_pair_kernel<MODE, true>, waves, ibftk::ROWS_PAIRS_PER_BLOCK, 128 * ibftk::ROWS_PAIRS_PER_BLOCK);
+      } else
         launch_verdict(vs, a, ibftk::ecrecover_rows_kernel<MODE>, waves, ibftk::WAVE_KERNEL_WAVES, 64 * ibftk::WAVE_KERNEL_WAVES);
     } else if (CG > 1) {
       // the lanes' window tables: LDS (no private segment) unless pinned otherwise (IBFT_COLD_TABLE=private: round 4's form, A/B)
@@ -1772,6 +1785,11 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   if (const char *e = getenv("IBFT_ROWS_PAIR")) {
     if (!strcmp(e, "0")) c->rows_pair_force = 0;
     else if (!strcmp(e, "1")) c->rows_pair_force = 1;
+  }
+  c->compute_units = (uint32_t)prop.multiProcessorCount;
+  if (const char *e = getenv("IBFT_PAIR_LEAVE")) {
+    if (!strcmp(e, "0")) c->pair_leave_force = 0;
+    else if (!strcmp(e, "1")) c->pair_leave_force = 1;
   }
   int rc = IBFT_OK;
   do {

@@ -1260,11 +1260,39 @@ __global__ void __launch_bounds__(64 * WAVE_KERNEL_WAVES) __attribute__((amdgpu_
 // A workgroup is four MAIN wavefronts (0…3: R′, tables, main loop, closing chain, Keccak) and their HELPERS (4…7, helper of
 // main w is w + 4: r⁻¹ mod n, u1, u2, the GLV split, then u1·G) for the same four rows each (wave_fe_dev.h: rows_pair_shared,
 // recover_pubkey_row<…, PAIR>, recover_helper_row).  Wavefronts w and w + 4 of a workgroup share a SIMD
-// (tools/simd_placement_probe.hip), so a helper issues in its main wavefront's stalls.  The two meet in LDS at two workgroup
-// barriers: every wavefront passes both, whatever its rows turn out to be — a pair with nothing to do only synchronises, and
-// main and helper decide that on the same rows.  More than 128 registers: a second workgroup never shares the compute unit.
+// (tools/simd_placement_probe.hip), so a helper issues in its main wavefront's stalls.  The two meet in LDS twice.
+// BARRIER 1 is a barrier of all eight wavefronts: every wavefront passes it, whatever its rows turn out to be, before any
+// wavefront of the workgroup ends.  BARRIER 2 is a hand-over (rows_pair_handover): a helper stores u1·G, waits for its own LDS
+// stores and ENDS; only the four main wavefronts execute the second s_barrier.  That rests on one documented property of the
+// hardware: s_barrier waits for the wavefronts of the workgroup that have NOT ENDED, so the barrier is satisfied once the four
+// main wavefronts stand at it and the four helpers are gone — the same whether a helper ended long before the mains arrived
+// (its stores were complete before its s_endpgm) or after (the mains are held until the last helper has ended).  `if (row >=
+// n) return;` in front of a later __syncthreads() relies on the same property.  A pair with nothing to do only synchronises —
+// main: barrier 1, barrier 2; helper: barrier 1, end — and main and helper decide that on the same rows.  n = 17: workgroup 0
+// is four working pairs; in workgroup 1 pair 0 works on row 16 (its other three rows repeat it, unreported) and pairs 1…3 are
+// idle.  At barrier 1 stand all eight: main 0 behind its tables, helper 0 behind the split, the six idle wavefronts at once.
+// The three idle helpers end there; helper 0 adds u1·G, publishes and ends.  At barrier 2 stand main 0 (behind its main loop)
+// and the idle mains (at once): it opens when helper 0 has ended, which is all main 0 needs, and the idle mains read nothing.
+// WHY the helper leaves: it holds 168 of a SIMD's 512 registers per lane.  Parked at barrier 2 it kept the next pipelined
+// pass's workgroup (2 × 168 more per SIMD) off the compute unit for most of this pass; gone, 168 + 336 fit.
+// WHERE it does not: a launch that covers only half of the device's compute units leaves idle ones enough to the next pass,
+// and there a parked helper is useful — it keeps that pass off this one's SIMDs (2 049 rows: + 0.9 % per step with the
+// helpers gone, profiles/r27_helper_leave_ab.txt).  The host picks the instantiation (launch_cold): with STAY the helpers stand at
+// barrier 2 as well, as they did before round 27, and the barrier is one of all eight again.
 constexpr int ROWS_PAIRS_PER_BLOCK = 4;
-template <int MODE>
+template <bool STAY>
+struct rows_pair_handover {
+  __device__ void operator()() const { __syncthreads(); }  // barrier 1
+  // the LDS stores of this wavefront are complete (s_waitcnt lgkmcnt(0)) before the caller's return ends the program
+  __device__ void publish_and_leave() const {
+    if constexpr (STAY)
+      __syncthreads();
+    else
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  }
+  __device__ void wait() const { __syncthreads(); }  // barrier 2: the main wavefronts (and the helpers that stay)
+};
+template <int MODE, bool STAY = false>
 __global__ void __launch_bounds__(128 * ROWS_PAIRS_PER_BLOCK) ecrecover_rows_pair_kernel(recover_args a) {
   __shared__ uint32_t row_tab[ROWS_PAIRS_PER_BLOCK][wv::ROW_TAB_SLOTS * 64];  // the main wavefronts' window tables
   __shared__ wv::rows_pair_shared sh[ROWS_PAIRS_PER_BLOCK];
@@ -1282,12 +1310,12 @@ __global__ void __launch_bounds__(128 * ROWS_PAIRS_PER_BLOCK) ecrecover_rows_pai
   const bool done = row_done(a, row);
   const bool need = live && !done;
   if (MODE != MODE_EMIT && report && need) a.vidx[row] = vi;
-  auto sync = [] { __syncthreads(); };
+  const rows_pair_handover<STAY> sync;
   // (wave-uniform, the same for both wavefronts of the pair: in MODE_EMIT from pre_flags and `live` alone)
   if (!__any(needs_curve<MODE>(need, pre, vi) ? 1 : 0)) {
     if (MODE == MODE_EMIT && report && need) emit_store_none(a, row);  // (every row left is a pre_flags row)
     sync();
-    sync();
+    if (!helper || STAY) sync.wait();  // (an idle helper has nothing to publish: unless it stays, it ends behind barrier 1)
     return;
   }
   u256 r, s;

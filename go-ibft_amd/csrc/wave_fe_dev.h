@@ -927,8 +927,14 @@ struct pair_shared {
   uint32_t ginf;                    // u₁·G is the point at infinity (u₁ = 0)
   uint32_t gx[16], gy[16], gz[16];  // u₁·G, Jacobian, limb i in slot i (slots 10…15 zero: the row layout's idle lanes)
 };
+// A pair's SYNC policy.  operator() is a barrier of the whole workgroup.  The rows pair (rows_pair_shared) ends with a HAND-OVER
+// in its place: the helper's last act is publish_and_leave() — everything it stored into `sh` is complete, and the wavefront
+// ends right behind it —, the main wavefront's wait() returns once every helper of the workgroup has done that.  no_sync is
+// the policy of code that runs helper, then main, in sequence (the host emulator): nothing to wait for on either side.
 struct no_sync {
   HD void operator()() const {}
+  HD void publish_and_leave() const {}
+  HD void wait() const {}
 };
 template <int STOP = 99, bool PAIR = false, class SYNC = no_sync>
 WVF bool recover_pubkey_wave(const uint32_t *__restrict__ gtab, const u256 &z_raw, const u256 &r, const u256 &s,
@@ -1336,6 +1342,9 @@ WVF row_scalars_out row_scalars(const u256 &z_raw, const u256 &r, const u256 &s,
 // the same four rows, on the same SIMD, meanwhile.  The hand-over holds exactly the values the single form computes
 // itself, by the same code (row_scalars, rows_fixed_base), so the verdicts are the same, rare rows included.  The split
 // is all the main wavefront waits for at barrier 1: row_scalars hands it over before u1 is finished.
+// Barrier 2 is a hand-over, not a meeting (SYNC: publish_and_leave / wait, at no_sync): the helper is done a third of the way
+// into the main wavefront's life, and a helper parked at a barrier keeps its registers — a third of the SIMD's file — from
+// the next pass's workgroup.  So it publishes u1·G and ENDS; only the main wavefronts stand at barrier 2.
 struct rows_pair_shared {
   uint32_t sc[4][9];                          // per row: |k1| (4 words), |k2| (4 words), signs (bit 0: k1 < 0, bit 1: k2 < 0)
   uint32_t gx[64], gy[64], gz[64], ginf[64];  // u1·G in the row layout, per lane
@@ -1496,7 +1505,7 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
   // the accumulator still lives on the isomorphic one (PAIR: the helper wavefront has summed them meanwhile)
   wjac accg;
   if constexpr (PAIR) {
-    sync();  // barrier 2: u1·G is in `sh`
+    sync.wait();  // barrier 2: every helper of the workgroup has published and left, u1·G is in `sh`
     accg.x = sh->gx[lane_];
     accg.y = sh->gy[lane_];
     accg.z = sh->gz[lane_];
@@ -1516,7 +1525,8 @@ WVF bool recover_pubkey_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
 
 // The HELPER wavefront of a rows pair (see rows_pair_shared): for the same four rows as its main wavefront, r⁻¹ mod n, u2
 // and the GLV split of u2 → `sh`, barrier 1 (inside row_scalars, ahead of u1's last steps); then u1·G (rows_fixed_base) →
-// `sh`, barrier 2.  Every wavefront that gets here passes both barriers, whatever its rows are.
+// `sh`, publish_and_leave: the caller returns from its kernel right behind this call, and the helper never stands at barrier 2.
+// Every wavefront that gets here passes barrier 1, whatever its rows are.
 template <class SYNC>
 WVF void recover_helper_row(const uint32_t *__restrict__ gtab, const u256 &z_raw, const u256 &r, const u256 &s,
                             rows_pair_shared *sh, SYNC sync) {
@@ -1540,7 +1550,7 @@ WVF void recover_helper_row(const uint32_t *__restrict__ gtab, const u256 &z_raw
   sh->gy[l] = accg.y;
   sh->gz[l] = accg.z;
   sh->ginf[l] = accg.inf ? 1u : 0u;
-  sync();  // barrier 2
+  sync.publish_and_leave();  // (in place of barrier 2: the main wavefronts wait there for this wavefront's end)
 }
 
 // ---- the warm path, one signature per wavefront --------------------------------------------------------

@@ -3,7 +3,8 @@ Usage: python tools/rows_pair_stages.py [n_rows=4096]
 
 The pair kernel (devtest_rows_pair_kernel: recover_pubkey_row<…, PAIR> + recover_helper_row) stamps s_memrealtime on both
 sides of its two workgroup barriers: per wavefront, the stage before barrier 1, the wait there, the stage between the
-barriers, the wait at barrier 2 and the rest; a second run whose main wavefronts stop behind the closing chain
+barriers, the wait at barrier 2 and the rest (a helper ends where it has published u1·G: "helper resident until" is how long
+it holds its registers, next to the main wavefront's length); a second run whose main wavefronts stop behind the closing chain
 (devtest_rows_pair_stamps_stop, STOP = 6) splits "after barrier 2" into closing chain and address hash.  Next to it, the single-wavefront form's stage deltas (devtest_rows_stage_ms:
 launches cut short after each stage) — its main loop against the pair's main loop, which shares the SIMD with the helper."""
 import ctypes as C
@@ -43,13 +44,16 @@ us = lambda a, b: np.median(s[:, :, b] - s[:, :, a], axis=0) / 100.0     # 100 M
 main, helper = slice(0, 4), slice(4, 8)
 print(f"# rows pair, {n} rows = {blocks} workgroups of 4 main + 4 helper wavefronts; kernel {pms.value:.4f} ms (devtest build)")
 print("# median over workgroups, µs, per wavefront index 0-3 (main) / 4-7 (helper)")
-for nm, a, b in [("before barrier 1", 0, 1), ("wait at barrier 1", 1, 2), ("between the barriers", 2, 3),
-                 ("wait at barrier 2", 3, 4), ("after barrier 2", 4, 5), ("whole wavefront", 0, 5)]:
-    v = us(a, b)
-    print(f"  {nm:24s} main {' '.join(f'{x:7.1f}' for x in v[main])}   helper {' '.join(f'{x:7.1f}' for x in v[helper])}")
+# a helper publishes u1·G and ends: it never stands at barrier 2, its end stamp [5] closes "between the barriers"
+row = lambda v: " ".join(f"{x:7.1f}" for x in v)
+gone = " ".join(f"{'-':>7s}" for _ in range(4))
+for nm, a, b, hb in [("before barrier 1", 0, 1, 1), ("wait at barrier 1", 1, 2, 2), ("between the barriers", 2, 3, 5),
+                     ("wait at barrier 2", 3, 4, None), ("after barrier 2", 4, 5, None), ("whole wavefront", 0, 5, 5)]:
+    print(f"  {nm:24s} main {row(us(a, b)[main])}   helper {row(us(a, hb)[helper]) if hb else gone}")
+print(f"# main wavefront {us(0, 5)[main].mean():.1f} µs, helper resident until {us(0, 5)[helper].mean():.1f} µs")
 print(f"# main: tables {us(0, 1)[main].mean():.1f} µs (single form {1000 * (st1[2] - st1[1]):.1f}), barrier-1 wait "
       f"{us(1, 2)[main].mean():.1f}, main loop {us(2, 3)[main].mean():.1f} (single form {1000 * (st1[3] - st1[2]):.1f}), barrier-2 wait "
-      f"{us(3, 4)[main].mean():.1f}; helper: scalars {us(0, 1)[helper].mean():.1f}, G additions {us(2, 3)[helper].mean():.1f}")
+      f"{us(3, 4)[main].mean():.1f}; helper: scalars {us(0, 1)[helper].mean():.1f}, G additions {us(2, 5)[helper].mean():.1f}")
 if hasattr(L, "devtest_rows_pair_stamps_stop"):
     # the same launches with the main wavefronts ending behind the closing chain: what is left of "after barrier 2" is the hash
     st6 = np.zeros_like(stamps)
