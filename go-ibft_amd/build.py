@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libibftgpu.so")
-SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "wire_recode_dev.h", "cert_wave_dev.h", "cert_scan_dev.h", "cert_verdict_dev.h", "cert_dedup_dev.h", "cert_dedup_kernels.h", "modinv_dev.h",
+SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "wire_recode_dev.h", "cert_wave_dev.h", "cert_scan_dev.h", "cert_verdict_dev.h", "cert_decide_dev.h", "cert_dedup_dev.h", "cert_dedup_kernels.h", "modinv_dev.h",
            "sign_dev.h", "sign_message_dev.h", "sign_envelope_dev.h", "sha256_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
 # Code-generation flags of the product library (part of its build stamp).  max-ilp: the verdict kernels run ONE wavefront per
 # SIMD at the sizes that matter (N ≤ 4 096), where every hazard s_nop is a lost issue slot — scheduling for instruction-level
@@ -304,6 +304,20 @@ def build_cert_verdict_harness(force: bool = False) -> str:
                                "-o", CERT_VERDICT_HARNESS, os.path.join(CSRC, "host_cert_verdict_harness.hip")], cwd=CSRC)
         _mark(CERT_VERDICT_HARNESS, deps)
     return CERT_VERDICT_HARNESS
+
+
+CERT_DECIDE_HARNESS = os.path.join(CSRC, "libdev_cert_decide_host.so")
+
+
+def build_cert_decide_harness(force: bool = False) -> str:
+    """TEST-ONLY: cert_decide_dev.h (the proposer table, valid_pc / round_change per record, the proposal clauses, the selection of
+    the highest prepared round) and the resumed sponge of cert_wave_dev.h on the CPU; the cross-lane parts through wave_emul.h."""
+    deps = ["host_cert_decide_harness.hip", "cert_decide_dev.h", "cert_verdict_dev.h", "cert_wave_dev.h", "wave_emul.h", "wire_dev.h", "keccak_dev.h"]
+    if force or _stale(CERT_DECIDE_HARNESS, deps):
+        subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
+                               "-o", CERT_DECIDE_HARNESS, os.path.join(CSRC, "host_cert_decide_harness.hip")], cwd=CSRC)
+        _mark(CERT_DECIDE_HARNESS, deps)
+    return CERT_DECIDE_HARNESS
 
 
 CERT_DEDUP_HARNESS = os.path.join(CSRC, "libdev_cert_dedup_host.so")

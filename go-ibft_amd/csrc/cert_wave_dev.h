@@ -119,11 +119,20 @@ struct wave_sponge {
 // signature field [cut0, cut0 + gap) —, total = len − gap.  with_tail = true: a Proposal — gap = 0, m[0, cut0) is the raw proposal and
 // the 8 bytes of `tail` (as they lie in memory) follow.  Lanes 0…16 fetch their 8 bytes of each block with aligned dword loads (up
 // to 3 bytes past them: buffer slack), byte by byte only where a word straddles the cut or lies in the last block.
-HD uint64_t sponge_message(const uint8_t *m, uint32_t cut0, uint32_t gap, uint32_t total, uint64_t tail, bool with_tail, uint32_t lane,
-                           uint64_t *A, uint64_t *B) {
+//
+// sponge_message_from is the same sponge between two points of the message: it STARTS behind the first done0 bytes (a multiple of
+// 136) from the state whose word sponge_word(lane) the lane passes as s0 — zero state, done0 = 0: the whole message —, and when
+// `save` is not null it stores the 25 state words as they stand behind the first save_at bytes (a multiple of 136 in
+// [done0, total]).  Two messages that agree in their first save_at bytes share that state: keccak(raw ‖ BE64(r)) for another r
+// costs the blocks behind ⌊raw_len / 136⌋ · 136 only (cert_decide_proposals_kernel).
+HD uint32_t sponge_word(uint32_t lane) { return lane < 25u ? lane : 0u; }
+HD uint64_t sponge_message_from(const uint8_t *m, uint32_t cut0, uint32_t gap, uint32_t total, uint64_t tail, bool with_tail, uint32_t lane,
+                                uint64_t *A, uint64_t *B, uint64_t s0, uint32_t done0, uint64_t *save, uint32_t save_at) {
   wave_sponge sp;
   sp.init(lane);
-  for (uint32_t done = 0;; done += 136u) {
+  sp.s = s0;
+  for (uint32_t done = done0;; done += 136u) {
+    if (save && done == save_at && sp.act) save[sp.i] = sp.s;
     const uint32_t left = total - done;
     const bool last = left < 136u;
     if (lane < 17u) {
@@ -158,6 +167,10 @@ HD uint64_t sponge_message(const uint8_t *m, uint32_t cut0, uint32_t gap, uint32
     if (last) break;
   }
   return sp.s;
+}
+HD uint64_t sponge_message(const uint8_t *m, uint32_t cut0, uint32_t gap, uint32_t total, uint64_t tail, bool with_tail, uint32_t lane,
+                           uint64_t *A, uint64_t *B) {
+  return sponge_message_from(m, cut0, gap, total, tail, with_tail, lane, A, B, 0ull, 0u, nullptr, 0u);
 }
 
 // ---- the walk over a certificate ------------------------------------------------------------------------------------------

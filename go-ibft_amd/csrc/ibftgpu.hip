@@ -186,6 +186,11 @@ struct CertState {
   DevBuf nodes, span, count, slot, prop, masks, total, tiles;
   DevBuf rec, recbase;            // ibft_judge_certificates_wire: one record per carrier, the roots' first records
   DevBuf dd_table, dd_slot, dd_pos;  // the dedup: the table, every row's slot, every representative's dense position
+  // ibft_decide_certificates_wire: one decision per record, the roots' sponge states behind the full blocks of their proposals;
+  // ibft_set_proposers: the proposers of rounds [prop_first, prop_first + prop_rounds) of prop_height (room for the most, once)
+  DevBuf dec, mid, proposers;
+  uint64_t prop_height = 0, prop_first = 0;
+  uint32_t prop_rounds = 0;
   cert_counters *h_total = nullptr, *dh_total = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // the side stream (hstream) hashes the deferred rows next to the verdict launch
   bool overlap = true;                              // IBFT_CERT_OVERLAP=0: everything on one stream, one verdict launch
@@ -196,7 +201,7 @@ struct CertState {
   uint32_t stat[4] = {0, 0, 0, 0};  // ibft_cert_stats: rows, judged, given to the verdict kernels, unplaced — of the last certificate call
 
   void release_all() {  // device buffers, the pinned block, the two events (ibft_ctx_destroy)
-    for (DevBuf *b : {&nodes, &span, &count, &slot, &prop, &masks, &total, &tiles, &rec, &recbase, &dd_table, &dd_slot, &dd_pos}) release(*b);
+    for (DevBuf *b : {&nodes, &span, &count, &slot, &prop, &masks, &total, &tiles, &rec, &recbase, &dd_table, &dd_slot, &dd_pos, &dec, &mid, &proposers}) release(*b);
     if (h_total) (void)hipHostFree(h_total);
     for (hipEvent_t e : {ev_fork, ev_join})
       if (e) (void)hipEventDestroy(e);
@@ -4265,14 +4270,18 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
 // (cert_verdict_dev.h) over the rows where they lie (kernels.hip.h: cert_judge_kernel); every per-row output is optional then.
 //
 // The call runs as stages over one cert_call (what the caller gave) and one cert_plan (what the stages found out), in this
-// order: cert_check, cert_reserve, cert_expand, cert_digests, cert_verdicts, cert_compare_and_judge, cert_deliver.
+// order: cert_check, cert_reserve, cert_expand, cert_digests, cert_verdicts, cert_compare_and_judge, cert_decide, cert_deliver.
+//
+// decide (ibft_decide_certificates_wire): the judge path, then one decision per record under the proposer table of
+// ibft_set_proposers (cert_decide_dev.h; kernels.hip.h: cert_decide_records_kernel, cert_decide_proposals_kernel).
 struct cert_call {
   const uint8_t *wire_bytes;
   const uint32_t *off;
   size_t n, rows_cap, certs_cap;  // certs_cap: judge only
-  bool judge;
+  bool judge, decide;                // decide: judge, and out_decision[i] next to out_cert[i]
   size_t *out_n_rows, *out_n_certs;  // out_n_certs, out_cert: judge only
   ibft_cert_verdict_t *out_cert;
+  ibft_cert_decision_t *out_decision;
   ibft_cert_node_t *out_nodes;  // every per-row output may be null (out_sender_mask: with judge only)
   ibft_wire_row_t *out_rows;
   uint8_t *out_class;
@@ -4298,6 +4307,7 @@ static int cert_check(const ibft_ctx *c, const cert_call &k, cert_plan &p, bool 
   if (!locked) {
     if (!c || !k.out_n_rows || (k.n && (!k.off || (!k.judge && !k.out_sender_mask)))) return IBFT_E_INVAL;
     if (k.judge && (!k.out_n_certs || (k.n && !k.out_cert))) return IBFT_E_INVAL;
+    if (k.decide && k.n && !k.out_decision) return IBFT_E_INVAL;
     if (!offsets_ok(k.off, k.n) || !bytes_ok(k.off, k.n, k.wire_bytes)) return IBFT_E_INVAL;
     *k.out_n_rows = 0;
     if (k.judge) *k.out_n_certs = 0;
@@ -4335,6 +4345,8 @@ static int cert_reserve(ibft_ctx *c, const cert_call &k, cert_plan &p) {
   if (s.dedup && (rc = ensure(c, s.dd_pos, m * 4))) return rc;
   if (k.judge && (rc = ensure(c, s.rec, m * sizeof(certv::record)))) return rc;
   if (k.judge && (rc = ensure(c, s.recbase, (m + 1) * 4))) return rc;
+  if (k.decide && (rc = ensure(c, s.dec, m * sizeof(certd::decision)))) return rc;
+  if (k.decide && (rc = ensure(c, s.mid, k.n * 25 * sizeof(uint64_t)))) return rc;
   if (!s.h_total) {
     if (hipHostMalloc((void **)&s.h_total, sizeof(cert_counters)) != hipSuccess) return IBFT_E_NOMEM;
     void *d = nullptr;
@@ -4425,7 +4437,7 @@ static int cert_expand(ibft_ctx *c, const cert_call &k, cert_plan &p) {
 // What the parents know goes down the levels; then the rows' digests: the proposal digests cleared, the deferred digests a
 // wavefront each, the rest by cert_finish_kernel — on the side stream when the deferred rows get a verdict launch of their own
 // (→ p.two, p.region), which the carrier stage then fills; the join event is left for cert_verdicts to wait on.
-static int cert_digests(ibft_ctx *c, const cert_call &, cert_plan &p) {
+static int cert_digests(ibft_ctx *c, const cert_call &k, cert_plan &p) {
   CertState &s = c->cert;
   int rc;
   const uint8_t *d_wire = (const uint8_t *)c->d_payload.p;
@@ -4459,7 +4471,8 @@ static int cert_digests(ibft_ctx *c, const cert_call &, cert_plan &p) {
   HIPCHK(c, hipMemsetAsync(d_prop, 0, (size_t)rows * 32, ds));  // rows without a Proposal: a zero digest (cert_finish_kernel skips them)
   if (carriers) {
     hipLaunchKernelGGL(ibftk::cert_digest_wave_kernel, dim3(2 * carriers), dim3(64), 0, ds, d_wire, (const wire::node_info *)d_nodes,
-                       (const wire::row_info *)d_rows, d_slot, p.region, p.d_digest, d_prop);
+                       (const wire::row_info *)d_rows, d_slot, p.region, p.d_digest, d_prop, k.decide ? (uint64_t *)s.mid.p : (uint64_t *)nullptr,
+                       k.decide ? (uint32_t)k.n : 0u);
     HIPCHK(c, hipGetLastError());
   }
   hipLaunchKernelGGL(ibftk::cert_finish_kernel, dim3((rows + 63) / 64), dim3(64), 0, ds, d_wire, d_nodes, (const wire::row_info *)d_rows, rows,
@@ -4598,6 +4611,37 @@ static int cert_compare_and_judge(ibft_ctx *c, const cert_call &k, cert_plan &p)
   return IBFT_OK;
 }
 
+// decide: behind the records, one decision per record and its way home.  (With kernel timing on, the two launches get an event
+// pair of their own: ibft_last_kernel_ms after this call is the record kernels' time plus theirs.)
+static int cert_decide(ibft_ctx *c, const cert_call &k, cert_plan &p) {
+  if (!k.decide) return IBFT_OK;
+  CertState &s = c->cert;
+  int rc;
+  ibftk::cert_decide_args da{};
+  da.nodes = (const wire::node_info *)s.nodes.p;
+  da.rows = (const wire::row_info *)c->d_wire_rows.p;
+  da.rec = (const certv::record *)s.rec.p;
+  da.wire_bytes = (const uint8_t *)c->d_payload.p;
+  da.mid_state = (const uint64_t *)s.mid.p;
+  da.table = certd::proposer_table{s.prop_height, s.prop_first, (const uint8_t *)s.proposers.p, s.proposers.p ? s.prop_rounds : 0u};
+  da.n_roots = (uint32_t)k.n;
+  da.n_rows = p.rows;
+  da.n_records = p.records;
+  da.out = (certd::decision *)s.dec.p;
+  hipEvent_t d0 = nullptr, d1 = nullptr;
+  if (c->time_every) {
+    if ((rc = next_events(c, &d0, &d1))) return rc;
+    HIPCHK(c, hipEventRecord(d0, c->stream));
+  }
+  hipLaunchKernelGGL(ibftk::cert_decide_records_kernel, dim3((p.records + 255) / 256), dim3(256), 0, c->stream, da);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(ibftk::cert_decide_proposals_kernel, dim3(std::min((uint32_t)k.n, ibftk::CERT_JUDGE_MAX_GRID)), dim3(64), 0, c->stream, da);
+  HIPCHK(c, hipGetLastError());
+  if (d1) HIPCHK(c, hipEventRecord(d1, c->stream));
+  HIPCHK(c, hipMemcpyAsync(k.out_decision, da.out, (size_t)p.records * sizeof(certd::decision), hipMemcpyDeviceToHost, c->stream));
+  return IBFT_OK;
+}
+
 // the per-row outputs that were asked for, the sender words (fetch_results waits for the stream), the counts, the stats
 static int cert_deliver(ibft_ctx *c, const cert_call &k, cert_plan &p) {
   CertState &s = c->cert;
@@ -4635,6 +4679,16 @@ static int certificates_wire_impl(ibft_ctx *c, const cert_call &k) {
                     IBFT_CERT_BIT_SELF == certv::BIT_SELF && IBFT_CERT_BIT_HAS_PROPOSAL == certv::BIT_HAS_PROPOSAL &&
                     IBFT_CERT_BIT_HAS_CERTIFICATE == certv::BIT_HAS_CERTIFICATE,
                 "ABI");
+  static_assert(sizeof(ibft_cert_decision_t) == sizeof(certd::decision) && sizeof(ibft_cert_decision_t) == 64, "ABI");
+  static_assert(offsetof(ibft_cert_decision_t, valid_pc) == offsetof(certd::decision, valid_pc) &&
+                    offsetof(ibft_cert_decision_t, proposal) == offsetof(certd::decision, proposal) &&
+                    offsetof(ibft_cert_decision_t, flags) == offsetof(certd::decision, flags) &&
+                    offsetof(ibft_cert_decision_t, prepared_record) == offsetof(certd::decision, prepared_record) &&
+                    offsetof(ibft_cert_decision_t, prepared_round) == offsetof(certd::decision, prepared_round) &&
+                    offsetof(ibft_cert_decision_t, prepared_hash) == offsetof(certd::decision, prepared_hash) &&
+                    offsetof(ibft_cert_decision_t, reserved) == offsetof(certd::decision, reserved),
+                "ABI");
+  static_assert(IBFT_PROPOSER_ROUNDS_MAX == certd::PROPOSER_ROUNDS_MAX && IBFT_CERT_DECISION_HAS_PREPARED == certd::HAS_PREPARED, "ABI");
   cert_plan p;
   int rc;
   if ((rc = cert_check(c, k, p, /*locked=*/false))) return rc;
@@ -4643,7 +4697,7 @@ static int certificates_wire_impl(ibft_ctx *c, const cert_call &k) {
   HIPCHK(c, hipSetDevice(c->device));
   c->wire.columns = false;
   c->staged_n = 0;
-  for (auto stage : {cert_reserve, cert_expand, cert_digests, cert_verdicts, cert_compare_and_judge, cert_deliver})
+  for (auto stage : {cert_reserve, cert_expand, cert_digests, cert_verdicts, cert_compare_and_judge, cert_decide, cert_deliver})
     if ((rc = stage(c, k, p))) return rc;
   return IBFT_OK;
 }
@@ -4676,6 +4730,47 @@ int ibft_judge_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const u
   k.out_n_rows = out_n_rows, k.out_nodes = out_nodes, k.out_rows = out_rows, k.out_class = out_class;
   k.out_sender_mask = out_sender_mask, k.out_hash_mask = out_hash_mask, k.out_self_mask = out_self_mask;
   return certificates_wire_impl(c, k);
+}
+
+int ibft_decide_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap, size_t certs_cap,
+                                  size_t *out_n_rows, size_t *out_n_certs, ibft_cert_verdict_t *out_cert, ibft_cert_decision_t *out_decision,
+                                  ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows, uint8_t *out_class, uint64_t *out_sender_mask,
+                                  uint64_t *out_hash_mask, uint64_t *out_self_mask) {
+  cert_call k{};
+  k.wire_bytes = wire_bytes, k.off = off, k.n = n, k.rows_cap = rows_cap;
+  k.judge = k.decide = true, k.certs_cap = certs_cap, k.out_n_certs = out_n_certs, k.out_cert = out_cert, k.out_decision = out_decision;
+  k.out_n_rows = out_n_rows, k.out_nodes = out_nodes, k.out_rows = out_rows, k.out_class = out_class;
+  k.out_sender_mask = out_sender_mask, k.out_hash_mask = out_hash_mask, k.out_self_mask = out_self_mask;
+  return certificates_wire_impl(c, k);
+}
+
+// The proposer table of the decide call: replaced whole, on the context's stream and waited for (the caller's array is free when
+// the call returns; whatever was enqueued before it has run under the table it saw).  A refused call leaves the table alone.
+int ibft_set_proposers(ibft_ctx *c, uint64_t height, uint64_t first_round, const uint8_t *proposer20, size_t n_rounds) {
+  if (!c || (n_rounds && !proposer20)) return IBFT_E_INVAL;
+  if (first_round + (uint64_t)n_rounds < first_round) return IBFT_E_INVAL;  // the range runs past 2^64
+  if (n_rounds > IBFT_PROPOSER_ROUNDS_MAX) return IBFT_E_TOOBIG;
+  ctx_lock lk(c);
+  CertState &s = c->cert;
+  if (n_rounds) {
+    int rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = ensure(c, s.proposers, (size_t)IBFT_PROPOSER_ROUNDS_MAX * 20))) return rc;
+    HIPCHK(c, hipMemcpyAsync(s.proposers.p, proposer20, n_rounds * 20, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  s.prop_height = n_rounds ? height : 0;
+  s.prop_first = n_rounds ? first_round : 0;
+  s.prop_rounds = (uint32_t)n_rounds;
+  return IBFT_OK;
+}
+int ibft_proposers_info(ibft_ctx *c, uint64_t *height, uint64_t *first_round, uint32_t *n_rounds) {
+  if (!c) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  if (height) *height = c->cert.prop_height;
+  if (first_round) *first_round = c->cert.prop_first;
+  if (n_rounds) *n_rounds = c->cert.prop_rounds;
+  return IBFT_OK;
 }
 
 int ibft_wire_stage_seals(ibft_ctx *c) {

@@ -50,6 +50,7 @@
 #include "wire_recode_dev.h"
 #include "cert_wave_dev.h"
 #include "cert_verdict_dev.h"
+#include "cert_decide_dev.h"
 #include "cert_dedup_dev.h"
 
 namespace ibftk {
@@ -1597,10 +1598,14 @@ __global__ void cert_propagate_kernel(const wire::node_info *__restrict__ nodes,
 // One job per wavefront: job 2k hashes PayloadNoSig of deferred row k → digest32[row]; job 2k + 1 hashes the Proposal that row
 // carries, keccak(rawProposal ‖ BE64(round)) → prop_digest32[row] (exits at once when there is none).  The message is
 // piece A = [a0, a0 + na) followed by piece B = [b0, b0 + nb) of the buffer, then `tail` (≤ 8 bytes, by value).
+// mid_state (ibft_decide_certificates_wire; null otherwise): the proposal job of a ROOT (row < mid_roots) also leaves the sponge
+// state behind the ⌊raw_len / 136⌋ full blocks of raw, 25 words at mid_state + 25·row — keccak(raw ‖ BE64(another round)) is
+// closed from there by cert_decide_proposals_kernel.
 __global__ void __launch_bounds__(64) cert_digest_wave_kernel(const uint8_t *__restrict__ wire_bytes, const wire::node_info *__restrict__ nodes,
                                                               const wire::row_info *__restrict__ rows,
                                                               const uint32_t *__restrict__ deferred_rows, uint32_t region,
-                                                              uint8_t *__restrict__ digest32, uint8_t *__restrict__ prop_digest32) {
+                                                              uint8_t *__restrict__ digest32, uint8_t *__restrict__ prop_digest32,
+                                                              uint64_t *__restrict__ mid_state, uint32_t mid_roots) {
   __shared__ uint64_t A[32], B[32];
   const uint32_t row = deferred_rows[blockIdx.x >> 1], lane = threadIdx.x;
   // region ≠ 0: the deferred rows form a batch of their own at rows [region, region + deferred) of the columns (cert_carrier_stage_kernel)
@@ -1625,7 +1630,8 @@ __global__ void __launch_bounds__(64) cert_digest_wave_kernel(const uint8_t *__r
     total = nd.raw_len + 8u;
     for (int k = 0; k < 8; k++) tail |= (uint64_t)((nd.proposal_round >> (8 * (7 - k))) & 0xFFu) << (8 * k);  // BE64 as the bytes lie
   }
-  const uint64_t word = cw::sponge_message(m, cut0, gap, total, tail, proposal_job, lane, A, B);
+  uint64_t *save = mid_state && proposal_job && row < mid_roots ? mid_state + 25ull * row : nullptr;  // block-uniform
+  const uint64_t word = cw::sponge_message_from(m, cut0, gap, total, tail, proposal_job, lane, A, B, 0ull, 0u, save, cut0 / 136u * 136u);
   if (lane < 4u) *reinterpret_cast<uint64_t *>((proposal_job ? prop_digest32 + 32ull * row : digest32 + 32ull * digest_row) + 8u * lane) = word;
 }
 // After the deferred digests: every row's final pre-flag and class bits, and the hash of the Proposal it carries (a lane per row;
@@ -2445,6 +2451,82 @@ __global__ void __launch_bounds__(64) cert_judge_children_kernel(certv::record *
     for (uint32_t k = lane; k < r.n_children; k += 64u) undecided = undecided || out[r.first_child_cert + k].pc == certv::UNDECIDED;
     const int rcc = certv::rcc_with_children(certv::VALID, __any(undecided));
     if (lane == 0 && rcc != certv::VALID) out[root].rcc = (int8_t)rcc;
+  }
+}
+
+// ---- certificates: one decision per record (ibft_decide_certificates_wire; the rules: cert_decide_dev.h) --------------------
+// Behind the two record kernels, with the proposer table of ibft_set_proposers: first a lane per record (valid_pc,
+// round_change; everything else of the decision at its "nothing" value), then a wavefront per root for `proposal`.
+struct cert_decide_args {
+  const wire::node_info *nodes;
+  const wire::row_info *rows;
+  const certv::record *rec;
+  const uint8_t *wire_bytes;
+  const uint64_t *mid_state;  // 25 words per root (cert_digest_wave_kernel)
+  certd::proposer_table table;
+  uint32_t n_roots, n_rows, n_records;
+  certd::decision *out;
+};
+__global__ void __launch_bounds__(256) cert_decide_records_kernel(cert_decide_args a) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n_records) return;
+  const certv::record &r = a.rec[i];
+  const bool root = i < a.n_roots;
+  uint64_t height = r.height;
+  bool known = true;
+  if (!root) {  // a record of a root PREPREPARE's certificate: validPC is asked for the PREPREPARE's height
+    const uint32_t parent = r.row < a.n_rows ? a.nodes[r.row].parent : wire::NO_PARENT;
+    known = parent < a.n_roots;
+    height = known ? a.rec[parent].height : 0ull;
+  }
+  certd::decision d;
+  certd::decide_record(d, r, root, height, known, a.table);
+  a.out[i] = d;
+}
+// One wavefront per workgroup (the wavefront sponge's LDS protocol), roots r, r + grid, …  A root that is no regular PREPREPARE,
+// or whose own clauses decide, leaves wave-uniformly; otherwise the lanes stride over the records of its RoundChangeCertificate
+// (their valid_pc was written by the launch before this one), the highest prepared round is selected across the lanes, and
+// keccak256(raw ‖ BE64(that round)) is closed from the state behind raw's full blocks: one permutation, two when
+// raw_len mod 136 ≥ 128 — whatever raw_len is.
+__global__ void __launch_bounds__(64) cert_decide_proposals_kernel(cert_decide_args a) {
+  __shared__ uint64_t A[32], B[32];
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t root = blockIdx.x; root < a.n_roots; root += gridDim.x) {
+    const certv::record &r = a.rec[root];
+    if (r.row != root || root >= a.n_rows) continue;  // (record i < n_roots is row i)
+    const wire::row_info &ri = a.rows[root];
+    const wire::node_info &nd = a.nodes[root];
+    int v = certd::proposal_head(r, ri, nd, true, a.table);  // wave-uniform: every lane reads the same record
+    if (v != certd::GO) {
+      if (lane == 0) a.out[root].proposal = (int8_t)v;
+      continue;
+    }
+    const uint32_t first = r.first_child_cert, n = r.n_children;
+    if (first == certv::NO_RECORD || first < a.n_roots || (uint64_t)first + n > a.n_records) continue;  // stays −1: no such records
+    certd::candidate best{0ull, 0u, 0u};
+    bool undecided = false;
+    for (uint32_t k = lane; k < n; k += 64u) certd::child_step(best, undecided, a.out[first + k].valid_pc, a.rec[first + k].pc_round, k);
+    const certd::candidate win = certd::wave_select(best, lane);
+    v = certd::proposal_after_children(__any(undecided), win);
+    if (v != certd::GO) {
+      if (lane == 0) a.out[root].proposal = (int8_t)v;
+      continue;
+    }
+    const uint32_t prepared = first + win.k;  // win.k < n: a child index some lane stepped over
+    const certv::record &w = a.rec[prepared];
+    const uint32_t raw_len = nd.raw_len, full = raw_len / 136u * 136u;
+    const uint64_t word = cw::sponge_message_from(a.wire_bytes + nd.raw_off, raw_len, 0u, raw_len + 8u, keccak::round_tail(w.pc_round), true, lane, A, B,
+                                                  a.mid_state[25ull * root + cw::sponge_word(lane)], full, nullptr, 0u);
+    uint64_t want = 0;
+    if (lane < 4u)
+      for (uint32_t b = 0; b < 8u; b++) want |= (uint64_t)w.pc_hash[8u * lane + b] << (8u * b);
+    const bool differs = lane < 4u && word != want;
+    const bool match = !__any(differs);
+    if (lane == 0) {
+      certd::decision d = a.out[root];
+      certd::record_prepared(d, prepared, w, match);
+      a.out[root] = d;
+    }
   }
 }
 

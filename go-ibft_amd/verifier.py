@@ -57,6 +57,7 @@ EXPORTS = [
     "ibft_block_seals_submit_sets_raw", "ibft_recover_block_seals_submit_sets", "ibft_recover_block_seals_submit_sets_raw",
     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
+    "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
@@ -73,7 +74,8 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_verify_block_seals_sets_raw", "ibft_recover_block_seals_sets_raw", "ibft_block_seals_submit_sets",
                     "ibft_block_seals_submit_sets_raw", "ibft_recover_block_seals_submit_sets", "ibft_recover_block_seals_submit_sets_raw",
                     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
-                    "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats"}
+                    "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
+                    "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
 ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
@@ -102,6 +104,12 @@ CERT_VERDICT = np.dtype([("row", "<u4"), ("first_child", "<u4"), ("n_children", 
 assert CERT_VERDICT.itemsize == 128
 CERT_NO_RECORD = 0xFFFFFFFF
 CERT_BIT_SENDER, CERT_BIT_HASH, CERT_BIT_SELF, CERT_BIT_HAS_PROPOSAL, CERT_BIT_HAS_CERTIFICATE = 1, 2, 4, 8, 16
+# ibft_cert_decision_t (include/ibftgpu.h): one decision per record of ibft_decide_certificates_wire
+CERT_DECISION = np.dtype([("valid_pc", "i1"), ("round_change", "i1"), ("proposal", "i1"), ("flags", "u1"), ("prepared_record", "<u4"),
+                          ("prepared_round", "<u8"), ("prepared_hash", "u1", 32), ("reserved", "u1", 16)])
+assert CERT_DECISION.itemsize == 64
+CERT_DECISION_HAS_PREPARED = 1
+PROPOSER_ROUNDS_MAX = 4096   # IBFT_PROPOSER_ROUNDS_MAX
 
 
 class GpuUnavailable(RuntimeError):
@@ -258,6 +266,13 @@ def load_library() -> C.CDLL:
     if hasattr(L, "ibft_judge_certificates_wire"):
         L.ibft_judge_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                                    vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_decide_certificates_wire"):
+        L.ibft_decide_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                                    vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_set_proposers"):
+        L.ibft_set_proposers.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_size_t]
+    if hasattr(L, "ibft_proposers_info"):
+        L.ibft_proposers_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     if hasattr(L, "ibft_cert_stats"):
         L.ibft_cert_stats.argtypes = [vp] + [C.POINTER(C.c_uint32)] * 4
     if hasattr(L, "ibft_wire_stats"):
@@ -299,11 +314,13 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def _judge_certificates_wire(L, handle, chk, wire, off, rows_cap: int, certs_cap: int | None, per_row: bool):
+def _judge_certificates_wire(L, handle, chk, wire, off, rows_cap: int, certs_cap: int | None, per_row: bool, decide: bool = False):
     """ibft_judge_certificates_wire on one context → (certs[CERT_VERDICT], n_rows, per-row outputs or None); the per-row outputs
-    are verify_certificates_wire's tuple without its first element"""
-    if not hasattr(L, "ibft_judge_certificates_wire"):
-        raise GpuUnavailable("this build of libibftgpu.so has no ibft_judge_certificates_wire — rebuild")
+    are verify_certificates_wire's tuple without its first element.  decide: ibft_decide_certificates_wire →
+    (certs, decisions[CERT_DECISION], n_rows, per-row outputs or None)"""
+    name = "ibft_decide_certificates_wire" if decide else "ibft_judge_certificates_wire"
+    if not hasattr(L, name):
+        raise GpuUnavailable(f"this build of libibftgpu.so has no {name} — rebuild")
     wb = _bytes_col(wire)
     off = np.ascontiguousarray(off, dtype=np.uint32)
     n = len(off) - 1
@@ -318,13 +335,38 @@ def _judge_certificates_wire(L, handle, chk, wire, off, rows_cap: int, certs_cap
         cls = np.zeros(max(cap, 1), dtype=np.uint8)
         ms, mh, mself = (np.zeros(words, dtype=np.uint64) for _ in range(3))
     n_rows, n_certs = C.c_size_t(0), C.c_size_t(0)
-    chk(L.ibft_judge_certificates_wire(handle, _p(wb), _p(off), n, cap, ccap, C.byref(n_rows), C.byref(n_certs), _p(certs), _p(nodes),
-                                       _p(rows), _p(cls), _p(ms), _p(mh), _p(mself)), "ibft_judge_certificates_wire")
+    decisions = np.zeros(max(ccap, 1), dtype=CERT_DECISION) if decide else None
+    if decide:
+        chk(L.ibft_decide_certificates_wire(handle, _p(wb), _p(off), n, cap, ccap, C.byref(n_rows), C.byref(n_certs), _p(certs), _p(decisions),
+                                            _p(nodes), _p(rows), _p(cls), _p(ms), _p(mh), _p(mself)), name)
+    else:
+        chk(L.ibft_judge_certificates_wire(handle, _p(wb), _p(off), n, cap, ccap, C.byref(n_rows), C.byref(n_certs), _p(certs), _p(nodes),
+                                           _p(rows), _p(cls), _p(ms), _p(mh), _p(mself)), name)
     k = int(n_rows.value)
     out = None
     if per_row:
         out = (nodes[:k], rows[:k], cls[:k], mask_to_bool(ms, k), mask_to_bool(mh, k), mask_to_bool(mself, k))
+    if decide:
+        return certs[:int(n_certs.value)], decisions[:int(n_certs.value)], k, out
     return certs[:int(n_certs.value)], k, out
+
+
+def _set_proposers(L, handle, chk, height: int, first_round: int, addrs) -> None:
+    """ibft_set_proposers on one context: addrs[k] (20 bytes) proposes round first_round + k of `height`; no addrs: the table is cleared"""
+    if not hasattr(L, "ibft_set_proposers"):
+        raise GpuUnavailable("this build of libibftgpu.so has no ibft_set_proposers — rebuild")
+    flat = addrs if isinstance(addrs, np.ndarray) else np.frombuffer(b"".join(bytes(x) for x in addrs), dtype=np.uint8)
+    a = np.ascontiguousarray(flat, dtype=np.uint8).reshape(-1, 20)   # raises for anything that is not 20 bytes per round
+    chk(L.ibft_set_proposers(handle, int(height), int(first_round), _p(a) if len(a) else None, len(a)), "ibft_set_proposers")
+
+
+def _proposers_info(L, handle, chk):
+    """ibft_proposers_info on one context → (height, first_round, n_rounds); n_rounds == 0: no table"""
+    if not hasattr(L, "ibft_proposers_info"):
+        raise GpuUnavailable("this build of libibftgpu.so has no ibft_proposers_info — rebuild")
+    h, f, n = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    chk(L.ibft_proposers_info(handle, C.byref(h), C.byref(f), C.byref(n)), "ibft_proposers_info")
+    return int(h.value), int(f.value), int(n.value)
 
 
 class _PinnedOwner:
@@ -955,6 +997,22 @@ class BatchVerifier:
         return _judge_certificates_wire(self._L, self._h, self._chk, wire, off, int(rows_cap if rows_cap is not None else self.max_rows),
                                         certs_cap, per_row)
 
+    def set_proposers(self, height: int, first_round: int, addrs) -> None:
+        """the proposer table of decide_certificates_wire (ibft_set_proposers): addrs[k] proposes round first_round + k of
+        `height`; it replaces the previous table, an empty addrs clears it.  set_validators leaves it alone."""
+        _set_proposers(self._L, self._h, self._chk, height, first_round, addrs)
+
+    def proposers_info(self):
+        """(height, first_round, n_rounds) of the installed proposer table; n_rounds == 0: none"""
+        return _proposers_info(self._L, self._h, self._chk)
+
+    def decide_certificates_wire(self, wire, off, rows_cap: int | None = None, certs_cap: int | None = None, per_row: bool = False):
+        """judge_certificates_wire, and for every record a decision under the proposer table (ibft_decide_certificates_wire):
+        → (certs[CERT_VERDICT], decisions[CERT_DECISION], n_rows, per_row outputs) — valid_pc, round_change and proposal are
+        −1 (undecided here: no table entry, or an irregular shape), 0 or 1 (valid_pc also 2: no certificate)."""
+        return _judge_certificates_wire(self._L, self._h, self._chk, wire, off, int(rows_cap if rows_cap is not None else self.max_rows),
+                                        certs_cap, per_row, decide=True)
+
     def cert_stats(self):
         """ibft_cert_stats, of the last verify_ / judge_certificates_wire call: (rows of the tree, rows judged — no pre-flag —,
         rows given to the verdict kernels, rows the dedup table could not place).  FLAG_CERT_DEDUP off: judged == given, 0."""
@@ -1346,6 +1404,18 @@ class DeviceGroup:
         """BatchVerifier.judge_certificates_wire on the group's FIRST context (there is no sharded form of this call: a
         carrier's children must lie on the device that judges it); same results"""
         return _judge_certificates_wire(self._L, self._L.ibft_group_ctx(self._g, 0), self._chk, wire, off, int(rows_cap), certs_cap, per_row)
+
+    def set_proposers(self, height: int, first_round: int, addrs) -> None:
+        """BatchVerifier.set_proposers on the group's FIRST context (where decide_certificates_wire runs)"""
+        _set_proposers(self._L, self._L.ibft_group_ctx(self._g, 0), self._chk, height, first_round, addrs)
+
+    def proposers_info(self):
+        return _proposers_info(self._L, self._L.ibft_group_ctx(self._g, 0), self._chk)
+
+    def decide_certificates_wire(self, wire, off, rows_cap: int = 65536, certs_cap: int | None = None, per_row: bool = False):
+        """BatchVerifier.decide_certificates_wire on the group's FIRST context (no sharded form, as for the judge call)"""
+        return _judge_certificates_wire(self._L, self._L.ibft_group_ctx(self._g, 0), self._chk, wire, off, int(rows_cap), certs_cap, per_row,
+                                        decide=True)
 
     def verify_messages(self, payload: bytes, off, msg_sig65, from20, hash32, hash_len, seal65=None, sender_pre=None,
                         valid_pre=None, raw: bytes | None = None, round_: int = 0, digest32: bytes | None = None,

@@ -48,6 +48,10 @@
  *                        <- the same, and validPC / AreValidPCMessages / HasUniqueSenders (core/ibft.go:1162-1231,
  *                           messages/helpers.go:148-213) and the RoundChangeCertificate half of validateProposal
  *                           (core/ibft.go:697-778) themselves, per certificate, up to IsProposer: one record per carrier
+ *   ibft_set_proposers, ibft_decide_certificates_wire
+ *                        <- Backend.IsProposer (core/backend.go:47-48) as a table of one height, and with it validPC whole,
+ *                           handleRoundChangeMessage's closure and validateProposal with its closing
+ *                           IsValidProposalHash (core/ibft.go:478-489, 640-787): one decision per record
  *   ibft_comm_*, ibft_group_*  validator shards over several MI355X, one RCCL all-reduce inside the library
  *   ibft_sign_seals, ibft_sign_seals_ex
  *                        <- n × Backend.BuildCommitMessage's seal (core/backend.go:12-34), simulators only (_ex: with
@@ -1014,6 +1018,78 @@ int ibft_judge_certificates_wire(ibft_ctx *ctx, const uint8_t *wire, const uint3
                                  size_t certs_cap, size_t *out_n_rows, size_t *out_n_certs, ibft_cert_verdict_t *out_cert,
                                  ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows, uint8_t *out_class,
                                  uint64_t *out_sender_mask, uint64_t *out_hash_mask, uint64_t *out_self_mask);
+
+/* ---- certificates decided: a proposer table on the device -----------------------------------------------------------
+ * The records above stop at "pc == 1: valid up to the proposer rule", because IsProposer is the Backend's.  For a Backend whose
+ * IsProposer is a pure function of (height, round) that accepts ONE address — the contract the records already rest on — the
+ * caller can hand the device that function as a table, and the device finishes validPC, the round-change rule and the
+ * proposal rule, the closing IsValidProposalHash(Proposal{raw, maxRound}, hash) of validateProposal (core/ibft.go:780-787)
+ * included.
+ *
+ * ibft_set_proposers installs the proposer of rounds [first_round, first_round + n_rounds) of ONE height, 20 bytes per round
+ * (proposer20[20·k .. 20·k + 20) = the proposer of round first_round + k).  It REPLACES the previous table; n_rounds == 0
+ * clears it.  The table is copied on the context's stream: calls enqueued before it keep the table they saw.
+ * ibft_set_validators does not touch the table — a caller whose proposers follow from the validator set installs it again when
+ * the set changes.  Errors: IBFT_E_INVAL for a NULL ctx, a NULL proposer20 with n_rounds > 0, or first_round + n_rounds past
+ * 2^64; IBFT_E_TOOBIG for n_rounds > IBFT_PROPOSER_ROUNDS_MAX.  A refused call leaves the earlier table in place.
+ * ibft_proposers_info reports the installed range (all zero: no table); any out pointer may be NULL.
+ *
+ *   T(h, r)                          UNKNOWN when there is no table, h is not the table's height, or r lies outside its range;
+ *                                    the entry otherwise.
+ *   IsProposer(who, who_len, h, r)   undecided when T(h, r) is UNKNOWN; true when who_len == 20 and the bytes are T(h, r)'s;
+ *                                    false otherwise.
+ *
+ * ibft_decide_certificates_wire is ibft_judge_certificates_wire with one more output: out_decision (certs_cap entries; NULL with
+ * n > 0: IBFT_E_INVAL), out_decision[i] belonging to out_cert[i].  Every output the judge call has, out_cert included, is bit
+ * for bit the judge call's for the same input; errors are the judge call's in its order; a refused call writes nothing.
+ * Values: −1 undecided here, 0 false, 1 true.
+ *
+ *   valid_pc      validPC whole: the record's pc when pc != 1 (so 2 = no certificate stays 2); for pc == 1
+ *                 IsProposer(pc_from, 20, H, pc_round), H = the record's own height for a level-0 record and the parent
+ *                 PREPREPARE's height for a record of its RoundChangeCertificate.  ("No PREPARE from the proposer" follows from
+ *                 unique senders, as argued above.)
+ *   round_change  for a level-0 record whose row is a judged ROUND_CHANGE, handleRoundChangeMessage's closure: valid_pc, and
+ *                 for valid_pc == 2: 0 when bits & IBFT_CERT_BIT_HAS_PROPOSAL, else 1.  −1 for every other record.
+ *   proposal      −1 for records of level 1 and for level-0 records that are no regular PREPREPARE (class 0, judged, with a
+ *                 view, type PREPREPARE, payload PREPREPARE).  Otherwise the clauses below in the reference's order; the first
+ *                 one that is not true decides — false: 0, undecided: −1:
+ *                   (a) the message carries a Proposal;  (b) Proposal.round == the message's round;
+ *                   (c) IsProposer(from, from_len, height, round);  (d) the self bit;
+ *                   (e) round == 0: 1 here (validateProposal0 never looks at a certificate);
+ *                   (f) rcc: 2 and 0 are false, −1 undecided;
+ *                   (g) every record of the certificate has valid_pc != −1;
+ *                   (h) no record of the certificate has valid_pc == 1: 1 here;
+ *                   (i) among those with valid_pc == 1 the highest pc_round wins, the LAST among equals:
+ *                       keccak256(rawProposal ‖ BE64(prepared_round)) == prepared_hash.
+ *                 Whenever (i) is reached — whether the hashes agree or not — flags has IBFT_CERT_DECISION_HAS_PREPARED,
+ *                 prepared_record is the winner's index in out_cert, prepared_round / prepared_hash its pc_round / pc_hash;
+ *                 otherwise they are 0, IBFT_CERT_NO_RECORD and zeros.  The hash of (i) costs one or two Keccak permutations
+ *                 whatever the proposal's length: the call keeps the sponge state it had behind the full blocks of
+ *                 rawProposal when it computed the self bit.  A proposal beyond IBFT_CERT_DIGEST_MAX_BYTES has class
+ *                 IBFT_CERT_CLASS_PROPOSAL_BY_HOST, so its proposal is −1.
+ *
+ * Left to the caller: the message's view against its own current view (both are in the record), IsValidProposal(raw), and
+ * "this node is not the proposer".  Without a table every IsProposer is undecided: the call is the judge call plus −1s, never
+ * wrong.  IBFT_FLAG_CERT_DEDUP and both settings of IBFT_CERT_OVERLAP change no byte of out_decision.  With kernel timing on,
+ * ibft_last_kernel_ms after this call is the time of the record kernels plus the decision kernels (one more launch pair than
+ * after the judge call).  No new ibft_version(): a build without the symbols simply lacks them.                          */
+#define IBFT_PROPOSER_ROUNDS_MAX 4096u
+int ibft_set_proposers(ibft_ctx *ctx, uint64_t height, uint64_t first_round, const uint8_t *proposer20, size_t n_rounds);
+int ibft_proposers_info(ibft_ctx *ctx, uint64_t *height, uint64_t *first_round, uint32_t *n_rounds);
+#define IBFT_CERT_DECISION_HAS_PREPARED 0x01u
+typedef struct {
+  int8_t valid_pc, round_change, proposal; /* −1 undecided here, 0 false, 1 true; valid_pc also 2 */
+  uint8_t flags;
+  uint32_t prepared_record; /* index in out_cert of the winning record, else IBFT_CERT_NO_RECORD */
+  uint64_t prepared_round;
+  uint8_t prepared_hash[32];
+  uint8_t reserved[16]; /* zero */
+} ibft_cert_decision_t; /* 64 bytes */
+int ibft_decide_certificates_wire(ibft_ctx *ctx, const uint8_t *wire, const uint32_t *off, size_t n, size_t rows_cap,
+                                  size_t certs_cap, size_t *out_n_rows, size_t *out_n_certs, ibft_cert_verdict_t *out_cert,
+                                  ibft_cert_decision_t *out_decision, ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows,
+                                  uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
+                                  uint64_t *out_self_mask);
 
 /* ---- certificates: identical nested messages (IBFT_FLAG_CERT_DEDUP) ----------------------------------------------
  * After a prepared round every ROUND_CHANGE carries a PreparedCertificate built from the same few messages, each signed once

@@ -1038,6 +1038,54 @@ func (c *Ctx) JudgeCertificatesWire(wire []byte, off []uint32, rowsCap, certsCap
 	return certs[:int(nCerts)], int(nRows), c.check(rc)
 }
 
+// CertDecision mirrors ibft_cert_decision_t: what the reference decides about the record next to it once IsProposer is
+// answered from the table of SetProposers (DecideCertificatesWire).  ValidPC / RoundChange / Proposal: -1 undecided here
+// (no table entry for the view, or an irregular shape), 0 false, 1 true; ValidPC also 2, the message carries no certificate.
+type CertDecision struct {
+	ValidPC, RoundChange, Proposal int8
+	Flags                          uint8  // CertDecisionHasPrepared
+	PreparedRecord                 uint32 // index of the record whose certificate is the highest prepared round (CertNoRecord: none)
+	PreparedRound                  uint64
+	PreparedHash                   [32]byte
+	Reserved                       [16]byte
+}
+
+const (
+	_ = unsafe.Sizeof(CertDecision{}) - 64
+	_ = 64 - unsafe.Sizeof(CertDecision{})
+)
+
+const (
+	CertDecisionHasPrepared = uint8(C.IBFT_CERT_DECISION_HAS_PREPARED)
+	ProposerRoundsMax       = int(C.IBFT_PROPOSER_ROUNDS_MAX)
+)
+
+// SetProposers installs the proposer of rounds [firstRound, firstRound + len(proposers20)/20) of ONE height
+// (ibft_set_proposers), 20 bytes per round; it replaces the previous table, an empty slice clears it.  SetValidators leaves
+// the table alone: install it again when the validator set changes.  A Backend has only the IsProposer predicate
+// (core/backend.go:47-48), so it fills the slice by asking once per validator and round, or from its own proposer calculator.
+func (c *Ctx) SetProposers(height, firstRound uint64, proposers20 []byte) error {
+	if len(proposers20)%20 != 0 {
+		return fmt.Errorf("%w: %d bytes are no whole number of 20-byte addresses", ErrFallback, len(proposers20))
+	}
+	return c.check(C.ibft_set_proposers(c.h, C.uint64_t(height), C.uint64_t(firstRound), ptr8(proposers20), C.size_t(len(proposers20)/20)))
+}
+
+// DecideCertificatesWire = JudgeCertificatesWire, and for every record a decision under the table of SetProposers
+// (ibft_decide_certificates_wire): validPC whole, handleRoundChangeMessage's closure for a root ROUND_CHANGE, and for a root
+// PREPREPARE validateProposal with its closing IsValidProposalHash (core/ibft.go:640-787).  decisions[i] belongs to certs[i].
+// Left to the caller: the message's view against its own, IsValidProposal(raw), and "this node is not the proposer".
+func (c *Ctx) DecideCertificatesWire(wire []byte, off []uint32, rowsCap, certsCap int) (certs []CertVerdict, decisions []CertDecision, rows int, err error) {
+	n := len(off) - 1
+	certs = make([]CertVerdict, certsCap+1)
+	decisions = make([]CertDecision, certsCap+1)
+	var nRows, nCerts C.size_t
+	rc := C.ibft_decide_certificates_wire(c.h, ptr8(wire), (*C.uint32_t)(unsafe.Pointer(&off[0])), C.size_t(n), C.size_t(rowsCap),
+		C.size_t(certsCap), &nRows, &nCerts, (*C.ibft_cert_verdict_t)(unsafe.Pointer(&certs[0])),
+		(*C.ibft_cert_decision_t)(unsafe.Pointer(&decisions[0])), nil, nil, nil, nil, nil, nil)
+	return certs[:int(nCerts)], decisions[:int(nCerts)], int(nRows), c.check(rc)
+}
+
 // WireStats reports on the context's last flat wire call (ibft_wire_stats): its rows, the rows judged through the recode class
 // (FlagWireRecode; 0 without it) and the rows left WireNeedsHost.  A diagnostic: the library copies the parse results to count.
 func (c *Ctx) WireStats() (rows, recoded, needsHost uint32, err error) {
