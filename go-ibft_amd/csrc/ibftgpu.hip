@@ -108,6 +108,7 @@ struct ValFamily {
 
   bool have = false;
   uint32_t n_sets = 0, power_words = 1, largest_set = 0;
+  uint32_t entries = 0;  // Σ distinct addresses over the sets: entries of d_power, bits of the wire route's bitmap
   DevBuf d_setidx, d_meta, d_power, d_quorum, d_seen, d_bset;
   std::vector<uint64_t> quorum;  // n_sets × TALLY_SUM_WORDS
   uint64_t device_bytes = 0;
@@ -215,6 +216,17 @@ struct WireBatch {
   uint32_t rows = 0;
   bool columns = false;  // ibft_wire_stage_seals: the senders-wire batch is still the resident one
   bool parsed = false;   // ibft_wire_stats: its parse results are still in d_wire_rows
+};
+
+// The height map of the live route under a family (ibft_set_height_sets) and what ibft_verify_senders_wire_sets keeps next to
+// the shared columns: the rows' sets, the per-set accumulators and the (set, member) bitmap of wire_sets_tally_kernel — both
+// sized for the family the map was installed under, zeroed then, and left zero by every launch.  The map's indices name sets
+// of THAT family: installing a family drops the map.
+struct HeightSets {
+  bool have = false;
+  uint32_t n_ranges = 0;
+  uint64_t lo = 0, hi = 0;  // first_height[0], first_height[n_ranges]
+  DevBuf d_first, d_range_set, d_row_set, d_acc, d_seen;
 };
 
 struct ibft_ctx {
@@ -340,6 +352,7 @@ struct ibft_ctx {
   uint32_t envelope_lanes_force = 0;           // IBFT_ENVELOPE_LANES=1|64 pins the form of envelope_digest_kernel (tests, A/B)
   uint32_t proposal_lane_rows = 8192;          // AUTO: the lane form from this many proposals of the longest one's length on
   ValFamily fam;                                     // ibft_set_validator_sets / the _sets block calls
+  HeightSets hsets;                                  // ibft_set_height_sets / ibft_verify_senders_wire_sets
   uint64_t valsets_bytes_max = 512ull << 20;         // IBFT_VALSETS_BYTES_MAX: the most a family's device tables may take
   uint64_t last_wide[ibftk::TALLY_SUM_WORDS] = {0};  // full-width power of the last fetched tally
   uint64_t height = 0;
@@ -1881,7 +1894,8 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_signer_nx, &c->d_pre_nx, &c->d_mask_b, &c->d_vidx_b, &c->d_bhash, &c->d_boff, &c->brec.d,
                     &c->d_boff_nx, &c->d_praw, &c->d_proff, &c->d_pround,
                     &c->d_phash, &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
-                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
+                    &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->hsets.d_first, &c->hsets.d_range_set, &c->hsets.d_row_set,
+                    &c->hsets.d_acc, &c->hsets.d_seen, &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
     release(*b);
   if (c->h_phash) (void)hipHostFree(c->h_phash);
   if (c->tstream) {
@@ -2314,8 +2328,12 @@ static int set_validator_sets_impl(ibft_ctx *c, size_t n_sets, const uint32_t *s
   f.n_sets = (uint32_t)n_sets;
   f.power_words = pw;
   f.largest_set = largest;
+  f.entries = pbase[n_sets];
   f.quorum.swap(quorum);
   f.have = true;
+  // the height map named sets of the family that just went (the wait above covers whatever read it)
+  c->hsets.have = false;
+  c->hsets.n_ranges = 0;
   // warm path: the union's addresses hold key-cache slots while the family is installed — references of their own, next to
   // those of the context's single set; an address the previous family held keeps its slot and its table
   if (c->flags & IBFT_FLAG_PUBKEY_CACHE) {
@@ -2360,6 +2378,68 @@ int ibft_validator_sets_info(ibft_ctx *c, uint32_t *n_sets, uint32_t *union_size
   if (union_size) *union_size = c->fam.have ? c->fam.n_union : 0;
   // + the calls' block_set column, and those of the two slots of the streamed _sets submits
   if (device_bytes) *device_bytes = c->fam.have ? c->fam.device_bytes + c->fam.d_bset.cap + c->bs[0].block_set_bytes() + c->bs[1].block_set_bytes() : 0;
+  return IBFT_OK;
+}
+
+// ---- the height map of the live route under a family: heights [first_height[k], first_height[k + 1]) → set range_set[k] --------
+// The new map is complete in buffers of its own before the old one goes: a refused install leaves the old map in place.  Its
+// only reader is ibft_verify_senders_wire_sets, which has synchronised before it returned.
+int ibft_set_height_sets(ibft_ctx *c, size_t n_ranges, const uint64_t *first_height, const uint32_t *range_set) {
+  if (!c) return IBFT_E_INVAL;
+  if (n_ranges == 0) {
+    ctx_lock lk(c);
+    c->hsets.have = false;
+    c->hsets.n_ranges = 0;
+    return IBFT_OK;
+  }
+  if (!first_height || !range_set) return IBFT_E_INVAL;
+  for (size_t k = 0; k < n_ranges; k++)
+    if (first_height[k + 1] <= first_height[k]) return IBFT_E_INVAL;
+  if (n_ranges > IBFT_HEIGHT_RANGES_MAX) return IBFT_E_TOOBIG;
+  ctx_lock lk(c);
+  const ValFamily &f = c->fam;
+  if (!f.have) return IBFT_E_NOVALSET;
+  for (size_t k = 0; k < n_ranges; k++)
+    if (range_set[k] >= f.n_sets) return IBFT_E_INVAL;
+  HIPCHK(c, hipSetDevice(c->device));
+  HeightSets &h = c->hsets;
+  DevBuf nfirst, nset;
+  const size_t acc_bytes = (size_t)f.n_sets * (2 * f.power_words + 1) * 8, seen_bytes = std::max<size_t>(((size_t)f.entries + 31) / 32 * 4, 4);
+  int rc;
+  if (!(rc = upload(c, nfirst, first_height, (n_ranges + 1) * 8)) && !(rc = upload(c, nset, range_set, n_ranges * 4)) &&
+      !(rc = ensure(c, h.d_acc, acc_bytes)) && !(rc = ensure(c, h.d_seen, seen_bytes)) &&
+      !(rc = ensure(c, h.d_row_set, (size_t)c->max_rows * 4))) {
+    if (hipMemsetAsync(h.d_acc.p, 0, h.d_acc.cap, c->stream) != hipSuccess || hipMemsetAsync(h.d_seen.p, 0, h.d_seen.cap, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+      c->last_error = "ibft_set_height_sets: upload failed";
+      rc = IBFT_E_HIP;
+    }
+  }
+  if (rc) {  // (the scratch buffers may have been re-allocated: without them the old map cannot be used either)
+    (void)hipStreamSynchronize(c->stream);
+    release(nfirst);
+    release(nset);
+    if (!h.d_acc.p || !h.d_seen.p || !h.d_row_set.p) h.have = false;
+    return rc;
+  }
+  std::swap(h.d_first, nfirst);
+  std::swap(h.d_range_set, nset);
+  release(nfirst);
+  release(nset);
+  h.n_ranges = (uint32_t)n_ranges;
+  h.lo = first_height[0];
+  h.hi = first_height[n_ranges];
+  h.have = true;
+  return IBFT_OK;
+}
+
+int ibft_height_sets_info(ibft_ctx *c, uint32_t *n_ranges, uint64_t *lo, uint64_t *hi) {
+  if (!c) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  const HeightSets &h = c->hsets;
+  if (n_ranges) *n_ranges = h.have ? h.n_ranges : 0;
+  if (lo) *lo = h.have ? h.lo : 0;
+  if (hi) *hi = h.have ? h.hi : 0;
   return IBFT_OK;
 }
 
@@ -4187,6 +4267,111 @@ int ibft_verify_senders_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint3
     HIPCHK(c, hipMemcpyAsync(out_rows, c->d_wire_rows.p, n * sizeof(ibft_wire_row_t), hipMemcpyDeviceToHost, c->stream));
   if ((rc = fetch_results(c, (uint32_t)n, out_mask, tally, true))) return rc;
   c->wire.parsed = true;
+  return IBFT_OK;
+}
+
+// The same under a family of sets: every message judged under the set of ITS height (ibft_set_height_sets).  The walks, then
+// wire_row_set_kernel (the rows' sets; rows without one pre-flagged), the verdict launch against the family's union
+// (family_view), wire_sets_tally_kernel (the union verdicts → per-set verdicts, indices and records), one synchronisation.
+static int enqueue_wire_sets_tally(ibft_ctx *c, uint32_t n, uint64_t *out) {
+  if (c->read_pending) {  // a consumer stream is still copying the previous results (ibft_seals_export_on / exchange)
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
+    c->read_pending = false;
+  }
+  const ValFamily &f = c->fam;
+  const HeightSets &h = c->hsets;
+  ibftk::wire_sets_tally_args t{};
+  t.work_mask = (uint64_t *)c->d_mask.p;
+  t.mask = (uint64_t *)c->d_mask_out.p;
+  t.host_mask = c->dh_mask;
+  t.vidx = (int32_t *)c->d_vidx.p;
+  t.row_set = (const int32_t *)h.d_row_set.p;
+  t.setidx = (const int32_t *)f.d_setidx.p;
+  t.set_meta = (const uint2 *)f.d_meta.p;
+  t.vpower32 = (const uint32_t *)f.d_power.p;
+  t.quorum = (const uint64_t *)f.d_quorum.p;
+  t.n = n;
+  t.n_sets = f.n_sets;
+  t.n_union = c->n_validators;  // (under family_view: the union's size)
+  t.seen_words = (f.entries + 31) / 32;
+  const size_t lds = (size_t)t.seen_words * 4;
+  t.lds_bitmap = lds <= ibftk::WSETS_LDS_MAX ? 1u : 0u;
+  t.seen = (uint32_t *)h.d_seen.p;
+  t.set_acc = (uint64_t *)h.d_acc.p;
+  t.acc = (uint64_t *)c->d_acc.p;
+  t.out = out;
+  const dim3 grid((n + ibftk::WSETS_ROWS - 1) / ibftk::WSETS_ROWS), block(ibftk::WSETS_THREADS);
+  const size_t dyn = t.lds_bitmap ? lds : 0;
+  if (f.power_words == 1)
+    hipLaunchKernelGGL(ibftk::wire_sets_tally_kernel<1>, grid, block, dyn, c->stream, t);
+  else
+    hipLaunchKernelGGL(ibftk::wire_sets_tally_kernel<4>, grid, block, dyn, c->stream, t);
+  HIPCHK(c, hipGetLastError());
+  if ((uint32_t)mask_words(n) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed every word that held bits
+  return IBFT_OK;
+}
+
+int ibft_verify_senders_wire_sets(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, uint64_t *out_mask,
+                                  ibft_wire_row_t *out_rows, int32_t *out_set, int32_t *out_vidx, ibft_tally_t *out_tally) {
+  if (!c || (n && (!off || !out_mask))) return IBFT_E_INVAL;
+  if (!offsets_ok(off, n) || !bytes_ok(off, n, wire_bytes)) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  if (n > c->max_rows) return IBFT_E_TOOBIG;
+  if (!c->fam.have || !c->hsets.have) return IBFT_E_NOVALSET;
+  // from here to the return "the validator set" of the context is the family's union (table, size, key-cache slots)
+  family_view fv(c);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  const uint32_t nr = (uint32_t)n, ns = c->fam.n_sets;
+  const size_t wbytes = n ? off[n] : 0;
+  if ((rc = ensure_wire_buffers(c, wbytes))) return rc;
+  if ((rc = ensure_block_records(c, c->brec, ns))) return rc;
+  if (wbytes) HIPCHK(c, hipMemcpyAsync(c->d_payload.p, wire_bytes, wbytes, hipMemcpyHostToDevice, c->stream));
+  if ((rc = upload(c, c->d_off, off, (n + 1) * 4))) return rc;
+  // rows judged against the union are nothing ibft_seals_launch or ibft_wire_stage_seals could re-judge under the single set
+  c->staged_n = 0;
+  c->staged_pre = true;
+  c->wire.rows = nr;
+  c->wire.columns = false;
+  c->wire.parsed = false;
+  c->ev_used = 0;
+  // A call that fails once kernels are enqueued may leave the tally's scratch (per-set accumulators, bitmap) half used: the map
+  // goes with it, and ibft_set_height_sets — which the caller then needs again — zeroes both.
+  struct map_guard {
+    ibft_ctx *c;
+    bool done = false;
+    ~map_guard() {
+      if (!done) c->hsets.have = false;
+    }
+  } guard{c};
+  if (nr) {
+    if ((rc = enqueue_wire_parse(c, nr))) return rc;
+    const HeightSets &h = c->hsets;
+    const ibftk::height_map m{(const uint64_t *)h.d_first.p, (const uint32_t *)h.d_range_set.p, h.n_ranges};
+    hipLaunchKernelGGL(ibftk::wire_row_set_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, (const wire::row_info *)c->d_wire_rows.p,
+                       nr, m, (int32_t *)h.d_row_set.p, (uint8_t *)c->d_pre.p);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = enqueue_recover(c, c->stream, nr, true, ibftk::MODE_SEALS, true))) return rc;
+    if ((rc = enqueue_wire_sets_tally(c, nr, c->brec.map ? c->brec.map : (uint64_t *)c->brec.d.p))) return rc;
+    c->host_direct = false;
+    const size_t mw = (size_t)mask_words(nr);
+    if (!c->dh_mask) HIPCHK(c, hipMemcpyAsync(c->h_mask, c->d_mask_out.p, mw * 8, hipMemcpyDeviceToHost, c->stream));
+    if (!c->brec.map) HIPCHK(c, hipMemcpyAsync(c->brec.h, c->brec.d.p, (size_t)ns * 32, hipMemcpyDeviceToHost, c->stream));
+    if (c->cache_on) HIPCHK(c, hipMemcpyAsync(c->h_tally + 4, c->dev->d_learned.p, 8, hipMemcpyDeviceToHost, c->stream));
+    if (out_rows) HIPCHK(c, hipMemcpyAsync(out_rows, c->d_wire_rows.p, n * sizeof(ibft_wire_row_t), hipMemcpyDeviceToHost, c->stream));
+    if (out_set) HIPCHK(c, hipMemcpyAsync(out_set, h.d_row_set.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (out_vidx) HIPCHK(c, hipMemcpyAsync(out_vidx, c->d_vidx.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->cache_on) {  // keys these rows taught the device → tables (the next call is warm)
+      const uint32_t *lw = reinterpret_cast<const uint32_t *>(c->h_tally + 4);
+      if ((rc = build_new_tables(c, lw[0], lw[1]))) return rc;
+    }
+    memcpy(out_mask, c->h_mask, mw * 8);
+    if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
+  }
+  fill_block_tallies(out_tally, ns, nr, c->brec.h, [&](uint32_t s) -> const uint64_t * { return &c->fam.quorum[(size_t)s * ibftk::TALLY_SUM_WORDS]; });
+  c->wire.parsed = true;
+  guard.done = true;
   return IBFT_OK;
 }
 

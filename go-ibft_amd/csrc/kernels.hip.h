@@ -48,6 +48,7 @@
 #include "wave_fe_dev.h"
 #include "wire_dev.h"
 #include "wire_recode_dev.h"
+#include "wire_sets_dev.h"
 #include "cert_wave_dev.h"
 #include "cert_verdict_dev.h"
 #include "cert_decide_dev.h"
@@ -1712,8 +1713,7 @@ __global__ void __launch_bounds__(256) cert_compare_kernel(const wire::node_info
 //   [16..16+2·PW) the raw 32-bit piece sums (what the multi-GPU exchange adds across ranks).
 constexpr int TALLY_THREADS = 1024;
 constexpr int TALLY_ROWS_PER_BLOCK = 4096;
-constexpr int TALLY_SUM_WORDS = 5;       // 256-bit powers × up to 2^20 validators < 2^276
-constexpr int TALLY_MAX_PIECES = 8;      // 2·PW 32-bit pieces
+// (TALLY_SUM_WORDS, TALLY_MAX_PIECES, pieces_to_words and words_ge: wire_sets_dev.h, where the CPU harness reaches them)
 constexpr int TALLY_OUT_WIDE = 5;        // out[5..10)
 constexpr int TALLY_OUT_PIECES = 16;     // out[16..24)
 constexpr int TALLY_OUT_WORDS = 24;
@@ -1725,27 +1725,6 @@ __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-// Σ piece_k·2^(32k) → TALLY_SUM_WORDS little-endian u64 words (pieces are sums of 32-bit values, < 2^60)
-__device__ __forceinline__ void pieces_to_words(const uint64_t *piece, int n_pieces, uint64_t w[TALLY_SUM_WORDS]) {
-  uint64_t carry = 0;  // running value >> 32 at each 32-bit position
-  uint32_t half[2 * TALLY_SUM_WORDS];
-#pragma unroll
-  for (int k = 0; k < 2 * TALLY_SUM_WORDS; k++) {
-    const uint64_t t = carry + (k < n_pieces ? piece[k] : 0ull);  // < 2^61
-    half[k] = (uint32_t)t;
-    carry = t >> 32;
-  }
-#pragma unroll
-  for (int i = 0; i < TALLY_SUM_WORDS; i++) w[i] = (uint64_t)half[2 * i] | ((uint64_t)half[2 * i + 1] << 32);
-}
-__device__ __forceinline__ bool words_ge(const uint64_t a[TALLY_SUM_WORDS], const uint64_t *b) {
-#pragma unroll
-  for (int i = TALLY_SUM_WORDS - 1; i >= 0; i--) {
-    if (a[i] != b[i]) return a[i] > b[i];
-  }
-  return true;
 }
 
 // After the verdict launch of a message set: word w of the work mask holds the envelope verdicts of rows 64w.., word
@@ -2266,6 +2245,204 @@ __global__ void __launch_bounds__(THREADS)
     a.work_mask[i] = 0;
     a.mask[i] = w;
     if (a.host_mask) a.host_mask[i] = w;
+  }
+  if (tid == 0) __hip_atomic_store(a.acc + TALLY_MAX_PIECES + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- the live route under a family of sets (ibft_verify_senders_wire_sets; the row bodies: wire_sets_dev.h) -----------------
+// Behind wire_parse_kernel and the recode walk, in front of the verdict launch: a thread per message looks its decoded height
+// up in the height map, writes the row's set and pre-flags the rows that have none — the verdict kernels skip them, so a peer
+// that sprays heights of no range buys no ECDSA work.
+__global__ void __launch_bounds__(256) wire_row_set_kernel(const wire::row_info *__restrict__ rows, uint32_t n, height_map m,
+                                                           int32_t *__restrict__ row_set, uint8_t *__restrict__ pre_flags) {
+  const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  const int32_t s = wire_row_set_row(rows[row], m);
+  row_set[row] = s;
+  if (s < 0) pre_flags[row] = 1;
+}
+
+// HasQuorum per SET over rows whose sets are INTERLEAVED (block_tally_kernel wants a block's rows contiguous): the verdict
+// kernels judged every row against the union of the family's addresses and left the signer's union index; this kernel is
+// row-parallel — a workgroup takes WSETS_ROWS consecutive rows whatever their sets —, so its work does not depend on how many of the
+// family's sets the batch touches (the bound: `work` below).
+//   per row      wire_sets_row: the verdict under the row's set (an atomic AND where a member of the union outside the set
+//                loses its bit), the index column rewritten from union to set index, the member's entry in the family's
+//                packed columns (set_meta[s].x + index).
+//   distinct     one bit per (set, member) ENTRY — the bitmap spans the whole family, ⌈Σ set sizes / 32⌉ words.  As in
+//                tally_kernel a workgroup collects its rows' bits in LDS and merges them into the HBM bitmap word by word,
+//                keeping the bits it was first to set: a row adds its power iff it was first in its workgroup and its
+//                workgroup first for the entry.  A family whose bitmap does not fit WSETS_LDS_MAX (more than 393 216
+//                entries) sends every counting row's bit to HBM directly (lds_bitmap = 0).
+//   sums         a wavefront reduces the rows of one set at a time — every thread first adds up those of its four rows that
+//                belong to the turn's set (the set of the first lane that still waits; a receive queue mixes two or three
+//                heights, so two or three turns per 256 rows) — and the leader adds valid | distinct << 32 and, only where a
+//                row was first, the 2·PW pieces to the set's accumulators in HBM: NP + 1 words per set.
+//   work         O(n + n_sets) for the rows and the records; on top of that every workgroup of the LDS form zeroes and scans
+//                the whole bitmap once: ⌈n / 1 024⌉ · ⌈entries / 32⌉ LDS words in all — 7 words per workgroup for two sets of
+//                100, 3 200 for 1 024 sets of 100, 12 288 at the LDS cap — and the last workgroup its entries / 32 HBM words.
+//   the end      the workgroup that draws the last ticket (block_tally_kernel's discipline: every thread fences its atomics,
+//                then one ticket per workgroup in acc[TALLY_MAX_PIECES + 2]) moves and zeroes the work mask, turns every
+//                set's accumulators into tally_kernel's record against the set's quorum and zeroes them, and zeroes the
+//                bitmap — by its words in the LDS form, by the rows' entries (re-read from the rewritten index column) in
+//                the HBM form — and the ticket: all scratch is zero again when the kernel ends.
+constexpr int WSETS_THREADS = 256, WSETS_RPT = 4;
+constexpr uint32_t WSETS_ROWS = WSETS_THREADS * WSETS_RPT;
+constexpr uint32_t WSETS_LDS_MAX = 49152;
+struct wire_sets_tally_args {
+  uint64_t *work_mask;         // verdict words of the launch; consumed (moved to mask / host_mask, zeroed) here
+  uint64_t *mask, *host_mask;  // host_mask: mapped pinned host memory or null
+  int32_t *vidx;               // n: in — union index (meaningful where the verdict bit is set), out — index in the row's set or −1
+  const int32_t *row_set;      // n: the row's set (wire_row_set_kernel), −1: none
+  const int32_t *setidx;       // n_sets × n_union
+  const uint2 *set_meta;       // n_sets × {first entry, distinct addresses}
+  const uint32_t *vpower32;    // Σ set sizes × 2·PW pieces
+  const uint64_t *quorum;      // n_sets × TALLY_SUM_WORDS
+  uint32_t n, n_sets, n_union;
+  uint32_t seen_words;         // ⌈Σ set sizes / 32⌉
+  uint32_t lds_bitmap;         // seen_words words of dynamic LDS; 0: every row's bit goes to `seen` directly
+  uint32_t *seen;              // seen_words, zero between launches
+  uint64_t *set_acc;           // n_sets × (2·PW + 1): pieces, valid | distinct << 32; zero between launches
+  uint64_t *acc;               // TALLY_ACC_WORDS, zero between launches (the ticket)
+  uint64_t *out;               // n_sets × 4 u64 (device memory or mapped pinned host memory)
+};
+template <int PW>
+__global__ void __launch_bounds__(WSETS_THREADS) wire_sets_tally_kernel(wire_sets_tally_args a) {
+  constexpr int NP = 2 * PW;
+  extern __shared__ uint32_t wseen[];
+  __shared__ uint32_t last_flag;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t row0 = blockIdx.x * WSETS_ROWS;
+  // a verdict word: other workgroups may atomic-AND other bits of the same word
+  auto mask_word = [&](uint32_t i) -> uint64_t { return __hip_atomic_load(a.work_mask + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  if (a.lds_bitmap)
+    for (uint32_t i = tid; i < a.seen_words; i += WSETS_THREADS) wseen[i] = 0;
+  bool bit[WSETS_RPT];
+  int vi[WSETS_RPT];
+  int32_t set[WSETS_RPT];
+  wire_sets_row_t sr[WSETS_RPT];
+  uint32_t pw[WSETS_RPT][NP];
+#pragma unroll
+  for (int j = 0; j < WSETS_RPT; j++) {
+    const uint32_t r = row0 + (uint32_t)j * WSETS_THREADS + tid;
+    bit[j] = r < a.n && ((mask_word(r >> 6) >> (r & 63)) & 1ull);
+    vi[j] = r < a.n ? a.vidx[r] : -1;
+    set[j] = r < a.n ? a.row_set[r] : -1;
+  }
+#pragma unroll
+  for (int j = 0; j < WSETS_RPT; j++) sr[j] = wire_sets_row(bit[j], vi[j], set[j], a.setidx, a.n_union, a.set_meta);
+#pragma unroll
+  for (int j = 0; j < WSETS_RPT; j++) {
+#pragma unroll
+    for (int k = 0; k < NP; k++) pw[j][k] = sr[j].counts ? a.vpower32[(size_t)sr[j].entry * NP + k] : 0u;
+  }
+#pragma unroll
+  for (int j = 0; j < WSETS_RPT; j++) {
+    const uint32_t r = row0 + (uint32_t)j * WSETS_THREADS + tid;
+    if (r < a.n) a.vidx[r] = sr[j].si;
+    if (sr[j].clear) atomicAnd(reinterpret_cast<unsigned long long *>(a.work_mask + (r >> 6)), ~(1ull << (r & 63)));
+  }
+  __syncthreads();  // the LDS bitmap is zero
+  uint32_t *bm = a.lds_bitmap ? wseen : a.seen;
+  bool first[WSETS_RPT];
+#pragma unroll
+  for (int j = 0; j < WSETS_RPT; j++) {
+    first[j] = false;
+    if (!sr[j].counts) continue;
+    const uint32_t m = 1u << (sr[j].entry & 31);
+    first[j] = !(atomicOr(&bm[sr[j].entry >> 5], m) & m);  // a signer's power counts once per set (validator_manager.go:147-155)
+  }
+  if (a.lds_bitmap) {  // (launch-uniform) the workgroup's words → the HBM bitmap; what stays in LDS: the bits it was first to set
+    __syncthreads();
+    for (uint32_t i = tid; i < a.seen_words; i += WSETS_THREADS) {
+      const uint32_t mine = wseen[i];
+      if (mine) wseen[i] = mine & ~atomicOr(&a.seen[i], mine);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < WSETS_RPT; j++) {
+      const uint32_t e = first[j] ? sr[j].entry : 0u;
+      first[j] = first[j] && ((wseen[e >> 5] >> (e & 31)) & 1u);
+    }
+  }
+  // a thread's four rows and a wavefront's 64 threads, one set per turn: the set of the first lane that still holds a valid row
+  uint32_t pend = 0;  // the thread's valid rows not yet added
+#pragma unroll
+  for (int j = 0; j < WSETS_RPT; j++) pend |= sr[j].bit ? 1u << j : 0u;
+  for (uint64_t todo = __ballot(pend ? 1 : 0); todo; todo = __ballot(pend ? 1 : 0)) {  // (wave-uniform: every lane takes every turn)
+    const int leader = __ffsll((long long)todo) - 1;
+    int32_t next = -1;  // the set of this thread's first pending row
+#pragma unroll
+    for (int j = WSETS_RPT - 1; j >= 0; j--)
+      if ((pend >> j) & 1u) next = set[j];
+    const int32_t s = __shfl(next, leader, 64);
+    uint64_t cnt = 0, p[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) p[k] = 0;
+#pragma unroll
+    for (int j = 0; j < WSETS_RPT; j++) {
+      if (!((pend >> j) & 1u) || set[j] != s) continue;
+      pend &= ~(1u << j);
+      cnt += 1ull | ((uint64_t)(first[j] ? 1u : 0u) << 32);
+      if (first[j]) {
+#pragma unroll
+        for (int k = 0; k < NP; k++) p[k] += pw[j][k];
+      }
+    }
+    uint64_t *acc = a.set_acc + (size_t)s * (NP + 1);
+    cnt = wave_sum_u64(cnt);
+    if (cnt >> 32) {  // (wave-uniform) somebody was first: the pieces
+#pragma unroll
+      for (int k = 0; k < NP; k++) {
+        const uint64_t sum = wave_sum_u64(p[k]);
+        if ((int)lane == leader && sum) atomicAdd(reinterpret_cast<unsigned long long *>(acc + k), (unsigned long long)sum);
+      }
+    }
+    if ((int)lane == leader) atomicAdd(reinterpret_cast<unsigned long long *>(acc + NP), (unsigned long long)cnt);
+  }
+  // ---- every workgroup has judged its rows: the last one delivers ----
+  __threadfence();  // (every thread: its atomics and its index stores are performed before the ticket is taken)
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES + 2), 1ull);
+    last_flag = (t == (unsigned long long)gridDim.x - 1ull) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!last_flag) return;
+  const uint32_t words = (a.n + 63) / 64;
+  for (uint32_t i = tid; i < words; i += WSETS_THREADS) {
+    const uint64_t w = mask_word(i);
+    a.work_mask[i] = 0;
+    a.mask[i] = w;
+    if (a.host_mask) a.host_mask[i] = w;
+  }
+  for (uint32_t s = tid; s < a.n_sets; s += WSETS_THREADS) {
+    uint64_t *acc = a.set_acc + (size_t)s * (NP + 1);
+    uint64_t piece[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) piece[k] = __hip_atomic_load(acc + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t cnt = __hip_atomic_load(acc + NP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cnt) {  // (a set without valid rows added nothing)
+#pragma unroll
+      for (int k = 0; k <= NP; k++) __hip_atomic_store(acc + k, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    uint64_t rec[4];
+    wire_sets_record(piece, NP, cnt, a.quorum + (size_t)s * TALLY_SUM_WORDS, rec);
+    uint64_t *o = a.out + 4ull * s;
+#pragma unroll
+    for (int i = 0; i < 4; i++) o[i] = rec[i];
+  }
+  if (a.lds_bitmap) {
+    for (uint32_t i = tid; i < a.seen_words; i += WSETS_THREADS)
+      if (__hip_atomic_load(a.seen + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        __hip_atomic_store(a.seen + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {  // by the rows that set a bit: the index column holds set indices now, −1 wherever the row set nothing
+    for (uint32_t r = tid; r < a.n; r += WSETS_THREADS) {
+      const int32_t s = a.row_set[r];
+      const int v = __hip_atomic_load(a.vidx + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (s >= 0 && v >= 0) __hip_atomic_store(a.seen + ((a.set_meta[s].x + (uint32_t)v) >> 5), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
   if (tid == 0) __hip_atomic_store(a.acc + TALLY_MAX_PIECES + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -58,6 +58,7 @@ EXPORTS = [
     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
     "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire",
+    "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
@@ -75,7 +76,8 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_block_seals_submit_sets_raw", "ibft_recover_block_seals_submit_sets", "ibft_recover_block_seals_submit_sets_raw",
                     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
                     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
-                    "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire"}
+                    "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire",
+                    "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
 ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
@@ -252,6 +254,9 @@ def load_library() -> C.CDLL:
         "ibft_set_validator_sets": [vp, C.c_size_t, vp, vp, vp, vp],
         "ibft_set_validator_sets_u256": [vp, C.c_size_t, vp, vp, vp, vp],
         "ibft_validator_sets_info": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)],
+        "ibft_set_height_sets": [vp, C.c_size_t, vp, vp],
+        "ibft_height_sets_info": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+        "ibft_verify_senders_wire_sets": [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp],
         "ibft_block_seals_collect": [vp, vp, vp],
         "ibft_block_seals_pending": [vp] + [C.POINTER(C.c_uint32)] * 3,
         "ibft_block_seals_collect_ex": [vp, vp, vp, vp, vp, vp],
@@ -941,6 +946,46 @@ class BatchVerifier:
                                                    C.byref(t)), "ibft_verify_senders_wire")
         self._staged = n
         return mask_to_bool(mask, n), rows, t
+
+    # the same under a family of sets: every message judged under the validator set of ITS height
+    def try_set_height_sets(self, first_height, range_set) -> int:
+        self._need("ibft_set_height_sets")
+        fh = np.ascontiguousarray(first_height, dtype=np.uint64)
+        rs = np.ascontiguousarray(range_set, dtype=np.uint32)
+        if len(rs) and len(fh) != len(rs) + 1:
+            raise ValueError("first_height needs one entry more than range_set")
+        return self._L.ibft_set_height_sets(self._h, len(rs), _p(fh) if len(rs) else None, _p(rs) if len(rs) else None)
+
+    def set_height_sets(self, first_height, range_set) -> None:
+        """ibft_set_height_sets: heights in [first_height[k], first_height[k+1]) are judged under set range_set[k] of the
+        installed family; empty lists clear the map.  Installing a family drops the map."""
+        self._chk(self.try_set_height_sets(first_height, range_set), "ibft_set_height_sets")
+
+    def height_sets_info(self):
+        """→ (ranges, first mapped height, first height past the last range) of the installed map; (0, 0, 0) without one"""
+        self._need("ibft_height_sets_info")
+        n, lo, hi = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        self._chk(self._L.ibft_height_sets_info(self._h, C.byref(n), C.byref(lo), C.byref(hi)), "ibft_height_sets_info")
+        return n.value, lo.value, hi.value
+
+    def verify_senders_wire_sets(self, wire, off, want_rows: bool = True):
+        """ibft_verify_senders_wire_sets: is_valid_validator_wire for a batch that mixes heights, every message under the set the
+        height map names for its height → (verdict bool[n], rows or None, set int32[n] (-1: none), vidx int32[n] — the index in
+        the ROW's set or -1 —, Tally list[n_sets])"""
+        self._need("ibft_verify_senders_wire_sets")
+        wb = _bytes_col(wire)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        n = len(off) - 1
+        ns = self.validator_sets_info()[0]
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        rows = np.zeros(n, dtype=WIRE_ROW) if want_rows else None
+        rset = np.full(max(n, 1), -1, dtype=np.int32)
+        vidx = np.full(max(n, 1), -1, dtype=np.int32)
+        tal = (Tally * max(ns, 1))()
+        self._chk(self._L.ibft_verify_senders_wire_sets(self._h, _p(wb), _p(off), n, _p(mask), _p(rows) if (n and want_rows) else None,
+                                                        _p(rset), _p(vidx), tal), "ibft_verify_senders_wire_sets")
+        self._staged = 0
+        return mask_to_bool(mask, n), rows, rset[:n], vidx[:n], [tal[s] for s in range(ns)]
 
     def verify_messages_wire(self, wire, off, height: int, round_: int, raw: bytes | None = None, proposal_round: int | None = None,
                              digest32: bytes | None = None, want_rows: bool = True, proposer: bytes | None = None):

@@ -551,8 +551,9 @@ int ibft_block_seals_pending_ex(ibft_ctx *ctx, uint32_t *batches_in_flight, uint
  * at every set change and streamed under ibft_set_validators it takes 0.13 … 0.16 × at 65 500 rows and 0.36 … 0.45 × at 16 300.
  * What the _sets call gains over a cut batch and what it costs over the single-set call: DESIGN.md §5.11.
  * Out of scope: streamed (submit / collect) forms over a device group, the sharded group calls as a whole, appending to a
- * family in place, more than two batches in flight, and a family for the message-set / wire entry points (consensus runs
- * at one height).                                                                                                      */
+ * family in place, more than two batches in flight, and a family for the message-set and certificate entry points.  (The
+ * live route is NOT out of scope: IsValidValidator is defined per message, against the validators at the height IN the
+ * message, and a node stores the messages of heights ahead of its own — ibft_verify_senders_wire_sets, further down.)  */
 int ibft_set_validator_sets(ibft_ctx *ctx, size_t n_sets, const uint64_t *height, const uint32_t *set_off,
                             const uint8_t *addrs20, const uint64_t *power);
 int ibft_set_validator_sets_u256(ibft_ctx *ctx, size_t n_sets, const uint64_t *height, const uint32_t *set_off,
@@ -663,6 +664,65 @@ int ibft_wire_stage_seals(ibft_ctx *ctx);
  * ctx: IBFT_E_INVAL; all zero before the first such call or after a certificate call has reused the rows.  No new
  * ibft_version(): a build without the symbol simply lacks it.                                                        */
 int ibft_wire_stats(ibft_ctx *ctx, uint32_t *rows, uint32_t *recoded_rows, uint32_t *needs_host_rows);
+
+/* ---- the wire route under a FAMILY of sets: every message judged under the validator set of ITS OWN height -------------
+ * IsValidValidator asks whether "the signer address is one of the validators at the height in message"
+ * (core/backend.go:41-45), and IBFT.AddMessage accepts — and stores for later — every message of the node's own height OR
+ * A GREATER ONE (core/ibft.go:1126-1149), dropping for good what IsValidValidator rejects.  On a chain whose validator set
+ * moves at an epoch boundary a node one block behind therefore receives PREPAREs and COMMITs of height h + 1 while it runs
+ * h, at every height: under the one set of ibft_verify_senders_wire a validator that joins at h + 1 is rejected (its
+ * message is lost) and one that left is accepted, unless the caller cuts every receive-queue batch by height and pays an
+ * ibft_set_validators per piece.  With the validator-set family (ibft_set_validator_sets, above) and a map from heights to
+ * its sets, the batch goes in whole.
+ *
+ * ibft_set_height_sets: heights in [first_height[k], first_height[k+1]) are judged under set range_set[k] of the installed
+ *   family (first_height has n_ranges + 1 entries, strictly increasing; adjacent ranges may name the same set); every other
+ *   height has no set.  Checked in this order: IBFT_E_INVAL NULL ctx; n_ranges = 0 clears the map and returns IBFT_OK;
+ *   IBFT_E_INVAL NULL first_height / range_set, or heights that are not strictly increasing; IBFT_E_TOOBIG n_ranges above
+ *   IBFT_HEIGHT_RANGES_MAX; IBFT_E_NOVALSET no family installed; IBFT_E_INVAL an entry of range_set >= n_sets.
+ *   A refused install leaves the old map in place.  Installing a family (ibft_set_validator_sets[_u256]) DROPS the map — its indices
+ *   named sets of the old family — behind the same wait for work in flight that lets the old family go; install the map
+ *   again after every family.  The map is two small device tables; the call also sizes and zeroes the per-set scratch of
+ *   the tally (8 bytes × (2 · power words + 1) per set, one bit per (set, member)) and waits for the context's stream.
+ * ibft_height_sets_info: ranges of the installed map, its first mapped height (lo) and the first height past its last
+ *   range (hi); 0, 0, 0 without a map.  Any pointer may be NULL; IBFT_E_INVAL for a NULL ctx.
+ *
+ * ibft_verify_senders_wire_sets: ibft_verify_senders_wire for a batch that mixes heights.  out_rows, out_set, out_vidx
+ *   (n entries each) and out_tally (n_sets entries, one per set of the family) may be NULL.
+ * Row rule: out_set[i] is the map's set for the height the walk decoded for row i, and −1 when the walks left the row
+ *   IBFT_WIRE_NEEDS_HOST, when the message has no View, or when its height is in no range.  A View that is present but empty
+ *   has height 0 and is mapped like any height.  With IBFT_FLAG_WIRE_RECODE the recoded row's height counts.  A row with
+ *   set −1 has verdict bit 0 and out_vidx −1 and is counted in no tally; it is
+ *   pre-flagged on the device IN FRONT of the verdict launch, so a peer that sprays far-future heights buys no ECDSA work.
+ * Defining property: for every set s, with R_s the subsequence of rows with out_set == s, the mask bits of those rows and
+ *   out_tally[s] (every field; quorum_* is the quorum of set s) are bit for bit what ibft_set_validators(set s) followed by
+ *   ibft_verify_senders_wire(R_s) returns; out_vidx is the index ibft_set_validators(set s) would give the sender, −1 where
+ *   the bit is 0 — cold and warm (IBFT_FLAG_PUBKEY_CACHE), for u64 and u256 families (low 128 bits of the power and the exact
+ *   has_quorum, as the block calls; ibft_last_tally_wide is not updated), with IBFT_FLAG_WIRE_RECODE on and off.  A set
+ *   without rows has its own quorum, zero counts and has_quorum = 0.  out_rows is what ibft_verify_senders_wire delivers
+ *   for the whole batch.  A sender in the union but not in its row's set is verified like any row and then loses its bit:
+ *   the rule of the block _sets calls.
+ * Errors: those of ibft_verify_senders_wire in its order, except that IBFT_E_NOVALSET means
+ *   "no family installed or no height map installed".  A call that fails with a device or
+ *   allocation error after its checks drops the height map (its scratch may be half used): install the map again.  The call never reads the context's single set and does not need one.  A refused call writes
+ *   nothing to any out buffer.
+ * Afterwards the rows are NOT a resident staged batch (ibft_seals_launch finds no rows), and
+ *   ibft_wire_stage_seals answers IBFT_E_INVAL, as it does whenever no senders-wire batch is resident: the columns hold verdicts against the union,
+ *   nothing the single-set seal pass could continue from.  ibft_wire_stats reports on this call like on any flat wire call.
+ *   Towards the two pipelines, ibft_last_dispatch, ibft_last_kernel_ms and the key cache the call behaves as
+ *   ibft_verify_senders_wire does (keys are learned over the union's slots, as by the block _sets calls).  No new
+ *   ibft_version(): a build without the symbols simply lacks them.
+ * MEASURED (tools/wire_sets_rate.py, profiles/r29_wire_sets_rate.txt): N = 4 096 COMMIT messages of two
+ * interleaved heights, V = 100, ten validators leave and ten join: one call 0.448 ms cold / 0.273 ms with known keys; per height
+ * ibft_set_validators + ibft_verify_senders_wire 1.012 / 0.504 ms (0.44 x / 0.54 x; the host split not counted); ONE
+ * ibft_verify_senders_wire over the batch, wrong for 200 rows, 0.417 / 0.240 ms (the price of the feature: + 0.03 ms).
+ * Out of scope: ibft_verify_messages_wire and the certificate calls under a family, a streamed form, the group calls, and
+ * tallies per (height, round, type).                                                                                    */
+#define IBFT_HEIGHT_RANGES_MAX 4096u
+int ibft_set_height_sets(ibft_ctx *ctx, size_t n_ranges, const uint64_t *first_height, const uint32_t *range_set);
+int ibft_height_sets_info(ibft_ctx *ctx, uint32_t *n_ranges, uint64_t *lo, uint64_t *hi);
+int ibft_verify_senders_wire_sets(ibft_ctx *ctx, const uint8_t *wire, const uint32_t *off, size_t n, uint64_t *out_mask,
+                                  ibft_wire_row_t *out_rows, int32_t *out_set, int32_t *out_vidx, ibft_tally_t *out_tally);
 
 /* a8 alone: HasQuorum over the rows whose bit is set in mask.                      */
 int ibft_tally(ibft_ctx *ctx, const uint8_t *sender20, const uint64_t *mask, size_t n,

@@ -1185,6 +1185,66 @@ func (c *Ctx) VerifySendersWire(wire []byte, off []uint32) ([]uint64, []WireRow,
 	return mask, rows[:n], tally(t), c.check(rc)
 }
 
+// SetHeightSets installs the height map of VerifySendersWireSets (ibft_set_height_sets): heights in
+// [firstHeight[k], firstHeight[k+1]) are judged under set rangeSet[k] of the family SetValidatorSets installed; every other
+// height has no set.  firstHeight needs one entry more than rangeSet and must increase strictly; empty slices clear the map.
+// SetValidatorSets DROPS the map (its indices named the old family): install it again after every family.
+func (c *Ctx) SetHeightSets(firstHeight []uint64, rangeSet []uint32) error {
+	if len(rangeSet) == 0 {
+		return c.check(C.ibft_set_height_sets(c.h, 0, nil, nil))
+	}
+	if len(firstHeight) != len(rangeSet)+1 {
+		return fmt.Errorf("%w: firstHeight needs one entry more than rangeSet", ErrFallback)
+	}
+	return c.check(C.ibft_set_height_sets(c.h, C.size_t(len(rangeSet)), (*C.uint64_t)(unsafe.Pointer(&firstHeight[0])),
+		(*C.uint32_t)(unsafe.Pointer(&rangeSet[0]))))
+}
+
+// HeightSetsInfo reports the installed height map (ibft_height_sets_info): its ranges, its first mapped height and the first
+// height past its last range; zeros without a map.
+func (c *Ctx) HeightSetsInfo() (ranges uint32, lo, hi uint64, err error) {
+	var nr C.uint32_t
+	var l, h C.uint64_t
+	err = c.check(C.ibft_height_sets_info(c.h, &nr, &l, &h))
+	return uint32(nr), uint64(l), uint64(h), err
+}
+
+// VerifySendersWireSets = VerifySendersWire for a receive-queue batch that mixes heights (ibft_verify_senders_wire_sets): every
+// message is judged under the validator set of ITS OWN height — IsValidValidator's definition (core/backend.go:41-45) — through
+// the map of SetHeightSets.  set[i] is the row's set (−1: the row needs the host, has no View, or its height is in no range; such
+// a row has verdict 0 and cost no signature check), vidx[i] the sender's index in that set (−1 where the bit is 0), tallies[s]
+// HasQuorum over the rows of set s.  Bit for bit what SetValidators(set s) + VerifySendersWire over the rows of set s returns.
+// Afterwards no batch is resident: StageWireSeals refuses.
+func (c *Ctx) VerifySendersWireSets(wire []byte, off []uint32) (mask []uint64, rows []WireRow, set, vidx []int32, tallies []Tally, err error) {
+	if len(off) == 0 {
+		return nil, nil, nil, nil, nil, fmt.Errorf("%w: off needs n + 1 entries", ErrFallback)
+	}
+	n := len(off) - 1
+	if len(wire) < int(off[n]) {
+		return nil, nil, nil, nil, nil, fmt.Errorf("%w: wire shorter than off says", ErrFallback)
+	}
+	ns, _, _, err := c.ValidatorSetsInfo() // the LIBRARY's count sizes the tallies
+	if err != nil {
+		return nil, nil, nil, nil, nil, err
+	}
+	mask = make([]uint64, (n+63)/64+1)
+	rows = make([]WireRow, n+1)
+	set = make([]int32, n+1)
+	vidx = make([]int32, n+1)
+	ct := make([]C.ibft_tally_t, ns+1)
+	rc := C.ibft_verify_senders_wire_sets(c.h, ptr8(wire), (*C.uint32_t)(unsafe.Pointer(&off[0])), C.size_t(n),
+		(*C.uint64_t)(unsafe.Pointer(&mask[0])), (*C.ibft_wire_row_t)(unsafe.Pointer(&rows[0])),
+		(*C.int32_t)(unsafe.Pointer(&set[0])), (*C.int32_t)(unsafe.Pointer(&vidx[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])))
+	if err = c.check(rc); err != nil {
+		return nil, nil, nil, nil, nil, err
+	}
+	tallies = make([]Tally, ns)
+	for s := range tallies {
+		tallies[s] = tally(ct[s])
+	}
+	return mask, rows[:n], set[:n], vidx[:n], tallies, nil
+}
+
 // StageWireSeals makes the COMMIT seals found by the last VerifySendersWire the resident seal batch;
 // follow with SealsRun (IsValidCommittedSeal without a second upload).
 func (c *Ctx) StageWireSeals() error { return c.check(C.ibft_wire_stage_seals(c.h)) }
