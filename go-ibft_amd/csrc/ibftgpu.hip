@@ -18,6 +18,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <random>
 #include <thread>
 #include <unordered_map>
 #include <string>
@@ -229,6 +230,18 @@ struct HeightSets {
   DevBuf d_first, d_range_set, d_row_set, d_acc, d_seen;
 };
 
+// What ibft_verify_senders_wire_views keeps behind the sets call's columns (kernels.hip.h: wire_views_*_kernel), sized lazily by
+// n and views_cap in the call itself: the two tables with the call's two words behind them (2 · slots + 2 words, set to all-ones
+// — EMPTY, "no error" — by ONE fill in front of every insert), the rows' slots, ranks and views, the stored words, and the
+// per-view accumulators, which every successful call leaves zero (acc_dirty: a call that failed midway may not have; the next
+// one clears them first).
+struct WireViews {
+  DevBuf d_tables, d_slots, d_rank, d_first, d_view, d_stored, d_acc, d_recs;
+  bool acc_dirty = true;
+  uint32_t salt = 0;        // per context, from the system's entropy: nobody outside can aim rows at one probe run
+  uint32_t slots_hook = 0;  // IBFT_WIRE_VIEWS_SLOTS (test hook): lowers the slot count, never below the first power of two above n
+};
+
 struct ibft_ctx {
   std::mutex mu;
   std::shared_ptr<DeviceShared> dev;   // the G table and the key cache of this context's device
@@ -353,6 +366,7 @@ struct ibft_ctx {
   uint32_t proposal_lane_rows = 8192;          // AUTO: the lane form from this many proposals of the longest one's length on
   ValFamily fam;                                     // ibft_set_validator_sets / the _sets block calls
   HeightSets hsets;                                  // ibft_set_height_sets / ibft_verify_senders_wire_sets
+  WireViews wviews;                                  // ibft_verify_senders_wire_views
   uint64_t valsets_bytes_max = 512ull << 20;         // IBFT_VALSETS_BYTES_MAX: the most a family's device tables may take
   uint64_t last_wide[ibftk::TALLY_SUM_WORDS] = {0};  // full-width power of the last fetched tally
   uint64_t height = 0;
@@ -1783,6 +1797,11 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   c->wire_recode = (c->flags & IBFT_FLAG_WIRE_RECODE) != 0;
   if (const char *e = getenv("IBFT_WIRE_RECODE")) c->wire_recode = atoi(e) != 0;
   if (const char *e = getenv("IBFT_CERT_DEDUP_SLOTS")) c->cert.dedup_slots_cap = (uint32_t)strtoul(e, nullptr, 10);
+  if (const char *e = getenv("IBFT_WIRE_VIEWS_SLOTS")) c->wviews.slots_hook = (uint32_t)strtoul(e, nullptr, 10);
+  {
+    std::random_device rd;
+    c->wviews.salt = (uint32_t)rd();
+  }
   if (getenv("IBFT_DIGEST_FUSION")) c->digest_in_gather = true;
   if (const char *e = getenv("IBFT_WAVE_ROWS_MAX")) c->wave_rows_max = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_PAIR_ROWS_MAX")) c->pair_rows_max = (uint32_t)strtoul(e, nullptr, 10);
@@ -1895,7 +1914,8 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_boff_nx, &c->d_praw, &c->d_proff, &c->d_pround,
                     &c->d_phash, &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
                     &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->hsets.d_first, &c->hsets.d_range_set, &c->hsets.d_row_set,
-                    &c->hsets.d_acc, &c->hsets.d_seen, &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
+                    &c->hsets.d_acc, &c->hsets.d_seen, &c->wviews.d_tables, &c->wviews.d_slots, &c->wviews.d_rank, &c->wviews.d_first,
+                    &c->wviews.d_view, &c->wviews.d_stored, &c->wviews.d_acc, &c->wviews.d_recs, &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
     release(*b);
   if (c->h_phash) (void)hipHostFree(c->h_phash);
   if (c->tstream) {
@@ -4311,9 +4331,103 @@ static int enqueue_wire_sets_tally(ibft_ctx *c, uint32_t n, uint64_t *out) {
   return IBFT_OK;
 }
 
+// What ibft_verify_senders_wire_views asks for on top of the sets call (null: the sets call itself).
+struct wire_views_out {
+  size_t views_cap;
+  int32_t *out_view;
+  uint64_t *out_stored;
+  ibft_wire_view_t *out_views;
+  uint32_t *out_n_views;
+};
+
+// Buffers of the views stage for n rows (before anything is enqueued: ensure() may free and allocate).
+static int ensure_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t slots) {
+  WireViews &w = c->wviews;
+  const size_t acc_bytes = (size_t)cap * (2 * c->fam.power_words + 1) * 8;
+  int rc;
+  if (acc_bytes > w.d_acc.cap) w.acc_dirty = true;  // a fresh allocation holds anything
+  if ((rc = ensure(c, w.d_tables, (size_t)slots * 8 + 8)) || (rc = ensure(c, w.d_slots, (size_t)n * 8)) || (rc = ensure(c, w.d_rank, (size_t)n * 4)) ||
+      (rc = ensure(c, w.d_first, (size_t)cap * 4)) || (rc = ensure(c, w.d_view, (size_t)n * 4)) ||
+      (rc = ensure(c, w.d_stored, (size_t)mask_words(n) * 8)) || (rc = ensure(c, w.d_acc, acc_bytes)) ||
+      (rc = ensure(c, w.d_recs, (size_t)cap * sizeof(ibft_wire_view_t))))
+    return rc;
+  return IBFT_OK;
+}
+
+// The views stage behind wire_sets_tally_kernel (same stream): one fill (tables to EMPTY), then insert, rank, tally, records.  Reads the final mask (d_mask_out), the rewritten index column, the rows' sets and the parsed rows.
+static int enqueue_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t slots) {
+  WireViews &w = c->wviews;
+  const ValFamily &f = c->fam;
+  const CertState &s = c->cert;
+  if (w.acc_dirty) HIPCHK(c, hipMemsetAsync(w.d_acc.p, 0, w.d_acc.cap, c->stream));
+  w.acc_dirty = true;  // until this call has come back clean
+  HIPCHK(c, hipMemsetAsync(w.d_tables.p, 0xFF, (size_t)slots * 8 + 8, c->stream));  // (the tables and the two words behind them)
+  ibftk::wire_views_args a{};
+  a.rows = (const wire::row_info *)c->d_wire_rows.p;
+  a.vidx = (const int32_t *)c->d_vidx.p;
+  a.row_set = (const int32_t *)c->hsets.d_row_set.p;
+  a.mask = (const uint64_t *)c->d_mask_out.p;
+  a.n = n;
+  a.views_cap = cap;
+  a.slots = slots;
+  a.salt = w.salt;
+  a.key_table = (uint32_t *)w.d_tables.p;
+  a.last_table = a.key_table + slots;
+  a.slot_key = (uint32_t *)w.d_slots.p;
+  a.slot_last = a.slot_key + n;
+  a.rank_of = (uint32_t *)w.d_rank.p;
+  a.first_row = (uint32_t *)w.d_first.p;
+  a.words = a.key_table + 2 * (size_t)slots;
+  a.out_view = (int32_t *)w.d_view.p;
+  a.out_stored = (uint64_t *)w.d_stored.p;
+  a.view_acc = (uint64_t *)w.d_acc.p;
+  a.out_views = (wviews::view_t *)w.d_recs.p;
+  a.fam.setidx = (const int32_t *)f.d_setidx.p;
+  a.fam.set_meta = (const uint2 *)f.d_meta.p;
+  a.fam.vpower32 = (const uint32_t *)f.d_power.p;
+  a.fam.quorum = (const uint64_t *)f.d_quorum.p;
+  a.fam.vtab = (const uint32_t *)c->d_vtab.p;  // (under family_view: the union's table, mask and size)
+  a.fam.vslot_mask = c->vslot_mask;
+  a.fam.n_union = c->n_validators;
+  a.fam.n_pieces = 2 * (int)f.power_words;
+  a.table = certd::proposer_table{s.prop_height, s.prop_first, (const uint8_t *)s.proposers.p, s.proposers.p ? s.prop_rounds : 0u};
+  const dim3 rows_grid((n + ibftk::WVIEWS_THREADS - 1) / ibftk::WVIEWS_THREADS), block(ibftk::WVIEWS_THREADS);
+  hipLaunchKernelGGL(ibftk::wire_views_insert_kernel, rows_grid, block, 0, c->stream, a);
+  hipLaunchKernelGGL(ibftk::wire_views_rank_kernel, dim3(1), dim3(1024), 0, c->stream, a);
+  if (f.power_words == 1)
+    hipLaunchKernelGGL(ibftk::wire_views_tally_kernel<1>, rows_grid, block, 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(ibftk::wire_views_tally_kernel<4>, rows_grid, block, 0, c->stream, a);
+  hipLaunchKernelGGL(ibftk::wire_views_records_kernel, dim3((cap + ibftk::WVIEWS_THREADS - 1) / ibftk::WVIEWS_THREADS), block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return IBFT_OK;
+}
+
+static int wire_sets_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, uint64_t *out_mask, ibft_wire_row_t *out_rows,
+                          int32_t *out_set, int32_t *out_vidx, ibft_tally_t *out_tally, const wire_views_out *vo);
+
 int ibft_verify_senders_wire_sets(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, uint64_t *out_mask,
                                   ibft_wire_row_t *out_rows, int32_t *out_set, int32_t *out_vidx, ibft_tally_t *out_tally) {
+  return wire_sets_impl(c, wire_bytes, off, n, out_mask, out_rows, out_set, out_vidx, out_tally, nullptr);
+}
+
+// The sets call plus one quorum record per (height, round, type, proposal hash): the sets call's checks in its order, with
+// views_cap == 0 for a batch that has rows among the argument checks in front.
+int ibft_verify_senders_wire_views(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t views_cap, uint64_t *out_mask,
+                                   ibft_wire_row_t *out_rows, int32_t *out_set, int32_t *out_vidx, ibft_tally_t *out_tally, int32_t *out_view,
+                                   uint64_t *out_stored, ibft_wire_view_t *out_views, uint32_t *out_n_views) {
+  static_assert(sizeof(ibft_wire_view_t) == sizeof(wviews::view_t) && sizeof(ibft_wire_view_t) == 128 && sizeof(ibft_wire_view_t) % 8 == 0, "ABI");
+  static_assert(sizeof(ibft_tally_t) == sizeof(wviews::tally_t) && offsetof(ibft_wire_view_t, tally) == offsetof(wviews::view_t, tally) &&
+                    offsetof(ibft_wire_view_t, proposal_hash) == offsetof(wviews::view_t, proposal_hash),
+                "ABI");
+  const wire_views_out vo{views_cap, out_view, out_stored, out_views, out_n_views};
+  return wire_sets_impl(c, wire_bytes, off, n, out_mask, out_rows, out_set, out_vidx, out_tally, &vo);
+}
+
+static int wire_sets_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, uint64_t *out_mask, ibft_wire_row_t *out_rows,
+                          int32_t *out_set, int32_t *out_vidx, ibft_tally_t *out_tally, const wire_views_out *vo) {
   if (!c || (n && (!off || !out_mask))) return IBFT_E_INVAL;
+  if (vo && n && !vo->views_cap) return IBFT_E_INVAL;
   if (!offsets_ok(off, n) || !bytes_ok(off, n, wire_bytes)) return IBFT_E_INVAL;
   ctx_lock lk(c);
   if (n > c->max_rows) return IBFT_E_TOOBIG;
@@ -4326,6 +4440,9 @@ int ibft_verify_senders_wire_sets(ibft_ctx *c, const uint8_t *wire_bytes, const 
   const size_t wbytes = n ? off[n] : 0;
   if ((rc = ensure_wire_buffers(c, wbytes))) return rc;
   if ((rc = ensure_block_records(c, c->brec, ns))) return rc;
+  const uint32_t vcap = vo ? (uint32_t)std::min<size_t>(vo->views_cap, n) : 0u;  // (a cap above n behaves as n)
+  const uint32_t vslots = vo && nr ? wviews::table_slots(nr, c->wviews.slots_hook) : 0u;
+  if (vo && nr && (rc = ensure_wire_views(c, nr, vcap, vslots))) return rc;
   if (wbytes) HIPCHK(c, hipMemcpyAsync(c->d_payload.p, wire_bytes, wbytes, hipMemcpyHostToDevice, c->stream));
   if ((rc = upload(c, c->d_off, off, (n + 1) * 4))) return rc;
   // rows judged against the union are nothing ibft_seals_launch or ibft_wire_stage_seals could re-judge under the single set
@@ -4361,13 +4478,37 @@ int ibft_verify_senders_wire_sets(ibft_ctx *c, const uint8_t *wire_bytes, const 
     if (out_rows) HIPCHK(c, hipMemcpyAsync(out_rows, c->d_wire_rows.p, n * sizeof(ibft_wire_row_t), hipMemcpyDeviceToHost, c->stream));
     if (out_set) HIPCHK(c, hipMemcpyAsync(out_set, h.d_row_set.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out_vidx) HIPCHK(c, hipMemcpyAsync(out_vidx, c->d_vidx.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    uint32_t vwords[2] = {0, 0};  // {n_views, all-ones unless a table was exhausted}
+    if (vo) {
+      WireViews &w = c->wviews;
+      if ((rc = enqueue_wire_views(c, nr, vcap, vslots))) return rc;
+      HIPCHK(c, hipMemcpyAsync(vwords, (const uint32_t *)w.d_tables.p + 2 * (size_t)vslots, 8, hipMemcpyDeviceToHost, c->stream));
+      if (vo->out_view) HIPCHK(c, hipMemcpyAsync(vo->out_view, w.d_view.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+      if (vo->out_stored) HIPCHK(c, hipMemcpyAsync(vo->out_stored, w.d_stored.p, mw * 8, hipMemcpyDeviceToHost, c->stream));
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->cache_on) {  // keys these rows taught the device → tables (the next call is warm)
       const uint32_t *lw = reinterpret_cast<const uint32_t *>(c->h_tally + 4);
       if ((rc = build_new_tables(c, lw[0], lw[1]))) return rc;
     }
+    if (vo) {
+      if (vwords[1] != 0xFFFFFFFFu) {  // (more keys than slots cannot happen: table_slots gives more slots than rows)
+        c->last_error = "ibft_verify_senders_wire_views: a table was exhausted";
+        return IBFT_E_HIP;
+      }
+      c->wviews.acc_dirty = false;  // the records kernel zeroed what the tally added
+      if (vo->out_n_views) *vo->out_n_views = vwords[0];
+      // the records that exist — a handful in an honest batch, where views_cap is sized for the worst — once their number is known
+      const size_t filled = std::min(vwords[0], vcap);
+      if (vo->out_views && filled) {
+        HIPCHK(c, hipMemcpyAsync(vo->out_views, c->wviews.d_recs.p, filled * sizeof(ibft_wire_view_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+      }
+    }
     memcpy(out_mask, c->h_mask, mw * 8);
     if (nr & 63) out_mask[mw - 1] &= (~0ull) >> (64 - (nr & 63));
+  } else if (vo && vo->out_n_views) {
+    *vo->out_n_views = 0;
   }
   fill_block_tallies(out_tally, ns, nr, c->brec.h, [&](uint32_t s) -> const uint64_t * { return &c->fam.quorum[(size_t)s * ibftk::TALLY_SUM_WORDS]; });
   c->wire.parsed = true;

@@ -52,6 +52,7 @@
 #include "cert_wave_dev.h"
 #include "cert_verdict_dev.h"
 #include "cert_decide_dev.h"
+#include "wire_views_dev.h"
 #include "cert_dedup_dev.h"
 
 namespace ibftk {
@@ -2445,6 +2446,135 @@ __global__ void __launch_bounds__(WSETS_THREADS) wire_sets_tally_kernel(wire_set
     }
   }
   if (tid == 0) __hip_atomic_store(a.acc + TALLY_MAX_PIECES + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- the live route's quorum records (ibft_verify_senders_wire_views; the row bodies: wire_views_dev.h) ---------------------
+// Four launches behind wire_sets_tally_kernel on the same stream; each phase that needs every row of the one before it is a
+// launch of its own, so nothing here waits for another workgroup.
+//   insert   a thread per row: a valid row (final mask bit) goes into the key table (lowest row of its key) and the last table
+//            (highest row of its view and sender); its two slots are kept.  A row that exhausts a table raises *err.
+//   rank     ONE workgroup: representatives (key_table[slot] == row) ranked in ascending row order — cert_scan_kernel's
+//            shape (a run of rows per thread, a scan of the 1 024 sums through LDS); rank_of[rep], first_row[rank] for the
+//            views that fit, the number of keys.
+//   tally    a thread per row: out_view, the stored bit (one ballot per wavefront is one word of out_stored), and the view's
+//            accumulators — rows | stored << 32 and, for stored rows, the member's 2·PW pieces.  A wavefront reduces one view
+//            per turn (the view of the first lane that still waits), at most WVIEWS_TURNS turns; whoever still waits then — a
+//            hostile batch puts 64 views into a wavefront — adds for itself: O(n) whatever the number of views.
+//   records  a thread per view below min(n_views, views_cap): wviews::view_record, then the view's accumulators are zeroed —
+//            all scratch but the tables (set to EMPTY, with the call's two words behind them, by one fill in front of every
+//            insert) is zero again when the call returns.
+constexpr int WVIEWS_THREADS = 256, WVIEWS_TURNS = 4;
+struct wire_views_args {
+  const wire::row_info *rows;
+  const int32_t *vidx, *row_set;  // index in the row's set / the row's set, as wire_sets_tally_kernel left them
+  const uint64_t *mask;           // the final verdict words
+  uint32_t n, views_cap, slots, salt;
+  uint32_t *key_table, *last_table;  // slots words each
+  uint32_t *slot_key, *slot_last;    // n
+  uint32_t *rank_of;                 // n: rank of a representative
+  uint32_t *first_row;               // min(n, views_cap): the representative of view v
+  uint32_t *words;                   // behind the tables, all-ones like them at the start: [0] ← n_views, [1] ← 0 when a table was exhausted
+  int32_t *out_view;                 // n
+  uint64_t *out_stored;              // ⌈n / 64⌉
+  uint64_t *view_acc;                // min(n, views_cap) × (2·PW + 1), zero between calls
+  wviews::view_t *out_views;         // min(n, views_cap)
+  wviews::family fam;
+  certd::proposer_table table;
+};
+__global__ void __launch_bounds__(WVIEWS_THREADS) wire_views_insert_kernel(wire_views_args a) {
+  const uint32_t row = blockIdx.x * WVIEWS_THREADS + threadIdx.x;
+  if (row >= a.n) return;
+  const bool valid = (a.mask[row >> 6] >> (row & 63)) & 1ull;
+  const wviews::row_slots s = wviews::insert_row(wviews::columns{a.rows, a.vidx}, row, valid, a.key_table, a.last_table, a.slots, a.salt);
+  a.slot_key[row] = s.key;
+  a.slot_last[row] = s.last;
+  if (s.key == wviews::UNPLACED || s.last == wviews::UNPLACED) atomicAnd(a.words + 1, 0u);
+}
+__global__ void __launch_bounds__(1024) wire_views_rank_kernel(wire_views_args a) {
+  __shared__ uint32_t part[1024];
+  const uint32_t t = threadIdx.x, per = (a.n + 1023u) / 1024u;
+  const uint32_t b = t * per < a.n ? t * per : a.n, e = b + per < a.n ? b + per : a.n;
+  uint32_t sum = 0;
+  for (uint32_t i = b; i < e; i++) sum += wviews::is_rep(a.key_table, a.slot_key[i], i) ? 1u : 0u;
+  part[t] = sum;
+  __syncthreads();
+  for (uint32_t o = 1; o < 1024u; o <<= 1) {
+    const uint32_t v = t >= o ? part[t - o] : 0u;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[t] - sum;
+  for (uint32_t i = b; i < e; i++) {
+    if (!wviews::is_rep(a.key_table, a.slot_key[i], i)) continue;
+    a.rank_of[i] = run;
+    if (run < a.views_cap) a.first_row[run] = i;
+    run++;
+  }
+  if (t == 1023u) a.words[0] = part[1023];
+}
+template <int PW>
+__global__ void __launch_bounds__(WVIEWS_THREADS) wire_views_tally_kernel(wire_views_args a) {
+  constexpr int NP = 2 * PW;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t row = blockIdx.x * WVIEWS_THREADS + tid;
+  const uint32_t sk = row < a.n ? a.slot_key[row] : wviews::SKIP;
+  const bool valid = sk < wviews::SKIP;
+  int32_t v = wviews::VIEW_NONE;
+  bool stored = false;
+  if (valid) {
+    v = wviews::view_of_rank(a.rank_of[a.key_table[sk]], a.views_cap);
+    stored = wviews::is_stored(a.last_table, a.slot_last[row], row);  // a row beyond the cap still supersedes
+  }
+  if (row < a.n) a.out_view[row] = v;
+  const uint64_t sw = __ballot(stored ? 1 : 0);
+  if (lane == 0 && (row & ~63u) < a.n) a.out_stored[row >> 6] = sw;
+  bool pend = v >= 0;
+  uint32_t pw[NP];
+  {
+    const bool adds = pend && stored;
+    const uint32_t entry = adds ? a.fam.set_meta[a.row_set[row]].x + (uint32_t)a.vidx[row] : 0u;
+#pragma unroll
+    for (int k = 0; k < NP; k++) pw[k] = adds ? a.fam.vpower32[(size_t)entry * NP + k] : 0u;
+  }
+  for (int turn = 0; turn < WVIEWS_TURNS; turn++) {  // (wave-uniform: every lane takes every turn)
+    const uint64_t todo = __ballot(pend ? 1 : 0);
+    if (!todo) break;
+    const int leader = __ffsll((long long)todo) - 1;
+    const int32_t lv = __shfl(v, leader, 64);
+    const bool mine = pend && v == lv;
+    uint64_t *acc = a.view_acc + (size_t)lv * (NP + 1);
+    const uint64_t cnt = wave_sum_u64(mine ? (1ull | ((uint64_t)(stored ? 1u : 0u) << 32)) : 0ull);
+    if (cnt >> 32) {  // (wave-uniform) a stored row among them: the pieces
+#pragma unroll
+      for (int k = 0; k < NP; k++) {
+        const uint64_t sum = wave_sum_u64(mine ? (uint64_t)pw[k] : 0ull);
+        if ((int)lane == leader && sum) atomicAdd(reinterpret_cast<unsigned long long *>(acc + k), (unsigned long long)sum);
+      }
+    }
+    if ((int)lane == leader) atomicAdd(reinterpret_cast<unsigned long long *>(acc + NP), (unsigned long long)cnt);
+    if (mine) pend = false;
+  }
+  if (pend) {  // more views in this wavefront than turns: the lane adds for itself
+    uint64_t *acc = a.view_acc + (size_t)v * (NP + 1);
+    if (stored) {
+#pragma unroll
+      for (int k = 0; k < NP; k++)
+        if (pw[k]) atomicAdd(reinterpret_cast<unsigned long long *>(acc + k), (unsigned long long)pw[k]);
+    }
+    atomicAdd(reinterpret_cast<unsigned long long *>(acc + NP), 1ull | ((uint64_t)(stored ? 1u : 0u) << 32));
+  }
+}
+__global__ void __launch_bounds__(WVIEWS_THREADS) wire_views_records_kernel(wire_views_args a) {
+  const uint32_t v = blockIdx.x * WVIEWS_THREADS + threadIdx.x;
+  const uint32_t n_views = a.words[0];
+  if (v >= n_views || v >= a.views_cap) return;
+  uint64_t *acc = a.view_acc + (size_t)v * (a.fam.n_pieces + 1);
+  wviews::view_t rec;
+  wviews::view_record(rec, a.first_row[v], acc, wviews::columns{a.rows, a.vidx}, a.row_set, a.out_view, (int32_t)v, a.fam, a.table, a.last_table,
+                      a.slots, a.salt);
+  a.out_views[v] = rec;
+  for (int k = 0; k <= a.fam.n_pieces; k++) acc[k] = 0;
 }
 
 // ---- certificates: one record per carrier (ibft_judge_certificates_wire; the rules: cert_verdict_dev.h) ---------------------

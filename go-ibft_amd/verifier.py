@@ -58,7 +58,7 @@ EXPORTS = [
     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
     "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire",
-    "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets",
+    "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets", "ibft_verify_senders_wire_views",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
@@ -77,7 +77,7 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
                     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
                     "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire",
-                    "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets"}
+                    "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets", "ibft_verify_senders_wire_views"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
 ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
@@ -112,6 +112,13 @@ CERT_DECISION = np.dtype([("valid_pc", "i1"), ("round_change", "i1"), ("proposal
 assert CERT_DECISION.itemsize == 64
 CERT_DECISION_HAS_PREPARED = 1
 PROPOSER_ROUNDS_MAX = 4096   # IBFT_PROPOSER_ROUNDS_MAX
+# ibft_wire_view_t (include/ibftgpu.h); tally: ibft_tally_t, field for field the Tally structure
+WIRE_VIEW = np.dtype([("height", "<u8"), ("round", "<u8"), ("set", "<i4"), ("first_row", "<u4"), ("rows", "<u4"), ("stored_rows", "<u4"),
+                      ("type", "u1"), ("hash_len", "u1"), ("prepare_rule", "u1"), ("pad", "u1", 5), ("proposal_hash", "u1", 32),
+                      ("tally", [("quorum_lo", "<u8"), ("quorum_hi", "<u8"), ("power_lo", "<u8"), ("power_hi", "<u8"),
+                                 ("valid_rows", "<u4"), ("distinct_senders", "<u4"), ("has_quorum", "<u4"), ("shard_overlap", "<u4"),
+                                 ("proposer_rows", "<u4"), ("reserved", "<u4")])])
+assert WIRE_VIEW.itemsize == 128
 
 
 class GpuUnavailable(RuntimeError):
@@ -257,6 +264,7 @@ def load_library() -> C.CDLL:
         "ibft_set_height_sets": [vp, C.c_size_t, vp, vp],
         "ibft_height_sets_info": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
         "ibft_verify_senders_wire_sets": [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp],
+        "ibft_verify_senders_wire_views": [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_uint32)],
         "ibft_block_seals_collect": [vp, vp, vp],
         "ibft_block_seals_pending": [vp] + [C.POINTER(C.c_uint32)] * 3,
         "ibft_block_seals_collect_ex": [vp, vp, vp, vp, vp, vp],
@@ -986,6 +994,34 @@ class BatchVerifier:
                                                         _p(rset), _p(vidx), tal), "ibft_verify_senders_wire_sets")
         self._staged = 0
         return mask_to_bool(mask, n), rows, rset[:n], vidx[:n], [tal[s] for s in range(ns)]
+
+    def verify_senders_wire_views(self, wire, off, views_cap: int, want_rows: bool = True):
+        """ibft_verify_senders_wire_views: verify_senders_wire_sets plus one quorum record per (height, round, type, proposal
+        hash) with a valid message in the batch → (verdict bool[n], rows or None, set int32[n], vidx int32[n], Tally
+        list[n_sets] — byte for byte the sets call's —, view int32[n] (-1: not valid, -2: its view did not fit views_cap),
+        stored bool[n] — the rows a Messages store fed the batch in row order still holds —, views WIRE_VIEW[min(n_views,
+        views_cap)], n_views)"""
+        self._need("ibft_verify_senders_wire_views")
+        wb = _bytes_col(wire)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        n = len(off) - 1
+        ns = self.validator_sets_info()[0]
+        cap = min(int(views_cap), n)
+        mask = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        stored = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        rows = np.zeros(n, dtype=WIRE_ROW) if want_rows else None
+        rset = np.full(max(n, 1), -1, dtype=np.int32)
+        vidx = np.full(max(n, 1), -1, dtype=np.int32)
+        view = np.full(max(n, 1), -1, dtype=np.int32)
+        views = np.zeros(max(cap, 1), dtype=WIRE_VIEW)
+        nv = C.c_uint32(0)
+        tal = (Tally * max(ns, 1))()
+        self._chk(self._L.ibft_verify_senders_wire_views(self._h, _p(wb), _p(off), n, int(views_cap), _p(mask),
+                                                         _p(rows) if (n and want_rows) else None, _p(rset), _p(vidx), tal, _p(view),
+                                                         _p(stored), _p(views), C.byref(nv)), "ibft_verify_senders_wire_views")
+        self._staged = 0
+        return (mask_to_bool(mask, n), rows, rset[:n], vidx[:n], [tal[s] for s in range(ns)], view[:n], mask_to_bool(stored, n),
+                views[:min(nv.value, cap)], nv.value)
 
     def verify_messages_wire(self, wire, off, height: int, round_: int, raw: bytes | None = None, proposal_round: int | None = None,
                              digest32: bytes | None = None, want_rows: bool = True, proposer: bytes | None = None):

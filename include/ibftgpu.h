@@ -716,13 +716,82 @@ int ibft_wire_stats(ibft_ctx *ctx, uint32_t *rows, uint32_t *recoded_rows, uint3
  * interleaved heights, V = 100, ten validators leave and ten join: one call 0.448 ms cold / 0.273 ms with known keys; per height
  * ibft_set_validators + ibft_verify_senders_wire 1.012 / 0.504 ms (0.44 x / 0.54 x; the host split not counted); ONE
  * ibft_verify_senders_wire over the batch, wrong for 200 rows, 0.417 / 0.240 ms (the price of the feature: + 0.03 ms).
- * Out of scope: ibft_verify_messages_wire and the certificate calls under a family, a streamed form, the group calls, and
- * tallies per (height, round, type).                                                                                    */
+ * Out of scope: ibft_verify_messages_wire and the certificate calls under a family, a streamed form and the group calls.
+ * (Tallies per (height, round, type, hash): ibft_verify_senders_wire_views, below.)                                      */
 #define IBFT_HEIGHT_RANGES_MAX 4096u
 int ibft_set_height_sets(ibft_ctx *ctx, size_t n_ranges, const uint64_t *first_height, const uint32_t *range_set);
 int ibft_height_sets_info(ibft_ctx *ctx, uint32_t *n_ranges, uint64_t *lo, uint64_t *hi);
 int ibft_verify_senders_wire_sets(ibft_ctx *ctx, const uint8_t *wire, const uint32_t *off, size_t n, uint64_t *out_mask,
                                   ibft_wire_row_t *out_rows, int32_t *out_set, int32_t *out_vidx, ibft_tally_t *out_tally);
+
+/* ---- the sets call plus ONE QUORUM RECORD per (height, round, type, proposal hash) of the batch -------------------------
+ * The tallies of ibft_verify_senders_wire_sets are per SET; the reference asks per view and hash.  It keeps messages in
+ * messages.Messages keyed by type, height, round and sender — a sender's later message REPLACES the earlier one
+ * (messages/messages.go:64) — and asks HasQuorum / HasPrepareQuorum over GetValidMessages(view, type, isValid) on every
+ * arriving message (core/ibft.go:1113-1121), in handlePrepare (:855-873, isValid = "names my proposal's hash") and in
+ * handleCommit (:931-946).  ibft_verify_senders_wire_views answers that for every view and hash of a receive-queue batch
+ * in the same call, on the device, and tells which rows a Messages store fed the batch in row order would still hold.
+ *
+ * out_mask, out_rows, out_set, out_vidx, out_tally: byte for byte what ibft_verify_senders_wire_sets returns for the same
+ *   batch (its kernels run unchanged, in its order; the new work follows on the same stream before the one wait).
+ * Definitions: a row is VALID when its final verdict bit is 1 (a member of its height's set, out_vidx >= 0); only PREPARE
+ *   and COMMIT rows can be.  A valid row's VIEW is (height, round, type) of its parsed row, its KEY the view plus
+ *   (hash_len, proposal_hash[0 .. hash_len)).
+ * out_stored (a bit per row, ceil(n / 64) words; bits past n are 0): bit i is set iff row i is valid and no valid row
+ *   j > i has the same view and the same sender (out_vidx under the same set) — the messages the store holds after
+ *   AddMessage of every valid row in row order.  Per VIEW, not per key: a later message with another hash replaces too.
+ * Views: the keys ordered by their lowest valid row, ascending; view v is the v-th key.  *out_n_views is the number of
+ *   distinct keys and may exceed views_cap.  out_view[i] (n entries) is -1 for a row that is not valid, v for a valid row
+ *   of view v < views_cap, -2 for a valid row whose view did not fit; -2 rows still supersede earlier rows of their
+ *   sender in out_stored.  A views_cap above n behaves as n.
+ * out_views: min(*out_n_views, views_cap, n) records, one per view (the caller provides min(views_cap, n) entries):
+ *   height, round, type, hash_len, proposal_hash (bytes past hash_len zero) of the view's first row; set — the set of that
+ *   height; first_row; rows — the valid rows with out_view == v; stored_rows — those of them with the stored bit;
+ *   prepare_rule; tally.
+ * Defining property of tally: with S_v the From column of the rows with out_view == v and the stored bit, in row order, it
+ *   is field for field what ibft_set_validators(set) followed by ibft_tally(S_v, all-ones mask) returns — u64 and u256
+ *   families (low 128 bits of the power, exact has_quorum), cold and warm, IBFT_FLAG_WIRE_RECODE on and off.  For a
+ *   PREPARE record whose height is the height of the proposer table (ibft_set_proposers) and whose round lies inside it,
+ *   prepare_rule = 1 and tally is instead what ibft_tally_prepare(S_v, all-ones, table[round]) returns — HasPrepareQuorum
+ *   (validator_manager.go:99-127): the proposer's seat joins, a stored row FROM the proposer voids has_quorum and is
+ *   counted in proposer_rows.  Otherwise prepare_rule = 0 and the plain rule holds.  The proposalMessage == nil case stays
+ *   with the caller, as everywhere else.  A COMMIT record answers "who sent a valid COMMIT naming this hash as their last
+ *   word in this view"; the committed seals of those rows stay with the caller (ibft_verify_seals over the stored rows).
+ * Every output is a pure function of the batch, the family, the map, the proposer table and views_cap: nothing depends on
+ *   the order threads arrive in, on the size of the device's tables or on the context's hash salt.
+ * Errors: those of ibft_verify_senders_wire_sets in its order; views_cap == 0 with n > 0 is IBFT_E_INVAL and is checked
+ *   with the argument checks in front — after "NULL ctx / NULL off / NULL out_mask", before the offsets are looked at, so
+ *   before IBFT_E_TOOBIG and IBFT_E_NOVALSET.  out_mask is required when n > 0; every other out pointer may be NULL.  A
+ *   refused call writes nothing.  n = 0: *out_n_views = 0 and out_tally as the sets call fills it.  Side effects (no
+ *   resident staged batch, ibft_wire_stats, key cache, pipelines, the height map dropped by a call that fails midway):
+ *   those of the sets call.  No new ibft_version().
+ * The device groups through two open-addressing tables of row numbers (at least 2 n slots each, sized in the call) under a
+ *   per-context random salt; scratch is sized by n and views_cap.  IBFT_WIRE_VIEWS_SLOTS (environment, tests only) lowers
+ *   the slot count, never below the smallest power of two above n.
+ * MEASURED (tools/wire_views_rate.py, profiles/r30_wire_views_rate.txt): N = 4 096 PREPARE and COMMIT
+ * messages of two interleaved heights, V = 100, ten validators changed: 0.579 ms cold / 0.415 ms with known keys for six
+ * views, 0.584 / 0.425 ms for 2 006 views (one validator's 2 000 PREPAREs each in a round of its own); the sets call alone
+ * 0.451 / 0.288 ms (the records: + 0.13 ms); rows read back, grouped on the host, ibft_set_validators per height and
+ * ibft_tally per record: 9.5 ms for six views (8.7 ms of it the tool's host pass in Python), 69 ms for 2 006.
+ * Out of scope: checking the COMMIT seals of a record's rows in the same verdict launch (the caller runs
+ * ibft_verify_seals over the stored rows), a streamed form, a group form.                                              */
+typedef struct {
+  uint64_t height, round; /* the view's                                                             */
+  int32_t set;            /* the set of the family the view's height is judged under                */
+  uint32_t first_row;     /* the lowest valid row of the key                                        */
+  uint32_t rows;          /* valid rows with out_view == v                                          */
+  uint32_t stored_rows;   /* ... of them with the stored bit: the length of S_v                     */
+  uint8_t type;           /* IbftMessage.type: 1 PREPARE, 2 COMMIT                                  */
+  uint8_t hash_len;       /* proposal hash bytes present (<= 32)                                    */
+  uint8_t prepare_rule;   /* 1: tally follows HasPrepareQuorum with the table's proposer            */
+  uint8_t pad[5];
+  uint8_t proposal_hash[32];
+  ibft_tally_t tally;
+} ibft_wire_view_t; /* 128 bytes */
+int ibft_verify_senders_wire_views(ibft_ctx *ctx, const uint8_t *wire, const uint32_t *off, size_t n, size_t views_cap,
+                                   uint64_t *out_mask, ibft_wire_row_t *out_rows, int32_t *out_set, int32_t *out_vidx,
+                                   ibft_tally_t *out_tally, int32_t *out_view, uint64_t *out_stored,
+                                   ibft_wire_view_t *out_views, uint32_t *out_n_views);
 
 /* a8 alone: HasQuorum over the rows whose bit is set in mask.                      */
 int ibft_tally(ibft_ctx *ctx, const uint8_t *sender20, const uint64_t *mask, size_t n,

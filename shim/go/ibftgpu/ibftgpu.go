@@ -1245,6 +1245,108 @@ func (c *Ctx) VerifySendersWireSets(wire []byte, off []uint32) (mask []uint64, r
 	return mask, rows[:n], set[:n], vidx[:n], tallies, nil
 }
 
+// WireView is one quorum record of VerifySendersWireViews (ibft_wire_view_t): a (height, round, type, proposal hash) that has a
+// valid message in the batch.  Tally is HasQuorum — for a PREPARE view the proposer table covers (PrepareRule) HasPrepareQuorum
+// with the table's proposer — over the view's STORED rows: the messages a messages.Messages store fed the batch in row order
+// still holds under this hash.
+type WireView struct {
+	Height, Round uint64
+	Set           int32  // the set of the family the view's height is judged under
+	FirstRow      uint32 // the lowest valid row of the key
+	Rows          uint32 // valid rows of the view
+	StoredRows    uint32 // … of them stored: the rows Tally counts
+	Type          uint8  // 1 PREPARE, 2 COMMIT
+	HashLen       uint8
+	PrepareRule   bool
+	ProposalHash  [32]byte
+	Tally         Tally
+}
+
+// WireViewNone and WireViewOver are the two negative values of the view column: the row is not valid / its view did not fit
+// viewsCap (the row still supersedes earlier rows of its sender).
+const (
+	WireViewNone = int32(-1)
+	WireViewOver = int32(-2)
+)
+
+// WireViewsResult is what VerifySendersWireViews returns: the five outputs of VerifySendersWireSets, byte for byte, then the
+// view of every row, the stored bits (the rows a Messages store would hold after AddMessage of every valid row in row order:
+// per view, a sender's later message replaces the earlier one, whatever hash it names), the records of the first viewsCap
+// views and the number of views in the batch, which may exceed viewsCap.
+type WireViewsResult struct {
+	Mask      []uint64
+	Rows      []WireRow
+	Set, Vidx []int32
+	Tallies   []Tally
+	View      []int32
+	Stored    []uint64
+	Views     []WireView
+	NViews    uint32
+}
+
+// VerifySendersWireViews = VerifySendersWireSets plus one quorum record per (height, round, type, proposal hash) that has a valid
+// message in the batch (ibft_verify_senders_wire_views): what core/ibft.go:1113-1121, handlePrepare (:855-873) and handleCommit
+// (:931-946) ask of GetValidMessages, for every view of a receive-queue batch in one call.  Views are numbered by their lowest
+// valid row.  A PREPARE record follows HasPrepareQuorum when SetProposers covers its height and round; the proposalMessage ==
+// nil case and the committed seals of a COMMIT record's rows stay with the caller.  viewsCap must be positive for a batch that
+// has rows; a cap above the row count behaves as the row count.
+func (c *Ctx) VerifySendersWireViews(wire []byte, off []uint32, viewsCap int) (*WireViewsResult, error) {
+	if len(off) == 0 {
+		return nil, fmt.Errorf("%w: off needs n + 1 entries", ErrFallback)
+	}
+	n := len(off) - 1
+	if len(wire) < int(off[n]) {
+		return nil, fmt.Errorf("%w: wire shorter than off says", ErrFallback)
+	}
+	if viewsCap < 0 || (n > 0 && viewsCap == 0) {
+		return nil, fmt.Errorf("%w: viewsCap must be positive", ErrFallback)
+	}
+	ns, _, _, err := c.ValidatorSetsInfo() // the LIBRARY's count sizes the tallies
+	if err != nil {
+		return nil, err
+	}
+	vcap := viewsCap
+	if vcap > n {
+		vcap = n
+	}
+	r := &WireViewsResult{Mask: make([]uint64, (n+63)/64+1), Rows: make([]WireRow, n+1), Set: make([]int32, n+1), Vidx: make([]int32, n+1),
+		View: make([]int32, n+1), Stored: make([]uint64, (n+63)/64+1)}
+	ct := make([]C.ibft_tally_t, ns+1)
+	cv := make([]C.ibft_wire_view_t, vcap+1)
+	var nv C.uint32_t
+	rc := C.ibft_verify_senders_wire_views(c.h, ptr8(wire), (*C.uint32_t)(unsafe.Pointer(&off[0])), C.size_t(n), C.size_t(viewsCap),
+		(*C.uint64_t)(unsafe.Pointer(&r.Mask[0])), (*C.ibft_wire_row_t)(unsafe.Pointer(&r.Rows[0])),
+		(*C.int32_t)(unsafe.Pointer(&r.Set[0])), (*C.int32_t)(unsafe.Pointer(&r.Vidx[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])),
+		(*C.int32_t)(unsafe.Pointer(&r.View[0])), (*C.uint64_t)(unsafe.Pointer(&r.Stored[0])), (*C.ibft_wire_view_t)(unsafe.Pointer(&cv[0])), &nv)
+	if err = c.check(rc); err != nil {
+		return nil, err
+	}
+	r.Rows, r.Set, r.Vidx, r.View = r.Rows[:n], r.Set[:n], r.Vidx[:n], r.View[:n]
+	r.Mask, r.Stored = r.Mask[:(n+63)/64], r.Stored[:(n+63)/64]
+	r.Tallies = make([]Tally, ns)
+	for s := range r.Tallies {
+		r.Tallies[s] = tally(ct[s])
+	}
+	r.NViews = uint32(nv)
+	filled := int(r.NViews)
+	if filled > vcap {
+		filled = vcap
+	}
+	r.Views = make([]WireView, filled)
+	for v := range r.Views {
+		w := cv[v]
+		o := &r.Views[v]
+		o.Height, o.Round, o.Set = uint64(w.height), uint64(w.round), int32(w.set)
+		o.FirstRow, o.Rows, o.StoredRows = uint32(w.first_row), uint32(w.rows), uint32(w.stored_rows)
+		o.Type, o.HashLen, o.PrepareRule = uint8(w._type), uint8(w.hash_len), w.prepare_rule != 0
+		for i := range o.ProposalHash {
+			o.ProposalHash[i] = byte(w.proposal_hash[i])
+		}
+		o.Tally = tally(w.tally)
+	}
+	return r, nil
+}
+
 // StageWireSeals makes the COMMIT seals found by the last VerifySendersWire the resident seal batch;
 // follow with SealsRun (IsValidCommittedSeal without a second upload).
 func (c *Ctx) StageWireSeals() error { return c.check(C.ibft_wire_stage_seals(c.h)) }
