@@ -217,6 +217,12 @@ struct WireBatch {
   uint32_t rows = 0;
   bool columns = false;  // ibft_wire_stage_seals: the senders-wire batch is still the resident one
   bool parsed = false;   // ibft_wire_stats: its parse results are still in d_wire_rows
+  // ibft_wire_seal_stats: the two counts of the last ibft_verify_messages_wire_views (zero once any other wire call has begun)
+  uint32_t commit_rows = 0, seal_rows = 0;
+  void begin() {  // a wire call takes the columns over
+    parsed = false;
+    commit_rows = seal_rows = 0;
+  }
 };
 
 // The height map of the live route under a family (ibft_set_height_sets) and what ibft_verify_senders_wire_sets keeps next to
@@ -235,8 +241,12 @@ struct HeightSets {
 // — EMPTY, "no error" — by ONE fill in front of every insert), the rows' slots, ranks and views, the stored words, and the
 // per-view accumulators, which every successful call leaves zero (acc_dirty: a call that failed midway may not have; the next
 // one clears them first).
+// ibft_verify_messages_wire_views adds, allocated by its first call: the rows' flags, seal rows and their source rows, the
+// call's three words (kernels.hip.h: wire_seals_args) and the seal mask.  Its accumulators are one word per view longer — the
+// same buffer, zero between calls whichever of the two calls ran.
 struct WireViews {
   DevBuf d_tables, d_slots, d_rank, d_first, d_view, d_stored, d_acc, d_recs;
+  DevBuf d_sflags, d_seal_row, d_seal_src, d_seal_words, d_seal_mask;
   bool acc_dirty = true;
   uint32_t salt = 0;        // per context, from the system's entropy: nobody outside can aim rows at one probe run
   uint32_t slots_hook = 0;  // IBFT_WIRE_VIEWS_SLOTS (test hook): lowers the slot count, never below the first power of two above n
@@ -1915,7 +1925,8 @@ void ibft_ctx_destroy(ibft_ctx *c) {
                     &c->d_phash, &c->fam.d_vtab, &c->fam.d_vslot, &c->fam.d_setidx, &c->fam.d_meta, &c->fam.d_power,
                     &c->fam.d_quorum, &c->fam.d_seen, &c->fam.d_bset, &c->hsets.d_first, &c->hsets.d_range_set, &c->hsets.d_row_set,
                     &c->hsets.d_acc, &c->hsets.d_seen, &c->wviews.d_tables, &c->wviews.d_slots, &c->wviews.d_rank, &c->wviews.d_first,
-                    &c->wviews.d_view, &c->wviews.d_stored, &c->wviews.d_acc, &c->wviews.d_recs, &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
+                    &c->wviews.d_view, &c->wviews.d_stored, &c->wviews.d_acc, &c->wviews.d_recs, &c->wviews.d_sflags, &c->wviews.d_seal_row,
+                    &c->wviews.d_seal_src, &c->wviews.d_seal_words, &c->wviews.d_seal_mask, &c->d_msg_cols, &c->d_msg_wire, &c->d_env_cols, &c->d_env_body, &c->d_env_wire})
     release(*b);
   if (c->h_phash) (void)hipHostFree(c->h_phash);
   if (c->tstream) {
@@ -4277,7 +4288,7 @@ int ibft_verify_senders_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint3
   c->staged_pre = true;
   c->wire.rows = (uint32_t)n;
   c->wire.columns = true;
-  c->wire.parsed = false;
+  c->wire.begin();
   c->ev_used = 0;
   if (n && (rc = enqueue_wire_parse(c, (uint32_t)n))) return rc;
   // the digest column now holds keccak256(PayloadNoSig): the sender check is the seal-style pass (mode 0)
@@ -4338,12 +4349,14 @@ struct wire_views_out {
   uint64_t *out_stored;
   ibft_wire_view_t *out_views;
   uint32_t *out_n_views;
+  bool seals;          // ibft_verify_messages_wire_views: the committed seals in the same verdict launch, COMMIT records over stored ∧ sealed
+  uint64_t *out_seal;  // (seals) may be null
 };
 
 // Buffers of the views stage for n rows (before anything is enqueued: ensure() may free and allocate).
-static int ensure_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t slots) {
+static int ensure_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t slots, bool seals) {
   WireViews &w = c->wviews;
-  const size_t acc_bytes = (size_t)cap * (2 * c->fam.power_words + 1) * 8;
+  const size_t acc_bytes = (size_t)cap * (2 * c->fam.power_words + (seals ? 2 : 1)) * 8;
   int rc;
   if (acc_bytes > w.d_acc.cap) w.acc_dirty = true;  // a fresh allocation holds anything
   if ((rc = ensure(c, w.d_tables, (size_t)slots * 8 + 8)) || (rc = ensure(c, w.d_slots, (size_t)n * 8)) || (rc = ensure(c, w.d_rank, (size_t)n * 4)) ||
@@ -4351,11 +4364,79 @@ static int ensure_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t slo
       (rc = ensure(c, w.d_stored, (size_t)mask_words(n) * 8)) || (rc = ensure(c, w.d_acc, acc_bytes)) ||
       (rc = ensure(c, w.d_recs, (size_t)cap * sizeof(ibft_wire_view_t))))
     return rc;
+  if (seals && ((rc = ensure(c, w.d_sflags, n)) || (rc = ensure(c, w.d_seal_row, (size_t)n * 4)) || (rc = ensure(c, w.d_seal_src, (size_t)n * 4)) ||
+                (rc = ensure(c, w.d_seal_words, 16)) || (rc = ensure(c, w.d_seal_mask, (size_t)mask_words(n) * 8))))
+    return rc;
+  return IBFT_OK;
+}
+
+// the family's lookup and power columns as the views and seal kernels read them (under family_view)
+static wviews::family wire_views_family(const ibft_ctx *c) {
+  const ValFamily &f = c->fam;
+  wviews::family o{};
+  o.setidx = (const int32_t *)f.d_setidx.p;
+  o.set_meta = (const uint2 *)f.d_meta.p;
+  o.vpower32 = (const uint32_t *)f.d_power.p;
+  o.quorum = (const uint64_t *)f.d_quorum.p;
+  o.vtab = (const uint32_t *)c->d_vtab.p;  // (under family_view: the union's table, mask and size)
+  o.vslot_mask = c->vslot_mask;
+  o.n_union = c->n_validators;
+  o.n_pieces = 2 * (int)f.power_words;
+  return o;
+}
+
+static ibftk::wire_seals_args wire_seals_args_of(ibft_ctx *c, uint32_t n, uint32_t half) {
+  WireViews &w = c->wviews;
+  ibftk::wire_seals_args a{};
+  a.rows = (const wire::row_info *)c->d_wire_rows.p;
+  a.row_set = (const int32_t *)c->hsets.d_row_set.p;
+  a.seal65 = (const uint8_t *)c->d_seal.p;
+  a.n = n;
+  a.half = half;
+  a.fam = wire_views_family(c);
+  a.flags = (uint8_t *)w.d_sflags.p;
+  a.seal_row = (uint32_t *)w.d_seal_row.p;
+  a.src = (uint32_t *)w.d_seal_src.p;
+  a.words = (uint32_t *)w.d_seal_words.p;
+  a.hash32 = (uint8_t *)c->d_hash.p;
+  a.sig65 = (uint8_t *)c->d_sig.p;
+  a.signer20 = (uint8_t *)c->d_signer.p;
+  a.pre_flags = (uint8_t *)c->d_pre.p;
+  a.mask = (const uint64_t *)c->d_mask_out.p;
+  a.work_mask = (uint64_t *)c->d_mask.p;
+  a.seal_mask = (uint64_t *)w.d_seal_mask.p;
+  return a;
+}
+
+// The seal rows of ibft_verify_messages_wire_views behind wire_row_set_kernel, in front of the verdict launch over half + n
+// rows: mark, scan, stage (kernels.hip.h), the rows between n and half pre-flagged, the seal-digest convention over the
+// dense hashes.
+static int enqueue_wire_seals_stage(ibft_ctx *c, uint32_t n, uint32_t half) {
+  const ibftk::wire_seals_args a = wire_seals_args_of(c, n, half);
+  const dim3 grid((n + ibftk::WSEALS_THREADS - 1) / ibftk::WSEALS_THREADS), block(ibftk::WSEALS_THREADS);
+  hipLaunchKernelGGL(ibftk::wire_seals_mark_kernel, grid, block, 0, c->stream, a);
+  hipLaunchKernelGGL(ibftk::wire_seals_scan_kernel, dim3(1), dim3(1024), 0, c->stream, a);
+  hipLaunchKernelGGL(ibftk::wire_seals_stage_kernel, grid, block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  if (half != n) {
+    HIPCHK(c, hipMemsetAsync(a.sig65 + 65ull * n, 0, 65ull * (half - n), c->stream));
+    HIPCHK(c, hipMemsetAsync(a.pre_flags + n, 1, half - n, c->stream));
+  }
+  return apply_seal_digest(c, a.hash32 + 32ull * half, n);
+}
+
+// … and behind wire_sets_tally_kernel: the seal half's verdict words → the rows' seal bits; the work mask is zero again.
+static int enqueue_wire_seals_combine(ibft_ctx *c, uint32_t n, uint32_t half) {
+  const ibftk::wire_seals_args a = wire_seals_args_of(c, n, half);
+  hipLaunchKernelGGL(ibftk::wire_seals_combine_kernel, dim3((n + ibftk::WSEALS_THREADS - 1) / ibftk::WSEALS_THREADS), dim3(ibftk::WSEALS_THREADS), 0,
+                     c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  if ((uint32_t)mask_words((size_t)half + n) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed the sender words, this kernel the seal words
   return IBFT_OK;
 }
 
 // The views stage behind wire_sets_tally_kernel (same stream): one fill (tables to EMPTY), then insert, rank, tally, records.  Reads the final mask (d_mask_out), the rewritten index column, the rows' sets and the parsed rows.
-static int enqueue_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t slots) {
+static int enqueue_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t slots, bool seals) {
   WireViews &w = c->wviews;
   const ValFamily &f = c->fam;
   const CertState &s = c->cert;
@@ -4367,6 +4448,7 @@ static int enqueue_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t sl
   a.vidx = (const int32_t *)c->d_vidx.p;
   a.row_set = (const int32_t *)c->hsets.d_row_set.p;
   a.mask = (const uint64_t *)c->d_mask_out.p;
+  a.seal_mask = seals ? (const uint64_t *)w.d_seal_mask.p : nullptr;
   a.n = n;
   a.views_cap = cap;
   a.slots = slots;
@@ -4382,23 +4464,25 @@ static int enqueue_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t sl
   a.out_stored = (uint64_t *)w.d_stored.p;
   a.view_acc = (uint64_t *)w.d_acc.p;
   a.out_views = (wviews::view_t *)w.d_recs.p;
-  a.fam.setidx = (const int32_t *)f.d_setidx.p;
-  a.fam.set_meta = (const uint2 *)f.d_meta.p;
-  a.fam.vpower32 = (const uint32_t *)f.d_power.p;
-  a.fam.quorum = (const uint64_t *)f.d_quorum.p;
-  a.fam.vtab = (const uint32_t *)c->d_vtab.p;  // (under family_view: the union's table, mask and size)
-  a.fam.vslot_mask = c->vslot_mask;
-  a.fam.n_union = c->n_validators;
-  a.fam.n_pieces = 2 * (int)f.power_words;
+  a.fam = wire_views_family(c);
   a.table = certd::proposer_table{s.prop_height, s.prop_first, (const uint8_t *)s.proposers.p, s.proposers.p ? s.prop_rounds : 0u};
   const dim3 rows_grid((n + ibftk::WVIEWS_THREADS - 1) / ibftk::WVIEWS_THREADS), block(ibftk::WVIEWS_THREADS);
   hipLaunchKernelGGL(ibftk::wire_views_insert_kernel, rows_grid, block, 0, c->stream, a);
   hipLaunchKernelGGL(ibftk::wire_views_rank_kernel, dim3(1), dim3(1024), 0, c->stream, a);
-  if (f.power_words == 1)
-    hipLaunchKernelGGL(ibftk::wire_views_tally_kernel<1>, rows_grid, block, 0, c->stream, a);
-  else
-    hipLaunchKernelGGL(ibftk::wire_views_tally_kernel<4>, rows_grid, block, 0, c->stream, a);
-  hipLaunchKernelGGL(ibftk::wire_views_records_kernel, dim3((cap + ibftk::WVIEWS_THREADS - 1) / ibftk::WVIEWS_THREADS), block, 0, c->stream, a);
+  const dim3 views_grid((cap + ibftk::WVIEWS_THREADS - 1) / ibftk::WVIEWS_THREADS);
+  if (!seals) {
+    if (f.power_words == 1)
+      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<1, false>), rows_grid, block, 0, c->stream, a);
+    else
+      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<4, false>), rows_grid, block, 0, c->stream, a);
+    hipLaunchKernelGGL(ibftk::wire_views_records_kernel<false>, views_grid, block, 0, c->stream, a);
+  } else {
+    if (f.power_words == 1)
+      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<1, true>), rows_grid, block, 0, c->stream, a);
+    else
+      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<4, true>), rows_grid, block, 0, c->stream, a);
+    hipLaunchKernelGGL(ibftk::wire_views_records_kernel<true>, views_grid, block, 0, c->stream, a);
+  }
   HIPCHK(c, hipGetLastError());
   return IBFT_OK;
 }
@@ -4420,8 +4504,27 @@ int ibft_verify_senders_wire_views(ibft_ctx *c, const uint8_t *wire_bytes, const
   static_assert(sizeof(ibft_tally_t) == sizeof(wviews::tally_t) && offsetof(ibft_wire_view_t, tally) == offsetof(wviews::view_t, tally) &&
                     offsetof(ibft_wire_view_t, proposal_hash) == offsetof(wviews::view_t, proposal_hash),
                 "ABI");
-  const wire_views_out vo{views_cap, out_view, out_stored, out_views, out_n_views};
+  const wire_views_out vo{views_cap, out_view, out_stored, out_views, out_n_views, false, nullptr};
   return wire_sets_impl(c, wire_bytes, off, n, out_mask, out_rows, out_set, out_vidx, out_tally, &vo);
+}
+
+// The views call with the committed seals of the COMMIT rows judged in the SAME verdict launch (sender rows [0, n), the
+// sealable rows' seals dense from ⌈n/64⌉·64 on) and the COMMIT records tallied over stored ∧ sealed: the views call's checks
+// in its order.
+int ibft_verify_messages_wire_views(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t views_cap, uint64_t *out_mask,
+                                    ibft_wire_row_t *out_rows, int32_t *out_set, int32_t *out_vidx, ibft_tally_t *out_tally, int32_t *out_view,
+                                    uint64_t *out_stored, ibft_wire_view_t *out_views, uint32_t *out_n_views, uint64_t *out_seal) {
+  static_assert(IBFT_WIRE_VIEW_SEAL_RULE == wviews::SEAL_RULE, "ABI");
+  const wire_views_out vo{views_cap, out_view, out_stored, out_views, out_n_views, true, out_seal};
+  return wire_sets_impl(c, wire_bytes, off, n, out_mask, out_rows, out_set, out_vidx, out_tally, &vo);
+}
+
+int ibft_wire_seal_stats(ibft_ctx *c, uint32_t *commit_rows, uint32_t *seal_rows) {
+  if (!c) return IBFT_E_INVAL;
+  ctx_lock lk(c);
+  if (commit_rows) *commit_rows = c->wire.commit_rows;
+  if (seal_rows) *seal_rows = c->wire.seal_rows;
+  return IBFT_OK;
 }
 
 static int wire_sets_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, uint64_t *out_mask, ibft_wire_row_t *out_rows,
@@ -4437,12 +4540,16 @@ static int wire_sets_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   const uint32_t nr = (uint32_t)n, ns = c->fam.n_sets;
+  const bool seals = vo && vo->seals;
+  const uint32_t half = (nr + 63u) & ~63u;  // (seals) the seal rows begin here
+  // the seal rows double the rows of the columns: grown by the first call that asks for them
+  if (seals && nr && (rc = alloc_rows(c, 2 * (((uint32_t)c->max_rows + 63u) & ~63u)))) return rc;
   const size_t wbytes = n ? off[n] : 0;
   if ((rc = ensure_wire_buffers(c, wbytes))) return rc;
   if ((rc = ensure_block_records(c, c->brec, ns))) return rc;
   const uint32_t vcap = vo ? (uint32_t)std::min<size_t>(vo->views_cap, n) : 0u;  // (a cap above n behaves as n)
   const uint32_t vslots = vo && nr ? wviews::table_slots(nr, c->wviews.slots_hook) : 0u;
-  if (vo && nr && (rc = ensure_wire_views(c, nr, vcap, vslots))) return rc;
+  if (vo && nr && (rc = ensure_wire_views(c, nr, vcap, vslots, seals))) return rc;
   if (wbytes) HIPCHK(c, hipMemcpyAsync(c->d_payload.p, wire_bytes, wbytes, hipMemcpyHostToDevice, c->stream));
   if ((rc = upload(c, c->d_off, off, (n + 1) * 4))) return rc;
   // rows judged against the union are nothing ibft_seals_launch or ibft_wire_stage_seals could re-judge under the single set
@@ -4450,7 +4557,7 @@ static int wire_sets_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t
   c->staged_pre = true;
   c->wire.rows = nr;
   c->wire.columns = false;
-  c->wire.parsed = false;
+  c->wire.begin();
   c->ev_used = 0;
   // A call that fails once kernels are enqueued may leave the tally's scratch (per-set accumulators, bitmap) half used: the map
   // goes with it, and ibft_set_height_sets — which the caller then needs again — zeroes both.
@@ -4468,8 +4575,11 @@ static int wire_sets_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t
     hipLaunchKernelGGL(ibftk::wire_row_set_kernel, dim3((nr + 255) / 256), dim3(256), 0, c->stream, (const wire::row_info *)c->d_wire_rows.p,
                        nr, m, (int32_t *)h.d_row_set.p, (uint8_t *)c->d_pre.p);
     HIPCHK(c, hipGetLastError());
-    if ((rc = enqueue_recover(c, c->stream, nr, true, ibftk::MODE_SEALS, true))) return rc;
+    if (seals && (rc = enqueue_wire_seals_stage(c, nr, half))) return rc;
+    // (with the pre column: the seal half's tail — wavefronts whose rows are all dead — exits at once)
+    if ((rc = enqueue_recover(c, c->stream, seals ? half + nr : nr, true, ibftk::MODE_SEALS, true))) return rc;
     if ((rc = enqueue_wire_sets_tally(c, nr, c->brec.map ? c->brec.map : (uint64_t *)c->brec.d.p))) return rc;
+    if (seals && (rc = enqueue_wire_seals_combine(c, nr, half))) return rc;
     c->host_direct = false;
     const size_t mw = (size_t)mask_words(nr);
     if (!c->dh_mask) HIPCHK(c, hipMemcpyAsync(c->h_mask, c->d_mask_out.p, mw * 8, hipMemcpyDeviceToHost, c->stream));
@@ -4479,9 +4589,14 @@ static int wire_sets_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t
     if (out_set) HIPCHK(c, hipMemcpyAsync(out_set, h.d_row_set.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     if (out_vidx) HIPCHK(c, hipMemcpyAsync(out_vidx, c->d_vidx.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     uint32_t vwords[2] = {0, 0};  // {n_views, all-ones unless a table was exhausted}
+    uint32_t swords[2] = {0, 0};  // (seals) {sealable rows, COMMIT rows with a set}
     if (vo) {
       WireViews &w = c->wviews;
-      if ((rc = enqueue_wire_views(c, nr, vcap, vslots))) return rc;
+      if ((rc = enqueue_wire_views(c, nr, vcap, vslots, seals))) return rc;
+      if (seals) {
+        HIPCHK(c, hipMemcpyAsync(swords, w.d_seal_words.p, 8, hipMemcpyDeviceToHost, c->stream));
+        if (vo->out_seal) HIPCHK(c, hipMemcpyAsync(vo->out_seal, w.d_seal_mask.p, mw * 8, hipMemcpyDeviceToHost, c->stream));
+      }
       HIPCHK(c, hipMemcpyAsync(vwords, (const uint32_t *)w.d_tables.p + 2 * (size_t)vslots, 8, hipMemcpyDeviceToHost, c->stream));
       if (vo->out_view) HIPCHK(c, hipMemcpyAsync(vo->out_view, w.d_view.p, n * 4, hipMemcpyDeviceToHost, c->stream));
       if (vo->out_stored) HIPCHK(c, hipMemcpyAsync(vo->out_stored, w.d_stored.p, mw * 8, hipMemcpyDeviceToHost, c->stream));
@@ -4497,6 +4612,8 @@ static int wire_sets_impl(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t
         return IBFT_E_HIP;
       }
       c->wviews.acc_dirty = false;  // the records kernel zeroed what the tally added
+      c->wire.seal_rows = swords[0];
+      c->wire.commit_rows = swords[1];
       if (vo->out_n_views) *vo->out_n_views = vwords[0];
       // the records that exist — a handful in an honest batch, where views_cap is sized for the worst — once their number is known
       const size_t filled = std::min(vwords[0], vcap);
@@ -4531,7 +4648,7 @@ int ibft_verify_messages_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   c->wire.columns = false;
-  c->wire.parsed = false;
+  c->wire.begin();
   c->staged_n = 0;
   const uint32_t half = ((uint32_t)n + 63u) & ~63u;
   if ((rc = alloc_rows(c, 2 * (((uint32_t)c->max_rows + 63u) & ~63u)))) return rc;
@@ -4654,7 +4771,7 @@ static int cert_reserve(ibft_ctx *c, const cert_call &k, cert_plan &p) {
   const size_t wbytes = k.off[k.n], m = c->max_rows;
   if ((rc = ensure(c, c->d_payload, wbytes + 256))) return rc;
   if ((rc = ensure(c, c->d_wire_rows, m * sizeof(wire::row_info)))) return rc;
-  c->wire.parsed = false;  // the tree's rows take the place of the last flat call's
+  c->wire.begin();  // the tree's rows take the place of the last flat call's
   if ((rc = ensure(c, s.nodes, m * sizeof(wire::node_info)))) return rc;
   if ((rc = ensure(c, s.span, m * 8))) return rc;
   if ((rc = ensure(c, s.count, m * 4))) return rc;

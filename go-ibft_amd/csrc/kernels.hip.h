@@ -53,6 +53,7 @@
 #include "cert_verdict_dev.h"
 #include "cert_decide_dev.h"
 #include "wire_views_dev.h"
+#include "wire_seals_dev.h"
 #include "cert_dedup_dev.h"
 
 namespace ibftk {
@@ -2463,11 +2464,15 @@ __global__ void __launch_bounds__(WSETS_THREADS) wire_sets_tally_kernel(wire_set
 //   records  a thread per view below min(n_views, views_cap): wviews::view_record, then the view's accumulators are zeroed —
 //            all scratch but the tables (set to EMPTY, with the call's two words behind them, by one fill in front of every
 //            insert) is zero again when the call returns.
+// SEALS (ibft_verify_messages_wire_views, behind wire_seals_combine_kernel): tally reads the row's seal bit, a stored row adds
+// its pieces only where wseals::counts says so — in a COMMIT view a sealed row — and the rows that did are one more count per
+// view, so a view's accumulators are 2·PW + 2 words; records writes wviews::view_record's seal form and zeroes them all.
 constexpr int WVIEWS_THREADS = 256, WVIEWS_TURNS = 4;
 struct wire_views_args {
   const wire::row_info *rows;
   const int32_t *vidx, *row_set;  // index in the row's set / the row's set, as wire_sets_tally_kernel left them
   const uint64_t *mask;           // the final verdict words
+  const uint64_t *seal_mask;      // SEALS: the rows' seal bits
   uint32_t n, views_cap, slots, salt;
   uint32_t *key_table, *last_table;  // slots words each
   uint32_t *slot_key, *slot_last;    // n
@@ -2476,7 +2481,7 @@ struct wire_views_args {
   uint32_t *words;                   // behind the tables, all-ones like them at the start: [0] ← n_views, [1] ← 0 when a table was exhausted
   int32_t *out_view;                 // n
   uint64_t *out_stored;              // ⌈n / 64⌉
-  uint64_t *view_acc;                // min(n, views_cap) × (2·PW + 1), zero between calls
+  uint64_t *view_acc;                // min(n, views_cap) × (2·PW + 1; SEALS: + 2), zero between calls
   wviews::view_t *out_views;         // min(n, views_cap)
   wviews::family fam;
   certd::proposer_table table;
@@ -2513,9 +2518,9 @@ __global__ void __launch_bounds__(1024) wire_views_rank_kernel(wire_views_args a
   }
   if (t == 1023u) a.words[0] = part[1023];
 }
-template <int PW>
+template <int PW, bool SEALS = false>
 __global__ void __launch_bounds__(WVIEWS_THREADS) wire_views_tally_kernel(wire_views_args a) {
-  constexpr int NP = 2 * PW;
+  constexpr int NP = 2 * PW, STRIDE = NP + 1 + (SEALS ? 1 : 0);
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t row = blockIdx.x * WVIEWS_THREADS + tid;
   const uint32_t sk = row < a.n ? a.slot_key[row] : wviews::SKIP;
@@ -2531,8 +2536,13 @@ __global__ void __launch_bounds__(WVIEWS_THREADS) wire_views_tally_kernel(wire_v
   if (lane == 0 && (row & ~63u) < a.n) a.out_stored[row >> 6] = sw;
   bool pend = v >= 0;
   uint32_t pw[NP];
+  bool counted = stored;  // the row adds its sender's power
+  if constexpr (SEALS) {
+    const bool sealed = valid && ((a.seal_mask[row >> 6] >> (row & 63)) & 1ull);
+    counted = valid && wseals::counts(a.rows[row].type, stored, sealed);
+  }
   {
-    const bool adds = pend && stored;
+    const bool adds = pend && counted;
     const uint32_t entry = adds ? a.fam.set_meta[a.row_set[row]].x + (uint32_t)a.vidx[row] : 0u;
 #pragma unroll
     for (int k = 0; k < NP; k++) pw[k] = adds ? a.fam.vpower32[(size_t)entry * NP + k] : 0u;
@@ -2543,9 +2553,14 @@ __global__ void __launch_bounds__(WVIEWS_THREADS) wire_views_tally_kernel(wire_v
     const int leader = __ffsll((long long)todo) - 1;
     const int32_t lv = __shfl(v, leader, 64);
     const bool mine = pend && v == lv;
-    uint64_t *acc = a.view_acc + (size_t)lv * (NP + 1);
+    uint64_t *acc = a.view_acc + (size_t)lv * STRIDE;
     const uint64_t cnt = wave_sum_u64(mine ? (1ull | ((uint64_t)(stored ? 1u : 0u) << 32)) : 0ull);
-    if (cnt >> 32) {  // (wave-uniform) a stored row among them: the pieces
+    uint64_t adders = cnt >> 32;
+    if constexpr (SEALS) {
+      if (adders) adders = wave_sum_u64(mine && counted ? 1ull : 0ull);
+      if ((int)lane == leader && adders) atomicAdd(reinterpret_cast<unsigned long long *>(acc + NP + 1), (unsigned long long)adders);
+    }
+    if (adders) {  // (wave-uniform) a stored row that counts among them: the pieces
 #pragma unroll
       for (int k = 0; k < NP; k++) {
         const uint64_t sum = wave_sum_u64(mine ? (uint64_t)pw[k] : 0ull);
@@ -2556,25 +2571,130 @@ __global__ void __launch_bounds__(WVIEWS_THREADS) wire_views_tally_kernel(wire_v
     if (mine) pend = false;
   }
   if (pend) {  // more views in this wavefront than turns: the lane adds for itself
-    uint64_t *acc = a.view_acc + (size_t)v * (NP + 1);
-    if (stored) {
+    uint64_t *acc = a.view_acc + (size_t)v * STRIDE;
+    if (counted) {
 #pragma unroll
       for (int k = 0; k < NP; k++)
         if (pw[k]) atomicAdd(reinterpret_cast<unsigned long long *>(acc + k), (unsigned long long)pw[k]);
+      if constexpr (SEALS) atomicAdd(reinterpret_cast<unsigned long long *>(acc + NP + 1), 1ull);
     }
     atomicAdd(reinterpret_cast<unsigned long long *>(acc + NP), 1ull | ((uint64_t)(stored ? 1u : 0u) << 32));
   }
 }
+template <bool SEALS = false>
 __global__ void __launch_bounds__(WVIEWS_THREADS) wire_views_records_kernel(wire_views_args a) {
   const uint32_t v = blockIdx.x * WVIEWS_THREADS + threadIdx.x;
   const uint32_t n_views = a.words[0];
   if (v >= n_views || v >= a.views_cap) return;
-  uint64_t *acc = a.view_acc + (size_t)v * (a.fam.n_pieces + 1);
+  const int words = a.fam.n_pieces + 1 + (SEALS ? 1 : 0);
+  uint64_t *acc = a.view_acc + (size_t)v * words;
   wviews::view_t rec;
   wviews::view_record(rec, a.first_row[v], acc, wviews::columns{a.rows, a.vidx}, a.row_set, a.out_view, (int32_t)v, a.fam, a.table, a.last_table,
-                      a.slots, a.salt);
+                      a.slots, a.salt, SEALS);
   a.out_views[v] = rec;
-  for (int k = 0; k <= a.fam.n_pieces; k++) acc[k] = 0;
+  for (int k = 0; k < words; k++) acc[k] = 0;
+}
+
+// ---- the committed seals of the live route's COMMIT records (ibft_verify_messages_wire_views; the row bodies: wire_seals_dev.h)
+// Three launches between wire_row_set_kernel and the verdict launch lay the seal rows DENSE behind the sender rows, one
+// launch behind wire_sets_tally_kernel turns the seal half's verdict words into the rows' seal bits:
+//   mark     a thread per row: wseals::row_flags — is it a COMMIT with a set, is it sealable (the membership lookup included).
+//   scan     ONE workgroup (wire_views_rank_kernel's shape): the sealable rows ranked in ascending row order — seal_row[i] = k
+//            or NONE, src[k] = i — and the call's two counts: words[0] = sealable rows, words[1] = COMMIT rows with a set;
+//            words[2], combine's ticket, is set to zero.
+//   stage    a thread per seal row k < n: a live one (k < words[0]) gets the carried hash, the seal and From of src[k] and
+//            pre-flag 0; the others a zero signature and pre-flag 1 — the verdict launch covers half + n rows, whole
+//            wavefronts of the tail exit at once and the host never waits for the count.
+//   combine  a thread per row: wseals::seal_bit from the final sender bit and the verdict bit of the row's seal row; a
+//            wavefront's ballot is one word of the seal mask — every word written once, by one wavefront.  The workgroup
+//            that draws the last ticket zeroes the seal half's verdict words: the work mask is zero again.
+constexpr int WSEALS_THREADS = 256;
+struct wire_seals_args {
+  const wire::row_info *rows;
+  const int32_t *row_set;
+  const uint8_t *seal65;  // n × 65: the seals the walks found
+  uint32_t n, half;
+  wviews::family fam;   // (the lookup fields)
+  uint8_t *flags;       // n: wseals::ROW_*
+  uint32_t *seal_row;   // n: k of seal row half + k, or NONE
+  uint32_t *src;        // n: the row of seal row half + k
+  uint32_t *words;      // [0] sealable rows, [1] COMMIT rows with a set, [2] the ticket
+  uint8_t *hash32, *sig65, *signer20, *pre_flags;  // the verdict launch's columns (rows [half, half + n) are written)
+  const uint64_t *mask;  // the final verdict words of the sender rows
+  uint64_t *work_mask;   // the verdict launch's words; those of the seal half are consumed
+  uint64_t *seal_mask;   // ⌈n / 64⌉
+};
+__global__ void __launch_bounds__(WSEALS_THREADS) wire_seals_mark_kernel(wire_seals_args a) {
+  const uint32_t row = blockIdx.x * WSEALS_THREADS + threadIdx.x;
+  if (row >= a.n) return;
+  a.flags[row] = wseals::row_flags(a.rows[row], a.row_set[row], a.fam);
+}
+__global__ void __launch_bounds__(1024) wire_seals_scan_kernel(wire_seals_args a) {
+  __shared__ uint64_t part[1024];
+  const uint32_t t = threadIdx.x, per = (a.n + 1023u) / 1024u;
+  const uint32_t b = t * per < a.n ? t * per : a.n, e = b + per < a.n ? b + per : a.n;
+  uint64_t sum = 0;  // sealable | COMMIT << 32
+  for (uint32_t i = b; i < e; i++) {
+    const uint8_t f = a.flags[i];
+    sum += (uint64_t)((f & wseals::ROW_SEALABLE) ? 1u : 0u) | ((uint64_t)((f & wseals::ROW_COMMIT) ? 1u : 0u) << 32);
+  }
+  part[t] = sum;
+  __syncthreads();
+  for (uint32_t o = 1; o < 1024u; o <<= 1) {
+    const uint64_t v = t >= o ? part[t - o] : 0ull;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = (uint32_t)(part[t] - sum);
+  for (uint32_t i = b; i < e; i++) {
+    const bool sealable = a.flags[i] & wseals::ROW_SEALABLE;
+    a.seal_row[i] = sealable ? run : wseals::NONE;
+    if (sealable) a.src[run++] = i;
+  }
+  if (t == 1023u) {
+    a.words[0] = (uint32_t)part[1023];
+    a.words[1] = (uint32_t)(part[1023] >> 32);
+    a.words[2] = 0;
+  }
+}
+__global__ void __launch_bounds__(WSEALS_THREADS) wire_seals_stage_kernel(wire_seals_args a) {
+  const uint32_t k = blockIdx.x * WSEALS_THREADS + threadIdx.x;
+  if (k >= a.n) return;
+  const uint32_t dst = a.half + k;
+  const bool live = k < a.words[0];
+  a.pre_flags[dst] = live ? 0 : 1;
+  if (!live) {
+    for (int i = 0; i < 65; i++) a.sig65[65ull * dst + i] = 0;
+    return;
+  }
+  const uint32_t r = a.src[k];
+  const wire::row_info &ri = a.rows[r];
+  for (int i = 0; i < 32; i++) a.hash32[32ull * dst + i] = ri.proposal_hash[i];
+  for (int i = 0; i < 65; i++) a.sig65[65ull * dst + i] = a.seal65[65ull * r + i];
+  for (int i = 0; i < 20; i++) a.signer20[20ull * dst + i] = ri.from[i];
+}
+__global__ void __launch_bounds__(WSEALS_THREADS) wire_seals_combine_kernel(wire_seals_args a) {
+  __shared__ uint32_t last_flag;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t row = blockIdx.x * WSEALS_THREADS + tid;
+  const uint32_t words = (a.n + 63u) / 64u;
+  uint64_t *seal_words = a.work_mask + a.half / 64u;
+  const bool valid = row < a.n && ((a.mask[row >> 6] >> (row & 63)) & 1ull);
+  const bool bit = wseals::seal_bit(valid, row < a.n ? a.seal_row[row] : wseals::NONE, seal_words);
+  const uint64_t w = __ballot(bit ? 1 : 0);
+  if (lane == 0 && (row >> 6) < words) a.seal_mask[row >> 6] = w;
+  // ---- every workgroup has read its seal verdicts: the last one zeroes them ----
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t t = atomicAdd(a.words + 2, 1u);
+    last_flag = (t == gridDim.x - 1u) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!last_flag) return;
+  for (uint32_t i = tid; i < words; i += WSEALS_THREADS) seal_words[i] = 0;
+  if (tid == 0) a.words[2] = 0;
 }
 
 // ---- certificates: one record per carrier (ibft_judge_certificates_wire; the rules: cert_verdict_dev.h) ---------------------

@@ -20,7 +20,9 @@
 //                 row order, number the views.
 //   is_stored     the last table's slot holds the row.
 //   find_last     the stored row of (view, sender index), or none — how the record step asks for the proposer's PREPARE.
-//   view_record   a view's sums → its ibft_wire_view_t, the PREPARE rule (validator_manager.go:99-127) included.
+//   view_record   a view's sums → its ibft_wire_view_t, the PREPARE rule (validator_manager.go:99-127) included.  Its SEAL form
+//                 (ibft_verify_messages_wire_views; the rows' side: wire_seals_dev.h) reads one more count, the stored rows
+//                 that added their power, and marks a COMMIT record pad[SEAL_RULE] = 1.
 //
 // Everything here is __host__ __device__: csrc/host_wire_views_harness.hip runs it on the CPU against
 // tests/wire_views_model.py.  Nothing depends on the table size, the salt or the order rows arrive in.
@@ -39,7 +41,7 @@ constexpr uint32_t EMPTY = 0xFFFFFFFFu;     // a free table word (rows are numbe
 constexpr uint32_t UNPLACED = 0xFFFFFFFFu;  // slot of a row: the table was exhausted (an error)
 constexpr uint32_t SKIP = 0xFFFFFFFEu;      // slot of a row that is not valid
 constexpr int32_t VIEW_NONE = -1, VIEW_OVER = -2;
-constexpr uint8_t TYPE_PREPARE = 1;
+constexpr uint8_t TYPE_PREPARE = 1, TYPE_COMMIT = 2;
 
 // mirrors ibft_tally_t and ibft_wire_view_t (include/ibftgpu.h)
 struct tally_t {
@@ -220,9 +222,12 @@ struct family {
   int n_pieces;
 };
 // acc: the pieces of the powers of the view's stored rows, then rows | stored << 32.  out_view: the rows' views (complete).
+// seal_form: the pieces are those of the stored rows that COUNT (wseals::counts: in a COMMIT view the sealed ones), their
+// number follows in acc[n_pieces + 1]; a COMMIT record says so in pad[SEAL_RULE].
+constexpr int SEAL_RULE = 0;  // IBFT_WIRE_VIEW_SEAL_RULE
 __host__ __device__ inline void view_record(view_t &o, uint32_t first_row, const uint64_t *acc, const columns &k, const int32_t *row_set,
                                             const int32_t *out_view, int32_t v, const family &f, const certd::proposer_table &t,
-                                            const uint32_t *last_table, uint32_t slots, uint32_t salt) {
+                                            const uint32_t *last_table, uint32_t slots, uint32_t salt, bool seal_form = false) {
   const wire::row_info &me = k.rows[first_row];
   const int32_t set = row_set[first_row];
   const uint32_t len = hash_len_of(me);
@@ -236,10 +241,12 @@ __host__ __device__ inline void view_record(view_t &o, uint32_t first_row, const
   o.hash_len = (uint8_t)len;
   o.prepare_rule = 0;
   for (int i = 0; i < 5; i++) o.pad[i] = 0;
+  if (seal_form && me.type == TYPE_COMMIT) o.pad[SEAL_RULE] = 1;
+  const uint32_t counted = seal_form ? (uint32_t)acc[f.n_pieces + 1] : o.stored_rows;
   for (uint32_t i = 0; i < 32; i++) o.proposal_hash[i] = i < len ? me.proposal_hash[i] : 0;
   uint64_t piece[ibftk::TALLY_MAX_PIECES];
   for (int i = 0; i < ibftk::TALLY_MAX_PIECES; i++) piece[i] = i < f.n_pieces ? acc[i] : 0ull;
-  uint32_t distinct = o.stored_rows, proposer_rows = 0;  // stored rows are unique per (view, sender)
+  uint32_t distinct = counted, proposer_rows = 0;  // stored rows are unique per (view, sender)
   // HasPrepareQuorum: the proposer's seat joins, a stored PREPARE of the proposer voids the quorum
   const uint8_t *p = me.type == TYPE_PREPARE ? certd::table_lookup(t, me.height, me.round) : nullptr;
   if (p) {
@@ -265,7 +272,7 @@ __host__ __device__ inline void view_record(view_t &o, uint32_t first_row, const
   o.tally.quorum_hi = q[1];
   o.tally.power_lo = w[0];
   o.tally.power_hi = w[1];
-  o.tally.valid_rows = o.stored_rows;
+  o.tally.valid_rows = counted;
   o.tally.distinct_senders = distinct;
   o.tally.has_quorum = (ibftk::words_ge(w, q) && proposer_rows == 0) ? 1u : 0u;
   o.tally.shard_overlap = 0;

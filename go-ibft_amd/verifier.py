@@ -59,6 +59,7 @@ EXPORTS = [
     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
     "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire",
     "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets", "ibft_verify_senders_wire_views",
+    "ibft_verify_messages_wire_views", "ibft_wire_seal_stats",
 ]
 # exports younger than version 3: the version that brought them (ibft_verify_block_seals, the streamed ibft_block_seals_* and
 # ibft_recover_seals / ibft_recover_block_seals, ibft_proposal_hashes / the two _raw block calls and the validator-set family
@@ -77,7 +78,8 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
                     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
                     "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire",
-                    "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets", "ibft_verify_senders_wire_views"}
+                    "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets", "ibft_verify_senders_wire_views",
+                    "ibft_verify_messages_wire_views", "ibft_wire_seal_stats"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
 ENVELOPE_HEAD_MAX = 121  # the most ibft_sign_envelopes_wire puts in front of a body (sign_envelope_dev.h)
 MSG_PREPARE, MSG_COMMIT = 1, 2
@@ -119,6 +121,7 @@ WIRE_VIEW = np.dtype([("height", "<u8"), ("round", "<u8"), ("set", "<i4"), ("fir
                                  ("valid_rows", "<u4"), ("distinct_senders", "<u4"), ("has_quorum", "<u4"), ("shard_overlap", "<u4"),
                                  ("proposer_rows", "<u4"), ("reserved", "<u4")])])
 assert WIRE_VIEW.itemsize == 128
+WIRE_VIEW_SEAL_RULE = 0      # IBFT_WIRE_VIEW_SEAL_RULE: pad[0] = 1 — the record's tally counts only rows whose committed seal verifies
 
 
 class GpuUnavailable(RuntimeError):
@@ -265,6 +268,8 @@ def load_library() -> C.CDLL:
         "ibft_height_sets_info": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
         "ibft_verify_senders_wire_sets": [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, vp],
         "ibft_verify_senders_wire_views": [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_uint32)],
+        "ibft_verify_messages_wire_views": [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_uint32), vp],
+        "ibft_wire_seal_stats": [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
         "ibft_block_seals_collect": [vp, vp, vp],
         "ibft_block_seals_pending": [vp] + [C.POINTER(C.c_uint32)] * 3,
         "ibft_block_seals_collect_ex": [vp, vp, vp, vp, vp, vp],
@@ -1001,7 +1006,25 @@ class BatchVerifier:
         list[n_sets] — byte for byte the sets call's —, view int32[n] (-1: not valid, -2: its view did not fit views_cap),
         stored bool[n] — the rows a Messages store fed the batch in row order still holds —, views WIRE_VIEW[min(n_views,
         views_cap)], n_views)"""
-        self._need("ibft_verify_senders_wire_views")
+        return self._wire_views("ibft_verify_senders_wire_views", wire, off, views_cap, want_rows, False)
+
+    def verify_messages_wire_views(self, wire, off, views_cap: int, want_rows: bool = True):
+        """ibft_verify_messages_wire_views: verify_senders_wire_views with the committed seals of the COMMIT rows judged in the
+        same verdict launch → its tuple plus seal bool[n] — the row is valid and its seal recovers to its From over the digest
+        of the hash it names.  A COMMIT record has pad[WIRE_VIEW_SEAL_RULE] = 1 and its tally counts the stored rows whose seal
+        bit is set."""
+        return self._wire_views("ibft_verify_messages_wire_views", wire, off, views_cap, want_rows, True)
+
+    def wire_seal_stats(self):
+        """ibft_wire_seal_stats → (commit_rows, seal_rows) of the last verify_messages_wire_views: the COMMIT rows that have a
+        set, and the sealable ones — the seal checks the verdict launch was given"""
+        self._need("ibft_wire_seal_stats")
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.ibft_wire_seal_stats(self._h, C.byref(a), C.byref(b)), "ibft_wire_seal_stats")
+        return a.value, b.value
+
+    def _wire_views(self, name, wire, off, views_cap, want_rows, seals):
+        self._need(name)
         wb = _bytes_col(wire)
         off = np.ascontiguousarray(off, dtype=np.uint32)
         n = len(off) - 1
@@ -1016,12 +1039,14 @@ class BatchVerifier:
         views = np.zeros(max(cap, 1), dtype=WIRE_VIEW)
         nv = C.c_uint32(0)
         tal = (Tally * max(ns, 1))()
-        self._chk(self._L.ibft_verify_senders_wire_views(self._h, _p(wb), _p(off), n, int(views_cap), _p(mask),
-                                                         _p(rows) if (n and want_rows) else None, _p(rset), _p(vidx), tal, _p(view),
-                                                         _p(stored), _p(views), C.byref(nv)), "ibft_verify_senders_wire_views")
+        seal = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+        args = [self._h, _p(wb), _p(off), n, int(views_cap), _p(mask), _p(rows) if (n and want_rows) else None, _p(rset), _p(vidx), tal,
+                _p(view), _p(stored), _p(views), C.byref(nv)] + ([_p(seal)] if seals else [])
+        self._chk(getattr(self._L, name)(*args), name)
         self._staged = 0
-        return (mask_to_bool(mask, n), rows, rset[:n], vidx[:n], [tal[s] for s in range(ns)], view[:n], mask_to_bool(stored, n),
-                views[:min(nv.value, cap)], nv.value)
+        out = (mask_to_bool(mask, n), rows, rset[:n], vidx[:n], [tal[s] for s in range(ns)], view[:n], mask_to_bool(stored, n),
+               views[:min(nv.value, cap)], nv.value)
+        return out + (mask_to_bool(seal, n),) if seals else out
 
     def verify_messages_wire(self, wire, off, height: int, round_: int, raw: bytes | None = None, proposal_round: int | None = None,
                              digest32: bytes | None = None, want_rows: bool = True, proposer: bytes | None = None):

@@ -756,7 +756,7 @@ int ibft_verify_senders_wire_sets(ibft_ctx *ctx, const uint8_t *wire, const uint
  *   (validator_manager.go:99-127): the proposer's seat joins, a stored row FROM the proposer voids has_quorum and is
  *   counted in proposer_rows.  Otherwise prepare_rule = 0 and the plain rule holds.  The proposalMessage == nil case stays
  *   with the caller, as everywhere else.  A COMMIT record answers "who sent a valid COMMIT naming this hash as their last
- *   word in this view"; the committed seals of those rows stay with the caller (ibft_verify_seals over the stored rows).
+ *   word in this view" and does not look at committed seals: ibft_verify_messages_wire_views, below, does.
  * Every output is a pure function of the batch, the family, the map, the proposer table and views_cap: nothing depends on
  *   the order threads arrive in, on the size of the device's tables or on the context's hash salt.
  * Errors: those of ibft_verify_senders_wire_sets in its order; views_cap == 0 with n > 0 is IBFT_E_INVAL and is checked
@@ -773,8 +773,7 @@ int ibft_verify_senders_wire_sets(ibft_ctx *ctx, const uint8_t *wire, const uint
  * views, 0.584 / 0.425 ms for 2 006 views (one validator's 2 000 PREPAREs each in a round of its own); the sets call alone
  * 0.451 / 0.288 ms (the records: + 0.13 ms); rows read back, grouped on the host, ibft_set_validators per height and
  * ibft_tally per record: 9.5 ms for six views (8.7 ms of it the tool's host pass in Python), 69 ms for 2 006.
- * Out of scope: checking the COMMIT seals of a record's rows in the same verdict launch (the caller runs
- * ibft_verify_seals over the stored rows), a streamed form, a group form.                                              */
+ * Out of scope: a streamed form, a group form.  (The COMMIT seals of a record's rows: ibft_verify_messages_wire_views.)  */
 typedef struct {
   uint64_t height, round; /* the view's                                                             */
   int32_t set;            /* the set of the family the view's height is judged under                */
@@ -792,6 +791,59 @@ int ibft_verify_senders_wire_views(ibft_ctx *ctx, const uint8_t *wire, const uin
                                    uint64_t *out_mask, ibft_wire_row_t *out_rows, int32_t *out_set, int32_t *out_vidx,
                                    ibft_tally_t *out_tally, int32_t *out_view, uint64_t *out_stored,
                                    ibft_wire_view_t *out_views, uint32_t *out_n_views);
+
+/* ---- the views call with the COMMITTED SEALS checked inside the COMMIT records ------------------------------------------
+ * handleCommit (core/ibft.go:931-946) counts a stored COMMIT only if IsValidCommittedSeal(proposalHash, seal) holds; a COMMIT
+ * record of ibft_verify_senders_wire_views counts every stored COMMIT with a valid envelope, whatever its seal — an upper
+ * bound.  This call judges the seals in the SAME verdict launch as the envelopes (sender rows [0, n), the sealable rows'
+ * seals dense behind them from ceil(n / 64) * 64 on, the tail pre-flagged) and tallies a COMMIT record over stored AND
+ * sealed.
+ *
+ * out_mask, out_rows, out_set, out_vidx, out_tally, out_view, out_stored, *out_n_views: byte for byte what
+ *   ibft_verify_senders_wire_views returns for the same batch; so is every field of out_views but pad[0] and tally of COMMIT
+ *   records.  PREPARE records are the views call's, byte for byte.
+ * A row is SEALABLE when its status is OK, it has a set (out_set >= 0), type == 2 with a CommitMessage payload, a 20-byte
+ *   From, a 65-byte seal and a 32-byte proposal hash, and its From is a member of the row's set — a table lookup in front of
+ *   the verdict launch: an outsider, or a member of the union outside the row's set, loses its sender bit whatever its
+ *   signature says and buys no second ECDSA.  A hash that is not 32 bytes equals no proposal hash: no arithmetic either.
+ * out_seal (a bit per row, ceil(n / 64) words; bits past n are 0; may be NULL): bit i is set iff row i is valid AND
+ *   sealable AND its seal recovers to its From over the digest the context's seal-digest convention (ibft_set_seal_digest)
+ *   derives from the carried hash.  Defining property: for every set s the seal bits of the valid COMMIT rows with
+ *   out_set == s, in row order, are bit for bit what ibft_set_validators(set s) followed by ibft_verify_seals(proposal_hash,
+ *   seal, From) over those rows returns, a row that is not sealable pre-flagged — under IBFT_SEAL_DIGEST_IDENTITY and
+ *   _KECCAK_SUFFIX, cold and warm, u64 and u256 powers, IBFT_FLAG_WIRE_RECODE on and off (a recoded row's seal is the one
+ *   the recode walk stored).  The bit is defined for every valid COMMIT row, stored or not.
+ * A COMMIT record (type == 2) has pad[IBFT_WIRE_VIEW_SEAL_RULE] = 1 and its tally is field for field what
+ *   ibft_set_validators(set) followed by ibft_tally(S_v, mask = the seal bits of S_v) returns, S_v as in the views call:
+ *   rows and stored_rows keep their meaning, tally.valid_rows <= stored_rows.  The stored rule stays per view: a sender
+ *   whose stored (latest) COMMIT of the view has a bad seal contributes nothing, even if a superseded row of theirs had a
+ *   good one — the store holds one message per sender and GetValidMessages filters it.  The COMMIT record of the accepted
+ *   proposal's hash is handleCommit's hasQuorumByMsgType; the seals for setCommittedSeals are the rows with out_view == v,
+ *   the stored bit and the seal bit.
+ * Errors, side effects, optional pointers: exactly those of ibft_verify_senders_wire_views, in its order; a refused call
+ *   writes nothing.  The first call grows the context's row columns to twice max_rows (as ibft_verify_messages_wire does);
+ *   contexts that never make it allocate nothing more.  The two views calls may alternate on one context.
+ * ibft_wire_seal_stats: two counts of the last ibft_verify_messages_wire_views of the context — commit_rows, the COMMIT
+ *   rows (status OK, type 2, CommitMessage) that have a set; seal_rows, the sealable rows, i.e. the seal checks the verdict
+ *   launch was given.  0 / 0 after any other wire call.  IBFT_E_INVAL for a NULL ctx; either pointer may be NULL.
+ * MEASURED (tools/wire_view_seals_rate.py, profiles/r31_wire_view_seals_rate.txt; kernels:
+ * profiles/r31_kernel_meta_wire_view_seals.txt): the batch of the views call's measurement, N = 4 096 messages of two
+ * interleaved heights, V = 100, every seal valid; median of 25 single calls.  All COMMITs (4 096 seal rows): 0.960 ms cold /
+ * 0.545 ms with known keys against 0.605 / 0.430 ms for the views call alone: the seals cost + 0.355 / + 0.115 ms, where ONE
+ * ibft_verify_seals over the same 4 096 rows takes 0.363 / 0.182 ms.  PREPAREs and COMMITs half and half (2 000 seal rows):
+ * 0.908 / 0.501 ms against 0.567 / 0.389 ms (+ 0.341 / + 0.112 ms; one ibft_verify_seals of the 2 000: 0.442 / 0.169 ms).
+ * What a caller of the views call does for the same answer — rows read back, the 200 STORED COMMIT rows gathered per height,
+ * ibft_set_validators + ibft_verify_seals per height, ibft_tally per COMMIT record — takes 1.300 / 0.906 ms and 1.257 /
+ * 0.857 ms, of it 0.02 - 0.03 ms the host gather (numpy index selections over a seal column prepared beforehand); that route
+ * checks 200 seals where this call checks every valid COMMIT's.  The views call itself reads 0.595 and 0.608 ms cold, 0.406 and
+ * 0.445 ms warm on this build against 0.598 and 0.612, 0.432 and 0.435 ms on the parent's library in the same lease.
+ * Out of scope: streamed and group forms.  No new ibft_version().                                                       */
+#define IBFT_WIRE_VIEW_SEAL_RULE 0 /* index into ibft_wire_view_t.pad: 1 = the record's tally counts only rows whose committed seal verifies */
+int ibft_verify_messages_wire_views(ibft_ctx *ctx, const uint8_t *wire, const uint32_t *off, size_t n, size_t views_cap,
+                                    uint64_t *out_mask, ibft_wire_row_t *out_rows, int32_t *out_set, int32_t *out_vidx,
+                                    ibft_tally_t *out_tally, int32_t *out_view, uint64_t *out_stored,
+                                    ibft_wire_view_t *out_views, uint32_t *out_n_views, uint64_t *out_seal);
+int ibft_wire_seal_stats(ibft_ctx *ctx, uint32_t *commit_rows, uint32_t *seal_rows);
 
 /* a8 alone: HasQuorum over the rows whose bit is set in mask.                      */
 int ibft_tally(ibft_ctx *ctx, const uint8_t *sender20, const uint64_t *mask, size_t n,

@@ -1258,6 +1258,7 @@ type WireView struct {
 	Type          uint8  // 1 PREPARE, 2 COMMIT
 	HashLen       uint8
 	PrepareRule   bool
+	SealRule      bool // VerifyMessagesWireViews, a COMMIT record: Tally counts only the stored rows whose committed seal verifies
 	ProposalHash  [32]byte
 	Tally         Tally
 }
@@ -1282,15 +1283,40 @@ type WireViewsResult struct {
 	Stored    []uint64
 	Views     []WireView
 	NViews    uint32
+	Seal      []uint64 // VerifyMessagesWireViews only: a bit per row — the row is valid and its committed seal verifies
 }
 
 // VerifySendersWireViews = VerifySendersWireSets plus one quorum record per (height, round, type, proposal hash) that has a valid
 // message in the batch (ibft_verify_senders_wire_views): what core/ibft.go:1113-1121, handlePrepare (:855-873) and handleCommit
 // (:931-946) ask of GetValidMessages, for every view of a receive-queue batch in one call.  Views are numbered by their lowest
 // valid row.  A PREPARE record follows HasPrepareQuorum when SetProposers covers its height and round; the proposalMessage ==
-// nil case and the committed seals of a COMMIT record's rows stay with the caller.  viewsCap must be positive for a batch that
+// nil case stays with the caller; the committed seals of a COMMIT record's rows are not looked at (VerifyMessagesWireViews does).  viewsCap must be positive for a batch that
 // has rows; a cap above the row count behaves as the row count.
 func (c *Ctx) VerifySendersWireViews(wire []byte, off []uint32, viewsCap int) (*WireViewsResult, error) {
+	return c.wireViews(wire, off, viewsCap, false)
+}
+
+// VerifyMessagesWireViews = VerifySendersWireViews with the committed seals of the COMMIT rows judged in the same verdict launch
+// (ibft_verify_messages_wire_views).  Seal holds a bit per row: the row is valid, sealable (a COMMIT of a member of its set
+// with a 65-byte seal and a 32-byte hash) and its seal recovers to its From over the digest the seal-digest convention derives
+// from the hash it names.  A COMMIT record has SealRule set and its Tally counts the stored rows whose seal bit is set —
+// handleCommit's hasQuorumByMsgType (core/ibft.go:931-946) for the record of the accepted proposal's hash; the seals for
+// setCommittedSeals are the rows of that view with the stored bit and the seal bit.  Everything else is VerifySendersWireViews'.
+func (c *Ctx) VerifyMessagesWireViews(wire []byte, off []uint32, viewsCap int) (*WireViewsResult, error) {
+	return c.wireViews(wire, off, viewsCap, true)
+}
+
+// WireSealStats reports two counts of the last VerifyMessagesWireViews (ibft_wire_seal_stats): the COMMIT rows that have a set,
+// and the sealable ones — the seal checks the verdict launch was given.  0, 0 after any other wire call.
+func (c *Ctx) WireSealStats() (commitRows, sealRows uint32, err error) {
+	var a, b C.uint32_t
+	if err = c.check(C.ibft_wire_seal_stats(c.h, &a, &b)); err != nil {
+		return 0, 0, err
+	}
+	return uint32(a), uint32(b), nil
+}
+
+func (c *Ctx) wireViews(wire []byte, off []uint32, viewsCap int, seals bool) (*WireViewsResult, error) {
 	if len(off) == 0 {
 		return nil, fmt.Errorf("%w: off needs n + 1 entries", ErrFallback)
 	}
@@ -1314,10 +1340,21 @@ func (c *Ctx) VerifySendersWireViews(wire []byte, off []uint32, viewsCap int) (*
 	ct := make([]C.ibft_tally_t, ns+1)
 	cv := make([]C.ibft_wire_view_t, vcap+1)
 	var nv C.uint32_t
-	rc := C.ibft_verify_senders_wire_views(c.h, ptr8(wire), (*C.uint32_t)(unsafe.Pointer(&off[0])), C.size_t(n), C.size_t(viewsCap),
-		(*C.uint64_t)(unsafe.Pointer(&r.Mask[0])), (*C.ibft_wire_row_t)(unsafe.Pointer(&r.Rows[0])),
-		(*C.int32_t)(unsafe.Pointer(&r.Set[0])), (*C.int32_t)(unsafe.Pointer(&r.Vidx[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])),
-		(*C.int32_t)(unsafe.Pointer(&r.View[0])), (*C.uint64_t)(unsafe.Pointer(&r.Stored[0])), (*C.ibft_wire_view_t)(unsafe.Pointer(&cv[0])), &nv)
+	var rc C.int
+	if seals {
+		r.Seal = make([]uint64, (n+63)/64+1)
+		rc = C.ibft_verify_messages_wire_views(c.h, ptr8(wire), (*C.uint32_t)(unsafe.Pointer(&off[0])), C.size_t(n), C.size_t(viewsCap),
+			(*C.uint64_t)(unsafe.Pointer(&r.Mask[0])), (*C.ibft_wire_row_t)(unsafe.Pointer(&r.Rows[0])),
+			(*C.int32_t)(unsafe.Pointer(&r.Set[0])), (*C.int32_t)(unsafe.Pointer(&r.Vidx[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])),
+			(*C.int32_t)(unsafe.Pointer(&r.View[0])), (*C.uint64_t)(unsafe.Pointer(&r.Stored[0])), (*C.ibft_wire_view_t)(unsafe.Pointer(&cv[0])), &nv,
+			(*C.uint64_t)(unsafe.Pointer(&r.Seal[0])))
+		r.Seal = r.Seal[:(n+63)/64]
+	} else {
+		rc = C.ibft_verify_senders_wire_views(c.h, ptr8(wire), (*C.uint32_t)(unsafe.Pointer(&off[0])), C.size_t(n), C.size_t(viewsCap),
+			(*C.uint64_t)(unsafe.Pointer(&r.Mask[0])), (*C.ibft_wire_row_t)(unsafe.Pointer(&r.Rows[0])),
+			(*C.int32_t)(unsafe.Pointer(&r.Set[0])), (*C.int32_t)(unsafe.Pointer(&r.Vidx[0])), (*C.ibft_tally_t)(unsafe.Pointer(&ct[0])),
+			(*C.int32_t)(unsafe.Pointer(&r.View[0])), (*C.uint64_t)(unsafe.Pointer(&r.Stored[0])), (*C.ibft_wire_view_t)(unsafe.Pointer(&cv[0])), &nv)
+	}
 	if err = c.check(rc); err != nil {
 		return nil, err
 	}
@@ -1339,6 +1376,7 @@ func (c *Ctx) VerifySendersWireViews(wire []byte, off []uint32, viewsCap int) (*
 		o.Height, o.Round, o.Set = uint64(w.height), uint64(w.round), int32(w.set)
 		o.FirstRow, o.Rows, o.StoredRows = uint32(w.first_row), uint32(w.rows), uint32(w.stored_rows)
 		o.Type, o.HashLen, o.PrepareRule = uint8(w._type), uint8(w.hash_len), w.prepare_rule != 0
+		o.SealRule = w.pad[C.IBFT_WIRE_VIEW_SEAL_RULE] != 0
 		for i := range o.ProposalHash {
 			o.ProposalHash[i] = byte(w.proposal_hash[i])
 		}
