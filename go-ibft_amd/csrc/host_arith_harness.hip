@@ -308,6 +308,21 @@ static uint32_t build_vtab(const uint8_t *addrs20, uint32_t n_validators, std::v
   }
   return slots - 1;
 }
+// The table build_vtab makes of a list, as it stands: out_tab takes 6 dwords per slot (cap_slots of them at the most); returns the
+// number of slots.  dev_valset_lookup: valset_lookup itself over that table — the index of addr20, −1: no member.
+uint32_t dev_valset_table(const uint8_t *addrs20, uint32_t n_validators, uint32_t *out_tab, uint32_t cap_slots) {
+  std::vector<uint32_t> tab;
+  const uint32_t slots = build_vtab(addrs20, n_validators, tab) + 1;
+  if (slots <= cap_slots) memcpy(out_tab, tab.data(), tab.size() * 4);
+  return slots;
+}
+int dev_valset_lookup(const uint8_t *addrs20, uint32_t n_validators, const uint8_t *addr20) {
+  std::vector<uint32_t> tab;
+  const uint32_t slot_mask = build_vtab(addrs20, n_validators, tab);
+  uint32_t a[5];
+  memcpy(a, addr20, 20);
+  return ibftk::valset_lookup(tab.data(), slot_mask, a);
+}
 static bool recover_row(const uint8_t *digest32, const uint8_t *sig65, uint32_t flags, uint32_t got[5]) {
   dev_gtab_init();
   ibftk::aff Qa;
