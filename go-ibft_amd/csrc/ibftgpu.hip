@@ -3123,7 +3123,9 @@ static int enqueue_set_tally(ibft_ctx *c, size_t n, uint32_t half, const set_tai
   if ((rc = wait_proposal_hash(c))) return rc;
   if (t.note_proposer) note_proposer(c, t.proposer20);
   if ((rc = enqueue_tally(c, (uint32_t)n, &sa))) return rc;
-  c->mask_dirty_words = 0;  // the combine kernel zeroed the seal words, the tally the sender words
+  // the combine kernel zeroed the seal words, the tally the sender words: the mask is clean only if no earlier call left bits
+  // beyond them (the lane kernel stores whole words and asks for no clean mask in front)
+  if ((uint32_t)mask_words(t.half_words ? (size_t)half + n : n) >= c->mask_dirty_words) c->mask_dirty_words = 0;
   if (!c->dh_set)
     HIPCHK(c, hipMemcpyAsync(c->h_set, c->d_set.p, (size_t)mask_words(c->max_rows) * 16, hipMemcpyDeviceToHost, c->stream));
   return IBFT_OK;
