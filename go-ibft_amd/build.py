@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libibftgpu.so")
-SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "wire_recode_dev.h", "wire_sets_dev.h", "wire_views_dev.h", "wire_seals_dev.h", "cert_wave_dev.h", "cert_scan_dev.h", "cert_verdict_dev.h", "cert_decide_dev.h", "cert_dedup_dev.h", "cert_dedup_kernels.h", "modinv_dev.h",
+SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "wire_recode_dev.h", "wire_sets_dev.h", "tally_dev.h", "wire_views_dev.h", "wire_seals_dev.h", "cert_wave_dev.h", "cert_scan_dev.h", "cert_verdict_dev.h", "cert_decide_dev.h", "cert_dedup_dev.h", "cert_dedup_kernels.h", "modinv_dev.h",
            "sign_dev.h", "sign_message_dev.h", "sign_envelope_dev.h", "sha256_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
 # Code-generation flags of the product library (part of its build stamp).  max-ilp: the verdict kernels run ONE wavefront per
 # SIMD at the sizes that matter (N ≤ 4 096), where every hazard s_nop is a lost issue slot — scheduling for instruction-level
@@ -350,8 +350,9 @@ WIRE_SETS_HARNESS = os.path.join(CSRC, "libdev_wire_sets_host.so")
 
 
 def build_wire_sets_harness(force: bool = False) -> str:
-    """TEST-ONLY: wire_sets_dev.h (the height map, the row rule and the per-set tally of ibft_verify_senders_wire_sets) on the CPU."""
-    deps = ["host_wire_sets_harness.hip", "wire_sets_dev.h", "wire_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
+    """TEST-ONLY: wire_sets_dev.h (the height map, the row rule and the per-set tally of ibft_verify_senders_wire_sets) and
+    tally_dev.h (tally_record) on the CPU."""
+    deps = ["host_wire_sets_harness.hip", "wire_sets_dev.h", "tally_dev.h", "wire_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
     if force or _stale(WIRE_SETS_HARNESS, deps):
         subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
                                "-o", WIRE_SETS_HARNESS, os.path.join(CSRC, "host_wire_sets_harness.hip")], cwd=CSRC)
@@ -365,7 +366,7 @@ WIRE_VIEWS_HARNESS = os.path.join(CSRC, "libdev_wire_views_host.so")
 def build_wire_views_harness(force: bool = False) -> str:
     """TEST-ONLY: wire_views_dev.h (the two tables, the stored rule, the ranks and the per-view records of
     ibft_verify_senders_wire_views) on the CPU."""
-    deps = ["host_wire_views_harness.hip", "wire_views_dev.h", "wire_sets_dev.h", "wire_dev.h", "cert_decide_dev.h", "cert_verdict_dev.h",
+    deps = ["host_wire_views_harness.hip", "wire_views_dev.h", "wire_sets_dev.h", "tally_dev.h", "wire_dev.h", "cert_decide_dev.h", "cert_verdict_dev.h",
             "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
     if force or _stale(WIRE_VIEWS_HARNESS, deps):
         subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
@@ -380,7 +381,7 @@ WIRE_VIEW_SEALS_HARNESS = os.path.join(CSRC, "libdev_wire_view_seals_host.so")
 def build_wire_view_seals_harness(force: bool = False) -> str:
     """TEST-ONLY: wire_seals_dev.h and the seal form of wire_views_dev.h (the sealable decision, the dense seal rows, the seal
     bits and the COMMIT records of ibft_verify_messages_wire_views) on the CPU."""
-    deps = ["host_wire_view_seals_harness.hip", "wire_seals_dev.h", "wire_views_dev.h", "wire_sets_dev.h", "wire_dev.h", "cert_decide_dev.h",
+    deps = ["host_wire_view_seals_harness.hip", "wire_seals_dev.h", "wire_views_dev.h", "wire_sets_dev.h", "tally_dev.h", "wire_dev.h", "cert_decide_dev.h",
             "cert_verdict_dev.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
     if force or _stale(WIRE_VIEW_SEALS_HARNESS, deps):
         subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",

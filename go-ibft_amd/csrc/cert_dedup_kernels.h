@@ -35,16 +35,9 @@ __global__ void __launch_bounds__(1024) cert_dedup_apply_kernel(const uint32_t *
   __shared__ uint32_t a[1024];
   const uint32_t t = threadIdx.x, i = blockIdx.x * 1024u + t;
   const uint32_t rep = i < n ? scan_word[i] & 1u : 0u;
-  a[t] = rep;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024u; o <<= 1) {
-    const uint32_t x = t >= o ? a[t - o] : 0u;
-    __syncthreads();
-    a[t] += x;
-    __syncthreads();
-  }
+  const uint32_t incl = block_scan_1024(a, rep);
   if (!rep) return;
-  const uint32_t d = tile_off[blockIdx.x].x + a[t] - 1u;
+  const uint32_t d = tile_off[blockIdx.x].x + incl - 1u;
   dense_pos[i] = d;
   cdd::gather_row(k, i, dense_base + d);
 }

@@ -17,6 +17,46 @@ namespace ibftk {
 constexpr uint32_t CERT_SCAN_ONE_GROUP_MAX = 8192;
 constexpr uint32_t CERT_SCAN_TILE_ROWS = 1024;  // rows per tile = threads per workgroup of all four kernels
 
+// The inclusive scan of one value per thread across a workgroup of 1 024 threads (Hillis–Steele through LDS: ten steps, each
+// read of a neighbour's sum between two barriers).  value[k] of thread t becomes Σ value[k] of threads 0 … t; the total is
+// part[k][1023].  Every thread of the workgroup calls it; part[k] is 1 024 cells and free again behind a barrier of the
+// caller's.  N values are scanned in the same ten steps (the level scans carry a count and a deferred flag).
+template <int N, class T>
+__device__ __forceinline__ void block_scan_1024_n(T *const (&part)[N], T (&value)[N]) {
+  const uint32_t t = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < N; k++) part[k][t] = value[k];
+  __syncthreads();
+  for (uint32_t o = 1; o < 1024u; o <<= 1) {
+    T v[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = t >= o ? part[k][t - o] : (T)0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; k++) part[k][t] += v[k];
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < N; k++) value[k] = part[k][t];
+}
+// one value (T: uint32_t, or a uint64_t that packs two counts): returns the thread's inclusive sum
+template <class T>
+__device__ __forceinline__ T block_scan_1024(T *part, T value) {
+  T *const p[1] = {part};
+  T v[1] = {value};
+  block_scan_1024_n(p, v);
+  return v[0];
+}
+// a pair of values: they come back as the thread's inclusive sums
+template <class T>
+__device__ __forceinline__ void block_scan_1024(T *part, T *part2, T &value, T &value2) {
+  T *const p[2] = {part, part2};
+  T v[2] = {value, value2};
+  block_scan_1024_n(p, v);
+  value = v[0];
+  value2 = v[1];
+}
+
 // first_child of rows [lo, hi) = base + exclusive prefix sum of their child counts; the sum → total[0] (device and host).
 // The rows whose digest is deferred (wire::tree_deferred: they carry a certificate, or are long) are listed the same way:
 // deferred_rows[slot_base + rank] = row, their count → total[1].  child_count[i] bit 31 = row lo + i is deferred.
@@ -33,17 +73,9 @@ __global__ void __launch_bounds__(1024) cert_scan_kernel(const uint32_t *__restr
     sum += c & 0x7FFFFFFFu;
     sum2 += c >> 31;
   }
-  part[t] = sum;
-  part2[t] = sum2;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024u; o <<= 1) {
-    const uint32_t v = t >= o ? part[t - o] : 0u, v2 = t >= o ? part2[t - o] : 0u;
-    __syncthreads();
-    part[t] += v;
-    part2[t] += v2;
-    __syncthreads();
-  }
-  uint32_t run = base + part[t] - sum, run2 = slot_base + part2[t] - sum2;
+  uint32_t incl = sum, incl2 = sum2;
+  block_scan_1024(part, part2, incl, incl2);
+  uint32_t run = base + incl - sum, run2 = slot_base + incl2 - sum2;
   for (uint32_t i = b; i < e; i++) {
     const uint32_t c = child_count[i];
     nodes[lo + i].first_child = run;
@@ -85,17 +117,9 @@ __global__ void __launch_bounds__(1024) cert_scan_offsets_kernel(uint2 *__restri
   uint32_t run = 0, run2 = 0;  // sums of the passes before this one (the same in every thread)
   for (uint32_t t0 = 0; t0 < tiles; t0 += 1024u) {
     const uint2 v = t0 + t < tiles ? tile_sum[t0 + t] : make_uint2(0, 0);
-    a[t] = v.x;
-    b[t] = v.y;
-    __syncthreads();
-    for (uint32_t o = 1; o < 1024u; o <<= 1) {
-      const uint32_t x = t >= o ? a[t - o] : 0u, y = t >= o ? b[t - o] : 0u;
-      __syncthreads();
-      a[t] += x;
-      b[t] += y;
-      __syncthreads();
-    }
-    if (t0 + t < tiles) tile_sum[t0 + t] = make_uint2(base + run + a[t] - v.x, slot_base + run2 + b[t] - v.y);  // exclusive, with the bases
+    uint32_t x = v.x, y = v.y;
+    block_scan_1024(a, b, x, y);
+    if (t0 + t < tiles) tile_sum[t0 + t] = make_uint2(base + run + x - v.x, slot_base + run2 + y - v.y);  // exclusive, with the bases
     run += a[1023];
     run2 += b[1023];
     __syncthreads();
@@ -115,20 +139,12 @@ __global__ void __launch_bounds__(1024) cert_scan_apply_kernel(const uint32_t *_
   __shared__ uint32_t a[1024], b[1024];
   const uint32_t t = threadIdx.x, i = blockIdx.x * 1024u + t;
   const uint32_t c = i < n ? child_count[i] : 0u, cnt = c & 0x7FFFFFFFu, def = c >> 31;
-  a[t] = cnt;
-  b[t] = def;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024u; o <<= 1) {
-    const uint32_t x = t >= o ? a[t - o] : 0u, y = t >= o ? b[t - o] : 0u;
-    __syncthreads();
-    a[t] += x;
-    b[t] += y;
-    __syncthreads();
-  }
+  uint32_t x = cnt, y = def;
+  block_scan_1024(a, b, x, y);
   if (i >= n) return;
   const uint2 off = tile_off[blockIdx.x];
-  nodes[lo + i].first_child = off.x + a[t] - cnt;
-  if (def) deferred_rows[off.y + b[t] - 1u] = lo + i;
+  nodes[lo + i].first_child = off.x + x - cnt;
+  if (def) deferred_rows[off.y + y - 1u] = lo + i;
 }
 
 // Tiles of a level of cnt rows: the tiled form needs that many uint2 cells at d_tiles.

@@ -1,7 +1,7 @@
 // host_wire_sets_harness.hip — TEST-ONLY: the per-row bodies of wire_row_set_kernel and wire_sets_tally_kernel
 // (wire_sets_dev.h) on the CPU, so that tests/test_dev_wire_sets_host.py can check the exact device source without a GPU: a
 // height → its set, a parsed message → its set and pre-flag, a row's verdict bit + union index + set → bit / index / entry,
-// and the per-set records.  The cross-row part — who is first for an entry, the sums — is a plain loop here where the kernel
+// the per-set records, and tally_record on sums of the caller's.  The cross-row part — who is first for an entry, the sums — is a plain loop here where the kernel
 // has its bitmap merge and its wavefront turns.  Built with hipcc's host pass; never linked into libibftgpu.so, never a fallback.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,8 +56,15 @@ void wsh_tally(uint8_t *bit, int32_t *vidx, const int32_t *row_set, uint32_t n, 
   }
   for (uint32_t s = 0; s < n_sets; s++) {
     const uint64_t *a = &acc[(size_t)s * (n_pieces + 1)];
-    ibftk::wire_sets_record(a, (int)n_pieces, a[n_pieces], quorum + (size_t)s * ibftk::TALLY_SUM_WORDS, records + 4ull * s);
+    ibftk::tally_record(a, (int)n_pieces, a[n_pieces], quorum + (size_t)s * ibftk::TALLY_SUM_WORDS, 0ull, records + 4ull * s);
   }
+}
+
+// tally_record (tally_dev.h) itself: n_pieces piece sums, the counts word, 5 quorum words, the proposer's rows → the record's
+// 4 words and the power in full (5 words)
+void wsh_tally_record(const uint64_t *piece, uint32_t n_pieces, uint64_t counts, const uint64_t *quorum, uint64_t proposer_rows, uint64_t *out4,
+                      uint64_t *wide5) {
+  ibftk::tally_record(piece, (int)n_pieces, counts, quorum, proposer_rows, out4, wide5);
 }
 
 }  // extern "C"

@@ -735,6 +735,35 @@ template <class F>
 void with_warm_mode(int mode, F &&f) { with_int<ibftk::MODE_SEALS, ibftk::MODE_SENDERS>(mode, f); }  // (the verify kernels know no MODE_EMIT)
 template <class F>
 void with_qtab_form(int form, F &&f) { with_int<ibftk::QTAB_GLV, ibftk::QTAB_WIDE>(form, f); }
+template <class F>
+void with_power_words(uint32_t pw, F &&f) { with_int<1, 4>((int)pw, f); }  // PW of the tally kernels: u64 powers, else 256-bit
+
+// ---- the host side of every tally launch -----------------------------------------------------------------------------------------
+// A consumer stream may still be copying the previous results (ibft_seals_export_on / exchange): the tally that overwrites
+// them waits for it.
+static int wait_for_readers(ibft_ctx *c, hipStream_t stream) {
+  if (c->read_pending) {
+    HIPCHK(c, hipStreamWaitEvent(stream, c->ev_read, 0));
+    c->read_pending = false;
+  }
+  return IBFT_OK;
+}
+// A tally (and the kernels that finish its work: the seal combine) zeroes exactly the words of the work mask it walked —
+// [0, words).  The mask is clean only if no earlier call left bits BEYOND them: mask_dirty_words goes to 0 when the walk covered
+// every word that may hold bits, and stays what it was otherwise.  (One copy of this rule once compared against the wrong
+// count, and stale bits beyond row 65 536 were accepted as verdicts.)
+static void mask_consumed(ibft_ctx *c, size_t words) {
+  if ((uint32_t)words >= c->mask_dirty_words) c->mask_dirty_words = 0;
+}
+// The distinct-sender bitmap of a tally kernel — one bit per entry — lives in dynamic LDS while it fits
+// ibftk::TALLY_BITMAP_LDS_MAX (393 216 entries); beyond, the kernel sets every row's bit in the HBM bitmap directly.
+// Returns the kernel's lds_bitmap flag, *dyn_bytes: the launch's dynamic LDS size.
+static uint32_t bitmap_in_lds(size_t entries, size_t *dyn_bytes) {
+  const size_t bytes = (entries + 31) / 32 * 4;
+  const bool fits = bytes <= ibftk::TALLY_BITMAP_LDS_MAX;
+  *dyn_bytes = fits ? bytes : 0;
+  return fits ? 1u : 0u;
+}
 
 // one verdict kernel over `items` rows (or wavefronts), per_block of them in a workgroup of `threads`
 template <class K>
@@ -958,10 +987,8 @@ int build_new_tables(ibft_ctx *c, uint32_t learned_total, uint32_t any_slot) {
 // `on`: the stream the tally is enqueued on (default: the context's main stream; ibft_seals_submit passes the side stream)
 int enqueue_tally(ibft_ctx *c, uint32_t n, const ibftk::set_args *set = nullptr, hipStream_t on = nullptr) {
   const hipStream_t ts = on ? on : c->stream;
-  if (c->read_pending) {  // a consumer stream is still copying the previous results (ibft_seals_export_on / exchange)
-    HIPCHK(c, hipStreamWaitEvent(ts, c->ev_read, 0));
-    c->read_pending = false;
-  }
+  int rc;
+  if ((rc = wait_for_readers(c, ts))) return rc;
   ibftk::tally_args t{};
   t.work_mask = (uint64_t *)c->d_mask.p;
   t.mask = (uint64_t *)c->d_mask_out.p;
@@ -989,8 +1016,7 @@ int enqueue_tally(ibft_ctx *c, uint32_t n, const ibftk::set_args *set = nullptr,
   if (c->comm || c->xlocal) {  // a rank of a sharded batch: the bitmap of this launch is what the exchange merges
     const size_t bytes = (size_t)((c->n_validators + 63) / 64) * 8;
     if (bytes > c->d_seen_out.cap) {
-      int rc = ensure(c, c->d_seen_out, bytes);
-      if (rc) return rc;
+      if ((rc = ensure(c, c->d_seen_out, bytes))) return rc;
       HIPCHK(c, hipMemsetAsync(c->d_seen_out.p, 0, c->d_seen_out.cap, ts));  // (an odd trailing 32-bit word stays 0)
     }
     t.seen_out = (uint32_t *)c->d_seen_out.p;
@@ -999,26 +1025,18 @@ int enqueue_tally(ibft_ctx *c, uint32_t n, const ibftk::set_args *set = nullptr,
   // one workgroup (n ≤ 4 096): everything stays in the workgroup — no global atomics on the latency-critical sizes;
   // beyond: ticket form, each workgroup merging its LDS bitmap into the HBM one word by word.  A validator set whose
   // bitmap does not fit 48 KiB of dynamic LDS (> 393 216 validators) sends every row's bit to HBM directly.
-  const size_t lds = (size_t)((c->n_validators + 31) / 32) * 4;
-  t.lds_bitmap = lds <= 49152 ? 1u : 0u;
-  const size_t dyn = t.lds_bitmap ? lds : 0;
+  size_t dyn;
+  t.lds_bitmap = bitmap_in_lds(c->n_validators, &dyn);
   // (a side-stream tally has to FIT next to a resident verdict kernel: the one-workgroup form holds 126 registers in each of its
   // sixteen wavefronts — nothing else fits a compute unit beside it —, the ticket form 42)
   const bool single = grid.x == 1 && t.lds_bitmap && !on;
-  if (single) {
-    if (c->power_words == 1)
-      hipLaunchKernelGGL((ibftk::tally_kernel<1, false>), grid, block, dyn, ts, t);
-    else
-      hipLaunchKernelGGL((ibftk::tally_kernel<4, false>), grid, block, dyn, ts, t);
-  } else {
-    if (c->power_words == 1)
-      hipLaunchKernelGGL((ibftk::tally_kernel<1, true>), grid, block, dyn, ts, t);
-    else
-      hipLaunchKernelGGL((ibftk::tally_kernel<4, true>), grid, block, dyn, ts, t);
-  }
+  with_power_words(c->power_words, [&](auto PW) {
+    if (single) hipLaunchKernelGGL((ibftk::tally_kernel<decltype(PW)::value, false>), grid, block, dyn, ts, t);
+    else hipLaunchKernelGGL((ibftk::tally_kernel<decltype(PW)::value, true>), grid, block, dyn, ts, t);
+  });
   HIPCHK(c, hipGetLastError());
   c->host_direct = c->dh_mask != nullptr && c->tally_slot < 0;  // results of THIS tally are on their way to h_mask / h_tally
-  if ((uint32_t)mask_words(n) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // ... and it zeroed every word that held bits
+  mask_consumed(c, mask_words(n));
   return IBFT_OK;
 }
 
@@ -3123,9 +3141,9 @@ static int enqueue_set_tally(ibft_ctx *c, size_t n, uint32_t half, const set_tai
   if ((rc = wait_proposal_hash(c))) return rc;
   if (t.note_proposer) note_proposer(c, t.proposer20);
   if ((rc = enqueue_tally(c, (uint32_t)n, &sa))) return rc;
-  // the combine kernel zeroed the seal words, the tally the sender words: the mask is clean only if no earlier call left bits
-  // beyond them (the lane kernel stores whole words and asks for no clean mask in front)
-  if ((uint32_t)mask_words(t.half_words ? (size_t)half + n : n) >= c->mask_dirty_words) c->mask_dirty_words = 0;
+  // the combine step zeroed the seal words, the tally the sender words (the lane kernel stores whole words and asks for no
+  // clean mask in front)
+  mask_consumed(c, mask_words(t.half_words ? (size_t)half + n : n));
   if (!c->dh_set)
     HIPCHK(c, hipMemcpyAsync(c->h_set, c->d_set.p, (size_t)mask_words(c->max_rows) * 16, hipMemcpyDeviceToHost, c->stream));
   return IBFT_OK;
@@ -3531,10 +3549,8 @@ int ibft_recover_seals(ibft_ctx *c, const uint8_t *hash32, const uint8_t *sig65,
 // batches in flight take turns at it; the side-tally rule of the seal pipeline (enqueue_tally's `on`) does not apply to them.
 static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t widest, uint64_t *host_mask, uint64_t *out, bool sets,
                                const void *d_block_set = nullptr) {
-  if (c->read_pending) {  // a consumer stream is still copying the previous results (ibft_seals_export_on / exchange)
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
-    c->read_pending = false;
-  }
+  int rc;
+  if ((rc = wait_for_readers(c, c->stream))) return rc;
   const ValFamily &f = c->fam;
   ibftk::block_tally_sets_args t{};
   t.work_mask = (uint64_t *)c->d_mask.p;
@@ -3546,8 +3562,8 @@ static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t w
   t.n = nr;
   t.n_blocks = nb;
   t.n_validators = c->n_validators;  // (under family_view: the union's size)
-  const size_t lds = (size_t)(((sets ? f.largest_set : c->n_validators) + 31) / 32) * 4;
-  t.lds_bitmap = lds <= 49152 ? 1u : 0u;  // beyond: one workgroup walks every block over the HBM bitmap (tally_kernel's bound)
+  size_t dyn;
+  t.lds_bitmap = bitmap_in_lds(sets ? f.largest_set : c->n_validators, &dyn);  // 0: one workgroup walks every block over the HBM bitmap
   t.seen = (uint32_t *)(sets ? f.d_seen.p : c->d_seen.p);
   t.acc = (uint64_t *)c->d_acc.p;
   t.quorum = (const uint64_t *)(sets ? f.d_quorum.p : c->d_quorum.p);
@@ -3556,30 +3572,16 @@ static int enqueue_block_tally(ibft_ctx *c, uint32_t nb, uint32_t nr, uint32_t w
   t.setidx = (const int32_t *)f.d_setidx.p;
   t.set_meta = (const uint2 *)f.d_meta.p;
   const dim3 grid(t.lds_bitmap ? std::min(nb, ibftk::BTALLY_MAX_GRID) : 1u);
-  const size_t dyn = t.lds_bitmap ? lds : 0;
   const bool wide = widest > 256u * ibftk::BTALLY_RPT;  // a block that one step of 256 threads does not cover
   const ibftk::block_tally_args &plain = t;
-#define LAUNCH_BTALLY(PW, THREADS)                                                                                          \
-  do {                                                                                                                      \
-    if (sets)                                                                                                               \
-      hipLaunchKernelGGL((ibftk::block_tally_kernel<PW, THREADS, true>), grid, dim3(THREADS), dyn, c->stream, t);           \
-    else                                                                                                                    \
-      hipLaunchKernelGGL((ibftk::block_tally_kernel<PW, THREADS, false>), grid, dim3(THREADS), dyn, c->stream, plain);      \
-  } while (0)
-  if ((sets ? f.power_words : c->power_words) == 1) {
-    if (wide)
-      LAUNCH_BTALLY(1, 1024);
-    else
-      LAUNCH_BTALLY(1, 256);
-  } else {
-    if (wide)
-      LAUNCH_BTALLY(4, 1024);
-    else
-      LAUNCH_BTALLY(4, 256);
-  }
-#undef LAUNCH_BTALLY
+  with_power_words(sets ? f.power_words : c->power_words, [&](auto PW) {
+    with_int<1024, 256>(wide ? 1024 : 256, [&](auto THREADS) {
+      if (sets) hipLaunchKernelGGL((ibftk::block_tally_kernel<decltype(PW)::value, decltype(THREADS)::value, true>), grid, dim3(decltype(THREADS)::value), dyn, c->stream, t);
+      else hipLaunchKernelGGL((ibftk::block_tally_kernel<decltype(PW)::value, decltype(THREADS)::value, false>), grid, dim3(decltype(THREADS)::value), dyn, c->stream, plain);
+    });
+  });
   HIPCHK(c, hipGetLastError());
-  if ((uint32_t)mask_words(nr) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed every word that held bits
+  mask_consumed(c, mask_words(nr));
   return IBFT_OK;
 }
 
@@ -4307,10 +4309,8 @@ int ibft_verify_senders_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint3
 // wire_row_set_kernel (the rows' sets; rows without one pre-flagged), the verdict launch against the family's union
 // (family_view), wire_sets_tally_kernel (the union verdicts → per-set verdicts, indices and records), one synchronisation.
 static int enqueue_wire_sets_tally(ibft_ctx *c, uint32_t n, uint64_t *out) {
-  if (c->read_pending) {  // a consumer stream is still copying the previous results (ibft_seals_export_on / exchange)
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_read, 0));
-    c->read_pending = false;
-  }
+  int rc;
+  if ((rc = wait_for_readers(c, c->stream))) return rc;
   const ValFamily &f = c->fam;
   const HeightSets &h = c->hsets;
   ibftk::wire_sets_tally_args t{};
@@ -4327,20 +4327,16 @@ static int enqueue_wire_sets_tally(ibft_ctx *c, uint32_t n, uint64_t *out) {
   t.n_sets = f.n_sets;
   t.n_union = c->n_validators;  // (under family_view: the union's size)
   t.seen_words = (f.entries + 31) / 32;
-  const size_t lds = (size_t)t.seen_words * 4;
-  t.lds_bitmap = lds <= ibftk::WSETS_LDS_MAX ? 1u : 0u;
+  size_t dyn;
+  t.lds_bitmap = bitmap_in_lds(f.entries, &dyn);
   t.seen = (uint32_t *)h.d_seen.p;
   t.set_acc = (uint64_t *)h.d_acc.p;
   t.acc = (uint64_t *)c->d_acc.p;
   t.out = out;
   const dim3 grid((n + ibftk::WSETS_ROWS - 1) / ibftk::WSETS_ROWS), block(ibftk::WSETS_THREADS);
-  const size_t dyn = t.lds_bitmap ? lds : 0;
-  if (f.power_words == 1)
-    hipLaunchKernelGGL(ibftk::wire_sets_tally_kernel<1>, grid, block, dyn, c->stream, t);
-  else
-    hipLaunchKernelGGL(ibftk::wire_sets_tally_kernel<4>, grid, block, dyn, c->stream, t);
+  with_power_words(f.power_words, [&](auto PW) { hipLaunchKernelGGL(ibftk::wire_sets_tally_kernel<decltype(PW)::value>, grid, block, dyn, c->stream, t); });
   HIPCHK(c, hipGetLastError());
-  if ((uint32_t)mask_words(n) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed every word that held bits
+  mask_consumed(c, mask_words(n));
   return IBFT_OK;
 }
 
@@ -4433,7 +4429,7 @@ static int enqueue_wire_seals_combine(ibft_ctx *c, uint32_t n, uint32_t half) {
   hipLaunchKernelGGL(ibftk::wire_seals_combine_kernel, dim3((n + ibftk::WSEALS_THREADS - 1) / ibftk::WSEALS_THREADS), dim3(ibftk::WSEALS_THREADS), 0,
                      c->stream, a);
   HIPCHK(c, hipGetLastError());
-  if ((uint32_t)mask_words((size_t)half + n) >= c->mask_dirty_words) c->mask_dirty_words = 0;  // the tally zeroed the sender words, this kernel the seal words
+  mask_consumed(c, mask_words((size_t)half + n));  // the tally zeroed the sender words, this kernel the seal words
   return IBFT_OK;
 }
 
@@ -4472,19 +4468,15 @@ static int enqueue_wire_views(ibft_ctx *c, uint32_t n, uint32_t cap, uint32_t sl
   hipLaunchKernelGGL(ibftk::wire_views_insert_kernel, rows_grid, block, 0, c->stream, a);
   hipLaunchKernelGGL(ibftk::wire_views_rank_kernel, dim3(1), dim3(1024), 0, c->stream, a);
   const dim3 views_grid((cap + ibftk::WVIEWS_THREADS - 1) / ibftk::WVIEWS_THREADS);
-  if (!seals) {
-    if (f.power_words == 1)
-      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<1, false>), rows_grid, block, 0, c->stream, a);
-    else
-      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<4, false>), rows_grid, block, 0, c->stream, a);
-    hipLaunchKernelGGL(ibftk::wire_views_records_kernel<false>, views_grid, block, 0, c->stream, a);
-  } else {
-    if (f.power_words == 1)
-      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<1, true>), rows_grid, block, 0, c->stream, a);
-    else
-      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<4, true>), rows_grid, block, 0, c->stream, a);
-    hipLaunchKernelGGL(ibftk::wire_views_records_kernel<true>, views_grid, block, 0, c->stream, a);
-  }
+  with_power_words(f.power_words, [&](auto PW) {
+    if (!seals) {
+      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<decltype(PW)::value, false>), rows_grid, block, 0, c->stream, a);
+      hipLaunchKernelGGL(ibftk::wire_views_records_kernel<false>, views_grid, block, 0, c->stream, a);
+    } else {
+      hipLaunchKernelGGL((ibftk::wire_views_tally_kernel<decltype(PW)::value, true>), rows_grid, block, 0, c->stream, a);
+      hipLaunchKernelGGL(ibftk::wire_views_records_kernel<true>, views_grid, block, 0, c->stream, a);
+    }
+  });
   HIPCHK(c, hipGetLastError());
   return IBFT_OK;
 }
@@ -5028,12 +5020,11 @@ static int cert_compare_and_judge(ibft_ctx *c, const cert_call &k, cert_plan &p)
   ja.n_roots = (uint32_t)n;
   ja.n_rows = p.rows;
   ja.n_records = p.records;
-  const size_t lds = (size_t)((c->n_validators + 31) / 32) * 4;
-  ja.lds_bitmap = lds <= ibftk::CERT_JUDGE_LDS_MAX ? 1u : 0u;  // beyond: one workgroup walks every record over the HBM bitmap
+  size_t dyn;
+  ja.lds_bitmap = bitmap_in_lds(c->n_validators, &dyn);  // 0: one workgroup walks every record over the HBM bitmap
   ja.seen = (uint32_t *)c->d_seen.p;
   ja.out = (certv::record *)s.rec.p;
   const dim3 grid(ja.lds_bitmap ? std::min(p.records, ibftk::CERT_JUDGE_MAX_GRID) : 1u);
-  const size_t dyn = ja.lds_bitmap ? lds : 0;
   // (the verdict launches of this path are not timed: with kernel timing on, ibft_last_kernel_ms after this call is the two
   // record kernels' time)
   hipEvent_t j0 = nullptr, j1 = nullptr;
@@ -5041,10 +5032,7 @@ static int cert_compare_and_judge(ibft_ctx *c, const cert_call &k, cert_plan &p)
     if ((rc = next_events(c, &j0, &j1))) return rc;
     HIPCHK(c, hipEventRecord(j0, c->stream));
   }
-  if (c->power_words == 1)
-    hipLaunchKernelGGL(ibftk::cert_judge_kernel<1>, grid, dim3(64), dyn, c->stream, ja);
-  else
-    hipLaunchKernelGGL(ibftk::cert_judge_kernel<4>, grid, dim3(64), dyn, c->stream, ja);
+  with_power_words(c->power_words, [&](auto PW) { hipLaunchKernelGGL(ibftk::cert_judge_kernel<decltype(PW)::value>, grid, dim3(64), dyn, c->stream, ja); });
   HIPCHK(c, hipGetLastError());
   if (ja.rec_base) {
     hipLaunchKernelGGL(ibftk::cert_judge_children_kernel, dim3(std::min((uint32_t)n, ibftk::CERT_JUDGE_MAX_GRID)), dim3(64), 0, c->stream, ja.out,

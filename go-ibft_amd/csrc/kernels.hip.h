@@ -1715,18 +1715,127 @@ __global__ void __launch_bounds__(256) cert_compare_kernel(const wire::node_info
 //   [16..16+2·PW) the raw 32-bit piece sums (what the multi-GPU exchange adds across ranks).
 constexpr int TALLY_THREADS = 1024;
 constexpr int TALLY_ROWS_PER_BLOCK = 4096;
-// (TALLY_SUM_WORDS, TALLY_MAX_PIECES, pieces_to_words and words_ge: wire_sets_dev.h, where the CPU harness reaches them)
+// (TALLY_SUM_WORDS, TALLY_MAX_PIECES, pieces_to_words, words_ge and tally_record: tally_dev.h, where the CPU harness reaches them)
 constexpr int TALLY_OUT_WIDE = 5;        // out[5..10)
 constexpr int TALLY_OUT_PIECES = 16;     // out[16..24)
 constexpr int TALLY_OUT_WORDS = 24;
 constexpr int TALLY_ACC_WORDS = TALLY_MAX_PIECES + 4;  // pieces, valid, distinct, ticket, rows sent by the proposer
 constexpr int TALLY_OUT_PROPOSER_ROWS = 10;            // out[10]: valid rows whose sender is the proposer (HasPrepareQuorum)
 constexpr int32_t VIDX_PROPOSER_OUTSIDER = -2;         // lookup_kernel: sender == proposer and the proposer is no validator
+// bytes of dynamic LDS the distinct-sender bitmap of a tally kernel may take: 393 216 entries; beyond, lds_bitmap = 0
+constexpr uint32_t TALLY_BITMAP_LDS_MAX = 48 * 1024;
 
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// ---- what every tally kernel does around its own rows, written once -------------------------------------------------------------
+// (the arithmetic of the record — pieces_to_words, words_ge, tally_record — is tally_dev.h, where the CPU harness reaches it;
+// the scan of one value per thread, block_scan_1024, is cert_scan_dev.h)
+//
+// The distinct-sender claim: a sender's power counts once (a map[string]struct{} in core/validator_manager.go:147-155), so a
+// row counts iff it is the one that set the sender's bit.  bm: a bitmap in LDS (workgroup scope) or in HBM (device scope).
+__device__ __forceinline__ bool claim_first(uint32_t *bm, uint32_t index) {
+  const uint32_t m = 1u << (index & 31);
+  return !(atomicOr(&bm[index >> 5], m) & m);
+}
+// Several workgroups share the set through a bitmap in HBM, but device-scope atomics on one cache line retire at ≈12 ns each —
+// one per ROW made tally_kernel 52 µs at 4 096 rows.  So a workgroup claims in its LDS bitmap first and merges that WORD by
+// word (one returning atomicOr per non-empty word), keeping per word the bits it was the first to set: a row counts iff it
+// was first inside its workgroup (claim_first on lds) AND its workgroup was first for the sender (still_first afterwards).
+// The first barrier is behind every row's claim, the second in front of every re-test.
+template <int THREADS>
+__device__ __forceinline__ void merge_first_bits(uint32_t *lds, uint32_t *hbm, uint32_t words) {
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < words; i += THREADS) {
+    const uint32_t mine = lds[i];
+    if (mine) lds[i] = mine & ~atomicOr(&hbm[i], mine);
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ bool still_first(const uint32_t *lds, uint32_t index) { return (lds[index >> 5] >> (index & 31)) & 1u; }
+
+// "The last workgroup finishes": every workgroup draws one ticket when its work is done; the one that draws the last knows
+// that every other has drawn, and delivers / cleans up for the launch.  True in every thread of that workgroup.
+// What it may conclude depends on what the CALLER ordered in front of the call — two disciplines, each sufficient:
+//   fence     every thread __threadfence()s, then a barrier (block_tally_kernel<SETS>, wire_sets_tally_kernel,
+//             wire_seals_combine_kernel): each thread's earlier stores and atomics are performed device-wide before it passes
+//             the barrier, thread 0 draws behind the barrier, so whoever observes the ticket observes them.
+//   waitcnt   the threads that issued non-returning device-scope atomics wait for vmcnt(0), then a barrier
+//             (tally_kernel<*, true>): a device-scope read-modify-write is performed where it is acknowledged — at the L2,
+//             the one point of coherence of the device — so an acknowledged add is in place before the ticket is drawn, and
+//             returning atomics (the bitmap's atomicOr) were awaited by their users.  It orders atomics only, no plain stores:
+//             enough for tally_kernel, whose workgroups hand each other nothing else, and cheaper than a fence per thread.
+// (block_tally_kernel without SETS orders nothing in front: its workgroups only READ what the last one then clears, and a
+// load whose value was used has completed.)
+// The block and sets tallies let thread 0 fence once more directly in front of its draw, as they always have: that line
+// stays at their call sites too, and it is all the plain block tally has.  The last workgroup reads what the others added
+// with device-scope atomics.
+template <class T>
+__device__ __forceinline__ bool draw_last_ticket(T *ticket, uint32_t &last_flag) {
+  if (threadIdx.x == 0) {
+    T t;
+    if constexpr (sizeof(T) == 8) t = (T)atomicAdd(reinterpret_cast<unsigned long long *>(ticket), 1ull);
+    else t = atomicAdd(ticket, (T)1);
+    last_flag = (t == (T)gridDim.x - (T)1) ? 1u : 0u;
+  }
+  __syncthreads();
+  return last_flag != 0;
+}
+// … and the last workgroup leaves the ticket zero for the next launch.
+template <class T>
+__device__ __forceinline__ void reset_ticket(T *ticket) {
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, (T)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The verdict kernels accumulate into work_mask (atomicOr / ballot words).  A tally CONSUMES it: word i moves to `mask`, to
+// host_mask (mapped pinned host memory) when given, and work_mask is left zero for the next launch.  ATOMIC: under a family
+// of sets other workgroups atomic-AND other bits of the same word, so the word is read with a device-scope atomic load.
+template <bool ATOMIC>
+__device__ __forceinline__ uint64_t verdict_word(const uint64_t *work_mask, uint32_t i) {
+  if constexpr (ATOMIC) return __hip_atomic_load(work_mask + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return work_mask[i];
+}
+__device__ __forceinline__ void hand_over_word(uint64_t *work_mask, uint64_t *mask, uint64_t *host_mask, uint32_t i, uint64_t w) {
+  work_mask[i] = 0;
+  mask[i] = w;
+  if (host_mask) host_mask[i] = w;
+}
+template <bool ATOMIC, int THREADS>
+__device__ __forceinline__ void hand_over_words(uint64_t *work_mask, uint64_t *mask, uint64_t *host_mask, uint32_t words) {
+  for (uint32_t i = threadIdx.x; i < words; i += THREADS) hand_over_word(work_mask, mask, host_mask, i, verdict_word<ATOMIC>(work_mask, i));
+}
+
+// A workgroup's sums: every wavefront leaves its sum of v in row[wave] (wave_part), and behind a barrier one thread adds the
+// wavefronts' parts (parts_total).  on = false (launch-uniform): nobody has anything to add, the part is 0 without the shuffles.
+// block_sum / block_totals: the NP power pieces at once; the pieces beyond NP are 0.  block_tally_kernel writes its totals out
+// itself: through block_totals its <4, 1024> instantiations (8 × 16 parts) spill, as plain loops in the kernel they do not.
+template <int WAVES>
+__device__ __forceinline__ void wave_part(uint64_t (&row)[WAVES], uint64_t v, bool on = true) {
+  const uint64_t sum = on ? wave_sum_u64(v) : 0ull;
+  if ((threadIdx.x & 63u) == 0) row[threadIdx.x >> 6] = sum;
+}
+template <int WAVES>
+__device__ __forceinline__ uint64_t parts_total(const uint64_t (&row)[WAVES]) {
+  uint64_t sum = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; w++) sum += row[w];
+  return sum;
+}
+template <int NP, int ROWS, int WAVES>
+__device__ __forceinline__ void block_sum(uint64_t (&part)[ROWS][WAVES], const uint64_t (&p)[NP]) {
+#pragma unroll
+  for (int k = 0; k < NP; k++) wave_part(part[k], p[k]);
+}
+template <int NP, int ROWS, int WAVES>
+__device__ __forceinline__ void block_totals(const uint64_t (&part)[ROWS][WAVES], uint64_t (&piece)[TALLY_MAX_PIECES]) {
+#pragma unroll
+  for (int k = 0; k < TALLY_MAX_PIECES; k++) {
+    piece[k] = 0;
+    if (k < NP) piece[k] = parts_total(part[k]);
+  }
 }
 
 // After the verdict launch of a message set: word w of the work mask holds the envelope verdicts of rows 64w.., word
@@ -1837,8 +1946,7 @@ __global__ void __launch_bounds__(TALLY_THREADS) tally_kernel(tally_args a) {
     const uint32_t row = row0 + (uint32_t)j * TALLY_THREADS + tid;
     vi[j] = row < a.n ? a.vidx[row] : -1;
   }
-  // The verdict kernels accumulate into work_mask (atomicOr / ballot words).  The tally CONSUMES it: the words
-  // move to `mask`, to host_mask when given, and work_mask is left zeroed for the next launch.
+  // the tally consumes the work mask (hand_over_word): every workgroup the words of its own rows
   if (a.set_on) {
     // every wavefront combines its share of the workgroup's verdict words; all loads first, then the ballots and stores
     constexpr int WPW = (TALLY_ROWS_PER_BLOCK / 64) / (TALLY_THREADS / 64);  // words per wavefront
@@ -1860,11 +1968,7 @@ __global__ void __launch_bounds__(TALLY_THREADS) tally_kernel(tally_args a) {
       uint64_t w = 0;
       if (wi < total_words) {  // wave-uniform
         w = set_finish_word(a.set, a.work_mask, wi, ln, fl[q], sw[q], lw[q]);
-        if (ln == 0) {
-          a.work_mask[wi] = 0;
-          a.mask[wi] = w;
-          if (a.host_mask) a.host_mask[wi] = w;
-        }
+        if (ln == 0) hand_over_word(a.work_mask, a.mask, a.host_mask, wi, w);
       }
       if (ln == 0) wds[k] = w;
     }
@@ -1873,9 +1977,7 @@ __global__ void __launch_bounds__(TALLY_THREADS) tally_kernel(tally_args a) {
     uint64_t w = 0;
     if (wi < total_words) {
       w = a.work_mask[wi];
-      a.work_mask[wi] = 0;
-      a.mask[wi] = w;
-      if (a.host_mask) a.host_mask[wi] = w;
+      hand_over_word(a.work_mask, a.mask, a.host_mask, wi, w);
     }
     wds[tid] = w;
   }
@@ -1905,38 +2007,19 @@ __global__ void __launch_bounds__(TALLY_THREADS) tally_kernel(tally_args a) {
       const bool is_prepare = !(a.set_on && a.set.no_seal) || a.set.no_seal[row0 + lr] != 0;
       if (is_prepare) by_proposer++;
     }
-    if (bit && vi[j] >= 0) {  // unknown senders contribute 0 (validator_manager.go:88-92)
-      const uint32_t m = 1u << (vi[j] & 31);
-      const uint32_t old = a.lds_bitmap ? atomicOr(&lseen[vi[j] >> 5], m)
-                                        : atomicOr(&a.seen[vi[j] >> 5], m);  // device scope (huge sets only)
-      first[j] = !(old & m);  // distinct-sender set (validator_manager.go:147-155)
-    }
+    if (bit && vi[j] >= 0)  // unknown senders contribute 0 (validator_manager.go:88-92); HBM: device scope (huge sets only)
+      first[j] = a.lds_bitmap ? claim_first(lseen, (uint32_t)vi[j]) : claim_first(a.seen, (uint32_t)vi[j]);
   }
   // the proposer's seat in the sender set: one more "row" of thread 0 of the first workgroup
   bool pfirst = false;
-  if (a.prop_on && a.prop_seat && a.prop_vidx >= 0 && blockIdx.x == 0 && tid == 0) {
-    const uint32_t m = 1u << (a.prop_vidx & 31);
-    const uint32_t old = a.lds_bitmap ? atomicOr(&lseen[a.prop_vidx >> 5], m) : atomicOr(&a.seen[a.prop_vidx >> 5], m);
-    pfirst = !(old & m);
-  }
-  if (MULTI && a.lds_bitmap) {
-    // Several workgroups: the set is shared through a bitmap in HBM, but device-scope atomics on one cache line
-    // retire at ≈12 ns each — one per ROW made this kernel 52 µs at 4 096 rows.  So the workgroup merges its LDS
-    // bitmap WORD by word (one returning atomicOr per non-empty word) and keeps, per word, the bits it was the
-    // first to set: a row counts iff it was first inside its workgroup AND its workgroup was first for the validator.
-    __syncthreads();
-    for (uint32_t i = tid; i < seen_words; i += TALLY_THREADS) {
-      const uint32_t mine = lseen[i];
-      if (mine) lseen[i] = mine & ~atomicOr(&a.seen[i], mine);
-    }
-    __syncthreads();
+  if (a.prop_on && a.prop_seat && a.prop_vidx >= 0 && blockIdx.x == 0 && tid == 0)
+    pfirst = a.lds_bitmap ? claim_first(lseen, (uint32_t)a.prop_vidx) : claim_first(a.seen, (uint32_t)a.prop_vidx);
+  if (MULTI && a.lds_bitmap) {  // several workgroups: the set is shared through the bitmap in HBM
+    merge_first_bits<TALLY_THREADS>(lseen, a.seen, seen_words);
 #pragma unroll
     for (int j = 0; j < RPT; j++)
-    {
-      const uint32_t v = first[j] ? (uint32_t)vi[j] : 0u;  // (first[j] implies vi[j] ≥ 0)
-      first[j] = first[j] && ((lseen[v >> 5] >> (v & 31)) & 1u);
-    }
-    if (pfirst) pfirst = (lseen[a.prop_vidx >> 5] >> (a.prop_vidx & 31)) & 1u;
+      first[j] = first[j] && still_first(lseen, first[j] ? (uint32_t)vi[j] : 0u);  // (first[j] implies vi[j] ≥ 0)
+    if (pfirst) pfirst = still_first(lseen, (uint32_t)a.prop_vidx);
   }
   uint64_t p[NP];
 #pragma unroll
@@ -1953,25 +2036,15 @@ __global__ void __launch_bounds__(TALLY_THREADS) tally_kernel(tally_args a) {
 #pragma unroll
     for (int k = 0; k < NP; k++) p[k] += pw[j][k];
   }
-  const uint32_t wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-  for (int k = 0; k < NP; k++) {
-    const uint64_t sum = wave_sum_u64(p[k]);
-    if (lane == 0) part[k][wave] = sum;
-  }
-  {
-    const uint64_t cnt = wave_sum_u64(valid | (distinct << 32));
-    if (lane == 0) part[NP][wave] = cnt;
-    const uint64_t bp = a.prop_on ? wave_sum_u64((uint64_t)by_proposer) : 0ull;  // (prop_on is launch-uniform)
-    if (lane == 0) part[NP + 1][wave] = bp;
-  }
+  block_sum(part, p);
+  wave_part(part[NP], valid | (distinct << 32));
+  wave_part(part[NP + 1], (uint64_t)by_proposer, a.prop_on);
   __syncthreads();
   uint64_t piece[TALLY_MAX_PIECES];
   uint64_t v = 0, d = 0, proposer_rows = 0;
   if (MULTI) {
     if (tid <= NP + 1) {  // thread k adds piece k (thread NP: the two counters, NP + 1: the proposer's rows) of this workgroup to the launch-wide sums
-      uint64_t sum = 0;
-      for (int w = 0; w < TALLY_THREADS / 64; w++) sum += part[tid][w];
+      const uint64_t sum = parts_total(part[tid]);
       if (tid < NP) {
         if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + tid), (unsigned long long)sum);
       } else if (tid == NP + 1) {
@@ -1980,17 +2053,10 @@ __global__ void __launch_bounds__(TALLY_THREADS) tally_kernel(tally_args a) {
         if (sum & 0xFFFFFFFFull) atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES), (unsigned long long)(sum & 0xFFFFFFFFull));
         if (sum >> 32) atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES + 1), (unsigned long long)(sum >> 32));
       }
-      // the adds return nothing: wait until the memory side has acknowledged them before this workgroup's ticket
-      // can be drawn (device-scope read-modify-writes are performed where they are acknowledged)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // draw_last_ticket's "waitcnt" discipline: the adds return nothing
     }
     __syncthreads();  // the bitmap atomics returned values (awaited by their users), the adds were awaited above
-    if (tid == 0) {
-      const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES + 2), 1ull);
-      last_flag = (t == (unsigned long long)gridDim.x - 1ull) ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!last_flag) return;
+    if (!draw_last_ticket(a.acc + TALLY_MAX_PIECES + 2, last_flag)) return;
     // ---- the last workgroup: every other one has added its pieces and set its bits ----
     for (uint32_t i = tid; i < (a.n_validators + 31) / 32; i += TALLY_THREADS) {
       if (a.seen_out) a.seen_out[i] = __hip_atomic_load(a.seen + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2010,29 +2076,17 @@ __global__ void __launch_bounds__(TALLY_THREADS) tally_kernel(tally_args a) {
     if (a.seen_out)  // (the barrier above is behind every row's atomicOr)
       for (uint32_t i = tid; i < seen_words; i += TALLY_THREADS) a.seen_out[i] = lseen[i];
     if (tid != 0) return;
-#pragma unroll
-    for (int k = 0; k < TALLY_MAX_PIECES; k++) {
-      piece[k] = 0;
-      if (k < NP)
-        for (int w = 0; w < TALLY_THREADS / 64; w++) piece[k] += part[k][w];
-    }
-    uint64_t c = 0;
-    for (int w = 0; w < TALLY_THREADS / 64; w++) {
-      c += part[NP][w];
-      proposer_rows += part[NP + 1][w];
-    }
+    block_totals<NP>(part, piece);
+    const uint64_t c = parts_total(part[NP]);
+    proposer_rows = parts_total(part[NP + 1]);
     v = c & 0xFFFFFFFFull;
     d = c >> 32;
   }
-  uint64_t w[TALLY_SUM_WORDS];
-  pieces_to_words(piece, NP, w);
-  // a PREPARE from the proposer among the valid ones: no quorum, whatever the power (validator_manager.go:114-121)
-  const uint64_t hq = (words_ge(w, a.quorum) && proposer_rows == 0) ? 1 : 0;
-  const uint64_t c = (v & 0xFFFFFFFFull) | (d << 32);
-  a.out[0] = w[0];
-  a.out[1] = w[1];
-  a.out[2] = c;
-  a.out[3] = hq;
+  uint64_t w[TALLY_SUM_WORDS], rec[4];
+  tally_record(piece, NP, (v & 0xFFFFFFFFull) | (d << 32), a.quorum, proposer_rows, rec, w);
+  const uint64_t c = rec[2], hq = rec[3];
+#pragma unroll
+  for (int i = 0; i < 4; i++) a.out[i] = rec[i];
 #pragma unroll
   for (int i = 0; i < TALLY_SUM_WORDS; i++) a.out[TALLY_OUT_WIDE + i] = w[i];
 #pragma unroll
@@ -2083,8 +2137,8 @@ __global__ void __launch_bounds__(256) block_head_kernel(block_head_args a) {
 // the HBM-bitmap form runs ONE workgroup over all blocks, the bitmap being a single zeroed `seen`): distinct-sender bitmap
 // cleared, the block's rows walked, 2·PW 32-bit power pieces reduced through wave_sum_u64 and LDS, thread 0 recombines them
 // and writes the block's record {power_lo, power_hi, valid | distinct << 32, has_quorum}.
-// The work mask is read by several workgroups (block boundaries do not fall on verdict words), so it is moved and zeroed by
-// the LAST workgroup to finish (a ticket in acc[TALLY_MAX_PIECES + 2], left zero again): no word is cleared under a reader.
+// The work mask is read by several workgroups (block boundaries do not fall on verdict words), so it is handed over by
+// the LAST workgroup to finish (draw_last_ticket on acc[TALLY_MAX_PIECES + 2], left zero again): no word is cleared under a reader.
 // THREADS: 256 for blocks of chain-sized seal sets, 1024 when a block has more rows than that (the host picks); a thread
 // takes BTALLY_RPT rows per step and issues their loads together (verdict word, validator index, then the powers of the rows
 // whose bit is set) — one dependent round trip per step instead of one per row.  Row r of a block belongs to thread
@@ -2131,13 +2185,8 @@ __global__ void __launch_bounds__(THREADS)
   extern __shared__ uint32_t lseen[];
   __shared__ uint64_t part[NP + 1][WAVES];
   __shared__ uint32_t last_flag;
-  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint32_t tid = threadIdx.x;
   uint32_t *bm = a.lds_bitmap ? lseen : a.seen;
-  // a verdict word: under a family other workgroups may atomic-AND other bits of the same word
-  auto mask_word = [&](uint32_t i) -> uint64_t {
-    if constexpr (SETS) return __hip_atomic_load(a.work_mask + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return a.work_mask[i];
-  };
   // does the row add to its block's power?  (the index is only meaningful where the verdict bit is set; valsets_row says −1 elsewhere)
   auto counts = [](const valsets_row_t &s) { return (SETS || s.bit) && s.si >= 0; };
   for (uint32_t b = blockIdx.x; b < a.n_blocks; b += gridDim.x) {
@@ -2164,7 +2213,7 @@ __global__ void __launch_bounds__(THREADS)
 #pragma unroll
       for (int j = 0; j < BTALLY_RPT; j++) {
         const uint32_t r = base + (uint32_t)j * THREADS + tid;
-        bit[j] = r < r1 && ((mask_word(r >> 6) >> (r & 63)) & 1ull);
+        bit[j] = r < r1 && ((verdict_word<SETS>(a.work_mask, r >> 6) >> (r & 63)) & 1ull);
         vi[j] = r < r1 ? a.vidx[r] : -1;
         if constexpr (!SETS) sr[j] = valsets_row_t{vi[j], bit[j], false};  // the one set: the row as the verdict kernel left it
       }
@@ -2186,20 +2235,14 @@ __global__ void __launch_bounds__(THREADS)
         }
         valid += sr[j].bit;
         if (!counts(sr[j])) continue;  // unknown signers contribute 0 (validator_manager.go:88-92)
-        const uint32_t m = 1u << (sr[j].si & 31);
-        if (atomicOr(&bm[sr[j].si >> 5], m) & m) continue;  // a signer's power counts once per block (:147-155)
+        if (!claim_first(bm, (uint32_t)sr[j].si)) continue;  // a signer's power counts once per block (:147-155)
         distinct++;
 #pragma unroll
         for (int k = 0; k < NP; k++) p[k] += pw[j][k];
       }
     }
-#pragma unroll
-    for (int k = 0; k < NP; k++) {
-      const uint64_t s = wave_sum_u64(p[k]);
-      if (lane == 0) part[k][wave] = s;
-    }
-    const uint64_t cnt = wave_sum_u64(valid | (distinct << 32));
-    if (lane == 0) part[NP][wave] = cnt;
+    block_sum(part, p);
+    wave_part(part[NP], valid | (distinct << 32));
     __syncthreads();
     if (!a.lds_bitmap)  // the HBM bitmap is left zero for the next block: clear exactly the words this block set
       for (uint32_t r = r0 + tid; r < r1; r += THREADS) {
@@ -2211,7 +2254,7 @@ __global__ void __launch_bounds__(THREADS)
         }
       }
     if (tid == 0) {
-      uint64_t piece[TALLY_MAX_PIECES], c = 0;
+      uint64_t piece[TALLY_MAX_PIECES], c = 0;  // (not block_totals: see there)
 #pragma unroll
       for (int k = 0; k < TALLY_MAX_PIECES; k++) {
         piece[k] = 0;
@@ -2219,36 +2262,19 @@ __global__ void __launch_bounds__(THREADS)
           for (int w = 0; w < WAVES; w++) piece[k] += part[k][w];
       }
       for (int w = 0; w < WAVES; w++) c += part[NP][w];
-      uint64_t wd[TALLY_SUM_WORDS];
-      pieces_to_words(piece, NP, wd);
-      uint64_t *o = a.out + 4ull * b;
-      o[0] = wd[0];
-      o[1] = wd[1];
-      o[2] = c;
-      o[3] = words_ge(wd, a.quorum + (size_t)set * TALLY_SUM_WORDS) ? 1ull : 0ull;
+      tally_record(piece, NP, c, a.quorum + (size_t)set * TALLY_SUM_WORDS, 0ull, a.out + 4ull * b);
     }
     __syncthreads();  // part[] and the bitmap are reused by the next block
   }
   // ---- every workgroup has read its rows' verdict words (and cleared what it had to): the last one moves and zeroes them ----
-  if constexpr (SETS) {
-    __threadfence();  // (every thread: its atomic ANDs are performed before the ticket is taken)
+  if constexpr (SETS) {  // draw_last_ticket's "fence" discipline: every thread's atomic ANDs are performed before the ticket is drawn
+    __threadfence();
     __syncthreads();
   }
-  if (tid == 0) {
-    __threadfence();
-    const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES + 2), 1ull);
-    last_flag = (t == (unsigned long long)gridDim.x - 1ull) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!last_flag) return;
-  const uint32_t words = (a.n + 63) / 64;
-  for (uint32_t i = tid; i < words; i += THREADS) {
-    const uint64_t w = mask_word(i);
-    a.work_mask[i] = 0;
-    a.mask[i] = w;
-    if (a.host_mask) a.host_mask[i] = w;
-  }
-  if (tid == 0) __hip_atomic_store(a.acc + TALLY_MAX_PIECES + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) __threadfence();
+  if (!draw_last_ticket(a.acc + TALLY_MAX_PIECES + 2, last_flag)) return;
+  hand_over_words<SETS, THREADS>(a.work_mask, a.mask, a.host_mask, (a.n + 63) / 64);
+  reset_ticket(a.acc + TALLY_MAX_PIECES + 2);
 }
 
 // ---- the live route under a family of sets (ibft_verify_senders_wire_sets; the row bodies: wire_sets_dev.h) -----------------
@@ -2271,26 +2297,25 @@ __global__ void __launch_bounds__(256) wire_row_set_kernel(const wire::row_info 
 //   per row      wire_sets_row: the verdict under the row's set (an atomic AND where a member of the union outside the set
 //                loses its bit), the index column rewritten from union to set index, the member's entry in the family's
 //                packed columns (set_meta[s].x + index).
-//   distinct     one bit per (set, member) ENTRY — the bitmap spans the whole family, ⌈Σ set sizes / 32⌉ words.  As in
-//                tally_kernel a workgroup collects its rows' bits in LDS and merges them into the HBM bitmap word by word,
-//                keeping the bits it was first to set: a row adds its power iff it was first in its workgroup and its
-//                workgroup first for the entry.  A family whose bitmap does not fit WSETS_LDS_MAX (more than 393 216
-//                entries) sends every counting row's bit to HBM directly (lds_bitmap = 0).
+//   distinct     one bit per (set, member) ENTRY — the bitmap spans the whole family, ⌈Σ set sizes / 32⌉ words: claim_first
+//                in LDS, merge_first_bits, still_first.  A family whose bitmap does not fit TALLY_BITMAP_LDS_MAX (more than
+//                393 216 entries) sends every counting row's bit to HBM directly (lds_bitmap = 0).
 //   sums         a wavefront reduces the rows of one set at a time — every thread first adds up those of its four rows that
 //                belong to the turn's set (the set of the first lane that still waits; a receive queue mixes two or three
-//                heights, so two or three turns per 256 rows) — and the leader adds valid | distinct << 32 and, only where a
+//                heights, so two or three turns per 256 rows; wire_views_tally_kernel has the same turn with one row per
+//                thread and a bounded number of turns — through one helper that kernel takes 12–16 registers more, so the
+//                turn is written out in both) — and the leader adds valid | distinct << 32 and, only where a
 //                row was first, the 2·PW pieces to the set's accumulators in HBM: NP + 1 words per set.
 //   work         O(n + n_sets) for the rows and the records; on top of that every workgroup of the LDS form zeroes and scans
 //                the whole bitmap once: ⌈n / 1 024⌉ · ⌈entries / 32⌉ LDS words in all — 7 words per workgroup for two sets of
 //                100, 3 200 for 1 024 sets of 100, 12 288 at the LDS cap — and the last workgroup its entries / 32 HBM words.
-//   the end      the workgroup that draws the last ticket (block_tally_kernel's discipline: every thread fences its atomics,
-//                then one ticket per workgroup in acc[TALLY_MAX_PIECES + 2]) moves and zeroes the work mask, turns every
-//                set's accumulators into tally_kernel's record against the set's quorum and zeroes them, and zeroes the
+//   the end      the workgroup that draws the last ticket (draw_last_ticket, "fence" discipline; the ticket is
+//                acc[TALLY_MAX_PIECES + 2]) hands the work mask over, turns every set's accumulators into the record
+//                (tally_record against the set's quorum) and zeroes them, and zeroes the
 //                bitmap — by its words in the LDS form, by the rows' entries (re-read from the rewritten index column) in
 //                the HBM form — and the ticket: all scratch is zero again when the kernel ends.
 constexpr int WSETS_THREADS = 256, WSETS_RPT = 4;
 constexpr uint32_t WSETS_ROWS = WSETS_THREADS * WSETS_RPT;
-constexpr uint32_t WSETS_LDS_MAX = 49152;
 struct wire_sets_tally_args {
   uint64_t *work_mask;         // verdict words of the launch; consumed (moved to mask / host_mask, zeroed) here
   uint64_t *mask, *host_mask;  // host_mask: mapped pinned host memory or null
@@ -2315,8 +2340,6 @@ __global__ void __launch_bounds__(WSETS_THREADS) wire_sets_tally_kernel(wire_set
   __shared__ uint32_t last_flag;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t row0 = blockIdx.x * WSETS_ROWS;
-  // a verdict word: other workgroups may atomic-AND other bits of the same word
-  auto mask_word = [&](uint32_t i) -> uint64_t { return __hip_atomic_load(a.work_mask + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
   if (a.lds_bitmap)
     for (uint32_t i = tid; i < a.seen_words; i += WSETS_THREADS) wseen[i] = 0;
   bool bit[WSETS_RPT];
@@ -2327,7 +2350,7 @@ __global__ void __launch_bounds__(WSETS_THREADS) wire_sets_tally_kernel(wire_set
 #pragma unroll
   for (int j = 0; j < WSETS_RPT; j++) {
     const uint32_t r = row0 + (uint32_t)j * WSETS_THREADS + tid;
-    bit[j] = r < a.n && ((mask_word(r >> 6) >> (r & 63)) & 1ull);
+    bit[j] = r < a.n && ((verdict_word<true>(a.work_mask, r >> 6) >> (r & 63)) & 1ull);
     vi[j] = r < a.n ? a.vidx[r] : -1;
     set[j] = r < a.n ? a.row_set[r] : -1;
   }
@@ -2349,23 +2372,12 @@ __global__ void __launch_bounds__(WSETS_THREADS) wire_sets_tally_kernel(wire_set
   bool first[WSETS_RPT];
 #pragma unroll
   for (int j = 0; j < WSETS_RPT; j++) {
-    first[j] = false;
-    if (!sr[j].counts) continue;
-    const uint32_t m = 1u << (sr[j].entry & 31);
-    first[j] = !(atomicOr(&bm[sr[j].entry >> 5], m) & m);  // a signer's power counts once per set (validator_manager.go:147-155)
+    first[j] = sr[j].counts && claim_first(bm, sr[j].entry);  // a signer's power counts once per set (validator_manager.go:147-155)
   }
-  if (a.lds_bitmap) {  // (launch-uniform) the workgroup's words → the HBM bitmap; what stays in LDS: the bits it was first to set
-    __syncthreads();
-    for (uint32_t i = tid; i < a.seen_words; i += WSETS_THREADS) {
-      const uint32_t mine = wseen[i];
-      if (mine) wseen[i] = mine & ~atomicOr(&a.seen[i], mine);
-    }
-    __syncthreads();
+  if (a.lds_bitmap) {  // (launch-uniform)
+    merge_first_bits<WSETS_THREADS>(wseen, a.seen, a.seen_words);
 #pragma unroll
-    for (int j = 0; j < WSETS_RPT; j++) {
-      const uint32_t e = first[j] ? sr[j].entry : 0u;
-      first[j] = first[j] && ((wseen[e >> 5] >> (e & 31)) & 1u);
-    }
+    for (int j = 0; j < WSETS_RPT; j++) first[j] = first[j] && still_first(wseen, first[j] ? sr[j].entry : 0u);
   }
   // a thread's four rows and a wavefront's 64 threads, one set per turn: the set of the first lane that still holds a valid row
   uint32_t pend = 0;  // the thread's valid rows not yet added
@@ -2403,22 +2415,11 @@ __global__ void __launch_bounds__(WSETS_THREADS) wire_sets_tally_kernel(wire_set
     if ((int)lane == leader) atomicAdd(reinterpret_cast<unsigned long long *>(acc + NP), (unsigned long long)cnt);
   }
   // ---- every workgroup has judged its rows: the last one delivers ----
-  __threadfence();  // (every thread: its atomics and its index stores are performed before the ticket is taken)
+  __threadfence();  // draw_last_ticket's "fence" discipline: every thread's atomics and index stores
   __syncthreads();
-  if (tid == 0) {
-    __threadfence();
-    const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long *>(a.acc + TALLY_MAX_PIECES + 2), 1ull);
-    last_flag = (t == (unsigned long long)gridDim.x - 1ull) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!last_flag) return;
-  const uint32_t words = (a.n + 63) / 64;
-  for (uint32_t i = tid; i < words; i += WSETS_THREADS) {
-    const uint64_t w = mask_word(i);
-    a.work_mask[i] = 0;
-    a.mask[i] = w;
-    if (a.host_mask) a.host_mask[i] = w;
-  }
+  if (tid == 0) __threadfence();
+  if (!draw_last_ticket(a.acc + TALLY_MAX_PIECES + 2, last_flag)) return;
+  hand_over_words<true, WSETS_THREADS>(a.work_mask, a.mask, a.host_mask, (a.n + 63) / 64);
   for (uint32_t s = tid; s < a.n_sets; s += WSETS_THREADS) {
     uint64_t *acc = a.set_acc + (size_t)s * (NP + 1);
     uint64_t piece[NP];
@@ -2430,7 +2431,7 @@ __global__ void __launch_bounds__(WSETS_THREADS) wire_sets_tally_kernel(wire_set
       for (int k = 0; k <= NP; k++) __hip_atomic_store(acc + k, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     uint64_t rec[4];
-    wire_sets_record(piece, NP, cnt, a.quorum + (size_t)s * TALLY_SUM_WORDS, rec);
+    tally_record(piece, NP, cnt, a.quorum + (size_t)s * TALLY_SUM_WORDS, 0ull, rec);
     uint64_t *o = a.out + 4ull * s;
 #pragma unroll
     for (int i = 0; i < 4; i++) o[i] = rec[i];
@@ -2446,7 +2447,7 @@ __global__ void __launch_bounds__(WSETS_THREADS) wire_sets_tally_kernel(wire_set
       if (s >= 0 && v >= 0) __hip_atomic_store(a.seen + ((a.set_meta[s].x + (uint32_t)v) >> 5), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  if (tid == 0) __hip_atomic_store(a.acc + TALLY_MAX_PIECES + 2, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  reset_ticket(a.acc + TALLY_MAX_PIECES + 2);
 }
 
 // ---- the live route's quorum records (ibft_verify_senders_wire_views; the row bodies: wire_views_dev.h) ---------------------
@@ -2501,15 +2502,7 @@ __global__ void __launch_bounds__(1024) wire_views_rank_kernel(wire_views_args a
   const uint32_t b = t * per < a.n ? t * per : a.n, e = b + per < a.n ? b + per : a.n;
   uint32_t sum = 0;
   for (uint32_t i = b; i < e; i++) sum += wviews::is_rep(a.key_table, a.slot_key[i], i) ? 1u : 0u;
-  part[t] = sum;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024u; o <<= 1) {
-    const uint32_t v = t >= o ? part[t - o] : 0u;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = part[t] - sum;
+  uint32_t run = block_scan_1024(part, sum) - sum;
   for (uint32_t i = b; i < e; i++) {
     if (!wviews::is_rep(a.key_table, a.slot_key[i], i)) continue;
     a.rank_of[i] = run;
@@ -2638,15 +2631,7 @@ __global__ void __launch_bounds__(1024) wire_seals_scan_kernel(wire_seals_args a
     const uint8_t f = a.flags[i];
     sum += (uint64_t)((f & wseals::ROW_SEALABLE) ? 1u : 0u) | ((uint64_t)((f & wseals::ROW_COMMIT) ? 1u : 0u) << 32);
   }
-  part[t] = sum;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024u; o <<= 1) {
-    const uint64_t v = t >= o ? part[t - o] : 0ull;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = (uint32_t)(part[t] - sum);
+  uint32_t run = (uint32_t)(block_scan_1024(part, sum) - sum);
   for (uint32_t i = b; i < e; i++) {
     const bool sealable = a.flags[i] & wseals::ROW_SEALABLE;
     a.seal_row[i] = sealable ? run : wseals::NONE;
@@ -2685,16 +2670,11 @@ __global__ void __launch_bounds__(WSEALS_THREADS) wire_seals_combine_kernel(wire
   const uint64_t w = __ballot(bit ? 1 : 0);
   if (lane == 0 && (row >> 6) < words) a.seal_mask[row >> 6] = w;
   // ---- every workgroup has read its seal verdicts: the last one zeroes them ----
-  __threadfence();
+  __threadfence();  // draw_last_ticket's "fence" discipline
   __syncthreads();
-  if (tid == 0) {
-    const uint32_t t = atomicAdd(a.words + 2, 1u);
-    last_flag = (t == gridDim.x - 1u) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!last_flag) return;
+  if (!draw_last_ticket(a.words + 2, last_flag)) return;
   for (uint32_t i = tid; i < words; i += WSEALS_THREADS) seal_words[i] = 0;
-  if (tid == 0) a.words[2] = 0;
+  reset_ticket(a.words + 2);
 }
 
 // ---- certificates: one record per carrier (ibft_judge_certificates_wire; the rules: cert_verdict_dev.h) ---------------------
@@ -2717,15 +2697,7 @@ __global__ void __launch_bounds__(1024) cert_record_scan_kernel(const wire::node
   const uint32_t b = t * per < n_roots ? t * per : n_roots, e = b + per < n_roots ? b + per : n_roots;
   uint32_t sum = 0;
   for (uint32_t i = b; i < e; i++) sum += cert_rcc_children(nodes, i, rows_bound);
-  part[t] = sum;
-  __syncthreads();
-  for (uint32_t o = 1; o < 1024u; o <<= 1) {
-    const uint32_t v = t >= o ? part[t - o] : 0u;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = n_roots + part[t] - sum;
+  uint32_t run = n_roots + block_scan_1024(part, sum) - sum;
   for (uint32_t i = b; i < e; i++) {
     rec_base[i] = run;
     run += cert_rcc_children(nodes, i, rows_bound);
@@ -2738,7 +2710,6 @@ __global__ void __launch_bounds__(1024) cert_record_scan_kernel(const wire::node
   }
 }
 
-constexpr uint32_t CERT_JUDGE_LDS_MAX = 49152;     // bytes of LDS the distinct-validator bitmap may take (393 216 validators)
 constexpr uint32_t CERT_JUDGE_MAX_GRID = 1u << 16;  // workgroups of one launch (each takes records r, r + grid, …)
 struct cert_judge_args {
   const wire::node_info *nodes;
@@ -2822,8 +2793,7 @@ __global__ void __launch_bounds__(64) cert_judge_kernel(cert_judge_args a) {
         if (!sb) continue;
         const int vi = cert_row_validator(a, w);
         if (vi < 0 || (uint32_t)vi >= a.n_validators) continue;
-        const uint32_t m = 1u << (vi & 31);
-        if (atomicOr(&bm[vi >> 5], m) & m) continue;  // the same validator twice
+        if (!claim_first(bm, (uint32_t)vi)) continue;  // the same validator twice
         counts += 1;
 #pragma unroll
         for (int k = 0; k < NP; k++) pw[k] += a.vpower32[(size_t)vi * NP + k];
@@ -3061,43 +3031,18 @@ __global__ void __launch_bounds__(XUNPACK_THREADS) exchange_unpack_kernel(exchan
       }
     }
   }
-  const uint32_t wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-  for (int k = 0; k < TALLY_MAX_PIECES; k++) {
-    const uint64_t sum = wave_sum_u64(p[k]);
-    if (lane == 0) part[k][wave] = sum;
-  }
-  {
-    const uint64_t sd = wave_sum_u64(distinct), so = wave_sum_u64(overlap);
-    if (lane == 0) {
-      part[TALLY_MAX_PIECES][wave] = sd;
-      part[TALLY_MAX_PIECES + 1][wave] = so;
-    }
-  }
+  block_sum(part, p);
+  wave_part(part[TALLY_MAX_PIECES], distinct);
+  wave_part(part[TALLY_MAX_PIECES + 1], overlap);
   __syncthreads();
   if (tid != 0) return;
   uint64_t piece[TALLY_MAX_PIECES];
-#pragma unroll
-  for (int k = 0; k < TALLY_MAX_PIECES; k++) {
-    piece[k] = 0;
-    for (int w = 0; w < XUNPACK_THREADS / 64; w++) piece[k] += part[k][w];
-  }
-  uint64_t d = 0, o = 0;
-  for (int w = 0; w < XUNPACK_THREADS / 64; w++) {
-    d += part[TALLY_MAX_PIECES][w];
-    o += part[TALLY_MAX_PIECES + 1][w];
-  }
-  uint64_t w[TALLY_SUM_WORDS];
-  pieces_to_words(piece, TALLY_MAX_PIECES, w);
-  uint64_t t[6 + TALLY_SUM_WORDS];
+  block_totals<TALLY_MAX_PIECES>(part, piece);
+  const uint64_t d = parts_total(part[TALLY_MAX_PIECES]), o = parts_total(part[TALLY_MAX_PIECES + 1]);
+  uint64_t t[6 + TALLY_SUM_WORDS];  // the record, the power in full, the overlap, the proposer's rows
   const uint64_t counts = a.xbuf[seen_base + a.world * a.seen_words];
   const uint64_t proposer_rows = a.prop_on ? counts >> 32 : 0ull;
-  t[0] = w[0];
-  t[1] = w[1];
-  t[2] = (counts & 0xFFFFFFFFull) | (d << 32);
-  t[3] = (words_ge(w, a.quorum) && proposer_rows == 0) ? 1 : 0;
-#pragma unroll
-  for (int k = 0; k < TALLY_SUM_WORDS; k++) t[4 + k] = w[k];
+  tally_record(piece, TALLY_MAX_PIECES, (counts & 0xFFFFFFFFull) | (d << 32), a.quorum, proposer_rows, t, t + 4);
   t[4 + TALLY_SUM_WORDS] = o;
   t[5 + TALLY_SUM_WORDS] = proposer_rows;
 #pragma unroll

@@ -6,7 +6,7 @@
 //   wire_sets_row       what wire_sets_tally_kernel decides for one row from its verdict bit, the UNION index the verdict
 //                       kernel left (recover_dev.h: valsets_row) and the row's set: the bit, the index in the set, and which
 //                       (set, member) entry of the family's packed power column — and of the distinct-sender bitmap — it is
-//   wire_sets_record    a set's sums → tally_kernel's record {power_lo, power_hi, valid | distinct << 32, has_quorum}
+// A set's sums become its record through tally_record (tally_dev.h, included here), with no proposer rows.
 //
 // Everything here is __host__ __device__: csrc/host_wire_sets_harness.hip runs it on the CPU against tests/wire_sets_model.py.
 #pragma once
@@ -14,34 +14,10 @@
 #include <stdint.h>
 
 #include "recover_dev.h"
+#include "tally_dev.h"
 #include "wire_dev.h"
 
 namespace ibftk {
-
-// ---- power sums as words (every tally kernel of kernels.hip.h) --------------------------------------------------------------
-constexpr int TALLY_SUM_WORDS = 5;   // 256-bit powers × up to 2^20 validators < 2^276
-constexpr int TALLY_MAX_PIECES = 8;  // 2·PW 32-bit pieces
-
-// Σ piece_k·2^(32k) → TALLY_SUM_WORDS little-endian u64 words (pieces are sums of 32-bit values, < 2^60)
-__host__ __device__ __forceinline__ void pieces_to_words(const uint64_t *piece, int n_pieces, uint64_t w[TALLY_SUM_WORDS]) {
-  uint64_t carry = 0;  // running value >> 32 at each 32-bit position
-  uint32_t half[2 * TALLY_SUM_WORDS];
-#pragma unroll
-  for (int k = 0; k < 2 * TALLY_SUM_WORDS; k++) {
-    const uint64_t t = carry + (k < n_pieces ? piece[k] : 0ull);  // < 2^61
-    half[k] = (uint32_t)t;
-    carry = t >> 32;
-  }
-#pragma unroll
-  for (int i = 0; i < TALLY_SUM_WORDS; i++) w[i] = (uint64_t)half[2 * i] | ((uint64_t)half[2 * i + 1] << 32);
-}
-__host__ __device__ __forceinline__ bool words_ge(const uint64_t a[TALLY_SUM_WORDS], const uint64_t *b) {
-#pragma unroll
-  for (int i = TALLY_SUM_WORDS - 1; i >= 0; i--) {
-    if (a[i] != b[i]) return a[i] > b[i];
-  }
-  return true;
-}
 
 // ---- the height map ---------------------------------------------------------------------------------------------------------
 // first: n_ranges + 1 strictly increasing heights, range_set: n_ranges set indices (both checked on the host).  The set of
@@ -98,19 +74,6 @@ __host__ __device__ __forceinline__ wire_sets_row_t wire_sets_row(bool bit, int 
   r.counts = v.si >= 0;  // unknown signers contribute 0 (validator_manager.go:88-92)
   r.entry = r.counts ? set_meta[set].x + (uint32_t)v.si : 0u;
   return r;
-}
-
-// ---- one set's record -------------------------------------------------------------------------------------------------------
-// piece[0 .. n_pieces): the 32-bit pieces of the powers of the set's distinct senders, summed; counts = valid rows |
-// distinct senders << 32; quorum: the set's TALLY_SUM_WORDS words.  out[0..3]: what tally_kernel writes into out[0..3].
-__host__ __device__ __forceinline__ void wire_sets_record(const uint64_t *piece, int n_pieces, uint64_t counts, const uint64_t *quorum,
-                                                          uint64_t out[4]) {
-  uint64_t w[TALLY_SUM_WORDS];
-  pieces_to_words(piece, n_pieces, w);
-  out[0] = w[0];
-  out[1] = w[1];
-  out[2] = counts;
-  out[3] = words_ge(w, quorum) ? 1ull : 0ull;
 }
 
 }  // namespace ibftk

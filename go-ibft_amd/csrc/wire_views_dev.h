@@ -265,16 +265,16 @@ __host__ __device__ inline void view_record(view_t &o, uint32_t first_row, const
       }
     }
   }
-  uint64_t w[ibftk::TALLY_SUM_WORDS];
-  ibftk::pieces_to_words(piece, f.n_pieces, w);
   const uint64_t *q = f.quorum + (size_t)set * ibftk::TALLY_SUM_WORDS;
+  uint64_t rec[4];
+  ibftk::tally_record(piece, f.n_pieces, 0ull, q, proposer_rows, rec);
   o.tally.quorum_lo = q[0];
   o.tally.quorum_hi = q[1];
-  o.tally.power_lo = w[0];
-  o.tally.power_hi = w[1];
+  o.tally.power_lo = rec[0];
+  o.tally.power_hi = rec[1];
   o.tally.valid_rows = counted;
   o.tally.distinct_senders = distinct;
-  o.tally.has_quorum = (ibftk::words_ge(w, q) && proposer_rows == 0) ? 1u : 0u;
+  o.tally.has_quorum = (uint32_t)rec[3];
   o.tally.shard_overlap = 0;
   o.tally.proposer_rows = proposer_rows;
   o.tally.reserved = 0;

@@ -2,7 +2,8 @@
 (csrc/host_wire_sets_harness.hip), against the plain model of tests/wire_sets_model.py: the height map at every edge of a
 range, the row rule, and the per-set tally over interleaved rows — a union member outside the row's set, one address at
 different indices in two sets, senders repeated inside one set and across two, u64 power sums that carry past 2^64 and u256
-powers.  The tables the harness reads (union order, setidx, set_meta, packed power pieces, quorum words) are built here the
+powers; and tally_record (csrc/tally_dev.h), the one place that turns sums into a record, against Python integers at the
+quorum's edges, with every carry, and under the proposer rule.  The tables the harness reads (union order, setidx, set_meta, packed power pieces, quorum words) are built here the
 way ibft_set_validator_sets documents them."""
 import ctypes as C
 import random
@@ -26,7 +27,8 @@ def dev():
     L.wsh_heights.argtypes = [vp, vp, u32, vp, u32, vp]
     L.wsh_row_sets.argtypes = [vp, u32, vp, vp, u32, vp, vp]
     L.wsh_tally.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, u32, vp, u32, vp]
-    for f in (L.wsh_heights, L.wsh_row_sets, L.wsh_tally):
+    L.wsh_tally_record.argtypes = [vp, u32, C.c_uint64, vp, C.c_uint64, vp, vp]
+    for f in (L.wsh_heights, L.wsh_row_sets, L.wsh_tally, L.wsh_tally_record):
         f.restype = None
     return L
 
@@ -178,3 +180,68 @@ def test_random_rows_against_the_model(dev):
         rows = [(rng.randrange(-1, n_sets), rng.choice(pool + [_addr(500)]), rng.random() < 0.8) for _ in range(rng.randrange(0, 200))]
         rows = [(s, a, ok and s >= 0) for s, a, ok in rows]   # rows without a set are pre-flagged: no verdict bit
         _run(dev, sets, pw, rows)
+
+
+# ---- tally_record: piece sums → {power_lo, power_hi, counts, has_quorum} and the power in full ---------------------------------
+PIECE_MAX = (2**32 - 1) << 20      # a piece is a sum of 32-bit values over at most 2^20 rows
+
+
+def _record(dev, pieces, counts, quorum, proposer_rows):
+    """the harness's record and full-width power against Python integers; returns has_quorum"""
+    p = np.array(pieces, np.uint64)
+    q = np.array([(quorum >> (64 * j)) & U64_MAX for j in range(5)], np.uint64)
+    out, wide = np.full(4, 0xA5A5, np.uint64), np.full(5, 0xA5A5, np.uint64)
+    dev.wsh_tally_record(_p(p), len(pieces), counts, _p(q), proposer_rows, _p(out), _p(wide))
+    total = sum(int(v) << (32 * k) for k, v in enumerate(pieces))
+    assert total < 2**320 and quorum < 2**320
+    assert sum(int(w) << (64 * j) for j, w in enumerate(wide)) == total, (pieces, wide)
+    want = [total & U64_MAX, (total >> 64) & U64_MAX, counts, 1 if (total >= quorum and proposer_rows == 0) else 0]
+    assert [int(x) for x in out] == want, (pieces, quorum, proposer_rows, out, want)
+    return int(out[3])
+
+
+def _piece_sets(n_pieces):
+    rng = random.Random(40 + n_pieces)
+    return [[PIECE_MAX] * n_pieces,                                        # every carry of pieces_to_words propagates
+            [rng.randrange(1, PIECE_MAX + 1) for _ in range(n_pieces)],
+            [rng.randrange(1, 2**32) for _ in range(n_pieces)],            # no piece carries
+            [0] * (n_pieces - 1) + [PIECE_MAX],
+            [1] + [0] * (n_pieces - 1)]
+
+
+@pytest.mark.parametrize("n_pieces", [2, 8])
+def test_tally_record_at_the_quorum_edges(dev, n_pieces):
+    counts = 7 | (5 << 32)
+    for pieces in _piece_sets(n_pieces):
+        total = sum(v << (32 * k) for k, v in enumerate(pieces))
+        assert _record(dev, pieces, counts, total, 0) == 1          # sum == quorum
+        assert _record(dev, pieces, counts, total + 1, 0) == 0      # sum == quorum − 1
+        assert _record(dev, pieces, counts, total - 1, 0) == 1      # sum == quorum + 1
+        # the proposer rule on a sum that has the quorum: one valid PREPARE of the proposer voids it
+        assert _record(dev, pieces, counts, total - 1, 1) == 0
+        assert _record(dev, pieces, counts, total, 1) == 0
+    if n_pieces == 8:
+        assert sum(PIECE_MAX << (32 * k) for k in range(8)) >> 256                  # the fifth word is in use
+        assert sum(PIECE_MAX << (32 * k) for k in range(8)) < 2**312
+
+
+@pytest.mark.parametrize("n_pieces", [2, 8])
+def test_tally_record_word_that_decides(dev, n_pieces):
+    pieces = [PIECE_MAX] * n_pieces
+    total = sum(v << (32 * k) for k, v in enumerate(pieces))
+    top = (total.bit_length() - 1) // 64                  # the sum's highest word in use: 1 for two pieces, 4 for eight
+    assert top == (1 if n_pieces == 2 else 4)
+    low = (1 << (64 * top)) - 1
+    hi = total >> (64 * top)
+    # the top word decides, against what every lower word says
+    assert _record(dev, pieces, 1, ((hi - 1) << (64 * top)) | low, 0) == 1
+    assert _record(dev, pieces, 1, (hi + 1) << (64 * top), 0) == 0
+    if top < 4:                                           # a quorum word above everything the sum has
+        assert _record(dev, pieces, 1, 1 << 256, 0) == 0
+    # every word above equal: the lowest word decides
+    w0 = total & U64_MAX
+    assert 0 < w0 < U64_MAX
+    assert _record(dev, pieces, 1, total - w0, 0) == 1                     # quorum's low word 0
+    assert _record(dev, pieces, 1, total - w0 + U64_MAX, 0) == 0           # quorum's low word all ones
+    assert _record(dev, pieces, 1, total - 1, 0) == 1
+    assert _record(dev, pieces, 1, total + 1, 0) == 0

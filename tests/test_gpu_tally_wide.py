@@ -104,6 +104,109 @@ def test_tally_over_many_workgroups_with_duplicates_and_nonmembers(n, wide):
         bv.close()
 
 
+# The workgroup's distinct-sender bitmap is in LDS while ⌈validators / 32⌉ words fit 49 152 bytes: 48 · 1024 · 8 = 393 216
+# validators is the largest LDS form; one validator more and tally_kernel sends every row's bit to the HBM bitmap directly.
+LDS_VALIDATORS = 48 * 1024 * 8
+
+
+class _Msg:
+    def __init__(self, sender):
+        self.sender = sender
+
+
+@pytest.fixture(scope="module")
+def huge_set():
+    """LDS_VALIDATORS + 1 addresses with u64 and u256 powers, built once and left unchanged; validator 0 alone outweighs the rest"""
+    rng = np.random.default_rng(393217)
+    addrs = rng.integers(0, 256, (LDS_VALIDATORS + 1, 20), dtype=np.uint8)
+    small = [int(x) for x in rng.integers(1, 2**40, LDS_VALIDATORS + 1, dtype=np.uint64)]
+    p64 = [2**64 - 1] + small[1:]
+    p256 = [2**256 - 1] + [x << (i % 190) for i, x in enumerate(small)][1:]
+    keys = [bytes(a) for a in addrs]
+    assert len(set(keys)) == len(keys)
+    return addrs, keys, {False: p64, True: p256}
+
+
+def _huge_rows(addrs, n):
+    """n rows: duplicates inside a workgroup of 4 096 rows and — beyond 4 096 rows — across two, non-members, the set's last
+    validators (index 393 215: the last bit of the LDS form; 393 216: a member of the HBM form only), failed verdicts"""
+    rng = np.random.default_rng(n)
+    nv = len(addrs)
+    sender = addrs[rng.integers(1, nv - 2, n)].copy()
+    sender[rng.permutation(n)[: n // 10]] = rng.integers(0, 256, (n // 10, 20), dtype=np.uint8)   # not in the set
+    verdict = rng.random(n) < 0.7
+    sender[5], sender[6], sender[17] = addrs[nv - 1], addrs[nv - 2], addrs[nv - 2]
+    verdict[[5, 6, 17]] = True
+    sender[30] = sender[40] = addrs[4321]    # the same validator twice in one workgroup
+    verdict[[30, 40]] = True
+    sender[31], verdict[31] = addrs[7], False    # a validator whose only row failed
+    if n > 4096:
+        sender[10] = sender[4500] = addrs[1234]  # the same validator among the valid rows of both workgroups
+        sender[4600] = addrs[nv - 1]
+        sender[4700] = addrs[0]                  # the heavy validator: this batch has the quorum
+        verdict[[10, 4500, 4600, 4700]] = True
+    return sender, verdict
+
+
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("n", [300, 5000])
+@pytest.mark.parametrize("nv", [LDS_VALIDATORS, LDS_VALIDATORS + 1])
+def test_tally_at_the_edge_of_the_lds_bitmap(huge_set, nv, n, wide):
+    """tally_kernel at the largest validator set whose bitmap is in LDS and at the first one beyond it (every row's bit set
+    in HBM by the row itself, lds_bitmap = 0), over one workgroup and over two, u64 and u256 powers, on a caller-supplied
+    mask.  Run twice on one context: the second run must find bitmap, accumulators and ticket zero."""
+    import go_ibft_amd.verifier as V
+    from oracle.semantics import ValidatorManager
+    addrs, keys, powers = huge_set
+    sender, verdict = _huge_rows(addrs, n)
+    vm = ValidatorManager()
+    assert vm.init(dict(zip(keys[:nv], powers[wide][:nv])))
+    counted = {bytes(sender[i]) for i in np.nonzero(verdict)[0]}
+    exp_power = sum(vm.power.get(a, 0) for a in counted)
+    exp_distinct = sum(1 for a in counted if a in vm.power)
+    assert (keys[LDS_VALIDATORS] in vm.power) == (nv > LDS_VALIDATORS) and keys[LDS_VALIDATORS] in counted
+    assert (exp_power >= vm.quorum) == (n > 4096)
+    bv = V.BatchVerifier(max_rows=LDS_VALIDATORS + 4096)
+    try:
+        (bv.set_validators_u256 if wide else bv.set_validators)(1, addrs[:nv], powers[wide][:nv])
+        for _ in range(2):
+            t = bv.has_quorum(sender, verdict)
+            w = bv.last_tally_wide()
+            assert (t.valid_rows, t.distinct_senders) == (int(verdict.sum()), exp_distinct)
+            assert w.power == exp_power and w.quorum == vm.quorum
+            assert bool(t.has_quorum) == (exp_power >= vm.quorum) and t.proposer_rows == 0
+    finally:
+        bv.close()
+
+
+def test_prepare_quorum_seat_beyond_the_lds_bitmap(huge_set):
+    """HasPrepareQuorum at LDS_VALIDATORS + 1 validators: the proposer — a member without a row, here the one validator that
+    outweighs the rest — takes his seat in the HBM bitmap; plain HasQuorum before and after answers without him."""
+    import go_ibft_amd.verifier as V
+    from oracle.semantics import ValidatorManager
+    addrs, keys, powers = huge_set
+    sender, verdict = _huge_rows(addrs, 300)
+    vm = ValidatorManager()
+    assert vm.init(dict(zip(keys, powers[False])))
+    msgs = [_Msg(bytes(sender[i])) for i in np.nonzero(verdict)[0]]
+    counted = {m.sender for m in msgs}
+    plain_power = sum(vm.power.get(a, 0) for a in counted)
+    plain_distinct = sum(1 for a in counted if a in vm.power)
+    assert keys[0] not in counted and not vm.has_quorum(counted) and vm.has_prepare_quorum(_Msg(keys[0]), msgs)
+    bv = V.BatchVerifier(max_rows=LDS_VALIDATORS + 4096)
+    try:
+        bv.set_validators(1, addrs, powers[False])
+        for _ in range(2):
+            t = bv.has_quorum(sender, verdict)
+            assert (bool(t.has_quorum), t.distinct_senders, bv.last_tally_wide().power) == (False, plain_distinct, plain_power)
+            t = bv.has_prepare_quorum(sender, verdict, keys[0])
+            w = bv.last_tally_wide()
+            assert (bool(t.has_quorum), t.distinct_senders, t.proposer_rows, t.valid_rows) == (True, plain_distinct + 1, 0, int(verdict.sum()))
+            assert w.power == plain_power + vm.power[keys[0]] and w.quorum == vm.quorum
+    finally:
+        bv.close()
+
+
 def test_wide_powers_through_the_seal_path(oracle):
     """IsValidCommittedSeal + HasQuorum in one call with 256-bit powers (wei-denominated stakes)."""
     import go_ibft_amd.verifier as V

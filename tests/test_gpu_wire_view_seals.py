@@ -183,6 +183,21 @@ def test_corpus_b_across_workgroups(oracle):
         ref.close()
 
 
+def test_more_rows_than_scan_threads(oracle):
+    """1 029 rows: wire_seals_scan_kernel (and the views' rank kernel) give two rows to a thread, the last thread that has any
+    a single one; sealable rows, PREPAREs and bad seals interleaved, so the dense seal rows depend on every thread's offset"""
+    V = _V()
+    c = SC.corpus_b(1029)
+    bv, ref = V.BatchVerifier(max_rows=2048), V.BatchVerifier(max_rows=2048)
+    try:
+        K.install(bv, c)
+        out, _ = _check(bv, ref, c, WS.MAP_A, False, len(c.msgs))
+        assert 0 < bv.wire_seal_stats()[1] < 1029 and 0 < out[9].sum() < bv.wire_seal_stats()[1]
+    finally:
+        bv.close()
+        ref.close()
+
+
 def test_corpus_c_a_view_per_row(oracle):
     """64 views in every wavefront: the tally's per-lane fallback; views_cap below the number of views"""
     V = _V()

@@ -204,14 +204,15 @@ def corpus_t(n: int = T_ROWS) -> Corpus:
     return _finish(key, False, msgs, kinds, senders, None)
 
 
-def corpus_b() -> Corpus:
-    key = ("b",)
+def corpus_b(n: int = B_ROWS) -> Corpus:
+    """n rows (default B_ROWS): COMMITs and PREPAREs interleaved, a fifth of the COMMITs with a bad seal"""
+    key = ("b", n)
     if key in _CACHE:
         return _CACHE[key]
     pool = WS.corpus().pool
     msgs, kinds, senders = [], [], []
     commits = 0
-    for j in range(B_ROWS):
+    for j in range(n):
         i = WS.MEMBERS[0][j % 40]
         everywhere = j % 7 == 0                # one COMMIT view with rows in every workgroup; its senders come again 280 rows on
         typ = COMMIT if everywhere or j % 2 == 0 else PREPARE
