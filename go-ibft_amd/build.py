@@ -7,7 +7,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libibftgpu.so")
-SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "wire_recode_dev.h", "wire_sets_dev.h", "tally_dev.h", "wire_views_dev.h", "wire_seals_dev.h", "cert_wave_dev.h", "cert_scan_dev.h", "cert_verdict_dev.h", "cert_decide_dev.h", "cert_dedup_dev.h", "cert_dedup_kernels.h", "modinv_dev.h",
+SOURCES = ["ibftgpu.hip", "kernels.hip.h", "recover_dev.h", "verify_dev.h", "wave_fe_dev.h", "wire_dev.h", "wire_recode_dev.h", "wire_sets_dev.h", "tally_dev.h", "wire_views_dev.h", "wire_seals_dev.h", "round_change_dev.h", "cert_wave_dev.h", "cert_scan_dev.h", "cert_verdict_dev.h", "cert_decide_dev.h", "cert_dedup_dev.h", "cert_dedup_kernels.h", "modinv_dev.h",
            "sign_dev.h", "sign_message_dev.h", "sign_envelope_dev.h", "sha256_dev.h", "secp256k1_dev.h", "keccak_dev.h", "keccak_row_dev.h", os.path.join("..", "..", "include", "ibftgpu.h")]
 # Code-generation flags of the product library (part of its build stamp).  max-ilp: the verdict kernels run ONE wavefront per
 # SIMD at the sizes that matter (N ≤ 4 096), where every hazard s_nop is a lost issue slot — scheduling for instruction-level
@@ -388,6 +388,21 @@ def build_wire_view_seals_harness(force: bool = False) -> str:
                                "-o", WIRE_VIEW_SEALS_HARNESS, os.path.join(CSRC, "host_wire_view_seals_harness.hip")], cwd=CSRC)
         _mark(WIRE_VIEW_SEALS_HARNESS, deps)
     return WIRE_VIEW_SEALS_HARNESS
+
+
+ROUND_CHANGE_HARNESS = os.path.join(CSRC, "libdev_round_change_host.so")
+
+
+def build_round_change_harness(force: bool = False) -> str:
+    """TEST-ONLY: round_change_dev.h over wire_views_dev.h's tables (the participation rule, the stored rule, the per-round
+    records and the answer of ibft_decide_round_changes_wire) on the CPU; the answer's selection also through wave_emul.h."""
+    deps = ["host_round_change_harness.hip", "round_change_dev.h", "wire_views_dev.h", "wire_sets_dev.h", "tally_dev.h", "wire_dev.h", "cert_decide_dev.h",
+            "cert_verdict_dev.h", "wave_emul.h", "recover_dev.h", "modinv_dev.h", "secp256k1_dev.h", "keccak_dev.h"]
+    if force or _stale(ROUND_CHANGE_HARNESS, deps):
+        subprocess.check_call(["hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-shared", "-fPIC",
+                               "-o", ROUND_CHANGE_HARNESS, os.path.join(CSRC, "host_round_change_harness.hip")], cwd=CSRC)
+        _mark(ROUND_CHANGE_HARNESS, deps)
+    return ROUND_CHANGE_HARNESS
 
 
 QTAB_GLV_HARNESS = os.path.join(CSRC, "libdev_qtab_glv_host.so")

@@ -171,13 +171,16 @@ struct cert_counters {
   uint32_t dense, unplaced;               // cert_dedup_front_launch: representatives, rows the table could not place
   uint32_t judged_tree, judged_deferred;  // cert_dedup_count_launch: rows without a pre-flag, the tree's and the deferred batch's
   uint32_t count_acc[3];                  // cert_dedup_count_kernel's two sums and its ticket: zero between launches
-  uint32_t pad1[5];
+  // the round-change stage's three words (pinned mirror only: copied there from behind the stage's tables): keys, all-ones unless a
+  // table was exhausted, unjudged level-0 rows
+  uint32_t rc_words[3];
+  uint32_t pad1[2];
 };
 static_assert(sizeof(cert_counters) == 64, "the counter block the kernels address by word");
 static_assert(offsetof(cert_counters, next_rows) == 0 && offsetof(cert_counters, carriers) == 4 && offsetof(cert_counters, records) == 8 &&
                   offsetof(cert_counters, pad0) == 12 && offsetof(cert_counters, dense) == 16 && offsetof(cert_counters, unplaced) == 20 &&
                   offsetof(cert_counters, judged_tree) == 24 && offsetof(cert_counters, judged_deferred) == 28 &&
-                  offsetof(cert_counters, count_acc) == 32 && offsetof(cert_counters, pad1) == 44,
+                  offsetof(cert_counters, count_acc) == 32 && offsetof(cert_counters, rc_words) == 44 && offsetof(cert_counters, pad1) == 56,
               "cert_scan_launch writes words 0-1, cert_record_scan_kernel word 2, the dedup front words 4-5, the count launch 6-7 over 8-10");
 
 // Certificates from wire bytes (ibft_verify_certificates_wire, ibft_judge_certificates_wire): everything the route owns beyond
@@ -201,9 +204,19 @@ struct CertState {
   bool dedup = false;
   uint32_t dedup_slots_cap = 0;     // IBFT_CERT_DEDUP_SLOTS (test hook): at most that many table slots; 0 = no cap
   uint32_t stat[4] = {0, 0, 0, 0};  // ibft_cert_stats: rows, judged, given to the verdict kernels, unplaced — of the last certificate call
+  // ibft_decide_round_changes_wire (kernels.hip.h: round_change_*_kernel), sized by n and rc_cap in the call itself, in the
+  // views call's discipline: the two tables with the call's three words behind them (2 · slots + 4 words, set to all-ones by
+  // ONE fill in front of every insert), the rows' sender indices, slots, ranks and views, the stored words, the records, the
+  // answer, and the per-key accumulators, which every successful call leaves zero (rc_acc_dirty: a call that failed midway may
+  // not have; the next one clears them first).
+  DevBuf rc_tables, rc_slots, rc_vidx, rc_rank, rc_first, rc_view, rc_stored, rc_acc, rc_recs, rc_answer;
+  bool rc_acc_dirty = true;
+  uint32_t rc_slots_hook = 0;  // IBFT_ROUND_CHANGE_SLOTS (test hook): lowers the slot count, never below the first power of two above n
 
   void release_all() {  // device buffers, the pinned block, the two events (ibft_ctx_destroy)
-    for (DevBuf *b : {&nodes, &span, &count, &slot, &prop, &masks, &total, &tiles, &rec, &recbase, &dd_table, &dd_slot, &dd_pos, &dec, &mid, &proposers}) release(*b);
+    for (DevBuf *b : {&nodes, &span, &count, &slot, &prop, &masks, &total, &tiles, &rec, &recbase, &dd_table, &dd_slot, &dd_pos, &dec, &mid, &proposers,
+                      &rc_tables, &rc_slots, &rc_vidx, &rc_rank, &rc_first, &rc_view, &rc_stored, &rc_acc, &rc_recs, &rc_answer})
+      release(*b);
     if (h_total) (void)hipHostFree(h_total);
     for (hipEvent_t e : {ev_fork, ev_join})
       if (e) (void)hipEventDestroy(e);
@@ -1826,6 +1839,7 @@ int ibft_ctx_create(const ibft_cfg *cfg, ibft_ctx **out) {
   if (const char *e = getenv("IBFT_WIRE_RECODE")) c->wire_recode = atoi(e) != 0;
   if (const char *e = getenv("IBFT_CERT_DEDUP_SLOTS")) c->cert.dedup_slots_cap = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("IBFT_WIRE_VIEWS_SLOTS")) c->wviews.slots_hook = (uint32_t)strtoul(e, nullptr, 10);
+  if (const char *e = getenv("IBFT_ROUND_CHANGE_SLOTS")) c->cert.rc_slots_hook = (uint32_t)strtoul(e, nullptr, 10);
   {
     std::random_device rd;
     c->wviews.salt = (uint32_t)rd();
@@ -4723,8 +4737,18 @@ struct cert_call {
   ibft_wire_row_t *out_rows;
   uint8_t *out_class;
   uint64_t *out_sender_mask, *out_hash_mask, *out_self_mask;
+  // ibft_decide_round_changes_wire: decide, and the quorum records of the level-0 ROUND_CHANGE rows with the answer to `query`
+  bool round_changes;
+  const ibft_rc_query_t *query;  // null: no answer
+  size_t rc_cap;
+  int32_t *out_rc_view;          // may be null, as out_rc_stored and out_answer
+  uint64_t *out_rc_stored;
+  ibft_rc_record_t *out_rc;
+  size_t *out_n_rc;
+  ibft_rc_answer_t *out_answer;
 };
 struct cert_plan {
+  uint32_t rc_cap = 0, rc_slots = 0;                   // round changes: min(n, rc_cap), slots of each table
   size_t cap = 0;                                      // rows the tree may have: min(rows_cap, max_rows)
   std::vector<std::pair<uint32_t, uint32_t>> levels;   // rows [first, second) of each level
   uint32_t rows = 0, carriers = 0, records = 0;        // of the whole tree; carriers: the deferred rows (slot list)
@@ -4745,9 +4769,12 @@ static int cert_check(const ibft_ctx *c, const cert_call &k, cert_plan &p, bool 
     if (!c || !k.out_n_rows || (k.n && (!k.off || (!k.judge && !k.out_sender_mask)))) return IBFT_E_INVAL;
     if (k.judge && (!k.out_n_certs || (k.n && !k.out_cert))) return IBFT_E_INVAL;
     if (k.decide && k.n && !k.out_decision) return IBFT_E_INVAL;
+    if (k.round_changes && (!k.out_n_rc || (k.n && (!k.out_rc || !k.rc_cap)))) return IBFT_E_INVAL;
+    if (k.round_changes && k.query && (k.query->has_accepted_proposal > 1 || k.query->reserved)) return IBFT_E_INVAL;
     if (!offsets_ok(k.off, k.n) || !bytes_ok(k.off, k.n, k.wire_bytes)) return IBFT_E_INVAL;
     *k.out_n_rows = 0;
     if (k.judge) *k.out_n_certs = 0;
+    if (k.round_changes) *k.out_n_rc = 0;
     return IBFT_OK;
   }
   p.cap = std::min<size_t>(k.rows_cap, c->max_rows);
@@ -4784,6 +4811,18 @@ static int cert_reserve(ibft_ctx *c, const cert_call &k, cert_plan &p) {
   if (k.judge && (rc = ensure(c, s.recbase, (m + 1) * 4))) return rc;
   if (k.decide && (rc = ensure(c, s.dec, m * sizeof(certd::decision)))) return rc;
   if (k.decide && (rc = ensure(c, s.mid, k.n * 25 * sizeof(uint64_t)))) return rc;
+  if (k.round_changes) {
+    const uint32_t n = (uint32_t)k.n;
+    p.rc_cap = (uint32_t)std::min<size_t>(k.rc_cap, k.n);  // (a cap above n behaves as n)
+    p.rc_slots = wviews::table_slots(n, s.rc_slots_hook);
+    const size_t acc_bytes = (size_t)p.rc_cap * rcd::acc_words(2 * (int)c->power_words) * 8;
+    if (acc_bytes > s.rc_acc.cap) s.rc_acc_dirty = true;  // a fresh allocation holds anything
+    if ((rc = ensure(c, s.rc_tables, (size_t)p.rc_slots * 8 + 16)) || (rc = ensure(c, s.rc_slots, (size_t)n * 8)) ||
+        (rc = ensure(c, s.rc_vidx, (size_t)n * 4)) || (rc = ensure(c, s.rc_rank, (size_t)n * 4)) || (rc = ensure(c, s.rc_first, (size_t)p.rc_cap * 4)) ||
+        (rc = ensure(c, s.rc_view, (size_t)n * 4)) || (rc = ensure(c, s.rc_stored, (size_t)mask_words(n) * 8)) || (rc = ensure(c, s.rc_acc, acc_bytes)) ||
+        (rc = ensure(c, s.rc_recs, (size_t)p.rc_cap * sizeof(rcd::record))) || (rc = ensure(c, s.rc_answer, sizeof(rcd::answer))))
+      return rc;
+  }
   if (!s.h_total) {
     if (hipHostMalloc((void **)&s.h_total, sizeof(cert_counters)) != hipSuccess) return IBFT_E_NOMEM;
     void *d = nullptr;
@@ -5075,6 +5114,62 @@ static int cert_decide(ibft_ctx *c, const cert_call &k, cert_plan &p) {
   return IBFT_OK;
 }
 
+// round changes: behind the decisions, one fill (tables to EMPTY, the call's words to all-ones), then index, insert, rank, tally,
+// records and — with a query — select, and their way home.  No host wait: the three words leave with what cert_deliver waits for.
+static int cert_round_changes(ibft_ctx *c, const cert_call &k, cert_plan &p) {
+  if (!k.round_changes) return IBFT_OK;
+  CertState &s = c->cert;
+  const uint32_t n = (uint32_t)k.n, slots = p.rc_slots;
+  if (s.rc_acc_dirty) HIPCHK(c, hipMemsetAsync(s.rc_acc.p, 0, s.rc_acc.cap, c->stream));
+  s.rc_acc_dirty = true;  // until this call has come back clean
+  HIPCHK(c, hipMemsetAsync(s.rc_tables.p, 0xFF, (size_t)slots * 8 + 16, c->stream));
+  ibftk::round_change_args a{};
+  a.rows = (const wire::row_info *)c->d_wire_rows.p;
+  a.rec = (const certv::record *)s.rec.p;
+  a.dec = (const certd::decision *)s.dec.p;
+  a.vtab = (const uint32_t *)c->d_vtab.p;
+  a.vpower32 = (const uint32_t *)c->d_vpower.p;
+  a.quorum = (const uint64_t *)c->d_quorum.p;
+  a.vslot_mask = c->vslot_mask;
+  a.n_validators = c->n_validators;
+  a.n = n;
+  a.cap = p.rc_cap;
+  a.slots = slots;
+  a.salt = c->wviews.salt;
+  a.n_pieces = 2 * (int)c->power_words;
+  a.vidx = (int32_t *)s.rc_vidx.p;
+  a.key_table = (uint32_t *)s.rc_tables.p;
+  a.last_table = a.key_table + slots;
+  a.slot_key = (uint32_t *)s.rc_slots.p;
+  a.slot_last = a.slot_key + n;
+  a.rank_of = (uint32_t *)s.rc_rank.p;
+  a.first_row = (uint32_t *)s.rc_first.p;
+  a.words = a.key_table + 2 * (size_t)slots;
+  a.out_view = (int32_t *)s.rc_view.p;
+  a.out_stored = (uint64_t *)s.rc_stored.p;
+  a.acc = (uint64_t *)s.rc_acc.p;
+  a.out_rc = (rcd::record *)s.rc_recs.p;
+  a.out_answer = (rcd::answer *)s.rc_answer.p;
+  const bool ask = k.query && k.out_answer;
+  if (ask) a.query = rcd::query{k.query->height, k.query->round, k.query->min_round, k.query->has_accepted_proposal, 0u};
+  const dim3 rows_grid((n + ibftk::RC_THREADS - 1) / ibftk::RC_THREADS), block(ibftk::RC_THREADS);
+  hipLaunchKernelGGL(ibftk::round_change_index_kernel, rows_grid, block, 0, c->stream, a);
+  hipLaunchKernelGGL(ibftk::round_change_insert_kernel, rows_grid, block, 0, c->stream, a);
+  hipLaunchKernelGGL(ibftk::round_change_rank_kernel, dim3(1), dim3(1024), 0, c->stream, a);
+  with_power_words(c->power_words,
+                   [&](auto PW) { hipLaunchKernelGGL(ibftk::round_change_tally_kernel<decltype(PW)::value>, rows_grid, block, 0, c->stream, a); });
+  hipLaunchKernelGGL(ibftk::round_change_records_kernel, dim3((p.rc_cap + ibftk::RC_THREADS - 1) / ibftk::RC_THREADS), block, 0, c->stream, a);
+  if (ask) hipLaunchKernelGGL(ibftk::round_change_select_kernel, dim3(1), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  // (into the pinned counter block, which outlives a call that returns early, not into this call's frame)
+  HIPCHK(c, hipMemcpyAsync(s.h_total->rc_words, a.words, sizeof s.h_total->rc_words, hipMemcpyDeviceToHost, c->stream));
+  if (k.out_rc_view) HIPCHK(c, hipMemcpyAsync(k.out_rc_view, a.out_view, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (k.out_rc_stored) HIPCHK(c, hipMemcpyAsync(k.out_rc_stored, a.out_stored, (size_t)mask_words(n) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(k.out_rc, a.out_rc, (size_t)p.rc_cap * sizeof(rcd::record), hipMemcpyDeviceToHost, c->stream));
+  if (ask) HIPCHK(c, hipMemcpyAsync(k.out_answer, a.out_answer, sizeof(rcd::answer), hipMemcpyDeviceToHost, c->stream));
+  return IBFT_OK;
+}
+
 // the per-row outputs that were asked for, the sender words (fetch_results waits for the stream), the counts, the stats
 static int cert_deliver(ibft_ctx *c, const cert_call &k, cert_plan &p) {
   CertState &s = c->cert;
@@ -5089,6 +5184,15 @@ static int cert_deliver(ibft_ctx *c, const cert_call &k, cert_plan &p) {
   if (k.out_self_mask) HIPCHK(c, hipMemcpyAsync(k.out_self_mask, d_self_mask, mw * 8, hipMemcpyDeviceToHost, c->stream));
   // no tally: the rows of a tree belong to many certificates; their quorum rules are the caller's (From / type / view columns)
   if ((rc = fetch_results(c, rows, k.out_sender_mask, nullptr, false))) return rc;
+  if (k.round_changes) {
+    const volatile cert_counters *hw = s.h_total;
+    if (hw->rc_words[1] != 0xFFFFFFFFu) {  // (more keys than slots cannot happen: table_slots gives more slots than rows)
+      c->last_error = "ibft_decide_round_changes_wire: a table was exhausted";
+      return IBFT_E_HIP;
+    }
+    s.rc_acc_dirty = false;  // the records kernel zeroed what the tally added
+    *k.out_n_rc = hw->rc_words[0];
+  }
   *k.out_n_rows = rows;
   if (k.judge) *k.out_n_certs = p.records;
   const volatile cert_counters *h = s.h_total;
@@ -5126,11 +5230,19 @@ static int certificates_wire_impl(ibft_ctx *c, const cert_call &k) {
   int rc;
   if ((rc = cert_check(c, k, p, /*locked=*/false))) return rc;
   ctx_lock lk(c);
-  if ((rc = cert_check(c, k, p, /*locked=*/true))) return rc == CERT_NOTHING_TO_DO ? IBFT_OK : rc;
+  if ((rc = cert_check(c, k, p, /*locked=*/true))) {
+    if (rc != CERT_NOTHING_TO_DO) return rc;
+    if (k.round_changes && k.query && k.out_answer) {  // the answer over no records
+      rcd::answer none;
+      rcd::make_answer(none, rcd::lane_init(), 0u, 0u, 0u);
+      memcpy(k.out_answer, &none, sizeof none);
+    }
+    return IBFT_OK;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   c->wire.columns = false;
   c->staged_n = 0;
-  for (auto stage : {cert_reserve, cert_expand, cert_digests, cert_verdicts, cert_compare_and_judge, cert_decide, cert_deliver})
+  for (auto stage : {cert_reserve, cert_expand, cert_digests, cert_verdicts, cert_compare_and_judge, cert_decide, cert_round_changes, cert_deliver})
     if ((rc = stage(c, k, p))) return rc;
   return IBFT_OK;
 }
@@ -5174,6 +5286,39 @@ int ibft_decide_certificates_wire(ibft_ctx *c, const uint8_t *wire_bytes, const 
   k.judge = k.decide = true, k.certs_cap = certs_cap, k.out_n_certs = out_n_certs, k.out_cert = out_cert, k.out_decision = out_decision;
   k.out_n_rows = out_n_rows, k.out_nodes = out_nodes, k.out_rows = out_rows, k.out_class = out_class;
   k.out_sender_mask = out_sender_mask, k.out_hash_mask = out_hash_mask, k.out_self_mask = out_self_mask;
+  return certificates_wire_impl(c, k);
+}
+
+// The decide call plus what handleRoundChangeMessage does with its per-message answers: one quorum record per (height, round)
+// of the level-0 ROUND_CHANGE rows and the answer to `query` (round_change_dev.h).  The decide call's checks in its order, the
+// new arguments among the argument checks in front.
+int ibft_decide_round_changes_wire(ibft_ctx *c, const uint8_t *wire_bytes, const uint32_t *off, size_t n, size_t rows_cap, size_t certs_cap,
+                                   size_t *out_n_rows, size_t *out_n_certs, ibft_cert_verdict_t *out_cert, ibft_cert_decision_t *out_decision,
+                                   ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows, uint8_t *out_class, uint64_t *out_sender_mask,
+                                   uint64_t *out_hash_mask, uint64_t *out_self_mask, const ibft_rc_query_t *query, int32_t *out_rc_view,
+                                   uint64_t *out_rc_stored, ibft_rc_record_t *out_rc, size_t rc_cap, size_t *out_n_rc, ibft_rc_answer_t *out_answer) {
+  static_assert(sizeof(ibft_rc_query_t) == sizeof(rcd::query) && sizeof(ibft_rc_query_t) == 32, "ABI");
+  static_assert(sizeof(ibft_rc_record_t) == sizeof(rcd::record) && sizeof(ibft_rc_record_t) == 128, "ABI");
+  static_assert(sizeof(ibft_rc_answer_t) == sizeof(rcd::answer) && sizeof(ibft_rc_answer_t) == 64, "ABI");
+  static_assert(offsetof(ibft_rc_query_t, min_round) == offsetof(rcd::query, min_round) &&
+                    offsetof(ibft_rc_query_t, has_accepted_proposal) == offsetof(rcd::query, has_accepted_proposal) &&
+                    offsetof(ibft_rc_record_t, open_rows) == offsetof(rcd::record, open_rows) &&
+                    offsetof(ibft_rc_record_t, has_quorum) == offsetof(rcd::record, has_quorum) &&
+                    offsetof(ibft_rc_record_t, open_power_lo) == offsetof(rcd::record, open_power_lo) &&
+                    offsetof(ibft_rc_record_t, tally) == offsetof(rcd::record, tally) &&
+                    offsetof(ibft_rc_answer_t, record) == offsetof(rcd::answer, record) && offsetof(ibft_rc_answer_t, round) == offsetof(rcd::answer, round) &&
+                    offsetof(ibft_rc_answer_t, most_round) == offsetof(rcd::answer, most_round) &&
+                    offsetof(ibft_rc_answer_t, most_rows) == offsetof(rcd::answer, most_rows) &&
+                    offsetof(ibft_rc_answer_t, unjudged_rows) == offsetof(rcd::answer, unjudged_rows),
+                "ABI");
+  static_assert(IBFT_RC_OVER == rcd::FLAG_OVER && IBFT_RC_VIEW_NONE == rcd::VIEW_NONE && IBFT_RC_VIEW_OVER == rcd::VIEW_OVER, "ABI");
+  cert_call k{};
+  k.wire_bytes = wire_bytes, k.off = off, k.n = n, k.rows_cap = rows_cap;
+  k.judge = k.decide = true, k.certs_cap = certs_cap, k.out_n_certs = out_n_certs, k.out_cert = out_cert, k.out_decision = out_decision;
+  k.out_n_rows = out_n_rows, k.out_nodes = out_nodes, k.out_rows = out_rows, k.out_class = out_class;
+  k.out_sender_mask = out_sender_mask, k.out_hash_mask = out_hash_mask, k.out_self_mask = out_self_mask;
+  k.round_changes = true, k.query = query, k.rc_cap = rc_cap, k.out_rc_view = out_rc_view, k.out_rc_stored = out_rc_stored;
+  k.out_rc = out_rc, k.out_n_rc = out_n_rc, k.out_answer = out_answer;
   return certificates_wire_impl(c, k);
 }
 

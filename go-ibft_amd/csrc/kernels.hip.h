@@ -53,6 +53,7 @@
 #include "cert_verdict_dev.h"
 #include "cert_decide_dev.h"
 #include "wire_views_dev.h"
+#include "round_change_dev.h"
 #include "wire_seals_dev.h"
 #include "cert_dedup_dev.h"
 
@@ -2924,6 +2925,172 @@ __global__ void __launch_bounds__(64) cert_decide_proposals_kernel(cert_decide_a
       certd::record_prepared(d, prepared, w, match);
       a.out[root] = d;
     }
+  }
+}
+
+// ---- round changes: one quorum record per (height, round), GetExtendedRCC (ibft_decide_round_changes_wire; round_change_dev.h)
+// Six launches behind the decision kernels on the same stream, in the shape of the views stage above: each phase that needs
+// every row of the one before it is a launch of its own.
+//   index    a thread per level-0 row: the sender's validator index of a row that takes part (rcd::row_index), −1 for every
+//            other row.  A launch of its own because wviews::insert_row compares the index of OTHER rows: the columns the tables
+//            are keyed by must all be written by an earlier launch (wire_views_dev.h: columns).
+//   insert   a thread per level-0 row: a row that takes part goes, under that index, into wviews' key table (lowest row of its
+//            (height, round)) and last table (highest row of its key and sender).
+//   rank     ONE workgroup (wire_views_rank_kernel's shape): the representatives ranked in ascending row order; words[0] = keys,
+//            words[2] = the level-0 rows the tree left to the host.
+//   tally    a thread per row: out_rc_view, the stored bit (one ballot per wavefront is one word of out_rc_stored) and the key's
+//            accumulators (rcd::acc_words).  A wavefront reduces one key per turn, at most RC_TURNS turns; whoever still waits
+//            then — one sender's rows of 64 rounds in one wavefront — adds for itself.
+//   records  a thread per record slot below min(n, rc_cap): rcd::key_record, then the key's accumulators are zeroed; a slot past
+//            the number of keys is zeroed.
+//   select   ONE wavefront strides over the records that were written: rcd::record_step, rcd::wave_state, rcd::make_answer.
+constexpr int RC_THREADS = 256, RC_TURNS = 4;
+struct round_change_args {
+  const wire::row_info *rows;       // the tree's rows; level 0 is rows [0, n)
+  const certv::record *rec;         // record i < n belongs to row i
+  const certd::decision *dec;
+  const uint32_t *vtab;             // the validator table (valset_lookup)
+  const uint32_t *vpower32;         // n_validators × 2·PW pieces
+  const uint64_t *quorum;           // TALLY_SUM_WORDS
+  uint32_t vslot_mask, n_validators;
+  uint32_t n, cap, slots, salt;     // cap: min(n, rc_cap)
+  int n_pieces;
+  int32_t *vidx;                    // n: the sender's validator index of a row that takes part, else −1 (index kernel; read-only afterwards)
+  uint32_t *key_table, *last_table;  // slots words each
+  uint32_t *slot_key, *slot_last;    // n
+  uint32_t *rank_of;                 // n: rank of a representative
+  uint32_t *first_row;               // cap: the representative of record v
+  uint32_t *words;                   // behind the tables, all-ones like them at the start: [0] ← keys, [1] ← 0 when a table was exhausted, [2] ← unjudged rows
+  int32_t *out_view;                 // n
+  uint64_t *out_stored;              // ⌈n / 64⌉
+  uint64_t *acc;                     // cap × rcd::acc_words, zero between calls
+  rcd::record *out_rc;               // cap
+  rcd::query query;
+  rcd::answer *out_answer;
+};
+__global__ void __launch_bounds__(RC_THREADS) round_change_index_kernel(round_change_args a) {
+  const uint32_t row = blockIdx.x * RC_THREADS + threadIdx.x;
+  if (row >= a.n) return;
+  a.vidx[row] = rcd::row_index(a.rec[row], a.rows[row], a.vtab, a.vslot_mask, a.n_validators);
+}
+__global__ void __launch_bounds__(RC_THREADS) round_change_insert_kernel(round_change_args a) {
+  const uint32_t row = blockIdx.x * RC_THREADS + threadIdx.x;
+  if (row >= a.n) return;
+  const int32_t *vidx = a.vidx;  // (complete: the launch before this one wrote every entry)
+  const wviews::row_slots s = wviews::insert_row(wviews::columns{a.rows, vidx}, row, vidx[row] >= 0, a.key_table, a.last_table, a.slots, a.salt);
+  a.slot_key[row] = s.key;
+  a.slot_last[row] = s.last;
+  if (s.key == wviews::UNPLACED || s.last == wviews::UNPLACED) atomicAnd(a.words + 1, 0u);
+}
+__global__ void __launch_bounds__(1024) round_change_rank_kernel(round_change_args a) {
+  __shared__ uint64_t part[1024];
+  const uint32_t t = threadIdx.x, per = (a.n + 1023u) / 1024u;
+  const uint32_t b = t * per < a.n ? t * per : a.n, e = b + per < a.n ? b + per : a.n;
+  uint64_t sum = 0;  // representatives | unjudged rows << 32
+  for (uint32_t i = b; i < e; i++)
+    sum += (wviews::is_rep(a.key_table, a.slot_key[i], i) ? 1ull : 0ull) | ((uint64_t)(rcd::unjudged(a.rec[i]) ? 1u : 0u) << 32);
+  uint32_t run = (uint32_t)(block_scan_1024(part, sum) - sum);
+  for (uint32_t i = b; i < e; i++) {
+    if (!wviews::is_rep(a.key_table, a.slot_key[i], i)) continue;
+    a.rank_of[i] = run;
+    if (run < a.cap) a.first_row[run] = i;
+    run++;
+  }
+  if (t == 1023u) {
+    a.words[0] = (uint32_t)part[1023];
+    a.words[2] = (uint32_t)(part[1023] >> 32);
+  }
+}
+template <int PW>
+__global__ void __launch_bounds__(RC_THREADS) round_change_tally_kernel(round_change_args a) {
+  constexpr int NP = 2 * PW, STRIDE = 2 * NP + 2;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t row = blockIdx.x * RC_THREADS + tid;
+  const uint32_t sk = row < a.n ? a.slot_key[row] : wviews::SKIP;
+  int32_t v = wviews::VIEW_NONE;
+  bool stored = false;
+  if (sk < wviews::SKIP) {
+    v = wviews::view_of_rank(a.rank_of[a.key_table[sk]], a.cap);
+    stored = wviews::is_stored(a.last_table, a.slot_last[row], row);  // a row beyond the cap still supersedes
+  }
+  if (row < a.n) a.out_view[row] = v;
+  const uint64_t sw = __ballot(stored ? 1 : 0);
+  if (lane == 0 && (row & ~63u) < a.n) a.out_stored[row >> 6] = sw;
+  bool pend = v >= 0;
+  const int rc = pend && stored ? (int)a.dec[row].round_change : 0;
+  const bool yes = rc == certd::YES, open = rc == certd::UNDECIDED;
+  uint32_t pw[NP];
+  {
+    const bool adds = yes || open;
+    const uint32_t entry = adds ? (uint32_t)a.vidx[row] : 0u;
+#pragma unroll
+    for (int k = 0; k < NP; k++) pw[k] = adds ? a.vpower32[(size_t)entry * NP + k] : 0u;
+  }
+  const uint64_t c0 = 1ull | ((uint64_t)(stored ? 1u : 0u) << 32), c1 = (yes ? 1ull : 0ull) | ((uint64_t)(open ? 1u : 0u) << 32);
+  for (int turn = 0; turn < RC_TURNS; turn++) {  // (wave-uniform: every lane takes every turn)
+    const uint64_t todo = __ballot(pend ? 1 : 0);
+    if (!todo) break;
+    const int leader = __ffsll((long long)todo) - 1;
+    const int32_t lv = __shfl(v, leader, 64);
+    const bool mine = pend && v == lv;
+    uint64_t *acc = a.acc + (size_t)lv * STRIDE;
+    const uint64_t s0 = wave_sum_u64(mine ? c0 : 0ull), s1 = wave_sum_u64(mine ? c1 : 0ull);
+    if (s1 & 0xFFFFFFFFull) {  // (wave-uniform) a yes row among them: its pieces
+#pragma unroll
+      for (int k = 0; k < NP; k++) {
+        const uint64_t sum = wave_sum_u64(mine && yes ? (uint64_t)pw[k] : 0ull);
+        if ((int)lane == leader && sum) atomicAdd(reinterpret_cast<unsigned long long *>(acc + k), (unsigned long long)sum);
+      }
+    }
+    if (s1 >> 32) {  // (wave-uniform) an open row among them
+#pragma unroll
+      for (int k = 0; k < NP; k++) {
+        const uint64_t sum = wave_sum_u64(mine && open ? (uint64_t)pw[k] : 0ull);
+        if ((int)lane == leader && sum) atomicAdd(reinterpret_cast<unsigned long long *>(acc + NP + k), (unsigned long long)sum);
+      }
+    }
+    if ((int)lane == leader) {
+      atomicAdd(reinterpret_cast<unsigned long long *>(acc + 2 * NP), (unsigned long long)s0);
+      if (s1) atomicAdd(reinterpret_cast<unsigned long long *>(acc + 2 * NP + 1), (unsigned long long)s1);
+    }
+    if (mine) pend = false;
+  }
+  if (pend) {  // more keys in this wavefront than turns: the lane adds for itself
+    uint64_t *acc = a.acc + (size_t)v * STRIDE;
+    if (yes || open) {
+#pragma unroll
+      for (int k = 0; k < NP; k++)
+        if (pw[k]) atomicAdd(reinterpret_cast<unsigned long long *>(acc + (yes ? 0 : NP) + k), (unsigned long long)pw[k]);
+      atomicAdd(reinterpret_cast<unsigned long long *>(acc + 2 * NP + 1), (unsigned long long)c1);
+    }
+    atomicAdd(reinterpret_cast<unsigned long long *>(acc + 2 * NP), (unsigned long long)c0);
+  }
+}
+__global__ void __launch_bounds__(RC_THREADS) round_change_records_kernel(round_change_args a) {
+  const uint32_t v = blockIdx.x * RC_THREADS + threadIdx.x;
+  if (v >= a.cap) return;
+  rcd::record rec;
+  if (v < a.words[0]) {
+    const int words = rcd::acc_words(a.n_pieces);
+    uint64_t *acc = a.acc + (size_t)v * words;
+    const uint32_t first = a.first_row[v];
+    rcd::key_record(rec, first, a.rows[first], acc, a.n_pieces, a.quorum);
+    for (int k = 0; k < words; k++) acc[k] = 0;
+  } else {
+    rcd::empty_record(rec);
+  }
+  a.out_rc[v] = rec;
+}
+__global__ void __launch_bounds__(64) round_change_select_kernel(round_change_args a) {
+  const uint32_t lane = threadIdx.x;
+  const uint32_t n_keys = a.words[0], filled = n_keys < a.cap ? n_keys : a.cap;
+  rcd::lane_state s = rcd::lane_init();
+  for (uint32_t i = lane; i < filled; i += 64u) rcd::record_step(s, a.out_rc[i], i, a.query);
+  const rcd::lane_state w = rcd::wave_state(s, lane);
+  if (lane == 0) {
+    rcd::answer ans;
+    rcd::make_answer(ans, w, n_keys, a.cap, a.words[2]);
+    *a.out_answer = ans;
   }
 }
 

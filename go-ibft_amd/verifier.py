@@ -57,7 +57,7 @@ EXPORTS = [
     "ibft_block_seals_submit_sets_raw", "ibft_recover_block_seals_submit_sets", "ibft_recover_block_seals_submit_sets_raw",
     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
-    "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire",
+    "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire", "ibft_decide_round_changes_wire",
     "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets", "ibft_verify_senders_wire_views",
     "ibft_verify_messages_wire_views", "ibft_wire_seal_stats",
 ]
@@ -77,7 +77,7 @@ OPTIONAL_EXPORTS = {"ibft_verify_block_seals", "ibft_block_seals_submit", "ibft_
                     "ibft_block_seals_submit_sets_raw", "ibft_recover_block_seals_submit_sets", "ibft_recover_block_seals_submit_sets_raw",
                     "ibft_sign_seals_ex", "ibft_sign_messages_wire", "ibft_sign_envelopes_wire", "ibft_judge_certificates_wire",
                     "ibft_cert_stats", "ibft_pipeline_stats_ex", "ibft_cache_form", "ibft_wire_stats",
-                    "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire",
+                    "ibft_set_proposers", "ibft_proposers_info", "ibft_decide_certificates_wire", "ibft_decide_round_changes_wire",
                     "ibft_set_height_sets", "ibft_height_sets_info", "ibft_verify_senders_wire_sets", "ibft_verify_senders_wire_views",
                     "ibft_verify_messages_wire_views", "ibft_wire_seal_stats"}
 SIGN_MESSAGE_MAX = 218   # IBFT_SIGN_MESSAGE_MAX: the longest message ibft_sign_messages_wire emits
@@ -121,6 +121,15 @@ WIRE_VIEW = np.dtype([("height", "<u8"), ("round", "<u8"), ("set", "<i4"), ("fir
                                  ("valid_rows", "<u4"), ("distinct_senders", "<u4"), ("has_quorum", "<u4"), ("shard_overlap", "<u4"),
                                  ("proposer_rows", "<u4"), ("reserved", "<u4")])])
 assert WIRE_VIEW.itemsize == 128
+# ibft_rc_query_t / ibft_rc_record_t / ibft_rc_answer_t (include/ibftgpu.h): ibft_decide_round_changes_wire
+RC_QUERY = np.dtype([("height", "<u8"), ("round", "<u8"), ("min_round", "<u8"), ("has_accepted_proposal", "<u4"), ("reserved", "<u4")])
+RC_RECORD = np.dtype([("height", "<u8"), ("round", "<u8"), ("first_row", "<u4"), ("rows", "<u4"), ("stored_rows", "<u4"), ("yes_rows", "<u4"),
+                      ("open_rows", "<u4"), ("has_quorum", "i1"), ("pad", "u1", 3), ("open_power_lo", "<u8"), ("open_power_hi", "<u8"),
+                      ("tally", WIRE_VIEW.fields["tally"][0]), ("reserved", "u1", 16)])
+RC_ANSWER = np.dtype([("extended", "i1"), ("pad", "u1", 3), ("flags", "<u4"), ("record", "<u4"), ("most_record", "<u4"), ("round", "<u8"),
+                      ("most_round", "<u8"), ("most_rows", "<u4"), ("records_of_height", "<u4"), ("unjudged_rows", "<u4"), ("reserved", "u1", 20)])
+assert (RC_QUERY.itemsize, RC_RECORD.itemsize, RC_ANSWER.itemsize) == (32, 128, 64)
+RC_VIEW_NONE, RC_VIEW_OVER, RC_OVER = -1, -2, 1   # IBFT_RC_VIEW_NONE, IBFT_RC_VIEW_OVER, IBFT_RC_OVER
 WIRE_VIEW_SEAL_RULE = 0      # IBFT_WIRE_VIEW_SEAL_RULE: pad[0] = 1 — the record's tally counts only rows whose committed seal verifies
 
 
@@ -287,6 +296,9 @@ def load_library() -> C.CDLL:
     if hasattr(L, "ibft_decide_certificates_wire"):
         L.ibft_decide_certificates_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                                     vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "ibft_decide_round_changes_wire"):
+        L.ibft_decide_round_changes_wire.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
     if hasattr(L, "ibft_set_proposers"):
         L.ibft_set_proposers.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_size_t]
     if hasattr(L, "ibft_proposers_info"):
@@ -367,6 +379,52 @@ def _judge_certificates_wire(L, handle, chk, wire, off, rows_cap: int, certs_cap
     if decide:
         return certs[:int(n_certs.value)], decisions[:int(n_certs.value)], k, out
     return certs[:int(n_certs.value)], k, out
+
+
+def rc_query(height: int, round_: int, has_accepted_proposal: bool = False, min_round: int = 0) -> np.ndarray:
+    """an ibft_rc_query_t: the node's view, whether it has accepted a proposal, GetMostRoundChangeMessages' min_round"""
+    q = np.zeros(1, dtype=RC_QUERY)
+    q["height"], q["round"], q["min_round"], q["has_accepted_proposal"] = int(height), int(round_), int(min_round), 1 if has_accepted_proposal else 0
+    return q
+
+
+def _decide_round_changes_wire(L, handle, chk, wire, off, query, rows_cap: int, certs_cap: int | None, rc_cap: int | None, per_row: bool):
+    """ibft_decide_round_changes_wire on one context → (certs, decisions, n_rows, per-row outputs or None, rc) with rc =
+    (rc_view[n], rc_stored[n] as bools, records[min(n_rc, rc_cap)] as RC_RECORD, n_rc, answer as an RC_ANSWER scalar or None)"""
+    name = "ibft_decide_round_changes_wire"
+    if not hasattr(L, name):
+        raise GpuUnavailable(f"this build of libibftgpu.so has no {name} — rebuild")
+    wb = _bytes_col(wire)
+    off = np.ascontiguousarray(off, dtype=np.uint32)
+    n = len(off) - 1
+    cap = int(rows_cap)
+    ccap = cap if certs_cap is None else int(certs_cap)
+    rcap = n if rc_cap is None else int(rc_cap)
+    certs = np.zeros(max(ccap, 1), dtype=CERT_VERDICT)
+    decisions = np.zeros(max(ccap, 1), dtype=CERT_DECISION)
+    nodes = rows = cls = ms = mh = mself = None
+    if per_row:
+        words = (cap + 63) // 64 or 1
+        nodes = np.zeros(max(cap, 1), dtype=CERT_NODE)
+        rows = np.zeros(max(cap, 1), dtype=WIRE_ROW)
+        cls = np.zeros(max(cap, 1), dtype=np.uint8)
+        ms, mh, mself = (np.zeros(words, dtype=np.uint64) for _ in range(3))
+    q = None if query is None else np.ascontiguousarray(query, dtype=RC_QUERY).reshape(1)
+    rc_view = np.zeros(max(n, 1), dtype=np.int32)
+    rc_stored = np.zeros((n + 63) // 64 or 1, dtype=np.uint64)
+    recs = np.zeros(max(min(rcap, n), 1), dtype=RC_RECORD)
+    answer = np.zeros(1, dtype=RC_ANSWER)
+    n_rows, n_certs, n_rc = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    chk(L.ibft_decide_round_changes_wire(handle, _p(wb), _p(off), n, cap, ccap, C.byref(n_rows), C.byref(n_certs), _p(certs), _p(decisions),
+                                         _p(nodes), _p(rows), _p(cls), _p(ms), _p(mh), _p(mself), _p(q), _p(rc_view), _p(rc_stored), _p(recs),
+                                         rcap, C.byref(n_rc), _p(answer)), name)
+    k = int(n_rows.value)
+    out = None
+    if per_row:
+        out = (nodes[:k], rows[:k], cls[:k], mask_to_bool(ms, k), mask_to_bool(mh, k), mask_to_bool(mself, k))
+    filled = min(int(n_rc.value), rcap, n)
+    rc = (rc_view[:n], mask_to_bool(rc_stored, n), recs[:filled], int(n_rc.value), None if q is None else answer[0])
+    return certs[:int(n_certs.value)], decisions[:int(n_certs.value)], k, out, rc
 
 
 def _set_proposers(L, handle, chk, height: int, first_round: int, addrs) -> None:
@@ -1119,6 +1177,15 @@ class BatchVerifier:
         return _judge_certificates_wire(self._L, self._h, self._chk, wire, off, int(rows_cap if rows_cap is not None else self.max_rows),
                                         certs_cap, per_row, decide=True)
 
+    def decide_round_changes_wire(self, wire, off, query=None, rows_cap: int | None = None, certs_cap: int | None = None,
+                                  rc_cap: int | None = None, per_row: bool = False):
+        """decide_certificates_wire, and what handleRoundChangeMessage does with its answers (ibft_decide_round_changes_wire): one
+        quorum record per (height, round) of the level-0 ROUND_CHANGE rows and, for `query` (rc_query(...)), GetExtendedRCC /
+        GetMostRoundChangeMessages over them → (certs, decisions, n_rows, per_row outputs, (rc_view int32[n], rc_stored bool[n],
+        records[RC_RECORD], n_rc, answer[RC_ANSWER] or None)).  rc_cap None: n, which always fits."""
+        return _decide_round_changes_wire(self._L, self._h, self._chk, wire, off, query, int(rows_cap if rows_cap is not None else self.max_rows),
+                                          certs_cap, rc_cap, per_row)
+
     def cert_stats(self):
         """ibft_cert_stats, of the last verify_ / judge_certificates_wire call: (rows of the tree, rows judged — no pre-flag —,
         rows given to the verdict kernels, rows the dedup table could not place).  FLAG_CERT_DEDUP off: judged == given, 0."""
@@ -1522,6 +1589,12 @@ class DeviceGroup:
         """BatchVerifier.decide_certificates_wire on the group's FIRST context (no sharded form, as for the judge call)"""
         return _judge_certificates_wire(self._L, self._L.ibft_group_ctx(self._g, 0), self._chk, wire, off, int(rows_cap), certs_cap, per_row,
                                         decide=True)
+
+    def decide_round_changes_wire(self, wire, off, query=None, rows_cap: int = 65536, certs_cap: int | None = None, rc_cap: int | None = None,
+                                  per_row: bool = False):
+        """BatchVerifier.decide_round_changes_wire on the group's FIRST context (no sharded form, as for the decide call)"""
+        return _decide_round_changes_wire(self._L, self._L.ibft_group_ctx(self._g, 0), self._chk, wire, off, query, int(rows_cap), certs_cap,
+                                          rc_cap, per_row)
 
     def verify_messages(self, payload: bytes, off, msg_sig65, from20, hash32, hash_len, seal65=None, sender_pre=None,
                         valid_pre=None, raw: bytes | None = None, round_: int = 0, digest32: bytes | None = None,

@@ -1272,6 +1272,98 @@ int ibft_decide_certificates_wire(ibft_ctx *ctx, const uint8_t *wire, const uint
                                   uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
                                   uint64_t *out_self_mask);
 
+/* ---- round changes: one quorum record per (height, round), GetExtendedRCC on the device ---------------------------
+ * What handleRoundChangeMessage does with the per-message answers above (core/ibft.go:470-512, messages/messages.go:202-245):
+ * per round it takes the ROUND_CHANGE messages the store still holds — one per sender, a later one replacing an earlier one —,
+ * keeps those whose closure holds, asks HasQuorum over their senders and returns the highest round ≥ 1 that has one.
+ * ibft_decide_round_changes_wire is ibft_decide_certificates_wire with one more input, `query`, and four more outputs: every
+ * output the decide call has is byte for byte the decide call's for the same input, errors are the decide call's in its
+ * order.  What a refused call writes is what the decide call writes: one refused among the argument checks in front
+ * (IBFT_E_INVAL) writes nothing at all; one refused behind them (IBFT_E_TOOBIG, IBFT_E_NOVALSET) has zeroed the three counts
+ * *out_n_rows, *out_n_certs and *out_n_rc, as the decide call zeroes its two once its arguments stand, and writes nothing else.
+ *
+ *   takes part    a level-0 row that is judged (class 0, status OK, with a view), of type ROUND_CHANGE with a ROUND_CHANGE
+ *                 payload, with a 20-byte From and its sender bit (IBFT_CERT_BIT_SENDER) set: the message IBFT.AddMessage would
+ *                 have stored.  Every other level-0 row — a PREPREPARE root, a row the tree hands to the host, a row whose
+ *                 signature does not verify — has out_rc_view = IBFT_RC_VIEW_NONE (−1), takes no part and supersedes nothing.
+ *   key           (height, round) of a row that takes part.  Records are the keys ordered by their lowest such row, ascending.
+ *   out_rc_view   n entries: the row's record index, or IBFT_RC_VIEW_OVER (−2) for a key beyond rc_cap — such rows still
+ *                 supersede.  *out_n_rc = the number of keys, which may exceed rc_cap.
+ *   stored        out_rc_stored, ⌈n/64⌉ words, bits past n zero: bit i is set iff row i takes part and no row j > i that takes
+ *                 part has the same key and the same From — what a Messages store fed the batch in row order still holds.
+ *   record        out_rc[v], v < min(*out_n_rc, rc_cap, n); entries from there up to min(rc_cap, n) are zeroed:
+ *                   height, round, first_row (the key's lowest row), rows (that take part), stored_rows;
+ *                   yes_rows / open_rows   stored rows whose decision's round_change is 1 / −1;
+ *                   tally                  with S_yes the From column of the stored rows with round_change == 1, in row order:
+ *                                          field for field what ibft_tally(S_yes, all-ones) returns on this context (u64 and
+ *                                          u256 sets, cold and warm);
+ *                   open_power_lo / _hi    the power ibft_tally(S_open, all-ones) reports for the stored rows with
+ *                                          round_change == −1 (low 128 bits);
+ *                   has_quorum             1 when tally.has_quorum; 0 when the powers of S_yes and S_open TOGETHER stay below
+ *                                          the quorum (compared exactly, in full width); −1 otherwise.  Undecided never hides
+ *                                          a false and never claims a true.
+ *   answer        for `query` = {height, round: the node's view; has_accepted_proposal: 0 or 1; min_round; reserved: 0}; query
+ *                 or out_answer NULL: no answer is computed.  R = the records of query.height with round ≥ 1 (GetExtendedRCC's
+ *                 accumulator highestRound starts at 0, so round 0 never wins), without the record of query.round when
+ *                 has_accepted_proposal is set; r1 = the highest round of R with has_quorum == 1, ru = the highest with −1.
+ *                   extended            1: r1 exists and no ru lies above it; −1: an ru above r1, or an ru and no r1; else 0.
+ *                   record, round       those of r1, or IBFT_CERT_NO_RECORD and 0.  The RoundChangeCertificate's messages are
+ *                                       the stored rows of `record` whose round_change is 1.
+ *                   most_record, most_round, most_rows   GetMostRoundChangeMessages(min_round, height): the record of
+ *                                       query.height with round ≥ max(min_round, 1) that has the most stored_rows, the LOWEST
+ *                                       round among equals (the reference's answer among equals depends on Go's map order,
+ *                                       and it answers nothing where round 0 holds the most: its callers ask from round 1
+ *                                       up); IBFT_CERT_NO_RECORD, 0, 0 when there is none.
+ *                   records_of_height   records of query.height.
+ *                   unjudged_rows       level-0 rows of class != 0: the tree left them to the host, the caller still owes
+ *                                       them the host route.
+ *                   flags               IBFT_RC_OVER when *out_n_rc > rc_cap: the answer covers the records that fit.
+ *                                       rc_cap = n always fits.
+ *
+ * ONE SET, ONE TABLE.  Like every certificate call this one knows one validator set and one proposer table: keys of other
+ * heights are formed and tallied under that set, and where their round_change is −1 for want of a table they show it in
+ * open_rows.  Every output is a pure function of the batch, the set, the table, the query and rc_cap: nothing depends on thread
+ * order, table size or salt.  IBFT_FLAG_CERT_DEDUP and both settings of IBFT_CERT_OVERLAP change no byte of the new outputs.
+ *
+ * out_rc_view, out_rc_stored and out_answer may be NULL.  IBFT_E_INVAL, with the argument checks in front: a NULL out_n_rc; with
+ * n > 0 a NULL out_rc or rc_cap == 0; a query with has_accepted_proposal > 1 or reserved != 0.  An rc_cap above n behaves as n.
+ * IBFT_ROUND_CHANGE_SLOTS=<n> (tests only, read at ibft_ctx_create) lowers the slot count of the call's tables, never below the
+ * first power of two above n.  No new ibft_version(): a build without the symbol simply lacks it.                     */
+#define IBFT_RC_VIEW_NONE (-1)
+#define IBFT_RC_VIEW_OVER (-2)
+#define IBFT_RC_OVER 1u
+typedef struct {
+  uint64_t height, round; /* the node's view */
+  uint64_t min_round;     /* GetMostRoundChangeMessages */
+  uint32_t has_accepted_proposal; /* 0 or 1 */
+  uint32_t reserved;      /* zero */
+} ibft_rc_query_t; /* 32 bytes */
+typedef struct {
+  uint64_t height, round;
+  uint32_t first_row, rows, stored_rows, yes_rows, open_rows;
+  int8_t has_quorum; /* −1 undecided here, 0 false, 1 true */
+  uint8_t pad[3];
+  uint64_t open_power_lo, open_power_hi;
+  ibft_tally_t tally;
+  uint8_t reserved[16]; /* zero */
+} ibft_rc_record_t; /* 128 bytes */
+typedef struct {
+  int8_t extended; /* −1 undecided here, 0 false, 1 true */
+  uint8_t pad[3];
+  uint32_t flags; /* IBFT_RC_OVER */
+  uint32_t record, most_record;
+  uint64_t round, most_round;
+  uint32_t most_rows, records_of_height, unjudged_rows;
+  uint8_t reserved[20]; /* zero */
+} ibft_rc_answer_t; /* 64 bytes */
+int ibft_decide_round_changes_wire(ibft_ctx *ctx, const uint8_t *wire, const uint32_t *off, size_t n, size_t rows_cap,
+                                   size_t certs_cap, size_t *out_n_rows, size_t *out_n_certs, ibft_cert_verdict_t *out_cert,
+                                   ibft_cert_decision_t *out_decision, ibft_cert_node_t *out_nodes, ibft_wire_row_t *out_rows,
+                                   uint8_t *out_class, uint64_t *out_sender_mask, uint64_t *out_hash_mask,
+                                   uint64_t *out_self_mask, const ibft_rc_query_t *query, int32_t *out_rc_view,
+                                   uint64_t *out_rc_stored, ibft_rc_record_t *out_rc, size_t rc_cap, size_t *out_n_rc,
+                                   ibft_rc_answer_t *out_answer);
+
 /* ---- certificates: identical nested messages (IBFT_FLAG_CERT_DEDUP) ----------------------------------------------
  * After a prepared round every ROUND_CHANGE carries a PreparedCertificate built from the same few messages, each signed once
  * and byte-identical wherever it is nested: O(N²) rows, O(N) distinct signatures.  With the flag on, the signature work of

@@ -1086,6 +1086,111 @@ func (c *Ctx) DecideCertificatesWire(wire []byte, off []uint32, rowsCap, certsCa
 	return certs[:int(nCerts)], decisions[:int(nCerts)], int(nRows), c.check(rc)
 }
 
+// RCQuery mirrors ibft_rc_query_t: the node's view, whether it has accepted a proposal (0 or 1), and the minRound of
+// GetMostRoundChangeMessages.
+type RCQuery struct {
+	Height, Round       uint64
+	MinRound            uint64
+	HasAcceptedProposal uint32
+	Reserved            uint32
+}
+
+// RCTally is ibft_tally_t as it lies inside an RCRecord; Tally() gives it the shape every other call returns.
+type RCTally struct {
+	QuorumLo, QuorumHi, PowerLo, PowerHi                                        uint64
+	ValidRows, DistinctSenders, HasQuorum, ShardOverlap, ProposerRows, Reserved uint32
+}
+
+// Tally converts the record's tally.
+func (t RCTally) Tally() Tally {
+	return Tally{t.QuorumLo, t.QuorumHi, t.PowerLo, t.PowerHi, t.ValidRows, t.DistinctSenders, t.HasQuorum != 0, t.ShardOverlap, t.ProposerRows}
+}
+
+// RCRecord mirrors ibft_rc_record_t: one (height, round) that has a stored ROUND_CHANGE message in the batch.  Tally is HasQuorum
+// over the stored rows whose closure holds (round_change 1), OpenPower the power of those whose closure is undecided here (-1);
+// HasQuorum is 1, 0 or -1: undecided where the open rows could still change the answer.
+type RCRecord struct {
+	Height, Round                                 uint64
+	FirstRow, Rows, StoredRows, YesRows, OpenRows uint32
+	HasQuorum                                     int8
+	Pad                                           [3]byte
+	OpenPowerLo, OpenPowerHi                      uint64
+	Tally                                         RCTally
+	Reserved                                      [16]byte
+}
+
+// RCAnswer mirrors ibft_rc_answer_t: GetExtendedRCC (Extended 1: Record / Round name the winning round, 0: none, -1: undecided
+// here) and GetMostRoundChangeMessages (MostRecord, MostRound, MostRows) for the query, the records of its height, the level-0
+// rows the tree left to the host, and RCOver in Flags when the batch had more keys than rcCap.
+type RCAnswer struct {
+	Extended                                int8
+	Pad                                     [3]byte
+	Flags                                   uint32
+	Record, MostRecord                      uint32
+	Round, MostRound                        uint64
+	MostRows, RecordsOfHeight, UnjudgedRows uint32
+	Reserved                                [20]byte
+}
+
+const (
+	_ = unsafe.Sizeof(RCQuery{}) - 32
+	_ = 32 - unsafe.Sizeof(RCQuery{})
+	_ = unsafe.Sizeof(RCRecord{}) - 128
+	_ = 128 - unsafe.Sizeof(RCRecord{})
+	_ = unsafe.Sizeof(RCAnswer{}) - 64
+	_ = 64 - unsafe.Sizeof(RCAnswer{})
+)
+
+const (
+	RCViewNone = int32(C.IBFT_RC_VIEW_NONE)
+	RCViewOver = int32(C.IBFT_RC_VIEW_OVER)
+	RCOver     = uint32(C.IBFT_RC_OVER)
+)
+
+// RoundChangesResult is what DecideRoundChangesWire adds to DecideCertificatesWire: the record of every level-0 row (RCViewNone:
+// it takes no part, RCViewOver: its key did not fit rcCap), the stored bits, the records that fit, the number of keys, and the
+// answer (nil without a query).
+type RoundChangesResult struct {
+	View    []int32
+	Stored  []uint64
+	Records []RCRecord
+	Keys    int
+	Answer  *RCAnswer
+}
+
+// DecideRoundChangesWire = DecideCertificatesWire, and what handleRoundChangeMessage does with its per-message answers
+// (ibft_decide_round_changes_wire; core/ibft.go:470-512): per (height, round) the ROUND_CHANGE messages a store fed the batch in
+// row order still holds, those whose closure holds, HasQuorum over their senders, and for the query the highest round >= 1 that
+// has one.  The RoundChangeCertificate's messages are the stored rows of Answer.Record whose decision's RoundChange is 1.
+func (c *Ctx) DecideRoundChangesWire(wire []byte, off []uint32, rowsCap, certsCap, rcCap int, query *RCQuery) (certs []CertVerdict, decisions []CertDecision, rows int, rc RoundChangesResult, err error) {
+	n := len(off) - 1
+	certs = make([]CertVerdict, certsCap+1)
+	decisions = make([]CertDecision, certsCap+1)
+	rc.View = make([]int32, n+1)
+	rc.Stored = make([]uint64, (n+63)/64+1)
+	recs := make([]RCRecord, rcCap+1)
+	var answer RCAnswer
+	var nRows, nCerts, nRC C.size_t
+	code := C.ibft_decide_round_changes_wire(c.h, ptr8(wire), (*C.uint32_t)(unsafe.Pointer(&off[0])), C.size_t(n), C.size_t(rowsCap),
+		C.size_t(certsCap), &nRows, &nCerts, (*C.ibft_cert_verdict_t)(unsafe.Pointer(&certs[0])),
+		(*C.ibft_cert_decision_t)(unsafe.Pointer(&decisions[0])), nil, nil, nil, nil, nil, nil,
+		(*C.ibft_rc_query_t)(unsafe.Pointer(query)), (*C.int32_t)(unsafe.Pointer(&rc.View[0])), (*C.uint64_t)(unsafe.Pointer(&rc.Stored[0])),
+		(*C.ibft_rc_record_t)(unsafe.Pointer(&recs[0])), C.size_t(rcCap), &nRC, (*C.ibft_rc_answer_t)(unsafe.Pointer(&answer)))
+	rc.View, rc.Stored, rc.Keys = rc.View[:n], rc.Stored[:(n+63)/64], int(nRC)
+	filled := rc.Keys
+	if filled > rcCap {
+		filled = rcCap
+	}
+	if filled > n {
+		filled = n
+	}
+	rc.Records = recs[:filled]
+	if query != nil {
+		rc.Answer = &answer
+	}
+	return certs[:int(nCerts)], decisions[:int(nCerts)], int(nRows), rc, c.check(code)
+}
+
 // WireStats reports on the context's last flat wire call (ibft_wire_stats): its rows, the rows judged through the recode class
 // (FlagWireRecode; 0 without it) and the rows left WireNeedsHost.  A diagnostic: the library copies the parse results to count.
 func (c *Ctx) WireStats() (rows, recoded, needsHost uint32, err error) {
